@@ -494,6 +494,49 @@ def fleet_cpu_baseline(entry, rank, world, dist, core):
                       "map, run concurrently); value = sum of their rates.  Each: %s" % (world, e0["sample"])}
 
 
+DUMP_BYTES_MAX = 64 << 20  # --dump-outputs: cap on all files of all ranks together
+DUMP_VOXELS = 1 << 20      # voxel sample of the map buffers (fixed seed: the same voxels in every run)
+
+
+def dump_outputs(cyc, out_dir, suffix="", budget=DUMP_BYTES_MAX):
+    """--dump-outputs: what the timed path computed in its last step, as a caller of it receives it -- the map's
+    occupancy log-odds / inflated occupancy / distance buffers on a fixed voxel sample, the cells of every frontier
+    list and the cost + gradient of every B-spline candidate -- one DIR/<name>.npy each (float32 / float64), `budget`
+    bytes at most: the voxel sample takes up to half of it, the frontier cells what the rest leaves (a fixed-seed sample
+    of every list, in proportion to its length, when they do not fit)."""
+    cyc.finish()
+    files = {}
+    cost, grad = cyc.dev_problem.download()
+    files["bspline_cost"] = cost.astype(np.float64)
+    files["bspline_grad"] = grad.astype(np.float64)
+    nvox = cyc.map.N
+    n_s = min(nvox, DUMP_VOXELS, (budget // 2) // (8 + 8 + 4 + 8))  # index, occupancy, inflate, distance per voxel
+    idx = np.sort(np.random.default_rng(20240607).choice(nvox, size=n_s, replace=False)) if n_s < nvox else np.arange(nvox)
+    files["map_sample_voxel_index"] = idx.astype(np.float64)
+    for key, dt in (("occupancy", np.float64), ("inflate", np.float32), ("distance", np.float64)):
+        h = cyc.map.syncHost(**{key: True})[key]  # (one full-size host mirror at a time)
+        files["map_" + key] = h[idx].astype(dt)
+        del h
+    lists = []
+    for which, name in ((0, "tmp_frontiers"), (1, "frontiers"), (2, "dormant_frontiers")):
+        cl = cyc.ff.clusters(which)
+        if cl:
+            files["frontier_%s_sizes" % name] = np.array([len(c) for c in cl], dtype=np.float64)
+            lists.append((which, name, np.concatenate(cl).astype(np.float64)))
+    room = (budget - sum(a.nbytes for a in files.values())) // 8  # float64 cells that still fit
+    n_cells = sum(len(c) for _, _, c in lists)
+    for which, name, cells in lists:
+        if n_cells > room:
+            keep = len(cells) * max(room, 0) // n_cells
+            cells = cells[np.sort(np.random.default_rng(20240608 + which).choice(len(cells), keep, replace=False))]
+        files["frontier_%s_cells" % name] = cells
+    total = sum(a.nbytes for a in files.values())
+    assert total <= budget, "--dump-outputs: %d bytes exceed the %d-byte budget" % (total, budget)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+
+
 def timed_fleet_run(step, finish, steps, dist=None, device_sync=None, device="cuda"):
     """Time exactly `steps` steps, bracketed by barrier + device sync on both sides; returns the MAX
     elapsed seconds over ranks.  No data-path collective: ranks are independent maps."""
@@ -528,8 +571,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None,
-                    help="timed cycles (default 200 for the full-box workloads: 20 cycles are 4 ms, too short for "
-                         "a steady clock; 20 for the streaming ones, one distinct depth frame each)")
+                    help="timed cycles per timed region (default 200 for the full-box workloads: 20 cycles are 4 ms, "
+                         "too short for a steady clock; 20 for the streaming ones, one distinct depth frame each)")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="full-box workloads: timed regions of --steps cycles each, the median one reported (default 9 "
+                         "when --steps < 100, else 1; --regions 1 times exactly --steps cycles).  Streaming: always 1")
     ap.add_argument("--warmup", type=int, default=None, help="untimed cycles first (default 20 / 3)")
     ap.add_argument("--workload", default="G400", choices=sorted(WORKLOADS))
     ap.add_argument("--candidates", type=int, default=64,
@@ -545,7 +591,12 @@ def main():
                          "(default), 0 packed plain, 1 far-field, 2 32-bit plain")
     ap.add_argument("--serial-stages", action="store_true",
                     help="diagnostic: run the frontier scan after the ESDF chain instead of beside it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy "
+                         "(map buffers on a fixed voxel sample, frontier cells, B-spline cost / gradient; <= 64 MB)")
     args = ap.parse_args()
+    if args.regions is not None and args.regions < 1:
+        ap.error("--regions must be at least 1")
     stream_wl = args.workload.endswith("S")
     if args.steps is None:
         args.steps = 20 if stream_wl else 200
@@ -711,12 +762,14 @@ def main():
         # A K-cycle region of 20 cycles is 2 ms: one disturbed cycle moves it by 5 %.  Short regions are therefore
         # repeated and the MEDIAN region is the one reported: every repetition times exactly K cycles,
         # bracketed like the contract says; `region_ms` lists them all.
-        reps = 9 if args.steps < 100 else 1
+        reps = args.regions if args.regions is not None else (9 if args.steps < 100 else 1)
         regions = [timed_fleet_run(lambda: cyc.run_native(args.steps, args.serial_stages), cyc.finish, 1, dist,
                                    torch.cuda.synchronize) for _ in range(reps)]
         elapsed = float(np.median(regions))
     n_launch, dom_total_ms = cyc.map.profileGet(stages[dominant])
     host_issue = None if streaming else cyc.host_profile()  # (of the timed run)
+    if args.dump_outputs:  # before anything else runs on this map: the state the last timed step left
+        dump_outputs(cyc, args.dump_outputs, "" if world == 1 else "_rank%d" % rank, DUMP_BYTES_MAX // world)
     frame_source = None
     if streaming:
         # The same K frames handed over from host memory instead, each source from an IDENTICAL map state: a fresh map
@@ -825,8 +878,11 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": 1e3 * elapsed / args.steps,
-            "timed_regions": ({"repetitions": len(regions), "reported": "median", "region_ms": [round(1e3 * r, 4) for r in regions]}
-                              if not streaming else {"repetitions": 1, "reported": "the one region"}),
+            "timed_regions": ({"repetitions": len(regions), "reported": "median", "steps_per_region": args.steps,
+                               "timed_steps_total": len(regions) * args.steps,
+                               "region_ms": [round(1e3 * r, 4) for r in regions]}
+                              if not streaming else {"repetitions": 1, "reported": "the one region",
+                                                     "steps_per_region": args.steps, "timed_steps_total": args.steps}),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,

@@ -44,10 +44,10 @@ extern "C" {
 /* Process-level set-up: hardware queues.  A map owns one HIP stream, a finder two, every busy query thread one; the HIP
  * runtime deals a process's streams onto GPU_MAX_HW_QUEUES hardware queues (4 by default) and streams that share one
  * time-slice (INTEGRATION.md "streams and queues").  The runtime latches the variable at its first call, so the robust
- * way is to export GPU_MAX_HW_QUEUES=16 where the process is launched.  fuelmi_init() is the explicit in-process
+ * way is to export GPU_MAX_HW_QUEUES where the process is launched.  fuelmi_init() is the explicit in-process
  * alternative (rounds 4-5 did this from a load-time constructor; that is now opt-in, FUELMI_SET_HW_QUEUES=1): called
  * BEFORE the process's first HIP call and before threads that touch the environment exist, it puts
- * GPU_MAX_HW_QUEUES=<hw_queues, 16 if <= 0> into the environment unless a value is already there.  Idempotent; always
+ * GPU_MAX_HW_QUEUES=<hw_queues capped at 2, 2 if <= 0> into the environment unless a value is already there.  Idempotent; always
  * returns FUELMI_OK and reports through fuelmi_hw_queues_state() what happened -- including FUELMI_HWQ_LATE when the HIP
  * runtime was already up (it is detected through the runtime's open /dev/kfd handle; one line on stderr unless
  * FUELMI_QUIET is set): the streams then share the runtime's default of 4 queues.  fuelmi_map_create says so once on

@@ -77,8 +77,8 @@ fi
 timeout 300 python bench.py --steps 20 --warmup 5 > $O/bench_G400_driver_cmdline.json 2>/dev/null
 { echo "# FUELMI_HOST_TIMING=1 python bench.py --no-cpu-baseline (host microseconds inside fuelmi_frontier_search_begin / _end per search), commit $FUELMI_COMMIT"
   FUELMI_HOST_TIMING=1 python bench.py --no-cpu-baseline 2>&1 >/dev/null | grep host-timing | tail -2
-  echo "# hardware queues: scripts/r5_hwq.py at the library's fuelmi_init() default, then with the runtime's (GPU_MAX_HW_QUEUES=4)"
-  python scripts/r5_hwq.py 2>&1 | tail -5; GPU_MAX_HW_QUEUES=4 python scripts/r5_hwq.py 2>&1 | tail -5; } > $O/host_timing.txt 2>&1
+  echo "# hardware queues: scripts/r5_hwq.py at the library's fuelmi_init() default (2), then with one queue (GPU_MAX_HW_QUEUES=1)"
+  python scripts/r5_hwq.py 2>&1 | tail -5; GPU_MAX_HW_QUEUES=1 python scripts/r5_hwq.py 2>&1 | tail -5; } > $O/host_timing.txt 2>&1
 { echo "# FUELMI_FR_TIMING=1 python bench.py --workload W --no-cpu-baseline --steps 5 --warmup 2 --serial-stages: in-kernel phase stamps of the frontier chain (last search), commit $FUELMI_COMMIT"
   for WL in G400 G800 G800S; do FUELMI_FR_TIMING=1 python bench.py --workload $WL --no-cpu-baseline --steps 5 --warmup 2 --serial-stages 2>&1 | grep "fr-timing" | tail -6 | grep -v "entry avg" | cut -c1-330 | sed "s/^/$WL /"; done; } > $O/frontier_phase_stamps.txt 2>&1
 timeout 300 python scripts/bench_next.py > $O/next_rows.json 2>/dev/null

@@ -1,7 +1,8 @@
 """Regenerates tests/golden/sdf_map_layout.txt: sizeof / offsetof lines of MapParam, MapData and SDFMap printed by
 tests/golden/sdf_map_layout_probe.cpp compiled against the REFERENCE's plan_env/sdf_map.h (this container only:
 needs /root/reference).  tests/test_abi_cpu.py::test_sdf_map_header_layout_is_the_references compares the facade's
-header with this file and, where the reference checkout is present, the reference with it -- read-only."""
+header with this file and, where oracle/_ref was built (oracle/ref_build/Makefile runs the same probe on the
+reference header), the reference's layout with it -- read-only."""
 import os
 import subprocess
 import sys
