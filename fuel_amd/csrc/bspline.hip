@@ -1119,11 +1119,7 @@ extern "C" int fuelmi_bspline_dev_eval_pinned(fuelmi_bspline_dev* b, int slot) {
 extern "C" int fuelmi_bspline_dev_collect(fuelmi_bspline_dev* b, int slot, double* cost, double* grad) {
   ARGCHK(b && (slot == 0 || slot == 1) && cost && grad && b->pin_out[slot]);
   HIPCHK(hipSetDevice(b->map->device));
-  for (;;) {
-    const hipError_t q = hipEventQuery(b->ev_out[slot]);
-    if (q == hipSuccess) break;
-    if (q != hipErrorNotReady) HIPCHK(q);
-  }
+  HIPCHK(event_poll(b->ev_out[slot]));
   const size_t C = (size_t)b->a.C, n = (size_t)b->a.nvar;
   memcpy(cost, b->pin_out[slot], C * sizeof(double));
   memcpy(grad, b->pin_out[slot] + C, C * n * sizeof(double));

@@ -3269,15 +3269,25 @@ static void remove_changed_end(fuelmi_frontier* f) {
   f->pend_rm.clear();
 }
 
+// passes p0 .. p1 - 1 of the radix multisplit on A (the kernels stride over however many 2048-cell chunks there are)
+static void enqueue_ms_passes(fuelmi_frontier* f, const FArgs& A, int p0, int p1) {
+  for (int p = p0; p < p1; ++p) {
+    k_ms_hist<<<256, 256, 0, f->stream>>>(A, p);
+    FDBG("k_ms_hist");
+    k_ms_scan<<<1, 1024, 0, f->stream>>>(A, p);
+    FDBG("k_ms_scan");
+    k_ms_scatter<<<256, 256, 0, f->stream>>>(A, p);
+    FDBG("k_ms_scatter");
+  }
+}
+
 int frontier_regroup(fuelmi_frontier* f, const FArgs& F2, int npass) {
   const Geo& g = f->map->g;
-  for (int p = 0; p < npass; ++p) {
-    k_ms_hist<<<256, 256, 0, f->stream>>>(F2, p);
-    k_ms_scan<<<1, 1024, 0, f->stream>>>(F2, p);
-    k_ms_scatter<<<256, 256, 0, f->stream>>>(F2, p);
-  }
+  enqueue_ms_passes(f, F2, 0, npass);
   k_ms_info<<<256, 256, 0, f->stream>>>(g, F2);
+  FDBG("k_ms_info");
   k_pack<<<1, 256, 0, f->stream>>>(F2);
+  FDBG("k_pack");
   HIPCHK(hipGetLastError());
   return FUELMI_OK;
 }
@@ -3314,20 +3324,7 @@ static int frontier_enqueue_chain(fuelmi_frontier* f, int npass) {
   // ---- grouping + cluster info, still without touching the host ----
   k_rank_kept<<<16, 256, 0, f->stream>>>(F);
   FDBG("k_rank_kept");
-  for (int p = 0; p < npass; ++p) {
-    k_ms_hist<<<f->nb_launch, 256, 0, f->stream>>>(F, p);
-    FDBG("k_ms_hist");
-    k_ms_scan<<<1, 1024, 0, f->stream>>>(F, p);
-    FDBG("k_ms_scan");
-    k_ms_scatter<<<f->nb_launch, 256, 0, f->stream>>>(F, p);
-    FDBG("k_ms_scatter");
-  }
-  k_ms_info<<<256, 256, 0, f->stream>>>(g, F);
-  FDBG("k_ms_info");
-  k_pack<<<1, 256, 0, f->stream>>>(F);
-  FDBG("k_pack");
-  HIPCHK(hipGetLastError());
-  return FUELMI_OK;
+  return frontier_regroup(f, F, npass);
 }
 
 // FUELMI_HOST_TIMING: where the host's time inside _search_begin / _search_end goes (mean microseconds per call, printed
@@ -3359,16 +3356,30 @@ struct HostTiming {
 };
 static HostTiming g_ht;
 
+// tiles of menu entry mk over a qx x qy rectangle of z-lines
+static int menu_tiles(int qx, int qy, int mk) {
+  return ((qx + kFastMenu[mk][0] - 1) / kFastMenu[mk][0]) * ((qy + kFastMenu[mk][1] - 1) / kFastMenu[mk][1]);
+}
+// launch grid of the tile kernels: menu entry mk's tile over the largest rectangle a search can cover
+static int fast_launch_tiles(const FArgs& F, int mk) {
+  return menu_tiles(F.qbox.hi[0] - F.qbox.lo[0] + 2, F.qbox.hi[1] - F.qbox.lo[1] + 2, mk);
+}
+// the search's fast tiles: menu entry mk's tile over hv's rectangle px0..px1 x py0..py1
+static void set_fast_tiles(FVar& hv, int mk) {
+  const int qx = hv.px1 - hv.px0 + 1, qy = hv.py1 - hv.py0 + 1;
+  hv.ftx = kFastMenu[mk][0], hv.fty = kFastMenu[mk][1];
+  hv.ntx_f = std::max(0, (qx + hv.ftx - 1) / hv.ftx);
+  hv.nty_f = std::max(0, (qy + hv.fty - 1) / hv.fty);
+  hv.ntiles_f = hv.ntx_f * hv.nty_f;
+}
+
 // the fast chain: four direct launches (512-lane tile workgroups: 256 lanes measured 4-11 % slower in round 3 and again
 // in round 6, profiles/r06_frontier_threads_prio_sweep.txt); falls back to the legacy one through counts[2] == 2
 static int frontier_enqueue_fast(fuelmi_frontier* f) {
   const Geo& g = f->map->g;
   FArgs& F = f->F;
-  // launch grid of the tile kernels: the chosen tile over the largest rectangle a search can cover
-  const int qx = F.qbox.hi[0] - F.qbox.lo[0] + 2, qy = F.qbox.hi[1] - F.qbox.lo[1] + 2;
   const int mk = f->fast_menu;
-  const int ftx = kFastMenu[mk][0], fty = kFastMenu[mk][1];
-  const int tiles = ((qx + ftx - 1) / ftx) * ((qy + fty - 1) / fty);
+  const int tiles = fast_launch_tiles(F, mk);
   if (f->tl_ev) HIPCHK(hipEventRecord(f->tl_ev[0], f->stream));
   k_tile_ccl<512><<<tiles, 512, f->tile_lds[mk], f->stream>>>(g, F, *f->h_var);
   FDBG("k_tile_ccl");
@@ -3386,13 +3397,12 @@ static int frontier_enqueue_fast(fuelmi_frontier* f) {
   }
   if (f->tl_ev) HIPCHK(hipEventRecord(f->tl_ev[1], f->stream));
   g_ht.lap(5);
-  // round 6: the last workgroup of k_tile_cross resolves searches of up to 1 024 tile roots (FUELMI_FR_FUSE=0: never --
-  // the A/B switch of profiles/r06_cross_resolve_fusion_ab.txt)
-  static const bool fuse = !(getenv("FUELMI_FR_FUSE") && atoi(getenv("FUELMI_FR_FUSE")) == 0);
+  // round 6: the last workgroup of k_tile_cross resolves searches of up to 1 024 tile roots (measured against k_resolve
+  // as a launch of its own: profiles/r06_cross_resolve_fusion_ab.txt)
   {
     // (a finder whose last search had more tile roots than the launch's LDS holds -- the 800^2 x 200 map's full box: 2 465 --
     // does not try again for the next 16 searches: the attempt costs every workgroup a barrier and two atomics, -5 % there)
-    bool fuse_now = fuse && f->h_var->ntiles_f > 0;  // (no tile, no last workgroup: k_resolve publishes the empty result)
+    bool fuse_now = f->h_var->ntiles_f > 0;  // (no tile, no last workgroup: k_resolve publishes the empty result)
     if (fuse_now && f->fuse_skip > 0) --f->fuse_skip, fuse_now = false;
     f->fuse_tried = fuse_now;
     const size_t lds_x = fuse_now ? std::max(f->cross_lds[mk], resolve_lds_bytes(1024)) : f->cross_lds[mk];
@@ -3588,7 +3598,7 @@ extern "C" int fuelmi_frontier_search_begin(fuelmi_frontier* f) {
     const int qx = p1[0] - p0[0] + 1, qy = p1[1] - p0[1] + 1;
     int pick = 3;
     for (int k = 0; k < 4; ++k)
-      if (((qx + kFastMenu[k][0] - 1) / kFastMenu[k][0]) * ((qy + kFastMenu[k][1] - 1) / kFastMenu[k][1]) >= 512) {
+      if (menu_tiles(qx, qy, k) >= 512) {
         pick = k;
         break;
       }
@@ -3596,12 +3606,8 @@ extern "C" int fuelmi_frontier_search_begin(fuelmi_frontier* f) {
     // chain run; forgotten after 64 searches)
     if (f->menu_min_ttl > 0) --f->menu_min_ttl, pick = std::max(pick, f->menu_min);
     f->fast_menu = pick;
-    int ftx = kFastMenu[pick][0], fty = kFastMenu[pick][1];
-    hv.ftx = ftx, hv.fty = fty;
     hv.px0 = p0[0], hv.py0 = p0[1], hv.px1 = p1[0], hv.py1 = p1[1];
-    hv.ntx_f = std::max(0, (qx + ftx - 1) / ftx);
-    hv.nty_f = std::max(0, (qy + fty - 1) / fty);
-    hv.ntiles_f = hv.ntx_f * hv.nty_f;
+    set_fast_tiles(hv, pick);
   }
   // words to process: the x-slabs of the region plus one slab either side (neighbour look-ups of the
   // claims / unions read the Q0 plane there: it must not hold bits of an earlier search)
@@ -3629,7 +3635,6 @@ extern "C" int fuelmi_frontier_search_begin(fuelmi_frontier* f) {
 
   // the second radix pass is needed only beyond 256 kept clusters: guess from the previous search
   f->npass = f->last_nkept > 192 ? 2 : 1;
-  f->nb_launch = 256;  // the multisplit kernels stride over however many 2048-cell chunks there are
 
   // The fast chain's four kernels are launched DIRECTLY (rounds 2-3 replayed them as a hipGraph: cheaper for the host, but
   // the graph reaches the device ~10 us later, which is on the cycle's critical path since a fresh search runs beside the
@@ -3659,300 +3664,203 @@ extern "C" int fuelmi_frontier_search_begin(fuelmi_frontier* f) {
   return FUELMI_OK;
 }
 
-// searchFrontiers, second half: waits for the pipeline and assembles tmp_frontiers_.
-extern "C" int fuelmi_frontier_search_end(fuelmi_frontier* f, int* n_new) {
-  ARGCHK(f && n_new);
-  *n_new = 0;
-  FRONTIER_HAS_MAP(f);
-  if (!f->pending) {
-    fuelmi_set_error("fuelmi_frontier_search_end without a matching _begin");
-    return FUELMI_EINVAL;
+// FUELMI_FR_TIMING: where the tile kernel and the resolve kernel spend their time (100 MHz ticks)
+static void frontier_timing_report(fuelmi_frontier* f) {
+  const FArgs& F = f->F;
+  (void)hipStreamSynchronize(f->stream);
+  const int nt = f->h_var->ntiles_f;
+  std::vector<unsigned long long> d((size_t)(3 * (nt + 1)) * FR_DBG_SLOTS);
+  (void)hipMemcpy(d.data(), F.dbg, d.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+  unsigned long long t0 = ~0ull, t1 = 0;
+  double phase[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int busiest = 0, nonempty = 0;
+  for (int b = 0; b < nt; ++b) {
+    const unsigned long long* r = &d[(size_t)b * FR_DBG_SLOTS];
+    if (!r[0]) continue;
+    t0 = std::min(t0, r[0]);
+    for (int k = 1; k < 8; ++k)
+      if (r[k]) t1 = std::max(t1, r[k]);
+    if (r[8] > d[(size_t)busiest * FR_DBG_SLOTS + 8]) busiest = b;
+    if (r[8]) ++nonempty;
   }
-  f->pending = false;
-  struct ScopeEnd {  // closes the profiling bracket on every exit path
-    fuelmi_frontier* f;
-    ~ScopeEnd() { f->scope.reset(); }
-  } scope_end{f};
+  {
+    double st_av = 0, st_mx = 0, du_av = 0, du_mx = 0;
+    int cnt = 0;
+    for (int b = 0; b < nt; ++b) {
+      const unsigned long long* r = &d[(size_t)b * FR_DBG_SLOTS];
+      if (!r[0] || !r[6] || r[6] < r[0]) continue;
+      const double st = (double)(r[0] - t0) / 100.0, du = (double)(r[6] - r[0]) / 100.0;
+      st_av += st, st_mx = std::max(st_mx, st), du_av += du, du_mx = std::max(du_mx, du), ++cnt;
+    }
+    std::fprintf(stderr, "[fr-timing] ccl: %d tiles with cells: start avg %.1f max %.1f, duration avg %.1f max %.1f us\n", cnt,
+                 st_av / std::max(cnt, 1), st_mx, du_av / std::max(cnt, 1), du_mx);
+  }
+  const unsigned long long* rb = &d[(size_t)busiest * FR_DBG_SLOTS];
+  for (int k = 1; k < 8; ++k) phase[k] = rb[k] && rb[k - 1] ? (double)(rb[k] - rb[k - 1]) / 100.0 : 0.0;
+  std::fprintf(stderr, "[fr-timing] tiles %d (non-empty %d) span %.1f us; busiest tile %d (%llu cells, start +%.1f us): "
+               "bits %.1f labels %.1f unions %.1f roots %.1f records %.1f write %.1f us; %llu unions, %llu find steps, %llu links, %llu roots\n", nt, nonempty,
+               (double)(t1 - t0) / 100.0, busiest, rb[8], (double)(rb[0] - t0) / 100.0, phase[1], phase[2], phase[3],
+               phase[4], phase[5], phase[6], rb[9], rb[10], rb[11], rb[12]);
+  for (int kern = 1; kern <= 2; ++kern) {  // k_tile_cross, k_tile_out: rows behind those of the tiles and of k_resolve
+    const int np = kern == 1 ? 4 : 6;
+    double mx[8] = {0}, av[8] = {0};
+    unsigned long long c0 = ~0ull, c1 = 0;
+    int cnt = 0;
+    for (int b = 0; b < nt; ++b) {
+      const unsigned long long* r = &d[(size_t)(kern * (nt + 1) + b) * FR_DBG_SLOTS];
+      if (!r[0] || !r[np]) continue;
+      c0 = std::min(c0, r[0]), c1 = std::max(c1, r[np]);
+      for (int k = 1; k <= np; ++k) {
+        const double ph = r[k] && r[k - 1] ? (double)(r[k] - r[k - 1]) / 100.0 : 0.0;
+        mx[k] = std::max(mx[k], ph), av[k] += ph;
+      }
+      ++cnt;
+    }
+    double st_av = 0, st_mx = 0, du_av = 0, du_mx = 0;
+    for (int b = 0; b < nt; ++b) {
+      const unsigned long long* r = &d[(size_t)(kern * (nt + 1) + b) * FR_DBG_SLOTS];
+      if (!r[0] || !r[np]) continue;
+      const double st = (double)(r[0] - c0) / 100.0, du = (double)(r[np] - r[0]) / 100.0;
+      st_av += st, st_mx = std::max(st_mx, st), du_av += du, du_mx = std::max(du_mx, du);
+    }
+    {
+      unsigned long long e0 = ~0ull;
+      double ea = 0, em = 0, la = 0, lm = 0;
+      int n2 = 0;
+      for (int b = 0; b < nt; ++b) {
+        const unsigned long long v = d[(size_t)b * FR_DBG_SLOTS + 12 + kern];
+        if (v) e0 = std::min(e0, v);
+      }
+      for (int b = 0; b < nt; ++b) {
+        const unsigned long long v = d[(size_t)b * FR_DBG_SLOTS + 12 + kern];
+        const unsigned long long* r = &d[(size_t)(kern * (nt + 1) + b) * FR_DBG_SLOTS];
+        if (!v || !r[0] || r[0] < v) continue;
+        const double e = (double)(v - e0) / 100.0, l = (double)(r[0] - v) / 100.0;
+        ea += e, em = std::max(em, e), la += l, lm = std::max(lm, l), ++n2;
+      }
+      std::fprintf(stderr, "[fr-timing]   entry avg %.1f max %.1f us after the first workgroup; entry -> first stamp avg %.1f max %.1f us\n",
+                   ea / std::max(n2, 1), em, la / std::max(n2, 1), lm);
+    }
+    std::fprintf(stderr, "[fr-timing] %s: span %.1f us over %d tiles; start avg %.1f max %.1f, duration avg %.1f max %.1f; phases avg/max:",
+                 kern == 1 ? "cross (bits, build, list, append)" : "out (bits, cells, column, first, rows, flags)",
+                 cnt ? (double)(c1 - c0) / 100.0 : 0.0, cnt, st_av / std::max(cnt, 1), st_mx, du_av / std::max(cnt, 1), du_mx);
+    for (int k = 1; k <= np; ++k) std::fprintf(stderr, " %.1f/%.1f", av[k] / std::max(cnt, 1), mx[k]);
+    std::fprintf(stderr, "\n");
+  }
+  const unsigned long long* rr = &d[(size_t)nt * FR_DBG_SLOTS];
+  std::fprintf(stderr, "[fr-timing] resolve: init %.1f unions %.1f find %.1f reduce %.1f clusters %.1f seeds %.1f rank %.1f "
+               "codes %.1f publish %.1f us; pairs %llu roots %llu cells %llu\n", (rr[1] - rr[0]) / 100.0,
+               (rr[2] - rr[1]) / 100.0, (rr[3] - rr[2]) / 100.0, (rr[4] - rr[3]) / 100.0, (rr[5] - rr[4]) / 100.0, 0.0,
+               (rr[6] - rr[5]) / 100.0, (rr[7] - rr[6]) / 100.0, (rr[8] - rr[7]) / 100.0, rr[9], rr[10], rr[11]);
+}
+
+// the fast chain publishes counts + cluster records from k_resolve and stamps them with the search's epoch; the two
+// kernels behind it (flags, regrouping + copy-out of the cells) keep running -- whoever touches the cell lists waits for
+// them (frontier_tail_sync).  Then: the late resolve, the re-tiled runs and the legacy fallback, as the result asks.
+static int frontier_collect_fast(fuelmi_frontier* f) {
   fuelmi_map* m = f->map;
-  HIPCHK(hipSetDevice(m->device));
-  // (a plane mutator issued from here on comes behind this call's wait for the chain's result: the plane-reading
-  // kernels are done by then -- nothing left for it to wait for)
-  struct DropLate {
-    fuelmi_frontier* f;
-    ~DropLate() {
-      if (f->map) map_drop_late_reader(f->map, f->ev_planes_read);
-    }
-  } drop_late{f};
-  if (f->search_empty) {
-    if (!f->pend_rm.empty()) {
-      HIPCHK(hipStreamSynchronize(f->stream));
-      remove_changed_end(f);
-    }
-    return FUELMI_OK;
-  }
   const Geo& g = m->g;
   FArgs& F = f->F;
-  const int nb_launch = f->nb_launch;
   u32* counts = F.h_counts;
+  volatile u32* stamp = counts + 15;
+  const u32 want = f->h_var->epoch;
+  // (poll, ~100 us of chain: a blocking wake-up costs a noticeable fraction of that; the time spent polling is the part
+  // of _search_end that is the device's, not the host's)
+  const auto w0 = std::chrono::steady_clock::now();
+  const int rcw = stamp_wait<u32>(stamp, want, f->stream, "frontier search: the chain finished without publishing its result");
+  f->wait_us_acc += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - w0).count();
+  if (rcw) return rcw;
+  g_ht.lap(11);
+  f->tail_pending = true;
+  F.fast = 1;
+  if (F.dbg) frontier_timing_report(f);
+  if (counts[2] == 3u) {  // the search outgrew the launch that was to resolve it and no k_resolve was queued: do it now
+    const int mk = f->fast_menu;
+    *stamp = 0u;
+    k_resolve<<<1, RS_TK, f->resolve_lds, f->stream>>>(g, F);
+    k_tile_out<512><<<fast_launch_tiles(F, mk), 512, f->out_lds[mk], f->stream>>>(g, F);
+    HIPCHK(hipGetLastError());
+    const int rc = stamp_wait<u32>(stamp, want, f->stream, "frontier search: k_resolve finished without publishing its result");
+    if (rc) return rc;
+    ++f->n_late_resolve;
+  }
+  f->kr_skip_ok = counts[2] == 0u && counts[9] == 1u && 2u * counts[10] <= f->rcap_used;
+  ++f->n_fast;
+  if (counts[9] == 1u)
+    ++f->n_in_launch;
+  else if (f->fuse_tried && counts[2] == 0u)
+    f->fuse_skip = 16;  // (too many tile roots for the launch's LDS: k_resolve did it)
+  if (counts[2] == 2u && m->fusion_count != f->fusion_at_begin) {
+    fuelmi_set_error("frontier search: the fast chain overflowed AFTER the map was fused again (a frame queued between "
+                     "_search_begin and _search_end): the occupancy this search was about is gone -- call _search_end before the next fusion "
+                     "on inputs this noisy");
+    // the changed clusters' flags are already cleared on the device: take them off the lists too, and make the next
+    // search look at the whole box again (the lists and the flag plane must not part ways on this path)
+    remove_changed_end(f);
+    f->dirty_all = true;
+    return FUELMI_ELIMIT;
+  }
+  // A capacity of ONE TILE was exceeded (codes 11 cells, 12 components, 15 root pairs, 18 work-list entries -- a
+  // full-height frontier wall along a y-line puts 32 x nz cells into one 8 x 32 tile): nothing was modified, and
+  // the menu's next, smaller tile holds half as much per tile -- run the chain again on it before giving the search to
+  // the legacy chain (round 6, with FR_TCELL = 2 048).
+  while (counts[2] == 2u && f->fast_menu < 3 && (counts[6] == 11u || counts[6] == 12u || counts[6] == 15u || counts[6] == 18u)) {
+    HIPCHK(frontier_tail_sync(f) == FUELMI_OK ? hipSuccess : hipErrorUnknown);
+    ++f->fast_menu;
+    FVar hv = *f->h_var;
+    set_fast_tiles(hv, f->fast_menu);
+    hv.epoch = ++f->epoch;
+    if (hv.epoch == 0u) hv.epoch = f->epoch = 1u;
+    *f->h_var = hv;
+    f->kr_skip_ok = false;  // (k_resolve queued: no second round trip whatever the root count)
+    if (getenv("FUELMI_FR_TIMING")) std::fprintf(stderr, "[fr-timing] capacity code %u: again with %d x %d tiles\n", counts[6], hv.ftx, hv.fty);
+    const int rcr = frontier_enqueue_fast(f);
+    if (rcr) return rcr;
+    const int rcw = stamp_wait<u32>(stamp, hv.epoch, f->stream,
+                                    "frontier search: the re-tiled chain finished without publishing its result");
+    if (rcw) return rcw;
+    f->tail_pending = true;
+    ++f->n_retiled;
+    f->menu_min = f->fast_menu, f->menu_min_ttl = 64;
+  }
+  if (counts[2] == 2u) {
+    // a capacity of the fast path was exceeded (noise-like input): nothing was modified; run the legacy chain
+    --f->n_fast;
+    ++f->n_fallback;
+    if (getenv("FUELMI_FR_TIMING")) std::fprintf(stderr, "[fr-timing] fallback to the legacy chain: capacity code %u\n", counts[6]);
+    HIPCHK(frontier_tail_sync(f) == FUELMI_OK ? hipSuccess : hipErrorUnknown);
+    F.fast = 0;
+    f->npass = 1;
+    int rcl = frontier_enqueue_chain(f, f->npass);
+    if (rcl) return rcl;
+    HIPCHK(hipStreamSynchronize(f->stream));
+  }
+  return FUELMI_OK;
+}
+
+// more than 256 clusters but only one radix pass was enqueued: run the high-digit pass now, and wait for it
+static int frontier_second_pass(fuelmi_frontier* f) {
+  const Geo& g = f->map->g;
+  FArgs& F = f->F;
+  enqueue_ms_passes(f, F, 1, 2);
+  // cluster records must be re-initialised before the accumulators are refilled
+  k_rank_kept<<<16, 256, 0, f->stream>>>(F);
+  FDBG("k_rank_kept");
+  k_ms_info<<<256, 256, 0, f->stream>>>(g, F);
+  FDBG("k_ms_info");
+  k_pack<<<1, 256, 0, f->stream>>>(F);
+  FDBG("k_pack");
+  HIPCHK(hipStreamSynchronize(f->stream));
+  return FUELMI_OK;
+}
+
+// tmp_frontiers_ from the records of the search's nkept clusters (nq Q0 cells, n_out grouped cells)
+static int frontier_assemble(fuelmi_frontier* f, u32 nq, u32 nkept, u32 n_out) {
+  const Geo& g = f->map->g;
+  FArgs& F = f->F;
   KeptRec* h_rec = F.h_rec;
   const u32* h_part = F.h_part;
   const u32* h_cells = F.h_cells;
-  // poll instead of a blocking wait: the caller is about to consume the result and the chain is
-  // ~100 us long, an interrupt-driven wake-up costs a noticeable fraction of that
-  F.fast = 0;
-  g_ht.start();
-  if (g_ht.on) --g_ht.n;
-  g_ht.lap(10);
-  if (f->fast_launched) {
-    // the fast chain publishes counts + cluster records from k_resolve and stamps them with the search's epoch;
-    // the two kernels behind it (flags, regrouping + copy-out of the cells) keep running -- whoever touches the
-    // cell lists waits for them (frontier_tail_sync)
-    volatile u32* stamp = counts + 15;
-    const u32 want = f->h_var->epoch;
-    unsigned spins = 0;
-    const auto w0 = std::chrono::steady_clock::now();
-    struct WaitAcc {  // (time spent polling: the part of _search_end that is the device's, not the host's)
-      fuelmi_frontier* f;
-      std::chrono::steady_clock::time_point w0;
-      ~WaitAcc() { f->wait_us_acc += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - w0).count(); }
-    };
-    {
-    WaitAcc wacc{f, w0};
-    const bool yld = poll_yields();
-    while (*stamp != want) {
-      if (yld) std::this_thread::yield();
-      if ((++spins & 0x3FFFu) == 0u) {  // every ~16k polls: has the stream died under us?
-        const hipError_t q = hipStreamQuery(f->stream);
-        if (q != hipErrorNotReady && q != hipSuccess) HIPCHK(q);
-        if (q == hipSuccess && *stamp != want) {
-          fuelmi_set_error("frontier search: the chain finished without publishing its result");
-          return FUELMI_EHIP;
-        }
-      }
-    }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    g_ht.lap(11);
-    f->tail_pending = true;
-    F.fast = 1;
-    if (F.dbg) {  // FUELMI_FR_TIMING: where the tile kernel and the resolve kernel spend their time (100 MHz ticks)
-      (void)hipStreamSynchronize(f->stream);
-      const int nt = f->h_var->ntiles_f;
-      std::vector<unsigned long long> d((size_t)(3 * (nt + 1)) * FR_DBG_SLOTS);
-      (void)hipMemcpy(d.data(), F.dbg, d.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-      unsigned long long t0 = ~0ull, t1 = 0;
-      double phase[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      int busiest = 0, nonempty = 0;
-      for (int b = 0; b < nt; ++b) {
-        const unsigned long long* r = &d[(size_t)b * FR_DBG_SLOTS];
-        if (!r[0]) continue;
-        t0 = std::min(t0, r[0]);
-        for (int k = 1; k < 8; ++k)
-          if (r[k]) t1 = std::max(t1, r[k]);
-        if (r[8] > d[(size_t)busiest * FR_DBG_SLOTS + 8]) busiest = b;
-        if (r[8]) ++nonempty;
-      }
-      {
-        double st_av = 0, st_mx = 0, du_av = 0, du_mx = 0;
-        int cnt = 0;
-        for (int b = 0; b < nt; ++b) {
-          const unsigned long long* r = &d[(size_t)b * FR_DBG_SLOTS];
-          if (!r[0] || !r[6] || r[6] < r[0]) continue;
-          const double st = (double)(r[0] - t0) / 100.0, du = (double)(r[6] - r[0]) / 100.0;
-          st_av += st, st_mx = std::max(st_mx, st), du_av += du, du_mx = std::max(du_mx, du), ++cnt;
-        }
-        std::fprintf(stderr, "[fr-timing] ccl: %d tiles with cells: start avg %.1f max %.1f, duration avg %.1f max %.1f us\n", cnt,
-                     st_av / std::max(cnt, 1), st_mx, du_av / std::max(cnt, 1), du_mx);
-      }
-      const unsigned long long* rb = &d[(size_t)busiest * FR_DBG_SLOTS];
-      for (int k = 1; k < 8; ++k) phase[k] = rb[k] && rb[k - 1] ? (double)(rb[k] - rb[k - 1]) / 100.0 : 0.0;
-      std::fprintf(stderr, "[fr-timing] tiles %d (non-empty %d) span %.1f us; busiest tile %d (%llu cells, start +%.1f us): "
-                   "bits %.1f labels %.1f unions %.1f roots %.1f records %.1f write %.1f us; %llu unions, %llu find steps, %llu links, %llu roots\n", nt, nonempty,
-                   (double)(t1 - t0) / 100.0, busiest, rb[8], (double)(rb[0] - t0) / 100.0, phase[1], phase[2], phase[3],
-                   phase[4], phase[5], phase[6], rb[9], rb[10], rb[11], rb[12]);
-      for (int kern = 1; kern <= 2; ++kern) {  // k_tile_cross, k_tile_out: rows behind those of the tiles and of k_resolve
-        const int np = kern == 1 ? 4 : 6;
-        double mx[8] = {0}, av[8] = {0};
-        unsigned long long c0 = ~0ull, c1 = 0;
-        int cnt = 0;
-        for (int b = 0; b < nt; ++b) {
-          const unsigned long long* r = &d[(size_t)(kern * (nt + 1) + b) * FR_DBG_SLOTS];
-          if (!r[0] || !r[np]) continue;
-          c0 = std::min(c0, r[0]), c1 = std::max(c1, r[np]);
-          for (int k = 1; k <= np; ++k) {
-            const double ph = r[k] && r[k - 1] ? (double)(r[k] - r[k - 1]) / 100.0 : 0.0;
-            mx[k] = std::max(mx[k], ph), av[k] += ph;
-          }
-          ++cnt;
-        }
-        double st_av = 0, st_mx = 0, du_av = 0, du_mx = 0;
-        for (int b = 0; b < nt; ++b) {
-          const unsigned long long* r = &d[(size_t)(kern * (nt + 1) + b) * FR_DBG_SLOTS];
-          if (!r[0] || !r[np]) continue;
-          const double st = (double)(r[0] - c0) / 100.0, du = (double)(r[np] - r[0]) / 100.0;
-          st_av += st, st_mx = std::max(st_mx, st), du_av += du, du_mx = std::max(du_mx, du);
-        }
-        {
-          unsigned long long e0 = ~0ull;
-          double ea = 0, em = 0, la = 0, lm = 0;
-          int n2 = 0;
-          for (int b = 0; b < nt; ++b) {
-            const unsigned long long v = d[(size_t)b * FR_DBG_SLOTS + 12 + kern];
-            if (v) e0 = std::min(e0, v);
-          }
-          for (int b = 0; b < nt; ++b) {
-            const unsigned long long v = d[(size_t)b * FR_DBG_SLOTS + 12 + kern];
-            const unsigned long long* r = &d[(size_t)(kern * (nt + 1) + b) * FR_DBG_SLOTS];
-            if (!v || !r[0] || r[0] < v) continue;
-            const double e = (double)(v - e0) / 100.0, l = (double)(r[0] - v) / 100.0;
-            ea += e, em = std::max(em, e), la += l, lm = std::max(lm, l), ++n2;
-          }
-          std::fprintf(stderr, "[fr-timing]   entry avg %.1f max %.1f us after the first workgroup; entry -> first stamp avg %.1f max %.1f us\n",
-                       ea / std::max(n2, 1), em, la / std::max(n2, 1), lm);
-        }
-        std::fprintf(stderr, "[fr-timing] %s: span %.1f us over %d tiles; start avg %.1f max %.1f, duration avg %.1f max %.1f; phases avg/max:",
-                     kern == 1 ? "cross (bits, build, list, append)" : "out (bits, cells, column, first, rows, flags)",
-                     cnt ? (double)(c1 - c0) / 100.0 : 0.0, cnt, st_av / std::max(cnt, 1), st_mx, du_av / std::max(cnt, 1), du_mx);
-        for (int k = 1; k <= np; ++k) std::fprintf(stderr, " %.1f/%.1f", av[k] / std::max(cnt, 1), mx[k]);
-        std::fprintf(stderr, "\n");
-      }
-      const unsigned long long* rr = &d[(size_t)nt * FR_DBG_SLOTS];
-      std::fprintf(stderr, "[fr-timing] resolve: init %.1f unions %.1f find %.1f reduce %.1f clusters %.1f seeds %.1f rank %.1f "
-                   "codes %.1f publish %.1f us; pairs %llu roots %llu cells %llu\n", (rr[1] - rr[0]) / 100.0,
-                   (rr[2] - rr[1]) / 100.0, (rr[3] - rr[2]) / 100.0, (rr[4] - rr[3]) / 100.0, (rr[5] - rr[4]) / 100.0, 0.0,
-                   (rr[6] - rr[5]) / 100.0, (rr[7] - rr[6]) / 100.0, (rr[8] - rr[7]) / 100.0, rr[9], rr[10], rr[11]);
-    }
-    if (counts[2] == 3u) {  // the search outgrew the launch that was to resolve it and no k_resolve was queued: do it now
-      const int mk = f->fast_menu;
-      const int qx = F.qbox.hi[0] - F.qbox.lo[0] + 2, qy = F.qbox.hi[1] - F.qbox.lo[1] + 2;
-      const int tiles = ((qx + kFastMenu[mk][0] - 1) / kFastMenu[mk][0]) * ((qy + kFastMenu[mk][1] - 1) / kFastMenu[mk][1]);
-      *stamp = 0u;
-      k_resolve<<<1, RS_TK, f->resolve_lds, f->stream>>>(g, F);
-      k_tile_out<512><<<tiles, 512, f->out_lds[mk], f->stream>>>(g, F);
-      HIPCHK(hipGetLastError());
-      unsigned spins2 = 0;
-      while (*stamp != want) {
-        if ((++spins2 & 0x3FFFu) == 0u) {
-          const hipError_t q = hipStreamQuery(f->stream);
-          if (q != hipErrorNotReady && q != hipSuccess) HIPCHK(q);
-          if (q == hipSuccess && *stamp != want) {
-            fuelmi_set_error("frontier search: k_resolve finished without publishing its result");
-            return FUELMI_EHIP;
-          }
-        }
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
-      ++f->n_late_resolve;
-    }
-    f->kr_skip_ok = counts[2] == 0u && counts[9] == 1u && 2u * counts[10] <= f->rcap_used;
-    ++f->n_fast;
-    if (counts[9] == 1u)
-      ++f->n_in_launch;
-    else if (f->fuse_tried && counts[2] == 0u)
-      f->fuse_skip = 16;  // (too many tile roots for the launch's LDS: k_resolve did it)
-    if (counts[2] == 2u && m->fusion_count != f->fusion_at_begin) {
-      fuelmi_set_error("frontier search: the fast chain overflowed AFTER the map was fused again (a frame queued between "
-                       "_search_begin and _search_end): the occupancy this search was about is gone -- call _search_end before the next fusion "
-                       "on inputs this noisy");
-      // the changed clusters' flags are already cleared on the device: take them off the lists too, and make the next
-      // search look at the whole box again (the lists and the flag plane must not part ways on this path)
-      remove_changed_end(f);
-      f->dirty_all = true;
-      return FUELMI_ELIMIT;
-    }
-    // A capacity of ONE TILE was exceeded (codes 11 cells, 12 components, 15 root pairs, 18 work-list entries -- a
-    // full-height frontier wall along a y-line puts 32 x nz cells into one 8 x 32 tile): nothing was modified, and
-    // the menu's next, smaller tile holds half as much per tile -- run the chain again on it before giving the search to
-    // the legacy chain (round 6, with FR_TCELL = 2 048).
-    while (counts[2] == 2u && f->fast_menu < 3 && (counts[6] == 11u || counts[6] == 12u || counts[6] == 15u || counts[6] == 18u)) {
-      HIPCHK(frontier_tail_sync(f) == FUELMI_OK ? hipSuccess : hipErrorUnknown);
-      ++f->fast_menu;
-      FVar hv = *f->h_var;
-      const int qx = hv.px1 - hv.px0 + 1, qy = hv.py1 - hv.py0 + 1;
-      hv.ftx = kFastMenu[f->fast_menu][0], hv.fty = kFastMenu[f->fast_menu][1];
-      hv.ntx_f = std::max(0, (qx + hv.ftx - 1) / hv.ftx);
-      hv.nty_f = std::max(0, (qy + hv.fty - 1) / hv.fty);
-      hv.ntiles_f = hv.ntx_f * hv.nty_f;
-      hv.epoch = ++f->epoch;
-      if (hv.epoch == 0u) hv.epoch = f->epoch = 1u;
-      *f->h_var = hv;
-      f->kr_skip_ok = false;  // (k_resolve queued: no second round trip whatever the root count)
-      if (getenv("FUELMI_FR_TIMING")) std::fprintf(stderr, "[fr-timing] capacity code %u: again with %d x %d tiles\n", counts[6], hv.ftx, hv.fty);
-      const int rcr = frontier_enqueue_fast(f);
-      if (rcr) return rcr;
-      unsigned spins3 = 0;
-      while (*stamp != hv.epoch) {
-        if ((++spins3 & 0x3FFFu) == 0u) {
-          const hipError_t q = hipStreamQuery(f->stream);
-          if (q != hipErrorNotReady && q != hipSuccess) HIPCHK(q);
-          if (q == hipSuccess && *stamp != hv.epoch) {
-            fuelmi_set_error("frontier search: the re-tiled chain finished without publishing its result");
-            return FUELMI_EHIP;
-          }
-        }
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
-      f->tail_pending = true;
-      ++f->n_retiled;
-      f->menu_min = f->fast_menu, f->menu_min_ttl = 64;
-    }
-    if (counts[2] == 2u) {
-      // a capacity of the fast path was exceeded (noise-like input): nothing was modified; run the legacy chain
-      --f->n_fast;
-      ++f->n_fallback;
-      if (getenv("FUELMI_FR_TIMING")) std::fprintf(stderr, "[fr-timing] fallback to the legacy chain: capacity code %u\n", counts[6]);
-      HIPCHK(frontier_tail_sync(f) == FUELMI_OK ? hipSuccess : hipErrorUnknown);
-      F.fast = 0;
-      f->npass = 1;
-      int rcl = frontier_enqueue_chain(f, f->npass);
-      if (rcl) return rcl;
-      HIPCHK(hipStreamSynchronize(f->stream));
-    }
-  } else {
-    ++f->n_legacy;
-    hipError_t q;
-    while ((q = hipStreamQuery(f->stream)) == hipErrorNotReady) {
-    }
-    HIPCHK(q);
-  }
-  remove_changed_end(f);
-  if (f->rm_failed) {
-    f->rm_failed = false;
-    f->dirty_all = true;
-    fuelmi_set_error("frontier search: the changed-cluster test's in-kernel barrier timed out (device oversubscribed for 50 ms?)");
-    return FUELMI_EHIP;
-  }
-  if (counts[2] || counts[3] > F.cap_kept) {
-    fuelmi_set_error("frontier capacity exceeded (cells %u/%u seeds %u/%u clusters %u/%u)", counts[0], F.cap_q,
-                     counts[1], F.cap_s, counts[3], F.cap_kept);
-    return FUELMI_ELIMIT;
-  }
-  const u32 nq = counts[0], nkept = counts[3], n_out = counts[5];
-  f->last_nkept = (int)nkept;
-  if (nkept > 256 && f->npass < 2) {
-    // more than 256 clusters but only one radix pass was enqueued: run the high-digit pass now
-    for (int p = 1; p < 2; ++p) {
-      k_ms_hist<<<nb_launch, 256, 0, f->stream>>>(F, p);
-      FDBG("k_ms_hist");
-      k_ms_scan<<<1, 1024, 0, f->stream>>>(F, p);
-      FDBG("k_ms_scan");
-      k_ms_scatter<<<nb_launch, 256, 0, f->stream>>>(F, p);
-      FDBG("k_ms_scatter");
-    }
-    // cluster records must be re-initialised before the accumulators are refilled
-    k_rank_kept<<<16, 256, 0, f->stream>>>(F);
-    FDBG("k_rank_kept");
-    k_ms_info<<<256, 256, 0, f->stream>>>(g, F);
-    FDBG("k_ms_info");
-    k_pack<<<1, 256, 0, f->stream>>>(F);
-    FDBG("k_pack");
-    HIPCHK(hipStreamSynchronize(f->stream));
-  }
-  if (nkept == 0) {
-    f->dirty_all = false;
-    f->seen_epoch = m->occ_epoch;
-    return FUELMI_OK;
-  }
   u32 ncl = nkept, ncells = n_out;
   std::vector<std::vector<float>> filtered;
   const bool split_mode = f->cfg.split != 0;
@@ -4077,6 +3985,78 @@ extern "C" int fuelmi_frontier_search_end(fuelmi_frontier* f, int* n_new) {
       }
     }
   }
+  return FUELMI_OK;
+}
+
+// searchFrontiers, second half: waits for the pipeline and assembles tmp_frontiers_.
+extern "C" int fuelmi_frontier_search_end(fuelmi_frontier* f, int* n_new) {
+  ARGCHK(f && n_new);
+  *n_new = 0;
+  FRONTIER_HAS_MAP(f);
+  if (!f->pending) {
+    fuelmi_set_error("fuelmi_frontier_search_end without a matching _begin");
+    return FUELMI_EINVAL;
+  }
+  f->pending = false;
+  struct ScopeEnd {  // closes the profiling bracket on every exit path
+    fuelmi_frontier* f;
+    ~ScopeEnd() { f->scope.reset(); }
+  } scope_end{f};
+  fuelmi_map* m = f->map;
+  HIPCHK(hipSetDevice(m->device));
+  // (a plane mutator issued from here on comes behind this call's wait for the chain's result: the plane-reading
+  // kernels are done by then -- nothing left for it to wait for)
+  struct DropLate {
+    fuelmi_frontier* f;
+    ~DropLate() {
+      if (f->map) map_drop_late_reader(f->map, f->ev_planes_read);
+    }
+  } drop_late{f};
+  if (f->search_empty) {
+    if (!f->pend_rm.empty()) {
+      HIPCHK(hipStreamSynchronize(f->stream));
+      remove_changed_end(f);
+    }
+    return FUELMI_OK;
+  }
+  FArgs& F = f->F;
+  const u32* counts = F.h_counts;
+  F.fast = 0;
+  g_ht.start();
+  if (g_ht.on) --g_ht.n;
+  g_ht.lap(10);
+  if (f->fast_launched) {
+    const int rc = frontier_collect_fast(f);
+    if (rc) return rc;
+  } else {
+    ++f->n_legacy;
+    HIPCHK(stream_poll(f->stream));
+  }
+  remove_changed_end(f);
+  if (f->rm_failed) {
+    f->rm_failed = false;
+    f->dirty_all = true;
+    fuelmi_set_error("frontier search: the changed-cluster test's in-kernel barrier timed out (device oversubscribed for 50 ms?)");
+    return FUELMI_EHIP;
+  }
+  if (counts[2] || counts[3] > F.cap_kept) {
+    fuelmi_set_error("frontier capacity exceeded (cells %u/%u seeds %u/%u clusters %u/%u)", counts[0], F.cap_q,
+                     counts[1], F.cap_s, counts[3], F.cap_kept);
+    return FUELMI_ELIMIT;
+  }
+  const u32 nq = counts[0], nkept = counts[3], n_out = counts[5];
+  f->last_nkept = (int)nkept;
+  if (nkept > 256 && f->npass < 2) {
+    const int rc = frontier_second_pass(f);
+    if (rc) return rc;
+  }
+  if (nkept == 0) {
+    f->dirty_all = false;
+    f->seen_epoch = m->occ_epoch;
+    return FUELMI_OK;
+  }
+  const int rc = frontier_assemble(f, nq, nkept, n_out);
+  if (rc) return rc;
   *n_new = (int)f->tmp.size();
   f->dirty_all = false;
   f->seen_epoch = m->occ_epoch;

@@ -339,7 +339,7 @@ struct fuelmi_frontier {
   size_t d_stage_bytes = 0;
   void* h_pin = nullptr;  // pinned result staging
   size_t pin_bytes = 0;
-  int last_nkept = 0, nb_launch = 0, npass = 1;
+  int last_nkept = 0, npass = 1;
   FVar* h_var = nullptr;  // pinned per-search arguments
   FVar* d_var = nullptr;
   int TX = 1, TY = 16, ccl_tiles = 0;
@@ -429,20 +429,13 @@ static inline int frontier_tail_sync(const fuelmi_frontier* f) {
   f->tail_pending = false;
   // poll: the tail is a few microseconds of work that has usually finished long before anybody asks, and a
   // blocking stream synchronisation costs ~15 us of wake-up latency even then
-  for (;;) {
-    const hipError_t q = hipStreamQuery(f->stream);
-    if (q == hipSuccess) return FUELMI_OK;
-    if (q != hipErrorNotReady) HIPCHK(q);
-  }
+  HIPCHK(stream_poll(f->stream));
+  return FUELMI_OK;
 }
 // ... and make sure the grouped cell lists are in the pinned result buffer (the lazy clusters point into it)
 static inline int frontier_prev_ready(const fuelmi_frontier* f) {
   if (!f->prev_pending) return FUELMI_OK;
-  for (;;) {
-    const hipError_t q = hipEventQuery(f->ev_prev);
-    if (q == hipSuccess) break;
-    if (q != hipErrorNotReady) HIPCHK(q);
-  }
+  HIPCHK(event_poll(f->ev_prev));
   const_cast<fuelmi_frontier*>(f)->prev_pending = false;
   return FUELMI_OK;
 }

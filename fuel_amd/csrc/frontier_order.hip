@@ -652,11 +652,7 @@ int frontier_reference_order(fuelmi_frontier* f, u32 nq, u32 nkept, u32 n_out, i
     k_bfs_emit<<<dim3(64, nkept), 256, 0, st>>>(m->g, F, B);
     HIPCHK(hipGetLastError());
   }
-  for (;;) {  // (poll: a blocking synchronisation adds ~15 us of wake-up to a sweep of a few hundred)
-    const hipError_t q = hipStreamQuery(st);
-    if (q == hipSuccess) break;
-    if (q != hipErrorNotReady) HIPCHK(q);
-  }
+  HIPCHK(stream_poll(st));  // (a blocking synchronisation adds ~15 us of wake-up to a sweep of a few hundred)
   if (timing)
     std::fprintf(stderr, "[fr-timing] reference order: %u clusters, %u cells, largest in LDS %u (levels of cluster 0: %u), global sweep %d: %.1f us\n",
                  nkept, total, lcap, o->h_err[3], any_big ? 1 : 0,

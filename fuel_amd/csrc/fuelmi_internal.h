@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <condition_variable>
@@ -279,6 +280,41 @@ static inline hipError_t stream_wait(hipStream_t s) {
     if (yld) std::this_thread::yield();
   }
   return hipStreamSynchronize(s);
+}
+// poll a stream / an event until its work is done, never blocking (work that has usually finished when anybody asks)
+static inline hipError_t stream_poll(hipStream_t s) {
+  const bool yld = poll_yields();
+  hipError_t q;
+  while ((q = hipStreamQuery(s)) == hipErrorNotReady)
+    if (yld) std::this_thread::yield();
+  return q;
+}
+static inline hipError_t event_poll(hipEvent_t ev) {
+  const bool yld = poll_yields();
+  hipError_t q;
+  while ((q = hipEventQuery(ev)) == hipErrorNotReady)
+    if (yld) std::this_thread::yield();
+  return q;
+}
+// wait for a kernel on stream s to write `want` into the pinned word `stamp` (acquire: what it published is visible);
+// every ~16k polls: has the stream died under us (its error), or gone idle without the stamp (FUELMI_EHIP, `what`)?
+template <class T>
+static inline int stamp_wait(const volatile T* stamp, T want, hipStream_t s, const char* what) {
+  const bool yld = poll_yields();
+  unsigned spins = 0;
+  while (*stamp != want) {
+    if (yld) std::this_thread::yield();
+    if ((++spins & 0x3FFFu) == 0u) {
+      const hipError_t q = hipStreamQuery(s);
+      if (q != hipErrorNotReady && q != hipSuccess) HIPCHK(q);
+      if (q == hipSuccess && *stamp != want) {
+        fuelmi_set_error("%s", what);
+        return FUELMI_EHIP;
+      }
+    }
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  return FUELMI_OK;
 }
 
 // to be called by everything that rewrites the occupancy planes, before it queues its kernels

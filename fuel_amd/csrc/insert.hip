@@ -528,18 +528,9 @@ static int insert_points_dev(fuelmi_map* m, const unsigned char* d_pts, int stri
   u64 h_bbox[8];
   {
     volatile u64* hv = m->h_ins;
-    unsigned spins = 0;
-    while (hv[7] != A.epoch) {
-      if ((++spins & 0x3FFFu) == 0u) {
-        const hipError_t q = hipStreamQuery(m->stream);
-        if (q != hipErrorNotReady && q != hipSuccess) HIPCHK(q);
-        if (q == hipSuccess && hv[7] != A.epoch) {
-          fuelmi_set_error("fusion: the kernels finished without publishing the end-point box");
-          return FUELMI_EHIP;
-        }
-      }
-    }
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    const int rc = stamp_wait<u64>(hv + 7, A.epoch, m->stream,
+                                   "fusion: the kernels finished without publishing the end-point box");
+    if (rc) return rc;
     for (int k = 0; k < 8; ++k) h_bbox[k] = hv[k];
   }
   if (counted) {

@@ -62,9 +62,6 @@ timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stream -o
 # in-kernel phase stamps of the packed z/y pass, and the ESDF kernels per family (same box)
 { for WL in G400 G800 G400K; do FUELMI_ZY_TIMING=1 python scripts/esdf_only.py $WL 0 3 2>&1 | grep -E "zy2-timing|x2-timing|slowest" | tail -4 | sed "s/^/$WL /"; done
   for WL in G400 G800 G400K G400E; do for FAM in 0 2 1; do echo -n "$WL family $FAM: "; python scripts/esdf_only.py $WL $FAM 8; done; done; } > $O/esdf_family_ab.txt 2>&1
-# this round's one remaining switch, same box, interleaved: the last workgroup of k_tile_cross resolving the search (default)
-# against k_resolve as a launch of its own (FUELMI_FR_FUSE=0)
-NOTEST=1 bash scripts/r6_fuse_ab.sh > $O/cross_resolve_fusion_ab_final.txt 2>&1
 # the round-5 build of the library on the same box (build/r5 is a worktree of 5605e15 built by hand before the call)
 if [ -d build/r5/fuel_amd ]; then
   { echo "# same box, same call: round-5 final (5605e15) against this tree, twice, interleaved; bench.py --no-cpu-baseline of each (value, stage_ms in the cycle, isolated)"
