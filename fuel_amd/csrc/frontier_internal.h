@@ -1,9 +1,13 @@
-// frontier_internal.h -- structures shared by frontier.hip (scan + clustering) and
-// frontier_split.hip (splitLargeFrontiers / down-sampling on the device).
+// frontier_internal.h -- structures and host entry points shared by the frontier finder's sources: frontier.hip
+// (lifecycle, search_begin / _end, assembly of the result), frontier_tile.hip (the tile chain), frontier_legacy.hip
+// (the legacy chain), frontier_changed.hip (changed-cluster test, cell pool), frontier_query.hip (read-back),
+// frontier_split.hip (splitLargeFrontiers / down-sampling on the device), frontier_order.hip (the reference's cell
+// order), frontier_view.hip (viewpoints) and bench_drivers.hip.
 #ifndef FUELMI_FRONTIER_INTERNAL_H_
 #define FUELMI_FRONTIER_INTERNAL_H_
 
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <list>
 #include <memory>
@@ -46,7 +50,7 @@ struct FVar {
   int pad3[3];
 };
 
-// ---- fast path of the clustering chain (frontier.hip, "tile-root resolve") ---------------------------------
+// ---- fast path of the clustering chain (frontier_tile.hip, "tile-root resolve") ---------------------------------
 // A workgroup labels one spatial tile in LDS (k_tile_ccl) and describes every tile-local component by ONE record;
 // the cross-tile merge, the claims, the cluster sizes, the kept list and its ranking then run on those few
 // thousand records inside a single workgroup's LDS (k_resolve) instead of on the cells through global atomics.
@@ -235,6 +239,47 @@ __device__ __forceinline__ u32 rank_s(const FArgs& F, long a) {
   int rel = w - F.var->w0;
   u64 pk = F.blockscan[rel >> 8] + F.pref[rel];
   return (u32)(pk >> 32) + (u32)__popcll(F.sb[w] & ((1ull << (a & 63)) - 1ull));
+}
+
+// F1 for the 64 voxels of word w (knownfree && isNeighborUnknown); out-of-map neighbours are
+// "-1", i.e. not UNKNOWN (sdf_map.h:196-198)
+__device__ __forceinline__ u64 f1_word(const Geo& g, const u64* __restrict__ occ, const u64* __restrict__ unk,
+                                       int w, u64 z0, u64 zl, u64 y0, u64 yl) {
+  long a0 = 64L * w;
+  u64 valid = (a0 + 64 <= g.N) ? ~0ull : bit_range(0, (int)max(0L, g.N - a0));
+  u64 free_ = ~occ[w] & ~unk[w] & valid;
+  if (free_ == 0ull) return 0ull;
+  u64 nb = (plane_window(unk, a0 + 1) & ~zl) | (plane_window(unk, a0 - 1) & ~z0) |
+           (plane_window(unk, a0 + g.nz) & ~yl) | (plane_window(unk, a0 - g.nz) & ~y0) |
+           plane_window(unk, a0 + g.nyz) | plane_window(unk, a0 - g.nyz);
+  return free_ & nb;
+}
+// find with path halving for the long-lived structures of the fast chain (a few thousand tile roots hanging off
+// one giant component): the shortcut is an atomicMin, so a concurrent link is never overwritten by a larger value
+__device__ __forceinline__ u32 lds_find_h(u32* lab, u32 i) {
+  u32 p = reinterpret_cast<volatile u32*>(lab)[i];
+  while (p != i) {
+    const u32 gp = reinterpret_cast<volatile u32*>(lab)[p];
+    if (gp != p) atomicMin(&lab[i], gp);
+    i = p;
+    p = gp;
+  }
+  return i;
+}
+__device__ __forceinline__ void lds_union_h(u32* lab, u32 a, u32 b) {
+  while (true) {
+    a = lds_find_h(lab, a);
+    b = lds_find_h(lab, b);
+    if (a == b) return;
+    if (a < b) {
+      u32 t = a;
+      a = b;
+      b = t;
+    }
+    u32 old = atomicMin(&lab[a], b);
+    if (old == a) return;
+    a = old;
+  }
 }
 #endif
 
@@ -457,11 +502,86 @@ static inline int frontier_cells_ready(const fuelmi_frontier* f) {
       return FUELMI_EINVAL;                                                                    \
     }                                                                                          \
   } while (0)
+// a finder whose map was destroyed first (garbage collectors and destructor orders do that) only accepts _destroy
+#define FRONTIER_HAS_MAP(f)                                                                        \
+  do {                                                                                             \
+    if (!(f)->map) {                                                                               \
+      fuelmi_set_error("the map of this frontier finder has been destroyed: only fuelmi_frontier_destroy is legal"); \
+      return FUELMI_EINVAL;                                                                        \
+    }                                                                                              \
+  } while (0)
+// FUELMI_DEBUG_SYNC=1: synchronise and name every frontier kernel (locates device faults)
+#define FDBG(name)                                                                     \
+  do {                                                                                 \
+    static const bool on__ = getenv("FUELMI_DEBUG_SYNC") != nullptr;                   \
+    if (on__) {                                                                        \
+      hipError_t e__ = hipStreamSynchronize(f->stream);                                \
+      std::fprintf(stderr, "[fuelmi] %s: %s\n", name, hipGetErrorString(e__));         \
+    }                                                                                  \
+  } while (0)
+static inline int fblocks(long n, int t, int cap = 1 << 16) {
+  long b = (n + t - 1) / t;
+  return (int)std::max(1L, std::min((long)cap, b));
+}
+
+// FUELMI_HOST_TIMING: where the host's time inside _search_begin / _search_end goes (mean microseconds per call, printed
+// by fuelmi_bench_cycles)
+struct HostTiming {
+  bool on = getenv("FUELMI_HOST_TIMING") != nullptr;
+  double acc[16] = {0};
+  long n = 0;
+  std::chrono::steady_clock::time_point t;
+  void start() {
+    if (on) t = std::chrono::steady_clock::now(), ++n;
+  }
+  void lap(int k) {
+    if (!on) return;
+    const auto now = std::chrono::steady_clock::now();
+    acc[k] += std::chrono::duration<double, std::micro>(now - t).count();
+    t = now;
+  }
+  void report() {
+    if (!on || !n) return;
+    static const char* names[16] = {"b:lists+reset", "b:box+wait+scope", "b:rm_begin", "b:region", "b:launch ccl", "b:events", "b:launch cross",
+                                    "b:launch resolve", "b:launch out", "b:finish_reset", "e:pre-poll", "e:poll", "e:post-poll", "", "", ""};
+    std::fprintf(stderr, "[host-timing] per search:");
+    for (int k = 0; k < 13; ++k) std::fprintf(stderr, " %s %.2f", names[k], acc[k] / (double)n);
+    std::fprintf(stderr, "\n");
+    for (double& a : acc) a = 0;
+    n = 0;
+  }
+};
+
+// ---- host entry points that cross the finder's files (library-internal: not exported from libfuelmi.so) ----
+#pragma GCC visibility push(hidden)
+extern HostTiming g_ht;  // (frontier.hip)
+// frontier.hip
+int frontier_ensure_stage(fuelmi_frontier* f, size_t bytes);  // device staging buffer of at least `bytes`
+hipError_t frontier_drain(const fuelmi_frontier* f);            // both streams of the finder
+int frontier_fetch_cluster(const fuelmi_frontier* f, const HCluster* c);  // host list of a pool-only cluster
+int frontier_apply_reset(fuelmi_frontier* f, bool defer_zeroing = false); // executes a pending fuelmi_frontier_reset
+// frontier_changed.hip: the changed-cluster test, queued by _search_begin and applied by _search_end
+int remove_changed_begin(fuelmi_frontier* f, const double* umin, const double* umax);
+void remove_changed_end(fuelmi_frontier* f);
+// frontier_legacy.hip
+int frontier_enqueue_chain(fuelmi_frontier* f, int npass);  // the legacy chain of one search, direct launches
+int frontier_launch_legacy(fuelmi_frontier* f, int npass);  // ... as _search_begin queues it (hipGraph replay)
+int frontier_second_pass(fuelmi_frontier* f);               // the high-digit multisplit pass a search turned out to need
+int frontier_legacy_attrs(fuelmi_frontier* f);              // k_ccl_local's dynamic LDS ceiling (fuelmi_frontier_create)
+// frontier_tile.hip
+size_t frontier_tile_lds(fuelmi_frontier* f, int qx, int qy);  // per-menu LDS sizes; returns the segment words
+int frontier_tile_attrs(fuelmi_frontier* f);                    // dynamic LDS ceilings of the tile kernels, resolve_lds
+bool frontier_tile_fits(const fuelmi_frontier* f);              // the menu's largest tile fits the tile kernels
+int menu_tiles(int qx, int qy, int mk);
+void set_fast_tiles(FVar& hv, int mk);
+int frontier_enqueue_fast(fuelmi_frontier* f);
+int frontier_enqueue_late_resolve(fuelmi_frontier* f);  // k_resolve + k_tile_out of a search that outgrew its launch
+#pragma GCC visibility pop
 
 
 // runs the stable radix multisplit of F2.ms_key[0]/ms_val[0] (F2.counts[0] items, F2.counts[3] keys,
 // key records F2.krec already laid out), the per-cluster accumulators and the copy-out to the pinned
-// host buffers of F2, on f->stream (defined in frontier.hip; used by the split stage with its own
+// host buffers of F2, on f->stream (defined in frontier_legacy.hip; used by the split stage with its own
 // argument block)
 int frontier_regroup(fuelmi_frontier* f, const FArgs& F2, int npass);
 // splitLargeFrontiers on the device (frontier_split.hip)
