@@ -990,6 +990,11 @@ extern "C" int fuelmi_frontier_stats(const fuelmi_frontier* f, int out3[3]) {
   out3[0] = f->n_fast, out3[1] = f->n_legacy, out3[2] = f->n_fallback;
   return FUELMI_OK;
 }
+extern "C" int fuelmi_frontier_path_stats(const fuelmi_frontier* f, int out2[2]) {
+  ARGCHK(f && out2);
+  out2[0] = f->n_late_resolve, out2[1] = f->n_retiled;
+  return FUELMI_OK;
+}
 extern "C" int fuelmi_frontier_order_stats(const fuelmi_frontier* f, int out4[4]) {
   ARGCHK(f && out4);
   out4[0] = f->order_last, out4[1] = f->n_order_ref, out4[2] = f->n_order_fallback, out4[3] = (int)f->order_fallback_cells;

@@ -863,7 +863,7 @@ __global__ void __launch_bounds__(NT) k_tile_cross(Geo g, FArgs F, const u32 rca
     if (!s_last) return;
     const bool no_kr = (rcap >> 31) != 0u;  // no k_resolve is queued behind this launch (the host expected this search to fit)
     if (resolve_body<NT, true>(g, F, V, smem_raw, rcap & 0x7FFFFFFFu) || !no_kr) return;
-    // more tile roots than this launch's LDS holds and nobody behind to do the job: tell the host (it queues k_resolve and
+    // more tile roots (or clusters) than this launch's LDS holds and nobody behind to do the job: tell the host (it queues k_resolve and
     // k_tile_out again and waits for the stamp a second time) and make the k_tile_out already queued return at once
     if (threadIdx.x == 0) {
       F.counts[2] = 3u;
@@ -901,8 +901,8 @@ static inline size_t resolve_lds_bytes(size_t rcap) {
 // k_tile_cross holds when its last workgroup does the job).  IN_LAUNCH: pairs, claims and overflow codes were written
 // by other workgroups of the SAME launch (agent-scope stores / memory-side atomics): they are read with agent-scope
 // loads, past this XCD's L2 (the records are the previous kernel's and would be visible anyway; they take the same
-// path).  Returns false when the search has more tile roots than rcap (nothing written: the kernel k_resolve, always
-// queued behind, does the work).
+// path).  Returns false when the search has more tile roots than rcap or (IN_LAUNCH) more (kept cluster x tile column)
+// matrix entries than 2 rcap (nothing written: the kernel k_resolve, queued behind or by the host, does the work).
 template <int RS_T, bool IN_LAUNCH>
 __device__ __forceinline__ bool resolve_body(const Geo& g, const FArgs& F, const FVar& V, unsigned char* smem_raw, const u32 rcap) {
   auto ldw = [&](const u32* p) -> u32 { return IN_LAUNCH ? ld_agent(p) : *p; };
@@ -1110,8 +1110,12 @@ __device__ __forceinline__ bool resolve_body(const Geo& g, const FArgs& F, const
   FR_DBG_MARK(F, dblk, 5);
   const u32 nk = min(s_nk, (u32)FR_KCAP);
   const u32 nq = s_nq;
-  // (the matrix needs nk * ntx LDS words; beyond that -- hundreds of clusters on a huge map -- the legacy chain)
-  const bool bad = dead || s_ovf != 0u || (size_t)nk * (size_t)ntx > 2 * (size_t)rcap || ntx > F.pm_stride;
+  // (the matrix needs nk * ntx LDS words, 2 rcap of which fit.  In the launch, a search with more -- 43 clusters on a
+  // full G400 box with its 48 tile columns -- is left to the kernel k_resolve like one with too many tile roots: only LDS
+  // has been written so far, and nk comes from LDS behind a barrier (uniform).  k_resolve holds 2 FR_RCAP = FR_PMCAP
+  // entries; beyond that -- hundreds of clusters on a huge map -- the legacy chain)
+  if (IN_LAUNCH && !dead && s_ovf == 0u && (size_t)nk * (size_t)ntx > 2 * (size_t)rcap) return false;
+  const bool bad =dead || s_ovf != 0u || (size_t)nk * (size_t)ntx > 2 * (size_t)rcap || ntx > F.pm_stride;
   if (!bad) {
     // ---- creation order = ascending claimer address; offsets of the grouped cell array ----
     if (threadIdx.x < nk) {

@@ -391,6 +391,13 @@ class FrontierFinder:
         """fast-chain searches resolved by the last workgroup of k_tile_cross itself (the others: by k_resolve)"""
         return self.L.fuelmi_frontier_resolved_in_launch(self.h)
 
+    def pathStats(self):
+        """(fast-chain searches that outgrew the in-launch resolve with no k_resolve queued behind it -- the late
+        resolve --, fast-chain searches run again on a smaller tile)"""
+        o = (C.c_int * 2)()
+        check(self.L.fuelmi_frontier_path_stats(self.h, o))
+        return tuple(o)
+
     def orderStats(self):
         """(order of the last search: 0 address / 1 reference BFS, searches in the reference's order, mode-2 searches
         that fell back to the address order, cells of the cluster that forced the last fallback)"""

@@ -245,6 +245,10 @@ int fuelmi_frontier_stats(const fuelmi_frontier* f, int out3[3]);
  * caller polls for) by the last workgroup of the chain's second kernel itself rather than by a launch of their own --
  * searches of up to 1 024 tile-local components; for tests that must know which code ran */
 int fuelmi_frontier_resolved_in_launch(const fuelmi_frontier* f);
+/* of the searches the fast chain answered: [0] how many outgrew the launch that was to resolve them with no resolve
+ * launch queued behind it (the library queued one after the chain had reported), [1] how many ran the chain again on
+ * a smaller tile after a per-tile capacity overflow; for tests that must know which code ran */
+int fuelmi_frontier_path_stats(const fuelmi_frontier* f, int out2[2]);
 /* the cell order the searches delivered (cfg.reference_order is a request; mode 2 answers per search): [0] the last
  * search's order -- 0 ascending address, 1 the reference's BFS order --, [1] searches that delivered the reference's
  * order, [2] searches of a mode-2 finder that fell back to the address order because a cluster was too large for the

@@ -70,3 +70,113 @@ def bspline_inputs(ctrl, dt, mintime=True):
         end[c, 1] = 0.1
         end[c, 2] = 0.0
     return np.ascontiguousarray(x), pt_dist, start, end
+
+
+# ---- a G400-geometry map whose number of kept frontier clusters is chosen (test_frontier_capacity_*) ----
+# 40 x 40 x 10 m at 0.1 m, bench.exploration_box; everything known free except isolated unknown blocks, each of which
+# leaves one frontier cluster of a known size.  Blocks are placed against the tiles of the fast chain's full-box search.
+CAP_MAP = (40.0, 40.0, 10.0)
+CAP_CUBE = 5                    # side of a cube: its six faces are one 26-connected shell of 6 * 5 * 5 cells
+CUBE_SHELL = 6 * CAP_CUBE ** 2  # (150 > cluster_min = 100)
+CAP_SLAB = (8, 13, 5)           # a slab above the box's top face: its underside + the NQ seed that claims it
+SLAB_SHELL = CAP_SLAB[0] * CAP_SLAB[1] + 1
+CAP_SWEEP = (8, 32, 42, 43, 64, 128, 255, 256, 257)  # kept-cluster counts test_frontier_capacity_gpu runs
+_FAST_MENU = ((16, 32), (8, 32), (8, 16), (4, 8))  # frontier_tile.hip kFastMenu: (x-rows, y-lines) per tile
+
+
+def capacity_map():
+    """Oracle map of the fixture's geometry; its occupancy is left to capacity_occupancy."""
+    import bench
+    return fo.OracleMap(CAP_MAP, *bench.exploration_box(CAP_MAP))
+
+
+def capacity_tiles(om):
+    """(x0, y0, TX, TY, ntx) of the fast chain's tiles for a search whose updated box is the whole exploration box, as
+    fuelmi_frontier_search_begin derives them: the scan box (updated box +- (1, 1) m clipped to the exploration box,
+    as indices) joined with the Q box (min <= id < max) and cut to [Q lo, Q hi + 1]; the first menu tile that leaves
+    at least 512 tiles."""
+    blo, bhi = om.box_index()
+    p0, p1 = [], []
+    for k in range(2):
+        s_lo = int(np.floor((max(om.cfg.box_min[k] - 1.0, om.cfg.box_min[k]) - om.origin[k]) / om.res + 1e-9))
+        s_hi = int(np.floor((min(om.cfg.box_max[k] + 1.0, om.cfg.box_max[k]) - om.origin[k]) / om.res + 1e-9))
+        q_lo, q_hi = max(blo[k], 0), min(bhi[k] - 1, om.nvox[k] - 1)
+        p0.append(max(min(s_lo, q_lo), q_lo))
+        p1.append(min(max(s_hi, q_hi), q_hi + 1))
+    qx, qy = p1[0] - p0[0] + 1, p1[1] - p0[1] + 1
+    tiles = lambda t: -(-qx // t[0]) * -(-qy // t[1])  # noqa: E731
+    tx, ty = next((t for t in _FAST_MENU if tiles(t) >= 512), _FAST_MENU[-1])
+    return p0[0], p0[1], tx, ty, -(-qx // tx)
+
+
+def capacity_layout(om, n, faces=True, slabs=False, seed=3):
+    """n unknown blocks [(lo, hi)] (index boxes, hi exclusive) whose frontier shells are n separate clusters, and the
+    straddle counts the layout was planned with: {"x": crosses an x tile boundary only, "y": a y boundary only,
+    "corner": both (the shell lies in four tiles), "none"}.
+
+    slabs=False: cubes of side CAP_CUBE (shell CUBE_SHELL, claimed by one of their own cells) on two z layers, three of
+    every four across tile boundaries in the order corner, x, y, none; faces=True puts six of them against the
+    exploration box: its x / y low faces (the face outside the box is not a frontier), x / y / z high faces (frontier
+    cells one voxel outside the box: NQ seeds that stay one-cell clusters) and one slab above the top face (a cluster an
+    NQ seed claims, SLAB_SHELL cells).  slabs=True: n slabs only, inside one tile each (every shell SLAB_SHELL, every
+    cluster seed-claimed).  Blocks are >= 8 voxels apart: shells never touch."""
+    x0, y0, TX, TY, _ = capacity_tiles(om)
+    blo, bhi = om.box_index()
+    assert (TX, TY) == (8, 32), "the layout below is drawn for 8 x 32 tiles"
+    C = CAP_CUBE
+    blocks, plan = [], {"x": 0, "y": 0, "corner": 0, "none": 0}
+    sx, sy, sz = CAP_SLAB
+    if slabs:
+        for k in range(n):  # one per tile: x rows 1..8 of every fourth tile column, y lines 5..17 of a tile row
+            i, j = k % 11, k // 11
+            lo = (x0 + TX * (4 * i + 1), y0 + TY * (j + 1) + 5, bhi[2])
+            blocks.append((lo, (lo[0] + sx, lo[1] + sy, lo[2] + sz)))
+            plan["x"] += 1  # (the seeds either side of the slab lie in the tiles either side of its own)
+        assert blocks[-1][1][1] < bhi[1] - 1
+        return blocks, plan
+    if faces:
+        zf = 68
+        for lo, size, cat in (((blo[0], y0 + TY * 3 + 10, zf), (C, C, C), "none"),            # x low face
+                              ((x0 + TX * 17 + 1, blo[1], zf), (C, C, C), "none"),            # y low face
+                              ((bhi[0] - 4, y0 + TY * 6 + 5, zf), (4, C, C), "x"),            # x high face
+                              ((x0 + TX * 30 + 1, bhi[1] - C, zf), (C, C, C), "none"),        # y high face
+                              ((x0 + TX * 14 + 1, y0 + TY * 9 + 1, bhi[2] - C), (C, C, C), "none"),  # z high face
+                              ((x0 + TX * 36, y0 + TY * 9 + 1, bhi[2]), (sx, sy, sz), "x")):  # above the box
+            blocks.append((lo, tuple(lo[q] + size[q] for q in range(3))))
+            plan[cat] += 1
+    # grid slots: x slot i around the boundary of tile columns 2 i + 1 / 2 i + 2, y slot j (even: across the boundary
+    # of tile rows j / 2, j / 2 + 1; odd: inside tile row j / 2 + 1), z layers 30 and 50 (faces: 68 and above)
+    bxs = [x0 + TX * (2 * i + 1) for i in range(23)]
+    bys = [y0 + TY * (j // 2 + 1) for j in range(22)]
+    slots = [(i, j, z) for i in range(23) for j in range(22) for z in (30, 50)]
+    order = np.random.default_rng(seed).permutation(len(slots))
+    used = np.zeros(len(slots), dtype=bool)
+    for k in range(n - len(blocks)):
+        cat = ("corner", "x", "y", "none")[k % 4]
+        ystr = cat in ("corner", "y")
+        s = next(s for s in order if not used[s] and (slots[s][1] % 2 == 0) == ystr)
+        used[s] = True
+        i, j, z = slots[s]
+        xl = bxs[i] - 2 if cat in ("corner", "x") else bxs[i] + 1
+        yl = bys[j] - 2 if ystr else bys[j] + 14
+        blocks.append(((xl, yl, z), (xl + C, yl + C, z + C)))
+        plan[cat] += 1
+    return blocks, plan
+
+
+def capacity_occupancy(om, blocks):
+    """log-odds of the fixture: known free (l_min) everywhere, unknown (l_min - 0.01) in the blocks"""
+    o3 = np.full(om.nvox, om.l_min)
+    for lo, hi in blocks:
+        o3[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]] = om.l_min - 0.01
+    return o3.reshape(-1)
+
+
+def block_straddle(om, lo, hi):
+    """which tile boundaries of the full-box search the frontier shell of block [lo, hi) crosses (the voxels one step
+    outside the block, inside the tiles' rectangle): "x", "y", "corner" or "none" -- from the tile origin alone"""
+    x0, y0, TX, TY, ntx = capacity_tiles(om)
+    blo, bhi = om.box_index()
+    span = lambda k, t0, T: (max(lo[k] - 1, blo[k]) - t0) // T != (min(hi[k], bhi[k]) - t0) // T  # noqa: E731
+    cx, cy = span(0, x0, TX), span(1, y0, TY)
+    return "corner" if cx and cy else ("x" if cx else ("y" if cy else "none"))

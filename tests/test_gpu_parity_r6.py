@@ -166,6 +166,7 @@ def test_search_that_outgrows_the_in_launch_resolve(fa):
             assert gf.resolvedInLaunch() == 2, "the first two searches were expected to be resolved inside k_tile_cross"
     assert gf.stats() == (3, 0, 0), gf.stats()
     assert gf.resolvedInLaunch() == 2, "the last search was expected to outgrow the launch (k_resolve queued by _search_end)"
+    assert gf.pathStats() == (1, 0), "one late resolve (k_resolve + k_tile_out queued by _search_end) was expected: %s" % (gf.pathStats(),)
     gf.close()
     gm.close()
 
