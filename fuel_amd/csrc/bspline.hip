@@ -1126,6 +1126,69 @@ extern "C" int fuelmi_bspline_dev_collect(fuelmi_bspline_dev* b, int slot, doubl
   return FUELMI_OK;
 }
 
+// Which solve kernel a batch runs, with its dynamic LDS; shared by the batch (_dev_optimize_timed) and the query-slot
+// (fuelmi_bspline_optimize) paths.  npl 2 / 4: k_bspline_optimize_r<npl, waves> (register state, n <= 64 * npl);
+// npl 0: k_bspline_optimize (state in LDS, n > 256).  Four waves per candidate shorten ONE solve (the objective's terms
+// side by side); a batch that fills the device by itself (more candidates than CUs) is faster with one wave each:
+// 1 024 solves 2.5 ms against 7.9.  dim 2 is refused: the reference sets up its start point and bounds
+// (bspline_optimizer.cpp:194-214) for dim 1 or 3 only.
+struct OptPlan {
+  int npl, waves;
+  size_t lds;
+};
+static int bspline_opt_plan(const BsplineArgs& A, OptPlan& p) {
+  if (A.dim == 2) {
+    fuelmi_set_error("the B-spline optimiser takes dim 1 or 3, not 2");
+    return FUELMI_EINVAL;
+  }
+  const size_t n = (size_t)A.nvar;
+  const size_t lds_eval = ((size_t)A.N * 3 * 5 + EVAL_CONST) * sizeof(double);
+  p.npl = n <= 128 ? 2 : (n <= 256 ? 4 : 0);
+  p.waves = (p.npl && A.C <= 256) ? 4 : 1;
+  p.lds = p.npl ? lds_eval + ((size_t)A.N * 12 + 8) * sizeof(double) + 2 * n * sizeof(double)
+                : lds_eval + ((6 + 2 * LBFGS_MEM) * n + 2 * LBFGS_MEM) * sizeof(double);
+  if (p.lds > 160 * 1024) {
+    fuelmi_set_error("%d variables exceed the LDS budget of the device optimiser", (int)n);
+    return FUELMI_ELIMIT;
+  }
+  return FUELMI_OK;
+}
+// launches the planned kernel.  The LDS kernel's attribute is set to the whole 160 KiB budget (as for
+// k_bspline_cost_grad), never to one batch's size, so no caller can lower it under another's launch.
+static int bspline_opt_launch(const OptPlan& p, hipStream_t st, const Geo& g, const float* dist, const BsplineArgs& A,
+                              const LbfgsArgs& L) {
+  if (p.npl == 0 && p.lds > 64 * 1024)
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bspline_optimize),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  if (p.npl == 2 && p.waves == 4)
+    k_bspline_optimize_r<2, 4><<<A.C, 256, p.lds, st>>>(g, dist, A, L);
+  else if (p.npl == 4 && p.waves == 4)
+    k_bspline_optimize_r<4, 4><<<A.C, 256, p.lds, st>>>(g, dist, A, L);
+  else if (p.npl == 2)
+    k_bspline_optimize_r<2, 1><<<A.C, 64, p.lds, st>>>(g, dist, A, L);
+  else if (p.npl == 4)
+    k_bspline_optimize_r<4, 1><<<A.C, 64, p.lds, st>>>(g, dist, A, L);
+  else
+    k_bspline_optimize<<<A.C, 64, p.lds, st>>>(g, dist, A, L);
+  HIPCHK(hipGetLastError());
+  return FUELMI_OK;
+}
+
+extern "C" int fuelmi_bspline_opt_plan(const fuelmi_bspline_batch* batch, int out3[3]) {
+  ARGCHK(batch && out3);
+  fuelmi_bspline_cfg cfg;  // (the plan depends on the batch's shape only)
+  memset(&cfg, 0, sizeof(cfg));
+  cfg.bspline_degree = 3;
+  BsplineArgs A;
+  const int rca = bspline_args_init(&cfg, batch, A);
+  if (rca) return rca;
+  OptPlan p;
+  const int rc = bspline_opt_plan(A, p);
+  if (rc) return rc;
+  out3[0] = p.npl, out3[1] = p.waves, out3[2] = (int)p.lds;
+  return FUELMI_OK;
+}
+
 // whole solves on the device; synchronous: returns the best variables, their cost and the number of
 // objective evaluations per candidate
 extern "C" int fuelmi_bspline_dev_optimize(fuelmi_bspline_dev* b, int max_eval, double* x_out, double* cost_out,
@@ -1139,18 +1202,13 @@ extern "C" int fuelmi_bspline_dev_optimize_timed(fuelmi_bspline_dev* b, int max_
   HIPCHK(hipSetDevice(m->device));
   const BsplineArgs& A = b->a;
   const size_t C = (size_t)A.C, n = (size_t)A.nvar;
-  const int npl = n <= 128 ? 2 : (n <= 256 ? 4 : 0);  // register-state kernel up to 256 variables
-  const size_t lds_opt = npl ? b->lds_eval4 + 2 * n * sizeof(double)
-                             : b->lds + ((6 + 2 * LBFGS_MEM) * n + 2 * LBFGS_MEM) * sizeof(double);
-  if (lds_opt > 160 * 1024) {
-    fuelmi_set_error("%d variables exceed the LDS budget of the device optimiser", (int)n);
-    return FUELMI_ELIMIT;
+  OptPlan plan;
+  {
+    const int rcp = bspline_opt_plan(A, plan);
+    if (rcp) return rcp;
   }
   if (!b->opt_x) {
     void* d = nullptr;
-    if (lds_opt > 64 * 1024)
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bspline_optimize),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_opt));
     HIPCHK(hipMalloc(&d, C * n * sizeof(double)));
     b->allocs.push_back(d);
     b->opt_x = (double*)d;
@@ -1171,20 +1229,8 @@ extern "C" int fuelmi_bspline_dev_optimize_timed(fuelmi_bspline_dev* b, int max_
   L.x_out = b->opt_x, L.cost_out = b->opt_cost, L.evals_out = b->opt_evals;
   {
     StageScope sc(m, FUELMI_K_BSPLINE);
-    // four waves per candidate shorten ONE solve (the objective's terms side by side); a batch that fills the device
-    // by itself (more candidates than CUs) is faster with one wave each: 1 024 solves 2.5 ms against 7.9
-    const bool wide = A.C <= 256;
-    if (npl == 2 && wide)
-      k_bspline_optimize_r<2, 4><<<A.C, 256, lds_opt, m->stream>>>(m->g, m->dist, A, L);
-    else if (npl == 4 && wide)
-      k_bspline_optimize_r<4, 4><<<A.C, 256, lds_opt, m->stream>>>(m->g, m->dist, A, L);
-    else if (npl == 2)
-      k_bspline_optimize_r<2, 1><<<A.C, 64, lds_opt, m->stream>>>(m->g, m->dist, A, L);
-    else if (npl == 4)
-      k_bspline_optimize_r<4, 1><<<A.C, 64, lds_opt, m->stream>>>(m->g, m->dist, A, L);
-    else
-      k_bspline_optimize<<<A.C, 64, lds_opt, m->stream>>>(m->g, m->dist, A, L);
-    HIPCHK(hipGetLastError());
+    const int rcl = bspline_opt_launch(plan, m->stream, m->g, m->dist, A, L);
+    if (rcl) return rcl;
   }
   HIPCHK(hipMemcpyAsync(x_out, b->opt_x, C * n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
   HIPCHK(hipMemcpyAsync(cost_out, b->opt_cost, C * sizeof(double), hipMemcpyDeviceToHost, m->stream));
@@ -1247,6 +1293,11 @@ static int bspline_oneshot(fuelmi_map* m, const fuelmi_bspline_cfg* cfg, const f
   const size_t out_bytes = ((C * sizeof(double) + 15) & ~(size_t)15) + ((C * n * sizeof(double) + 15) & ~(size_t)15) +
                            ((C * sizeof(int) + 15) & ~(size_t)15);
   const size_t lds_eval = ((size_t)A.N * 3 * 5 + EVAL_CONST) * sizeof(double);
+  OptPlan plan;
+  if (max_eval > 0) {
+    const int rcp = bspline_opt_plan(A, plan);
+    if (rcp) return rcp;
+  }
   QuerySlotGuard q;
   {
     const int rcq = q.acquire(m, in_bytes + out_bytes);
@@ -1275,16 +1326,6 @@ static int bspline_oneshot(fuelmi_map* m, const fuelmi_bspline_cfg* cfg, const f
     A.cost = o_a, A.grad = o_b;
     k_bspline_cost_grad<<<A.C, 256, lds4, q.s->st>>>(m->g, m->dist, A);
   } else {
-    const int npl = n <= 128 ? 2 : (n <= 256 ? 4 : 0);
-    const size_t lds_opt = npl ? lds_eval + ((size_t)A.N * 12 + 8) * sizeof(double) + 2 * n * sizeof(double)
-                               : lds_eval + ((6 + 2 * LBFGS_MEM) * n + 2 * LBFGS_MEM) * sizeof(double);
-    if (lds_opt > 160 * 1024) {
-      fuelmi_set_error("%d variables exceed the LDS budget of the device optimiser", (int)n);
-      return FUELMI_ELIMIT;
-    }
-    if (lds_opt > 64 * 1024 && !npl)
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bspline_optimize), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)lds_opt));
     LbfgsArgs L;
     L.max_eval = max_eval;
     L.max_ticks = max_time_s > 0.0 ? (unsigned long long)(max_time_s * 1e8) + 1ull : 0ull;
@@ -1293,17 +1334,8 @@ static int bspline_oneshot(fuelmi_map* m, const fuelmi_bspline_cfg* cfg, const f
       L.box_hi[k] = m->cfg.box_max[k] - 0.1;
     }
     L.x_out = o_b, L.cost_out = o_a, L.evals_out = o_e;
-    const bool wide = A.C <= 256;
-    if (npl == 2 && wide)
-      k_bspline_optimize_r<2, 4><<<A.C, 256, lds_opt, q.s->st>>>(m->g, m->dist, A, L);
-    else if (npl == 4 && wide)
-      k_bspline_optimize_r<4, 4><<<A.C, 256, lds_opt, q.s->st>>>(m->g, m->dist, A, L);
-    else if (npl == 2)
-      k_bspline_optimize_r<2, 1><<<A.C, 64, lds_opt, q.s->st>>>(m->g, m->dist, A, L);
-    else if (npl == 4)
-      k_bspline_optimize_r<4, 1><<<A.C, 64, lds_opt, q.s->st>>>(m->g, m->dist, A, L);
-    else
-      k_bspline_optimize<<<A.C, 64, lds_opt, q.s->st>>>(m->g, m->dist, A, L);
+    const int rcl = bspline_opt_launch(plan, q.s->st, m->g, m->dist, A, L);
+    if (rcl) return rcl;
   }
   HIPCHK(hipGetLastError());
   HIPCHK(q.finish());

@@ -604,6 +604,15 @@ class BsplineOptimizer:
     def deviceProblem(self, problem):
         return BsplineDeviceProblem(self, problem)
 
+    @staticmethod
+    def optPlan(problem):
+        """Which solve kernel optimize() and deviceProblem().optimize() run for `problem` (fuelmi_bspline_opt_plan, host
+        only): (npl, waves per candidate, dynamic LDS bytes); npl 0 is the LDS-state kernel.  Raises FuelmiError for a
+        batch neither call would take."""
+        out = (C.c_int * 3)()
+        check(lib().fuelmi_bspline_opt_plan(C.byref(problem.c), out))
+        return tuple(out)
+
 
 class NonUniformBspline:
     """The two NonUniformBspline calls the planners wrap around optimize() (bspline/src/non_uniform_bspline.cpp),

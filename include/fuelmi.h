@@ -418,6 +418,11 @@ int fuelmi_bspline_dev_optimize(fuelmi_bspline_dev* b, int max_eval, double* x_o
  * like costFunction keeps them (:693-707).  max_time_s <= 0: no cap. */
 int fuelmi_bspline_dev_optimize_timed(fuelmi_bspline_dev* b, int max_eval, double max_time_s, double* x_out,
                                       double* cost_out, int* evals_out);
+/* which solve kernel both optimise calls run for this batch (host only, no device needed): out3 = {npl, waves per
+ * candidate, dynamic LDS bytes}.  npl 2 / 4: register state (nvar <= 128 / 256), 4 waves when n_traj <= 256, else 1;
+ * npl 0: state in LDS (nvar > 256).  FUELMI_ELIMIT past the 160 KiB LDS budget, FUELMI_EINVAL for dim 2 (both
+ * optimise calls refuse the batch the same way). */
+int fuelmi_bspline_opt_plan(const fuelmi_bspline_batch* batch, int out3[3]);
 void fuelmi_bspline_dev_destroy(fuelmi_bspline_dev* b);
 
 /* Spline glue around the solve, batched (NonUniformBspline, bspline/src/non_uniform_bspline.cpp).
