@@ -83,6 +83,12 @@ class ViewpointCfg(C.Structure):
                 ("right_angle", C.c_double), ("max_dist", C.c_double)]
 
 
+class PathCfg(C.Structure):
+    """fuelmi_path_cfg: ViewNode::searchPath's lattice (graph_node.cpp:49-60, astar2.cpp:105)."""
+    _fields_ = [("lattice_res", C.c_double), ("edge_step", C.c_double), ("no_path_cost", C.c_double),
+                ("max_path_points", C.c_int)]
+
+
 class BsplineCfg(C.Structure):
     _fields_ = [(n, C.c_double) for n in
                 ("ld_smooth", "ld_dist", "ld_feasi", "ld_start", "ld_end", "ld_guide", "ld_waypt",
@@ -183,6 +189,8 @@ SYMBOLS = {
     "fuelmi_frontier_removed_count": (C.c_int, [_P]),
     "fuelmi_frontier_removed_ids": (C.c_int, [_P, _ip]),
     "fuelmi_frontier_get_flags": (C.c_int, [_P, C.c_void_p]),
+    "fuelmi_map_path_costs": (C.c_int, [_P, C.POINTER(PathCfg), C.c_int, _dp, _dp, _dp, _ip, _ip, _dp]),
+    "fuelmi_map_path_stats": (C.c_int, [_P, _ip]),
     "fuelmi_bspline_cost_grad": (C.c_int, [_P, C.POINTER(BsplineCfg), C.POINTER(BsplineBatch), _dp, _dp]),
     "fuelmi_bspline_optimize": (C.c_int, [_P, C.POINTER(BsplineCfg), C.POINTER(BsplineBatch), C.c_int, C.c_double, _dp, _dp,
                                 C.POINTER(C.c_int)]),

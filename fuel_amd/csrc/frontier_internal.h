@@ -592,4 +592,75 @@ int frontier_regroup(fuelmi_frontier* f, const FArgs& F2, int npass);
 int frontier_split_run(fuelmi_frontier* f, u32 nq, u32 nkept, u32 n_out, int fin, u32* n_final, u32* n_cells,
                        std::vector<std::vector<float>>* filtered);
 
+
+// ---- voxel walks shared by the viewpoint scoring (frontier_view.hip) and the path costs (path_cost.hip) ----------
+#ifdef __HIPCC__
+__device__ __forceinline__ bool idx_in_map(const Geo& g, const int id[3]) {
+  return !(id[0] < 0 || id[1] < 0 || id[2] < 0 || id[0] > g.nx - 1 || id[1] > g.ny - 1 || id[2] > g.nz - 1);
+}
+__device__ __forceinline__ void pos_to_idx(const Geo& g, const double p[3], int id[3]) {
+  for (int k = 0; k < 3; ++k) id[k] = (int)floor((p[k] - g.org[k]) * g.res_inv);
+}
+__device__ __forceinline__ bool bit_at(const u64* pl, long a) { return (pl[a >> 6] >> (a & 63)) & 1ull; }
+
+// RayCaster::input + nextId loop (plan_env/src/raycast.cpp:374-407): true iff no visited voxel is inflated or
+// unknown; the walk starts in start's voxel and stops before end's voxel.  kBox: a voxel outside the index box
+// bmin <= id < bmax (SDFMap::isInBox(Vector3i)) also ends the walk unsafe -- ViewNode::searchPath's test
+// (graph_node.cpp:37-42); without it (countVisibleCells, frontier_finder.cpp:741-751) voxels outside the map pass.
+template <bool kBox>
+__device__ bool ray_clear(const Geo& g, const u64* infl, const u64* unk, const int* bmin, const int* bmax,
+                          const double start[3], const double end[3]) {
+  int c[3], ec[3], st[3];
+  double tmax[3], tdel[3];
+  for (int k = 0; k < 3; ++k) {
+    const double s = start[k] / g.res, e = end[k] / g.res;
+    c[k] = (int)floor(s);
+    ec[k] = (int)floor(e);
+    const double d = ec[k] - c[k];
+    const int di = (int)d;
+    st[k] = di == 0 ? 0 : (di < 0 ? -1 : 1);
+    // intbound(s, d) (raycast.cpp:14-23)
+    double ss = s, ds = d;
+    if (ds < 0) {
+      ss = -ss;
+      ds = -ds;
+    }
+    ss = fmod(fmod(ss, 1.0) + 1.0, 1.0);
+    tmax[k] = (1 - ss) / ds;
+    tdel[k] = ((double)st[k]) / d;
+  }
+  const double off[3] = {0.5 - g.org[0] / g.res, 0.5 - g.org[1] / g.res, 0.5 - g.org[2] / g.res};
+  int guard = abs(ec[0] - c[0]) + abs(ec[1] - c[1]) + abs(ec[2] - c[2]) + 4;
+  while (true) {
+    const int id[3] = {(int)((double)c[0] + off[0]), (int)((double)c[1] + off[1]), (int)((double)c[2] + off[2])};
+    if (c[0] == ec[0] && c[1] == ec[1] && c[2] == ec[2]) return true;
+    if (kBox)
+      for (int k = 0; k < 3; ++k)
+        if (id[k] < bmin[k] || id[k] >= bmax[k]) return false;
+    if (idx_in_map(g, id)) {
+      const long a = (long)id[0] * g.nyz + (long)id[1] * g.nz + id[2];
+      if (bit_at(infl, a) || bit_at(unk, a)) return false;
+    }
+    if (tmax[0] < tmax[1]) {
+      if (tmax[0] < tmax[2]) {
+        c[0] += st[0];
+        tmax[0] += tdel[0];
+      } else {
+        c[2] += st[2];
+        tmax[2] += tdel[2];
+      }
+    } else {
+      if (tmax[1] < tmax[2]) {
+        c[1] += st[1];
+        tmax[1] += tdel[1];
+      } else {
+        c[2] += st[2];
+        tmax[2] += tdel[2];
+      }
+    }
+    if (--guard < 0) return true;  // (the reference has no guard; unreachable for finite inputs)
+  }
+}
+#endif  // __HIPCC__
+
 #endif

@@ -38,66 +38,6 @@ struct VArgs {
   double* out;        // [ncl*ns][5]: valid, x, y, yaw, visib
 };
 
-__device__ __forceinline__ bool idx_in_map(const Geo& g, const int id[3]) {
-  return !(id[0] < 0 || id[1] < 0 || id[2] < 0 || id[0] > g.nx - 1 || id[1] > g.ny - 1 || id[2] > g.nz - 1);
-}
-__device__ __forceinline__ void pos_to_idx(const Geo& g, const double p[3], int id[3]) {
-  for (int k = 0; k < 3; ++k) id[k] = (int)floor((p[k] - g.org[k]) * g.res_inv);
-}
-__device__ __forceinline__ bool bit_at(const u64* pl, long a) { return (pl[a >> 6] >> (a & 63)) & 1ull; }
-
-// RayCaster::input + nextId loop of countVisibleCells (:741-751): true iff no visited voxel is
-// inflated or unknown; the walk starts in the cell's voxel and stops before the candidate's voxel
-__device__ bool ray_clear(const Geo& g, const VArgs& V, const double start[3], const double end[3]) {
-  int c[3], ec[3], st[3];
-  double tmax[3], tdel[3];
-  for (int k = 0; k < 3; ++k) {
-    const double s = start[k] / g.res, e = end[k] / g.res;
-    c[k] = (int)floor(s);
-    ec[k] = (int)floor(e);
-    const double d = ec[k] - c[k];
-    const int di = (int)d;
-    st[k] = di == 0 ? 0 : (di < 0 ? -1 : 1);
-    // intbound(s, d) (raycast.cpp:14-23)
-    double ss = s, ds = d;
-    if (ds < 0) {
-      ss = -ss;
-      ds = -ds;
-    }
-    ss = fmod(fmod(ss, 1.0) + 1.0, 1.0);
-    tmax[k] = (1 - ss) / ds;
-    tdel[k] = ((double)st[k]) / d;
-  }
-  const double off[3] = {0.5 - g.org[0] / g.res, 0.5 - g.org[1] / g.res, 0.5 - g.org[2] / g.res};
-  int guard = abs(ec[0] - c[0]) + abs(ec[1] - c[1]) + abs(ec[2] - c[2]) + 4;
-  while (true) {
-    const int id[3] = {(int)((double)c[0] + off[0]), (int)((double)c[1] + off[1]), (int)((double)c[2] + off[2])};
-    if (c[0] == ec[0] && c[1] == ec[1] && c[2] == ec[2]) return true;
-    if (idx_in_map(g, id)) {
-      const long a = (long)id[0] * g.nyz + (long)id[1] * g.nz + id[2];
-      if (bit_at(V.infl, a) || bit_at(V.unk, a)) return false;
-    }
-    if (tmax[0] < tmax[1]) {
-      if (tmax[0] < tmax[2]) {
-        c[0] += st[0];
-        tmax[0] += tdel[0];
-      } else {
-        c[2] += st[2];
-        tmax[2] += tdel[2];
-      }
-    } else {
-      if (tmax[1] < tmax[2]) {
-        c[1] += st[1];
-        tmax[1] += tdel[1];
-      } else {
-        c[2] += st[2];
-        tmax[2] += tdel[2];
-      }
-    }
-    if (--guard < 0) return true;  // (the reference has no guard; unreachable for finite inputs)
-  }
-}
-
 __global__ void __launch_bounds__(64) k_vp_sample(Geo g, VArgs V) {
   const int job = blockIdx.x;
   const int c = job / V.ns, s = job - c * V.ns;
@@ -181,7 +121,7 @@ __global__ void __launch_bounds__(64) k_vp_sample(Geo g, VArgs V) {
         for (int k = 0; k < 4; ++k)
           if (d[0] * nw[k][0] + d[1] * nw[k][1] + d[2] * nw[k][2] < 0.0) in = false;
       }
-      if (in) vis = ray_clear(g, V, p, pos);
+      if (in) vis = ray_clear<false>(g, V.infl, V.unk, nullptr, nullptr, p, pos);
     }
     cnt += __popcll(__ballot(vis));
   }

@@ -215,6 +215,10 @@ struct fuelmi_map {
     bool* sticky;
   };
   std::vector<LateReader> late_readers;
+  // grow-only device scratch of fuelmi_map_path_costs (path_cost.hip)
+  void* path_dev = nullptr;
+  size_t path_dev_bytes = 0;
+  int path_stats[4] = {0, 0, 0, 0};  // fuelmi_map_path_stats
   unsigned long long fusion_count = 0;  // fusions / uploads queued so far (a search notices one queued behind its back)
   unsigned profile_mask = 0;
   ProfileSlot prof[FUELMI_K_COUNT];
@@ -491,5 +495,6 @@ __device__ __forceinline__ double dist_with_grad_dev(const Geo& g, const float* 
 // ---- kernels' host launchers (defined in the .hip files) ---------------------------------------
 int esdf_update(fuelmi_map* m);
 int insert_points(fuelmi_map* m, const float* xyz, int stride_bytes, int n, const double cam[3]);
+void path_cost_release(fuelmi_map* m);
 
 #endif

@@ -4,9 +4,12 @@
 // Behind the same records (Frontier, Viewpoint) and calls: searchFrontiers() runs scan, clustering,
 // splitLargeFrontiers and the down-sampling on the device; computeFrontiersToVisit() samples and scores
 // the viewpoints there; isFrontierCovered() checks coverage there.  The cost-matrix / tour group
-// (updateFrontierCostMatrix, getFullCostMatrix, getPathForTour, setNextFrontier: A* searches through
-// ViewNode) is not part of this library -- a maintainer keeps the reference's code for it on top of
-// frontiers_ / viewpoints_.
+// (updateFrontierCostMatrix, getFullCostMatrix, getPathForTour, setNextFrontier) keeps the reference's
+// bookkeeping.  By default each path comes from the package's own ViewNode (A* through the map, one pair at a
+// time); with the addition frontier/device_path_cost = true the path searches run batched on the device
+// (fuelmi_map_path_costs: one call per updateFrontierCostMatrix, per getFullCostMatrix row 0, per
+// getPathForTour first leg) and ViewNode::computeCost's velocity / yaw terms are host arithmetic with
+// exploration/vm, exploration/yd, exploration/w_dir.
 #ifndef _FRONTIER_FINDER_H_
 #define _FRONTIER_FINDER_H_
 
@@ -93,12 +96,20 @@ public:
 
 private:
   void pull(int which, list<Frontier>& out, int from = 0);
+  // frontier/device_path_cost: searchPath for n pairs in one device call; paths may be NULL (costs only)
+  void devicePaths(const vector<Vector3d>& p1, const vector<Vector3d>& p2, vector<double>& length,
+                   vector<vector<Vector3d>>* paths);
+  // ViewNode::computeCost (graph_node.cpp:63-88) with the path length already known
+  double hostCost(double length, const Vector3d& p1, const Vector3d& p2, double y1, double y2,
+                  const Vector3d& v1) const;
 
   fuelmi_frontier* dev_;
   shared_ptr<EDTEnvironment> edt_env_;
   int cluster_min_;
   double resolution_, min_candidate_dist_;
   bool have_viewpoints_;  // frontier/candidate_* and perception_utils/* were all given
+  bool device_path_cost_ = false;  // frontier/device_path_cost (addition, default false)
+  double vm_ = -1.0, yd_ = -1.0, w_dir_ = -1.0;  // exploration/vm, exploration/yd, exploration/w_dir (with the opt-in)
   bool order_fallback_logged_ = false;  // the first address-order fallback of reference_order = 2 has been reported
   vector<int> removed_ids_;
   list<Frontier> frontiers_, dormant_frontiers_, tmp_frontiers_;

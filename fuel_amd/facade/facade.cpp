@@ -322,6 +322,15 @@ FrontierFinder::FrontierFinder(const shared_ptr<EDTEnvironment>& edt, ros::NodeH
   int ref_order = 2;
   nh.param("frontier/reference_order", ref_order, 2);
   c.reference_order = ref_order;
+  // addition: frontier/device_path_cost.  true: the cost-matrix group's path searches run batched on the device
+  // (fuelmi_map_path_costs) and computeCost's remaining terms need the exploration manager's ViewNode parameters
+  // (fast_exploration_manager.cpp:55-59); false (default): ViewNode as in the reference
+  nh.param("frontier/device_path_cost", device_path_cost_, false);
+  if (device_path_cost_) {
+    nh.param("exploration/vm", vm_, -1.0);
+    nh.param("exploration/yd", yd_, -1.0);
+    nh.param("exploration/w_dir", w_dir_, -1.0);
+  }
   warn("fuelmi_frontier_create", fuelmi_frontier_create(edt_env_->sdf_map_->device(), &c, &dev_));
   // viewpoint sampling parameters (frontier_finder.cpp:32-43, perception_utils.cpp:7-11)
   fuelmi_viewpoint_cfg v;
@@ -448,7 +457,57 @@ void FrontierFinder::computeFrontiersToVisit() {
 }
 
 // ---- tour planning: the reference's bookkeeping (frontier_finder.cpp:258-324, 507-589) on the host lists;
-// path costs come from the package's own ViewNode (A* through the map)
+// path costs come from the package's own ViewNode (A* through the map), or with frontier/device_path_cost from
+// fuelmi_map_path_costs in one call per method
+void FrontierFinder::devicePaths(const vector<Vector3d>& p1, const vector<Vector3d>& p2, vector<double>& length,
+                                 vector<vector<Vector3d>>* paths) {
+  const int n = (int)p1.size();
+  length.assign(n, 0.0);
+  if (paths) paths->assign(n, {});
+  if (n == 0) return;
+  vector<double> a(3 * (size_t)n), b(3 * (size_t)n), xyz;
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < 3; ++k) a[3 * i + k] = p1[i](k), b[3 * i + k] = p2[i](k);
+  vector<int> kind(n), plen(n);
+  fuelmi_path_cfg c;
+  c.lattice_res = 0.4;  // graph_node.cpp:49
+  c.edge_step = 0.1;    // astar2.cpp:105
+  c.no_path_cost = 1000.0;  // graph_node.cpp:60
+  c.max_path_points = paths ? 256 : 0;
+  fuelmi_map* m = edt_env_->sdf_map_->device();
+  int rc = FUELMI_OK;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    if (paths) xyz.assign((size_t)n * c.max_path_points * 3, 0.0);
+    rc = fuelmi_map_path_costs(m, &c, n, a.data(), b.data(), length.data(), kind.data(), plen.data(),
+                               paths ? xyz.data() : nullptr);
+    if (rc != FUELMI_ELIMIT || !paths) break;
+    c.max_path_points = *std::max_element(plen.begin(), plen.end());  // every path_len is filled: grow once
+  }
+  warn("fuelmi_map_path_costs", rc);
+  if (!paths || rc != FUELMI_OK) return;
+  for (int i = 0; i < n; ++i) {
+    auto& P = (*paths)[i];
+    P.resize(plen[i]);
+    const double* q = xyz.data() + (size_t)i * c.max_path_points * 3;
+    for (int r = 0; r < plen[i]; ++r) P[r] = Vector3d(q[3 * r], q[3 * r + 1], q[3 * r + 2]);
+  }
+}
+
+double FrontierFinder::hostCost(double length, const Vector3d& p1, const Vector3d& p2, double y1, double y2,
+                                const Vector3d& v1) const {  // graph_node.cpp:63-88
+  double pos_cost = length / vm_;
+  if (v1.norm() > 1e-3) {
+    Vector3d dir = (p2 - p1).normalized();
+    Vector3d vdir = v1.normalized();
+    double diff = acos(vdir.dot(dir));
+    pos_cost += w_dir_ * diff;
+  }
+  double diff = fabs(y2 - y1);
+  diff = std::min(diff, 2 * M_PI - diff);
+  double yaw_cost = diff / yd_;
+  return std::max(pos_cost, yaw_cost);
+}
+
 void FrontierFinder::updateFrontierCostMatrix() {
   if (!removed_ids_.empty()) {
     // every surviving old cluster forgets its entries towards the removed ones
@@ -476,6 +535,47 @@ void FrontierFinder::updateFrontierCostMatrix() {
     b.costs_.push_back(cost);
     b.paths_.push_back(path);
   };
+  if (device_path_cost_) {
+    // every link of the cycle in ONE call, in the order the loops below consume them.  An old x new link is searched
+    // from the new viewpoint (its lattice anchored there; sources are few per cycle) and the old record stores the
+    // reversed path; a new x new link from the first of the two, as the reference does
+    vector<Vector3d> p1, p2;
+    for (auto old = frontiers_.begin(); old != first_new_ftr_; ++old)
+      for (auto fresh = first_new_ftr_; fresh != frontiers_.end(); ++fresh)
+        p1.push_back(fresh->viewpoints_.front().pos_), p2.push_back(old->viewpoints_.front().pos_);
+    for (auto a = first_new_ftr_; a != frontiers_.end(); ++a) {
+      auto b = a;
+      for (++b; b != frontiers_.end(); ++b)
+        p1.push_back(a->viewpoints_.front().pos_), p2.push_back(b->viewpoints_.front().pos_);
+    }
+    vector<double> len;
+    vector<vector<Vector3d>> paths;
+    devicePaths(p1, p2, len, &paths);
+    size_t k = 0;
+    // a's record gets the path a -> b, b's the reverse; `from_b`: the device path runs b -> a
+    auto store = [&](Frontier& a, Frontier& b, bool from_b) {
+      const Viewpoint& va = a.viewpoints_.front();
+      const Viewpoint& vb = b.viewpoints_.front();
+      const double cost = hostCost(len[k], va.pos_, vb.pos_, va.yaw_, vb.yaw_, Vector3d(0, 0, 0));
+      vector<Vector3d> path = paths[k++];
+      if (from_b) std::reverse(path.begin(), path.end());
+      a.costs_.push_back(cost);
+      a.paths_.push_back(path);
+      std::reverse(path.begin(), path.end());
+      b.costs_.push_back(cost);
+      b.paths_.push_back(path);
+    };
+    for (auto old = frontiers_.begin(); old != first_new_ftr_; ++old)
+      for (auto fresh = first_new_ftr_; fresh != frontiers_.end(); ++fresh) store(*old, *fresh, true);
+    for (auto a = first_new_ftr_; a != frontiers_.end(); ++a) {
+      a->costs_.push_back(0);
+      a->paths_.push_back({});
+      auto b = a;
+      for (++b; b != frontiers_.end(); ++b) store(*a, *b, false);
+    }
+    first_new_ftr_ = frontiers_.end();
+    return;
+  }
   for (auto old = frontiers_.begin(); old != first_new_ftr_; ++old)
     for (auto fresh = first_new_ftr_; fresh != frontiers_.end(); ++fresh) link(*old, *fresh);
   for (auto a = first_new_ftr_; a != frontiers_.end(); ++a) {
@@ -499,6 +599,19 @@ void FrontierFinder::getFullCostMatrix(const Vector3d& cur_pos, const Vector3d& 
     ++i;
   }
   mat.leftCols<1>().setZero();
+  if (device_path_cost_) {  // row 0 in one call
+    vector<Vector3d> p1, p2;
+    for (auto& ftr : frontiers_) p1.push_back(cur_pos), p2.push_back(ftr.viewpoints_.front().pos_);
+    vector<double> len;
+    devicePaths(p1, p2, len, nullptr);
+    int j = 1;
+    for (auto& ftr : frontiers_) {
+      const Viewpoint& v = ftr.viewpoints_.front();
+      mat(0, j) = hostCost(len[j - 1], cur_pos, v.pos_, cur_yaw[0], v.yaw_, cur_vel);
+      ++j;
+    }
+    return;
+  }
   int j = 1;
   for (auto& ftr : frontiers_) {
     const Viewpoint& v = ftr.viewpoints_.front();
@@ -512,7 +625,14 @@ void FrontierFinder::getPathForTour(const Vector3d& pos, const vector<int>& fron
   vector<list<Frontier>::iterator> at;
   for (auto it = frontiers_.begin(); it != frontiers_.end(); ++it) at.push_back(it);
   vector<Vector3d> segment;
-  ViewNode::searchPath(pos, at[frontier_ids[0]]->viewpoints_.front().pos_, segment);
+  if (device_path_cost_) {  // the first leg in one call
+    vector<double> len;
+    vector<vector<Vector3d>> legs;
+    devicePaths({pos}, {at[frontier_ids[0]]->viewpoints_.front().pos_}, len, &legs);
+    segment = legs[0];
+  } else {
+    ViewNode::searchPath(pos, at[frontier_ids[0]]->viewpoints_.front().pos_, segment);
+  }
   path.insert(path.end(), segment.begin(), segment.end());
   for (size_t k = 0; k + 1 < frontier_ids.size(); ++k) {  // stored path from tour stop k to stop k+1
     auto p = at[frontier_ids[k]]->paths_.begin();

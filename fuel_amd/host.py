@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BsplineBatch, BsplineCfg, FrontierCfg, MapCfg, MapInfo, check, lib)
+from ._lib import (BsplineBatch, BsplineCfg, FrontierCfg, MapCfg, MapInfo, PathCfg, check, lib)
 
 # exploration.launch / algorithm.xml defaults (exploration_manager/launch/algorithm.xml:33-59,170-181)
 DEFAULT_MAP = dict(resolution=0.1, ground_height=-1.0, obstacles_inflation=0.199,
@@ -231,6 +231,32 @@ class SDFMap:
 
     def synchronize(self):
         check(self.L.fuelmi_map_synchronize(self.h))
+
+    # --- ViewNode::searchPath for a batch of pairs (include/fuelmi.h fuelmi_map_path_costs) ---
+    PATH_LINE, PATH_LATTICE, PATH_NONE = 0, 1, 2
+
+    def path_costs(self, p1, p2, res=0.4, edge_step=0.1, no_path_cost=1000.0, max_points=256):
+        """(length [n], kind [n], paths: list of [k, 3] arrays, or None when max_points is 0).  A path longer than
+        max_points raises FuelmiError (FUELMI_ELIMIT)."""
+        p1 = np.ascontiguousarray(p1, dtype=np.float64).reshape(-1, 3)
+        p2 = np.ascontiguousarray(p2, dtype=np.float64).reshape(-1, 3)
+        assert len(p1) == len(p2)
+        n = len(p1)
+        c = PathCfg(float(res), float(edge_step), float(no_path_cost), int(max_points))
+        length = np.empty(n)
+        kind = np.empty(n, dtype=np.int32)
+        plen = np.empty(n, dtype=np.int32)
+        buf = np.empty((n, max_points, 3)) if max_points > 0 else None
+        check(self.L.fuelmi_map_path_costs(self.h, C.byref(c), n, _dp(p1), _dp(p2), _dp(length), _ip(kind), _ip(plen),
+                                           _dp(buf)))
+        paths = None if buf is None else [buf[i, :plen[i]].copy() for i in range(n)]
+        return length, kind, paths
+
+    def path_stats(self):
+        """of the last path_costs call: relaxation launches in all, the most of one chunk, lattice sources, chunks"""
+        st = np.zeros(4, dtype=np.int32)
+        check(self.L.fuelmi_map_path_stats(self.h, _ip(st)))
+        return dict(zip(("launches", "max_chunk_launches", "sources", "chunks"), (int(v) for v in st)))
 
     # --- measurement ---
     def timerBegin(self):

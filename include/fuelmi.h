@@ -328,6 +328,35 @@ int fuelmi_frontier_removed_ids(const fuelmi_frontier* f, int* ids);
 int fuelmi_frontier_get_flags(fuelmi_frontier* f, char* flags);
 
 /* ------------------------------------------------------------------------------------------
+ * Viewpoint path costs: ViewNode::searchPath (active_perception/src/graph_node.cpp:32-61) for a batch of
+ * pairs, the entries of the tour cost matrix (frontier_finder.cpp:260-326, 508-592).  Per pair:
+ *   kind 0: the straight line p1 -> p2 (RayCaster walk from p1's voxel, stopping before p2's) meets no voxel
+ *           that is inflated, UNKNOWN or outside the index box: length = |p1 - p2|, path {p1, p2} -- bit for
+ *           bit the reference;
+ *   kind 1: the shortest path on the 26-connected lattice p1 + n * lattice_res under Astar::search's edge test
+ *           (path_searching/src/astar2.cpp:86-113, samples every edge_step) to the goal node -- posToIndex at
+ *           lattice_res within +-1 of p2's -- minimising d + |p2 - node|; path [p1, nodes..., p2], length its
+ *           sequential sum of segment norms (Astar::pathLength).  Deterministic, without the reference's
+ *           wall-clock cap (DESIGN.md section 10 lists the differences);
+ *   kind 2: no goal reachable: length = no_path_cost, path {p1, p2}.
+ * Reads the map's current inflated / unknown planes on the map's stream; same thread rule as the mutators.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  double lattice_res;  /* 0.4 (graph_node.cpp:49) */
+  double edge_step;    /* 0.1 (astar2.cpp:105) */
+  double no_path_cost; /* 1000 (graph_node.cpp:60) */
+  int max_path_points; /* points per pair in path_xyz */
+} fuelmi_path_cfg;
+/* p1_xyz, p2_xyz: n points each (host).  length[n], kind[n], path_len[n] (points of each path, always the full
+ * count).  path_xyz: n x max_path_points x 3 (host), may be NULL.  If a path has more than max_path_points points
+ * the call fills length / kind / path_len (and the paths that fit) and returns FUELMI_ELIMIT. */
+int fuelmi_map_path_costs(fuelmi_map* m, const fuelmi_path_cfg* cfg, int n, const double* p1_xyz,
+                          const double* p2_xyz, double* length, int* kind, int* path_len, double* path_xyz);
+/* what the last fuelmi_map_path_costs on this map did: [0] relaxation launches in all, [1] the most of one chunk of
+ * sources, [2] lattice sources, [3] chunks */
+int fuelmi_map_path_stats(const fuelmi_map* m, int stats[4]);
+
+/* ------------------------------------------------------------------------------------------
  * B-spline cost + gradient: replaces BsplineOptimizer::combineCost and the calc*Cost terms
  * (bspline_opt/src/bspline_optimizer.cpp:255-516, 518-691), batched over C trajectories.
  * ---------------------------------------------------------------------------------------- */
