@@ -139,6 +139,7 @@ SYMBOLS = {
     "fuelmi_map_update_esdf": (C.c_int, [_P]),
     "fuelmi_map_set_esdf_family": (C.c_int, [_P, C.c_int]),
     "fuelmi_map_last_esdf_family": (C.c_int, [_P]),
+    "fuelmi_map_esdf_plan": (C.c_int, [_ip, _ip, _ip, C.c_int, C.c_int, _ip]),
     "fuelmi_map_last_inflate_kernel": (C.c_int, [_P]),
     "fuelmi_map_reset_buffer_all": (C.c_int, [_P]),
     "fuelmi_map_reset_buffer": (C.c_int, [_P, _dp, _dp]),

@@ -260,9 +260,9 @@ __device__ __forceinline__ int line_src_up(const u64* __restrict__ infl, const u
 #define ESDF_FAR_D 8u  // statistic: an output counts as "far from sources" beyond this many voxels
 #define ESDF_NG 256    // groups of 16 x-slabs the statistic is kept for (maps wider than 4096 voxels share groups)
 // rows of the fused z/y pass that need no sweep (all sources / no source) take a short cut: measured 38.8 -> 37.2 us on
-// 400^2 x 100, 188 -> 172 us on 800^2 x 200
-static bool zy_fastrow() { return true; }
-static int esdf_near() { return 2; }  // rows the FAR kernels scan one by one before the block walk (even: two rows per trip)
+// 400^2 x 100, 188 -> 172 us on 800^2 x 200 (kernel argument fastrow; bit 8 of near for k_esdf_zy4)
+static constexpr int ZY_FASTROW = 1;
+static constexpr int ESDF_NEAR = 2;  // rows the FAR kernels scan one by one before the block walk (even: two rows per trip)
 // one 16-byte global store that stays one instruction (a plain uint4 assignment next to the per-component edge
 // path came out as a 12-byte plus a 4-byte store)
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
@@ -499,7 +499,7 @@ k_esdf_zy4(Geo g, Box3 b, const u64* __restrict__ infl, const u64* __restrict__ 
   u32* cm = reinterpret_cast<u32*>(bm + (size_t)((ylen + 7) >> 3) * ZC * 4);
   if (FAR && (int)threadIdx.x < ZC) cm[threadIdx.x] = INF32;
   const u64 inbox_mask = zs <= ze ? bit_range(zs - zc0, ze - zs + 1) : 0ull;
-  const bool fastrow = (near >> 8) & 1;  // (FUELMI_ZY_FASTROW=0 switches the sweep-free rows off)
+  const bool fastrow = (near >> 8) & 1;  // (ZY_FASTROW: rows that need no sweep take the short cut)
   near &= 0xff;
   // Source bits of the rows.  When the box's part of a z-line fits three plane words (z extents up to 129
   // voxels) every row takes ONE round of independent loads -- issued for all of the lane's rows before the first
@@ -977,149 +977,6 @@ k_esdf_x4(Geo g, Box3 b, const u32* __restrict__ tmp, float* __restrict__ dist, 
   }
 }
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per kernel and device, not once per launch (VERDICT r4 item 3)
-static hipError_t lds_attr_once(const void* fn, int bytes) {
-  static std::mutex mu;
-  static std::vector<std::pair<const void*, int>> done;  // (function, device)
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::lock_guard<std::mutex> lk(mu);
-  for (const auto& d : done)
-    if (d.first == fn && d.second == dev) return hipSuccess;
-  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess) done.push_back({fn, dev});
-  return e;
-}
-
-// "this kernel variant does not fit this box" (LDS tables, line length): the caller takes the next variant.  Positive,
-// so that it can never be taken for one of the negative FUELMI_E* codes
-enum { ESDF_NO_FIT = 1 };
-
-// the device and the pinned-host tables of the far-output statistic
-template <int OUT>
-static u32* esdf_stat_dev(fuelmi_map* m) {
-  return OUT == 0 ? m->esdf_stat : nullptr;
-}
-static volatile u32* esdf_stat_host(fuelmi_map* m) { return m->h_esdf_stat; }
-
-static inline bool use_vec4(const Geo& g, int xlen) { return (g.nz % 4) == 0 && (size_t)xlen * 64 <= 150 * 1024; }
-
-template <int MODE, bool FAR>
-static int launch_zy4(fuelmi_map* m, const Box3& b) {
-  const Geo& g = m->g;
-  const int xlen = b.hi[0] - b.lo[0] + 1, ylen = b.hi[1] - b.lo[1] + 1;
-  const int z0a = b.lo[2] & ~3, z1a = b.hi[2] | 3;
-  const int zlen_a = z1a - z0a + 1;
-  // ~20 z per chunk amortises the per-row bit fetches (measured: 400 rows x 20 z = 32 KB on G400,
-  // 800 rows x 20 z = 64 KB on G800 are the optima; bigger tiles lose occupancy, smaller ones repeat the
-  // row prologue)
-  const int budget = std::min(std::max(32 * 1024, ylen * 4 * 20), 80 * 1024);
-  int zc_max = std::max(4, (budget / (4 * ylen)) & ~3);
-  zc_max = std::min(zc_max, std::min(zlen_a, 64));
-  int nzc = (zlen_a + zc_max - 1) / zc_max;
-  int ZC = (((zlen_a + nzc - 1) / nzc) + 3) & ~3;
-  nzc = (zlen_a + ZC - 1) / ZC;
-  size_t lds = (size_t)(FAR ? ylen + ((ylen + 7) >> 3) + 1 : ylen) * ZC * sizeof(u32);  // tile (+ block and line minima)
-  if (lds > 160 * 1024) {
-    if (FAR) return ESDF_NO_FIT;  // (the far-field tables do not fit beside the tile: the caller takes the plain kernel)
-    fuelmi_set_error("ESDF y-line of %d voxels does not fit the LDS tile", ylen);
-    return FUELMI_ELIMIT;
-  }
-  if (lds > 64 * 1024)
-    HIPCHK(lds_attr_once(reinterpret_cast<const void*>(&k_esdf_zy4<MODE, FAR>), 160 * 1024));
-  STAGE_LAUNCH(m, (k_esdf_zy4<MODE, FAR>), ((xlen + 7) / 8) * 8 * nzc, 512, lds, g, b, (const u64*)m->infl_bits.p, (const u64*)m->unk_bits.p,
-               m->esdf_tmp, ZC, nzc, z0a, esdf_near() | (zy_fastrow() ? 256 : 0),
-               MODE == 2 ? nullptr : esdf_stat_dev<0>(m));
-  HIPCHK(hipGetLastError());
-  return FUELMI_OK;
-}
-
-// FUELMI_ZY_TIMING: a pass has left four 100 MHz stamps per workgroup (start, tile filled, barrier passed, done)
-static int pass_timing_report(fuelmi_map* m, unsigned long long* dbg, int grid, const char* what) {
-  HIPCHK(hipStreamSynchronize(m->stream));
-  std::vector<unsigned long long> d((size_t)grid * 8);
-  HIPCHK(hipMemcpy(d.data(), dbg, d.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  HIPCHK(hipFree(dbg));
-  unsigned long long t0 = ~0ull, t1 = 0;
-  double ph[3] = {0, 0, 0}, life = 0;
-  int n = 0;
-  for (int w = 0; w < grid; ++w) {
-    const unsigned long long* r = &d[(size_t)w * 8];
-    if (!r[0] || !r[3]) continue;
-    t0 = std::min(t0, r[0]), t1 = std::max(t1, r[3]);
-    ph[0] += (double)(r[1] - r[0]), ph[1] += (double)(r[2] - r[1]), ph[2] += (double)(r[3] - r[2]), life += (double)(r[3] - r[0]);
-    ++n;
-  }
-  int alive = 0, early = 0;
-  const unsigned long long mid = t0 + (t1 - t0) / 2;
-  for (int w = 0; w < grid; ++w) {
-    const unsigned long long* r = &d[(size_t)w * 8];
-    if (!r[0] || !r[3]) continue;
-    if (r[0] <= mid && r[3] >= mid) ++alive;
-    if (r[0] - t0 < 100) ++early;
-  }
-  std::vector<double> st, en;
-  for (int w = 0; w < grid; ++w) {
-    const unsigned long long* r = &d[(size_t)w * 8];
-    if (!r[0] || !r[3]) continue;
-    st.push_back((double)(r[0] - t0) / 100.0), en.push_back((double)(r[3] - t0) / 100.0);
-  }
-  std::sort(st.begin(), st.end());
-  std::sort(en.begin(), en.end());
-  int peak = 0;
-  {
-    size_t i = 0, j = 0;
-    int cur = 0;
-    while (i < st.size()) {
-      if (st[i] <= en[j]) ++cur, ++i, peak = std::max(peak, cur);
-      else --cur, ++j;
-    }
-  }
-  {  // the slowest tenth of the workgroups: where THEIR life goes, and which blocks they are
-    std::vector<std::pair<double, int>> lv;
-    for (int w = 0; w < grid; ++w) {
-      const unsigned long long* r = &d[(size_t)w * 8];
-      if (!r[0] || !r[3]) continue;
-      lv.push_back({(double)(r[3] - r[0]) / 100.0, w});
-    }
-    std::sort(lv.begin(), lv.end());
-    const size_t k0 = lv.size() - std::max<size_t>(1, lv.size() / 10);
-    double f = 0, bb = 0, sc = 0, lf = 0;
-    for (size_t k = k0; k < lv.size(); ++k) {
-      const unsigned long long* r = &d[(size_t)lv[k].second * 8];
-      f += (double)(r[1] - r[0]), bb += (double)(r[2] - r[1]), sc += (double)(r[3] - r[2]), lf += lv[k].first;
-    }
-    const double nn = (double)(lv.size() - k0) * 100.0;
-    std::fprintf(stderr, "[slowest tenth: fill %.2f barrier %.2f scan %.2f life %.2f us; slowest blocks:", f / nn, bb / nn, sc / nn, lf * 100.0 / nn);
-    for (size_t k = lv.size() - std::min<size_t>(8, lv.size()); k < lv.size(); ++k) std::fprintf(stderr, " %d(%.1f)", lv[k].second, lv[k].first);
-    std::fprintf(stderr, "]\n");
-  }
-  auto pct = [](const std::vector<double>& v, double f) { return v.empty() ? 0.0 : v[std::min(v.size() - 1, (size_t)(f * (double)v.size()))]; };
-  std::fprintf(stderr, "[%s: %d workgroups, span %.2f us; per workgroup: fill %.2f barrier %.2f scan %.2f life %.2f us; "
-               "alive at mid-span %d (peak %d), started in the first us %d; starts 25/50/75/100 %%: %.1f %.1f %.1f %.1f us, ends 25/50/75: %.1f %.1f %.1f\n",
-               what, n, (double)(t1 - t0) / 100.0, ph[0] / n / 100.0,
-               ph[1] / n / 100.0, ph[2] / n / 100.0, life / n / 100.0, alive, peak, early, pct(st, 0.25), pct(st, 0.5), pct(st, 0.75),
-               pct(st, 1.0), pct(en, 0.25), pct(en, 0.5), pct(en, 0.75));
-  return FUELMI_OK;
-}
-
-template <int OUT, int SEGS, bool FAR>
-static int launch_x4s(fuelmi_map* m, const Box3& b) {
-  const Geo& g = m->g;
-  const int xlen = b.hi[0] - b.lo[0] + 1, ylen = b.hi[1] - b.lo[1] + 1;
-  const int z0a = b.lo[2] & ~3, z1a = b.hi[2] | 3;
-  const int zlen_a = z1a - z0a + 1;
-  const size_t lds = (size_t)(FAR ? xlen + ((xlen + 7) >> 3) + 1 : xlen) * SEGS * 4 * sizeof(u32);
-  if (lds > 160 * 1024) return ESDF_NO_FIT;  // (FAR only: the longest lines, > 2270 voxels, scan without the far phase)
-  if (lds > 64 * 1024)
-    HIPCHK(lds_attr_once(reinterpret_cast<const void*>(&k_esdf_x4<OUT, SEGS, FAR>), 160 * 1024));
-  int ncol = ylen * zlen_a;
-  const int threads = 1024;
-  STAGE_LAUNCH(m, (k_esdf_x4<OUT, SEGS, FAR>), (ncol + 4 * SEGS - 1) / (4 * SEGS), threads, lds, g, b, (const u32*)m->esdf_tmp,
-               m->dist, z0a, zlen_a, esdf_near(), esdf_stat_dev<OUT>(m), esdf_stat_host(m));
-  HIPCHK(hipGetLastError());
-  return FUELMI_OK;
-}
 // ------------------------------------------------------------------------------------------------
 // Round 5: the hand-over between the two packed passes is 16-bit and tile-contiguous.
 // Rounds 2-4 stored the y-pass result as u32 at the voxel's own address (64 MB on the 400^2 x 100 map) and the x pass
@@ -1446,10 +1303,103 @@ k_esdf_x_pk2(Geo g, Box3 b, const uint4* __restrict__ tmp16, const u32* __restri
   if (stamp && threadIdx.x == 0) stamp[3] = wall_clock64();
 }
 
+// ================================================================================================================
+// Host side: one plan, then launch.  esdf_plan() computes every launch of an update (kernel instantiation, grid, block,
+// dynamic LDS, z-chunks) from the box, the family and the map's flags; esdf_update() issues them in order.  A pass (z/y
+// then x) of family fam runs the packed pair when fam is PLAIN and the box is the packed kind (else PLAIN runs as and
+// reports PLAIN32); else the vector pair k_esdf_zy4 + k_esdf_x4 when nz % 4 == 0 and x lines <= 2400 voxels, whose
+// far-field instantiations drop to the plain ones per pass where their minima do not fit the LDS; else the scalar
+// pair.  Signed maps add the negative pass, PLAIN for FAR.  A box no kernel takes fails before anything is launched.
+// ================================================================================================================
+
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per kernel and device, not once per launch (VERDICT r4 item 3)
+static hipError_t lds_attr_once(const void* fn, int bytes) {
+  static std::mutex mu;
+  static std::vector<std::pair<const void*, int>> done;  // (function, device)
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> lk(mu);
+  for (const auto& d : done)
+    if (d.first == fn && d.second == dev) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) done.push_back({fn, dev});
+  return e;
+}
+
+// FUELMI_ZY_TIMING: a pass has left four 100 MHz stamps per workgroup (start, tile filled, barrier passed, done)
+static int pass_timing_report(fuelmi_map* m, unsigned long long* dbg, int grid, const char* what) {
+  HIPCHK(hipStreamSynchronize(m->stream));
+  std::vector<unsigned long long> d((size_t)grid * 8);
+  HIPCHK(hipMemcpy(d.data(), dbg, d.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  HIPCHK(hipFree(dbg));
+  unsigned long long t0 = ~0ull, t1 = 0;
+  double ph[3] = {0, 0, 0}, life = 0;
+  int n = 0;
+  for (int w = 0; w < grid; ++w) {
+    const unsigned long long* r = &d[(size_t)w * 8];
+    if (!r[0] || !r[3]) continue;
+    t0 = std::min(t0, r[0]), t1 = std::max(t1, r[3]);
+    ph[0] += (double)(r[1] - r[0]), ph[1] += (double)(r[2] - r[1]), ph[2] += (double)(r[3] - r[2]), life += (double)(r[3] - r[0]);
+    ++n;
+  }
+  int alive = 0, early = 0;
+  const unsigned long long mid = t0 + (t1 - t0) / 2;
+  for (int w = 0; w < grid; ++w) {
+    const unsigned long long* r = &d[(size_t)w * 8];
+    if (!r[0] || !r[3]) continue;
+    if (r[0] <= mid && r[3] >= mid) ++alive;
+    if (r[0] - t0 < 100) ++early;
+  }
+  std::vector<double> st, en;
+  for (int w = 0; w < grid; ++w) {
+    const unsigned long long* r = &d[(size_t)w * 8];
+    if (!r[0] || !r[3]) continue;
+    st.push_back((double)(r[0] - t0) / 100.0), en.push_back((double)(r[3] - t0) / 100.0);
+  }
+  std::sort(st.begin(), st.end());
+  std::sort(en.begin(), en.end());
+  int peak = 0;
+  {
+    size_t i = 0, j = 0;
+    int cur = 0;
+    while (i < st.size()) {
+      if (st[i] <= en[j]) ++cur, ++i, peak = std::max(peak, cur);
+      else --cur, ++j;
+    }
+  }
+  {  // the slowest tenth of the workgroups: where THEIR life goes, and which blocks they are
+    std::vector<std::pair<double, int>> lv;
+    for (int w = 0; w < grid; ++w) {
+      const unsigned long long* r = &d[(size_t)w * 8];
+      if (!r[0] || !r[3]) continue;
+      lv.push_back({(double)(r[3] - r[0]) / 100.0, w});
+    }
+    std::sort(lv.begin(), lv.end());
+    const size_t k0 = lv.size() - std::max<size_t>(1, lv.size() / 10);
+    double f = 0, bb = 0, sc = 0, lf = 0;
+    for (size_t k = k0; k < lv.size(); ++k) {
+      const unsigned long long* r = &d[(size_t)lv[k].second * 8];
+      f += (double)(r[1] - r[0]), bb += (double)(r[2] - r[1]), sc += (double)(r[3] - r[2]), lf += lv[k].first;
+    }
+    const double nn = (double)(lv.size() - k0) * 100.0;
+    std::fprintf(stderr, "[slowest tenth: fill %.2f barrier %.2f scan %.2f life %.2f us; slowest blocks:", f / nn, bb / nn, sc / nn, lf * 100.0 / nn);
+    for (size_t k = lv.size() - std::min<size_t>(8, lv.size()); k < lv.size(); ++k) std::fprintf(stderr, " %d(%.1f)", lv[k].second, lv[k].first);
+    std::fprintf(stderr, "]\n");
+  }
+  auto pct = [](const std::vector<double>& v, double f) { return v.empty() ? 0.0 : v[std::min(v.size() - 1, (size_t)(f * (double)v.size()))]; };
+  std::fprintf(stderr, "[%s: %d workgroups, span %.2f us; per workgroup: fill %.2f barrier %.2f scan %.2f life %.2f us; "
+               "alive at mid-span %d (peak %d), started in the first us %d; starts 25/50/75/100 %%: %.1f %.1f %.1f %.1f us, ends 25/50/75: %.1f %.1f %.1f\n",
+               what, n, (double)(t1 - t0) / 100.0, ph[0] / n / 100.0,
+               ph[1] / n / 100.0, ph[2] / n / 100.0, life / n / 100.0, alive, peak, early, pct(st, 0.25), pct(st, 0.5), pct(st, 0.75),
+               pct(st, 1.0), pct(en, 0.25), pct(en, 0.5), pct(en, 0.75));
+  return FUELMI_OK;
+}
+
+
 // The column tiles of a box (x pass) and the chunks of its z/y pass.  Tiles: the aligned z range in pieces of 8, then 4,
 // 2, 1 segments that add up to it exactly (100 voxels: 8 + 8 + 8 + 1 segments); a tile of width w holds 8 / w y-rows.
-// Chunks: a tile piece wider than gz_max is cut into chunks of gz_max.  ESDF_NO_FIT beyond PK2_MAXCH pieces.
-static int pk2_chunks(int ylen, int nseg, int gz_max, Pk2Chunks* xs, Pk2ZChunks* zs) {
+// Chunks: a tile piece wider than gz_max is cut into chunks of gz_max.  false beyond PK2_MAXCH pieces / PK2_MAXZCH chunks.
+static bool pk2_chunks(int ylen, int nseg, int gz_max, Pk2Chunks* xs, Pk2ZChunks* zs) {
   *xs = Pk2Chunks{};
   *zs = Pk2ZChunks{};
   const int n8 = nseg >> 3;  // full-width pieces: tile (y, c) = y * n8 + c
@@ -1465,18 +1415,18 @@ static int pk2_chunks(int ylen, int nseg, int gz_max, Pk2Chunks* xs, Pk2ZChunks*
     return true;
   };
   for (int c = 0; c < n8; ++c, ++n, seg += 8) {
-    if (n == PK2_MAXCH) return ESDF_NO_FIT;
+    if (n == PK2_MAXCH) return false;
     xs->seg0[n] = (short)seg, xs->g[n] = 8, xs->tile0[n] = 0;  // (interleaved: see n8)
-    if (!add_z(seg, 8, 3, c, n8)) return ESDF_NO_FIT;
+    if (!add_z(seg, 8, 3, c, n8)) return false;
   }
   xs->n8 = n8;
   while (seg < nseg) {  // the remainder in binary: pieces of 4, 2, 1 segments, tiles of 2, 4, 8 y-rows
     int gw = 4;
     while (gw > nseg - seg) gw >>= 1;
     const int gsh = gw == 4 ? 2 : (gw == 2 ? 1 : 0);
-    if (n == PK2_MAXCH) return ESDF_NO_FIT;
+    if (n == PK2_MAXCH) return false;
     xs->seg0[n] = (short)seg, xs->g[n] = (short)gw, xs->tile0[n] = tile;
-    if (!add_z(seg, gw, gsh, tile, 1)) return ESDF_NO_FIT;
+    if (!add_z(seg, gw, gsh, tile, 1)) return false;
     tile += (ylen + 8 / gw - 1) / (8 / gw);
     seg += gw;
     ++n;
@@ -1486,160 +1436,134 @@ static int pk2_chunks(int ylen, int nseg, int gz_max, Pk2Chunks* xs, Pk2ZChunks*
   for (int k = n; k <= PK2_MAXCH; ++k) xs->tile0[k] = tile;
   for (int k = n; k < PK2_MAXCH; ++k) xs->g[k] = 1;
   if (n8 == n) xs->tile0[n8] = tile;
+  return true;
+}
+
+// bytes of the packed family's 16-bit hand-over (esdf_tmp16) on an nx x ny x nz grid: the column tiles of the full box
+// (8 segments per tile, ragged chunks) of 128 B per x-pair, x-pairs padded to 64.  0: the family cannot run (nz % 4 != 0)
+size_t esdf_handover_bytes(int nx, int ny, int nz) {
+  if (nz % 4 != 0) return 0;
+  const size_t ntiles = ((size_t)ny * (size_t)((nz + 7) / 4 + 1) + 7) / 8 + PK2_MAXCH + 1;
+  return ntiles * (size_t)(((nx + 1) / 2 + 63) / 64) * 64 * 128;
+}
+
+// one planned launch: kernel (FUELMI_ESDF_K_*) and its template arguments in declaration order (MODE / OUT first; unused: 0)
+struct EsdfLaunch {
+  int kernel = 0, targ[3] = {0, 0, 0};
+  int grid = 0, block = 0, lds = 0;
+  int ZC = 0, nzc = 0, z0a = 0;  // z-chunks (nzc of the packed kernels: the chunk / tile-piece count); aligned z start
+  int aux = 0;                   // npx (k_esdf_zy_pk2), zlen_a (k_esdf_x4), full8 (k_esdf_x_pk2)
+};
+struct EsdfPlan {
+  int n = 0;       // z/y+, x+ [, z/y-, x-]
+  int family = 0;  // what fuelmi_map_last_esdf_family reports: the positive pass's family
+  EsdfLaunch l[4];
+  Pk2Chunks ch;    // column tiles and z/y chunks of the packed passes (the same for both signs)
+  Pk2ZChunks zch;
+};
+
+// The launches of one update (pure: no device, no map).  family: PLAIN / FAR / PLAIN32 (AUTO is resolved by the caller);
+// handover: bytes of the 16-bit hand-over buffer (0: none).  FUELMI_ELIMIT for a box no kernel takes.
+static int esdf_plan(const int dims[3], const Box3& b, int family, bool optimistic, bool signed_dist, size_t handover,
+                     EsdfPlan* p) {
+  *p = EsdfPlan{};
+  const int xlen = b.hi[0] - b.lo[0] + 1, ylen = b.hi[1] - b.lo[1] + 1, zlen = b.hi[2] - b.lo[2] + 1;
+  const int z0a = b.lo[2] & ~3, zlen_a = (b.hi[2] | 3) - z0a + 1;
+  const int npx = (xlen + 1) >> 1, npair = (ylen + 1) >> 1;
+  const bool z4 = dims[2] % 4 == 0;
+  // packed: widest chunk 4 segments (16 voxels; the 8-segment body needs 110 VGPRs and measured 46 against 34 us on the
+  // 400^2 x 100 map) while the two tiles of a slab pair stay within 52 KB (three workgroups per CU), else 2
+  const int g_max = (size_t)npair * 4 * 32 > 52 * 1024 ? 2 : 4;
+  const size_t pk2_lds = (size_t)npair * g_max * 32;
+  const bool pk2 = z4 && zlen <= 255 && handover > 0 && (size_t)npx * 128 <= 150 * 1024 && pk2_lds <= 160 * 1024 - 64 &&
+                   pk2_chunks(ylen, zlen_a >> 2, g_max, &p->ch, &p->zch) &&
+                   (size_t)p->ch.tile0[p->ch.n] * npx * 128 <= handover;
+  // the 4-z vector kernels: the x pass's 16-column tile holds the x line
+  const bool vec4 = z4 && (size_t)xlen * 64 <= 150 * 1024;
+
+  // one pass (z/y into L[0], x into L[1]) of family fam; *ran: the family it reports
+  auto pass = [&](int fam, int mode, EsdfLaunch* L, int* ran) {
+    const int out = mode == 2;
+    EsdfLaunch& zy = L[0];
+    EsdfLaunch& x = L[1];
+    if (fam == FUELMI_ESDF_PLAIN && pk2) {
+      // a half fills its npair rows in two trips: 128 / 256 lanes for 400- / 800-voxel y lines (measured: 33.5 against
+      // 35.5 us with one trip on the 400^2 x 100 map, 158 against 203 us on 800^2 x 200, whose 896-thread workgroups fit
+      // one per CU); NW: aligned z-lines of up to 128 / 256 bits
+      zy = {FUELMI_ESDF_K_ZY_PK2, {mode, g_max, zlen_a > 128 ? 4 : 2}, ((npx + 7) / 8) * 8 * p->zch.n,
+            2 * std::min(256, std::max(64, ((npair / 2 + 63) / 64) * 64)), (int)pk2_lds, 0, p->zch.n, z0a, npx};
+      const int x_lds = npx * 8 * 16;
+      const int full8 = ((ylen + 7) / 8) * 8 * p->ch.n8;  // blocks of the full-width tiles, y-rows padded to a multiple of 8
+      x = {FUELMI_ESDF_K_X_PK2, {out, 0, 0}, full8 + (p->ch.tile0[p->ch.n] - ylen * p->ch.n8), x_lds > 32 * 1024 ? 512 : 256,
+           x_lds, 0, p->ch.n, z0a, full8};
+      *ran = FUELMI_ESDF_PLAIN;
+      return FUELMI_OK;
+    }
+    const bool far = fam == FUELMI_ESDF_FAR;
+    *ran = far ? FUELMI_ESDF_FAR : FUELMI_ESDF_PLAIN32;
+    if (vec4) {
+      // ~20 z per chunk amortises the per-row bit fetches (measured: 400 rows x 20 z = 32 KB on G400, 800 rows x 20 z =
+      // 64 KB on G800 are the optima; bigger tiles lose occupancy, smaller ones repeat the row prologue)
+      const int budget = std::min(std::max(32 * 1024, ylen * 4 * 20), 80 * 1024);
+      int zc_max = std::max(4, (budget / (4 * ylen)) & ~3);
+      zc_max = std::min(zc_max, std::min(zlen_a, 64));
+      int nzc = (zlen_a + zc_max - 1) / zc_max;
+      const int ZC = (((zlen_a + nzc - 1) / nzc) + 3) & ~3;
+      nzc = (zlen_a + ZC - 1) / ZC;
+      auto zy_lds = [&](bool f) { return (size_t)(f ? ylen + ((ylen + 7) >> 3) + 1 : ylen) * ZC * sizeof(u32); };  // tile (+ block and line minima)
+      const bool zy_far = far && zy_lds(true) <= 160 * 1024;
+      if (zy_lds(zy_far) > 160 * 1024) {
+        fuelmi_set_error("ESDF y-line of %d voxels does not fit the LDS tile", ylen);
+        return FUELMI_ELIMIT;
+      }
+      zy = {FUELMI_ESDF_K_ZY4, {mode, zy_far, 0}, ((xlen + 7) / 8) * 8 * nzc, 512, (int)zy_lds(zy_far), ZC, nzc, z0a, 0};
+      // the 32-column tile is faster whenever it fits (measured on 800-voxel lines: 0.32 vs 0.37 ms), the 16-column one
+      // extends the vector path to x lines of up to 2400 voxels
+      const int segs = (size_t)xlen * 128 > 150 * 1024 ? 4 : 8;
+      auto x_lds = [&](bool f) { return (size_t)(f ? xlen + ((xlen + 7) >> 3) + 1 : xlen) * segs * 4 * sizeof(u32); };
+      const bool x_far = far && x_lds(true) <= 160 * 1024;
+      x = {FUELMI_ESDF_K_X4, {out, segs, x_far}, (ylen * zlen_a + 4 * segs - 1) / (4 * segs), 1024, (int)x_lds(x_far), 0, 0,
+           z0a, zlen_a};
+      return FUELMI_OK;
+    }
+    // scalar: z-chunk LDS tile <= 16 KiB so several WGs share a CU, chunks balanced over the z extent
+    const int zc_max = std::min(std::min(std::max(1, (16 * 1024) / (2 * ylen)), zlen), 256);
+    const int nzc = (zlen + zc_max - 1) / zc_max;
+    const int ZC = (zlen + nzc - 1) / nzc;
+    const size_t lds = (size_t)ylen * ZC * sizeof(unsigned short);
+    if (lds > 160 * 1024) {
+      fuelmi_set_error("ESDF y-line of %d voxels does not fit the LDS tile", ylen);
+      return FUELMI_ELIMIT;
+    }
+    zy = {FUELMI_ESDF_K_ZY, {mode, 0, 0}, xlen * nzc, 256, (int)lds, ZC, nzc, 0, 0};
+    const int S = (size_t)xlen * 32 * 4 <= 64 * 1024 ? 32 : ((size_t)xlen * 16 * 4 <= 128 * 1024 ? 16 : ((size_t)xlen * 8 * 4 <= 128 * 1024 ? 8 : 0));
+    if (!S) {
+      fuelmi_set_error("ESDF x-line of %d voxels does not fit the LDS tile", xlen);
+      return FUELMI_ELIMIT;
+    }
+    x = {FUELMI_ESDF_K_X, {S, out, 0}, (ylen * zlen + S - 1) / S, 256, xlen * S * (int)sizeof(u32), 0, 0, 0, 0};
+    return FUELMI_OK;
+  };
+
+  int rc = pass(family, optimistic ? 1 : 0, &p->l[0], &p->family);
+  if (rc) return rc;
+  p->n = 2;
+  if (signed_dist) {  // inside obstacles the nearest free voxel is never far: plain kernels
+    int ran;
+    rc = pass(family == FUELMI_ESDF_FAR ? FUELMI_ESDF_PLAIN : family, 2, &p->l[2], &ran);
+    if (rc) return rc;
+    p->n = 4;
+  }
   return FUELMI_OK;
 }
+
+// the pinned-host table of the far-output statistic; the serial number and the any-source word of the packed passes
+static volatile u32* esdf_stat_host(fuelmi_map* m) { return m->h_esdf_stat; }
 static u32 pk2_next_serial(fuelmi_map* m) {
   if (++m->esdf_serial == 0u) m->esdf_serial = 1u;
   return m->esdf_serial;
 }
 static u32* pk2_src_flag(fuelmi_map* m) { return m->esdf_stat + 2 * ESDF_NG + 2; }
-
-template <int MODE, int GMAX, int NW>
-static int launch_zy_pk2_g(fuelmi_map* m, const Box3& b, int z0a, int threads, size_t lds) {
-  const int xlen = b.hi[0] - b.lo[0] + 1;
-  const int npx = (xlen + 1) >> 1;
-  const Pk2ZChunks& ch = m->pk2_zch;
-  if (lds > 64 * 1024) HIPCHK(lds_attr_once(reinterpret_cast<const void*>(&k_esdf_zy_pk2<MODE, GMAX, NW>), 160 * 1024));
-  const int grid = ((npx + 7) / 8) * 8 * ch.n;
-  static const bool timing = getenv("FUELMI_ZY_TIMING") != nullptr;  // debug: where a workgroup's life goes
-  unsigned long long* dbg = nullptr;
-  if (timing) {
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&dbg), (size_t)grid * 8 * sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(dbg, 0, (size_t)grid * 8 * sizeof(unsigned long long), m->stream));
-  }
-  STAGE_LAUNCH(m, (k_esdf_zy_pk2<MODE, GMAX, NW>), grid, threads, lds, m->g, b, (const u64*)m->infl_bits.p,
-               (const u64*)m->unk_bits.p, reinterpret_cast<uint4*>(m->esdf_tmp16), m->esdf_tmp, ch, z0a, npx,
-               (zy_fastrow() ? 1 : 0), MODE == 2 ? nullptr : esdf_stat_dev<0>(m), pk2_src_flag(m), m->esdf_serial, dbg);
-  HIPCHK(hipGetLastError());
-  if (timing) {
-    char what[96];
-    std::snprintf(what, sizeof what, "zy2-timing] GMAX %d chunks %d threads %d lds %zu", GMAX, (int)ch.n, threads, lds);
-    { const int rc_ = pass_timing_report(m, dbg, grid, what); if (rc_ != FUELMI_OK) return rc_; }
-  }
-  return FUELMI_OK;
-}
-// the packed family's z/y pass: ESDF_NO_FIT when the box is not its kind (z extents above 255 voxels, nz % 4 != 0,
-// y lines too long for two tiles, x lines too long for the x pass's tile)
-template <int MODE>
-static int launch_zy_pk2(fuelmi_map* m, const Box3& b) {
-  const Geo& g = m->g;
-  const int xlen = b.hi[0] - b.lo[0] + 1, ylen = b.hi[1] - b.lo[1] + 1, zlen = b.hi[2] - b.lo[2] + 1;
-  if ((g.nz % 4) != 0 || zlen > 255 || !m->esdf_tmp16) return ESDF_NO_FIT;
-  const int z0a = b.lo[2] & ~3, z1a = b.hi[2] | 3;
-  const int zlen_a = z1a - z0a + 1;
-  const int npair = (ylen + 1) >> 1;
-  if ((size_t)((xlen + 1) >> 1) * 128 > 150 * 1024) return ESDF_NO_FIT;  // (the x pass's tile)
-  // widest chunk: 4 segments (16 voxels; the 8-segment body needs 110 VGPRs and measured 46 against 34 us on the
-  // 400^2 x 100 map) while the two tiles of a slab pair stay within 52 KB (three workgroups per CU), else 2
-  int g_max = 4;
-  while (g_max > 2 && (size_t)npair * g_max * 32 > 52 * 1024) g_max >>= 1;
-  const size_t lds = (size_t)npair * g_max * 32;
-  if (lds > 160 * 1024 - 64) return ESDF_NO_FIT;
-  if (pk2_chunks(ylen, zlen_a >> 2, g_max, &m->pk2_ch, &m->pk2_zch) != FUELMI_OK) return ESDF_NO_FIT;
-  if ((size_t)m->pk2_ch.tile0[m->pk2_ch.n] * (size_t)((xlen + 1) >> 1) * 128 > m->esdf_tmp16_bytes) return ESDF_NO_FIT;
-  // a half fills its npair rows in two trips: 128 / 256 lanes for 400- / 800-voxel y lines (measured: 33.5 against 35.5 us
-  // with one trip on the 400^2 x 100 map, 158 against 203 us on 800^2 x 200, whose 896-thread workgroups fit one per CU)
-  const int threads = 2 * std::min(256, std::max(64, ((npair / 2 + 63) / 64) * 64));
-  const bool wide = zlen_a > 128;  // aligned z-lines of up to 128 / 256 bits
-  (void)pk2_next_serial(m);
-  if (g_max == 8) return wide ? launch_zy_pk2_g<MODE, 8, 4>(m, b, z0a, threads, lds) : launch_zy_pk2_g<MODE, 8, 2>(m, b, z0a, threads, lds);
-  if (g_max == 4) return wide ? launch_zy_pk2_g<MODE, 4, 4>(m, b, z0a, threads, lds) : launch_zy_pk2_g<MODE, 4, 2>(m, b, z0a, threads, lds);
-  return wide ? launch_zy_pk2_g<MODE, 2, 4>(m, b, z0a, threads, lds) : launch_zy_pk2_g<MODE, 2, 2>(m, b, z0a, threads, lds);
-}
-
-// the x pass behind launch_zy_pk2 (same box, same serial, same chunks)
-template <int OUT>
-static int launch_x_pk2(fuelmi_map* m, const Box3& b) {
-  const Geo& g = m->g;
-  const int xlen = b.hi[0] - b.lo[0] + 1;
-  const int z0a = b.lo[2] & ~3;
-  const int npx = (xlen + 1) >> 1;
-  const size_t lds = (size_t)npx * 8 * 16;
-  if (lds > 64 * 1024) HIPCHK(lds_attr_once(reinterpret_cast<const void*>(&k_esdf_x_pk2<OUT>), 150 * 1024));
-  const int threads = lds > 32 * 1024 ? 512 : 256;
-  static const bool timing = getenv("FUELMI_ZY_TIMING") != nullptr;
-  const int ylen = b.hi[1] - b.lo[1] + 1;
-  const int full8 = ((ylen + 7) / 8) * 8 * m->pk2_ch.n8;  // blocks of the full-width tiles, y-rows padded to a multiple of 8
-  const int grid = full8 + (m->pk2_ch.tile0[m->pk2_ch.n] - ylen * m->pk2_ch.n8);
-  unsigned long long* dbg = nullptr;
-  if (timing) {
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&dbg), (size_t)grid * 8 * sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(dbg, 0, (size_t)grid * 8 * sizeof(unsigned long long), m->stream));
-  }
-  STAGE_LAUNCH(m, (k_esdf_x_pk2<OUT>), grid, threads, lds, g, b, reinterpret_cast<const uint4*>(m->esdf_tmp16),
-               (const u32*)m->esdf_tmp, m->dist, m->pk2_ch, z0a, full8, esdf_stat_dev<OUT>(m), esdf_stat_host(m),
-               (const u32*)pk2_src_flag(m), m->esdf_serial, dbg);
-  HIPCHK(hipGetLastError());
-  if (timing) {
-    char what[96];
-    std::snprintf(what, sizeof what, "x2-timing] threads %d lds %zu", threads, lds);
-    { const int rc_ = pass_timing_report(m, dbg, grid, what); if (rc_ != FUELMI_OK) return rc_; }
-  }
-  return FUELMI_OK;
-}
-
-template <int OUT, bool FAR>
-static int launch_x4(fuelmi_map* m, const Box3& b) {
-  const int xlen = b.hi[0] - b.lo[0] + 1;
-  // the 32-column tile is faster whenever it fits (measured on 800-voxel lines: 0.32 vs 0.37 ms), the
-  // 16-column one extends the vector path to x lines of up to 2400 voxels
-  const bool narrow = (size_t)xlen * 128 > 150 * 1024;
-  const int rc = narrow ? launch_x4s<OUT, 4, FAR>(m, b) : launch_x4s<OUT, 8, FAR>(m, b);
-  if (rc != ESDF_NO_FIT || !FAR) return rc;
-  return narrow ? launch_x4s<OUT, 4, false>(m, b) : launch_x4s<OUT, 8, false>(m, b);
-}
-
-template <int MODE, bool FAR>
-static int launch_zy(fuelmi_map* m, const Box3& b) {
-  if (use_vec4(m->g, b.hi[0] - b.lo[0] + 1)) {
-    const int rc = launch_zy4<MODE, FAR>(m, b);
-    return (FAR && rc == ESDF_NO_FIT) ? launch_zy4<MODE, false>(m, b) : rc;
-  }
-  const Geo& g = m->g;
-  const int xlen = b.hi[0] - b.lo[0] + 1, ylen = b.hi[1] - b.lo[1] + 1, zlen = b.hi[2] - b.lo[2] + 1;
-  // z-chunk: LDS tile <= 16 KiB so several WGs share a CU, chunks balanced over the z extent
-  int zc_max = std::max(1, (16 * 1024) / (2 * ylen));
-  if (zc_max > zlen) zc_max = zlen;
-  if (zc_max > 256) zc_max = 256;
-  int nzc = (zlen + zc_max - 1) / zc_max;
-  int ZC = (zlen + nzc - 1) / nzc;
-  size_t lds = (size_t)ylen * ZC * sizeof(unsigned short);
-  if (lds > 160 * 1024) {
-    fuelmi_set_error("ESDF y-line of %d voxels does not fit the LDS tile", ylen);
-    return FUELMI_ELIMIT;
-  }
-  if (lds > 64 * 1024)
-    HIPCHK(lds_attr_once(reinterpret_cast<const void*>(&k_esdf_zy<MODE>), 160 * 1024));
-  STAGE_LAUNCH(m, (k_esdf_zy<MODE>), xlen * nzc, 256, lds, g, b, (const u64*)m->infl_bits.p, (const u64*)m->unk_bits.p,
-               m->esdf_tmp, ZC, nzc);
-  HIPCHK(hipGetLastError());
-  return FUELMI_OK;
-}
-
-template <int S, int OUT>
-static int launch_x_s(fuelmi_map* m, const Box3& b) {
-  const Geo& g = m->g;
-  const int xlen = b.hi[0] - b.lo[0] + 1, ylen = b.hi[1] - b.lo[1] + 1, zlen = b.hi[2] - b.lo[2] + 1;
-  size_t lds = (size_t)xlen * S * sizeof(u32);
-  if (lds > 64 * 1024)
-    HIPCHK(lds_attr_once(reinterpret_cast<const void*>(&k_esdf_x<S, OUT>), 160 * 1024));
-  int ncol = ylen * zlen;
-  STAGE_LAUNCH(m, (k_esdf_x<S, OUT>), (ncol + S - 1) / S, 256, lds, g, b, (const u32*)m->esdf_tmp, m->dist);
-  HIPCHK(hipGetLastError());
-  return FUELMI_OK;
-}
-
-template <int OUT, bool FAR>
-static int launch_x(fuelmi_map* m, const Box3& b) {
-  const int xlen = b.hi[0] - b.lo[0] + 1;
-  if (use_vec4(m->g, xlen)) return launch_x4<OUT, FAR>(m, b);
-  const size_t budget = 64 * 1024;
-  if ((size_t)xlen * 32 * 4 <= budget) return launch_x_s<32, OUT>(m, b);
-  if ((size_t)xlen * 16 * 4 <= 128 * 1024) return launch_x_s<16, OUT>(m, b);
-  if ((size_t)xlen * 8 * 4 <= 128 * 1024) return launch_x_s<8, OUT>(m, b);
-  fuelmi_set_error("ESDF x-line of %d voxels does not fit the LDS tile", xlen);
-  return FUELMI_ELIMIT;
-}
 
 // Which kernels: the y pass of every update counts, on one slab of every group of 16, the outputs further than
 // ESDF_FAR_D voxels from all sources; the x pass hands the counts to the host.  The host keeps the latest pair of
@@ -1672,56 +1596,129 @@ static bool esdf_use_far(fuelmi_map* m, const Box3& b) {
   return m->far_last;
 }
 
-template <int MODE>
-static int launch_zy_family(fuelmi_map* m, const Box3& b, int fam, int* ran) {
-  if (fam == FUELMI_ESDF_PLAIN) {
-    const int rc = launch_zy_pk2<MODE>(m, b);
-    m->esdf_pk2_last = rc != ESDF_NO_FIT;
-    if (rc != ESDF_NO_FIT) {
-      *ran = FUELMI_ESDF_PLAIN;
-      return rc;
-    }
-    fam = FUELMI_ESDF_PLAIN32;
-  }
-  *ran = fam;
-  if constexpr (MODE != 2) {  // (the negative pass of signed maps never runs the far-field kernels)
-    if (fam == FUELMI_ESDF_FAR) return launch_zy<MODE, true>(m, b);
-  }
-  *ran = FUELMI_ESDF_PLAIN32;
-  return launch_zy<MODE, false>(m, b);
+
+// one planned launch of kernel `kern` (lds_cap: the dynamic LDS it is allowed above 64 KiB)
+template <class K, class... A>
+static int esdf_launch(fuelmi_map* m, K kern, const EsdfLaunch& L, int lds_cap, A... args) {
+  if (L.lds > 64 * 1024) HIPCHK(lds_attr_once(reinterpret_cast<const void*>(kern), lds_cap));
+  STAGE_LAUNCH(m, kern, L.grid, L.block, L.lds, args...);
+  HIPCHK(hipGetLastError());
+  return FUELMI_OK;
 }
+
+// debug (FUELMI_ZY_TIMING): a packed pass stamps every workgroup's life into a buffer of its own, reported after the pass
+template <class F>
+static int timed_launch(fuelmi_map* m, const EsdfLaunch& L, F launch) {
+  static const bool timing = getenv("FUELMI_ZY_TIMING") != nullptr;
+  unsigned long long* dbg = nullptr;
+  if (timing) {
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&dbg), (size_t)L.grid * 8 * sizeof(unsigned long long)));
+    HIPCHK(hipMemsetAsync(dbg, 0, (size_t)L.grid * 8 * sizeof(unsigned long long), m->stream));
+  }
+  const int rc = launch(dbg);
+  if (rc != FUELMI_OK || !timing) return rc;
+  char what[96];
+  if (L.kernel == FUELMI_ESDF_K_ZY_PK2)
+    std::snprintf(what, sizeof what, "zy2-timing] GMAX %d chunks %d threads %d lds %d", L.targ[1], L.nzc, L.block, L.lds);
+  else
+    std::snprintf(what, sizeof what, "x2-timing] threads %d lds %d", L.block, L.lds);
+  return pass_timing_report(m, dbg, L.grid, what);
+}
+
+template <int MODE>
+static int launch_zy(fuelmi_map* m, const Box3& b, const EsdfPlan& p, const EsdfLaunch& L) {
+  const Geo& g = m->g;
+  const u64* infl = m->infl_bits.p;
+  const u64* unk = m->unk_bits.p;
+  u32* stat = MODE == 2 ? nullptr : m->esdf_stat;  // (the positive pass feeds the far-output statistic)
+  if (L.kernel == FUELMI_ESDF_K_ZY) return esdf_launch(m, &k_esdf_zy<MODE>, L, 160 * 1024, g, b, infl, unk, m->esdf_tmp, L.ZC, L.nzc);
+  if (L.kernel == FUELMI_ESDF_K_ZY4) {
+    auto go = [&](auto kern) {
+      return esdf_launch(m, kern, L, 160 * 1024, g, b, infl, unk, m->esdf_tmp, L.ZC, L.nzc, L.z0a, ESDF_NEAR | (ZY_FASTROW << 8), stat);
+    };
+    if constexpr (MODE != 2)  // (the negative pass never runs the far-field kernels)
+      if (L.targ[1]) return go(&k_esdf_zy4<MODE, true>);
+    return go(&k_esdf_zy4<MODE, false>);
+  }
+  const u32 serial = pk2_next_serial(m);
+  return timed_launch(m, L, [&](unsigned long long* dbg) {
+    auto go = [&](auto kern) {
+      return esdf_launch(m, kern, L, 160 * 1024, g, b, infl, unk, reinterpret_cast<uint4*>(m->esdf_tmp16), m->esdf_tmp,
+                         p.zch, L.z0a, L.aux, ZY_FASTROW, stat, pk2_src_flag(m), serial, dbg);
+    };
+    const bool g4 = L.targ[1] == 4, nw4 = L.targ[2] == 4;
+    return g4 ? (nw4 ? go(&k_esdf_zy_pk2<MODE, 4, 4>) : go(&k_esdf_zy_pk2<MODE, 4, 2>))
+              : (nw4 ? go(&k_esdf_zy_pk2<MODE, 2, 4>) : go(&k_esdf_zy_pk2<MODE, 2, 2>));
+  });
+}
+
+template <int OUT>
+static int launch_x(fuelmi_map* m, const Box3& b, const EsdfPlan& p, const EsdfLaunch& L) {
+  const Geo& g = m->g;
+  u32* stat = OUT == 0 ? m->esdf_stat : nullptr;
+  if (L.kernel == FUELMI_ESDF_K_X) {
+    auto go = [&](auto kern) { return esdf_launch(m, kern, L, 160 * 1024, g, b, (const u32*)m->esdf_tmp, m->dist); };
+    return L.targ[0] == 32 ? go(&k_esdf_x<32, OUT>) : (L.targ[0] == 16 ? go(&k_esdf_x<16, OUT>) : go(&k_esdf_x<8, OUT>));
+  }
+  if (L.kernel == FUELMI_ESDF_K_X4) {
+    auto go = [&](auto kern) {
+      return esdf_launch(m, kern, L, 160 * 1024, g, b, (const u32*)m->esdf_tmp, m->dist, L.z0a, L.aux, ESDF_NEAR, stat,
+                         esdf_stat_host(m));
+    };
+    const bool segs8 = L.targ[1] == 8;
+    if constexpr (OUT == 0)  // (the negative pass never runs the far-field kernels)
+      if (L.targ[2]) return segs8 ? go(&k_esdf_x4<OUT, 8, true>) : go(&k_esdf_x4<OUT, 4, true>);
+    return segs8 ? go(&k_esdf_x4<OUT, 8, false>) : go(&k_esdf_x4<OUT, 4, false>);
+  }
+  return timed_launch(m, L, [&](unsigned long long* dbg) {
+    return esdf_launch(m, &k_esdf_x_pk2<OUT>, L, 150 * 1024, g, b, reinterpret_cast<const uint4*>(m->esdf_tmp16),
+                       (const u32*)m->esdf_tmp, m->dist, p.ch, L.z0a, L.aux, stat, esdf_stat_host(m),
+                       (const u32*)pk2_src_flag(m), m->esdf_serial, dbg);
+  });
+}
+
+static bool esdf_is_zy(const EsdfLaunch& L) { return L.kernel <= FUELMI_ESDF_K_ZY_PK2; }
+
 
 int esdf_update(fuelmi_map* m) {
   const Box3& b = m->local_bound;
   const int fam = m->esdf_family_pin >= 0 ? m->esdf_family_pin : (esdf_use_far(m, b) ? FUELMI_ESDF_FAR : FUELMI_ESDF_PLAIN);
-  const bool far = fam == FUELMI_ESDF_FAR;
-  int rc, ran = fam;
-  {
-    StageScope sc(m, FUELMI_K_ESDF_ZY, nullptr, true);
-    rc = m->cfg.optimistic ? launch_zy_family<1>(m, b, fam, &ran) : launch_zy_family<0>(m, b, fam, &ran);
-  }
+  const int dims[3] = {m->g.nx, m->g.ny, m->g.nz};
+  EsdfPlan p;
+  int rc = esdf_plan(dims, b, fam, m->cfg.optimistic != 0, m->cfg.signed_dist != 0, m->esdf_tmp16_bytes, &p);
   if (rc) return rc;
-  m->esdf_family_last = ran;
-  {
-    StageScope sc(m, FUELMI_K_ESDF_X, nullptr, true);
-    rc = ESDF_NO_FIT;
-    if (ran == FUELMI_ESDF_PLAIN && m->esdf_pk2_last)
-      rc = launch_x_pk2<0>(m, b);  // the packed family: both passes on 16-bit lanes, 16-bit tile-contiguous hand-over
-    if (rc == ESDF_NO_FIT) rc = far ? launch_x<0, true>(m, b) : launch_x<0, false>(m, b);
-  }
-  if (rc) return rc;
-  if (m->cfg.signed_dist) {  // inside obstacles the nearest free voxel is never far: plain kernels
-    {
-      StageScope sc(m, FUELMI_K_ESDF_ZY, nullptr, true);
-      int ran2;
-      rc = launch_zy_family<2>(m, b, far ? FUELMI_ESDF_PLAIN : fam, &ran2);
-      if (ran2 != FUELMI_ESDF_PLAIN) m->esdf_pk2_last = false;
-    }
-    if (rc) return rc;
-    StageScope sc(m, FUELMI_K_ESDF_X, nullptr, true);
-    rc = m->esdf_pk2_last ? launch_x_pk2<1>(m, b) : launch_x<1, false>(m, b);
+  m->esdf_family_last = p.family;
+  for (int i = 0; i < p.n && rc == FUELMI_OK; ++i) {
+    const EsdfLaunch& L = p.l[i];
+    StageScope sc(m, esdf_is_zy(L) ? FUELMI_K_ESDF_ZY : FUELMI_K_ESDF_X, nullptr, true);
+    if (esdf_is_zy(L))
+      rc = L.targ[0] == 0 ? launch_zy<0>(m, b, p, L) : (L.targ[0] == 1 ? launch_zy<1>(m, b, p, L) : launch_zy<2>(m, b, p, L));
+    else
+      rc = (L.kernel == FUELMI_ESDF_K_X ? L.targ[1] : L.targ[0]) == 0 ? launch_x<0>(m, b, p, L) : launch_x<1>(m, b, p, L);
   }
   return rc;
+}
+
+extern "C" int fuelmi_map_esdf_plan(const int dims[3], const int lo[3], const int hi[3], int family, int flags,
+                                    int out[FUELMI_ESDF_PLAN_INTS]) {
+  ARGCHK(dims && lo && hi && out && family >= FUELMI_ESDF_PLAIN && family <= FUELMI_ESDF_PLAIN32);
+  Box3 b;
+  for (int i = 0; i < 3; ++i) {
+    ARGCHK(dims[i] > 0 && 0 <= lo[i] && lo[i] <= hi[i] && hi[i] < dims[i]);
+    b.lo[i] = lo[i], b.hi[i] = hi[i];
+  }
+  EsdfPlan p;
+  const int rc = esdf_plan(dims, b, family, (flags & FUELMI_ESDF_PLAN_OPTIMISTIC) != 0, (flags & FUELMI_ESDF_PLAN_SIGNED) != 0,
+                           esdf_handover_bytes(dims[0], dims[1], dims[2]), &p);
+  if (rc) return rc;
+  for (int k = 0; k < FUELMI_ESDF_PLAN_INTS; ++k) out[k] = 0;
+  out[0] = p.n, out[1] = p.family;
+  for (int i = 0; i < p.n; ++i) {
+    const EsdfLaunch& L = p.l[i];
+    const int v[10] = {L.kernel, L.targ[0], L.targ[1], L.targ[2], L.grid, L.block, L.lds, L.ZC, L.nzc, L.z0a};
+    for (int k = 0; k < 10; ++k) out[2 + 10 * i + k] = v[k];
+  }
+  return FUELMI_OK;
 }
 
 extern "C" int fuelmi_map_set_esdf_family(fuelmi_map* m, int family) {

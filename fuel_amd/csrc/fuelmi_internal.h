@@ -113,9 +113,6 @@ struct fuelmi_map {
   u32* esdf_tmp16 = nullptr;    // packed family: 16-bit y-pass result in the x pass's tile order   2 B/voxel (esdf.hip, round 5)
   size_t esdf_tmp16_bytes = 0;
   u32 esdf_serial = 0;          // stamps the "some slab holds a source" word of an update
-  bool esdf_pk2_last = false;   // the last z/y pass wrote the 16-bit hand-over
-  Pk2Chunks pk2_ch = {};        // ... in these column tiles
-  Pk2ZChunks pk2_zch = {};      // ... written by these chunks of the z/y pass
   unsigned char* flag_rayend = nullptr;  // flag_rayend_                      1 B/voxel
   u32* ray_owner = nullptr;     // per-frame end-voxel owner (point index)     4 B/voxel
   Plane hit_bits, miss_bits;    // per-frame touched voxels
@@ -494,6 +491,7 @@ __device__ __forceinline__ double dist_with_grad_dev(const Geo& g, const float* 
 
 // ---- kernels' host launchers (defined in the .hip files) ---------------------------------------
 int esdf_update(fuelmi_map* m);
+size_t esdf_handover_bytes(int nx, int ny, int nz);  // esdf_tmp16 of a grid (0: the packed family cannot run)
 int insert_points(fuelmi_map* m, const float* xyz, int stride_bytes, int n, const double cam[3]);
 void path_cost_release(fuelmi_map* m);
 

@@ -666,11 +666,10 @@ extern "C" int fuelmi_map_create(const fuelmi_map_cfg* c, fuelmi_map** out) {
     fuelmi_set_error("hipMalloc of %zu-voxel grid failed", Npad);
     return fail(FUELMI_ENOMEM);
   }
-  if ((g.nz % 4) == 0) {  // the packed ESDF family's 16-bit hand-over (esdf.hip): column tiles of 32 x x-pairs x 128 B
-    const size_t ntiles = ((size_t)g.ny * (size_t)((g.nz + 7) / 4 + 1) + 7) / 8 + PK2_MAXCH + 1;  // (8 segments per tile, ragged chunks)
-    m->esdf_tmp16_bytes = ntiles * (size_t)(((g.nx + 1) / 2 + 63) / 64) * 64 * 128;  // (tile rows of 128 B per x-pair)
+  m->esdf_tmp16_bytes = esdf_handover_bytes(g.nx, g.ny, g.nz);
+  if (m->esdf_tmp16_bytes) {  // the packed ESDF family's 16-bit hand-over (esdf.hip)
     // (+ ~2.3 B/voxel beside the 4 B/voxel of esdf_tmp: 300 MB on the 800^2 x 200 map.  Not fatal when it does not fit: the
-    // packed family then reports ESDF_NO_FIT and the 32-bit family runs -- ADVICE r5)
+    // packed family's plan then leaves it out and the 32-bit family runs -- ADVICE r5)
     if (hipMalloc(reinterpret_cast<void**>(&m->esdf_tmp16), m->esdf_tmp16_bytes) != hipSuccess) {
       (void)hipGetLastError();
       m->esdf_tmp16 = nullptr;

@@ -91,6 +91,29 @@ class SDFMap:
         """family the z/y pass of the last updateESDF3d ran"""
         return self.L.fuelmi_map_last_esdf_family(self.h)
 
+    # fuelmi_map_esdf_plan's FUELMI_ESDF_K_*: kernel, number of template arguments, which of them is the bool FAR
+    _ESDF_KERNELS = (("k_esdf_zy", 1, None), ("k_esdf_zy4", 2, 1), ("k_esdf_zy_pk2", 3, None), ("k_esdf_x", 2, None),
+                     ("k_esdf_x4", 3, 2), ("k_esdf_x_pk2", 1, None))
+
+    @staticmethod
+    def esdfPlan(dims, lo, hi, family, optimistic=False, signed_dist=False):
+        """The launches updateESDF3d issues for the box [lo, hi] of a dims grid with `family` (ESDF_PLAIN / _FAR /
+        _PLAIN32; fuelmi_map_esdf_plan, host only): {"family": what lastEsdfFamily() then reports, "launches": [{"kernel",
+        "grid", "block", "lds", "ZC", "nzc", "z0a"}, ...] in order z/y+, x+ (, z/y-, x- for signed maps)}.  Raises
+        FuelmiError for a box the update refuses."""
+        out = (C.c_int * 42)()
+        ints = lambda v: (C.c_int * 3)(*[int(a) for a in v])
+        flags = (1 if optimistic else 0) | (2 if signed_dist else 0)
+        check(lib().fuelmi_map_esdf_plan(ints(dims), ints(lo), ints(hi), int(family), flags, out))
+        launches = []
+        for i in range(out[0]):
+            k, a0, a1, a2, grid, block, lds, zc, nzc, z0a = out[2 + 10 * i:12 + 10 * i]
+            kname, nt, far = SDFMap._ESDF_KERNELS[k]
+            targs = [("true" if a else "false") if j == far else str(a) for j, a in enumerate((a0, a1, a2)[:nt])]
+            name = "%s<%s>" % (kname, ", ".join(targs))
+            launches.append({"kernel": name, "grid": grid, "block": block, "lds": lds, "ZC": zc, "nzc": nzc, "z0a": z0a})
+        return {"family": out[1], "launches": launches}
+
     def lastInflateKernel(self):
         """0: the fused inflation kernel ran in the last clearAndInflateLocalMap, 1: the factored pair"""
         return self.L.fuelmi_map_last_inflate_kernel(self.h)

@@ -159,6 +159,24 @@ int fuelmi_map_update_esdf(fuelmi_map* m);
 enum { FUELMI_ESDF_AUTO = -1, FUELMI_ESDF_PLAIN = 0, FUELMI_ESDF_FAR = 1, FUELMI_ESDF_PLAIN32 = 2 };
 int fuelmi_map_set_esdf_family(fuelmi_map* m, int family);
 int fuelmi_map_last_esdf_family(const fuelmi_map* m);
+/* The launches fuelmi_map_update_esdf issues for a box (host only, no device needed; the plan the update itself runs).
+ * dims: grid voxels; lo / hi: the inclusive box; family: PLAIN / FAR / PLAIN32 (AUTO is resolved per update from the
+ * statistic and refused here); flags: FUELMI_ESDF_PLAN_OPTIMISTIC | FUELMI_ESDF_PLAN_SIGNED.  The hand-over buffer of the
+ * packed family is taken at the size a map of dims allocates.  out[0] = launches (2, or 4 with SIGNED), out[1] = the
+ * family fuelmi_map_last_esdf_family then reports, then 10 ints per launch in order z/y+, x+, z/y-, x-: kernel
+ * (FUELMI_ESDF_K_*), its three template arguments in declaration order (0 where it has fewer), grid, block, dynamic LDS
+ * bytes, ZC, nzc, z0a.  FUELMI_ELIMIT, with the update's message, for a box the update refuses. */
+enum {
+  FUELMI_ESDF_K_ZY = 0,     /* k_esdf_zy<MODE>                  (z/y kernels first) */
+  FUELMI_ESDF_K_ZY4 = 1,    /* k_esdf_zy4<MODE, FAR> */
+  FUELMI_ESDF_K_ZY_PK2 = 2, /* k_esdf_zy_pk2<MODE, G, NW> */
+  FUELMI_ESDF_K_X = 3,      /* k_esdf_x<S, OUT> */
+  FUELMI_ESDF_K_X4 = 4,     /* k_esdf_x4<OUT, SEGS, FAR> */
+  FUELMI_ESDF_K_X_PK2 = 5   /* k_esdf_x_pk2<OUT> */
+};
+enum { FUELMI_ESDF_PLAN_OPTIMISTIC = 1, FUELMI_ESDF_PLAN_SIGNED = 2, FUELMI_ESDF_PLAN_INTS = 42 };
+int fuelmi_map_esdf_plan(const int dims[3], const int lo[3], const int hi[3], int family, int flags,
+                         int out[FUELMI_ESDF_PLAN_INTS]);
 /* which inflation kernels the last fuelmi_map_inflate_local ran: 0 the fused single launch, 1 the factored y/z + x pair
  * (chosen by the size of the box's address range; -1 before the first call).  For tests that must know which code ran. */
 int fuelmi_map_last_inflate_kernel(const fuelmi_map* m);

@@ -31,6 +31,15 @@ def explored_oracle_map(map_size, n_obstacles, n_frames, seed=42, cam_seed=7, wi
     return m, truth, frames, (box_min, box_max)
 
 
+def esdf_plan_kernels(fa, gm, lo, hi):
+    """the kernels the last updateESDF3d of gm ran over the box [lo, hi]: fuelmi_map_esdf_plan with the family that
+    update reported (a PLAIN update the packed pair did not take reports PLAIN32 and ran PLAIN32's plan)"""
+    fam = gm.lastEsdfFamily()
+    p = fa.SDFMap.esdfPlan(gm.nvox, lo, hi, fam, gm.cfg.optimistic, gm.cfg.signed_dist)
+    assert p["family"] == fam
+    return [launch["kernel"] for launch in p["launches"]]
+
+
 def full_box(nvox):
     return (0, 0, 0), (nvox[0] - 1, nvox[1] - 1, nvox[2] - 1)
 

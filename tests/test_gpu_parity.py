@@ -933,10 +933,16 @@ def test_error_paths_of_the_front_end_calls(fa):
 
 
 @pytest.mark.gpu
-def test_esdf_on_a_very_long_x_line(fa):
-    """x lines of 1300 voxels: the x pass switches to its 16-column tile (the 32-column one would not fit
-    the LDS); result against the oracle."""
-    map_size = (130.0, 4.0, 4.0)
+@pytest.mark.parametrize("map_size, family, x_kernel", [
+    ((130.0, 4.0, 4.0), 2, "k_esdf_x4<0, 4, false>"),   # 1300 voxels: the 16-column tile (the 32-column one does not fit)
+    ((130.0, 4.0, 4.0), None, "k_esdf_x_pk2<0>"),       # ... the family of a fresh map: packed
+    ((118.0, 0.8, 0.8), 1, "k_esdf_x4<0, 8, false>"),   # FAR: the minima do not fit beside the 32-column tile
+    ((230.0, 0.8, 0.8), 1, "k_esdf_x4<0, 4, false>"),   # ... nor beside the 16-column one
+    ((250.0, 0.8, 0.8), None, "k_esdf_x<8, 0>"),        # past the vector tiles: the scalar 8-column one
+], ids=["1300-plain32", "1300", "1180-far", "2300-far", "2500"])
+def test_esdf_on_a_very_long_x_line(fa, map_size, family, x_kernel):
+    """x lines of 1 180 - 2 500 voxels: the x pass switches to narrower tiles (the plan's row is asserted); result
+    against the oracle."""
     om = fo.OracleMap(map_size)
     rng = np.random.default_rng(21)
     occ = om.occ.reshape(om.nvox)
@@ -945,6 +951,8 @@ def test_esdf_on_a_very_long_x_line(fa):
     occ[idx[:, 0], idx[:, 1], idx[:, 2]] = om.l_occ + 0.5         # a few obstacles far apart along x
     occ[900:, :, :] = om.unknown_value                            # and an unknown end
     gm = fa.SDFMap(map_size)
+    if family is not None:
+        gm.setEsdfFamily(family)
     gm.uploadOccupancy(om.occ)
     lo, hi = helpers.full_box(om.nvox)
     om.set_local_bound(lo, hi)
@@ -953,5 +961,6 @@ def test_esdf_on_a_very_long_x_line(fa):
     om.update_esdf()
     gm.clearAndInflateLocalMap()
     gm.updateESDF3d()
+    assert helpers.esdf_plan_kernels(fa, gm, lo, hi)[1] == x_kernel
     assert_map_equal(om, gm)
     gm.close()

@@ -210,22 +210,40 @@ def test_sparse_map_long_scans(fa, esdf_kernels):
     gm.close()
 
 
-@pytest.mark.parametrize("optimistic", [0, 1])
-def test_esdf_kernel_families_agree_on_ragged_boxes(fa, optimistic, esdf_kernels):
+@pytest.mark.parametrize("optimistic, signed, map_size", [(0, 0, (9.0, 7.0, 4.0)), (1, 0, (9.0, 7.0, 4.0)),
+                                                          (0, 0, (3.2, 84.0, 2.4)), (0, 1, (3.2, 84.0, 2.4))],
+                         ids=["0", "1", "long_y", "long_y_signed"])
+def test_esdf_kernel_families_agree_on_ragged_boxes(fa, optimistic, signed, map_size, esdf_kernels):
     """half-explored world (short scans) and boxes that are not 4-aligned in z, not 8-aligned in x / y: the block
-    minima of the FAR kernels have partial last blocks and garbage columns outside the box"""
-    om, _, _, box = helpers.explored_oracle_map((9.0, 7.0, 4.0), 14, 25, optimistic=optimistic)
-    gm = fa.SDFMap(tuple(om.cfg.map_size), box[0], box[1], optimistic=optimistic)
+    minima of the FAR kernels have partial last blocks and garbage columns outside the box.  The thin map's y lines of
+    833 - 840 voxels take the packed z/y pass's 2-segment chunks (k_esdf_zy_pk2<MODE, 2, NW>), in both signs."""
+    if map_size[1] < 80:
+        om, _, _, box = helpers.explored_oracle_map(map_size, 14, 25, optimistic=optimistic, signed_dist=signed)
+    else:  # (the camera fixtures need a room: the thin map gets seeded obstacles and an unknown end instead)
+        om, box = fo.OracleMap(map_size, optimistic=optimistic, signed_dist=signed), (None, None)
+        rng = np.random.default_rng(5)
+        occ = om.occ.reshape(om.nvox)
+        occ[:] = om.l_min
+        idx = rng.integers(0, om.nvox, size=(80, 3))
+        occ[idx[:, 0], idx[:, 1], idx[:, 2]] = om.l_occ + 0.5
+        occ[:, 600:, :] = om.unknown_value
+    gm = fa.SDFMap(tuple(om.cfg.map_size), box[0], box[1], optimistic=optimistic, signed_dist=signed)
     gm.uploadOccupancy(om.occ)
     nv = om.nvox
     for lo, hi in [helpers.full_box(nv), ((3, 5, 1), (nv[0] - 6, nv[1] - 2, nv[2] - 3)), ((17, 9, 2), (58, 43, 30)),
                    ((0, 0, 5), (9, 8, 6))]:
+        if any(h >= n for h, n in zip(hi, nv)):
+            continue  # (the room's boxes that leave the thin map)
         om.set_local_bound(lo, hi)
         gm.setLocalBound(lo, hi)
         om.inflate_local()
         om.update_esdf()
         gm.clearAndInflateLocalMap()
         gm.updateESDF3d()
+        if hi[1] - lo[1] + 1 > 832:
+            packed = [k for k in helpers.esdf_plan_kernels(fa, gm, lo, hi) if k.startswith("k_esdf_zy_pk2")]
+            want = {"plain": ["k_esdf_zy_pk2<0, 2, 2>"], "far": [], "plain32": []}[esdf_kernels]
+            assert packed == want + (["k_esdf_zy_pk2<2, 2, 2>"] if signed and esdf_kernels != "plain32" else [])
         assert_map_equal(om, gm, (lo, hi))
     gm.close()
 
