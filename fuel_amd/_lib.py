@@ -89,6 +89,16 @@ class PathCfg(C.Structure):
                 ("max_path_points", C.c_int)]
 
 
+class RefineCfg(C.Structure):
+    """fuelmi_refine_cfg: refineLocalTour's edge searches, ViewNode::vm_ / yd_ / w_dir_, the polyline."""
+    _fields_ = [("path", PathCfg), ("vm", C.c_double), ("yd", C.c_double), ("w_dir", C.c_double),
+                ("tour_lattice_res", C.c_double), ("max_tour_points", C.c_int), ("flags", C.c_int)]
+
+
+REFINE_LAST_ARGMIN = 1
+REFINE_MAX_LAYERS, REFINE_MAX_NODES = 64, 256
+
+
 class BsplineCfg(C.Structure):
     _fields_ = [(n, C.c_double) for n in
                 ("ld_smooth", "ld_dist", "ld_feasi", "ld_start", "ld_end", "ld_guide", "ld_waypt",
@@ -192,6 +202,7 @@ SYMBOLS = {
     "fuelmi_frontier_get_flags": (C.c_int, [_P, C.c_void_p]),
     "fuelmi_map_path_costs": (C.c_int, [_P, C.POINTER(PathCfg), C.c_int, _dp, _dp, _dp, _ip, _ip, _dp]),
     "fuelmi_map_path_stats": (C.c_int, [_P, _ip]),
+    "fuelmi_map_refine_tours": (C.c_int, [_P, C.POINTER(RefineCfg), C.c_int, _dp, _ip, _ip, _dp, _ip, _dp, _ip, _dp]),
     "fuelmi_bspline_cost_grad": (C.c_int, [_P, C.POINTER(BsplineCfg), C.POINTER(BsplineBatch), _dp, _dp]),
     "fuelmi_bspline_optimize": (C.c_int, [_P, C.POINTER(BsplineCfg), C.POINTER(BsplineBatch), C.c_int, C.c_double, _dp, _dp,
                                 C.POINTER(C.c_int)]),

@@ -216,6 +216,9 @@ struct fuelmi_map {
   void* path_dev = nullptr;
   size_t path_dev_bytes = 0;
   int path_stats[4] = {0, 0, 0, 0};  // fuelmi_map_path_stats
+  // grow-only device scratch of fuelmi_map_refine_tours (refine.hip): problems in, choices / costs out
+  void* refine_dev = nullptr;
+  size_t refine_dev_bytes = 0;
   unsigned long long fusion_count = 0;  // fusions / uploads queued so far (a search notices one queued behind its back)
   unsigned profile_mask = 0;
   ProfileSlot prof[FUELMI_K_COUNT];
@@ -493,6 +496,16 @@ __device__ __forceinline__ double dist_with_grad_dev(const Geo& g, const float* 
 int esdf_update(fuelmi_map* m);
 size_t esdf_handover_bytes(int nx, int ny, int nz);  // esdf_tmp16 of a grid (0: the packed family cannot run)
 int insert_points(fuelmi_map* m, const float* xyz, int stride_bytes, int n, const double cam[3]);
-void path_cost_release(fuelmi_map* m);
+void path_cost_release(fuelmi_map* m);  // the path and refinement scratch
+// device results of one path_cost_enqueue, in the map's path scratch: length / kind / path_len per pair, paths
+// [n][maxp][3] (nullptr when maxp is 0)
+struct PathRun {
+  double* length = nullptr;
+  int* kind = nullptr;
+  int* plen = nullptr;
+  double* path = nullptr;
+};
+int path_cost_enqueue(fuelmi_map* m, const fuelmi_path_cfg* cfg, int n, const double* p1_xyz, const double* p2_xyz,
+                      int maxp, PathRun& out);
 
 #endif

@@ -436,21 +436,19 @@ void path_cost_release(fuelmi_map* m) {
   if (m->path_dev) (void)hipFree(m->path_dev);
   m->path_dev = nullptr;
   m->path_dev_bytes = 0;
+  if (m->refine_dev) (void)hipFree(m->refine_dev);
+  m->refine_dev = nullptr;
+  m->refine_dev_bytes = 0;
 }
 
-extern "C" int fuelmi_map_path_costs(fuelmi_map* m, const fuelmi_path_cfg* cfg, int n, const double* p1_xyz,
-                                     const double* p2_xyz, double* length, int* kind, int* path_len, double* path_xyz) {
-  ARGCHK(m && cfg);
-  ARGCHK(n >= 0);
-  if (n == 0) return FUELMI_OK;
-  ARGCHK(p1_xyz && p2_xyz && length && kind && path_len);
-  ARGCHK(cfg->lattice_res > 0.0 && cfg->edge_step > 0.0 && std::isfinite(cfg->lattice_res) && std::isfinite(cfg->edge_step));
-  ARGCHK(!path_xyz || cfg->max_path_points >= 0);
-  for (long k = 0; k < 3L * n; ++k) ARGCHK(std::fabs(p1_xyz[k]) < 1e7 && std::fabs(p2_xyz[k]) < 1e7);
+// The searches of n pairs queued on the map's stream: source dedup, chunks, k_path_los / _mask / _relax / _goal.  The
+// results stay in the map's path scratch (valid until the next enqueue); fuelmi_map_path_stats' counters accumulate.
+// The caller has checked the arguments (finite, |coordinate| < 1e7) and n > 0.
+
+int path_cost_enqueue(fuelmi_map* m, const fuelmi_path_cfg* cfg, int n, const double* p1_xyz, const double* p2_xyz,
+                      int maxp, PathRun& out) {
   HIPCHK(hipSetDevice(m->device));
   const Geo& g = m->g;
-  const int maxp = path_xyz ? cfg->max_path_points : 0;
-  for (int& v : m->path_stats) v = 0;
 
   PArgs A;
   A.infl = m->infl_bits.p;
@@ -567,7 +565,7 @@ extern "C" int fuelmi_map_path_costs(fuelmi_map* m, const fuelmi_path_cfg* cfg, 
     if (pairs_of[src_idx[i]].empty()) srcs.push_back(src_idx[i]);
     pairs_of[src_idx[i]].push_back(i);
   }
-  m->path_stats[2] = (int)srcs.size();
+  m->path_stats[2] += (int)srcs.size();
 
   // ---- chunks of sources: lattices that fit the node budget together ----
   std::vector<int> gp, gs;
@@ -642,10 +640,33 @@ extern "C" int fuelmi_map_path_costs(fuelmi_map* m, const fuelmi_path_cfg* cfg, 
     HIPCHK(hipGetLastError());
     s0 = s1;
   }
-  HIPCHK(hipMemcpyAsync(length, d_len, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(kind, d_kind, sizeof(int) * n, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(path_len, d_plen, sizeof(int) * n, hipMemcpyDeviceToHost, st));
-  if (d_path) HIPCHK(hipMemcpyAsync(path_xyz, d_path, sizeof(double) * 3 * maxp * (size_t)n, hipMemcpyDeviceToHost, st));
+  out.length = d_len;
+  out.kind = d_kind;
+  out.plen = d_plen;
+  out.path = d_path;
+  return FUELMI_OK;
+}
+
+extern "C" int fuelmi_map_path_costs(fuelmi_map* m, const fuelmi_path_cfg* cfg, int n, const double* p1_xyz,
+                                     const double* p2_xyz, double* length, int* kind, int* path_len, double* path_xyz) {
+  ARGCHK(m && cfg);
+  ARGCHK(n >= 0);
+  if (n == 0) return FUELMI_OK;
+  ARGCHK(p1_xyz && p2_xyz && length && kind && path_len);
+  ARGCHK(cfg->lattice_res > 0.0 && cfg->edge_step > 0.0 && std::isfinite(cfg->lattice_res) && std::isfinite(cfg->edge_step));
+  ARGCHK(!path_xyz || cfg->max_path_points >= 0);
+  for (long k = 0; k < 3L * n; ++k) ARGCHK(std::fabs(p1_xyz[k]) < 1e7 && std::fabs(p2_xyz[k]) < 1e7);
+  HIPCHK(hipSetDevice(m->device));
+  const int maxp = path_xyz ? cfg->max_path_points : 0;
+  for (int& v : m->path_stats) v = 0;
+  PathRun run;
+  const int rc = path_cost_enqueue(m, cfg, n, p1_xyz, p2_xyz, maxp, run);
+  if (rc != FUELMI_OK) return rc;
+  hipStream_t st = m->stream;
+  HIPCHK(hipMemcpyAsync(length, run.length, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(kind, run.kind, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(path_len, run.plen, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+  if (run.path) HIPCHK(hipMemcpyAsync(path_xyz, run.path, sizeof(double) * 3 * maxp * (size_t)n, hipMemcpyDeviceToHost, st));
   HIPCHK(stream_wait(st));
   bool over = false;
   for (int i = 0; i < n; ++i) {

@@ -85,6 +85,19 @@ public:
   void getPathForTour(const Vector3d& pos, const vector<int>& frontier_ids, vector<Vector3d>& path);
   void setNextFrontier(const int& id);
 
+  // addition: FastExplorationManager::refineLocalTour (fast_exploration_manager.cpp:429-503) on the device
+  // (fuelmi_map_refine_tours): the first node of each layer of n_points / n_yaws (getViewpointsInfo's output) that the
+  // cheapest route from the current state passes, and with refined_tour the polyline the reference draws (lattice
+  // 0.2).  Needs exploration/vm, exploration/yd, exploration/w_dir; false (with a message) when they are unset, a
+  // layer is empty or the last layer cannot be reached.
+  bool refineLocalTour(const Vector3d& cur_pos, const Vector3d& cur_vel, const Vector3d& cur_yaw,
+                       const vector<vector<Vector3d>>& n_points, const vector<vector<double>>& n_yaws,
+                       vector<Vector3d>& refined_pts, vector<double>& refined_yaws,
+                       vector<Vector3d>* refined_tour = nullptr);
+  // the single-destination branch (:197-208): the index of the cheapest of points (first on ties)
+  bool refineSingleDestination(const Vector3d& cur_pos, const Vector3d& cur_vel, const Vector3d& cur_yaw,
+                               const vector<Vector3d>& points, const vector<double>& yaws, int& min_cost_id);
+
   // camera model for the callers (field-of-view drawing); the device samples viewpoints with its own copy
   // of the same perception_utils/* parameters
   shared_ptr<PerceptionUtils> percep_utils_;
@@ -102,6 +115,10 @@ private:
   // ViewNode::computeCost (graph_node.cpp:63-88) with the path length already known
   double hostCost(double length, const Vector3d& p1, const Vector3d& p2, double y1, double y2,
                   const Vector3d& v1) const;
+  // one fuelmi_map_refine_tours problem; choice per layer
+  bool deviceRefine(const Vector3d& cur_pos, const Vector3d& cur_vel, double cur_yaw,
+                    const vector<vector<Vector3d>>& n_points, const vector<vector<double>>& n_yaws, int flags,
+                    vector<int>& choice, vector<Vector3d>* tour);
 
   fuelmi_frontier* dev_;
   shared_ptr<EDTEnvironment> edt_env_;
@@ -109,7 +126,7 @@ private:
   double resolution_, min_candidate_dist_;
   bool have_viewpoints_;  // frontier/candidate_* and perception_utils/* were all given
   bool device_path_cost_ = false;  // frontier/device_path_cost (addition, default false)
-  double vm_ = -1.0, yd_ = -1.0, w_dir_ = -1.0;  // exploration/vm, exploration/yd, exploration/w_dir (with the opt-in)
+  double vm_ = -1.0, yd_ = -1.0, w_dir_ = -1.0;  // exploration/vm, exploration/yd, exploration/w_dir (-1: unset)
   bool order_fallback_logged_ = false;  // the first address-order fallback of reference_order = 2 has been reported
   vector<int> removed_ids_;
   list<Frontier> frontiers_, dormant_frontiers_, tmp_frontiers_;

@@ -324,13 +324,12 @@ FrontierFinder::FrontierFinder(const shared_ptr<EDTEnvironment>& edt, ros::NodeH
   c.reference_order = ref_order;
   // addition: frontier/device_path_cost.  true: the cost-matrix group's path searches run batched on the device
   // (fuelmi_map_path_costs) and computeCost's remaining terms need the exploration manager's ViewNode parameters
-  // (fast_exploration_manager.cpp:55-59); false (default): ViewNode as in the reference
+  // (fast_exploration_manager.cpp:55-59); false (default): ViewNode as in the reference.  refineLocalTour needs the
+  // same parameters
   nh.param("frontier/device_path_cost", device_path_cost_, false);
-  if (device_path_cost_) {
-    nh.param("exploration/vm", vm_, -1.0);
-    nh.param("exploration/yd", yd_, -1.0);
-    nh.param("exploration/w_dir", w_dir_, -1.0);
-  }
+  nh.param("exploration/vm", vm_, -1.0);
+  nh.param("exploration/yd", yd_, -1.0);
+  nh.param("exploration/w_dir", w_dir_, -1.0);
   warn("fuelmi_frontier_create", fuelmi_frontier_create(edt_env_->sdf_map_->device(), &c, &dev_));
   // viewpoint sampling parameters (frontier_finder.cpp:32-43, perception_utils.cpp:7-11)
   fuelmi_viewpoint_cfg v;
@@ -639,6 +638,95 @@ void FrontierFinder::getPathForTour(const Vector3d& pos, const vector<int>& fron
     std::advance(p, frontier_ids[k + 1]);
     path.insert(path.end(), p->begin(), p->end());
   }
+}
+
+bool FrontierFinder::deviceRefine(const Vector3d& cur_pos, const Vector3d& cur_vel, double cur_yaw,
+                                  const vector<vector<Vector3d>>& n_points, const vector<vector<double>>& n_yaws,
+                                  int flags, vector<int>& choice, vector<Vector3d>* tour) {
+  if (!(vm_ > 0.0 && yd_ > 0.0 && w_dir_ >= 0.0)) {
+    std::fprintf(stderr, "[fuelmi facade] FrontierFinder::refineLocalTour needs exploration/vm, exploration/yd and "
+                 "exploration/w_dir (vm %g, yd %g, w_dir %g)\n", vm_, yd_, w_dir_);
+    return false;
+  }
+  if (n_points.empty() || n_points.size() != n_yaws.size()) {
+    std::fprintf(stderr, "[fuelmi facade] FrontierFinder::refineLocalTour: %zu layers of points, %zu of yaws\n",
+                 n_points.size(), n_yaws.size());
+    return false;
+  }
+  const int L = (int)n_points.size();
+  double start[7] = {cur_pos(0), cur_pos(1), cur_pos(2), cur_vel(0), cur_vel(1), cur_vel(2), cur_yaw};
+  int layer_ptr[2] = {0, L};
+  vector<int> node_ptr(1, 0);
+  vector<double> nodes;
+  for (int i = 0; i < L; ++i) {
+    if (n_points[i].size() != n_yaws[i].size()) {
+      std::fprintf(stderr, "[fuelmi facade] FrontierFinder::refineLocalTour: layer %d has %zu points, %zu yaws\n", i,
+                   n_points[i].size(), n_yaws[i].size());
+      return false;
+    }
+    for (size_t j = 0; j < n_points[i].size(); ++j) {
+      for (int k = 0; k < 3; ++k) nodes.push_back(n_points[i][j](k));
+      nodes.push_back(n_yaws[i][j]);
+    }
+    node_ptr.push_back(node_ptr.back() + (int)n_points[i].size());
+  }
+  fuelmi_refine_cfg c;
+  c.path.lattice_res = 0.4;     // graph_node.cpp:49
+  c.path.edge_step = 0.1;       // astar2.cpp:105
+  c.path.no_path_cost = 1000.0;  // graph_node.cpp:60
+  c.path.max_path_points = 0;
+  c.vm = vm_, c.yd = yd_, c.w_dir = w_dir_;
+  c.tour_lattice_res = tour ? 0.2 : 0.0;  // fast_exploration_manager.cpp:491
+  c.max_tour_points = 1024;
+  c.flags = flags;
+  choice.assign(L, -1);
+  double cost = 0.0;
+  int tlen = 0;
+  vector<double> xyz;
+  fuelmi_map* m = edt_env_->sdf_map_->device();
+  int rc = FUELMI_OK;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    if (tour) xyz.assign((size_t)c.max_tour_points * 3, 0.0);
+    rc = fuelmi_map_refine_tours(m, &c, 1, start, layer_ptr, node_ptr.data(), nodes.data(), choice.data(), &cost,
+                                 tour ? &tlen : nullptr, tour ? xyz.data() : nullptr);
+    if (rc != FUELMI_ELIMIT || !tour || tlen <= c.max_tour_points) break;
+    c.max_tour_points = tlen;  // tour_len holds the full count: grow once
+  }
+  warn("fuelmi_map_refine_tours", rc);
+  if (rc != FUELMI_OK) return false;
+  if (tour) {
+    tour->resize(tlen);
+    for (int r = 0; r < tlen; ++r) (*tour)[r] = Vector3d(xyz[3 * r], xyz[3 * r + 1], xyz[3 * r + 2]);
+  }
+  if (choice[0] < 0) {
+    std::fprintf(stderr, "[fuelmi facade] FrontierFinder::refineLocalTour: the last layer is not reachable\n");
+    return false;
+  }
+  return true;
+}
+
+bool FrontierFinder::refineLocalTour(const Vector3d& cur_pos, const Vector3d& cur_vel, const Vector3d& cur_yaw,
+                                     const vector<vector<Vector3d>>& n_points, const vector<vector<double>>& n_yaws,
+                                     vector<Vector3d>& refined_pts, vector<double>& refined_yaws,
+                                     vector<Vector3d>* refined_tour) {  // fast_exploration_manager.cpp:429-503
+  vector<int> choice;
+  if (!deviceRefine(cur_pos, cur_vel, cur_yaw(0), n_points, n_yaws, 0, choice, refined_tour)) return false;
+  for (size_t i = 0; i < choice.size(); ++i) {
+    refined_pts.push_back(n_points[i][choice[i]]);
+    refined_yaws.push_back(n_yaws[i][choice[i]]);
+  }
+  return true;
+}
+
+bool FrontierFinder::refineSingleDestination(const Vector3d& cur_pos, const Vector3d& cur_vel, const Vector3d& cur_yaw,
+                                             const vector<Vector3d>& points, const vector<double>& yaws,
+                                             int& min_cost_id) {  // fast_exploration_manager.cpp:197-208
+  vector<int> choice;
+  min_cost_id = -1;
+  if (!deviceRefine(cur_pos, cur_vel, cur_yaw(0), {points}, {yaws}, FUELMI_REFINE_LAST_ARGMIN, choice, nullptr))
+    return false;
+  min_cost_id = choice[0];
+  return true;
 }
 
 void FrontierFinder::setNextFrontier(const int& id) {  // declared by the reference, never defined there

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BsplineBatch, BsplineCfg, FrontierCfg, MapCfg, MapInfo, PathCfg, check, lib)
+from ._lib import (BsplineBatch, BsplineCfg, FrontierCfg, MapCfg, MapInfo, PathCfg, RefineCfg, check, lib)
 
 # exploration.launch / algorithm.xml defaults (exploration_manager/launch/algorithm.xml:33-59,170-181)
 DEFAULT_MAP = dict(resolution=0.1, ground_height=-1.0, obstacles_inflation=0.199,
@@ -280,6 +280,38 @@ class SDFMap:
         st = np.zeros(4, dtype=np.int32)
         check(self.L.fuelmi_map_path_stats(self.h, _ip(st)))
         return dict(zip(("launches", "max_chunk_launches", "sources", "chunks"), (int(v) for v in st)))
+
+    # --- FastExplorationManager::refineLocalTour for a batch of problems (include/fuelmi.h fuelmi_map_refine_tours) ---
+    def refine_tours(self, problems, vm, yd, w_dir, res=0.4, edge_step=0.1, no_path_cost=1000.0, tour_res=0.0,
+                     max_tour_points=1024, last_argmin=False):
+        """problems: list of (pos [3], vel [3], yaw, layers), layers a list of [k, 4] arrays (x, y, z, yaw).
+        Returns (choices: list of int arrays, one index per layer, -1 when unreached; costs [B], +inf when unreached;
+        tours: list of [k, 3] arrays when tour_res > 0, else None).  A polyline longer than max_tour_points raises
+        FuelmiError (FUELMI_ELIMIT)."""
+        B = len(problems)
+        start = np.zeros((B, 7))
+        layer_ptr, node_ptr, nodes = [0], [0], []
+        for b, (pos, vel, yaw, layers) in enumerate(problems):
+            start[b, :3], start[b, 3:6], start[b, 6] = pos, vel, yaw
+            for layer in layers:
+                layer = np.asarray(layer, dtype=np.float64).reshape(-1, 4)
+                nodes.append(layer)
+                node_ptr.append(node_ptr[-1] + len(layer))
+            layer_ptr.append(layer_ptr[-1] + len(layers))
+        nodes = np.ascontiguousarray(np.concatenate(nodes) if nodes else np.zeros((0, 4)))
+        layer_ptr = np.array(layer_ptr, dtype=np.int32)
+        node_ptr = np.array(node_ptr, dtype=np.int32)
+        c = RefineCfg(PathCfg(float(res), float(edge_step), float(no_path_cost), 0), float(vm), float(yd), float(w_dir),
+                      float(tour_res), int(max_tour_points), _lib.REFINE_LAST_ARGMIN if last_argmin else 0)
+        choice = np.empty(layer_ptr[-1], dtype=np.int32)
+        cost = np.empty(B)
+        tlen = np.zeros(B, dtype=np.int32) if tour_res > 0 else None
+        txyz = np.zeros((B, max_tour_points, 3)) if tour_res > 0 else None
+        check(self.L.fuelmi_map_refine_tours(self.h, C.byref(c), B, _dp(start), _ip(layer_ptr), _ip(node_ptr),
+                                             _dp(nodes), _ip(choice), _dp(cost), _ip(tlen), _dp(txyz)))
+        choices = [choice[layer_ptr[b]:layer_ptr[b + 1]].copy() for b in range(B)]
+        tours = None if txyz is None else [txyz[b, :tlen[b]].copy() for b in range(B)]
+        return choices, cost, tours
 
     # --- measurement ---
     def timerBegin(self):

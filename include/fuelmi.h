@@ -370,9 +370,50 @@ typedef struct {
  * the call fills length / kind / path_len (and the paths that fit) and returns FUELMI_ELIMIT. */
 int fuelmi_map_path_costs(fuelmi_map* m, const fuelmi_path_cfg* cfg, int n, const double* p1_xyz,
                           const double* p2_xyz, double* length, int* kind, int* path_len, double* path_xyz);
-/* what the last fuelmi_map_path_costs on this map did: [0] relaxation launches in all, [1] the most of one chunk of
- * sources, [2] lattice sources, [3] chunks */
+/* what the last fuelmi_map_path_costs or fuelmi_map_refine_tours on this map did: [0] relaxation launches in all, [1]
+ * the most of one chunk of sources, [2] lattice sources, [3] chunks.  After a refinement with a polyline: the sums
+ * (the most: the larger) over its edge searches and its polyline legs. */
 int fuelmi_map_path_stats(const fuelmi_map* m, int stats[4]);
+
+/* ------------------------------------------------------------------------------------------
+ * Local tour refinement: FastExplorationManager::refineLocalTour (exploration_manager/src/
+ * fast_exploration_manager.cpp:429-503) and the single-destination choice (:185-220), for n_prob independent
+ * problems in one call.  Problem b: node 0 = the start (pos, vel, yaw), then its layers in order (one per cluster
+ * of the global tour, nodes = the top viewpoints, FrontierFinder::getViewpointsInfo).  Every node of layer i-1 links
+ * to every node of layer i; the last layer keeps only its first node (:459-462) unless FUELMI_REFINE_LAST_ARGMIN.
+ * Edge cost = ViewNode::computeCost (active_perception/src/graph_node.cpp:63-88) on the edge's searchPath length
+ * (fuelmi_map_path_costs, cfg.path): max(length / vm + [|v| > 1e-3] w_dir acos(v^ . normalized(p2 - p1)),
+ * min(|dy|, 2 pi - |dy|) / yd) with std::max's NaN rule (a NaN edge is never taken) and real Eigen's normalized()
+ * (a zero-length edge adds w_dir pi / 2); only the start has a velocity.  Search = GraphSearch::DijkstraSearch
+ * (graph_search.h) as a layer-by-layer min-plus pass: g(start) = 0, g = 1e6 elsewhere, a candidate is taken only
+ * when strictly below; ties: smallest total, then smallest g(u), then smallest u.  Goal: the last layer's node 0, or
+ * with FUELMI_REFINE_LAST_ARGMIN its first cheapest node below 100000 (:199-208).  An unreached goal is no error:
+ * cost +inf, every choice -1.
+ * Polyline (:486-497, when tour_lattice_res > 0 and tour_len is given): [start], then per chosen node the whole
+ * path_costs path from the previous point at tour_lattice_res (shared joints appear twice, a no-path leg gives
+ * {p1, p2}), or the node alone for a leg of length 0; an unreached problem: [start].
+ * Limits, checked on the host before the map is touched: layers per problem <= FUELMI_REFINE_MAX_LAYERS, nodes per
+ * layer <= FUELMI_REFINE_MAX_NODES, the edge count of the call < 2^31 (FUELMI_ELIMIT); a problem without layers or a
+ * layer without nodes is FUELMI_EINVAL.  Same thread rule as the mutators.
+ * ---------------------------------------------------------------------------------------- */
+#define FUELMI_REFINE_LAST_ARGMIN 1 /* single-destination branch: keep the whole last layer, goal = its argmin */
+#define FUELMI_REFINE_MAX_LAYERS 64
+#define FUELMI_REFINE_MAX_NODES 256
+typedef struct {
+  fuelmi_path_cfg path;    /* edge searches: lattice_res 0.4, edge_step 0.1, no_path_cost 1000 (max_path_points unused) */
+  double vm, yd, w_dir;    /* ViewNode::vm_, yd_, w_dir_ (exploration/vm, exploration/yd, exploration/w_dir) */
+  double tour_lattice_res; /* 0.2 for the refined-tour polyline (:491); <= 0: no polyline */
+  int max_tour_points;     /* per problem, for tour_xyz */
+  int flags;               /* FUELMI_REFINE_* */
+} fuelmi_refine_cfg;
+/* start [n_prob][7] = pos xyz, vel xyz, yaw; problem b owns layers layer_ptr[b] .. layer_ptr[b+1]-1 (layer_ptr[0] =
+ * 0), layer l owns nodes node_ptr[l] .. node_ptr[l+1]-1 (node_ptr[0] = 0) of nodes [N][4] = x y z yaw.  Out:
+ * choice [n_layers] (index within its layer, -1 when unreached), cost [n_prob] (the goal's g, +inf when unreached);
+ * tour_len [n_prob] (always the full count) and tour_xyz [n_prob][max_tour_points][3] may be NULL.  A polyline
+ * longer than max_tour_points fills what fits and the call returns FUELMI_ELIMIT. */
+int fuelmi_map_refine_tours(fuelmi_map* m, const fuelmi_refine_cfg* cfg, int n_prob, const double* start,
+                            const int* layer_ptr, const int* node_ptr, const double* nodes, int* choice, double* cost,
+                            int* tour_len, double* tour_xyz);
 
 /* ------------------------------------------------------------------------------------------
  * B-spline cost + gradient: replaces BsplineOptimizer::combineCost and the calc*Cost terms
