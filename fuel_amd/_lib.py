@@ -99,6 +99,15 @@ REFINE_LAST_ARGMIN = 1
 REFINE_MAX_LAYERS, REFINE_MAX_NODES = 64, 256
 
 
+class TspCfg(C.Structure):
+    """fuelmi_tsp_cfg: the global-tour solver's restarts / kicks of the local search, the exact method's bound, the seed."""
+    _fields_ = [("restarts", C.c_int), ("kicks", C.c_int), ("exact_max", C.c_int), ("seed", C.c_uint64)]
+
+
+TSP_MAX_DIM, TSP_EXACT_CAP = 1024, 16
+TSP_DEFAULT_RESTARTS, TSP_DEFAULT_KICKS, TSP_DEFAULT_EXACT_MAX = 64, 8, 12
+
+
 class BsplineCfg(C.Structure):
     _fields_ = [(n, C.c_double) for n in
                 ("ld_smooth", "ld_dist", "ld_feasi", "ld_start", "ld_end", "ld_guide", "ld_waypt",
@@ -203,6 +212,9 @@ SYMBOLS = {
     "fuelmi_map_path_costs": (C.c_int, [_P, C.POINTER(PathCfg), C.c_int, _dp, _dp, _dp, _ip, _ip, _dp]),
     "fuelmi_map_path_stats": (C.c_int, [_P, _ip]),
     "fuelmi_map_refine_tours": (C.c_int, [_P, C.POINTER(RefineCfg), C.c_int, _dp, _ip, _ip, _dp, _ip, _dp, _ip, _dp]),
+    "fuelmi_tsp_create": (C.c_int, [C.c_int, C.POINTER(TspCfg), _PP]),
+    "fuelmi_tsp_destroy": (None, [_P]),
+    "fuelmi_tsp_solve": (C.c_int, [_P, C.c_int, _ip, C.POINTER(C.c_int32), _ip, C.POINTER(C.c_int64), _ip]),
     "fuelmi_bspline_cost_grad": (C.c_int, [_P, C.POINTER(BsplineCfg), C.POINTER(BsplineBatch), _dp, _dp]),
     "fuelmi_bspline_optimize": (C.c_int, [_P, C.POINTER(BsplineCfg), C.POINTER(BsplineBatch), C.c_int, C.c_double, _dp, _dp,
                                 C.POINTER(C.c_int)]),

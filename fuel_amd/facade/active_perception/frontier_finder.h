@@ -98,6 +98,13 @@ public:
   bool refineSingleDestination(const Vector3d& cur_pos, const Vector3d& cur_vel, const Vector3d& cur_yaw,
                                const vector<Vector3d>& points, const vector<double>& yaws, int& min_cost_id);
 
+  // addition: FastExplorationManager::findGlobalTour (fast_exploration_manager.cpp:327-420) without the file round
+  // trip through LKH: updateFrontierCostMatrix, getFullCostMatrix, the reference's int(cost * 100), then the device
+  // ATSP solver (fuelmi_tsp_solve, created on first use on the map's device with the FUELMI_TSP_DEFAULT_* settings).
+  // indices: the frontiers in tour order (LKH id - 2 in the reference); with global_tour also getPathForTour's polyline.
+  // false (with a message) when an entry cannot be converted to int or the solve fails.
+  bool findGlobalTour(const Vector3d& cur_pos, const Vector3d& cur_vel, const Vector3d cur_yaw, vector<int>& indices,
+                      vector<Vector3d>* global_tour = nullptr);
   // camera model for the callers (field-of-view drawing); the device samples viewpoints with its own copy
   // of the same perception_utils/* parameters
   shared_ptr<PerceptionUtils> percep_utils_;
@@ -121,6 +128,7 @@ private:
                     vector<int>& choice, vector<Vector3d>* tour);
 
   fuelmi_frontier* dev_;
+  fuelmi_tsp* tsp_ = nullptr;  // findGlobalTour's solver (created on first use)
   shared_ptr<EDTEnvironment> edt_env_;
   int cluster_min_;
   double resolution_, min_candidate_dist_;

@@ -1,6 +1,7 @@
 // facade.cpp -- the reference's C++ class interfaces over the libfuelmi C-ABI (host side only;
 // every computation is a HIP kernel behind include/fuelmi.h).  See INTEGRATION.md.
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -16,6 +17,9 @@
 
 namespace fast_planner {
 
+// the device of the map initMap set up last: the drop-in solveTSPLKH (libfuelmi_lkh.so) solves there
+static std::atomic<int> g_last_map_device(-1);
+
 static void warn(const char* what, int rc) {
   // error convention of the reference: void returns, log and continue
   if (rc != FUELMI_OK) std::fprintf(stderr, "[fuelmi] %s failed (%d): %s\n", what, rc, fuelmi_last_error());
@@ -24,7 +28,7 @@ static void warn(const char* what, int rc) {
 // ------------------------------------------------------------------------------------------------
 // SDFMap
 // ------------------------------------------------------------------------------------------------
-SDFMap::SDFMap() : ext_(new Ext{nullptr, true, true, true}) {}
+SDFMap::SDFMap() : ext_(new Ext{nullptr, true, true, true, 0}) {}
 SDFMap::~SDFMap() {
   if (ext_->dev) fuelmi_map_destroy(ext_->dev);
   delete ext_;
@@ -63,6 +67,8 @@ void SDFMap::initMap(ros::NodeHandle& nh) {
   int device = 0;
   nh.param("sdf_map/hip_device", device, 0);  // addition: which GPU hosts this map
   c.device = device;
+  ext_->hip_device = device;
+  g_last_map_device.store(device);
   c.map_size[0] = x_size, c.map_size[1] = y_size, c.map_size[2] = z_size;
   const double org[3] = {-x_size / 2.0, -y_size / 2.0, c.ground_height};
   const char* axis[3] = {"x", "y", "z"};
@@ -350,6 +356,7 @@ FrontierFinder::FrontierFinder(const shared_ptr<EDTEnvironment>& edt, ros::NodeH
   if (have_viewpoints_) warn("fuelmi_frontier_set_viewpoint_cfg", fuelmi_frontier_set_viewpoint_cfg(dev_, &v));
 }
 FrontierFinder::~FrontierFinder() {
+  if (tsp_) fuelmi_tsp_destroy(tsp_);
   if (dev_) fuelmi_frontier_destroy(dev_);
 }
 
@@ -638,6 +645,46 @@ void FrontierFinder::getPathForTour(const Vector3d& pos, const vector<int>& fron
     std::advance(p, frontier_ids[k + 1]);
     path.insert(path.end(), p->begin(), p->end());
   }
+}
+
+bool FrontierFinder::findGlobalTour(const Vector3d& cur_pos, const Vector3d& cur_vel, const Vector3d cur_yaw,
+                                    vector<int>& indices, vector<Vector3d>* global_tour) {
+  updateFrontierCostMatrix();
+  Eigen::MatrixXd mat;
+  getFullCostMatrix(cur_pos, cur_vel, cur_yaw, mat);
+  const int d = (int)mat.rows();
+  // int int_cost = cost_mat(i, j) * scale (:368-374), refused where that conversion is undefined
+  vector<int32_t> c((size_t)d * d);
+  for (int i = 0; i < d; ++i)
+    for (int j = 0; j < d; ++j) {
+      const double x = mat(i, j) * 100;
+      if (!std::isfinite(x) || std::fabs(x) >= 2147483648.0) {
+        std::fprintf(stderr, "[fuelmi facade] FrontierFinder::findGlobalTour: cost (%d, %d) = %g has no int value\n", i,
+                     j, mat(i, j));
+        return false;
+      }
+      c[(size_t)i * d + j] = (int32_t)x;
+    }
+  if (!tsp_) {
+    const fuelmi_tsp_cfg cfg = {FUELMI_TSP_DEFAULT_RESTARTS, FUELMI_TSP_DEFAULT_KICKS, FUELMI_TSP_DEFAULT_EXACT_MAX, 0};
+    const int rc = fuelmi_tsp_create(edt_env_->sdf_map_->hipDevice(), &cfg, &tsp_);
+    warn("fuelmi_tsp_create", rc);
+    if (rc != FUELMI_OK) return false;
+  }
+  const int dim_ptr[2] = {0, d};
+  vector<int> order(d);
+  int64_t cost = 0;
+  int method = 0;
+  const int rc = fuelmi_tsp_solve(tsp_, 1, dim_ptr, c.data(), order.data(), &cost, &method);
+  warn("fuelmi_tsp_solve", rc);
+  if (rc != FUELMI_OK) return false;
+  indices.clear();
+  for (int k = 1; k < d; ++k) indices.push_back(order[k] - 1);
+  if (global_tour) {
+    global_tour->clear();
+    getPathForTour(cur_pos, indices, *global_tour);
+  }
+  return true;
 }
 
 bool FrontierFinder::deviceRefine(const Vector3d& cur_pos, const Vector3d& cur_vel, double cur_yaw,
@@ -1020,3 +1067,6 @@ bool BsplineOptimizer::isQuadratic() {
 }
 
 }  // namespace fast_planner
+
+// for libfuelmi_lkh.so (a weak reference there): the device of the SDFMap initialised last, -1 if none
+extern "C" int fuelmi_facade_last_map_device(void) { return fast_planner::g_last_map_device.load(); }

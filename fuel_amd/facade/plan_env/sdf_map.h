@@ -92,6 +92,7 @@ public:
   // -- additions of this implementation (not in the reference) --
   // device handle for the FrontierFinder / BsplineOptimizer facades
   fuelmi_map* device() const { return ext_ ? ext_->dev : nullptr; }
+  int hipDevice() const { return ext_ ? ext_->hip_device : 0; }  // the HIP device ordinal of that map
   // which host mirrors the mutators keep coherent (default: all, as the reference's getters need)
   void setHostMirror(bool occupancy, bool inflate, bool distance);
   // batched getDistWithGrad for n positions (xyz packed), one kernel launch
@@ -120,6 +121,7 @@ private:
   struct Ext {
     fuelmi_map* dev;
     bool mirror_occ, mirror_infl, mirror_dist;
+    int hip_device;  // sdf_map/hip_device
   };
   unique_ptr<MapParam> mp_;
   unique_ptr<MapData> md_;

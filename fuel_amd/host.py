@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BsplineBatch, BsplineCfg, FrontierCfg, MapCfg, MapInfo, PathCfg, RefineCfg, check, lib)
+from ._lib import (BsplineBatch, BsplineCfg, FrontierCfg, MapCfg, MapInfo, PathCfg, RefineCfg, TspCfg, check, lib)
 
 # exploration.launch / algorithm.xml defaults (exploration_manager/launch/algorithm.xml:33-59,170-181)
 DEFAULT_MAP = dict(resolution=0.1, ground_height=-1.0, obstacles_inflation=0.199,
@@ -345,6 +345,61 @@ class SDFMap:
         n = C.c_int()
         check(self.L.fuelmi_profile_get_samples(self.h, stage, _dp(ms), cap, C.byref(n)))
         return ms[:n.value].copy()
+
+
+def tour_matrix(mat, scale=100):
+    """findGlobalTour's conversion of getFullCostMatrix (fast_exploration_manager.cpp:368-374): int_cost = cost * scale
+    truncated toward zero, as int32.  Raises ValueError where the reference's conversion is undefined (a non-finite
+    value, |cost * scale| >= 2^31)."""
+    m = np.asarray(mat, dtype=np.float64)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError("tour_matrix: a square matrix is needed, got shape %s" % (m.shape,))
+    x = m * scale
+    if not np.isfinite(x).all():
+        raise ValueError("tour_matrix: non-finite entry")
+    if (np.abs(x) >= 2.0 ** 31).any():
+        raise ValueError("tour_matrix: |cost * %g| >= 2^31" % scale)
+    return np.trunc(x).astype(np.int32)
+
+
+class TourSolver:
+    """fuelmi_tsp: the global tour (FastExplorationManager::findGlobalTour's ATSP) for a batch of int32 matrices.
+    solve(list of d x d matrices) -> (orders: list of int arrays starting at 0, costs: int64 array, methods: int array,
+    0 exact / 1 heuristic).  The rules are include/fuelmi.h's; tests/tsp_ref.py restates them."""
+
+    def __init__(self, device=0, restarts=_lib.TSP_DEFAULT_RESTARTS, kicks=_lib.TSP_DEFAULT_KICKS,
+                 exact_max=_lib.TSP_DEFAULT_EXACT_MAX, seed=0):
+        self.cfg = TspCfg(int(restarts), int(kicks), int(exact_max), int(seed))
+        self._h = C.c_void_p()
+        check(lib().fuelmi_tsp_create(int(device), C.byref(self.cfg), C.byref(self._h)))
+
+    def solve(self, mats):
+        mats = [np.ascontiguousarray(m, dtype=np.int32) for m in mats]
+        for m in mats:
+            if m.ndim != 2 or m.shape[0] != m.shape[1]:
+                raise ValueError("TourSolver.solve: square matrices are needed, got shape %s" % (m.shape,))
+        dims = np.array([m.shape[0] for m in mats], dtype=np.int32)
+        dim_ptr = np.zeros(len(mats) + 1, dtype=np.int32)
+        np.cumsum(dims, out=dim_ptr[1:])
+        costs = np.concatenate([m.reshape(-1) for m in mats]) if mats else np.zeros(1, np.int32)
+        order = np.zeros(max(1, int(dim_ptr[-1])), dtype=np.int32)
+        cost = np.zeros(max(1, len(mats)), dtype=np.int64)
+        method = np.zeros(max(1, len(mats)), dtype=np.int32)
+        check(lib().fuelmi_tsp_solve(self._h, len(mats), _ip(dim_ptr), costs.ctypes.data_as(C.POINTER(C.c_int32)),
+                                     _ip(order), cost.ctypes.data_as(C.POINTER(C.c_int64)), _ip(method)))
+        orders = [order[dim_ptr[b]:dim_ptr[b + 1]].copy() for b in range(len(mats))]
+        return orders, cost[:len(mats)], method[:len(mats)]
+
+    def close(self):
+        if self._h:
+            lib().fuelmi_tsp_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class DeviceBuffer:

@@ -416,6 +416,58 @@ int fuelmi_map_refine_tours(fuelmi_map* m, const fuelmi_refine_cfg* cfg, int n_p
                             int* tour_len, double* tour_xyz);
 
 /* ------------------------------------------------------------------------------------------
+ * Global tour: the ATSP of FastExplorationManager::findGlobalTour (exploration_manager/src/
+ * fast_exploration_manager.cpp:327-420), which the reference hands to LKH-2 as int(cost * 100) in a TSPLIB file,
+ * for n_prob independent int32 matrices in one call.  Needs no map: the solver owns a stream and a workspace that
+ * grows on demand (no allocation once warm).  Problem b has dimension d = dim_ptr[b+1] - dim_ptr[b] (dim_ptr[0] = 0)
+ * and its matrix c at costs + sum of the earlier d^2 (row-major).  The answer order[0..d-1] has order[0] = 0 and
+ * minimises the closed tour C = sum_k c[order[k]][order[k+1]] + c[order[d-1]][0], summed in int64 (with the
+ * reference's column 0 of zeros: the cheapest open path from the current state, which is what LKH answers;
+ * order[1..] - 1 are findGlobalTour's indices).  The method depends on d and the configuration only:
+ *   exact (method 0), d - 1 <= exact_max: Held-Karp.  Suffix DP g(S, j) = the cheapest way to visit the rest of
+ *     1..d-1 from j having visited S and close at 0; forward construction takes at every step the smallest j with
+ *     c[last][j] + g(S u {j}, j) equal to the optimum: the LEXICOGRAPHICALLY SMALLEST optimal order.  d = 1: {0},
+ *     cost 0; d = 2: {0, 1}, cost c01 + c10.  Table 2^(d-1) (d-1) int64 in the workspace (8 MiB at the cap).
+ *   heuristic (method 1), larger d: a deterministic iterated local search, `restarts` independent restarts r
+ *     (one workgroup each).  Restart r: the nearest-neighbour tour from 0 (ties: the smallest index); local search;
+ *     then `kicks` times: double bridge of the best tour, local search, keep the result iff its cost is strictly
+ *     below the restart's best (else back to the best).  Answer: the cheapest restart, the smallest r on ties.
+ *   Local search = best improvement: every pass evaluates the whole neighbourhood of the current tour and applies
+ *     the one move of the smallest key (delta, type, i, j, k) among those with delta < 0, until none is left.
+ *     type 0, 2-opt: reverse order[i..j], 1 <= i < j <= d-1 (k = 0).  Its delta takes the reversed inner edges from
+ *       prefix sums of the forward and backward edge costs along the tour.
+ *     type 1, Or-opt: the segment order[i .. i+L-1] (L = 1, 2, 3; i >= 1, i+L-1 <= d-1) moves into the gap after
+ *       position j (0 <= j <= d-1, the gap j = d-1 closes at 0; j outside [i-1, i+L-1]), forward (rev 0) or
+ *       reversed (rev 1, L >= 2 only); k = 2 (L - 1) + rev.  Positions are those of the tour the pass starts from.
+ *   Double bridge at 1 <= p1 < p2 < p3 <= d-1: A C B D with A = order[0..p1-1], B = [p1..p2-1], C = [p2..p3-1],
+ *     D = [p3..d-1] (orientation kept).  Points: h = mix(seed ^ mix(r << 32 | k)) for kick k, then draws
+ *     x_t = 1 + mix(h + t) % (d - 1) for t = 0, 1, ..., a value already drawn skipped, until three; sorted.
+ *     mix = splitmix64's step (z += 0x9E3779B97F4A7C15, two xor-shift-multiplies, xor-shift), all mod 2^64.
+ *     Seeds never depend on a problem's place in the batch: an answer is the same alone or batched, on any run.
+ * Limits, checked on the host before anything is written or launched: d <= FUELMI_TSP_MAX_DIM and the call's
+ * matrix entries < 2^31 (FUELMI_ELIMIT); d < 1, dim_ptr[0] != 0 are FUELMI_EINVAL.  fuelmi_tsp_create refuses
+ * restarts < 1, kicks < 0 and exact_max outside [3, FUELMI_TSP_EXACT_CAP] with FUELMI_EINVAL (and *out untouched),
+ * and returns FUELMI_ENODEV without a gfx950 device.  One thread per solver at a time.
+ * Defaults (FUELMI_TSP_DEFAULT_*): measured on the headline G400 first-cycle matrix, DESIGN.md section 10.
+ * ---------------------------------------------------------------------------------------- */
+#define FUELMI_TSP_MAX_DIM 1024
+#define FUELMI_TSP_EXACT_CAP 16
+#define FUELMI_TSP_DEFAULT_RESTARTS 64
+#define FUELMI_TSP_DEFAULT_KICKS 8
+#define FUELMI_TSP_DEFAULT_EXACT_MAX 12
+typedef struct {
+  int restarts, kicks, exact_max;
+  uint64_t seed;
+} fuelmi_tsp_cfg;
+typedef struct fuelmi_tsp fuelmi_tsp;
+int fuelmi_tsp_create(int device, const fuelmi_tsp_cfg* cfg, fuelmi_tsp** out);
+void fuelmi_tsp_destroy(fuelmi_tsp* t);
+/* Out: order (concatenated, d each, at dim_ptr[b]), tour_cost[b] (int64), method[b] (0 exact, 1 heuristic);
+ * synchronous. */
+int fuelmi_tsp_solve(fuelmi_tsp* t, int n_prob, const int* dim_ptr, const int32_t* costs, int* order,
+                     int64_t* tour_cost, int* method);
+
+/* ------------------------------------------------------------------------------------------
  * B-spline cost + gradient: replaces BsplineOptimizer::combineCost and the calc*Cost terms
  * (bspline_opt/src/bspline_optimizer.cpp:255-516, 518-691), batched over C trajectories.
  * ---------------------------------------------------------------------------------------- */
