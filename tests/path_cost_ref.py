@@ -270,3 +270,125 @@ def edge_ok(pm, a, b, res=0.4, edge_step=0.1):
             return False
         l += edge_step
     return True
+
+
+# ---- a serpentine map: one lattice layer, a shortest path of more than 8192 lattice edges ---------------------------
+SERP_SIZE = (24.0, 24.0, 3.0)
+SERP_BOX = ((-11.9, -11.9, 0.97), (11.9, 11.9, 1.03))  # z: one lattice layer for sources at z = 1
+SERP_RES = 0.05                                        # lattice resolution (voxels are 0.1)
+SERP_P1 = (-11.437, 10.013, 1.0)                       # corridor 0, below the gap at the top of wall 0; off the
+                                                       # voxel faces, so lattice nodes sit inside cells
+
+
+def serpentine_occupancy(om):
+    """walls of one voxel across the whole z range at x voxel 10, 18, .., 226, each open for 15 voxels at alternating
+    ends (top for even walls); after the 0.199 m inflation the corridors keep 3 free voxels"""
+    occ = np.full(om.nvox, om.l_min)
+    for k, ix in enumerate(range(10, 230, 8)):
+        if k % 2 == 0:
+            occ[ix, :225, :] = om.l_max
+        else:
+            occ[ix, 15:, :] = om.l_max
+    return occ
+
+
+def serpentine_map():
+    """(OracleMap, PathMap) of the serpentine, inflated by the oracle"""
+    from oracle import fuel_oracle as fo
+    om = fo.OracleMap(SERP_SIZE, SERP_BOX[0], SERP_BOX[1])
+    om.occ[:] = serpentine_occupancy(om).reshape(-1)
+    nv = om.nvox
+    om.set_local_bound((0, 0, 0), (nv[0] - 1, nv[1] - 1, nv[2] - 1))
+    om.inflate_local()
+    return om, PathMap.from_oracle(om)
+
+
+def goals_at_hops(pm, om, p1, hops, res):
+    """goal points p2 whose restated path from p1 runs through exactly H lattice edges, one per H in hops.  Node H of the
+    chain to the farthest reachable node is the goal when it is the earliest chain node in p2's neighbourhood (+-1
+    lattice cell): p2 is placed a cell or two ahead of it along the chain and nudged sideways, so that among the chain
+    nodes ahead the earliest one is strictly cheapest; the first placement whose restated search gives H edges is kept.
+    Returns ({H: p2}, lattice with .d)."""
+    lat = Lattice(pm, p1, res)
+    lat.d = lat.csgraph_dist()
+    d = np.where(np.isfinite(lat.d), lat.d, -1.0)
+    far = np.unravel_index(int(np.argmax(d)), lat.E)
+    _, _, path = lat.search(lat.pos[far], lat.d)
+    p1 = np.asarray(p1, dtype=np.float64)
+    out = {}
+    for H in hops:
+        assert H + 2 < len(path), (H, len(path))
+        a, b = np.array(path[H]), np.array(path[H + 1])
+        ahead = (b - a) / norm3(*(b - a))
+        side = np.array([-ahead[1], ahead[0], 0.0])
+        found = None
+        for along in (1.5, 1.2, 1.8, 1.0, 2.0, 0.6, 1.1, 1.3, 1.4, 1.6, 1.7, 1.9):
+            for nudge in (0.2, -0.2, 0.35, -0.35):
+                p2 = a + (along * ahead + nudge * side) * res
+                kind, _, p = lat.search(p2, lat.d)
+                if kind == 1 and len(p) == H + 2 and not straight_line_safe(pm, om, p1, p2):
+                    found = p2
+                    break
+            if found is not None:
+                break
+        assert found is not None, H
+        out[H] = found
+    return out, lat
+
+
+# ---- many ~0.8 M-node lattices: more than one source chunk (48 M nodes) ----------------------------------------------
+CHUNK_SIZE = (8.0, 8.0, 4.0)
+CHUNK_BOX = ((-3.9, -3.9, 0.05), (3.9, 3.9, 2.9))
+CHUNK_RES = 0.06
+CHUNK_NODE_BUDGET = 48 << 20  # path_cost.hip
+
+
+def chunk_map():
+    """(OracleMap, PathMap): a wall at x ~ -0.2 with a door, a second wall open at low y (the small map of
+    tests/test_path_cost_gpu.py), inflated by the oracle"""
+    from oracle import fuel_oracle as fo
+    om = fo.OracleMap(CHUNK_SIZE, CHUNK_BOX[0], CHUNK_BOX[1])
+    occ = np.full(om.nvox, om.l_min)
+    occ[38:40, :, :] = om.l_max
+    occ[38:40, 52:60, 10:26] = om.l_min
+    occ[50:52, 20:70, 10:40] = om.l_max
+    om.occ[:] = occ.reshape(-1)
+    nv = om.nvox
+    om.set_local_bound((0, 0, 0), (nv[0] - 1, nv[1] - 1, nv[2] - 1))
+    om.inflate_local()
+    return om, PathMap.from_oracle(om)
+
+
+def lattice_nodes(pm, p1, res):
+    """the node count of p1's lattice (Lattice's extent, without its edges)"""
+    E = 1
+    for k in range(3):
+        base = (pm.box_mind[k] - p1[k]) / res
+        top = (pm.box_maxd[k] - p1[k]) / res
+        ns = [n for n in range(int(math.floor(base)) - 2, int(math.ceil(top)) + 3)
+              if pm.box_mind[k] < p1[k] + n * res < pm.box_maxd[k]]
+        E *= max(ns + [0]) - min(ns + [0]) + 1
+    return E
+
+
+def chunk_case(pm, om, n_src=72, seed=21):
+    """n_src distinct sources west of the wall, each with one goal east of it (the straight line blocked), and the
+    chunk of every source as path_cost_enqueue forms them (sources in first-seen order while the nodes fit)"""
+    rng = np.random.default_rng(seed)
+    p1, p2 = [], []
+    while len(p1) < n_src:
+        a = np.array([-3.5, -3.5, 0.3]) + np.array([2.8, 7.0, 2.3]) * rng.random(3)
+        b = np.array([0.6, -3.5, 0.3]) + np.array([2.9, 7.0, 2.3]) * rng.random(3)
+        near = b + 0.1 * np.array(STEPS, dtype=np.float64)  # the goal clear of the walls: some goal node is reached
+        if pm.blocked(a[None])[0] or pm.blocked(near).any() or straight_line_safe(pm, om, a, b):
+            continue
+        p1.append(a)
+        p2.append(b)
+    chunk, nodes, c = [], 0, 0
+    for a in p1:
+        nn = lattice_nodes(pm, a, CHUNK_RES)
+        if nodes and nodes + nn > CHUNK_NODE_BUDGET:
+            c, nodes = c + 1, 0
+        nodes += nn
+        chunk.append(c)
+    return np.array(p1), np.array(p2), chunk

@@ -188,8 +188,16 @@ def apply_move(order, key):
     return rest[:gp + 1] + seg + rest[gp + 1:]
 
 
-def local_search(c, order):
-    """best improvement until no move has delta < 0; ties by the smallest key"""
+def move_type(d, key):
+    """"2opt", "or_fwd" or "or_rev" of a move key"""
+    if key < 6 * d * d:
+        return "2opt"
+    return "or_rev" if (key - 6 * d * d) % 6 & 1 else "or_fwd"
+
+
+def local_search(c, order, counts=None):
+    """best improvement until no move has delta < 0; ties by the smallest key.  counts: a dict that gains one per
+    applied move under its move_type"""
     order = list(order)
     while True:
         delta, key = move_deltas(c, order)
@@ -198,14 +206,19 @@ def local_search(c, order):
         m = delta.min()
         if m >= 0:
             break
-        order = apply_move(order, int(key[delta == m].min()))
+        k = int(key[delta == m].min())
+        if counts is not None:
+            t = move_type(len(order), k)
+            counts[t] = counts.get(t, 0) + 1
+        order = apply_move(order, k)
     return order, tour_cost(c, order)
 
 
-def ils(c, restarts, kicks, seed):
+def ils(c, restarts, kicks, seed, start=None):
+    """start: local_search(c, nearest_neighbour(c)) when the caller has it already (it depends on c alone)"""
     c = np.asarray(c, dtype=np.int64)
     d = len(c)
-    start, start_cost = local_search(c, nearest_neighbour(c))  # the same for every restart
+    start, start_cost = local_search(c, nearest_neighbour(c)) if start is None else start  # the same for every restart
     best_all = None
     for r in range(restarts):
         best, bcost = list(start), start_cost
@@ -317,3 +330,43 @@ def cycle_matrix(workload, seed=42, vm=2.0, yd=60 * 3.1415926 / 180.0, w_dir=1.5
     for j in range(n):
         m[0, j + 1] = rr.compute_cost(l0[j], cur, vp[j, :3], yaw, vp[j, 3], vel, vm, yd, w_dir)
     return m
+
+
+def planted_matrix(d, seed, n_traps=4):
+    """A d x d instance (d >= 64) with a cheap seeded Hamiltonian cycle and traps that send the nearest-neighbour start
+    astray, so that the local search needs many moves of every type and stays cheap to restate at d ~ 1024:
+      cycle      perm[t] <-> perm[t+1] costs 10..19 both ways (reversing a stretch of it costs nothing inside), but
+                 0 -> perm[d-1] costs 30, so the start runs forwards
+      elsewhere  2000..2999
+      2-opt trap perm[k] -> perm[k+5] costs 1 and perm[k+5] -> perm[k+4] is cheaper than -> perm[k+6]: the start runs
+                 perm[k+5] .. perm[k+1] backwards, then perm[k+1] -> perm[k+6] (100); reversing the stretch repairs it
+      Or-opt trap perm[k] -> perm[k+2] (1) skips perm[k+1], left for a jump (column 600): moved back forwards
+      pair trap  perm[k] -> perm[k+3] (1) skips perm[k+1], perm[k+2]; a jump enters perm[k+2] (column 500) first and
+                 leaves by perm[k+1]: moved back reversed
+    Returns (int64 matrix, perm)."""
+    assert d >= 64
+    rng = np.random.default_rng(seed)
+    perm = np.concatenate([[0], 1 + rng.permutation(d - 1)]).astype(np.int64)
+    c = rng.integers(2000, 3000, (d, d)).astype(np.int64)
+    nxt = np.roll(perm, -1)
+    w = rng.integers(10, 20, d)
+    c[perm, nxt] = w
+    c[nxt, perm] = w
+    c[0, perm[d - 1]] = 30
+    spots = (rng.choice((d - 16) // 12, 3 * n_traps, replace=False) + 1) * 12  # trap starts, 12 apart, off the ends
+    P = lambda t: int(perm[t])  # noqa: E731
+    for t, k in enumerate(spots.tolist()):
+        kind = t % 3
+        if kind == 0:  # 2-opt
+            c[P(k), P(k + 5)] = 1
+            c[P(k + 5), P(k + 4)] = 5
+            c[P(k + 1), P(k + 6)] = 100
+        elif kind == 1:  # Or-opt forward
+            c[P(k), P(k + 2)] = 1
+            col = c[:, P(k + 1)]
+            col[col >= 2000] = 600
+        else:  # Or-opt reversed
+            c[P(k), P(k + 3)] = 1
+            col = c[:, P(k + 2)]
+            col[col >= 2000] = 500
+    return c, perm
