@@ -995,6 +995,13 @@ extern "C" int fuelmi_frontier_path_stats(const fuelmi_frontier* f, int out2[2])
   out2[0] = f->n_late_resolve, out2[1] = f->n_retiled;
   return FUELMI_OK;
 }
+extern "C" int fuelmi_frontier_changed_stats(const fuelmi_frontier* f, int out[9]) {
+  ARGCHK(f && out);
+  for (int k = 0; k < 4; ++k) out[k] = f->rm_paths[k];
+  out[4] = f->rm_last_nc, out[5] = (int)f->rm_last_total, out[6] = f->rm_last_mark;
+  out[7] = f->n_pool_rebuilds, out[8] = (int)f->pool_cap;
+  return FUELMI_OK;
+}
 extern "C" int fuelmi_frontier_order_stats(const fuelmi_frontier* f, int out4[4]) {
   ARGCHK(f && out4);
   out4[0] = f->order_last, out4[1] = f->n_order_ref, out4[2] = f->n_order_fallback, out4[3] = (int)f->order_fallback_cells;

@@ -237,6 +237,7 @@ static int pool_reserve(fuelmi_frontier* f, size_t need) {
       live += c.cells.size();
     }
   HIPCHK(hipStreamSynchronize(f->stream));
+  if (f->pool) ++f->n_pool_rebuilds;  // (the first allocation is not a rebuild)
   if (live > f->pool_cap / 2 || !f->pool) {
     size_t cap = std::max<size_t>(1u << 20, f->pool_cap);
     while (cap / 2 < live) cap *= 2;
@@ -353,7 +354,8 @@ int remove_changed_begin(fuelmi_frontier* f, const double* umin, const double* u
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&f->h_cand), cap * sizeof(RmCand), hipHostMallocDefault));
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&f->d_mark), cap * sizeof(int)));
     HIPCHK(hipMemsetAsync(f->d_mark, 0, cap * sizeof(int), f->stream));
-    f->rm_mark = 0;
+    // rm_mark is NOT restarted: the fresh d_mark is zero and marks are >= 1, while k_rm_pool_bar's release words in
+    // rm_bar still hold the marks of earlier launches -- a repeated mark would let workgroups skip the barrier
     f->h_changed_cap = cap;
   }
   RmCand* hc = reinterpret_cast<RmCand*>(f->h_cand);
@@ -368,13 +370,18 @@ int remove_changed_begin(fuelmi_frontier* f, const double* umin, const double* u
     HIPCHK(hipMemcpyAsync(f->d_stage, hc, nc * sizeof(RmCand), hipMemcpyHostToDevice, f->stream));
     hc = reinterpret_cast<RmCand*>(f->d_stage);
   }
+  f->rm_last_nc = (int)nc;
+  f->rm_last_total = total;
+  f->rm_last_mark = 0;
   if (nc <= RM_LDS && total <= RM_ONE_CELLS) {
+    ++f->rm_paths[0];
     k_rm_pool_one<<<1, RM_ONE_T, 0, f->stream>>>(m->g, m->occ_bits.p, m->unk_bits.p, f->flag.p, f->pool, hc, (int)nc, total,
                                                  f->h_changed);
     FDBG("k_rm_pool_one");
     return FUELMI_OK;
   }
-  const int mark = ++f->rm_mark;  // (marks of earlier searches never match: no clearing pass)
+  const int mark = ++f->rm_mark;  // (marks of earlier searches never match -- rm_mark is never restarted: no clearing pass)
+  f->rm_last_mark = mark;
   if (nc <= RM_LDS && fblocks((long)total, 256) <= RM_BAR_BLOCKS) {
     if (!f->rm_bar) {
       HIPCHK(hipMalloc(reinterpret_cast<void**>(&f->rm_bar), 64 * (RM_BAR_BLOCKS + 1)));
@@ -382,12 +389,15 @@ int remove_changed_begin(fuelmi_frontier* f, const double* umin, const double* u
       f->rm_bar_total = 0u;
     }
     const int nb = fblocks((long)total, 256);
+    ++f->rm_paths[1];
     f->rm_bar_total += (u32)nb;
     k_rm_pool_bar<<<nb, 256, 0, f->stream>>>(m->g, m->occ_bits.p, m->unk_bits.p, f->flag.p, f->pool, hc, (int)nc, total, f->d_mark,
                                              mark, f->h_changed, f->rm_bar, f->rm_bar_total);
     FDBG("k_rm_pool_bar");
     return FUELMI_OK;
   }
+  // (fblocks caps the grid at 65 536 workgroups: 16.7 M candidate cells, far beyond any map of this library)
+  ++f->rm_paths[nc <= RM_LDS ? 2 : 3];
   k_rm_pool<0><<<fblocks((long)total, 256), 256, 0, f->stream>>>(m->g, m->occ_bits.p, m->unk_bits.p, f->flag.p, f->pool, hc,
                                                                (int)nc, total, f->d_mark, mark, f->h_changed);
   FDBG("k_rm_pool<0>");

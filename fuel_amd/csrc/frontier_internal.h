@@ -440,10 +440,16 @@ struct fuelmi_frontier {
   size_t h_changed_cap = 0;
   void* h_cand = nullptr;    // pinned (pool offset, first index) table of the candidates, read by the kernels
   int* d_mark = nullptr;     // device: search number in which candidate k was last found changed
-  int rm_mark = 0;
+  int rm_mark = 0;           // mark of the last test: grows for the finder's lifetime (k_rm_pool_bar's release words keep old marks)
   u32* rm_bar = nullptr;     // device: arrival counter of k_rm_pool_bar's in-kernel barrier (never reset: rm_bar_total is its target)
   u32 rm_bar_total = 0;
   bool rm_failed = false;    // the barrier of k_rm_pool_bar timed out in the search being collected (fuelmi_frontier_search_end fails)
+  // fuelmi_frontier_changed_stats: launches per path of the changed-cluster test (one workgroup, in-kernel barrier,
+  // two passes on a staged table, two passes on a device table), nc / total / mark of the last test, pool rebuilds
+  int rm_paths[4] = {0, 0, 0, 0};
+  int rm_last_nc = 0, rm_last_mark = 0;
+  u32 rm_last_total = 0;
+  int n_pool_rebuilds = 0;
   void* h_put = nullptr;     // pinned table of k_pool_put
   size_t h_put_cap = 0;
   u32* pool = nullptr;  // device copies of the cells of frontiers_ / dormant_frontiers_

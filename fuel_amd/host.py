@@ -534,6 +534,15 @@ class FrontierFinder:
         check(self.L.fuelmi_frontier_path_stats(self.h, o))
         return tuple(o)
 
+    def changedStats(self):
+        """the changed-cluster test in front of the searches: {"paths": launches of (one workgroup, in-kernel barrier,
+        two passes on an LDS table, two passes on a device table), "nc", "total", "mark": candidates, pooled cells and
+        mark of the last test (mark 0 on the one-workgroup path), "rebuilds": device pool rebuilds so far, "pool_cap":
+        the pool's capacity in cells}"""
+        o = (C.c_int * 9)()
+        check(self.L.fuelmi_frontier_changed_stats(self.h, o))
+        return {"paths": tuple(o[:4]), "nc": o[4], "total": o[5], "mark": o[6], "rebuilds": o[7], "pool_cap": o[8]}
+
     def orderStats(self):
         """(order of the last search: 0 address / 1 reference BFS, searches in the reference's order, mode-2 searches
         that fell back to the address order, cells of the cluster that forced the last fallback)"""

@@ -267,6 +267,13 @@ int fuelmi_frontier_resolved_in_launch(const fuelmi_frontier* f);
  * launch queued behind it (the library queued one after the chain had reported), [1] how many ran the chain again on
  * a smaller tile after a per-tile capacity overflow; for tests that must know which code ran */
 int fuelmi_frontier_path_stats(const fuelmi_frontier* f, int out2[2]);
+/* the changed-cluster test that runs in front of a search with committed clusters whose box overlaps the updated box
+ * (searchFrontiers' removal of outdated clusters): [0..3] launches of each of its four paths -- one workgroup, one
+ * launch with an in-kernel barrier, two launches on a candidate table staged in LDS, two launches on a table in device
+ * memory --; of the last test: [4] its candidates, [5] their pooled cells, [6] its mark (0 for the one-workgroup path);
+ * [7] rebuilds of the device pool of committed cells so far, [8] the pool's capacity in cells.  For tests that must know
+ * which code ran */
+int fuelmi_frontier_changed_stats(const fuelmi_frontier* f, int out[9]);
 /* the cell order the searches delivered (cfg.reference_order is a request; mode 2 answers per search): [0] the last
  * search's order -- 0 ascending address, 1 the reference's BFS order --, [1] searches that delivered the reference's
  * order, [2] searches of a mode-2 finder that fell back to the address order because a cluster was too large for the

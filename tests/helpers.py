@@ -189,3 +189,123 @@ def block_straddle(om, lo, hi):
     span = lambda k, t0, T: (max(lo[k] - 1, blo[k]) - t0) // T != (min(hi[k], bhi[k]) - t0) // T  # noqa: E731
     cx, cy = span(0, x0, TX), span(1, y0, TY)
     return "corner" if cx and cy else ("x" if cx else ("y" if cy else "none"))
+
+
+# ---- the changed-cluster test in front of a search (test_frontier_changed_*) ----
+# On the CAP_MAP geometry: a lattice of isolated unknown blocks, one committed cluster each.  An a x b x c block inside
+# the box leaves a shell of 2 (ab + bc + ca) frontier cells; a ("slab", a, b) above the box's top face leaves its
+# underside plus the NQ seed that claims it, ab + 1.  Blocks fill the lattice x slot first, then y, then z, so their
+# clusters come out of a full-box search -- and sit in the candidate table -- in the order of the list; a slab goes
+# into the x slot behind every block: it is the last cluster.  cluster_min = 5 keeps every shell (a single unknown
+# voxel leaves 6 cells).  frontier_changed.hip picks the test's path from nc (candidates) and total (their cells).
+CHG_CLUSTER_MIN = 5
+CHG_PITCH = 10                    # lattice pitch: blocks of up to 7 voxels keep 3 free voxels between their shells
+CHG_ORIGIN = (12, 12, 20)         # lowest slot; shells stay above min_z = 0.4 m and away from the box's faces
+CHG_SLOTS = (37, 37, 5)
+RM_ONE_CELLS, RM_BAR_CELLS, RM_LDS = 2048, 512 * 256, 1024
+RM_PATHS = ("one", "bar", "staged", "table")
+# (clusters, cells, path) of the layouts that pin the edges of the four paths
+CHG_EDGES = {
+    "one_2048": (24, 2048, "one"),
+    "bar_2049": (24, 2049, "bar"),
+    "bar_131072": (886, 131072, "bar"),               # 512 workgroups of 256 lanes
+    "staged_131073": (886, 131073, "staged"),
+    "bar_nc1024": (1024, 6200, "bar"),                # single voxels: a short grid
+    "table_nc1025": (1025, 6206, "table"),
+    "staged_nc1024": (1024, 151700, "staged"),
+    "table_nc1025_big": (1025, 151850, "table"),
+}
+WAVE_HEAD = 12                    # singles in front of every layout: several clusters in the first 64-lane wave
+
+
+def shell_size(shape):
+    if shape[0] == "slab":
+        return shape[1] * shape[2] + 1
+    a, b, c = shape
+    return 2 * (a * b + b * c + c * a)
+
+
+def rm_path(nc, total):
+    """the path remove_changed_begin takes for nc candidates of total pooled cells"""
+    if nc <= RM_LDS and total <= RM_ONE_CELLS:
+        return "one"
+    if nc <= RM_LDS and -(-total // 256) <= 512:
+        return "bar"
+    return "staged" if nc <= RM_LDS else "table"
+
+
+def changed_shapes(n, total, head=WAVE_HEAD, bulk=(5, 5, 5)):
+    """n shapes whose shells sum to total: head singles, bulk blocks, one filler block and a last slab"""
+    m = n - head - 2
+    rest = total - 6 * head - shell_size(bulk) * m
+    for a in range(1, 8):
+        for b in range(a, 8):
+            for c in range(b, 8):
+                s = rest - shell_size((a, b, c))
+                for sa in range(2, 17):
+                    if s - 1 > 0 and (s - 1) % sa == 0 and (s - 1) // sa <= 40:
+                        return [(1, 1, 1)] * head + [bulk] * m + [(a, b, c), ("slab", sa, (s - 1) // sa)]
+    raise ValueError("no filler for %d clusters of %d cells" % (n, total))
+
+
+def changed_edge_shapes(name):
+    n, total, _ = CHG_EDGES[name]
+    return changed_shapes(n, total, bulk=(1, 1, 1) if total < 8 * n else (5, 5, 5))
+
+
+def changed_blocks(om, shapes):
+    """index boxes [(lo, hi)] (hi exclusive) of the shapes, laid out as described above"""
+    blo, bhi = om.box_index()
+    blocks = []
+    nx, ny, nz = CHG_SLOTS
+    inner = [s for s in shapes if s[0] != "slab"]
+    assert len(inner) <= nx * ny * nz and inner == list(shapes[:len(inner)]), "slabs go last"
+    for q, s in enumerate(inner):
+        i, j, k = q // (ny * nz), q // nz % ny, q % nz
+        lo = (CHG_ORIGIN[0] + CHG_PITCH * i, CHG_ORIGIN[1] + CHG_PITCH * j, CHG_ORIGIN[2] + CHG_PITCH * k)
+        assert max(s) <= CHG_PITCH - 3
+        blocks.append((lo, (lo[0] + s[0], lo[1] + s[1], lo[2] + s[2])))
+    i = (len(inner) - 1) // (ny * nz) + 1 if inner else 0
+    for q, s in enumerate(shapes[len(inner):]):
+        assert s[0] == "slab"
+        lo = (CHG_ORIGIN[0] + CHG_PITCH * (i + 2 * q), CHG_ORIGIN[1], bhi[2])
+        blocks.append((lo, (lo[0] + s[1], lo[1] + s[2], bhi[2] + 5)))
+    for lo, hi in blocks:
+        assert all(blo[q] < lo[q] and hi[q] <= (bhi[q] - 1 if q < 2 else om.nvox[2]) for q in range(3)), (lo, hi)
+    return blocks
+
+
+def have_overlap(min1, max1, min2, max2):
+    """haveOverlap (frontier_finder.cpp:353-363), with its 1e-3 slack"""
+    return all(max(min1[i], min2[i]) <= min(max1[i], max2[i]) + 1e-3 for i in range(3))
+
+
+def pooled_cells(om, cells, device_order=True):
+    """a committed cluster's cells as the finder's device pool holds them: ascending addresses, an NQ seed (the BFS
+    root outside the box) last when the cluster was committed straight from the search (device_order); in plain
+    ascending order after the pool was rebuilt from the host lists"""
+    blo, bhi = om.box_index()
+    x, y, z = np.unravel_index(cells[0], om.nvox)
+    seeded = not (blo[0] <= x < bhi[0] and blo[1] <= y < bhi[1] and blo[2] <= z < bhi[2])
+    if not (device_order and seeded):
+        return np.sort(cells)
+    return np.concatenate([np.sort(cells[1:]), cells[:1]])
+
+
+def changed_candidates(of, om, lo, hi, device_order=True):
+    """the candidates of a changed-cluster test against the updated box [lo, hi], from the oracle's committed lists:
+    [(which, k, pooled cells)] in table order (frontiers_, then dormant_frontiers_)"""
+    out = []
+    for which in (1, 2):
+        for k, cells in enumerate(of.clusters(which)):
+            _, bmin, bmax = of.cluster_info(which, k)
+            if have_overlap(bmin, bmax, lo, hi):
+                out.append((which, k, pooled_cells(om, cells, device_order)))
+    return out
+
+
+def occupy(om, adrs):
+    """a copy of the oracle's log-odds with the cells adrs made occupied: no longer frontier cells"""
+    o = om.occ.copy()
+    o[np.asarray(adrs, dtype=np.int64)] = om.l_max
+    return o
