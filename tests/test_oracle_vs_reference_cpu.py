@@ -427,6 +427,80 @@ def test_viewpoint_sampling_against_real_reference(tape, seed, size_xy):
     assert flips > 0
 
 
+def _vp_limit_scene(name):
+    """the scenes of tests/test_viewpoint_limits_gpu.py the reference can run as they are (its down_sample is 3, its
+    z cut 0.4 m), in the reference's cell order"""
+    kind, _, arg = name.partition(":")
+    if kind == "clearance":
+        return helpers.vp_scene_clearance(arg)[0]
+    if kind == "box_face":
+        return helpers.vp_scene_box_face(arg, 0, reference_order=True)[0]
+    if kind == "min_visib":  # (the edge is looked for, and checked on the oracle, in the order this test runs in)
+        v, n = helpers.vp_min_visib_edge(reference_order=True)
+        helpers.vp_guard_min_visib(v, n, reference_order=True)
+        return helpers.vp_scene_occluded(min_visib_num=v - int(arg))
+    if kind == "max_dist":
+        base, p, edges = helpers.vp_max_dist_edges(down_sample=3, reference_order=True)
+        helpers.vp_guard_max_dist(base, p, edges, reference_order=True)
+        return base.variant(max_dist=edges[arg])
+    if kind == "collinear":
+        return helpers.vp_scene_collinear()
+    if kind == "frustum":
+        return helpers.vp_scene_frustum(arg)
+    if kind == "yaw":
+        scene = helpers.vp_scene_yaw_wrap("step" if arg == "step" else "patch")
+        if arg == "above_axis":
+            scene.vcfg["dphi"] = helpers.VP_DPHI_ABOVE
+        return scene
+    if kind == "grid":
+        return helpers.vp_scene_occluded(arg)
+    assert kind == "table"
+    return helpers.vp_scene_occluded(**helpers.VP_TABLES[arg])
+
+
+@pytest.mark.parametrize("name", [
+    "clearance:v2_nominal3", "clearance:v4", "box_face:x_min", "box_face:y_max", "min_visib:0", "min_visib:1",
+    "max_dist:between", "max_dist:equal", "max_dist:below", "collinear", "frustum:patch", "frustum:room",
+    "yaw:below_axis", "yaw:above_axis", "yaw:step", "grid:r0.15_offset", "grid:r0.05_offset", "table:rnum5",
+    "table:dphi0.5", "table:dphi7", "table:rmin0.05"])
+def test_viewpoint_limit_scenes_against_real_reference(tape, name):
+    """The hand-written states of the viewpoint-limits suite (helpers.vp_*) through the REAL frontier_finder.cpp and
+    perception_utils.cpp: the oracle the device is compared with there is itself bit-equal to the reference on them --
+    inflation, clusters, filtered cells, the active / dormant split, and per cluster positions, yaws and counts."""
+    scene = _vp_limit_scene(name)
+    assert scene.finder["down_sample"] == 3 and scene.finder["min_z"] == 0.4
+    om = helpers.vp_map(scene)
+    rm = helpers.vp_map(scene, ref.RefMap) if LIVE else None
+    occ = helpers.vp_occupancy(om, scene.paint)
+    for m_ in maps(om, rm):
+        m_.occ[:] = occ
+        m_.set_local_bound(*helpers.full_box(om.nvox))
+        m_.inflate_local()
+        m_.set_updated_box(*helpers.vp_whole_map(om))
+    tape.equal(om.infl, lambda: rm.infl)
+    vcfg = fo.viewpoint_cfg(**scene.vcfg)
+    of = fo.OracleFrontier(om, split=True, **scene.finder)
+    of.set_viewpoint_cfg(vcfg)
+    rf = ref.RefFrontier(rm, cluster_min=scene.finder["cluster_min"], cluster_size_xy=scene.finder["cluster_size_xy"],
+                         viewpoint_cfg=vcfg) if rm is not None else None
+    n = of.search()
+    tape.equal(n, lambda: rf.search())
+    assert n > 0
+    for k in range(n):
+        tape.equal(of.filtered(0, k), lambda: rf.filtered(0, k))
+    for f in maps(of, rf):
+        f.compute_to_visit()
+    n_act, n_dor = len(of.clusters(1)), len(of.clusters(2))
+    tape.equal([n_act, n_dor], lambda: [len(rf.clusters(1)), len(rf.clusters(2))])
+    assert n_act > 0 and helpers.vp_min_cell_distance(of, scene.vcfg) > 1e-6
+    for k in range(n_act):
+        pa, va = of.viewpoints(1, k)
+        tape.equal(va, lambda: rf.viewpoints(1, k)[1])
+        tape.equal(pa, lambda: rf.viewpoints(1, k)[0])
+    for i, a in enumerate(of.clusters(1) + of.clusters(2)):
+        tape.equal(a, lambda: (rf.clusters(1) + rf.clusters(2))[i])
+
+
 # ---- NonUniformBspline glue (bspline/src/non_uniform_bspline.cpp compiled unmodified) ----
 def _spline_case(seed, K, ts):
     rng = np.random.default_rng(seed)
