@@ -95,6 +95,13 @@ class RefineCfg(C.Structure):
                 ("tour_lattice_res", C.c_double), ("max_tour_points", C.c_int), ("flags", C.c_int)]
 
 
+class GoalCfg(C.Structure):
+    """fuelmi_goal_cfg: the search to the next viewpoint (lattice 0.2), shortenPath's and the length branch's constants."""
+    _fields_ = [("path", PathCfg), ("shorten_dist", C.c_double), ("end_eps", C.c_double), ("radius_close", C.c_double),
+                ("radius_far", C.c_double), ("max_way_points", C.c_int)]
+
+
+GOAL_CLOSE, GOAL_MID, GOAL_FAR, GOAL_NO_PATH = 0, 1, 2, 3
 REFINE_LAST_ARGMIN = 1
 REFINE_MAX_LAYERS, REFINE_MAX_NODES = 64, 256
 
@@ -213,6 +220,8 @@ SYMBOLS = {
     "fuelmi_map_path_costs": (C.c_int, [_P, C.POINTER(PathCfg), C.c_int, _dp, _dp, _dp, _ip, _ip, _dp]),
     "fuelmi_map_path_stats": (C.c_int, [_P, _ip]),
     "fuelmi_map_refine_tours": (C.c_int, [_P, C.POINTER(RefineCfg), C.c_int, _dp, _ip, _ip, _dp, _ip, _dp, _ip, _dp]),
+    "fuelmi_map_goal_paths": (C.c_int, [_P, C.POINTER(GoalCfg), C.c_int, _dp, _dp, _ip, _dp, _ip, _dp, _dp, _ip, _dp]),
+    "fuelmi_map_goal_path_times": (C.c_int, [_P, _dp]),
     "fuelmi_tsp_create": (C.c_int, [C.c_int, C.POINTER(TspCfg), _PP]),
     "fuelmi_tsp_destroy": (None, [_P]),
     "fuelmi_tsp_solve": (C.c_int, [_P, C.c_int, _ip, C.POINTER(C.c_int32), _ip, C.POINTER(C.c_int64), _ip]),

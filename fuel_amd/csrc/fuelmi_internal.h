@@ -219,6 +219,11 @@ struct fuelmi_map {
   // grow-only device scratch of fuelmi_map_refine_tours (refine.hip): problems in, choices / costs out
   void* refine_dev = nullptr;
   size_t refine_dev_bytes = 0;
+  // grow-only device scratch of fuelmi_map_goal_paths (goal_path.hip): results out; the events that split its time
+  void* goal_dev = nullptr;
+  size_t goal_dev_bytes = 0;
+  hipEvent_t goal_ev[3] = {nullptr, nullptr, nullptr};
+  double goal_ms[2] = {0.0, 0.0};  // fuelmi_map_goal_path_times
   unsigned long long fusion_count = 0;  // fusions / uploads queued so far (a search notices one queued behind its back)
   unsigned profile_mask = 0;
   ProfileSlot prof[FUELMI_K_COUNT];
@@ -497,15 +502,19 @@ int esdf_update(fuelmi_map* m);
 size_t esdf_handover_bytes(int nx, int ny, int nz);  // esdf_tmp16 of a grid (0: the packed family cannot run)
 int insert_points(fuelmi_map* m, const float* xyz, int stride_bytes, int n, const double cam[3]);
 void path_cost_release(fuelmi_map* m);  // the path and refinement scratch
+void goal_path_release(fuelmi_map* m);  // the goal-path scratch and its events (goal_path.hip)
 // device results of one path_cost_enqueue, in the map's path scratch: length / kind / path_len per pair, paths
-// [n][maxp][3] (nullptr when maxp is 0)
+// [n][maxp][3] (nullptr when maxp is 0), and the device copy of p2_xyz
 struct PathRun {
   double* length = nullptr;
   int* kind = nullptr;
   int* plen = nullptr;
   double* path = nullptr;
+  const double* p2 = nullptr;
 };
+// always_lattice: no straight-line attempt, every pair goes to the lattice search (Astar::search as
+// FastExplorationManager calls it, goal_path.hip)
 int path_cost_enqueue(fuelmi_map* m, const fuelmi_path_cfg* cfg, int n, const double* p1_xyz, const double* p2_xyz,
-                      int maxp, PathRun& out);
+                      int maxp, PathRun& out, bool always_lattice = false);
 
 #endif

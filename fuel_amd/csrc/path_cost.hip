@@ -443,10 +443,11 @@ void path_cost_release(fuelmi_map* m) {
 
 // The searches of n pairs queued on the map's stream: source dedup, chunks, k_path_los / _mask / _relax / _goal.  The
 // results stay in the map's path scratch (valid until the next enqueue); fuelmi_map_path_stats' counters accumulate.
-// The caller has checked the arguments (finite, |coordinate| < 1e7) and n > 0.
+// The caller has checked the arguments (finite, |coordinate| < 1e7) and n > 0.  always_lattice: k_path_los is skipped
+// and every pair is searched on its source's lattice.
 
 int path_cost_enqueue(fuelmi_map* m, const fuelmi_path_cfg* cfg, int n, const double* p1_xyz, const double* p2_xyz,
-                      int maxp, PathRun& out) {
+                      int maxp, PathRun& out, bool always_lattice) {
   HIPCHK(hipSetDevice(m->device));
   const Geo& g = m->g;
 
@@ -550,12 +551,14 @@ int path_cost_enqueue(fuelmi_map* m, const fuelmi_path_cfg* cfg, int n, const do
   hipStream_t st = m->stream;
   HIPCHK(hipMemcpyAsync(d_p1, p1_xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_p2, p2_xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_path_los, dim3((n + 255) / 256), dim3(256), 0, st, g, A, n, d_p1, d_p2, d_len, d_kind, d_plen,
-                     d_path, maxp);
-  HIPCHK(hipGetLastError());
-  std::vector<int> hk(n);
-  HIPCHK(hipMemcpyAsync(hk.data(), d_kind, sizeof(int) * n, hipMemcpyDeviceToHost, st));
-  HIPCHK(stream_wait(st));
+  std::vector<int> hk(n, -1);
+  if (!always_lattice) {
+    hipLaunchKernelGGL(k_path_los, dim3((n + 255) / 256), dim3(256), 0, st, g, A, n, d_p1, d_p2, d_len, d_kind, d_plen,
+                       d_path, maxp);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hk.data(), d_kind, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+    HIPCHK(stream_wait(st));
+  }
 
   // the sources the straight line did not settle, in first-seen order, with their pairs
   std::vector<std::vector<int>> pairs_of(lat.size());
@@ -644,6 +647,7 @@ int path_cost_enqueue(fuelmi_map* m, const fuelmi_path_cfg* cfg, int n, const do
   out.kind = d_kind;
   out.plen = d_plen;
   out.path = d_path;
+  out.p2 = d_p2;
   return FUELMI_OK;
 }
 

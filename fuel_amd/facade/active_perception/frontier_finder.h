@@ -98,6 +98,16 @@ public:
   bool refineSingleDestination(const Vector3d& cur_pos, const Vector3d& cur_vel, const Vector3d& cur_yaw,
                                const vector<Vector3d>& points, const vector<double>& yaws, int& min_cost_id);
 
+  // addition: the geometric path to the next viewpoint, FastExplorationManager::planExploreMotion's Astar::search +
+  // shortenPath + length branch (fast_exploration_manager.cpp:234-276, 295-325) on the device (fuelmi_map_goal_paths,
+  // lattice 0.2).  Returns the branch: GOAL_CLOSE / GOAL_FAR -- planExploreTraj on path_next_goal (the shortened
+  // path, truncated at 5 m for GOAL_FAR); GOAL_MID -- kinodynamicReplan to next_goal (path_next_goal: the shortened
+  // path); GOAL_NO_PATH -- the reference's `return FAIL` (path_next_goal empty, with a message); GOAL_ERROR -- the
+  // device call failed.  next_goal: ed_->next_goal_.
+  enum { GOAL_ERROR = -1, GOAL_CLOSE = 0, GOAL_MID = 1, GOAL_FAR = 2, GOAL_NO_PATH = 3 };
+  int planPathToViewpoint(const Vector3d& cur_pos, const Vector3d& next_pos, vector<Vector3d>& path_next_goal,
+                          Vector3d& next_goal);
+
   // addition: FastExplorationManager::findGlobalTour (fast_exploration_manager.cpp:327-420) without the file round
   // trip through LKH: updateFrontierCostMatrix, getFullCostMatrix, the reference's int(cost * 100), then the device
   // ATSP solver (fuelmi_tsp_solve, created on first use on the map's device with the FUELMI_TSP_DEFAULT_* settings).

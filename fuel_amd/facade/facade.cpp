@@ -776,6 +776,43 @@ bool FrontierFinder::refineSingleDestination(const Vector3d& cur_pos, const Vect
   return true;
 }
 
+int FrontierFinder::planPathToViewpoint(const Vector3d& cur_pos, const Vector3d& next_pos,
+                                        vector<Vector3d>& path_next_goal, Vector3d& next_goal) {
+  // fast_exploration_manager.cpp:234-276
+  fuelmi_goal_cfg c;
+  c.path.lattice_res = 0.2;  // astar/resolution_astar (algorithm.xml)
+  c.path.edge_step = 0.1;    // astar2.cpp:105
+  c.path.no_path_cost = 0.0;
+  c.path.max_path_points = 2048;
+  c.shorten_dist = 3.0;  // :301
+  c.end_eps = 1e-3;      // :319
+  c.radius_close = 1.5;  // :243
+  c.radius_far = 5.0;    // :242
+  c.max_way_points = 64;
+  const double s[3] = {cur_pos(0), cur_pos(1), cur_pos(2)}, g[3] = {next_pos(0), next_pos(1), next_pos(2)};
+  int status = -1, n_way = 0, raw_len = 0, rc = FUELMI_OK;
+  double length = 0.0, ng[3] = {g[0], g[1], g[2]};
+  vector<double> way;
+  fuelmi_map* m = edt_env_->sdf_map_->device();
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    way.assign((size_t)c.max_way_points * 3, 0.0);
+    rc = fuelmi_map_goal_paths(m, &c, 1, s, g, &status, &length, &n_way, way.data(), ng, &raw_len, nullptr);
+    if (rc != FUELMI_ELIMIT) break;
+    c.path.max_path_points = std::max(c.path.max_path_points, raw_len);  // both hold the full counts: grow once
+    c.max_way_points = std::max(c.max_way_points, n_way);
+  }
+  warn("fuelmi_map_goal_paths", rc);
+  path_next_goal.clear();
+  if (rc != FUELMI_OK) return GOAL_ERROR;
+  next_goal = Vector3d(ng[0], ng[1], ng[2]);
+  if (status == FUELMI_GOAL_NO_PATH) {
+    std::fprintf(stderr, "[fuelmi facade] FrontierFinder::planPathToViewpoint: no path to the next viewpoint\n");
+    return GOAL_NO_PATH;
+  }
+  for (int r = 0; r < n_way; ++r) path_next_goal.push_back(Vector3d(way[3 * r], way[3 * r + 1], way[3 * r + 2]));
+  return status;
+}
+
 void FrontierFinder::setNextFrontier(const int& id) {  // declared by the reference, never defined there
   for (auto& ftr : frontiers_)
     if (ftr.id_ == id) next_frontier_ = ftr;

@@ -13,7 +13,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BsplineBatch, BsplineCfg, FrontierCfg, MapCfg, MapInfo, PathCfg, RefineCfg, TspCfg, check, lib)
+from ._lib import (BsplineBatch, BsplineCfg, FrontierCfg, GoalCfg, MapCfg, MapInfo, PathCfg, RefineCfg, TspCfg, check,
+                   lib)
 
 # exploration.launch / algorithm.xml defaults (exploration_manager/launch/algorithm.xml:33-59,170-181)
 DEFAULT_MAP = dict(resolution=0.1, ground_height=-1.0, obstacles_inflation=0.199,
@@ -312,6 +313,46 @@ class SDFMap:
         choices = [choice[layer_ptr[b]:layer_ptr[b + 1]].copy() for b in range(B)]
         tours = None if txyz is None else [txyz[b, :tlen[b]].copy() for b in range(B)]
         return choices, cost, tours
+
+    # --- the path to the next viewpoint for a batch of problems (include/fuelmi.h fuelmi_map_goal_paths) ---
+    GOAL_CLOSE, GOAL_MID, GOAL_FAR, GOAL_NO_PATH = _lib.GOAL_CLOSE, _lib.GOAL_MID, _lib.GOAL_FAR, _lib.GOAL_NO_PATH
+
+    def goal_paths(self, starts, goals, res=0.2, edge_step=0.1, shorten_dist=3.0, end_eps=1e-3, radius_close=1.5,
+                   radius_far=5.0, max_path_points=4096, max_way_points=64, raw=True, allow_limit=False):
+        """Astar::search + shortenPath + the length branch of planExploreMotion per (start, goal).  Returns a dict:
+        status [n] (GOAL_*; -1: the raw path did not fit), length [n] (of the shortened path, before truncation), n_way
+        [n], way (list of [k, 3] arrays, at most max_way_points each), next_goal [n, 3], and with raw: raw_len [n],
+        raw (list of [k, 3] arrays, empty where the path did not fit), and limit (a count exceeded its maximum).
+        FUELMI_ELIMIT raises FuelmiError unless allow_limit."""
+        p1 = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+        p2 = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 3)
+        assert len(p1) == len(p2)
+        n = len(p1)
+        c = GoalCfg(PathCfg(float(res), float(edge_step), 0.0, int(max_path_points)), float(shorten_dist),
+                    float(end_eps), float(radius_close), float(radius_far), int(max_way_points))
+        status = np.zeros(n, dtype=np.int32)
+        length = np.zeros(n)
+        n_way = np.zeros(n, dtype=np.int32)
+        way = np.zeros((n, max(int(max_way_points), 0), 3))
+        nxt = np.zeros((n, 3))
+        rlen = np.zeros(n, dtype=np.int32) if raw else None
+        rxyz = np.zeros((n, max(int(max_path_points), 0), 3)) if raw else None
+        rc = self.L.fuelmi_map_goal_paths(self.h, C.byref(c), n, _dp(p1), _dp(p2), _ip(status), _dp(length), _ip(n_way),
+                                          _dp(way), _dp(nxt), _ip(rlen), _dp(rxyz))
+        if not (allow_limit and rc == -5):
+            check(rc)
+        out = {"status": status, "length": length, "n_way": n_way, "next_goal": nxt, "limit": rc == -5,
+               "way": [way[b, :min(n_way[b], way.shape[1])].copy() for b in range(n)]}
+        if raw:
+            out["raw_len"] = rlen
+            out["raw"] = [rxyz[b, :rlen[b] if rlen[b] <= rxyz.shape[1] else 0].copy() for b in range(n)]
+        return out
+
+    def goal_path_times(self):
+        """device milliseconds of the last goal_paths call: (the lattice run, k_goal_shorten)"""
+        ms = np.zeros(2)
+        check(self.L.fuelmi_map_goal_path_times(self.h, _dp(ms)))
+        return float(ms[0]), float(ms[1])
 
     # --- measurement ---
     def timerBegin(self):

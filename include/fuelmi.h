@@ -423,6 +423,59 @@ int fuelmi_map_refine_tours(fuelmi_map* m, const fuelmi_refine_cfg* cfg, int n_p
                             int* tour_len, double* tour_xyz);
 
 /* ------------------------------------------------------------------------------------------
+ * Path to the next viewpoint: the geometric part of FastExplorationManager::planExploreMotion (exploration_manager/
+ * src/fast_exploration_manager.cpp:234-276) with shortenPath (:295-325), for n_prob independent problems
+ * (start, goal) in one call.  Per problem:
+ *   1. raw path: Astar::search(start, goal) as the lattice search of fuelmi_map_path_costs' kind 1 at cfg.path
+ *      (lattice_res 0.2, the manager's astar/resolution_astar) -- ALWAYS the lattice, no straight-line attempt:
+ *      [start, nodes..., goal]; start = goal gives {start, goal}.  No goal node reachable: status
+ *      FUELMI_GOAL_NO_PATH (the reference's `return FAIL`), n_way 0, raw_len 0, length 0, next_goal = goal.
+ *   2. shortenPath, literally: short = [path[0]]; for i = 1 .. size-2: if |path[i] - short.back()| > shorten_dist push
+ *      path[i], else walk RayCaster::input(short.back(), path[i+1]) / nextId and push path[i] at the first voxel that
+ *      is inflated or UNKNOWN (no box test; voxels outside the map pass; the walk starts in short.back()'s voxel and
+ *      stops before path[i+1]'s).  Then push path.back() iff |path.back() - short.back()| > end_eps; then, iff
+ *      exactly two points are left, insert 0.5 * (short[0] + short[1]) between them.  ({p, p} comes out as {p}.)
+ *   3. length = Astar::pathLength(short): segment norms sqrt(x x + y y + z z) summed left to right.
+ *      length < radius_close: FUELMI_GOAL_CLOSE, way-points = short, next_goal = goal.
+ *      length > radius_far:   FUELMI_GOAL_FAR: trunc = [short[0]], len2 = 0, for i = 1 while i < size and len2 <
+ *                             radius_far: len2 += |short[i] - trunc.back()|, push short[i]; way-points = trunc,
+ *                             next_goal = trunc.back().
+ *      otherwise:             FUELMI_GOAL_MID (the reference's kinodynamicReplan branch): way-points = short,
+ *                             next_goal = goal.
+ * Every quantity is f64 + - * / sqrt in the order written: results do not depend on the batch.
+ * Differences from the reference are those of the lattice search: the shortest lattice path in
+ * place of A*'s, no wall-clock cap, no node pool.
+ * Limits: all arguments are checked on the host before the map is touched (points finite with |coordinate| < 1e7;
+ * lattice_res, edge_step, shorten_dist, radius_close, radius_far > 0 and finite, end_eps >= 0, max_path_points >= 2,
+ * max_way_points >= 1: FUELMI_EINVAL).  A raw path of more than max_path_points points: raw_len holds the full count,
+ * status -1, n_way 0; more way-points than max_way_points: n_way holds the full count, the first max_way_points are
+ * written, status / length / next_goal are complete.  Either way every other problem is complete and the call
+ * returns FUELMI_ELIMIT.  n_prob = 0 is FUELMI_OK.  Same thread rule as the mutators; fuelmi_map_path_stats
+ * afterwards describes the lattice run.
+ * ---------------------------------------------------------------------------------------- */
+#define FUELMI_GOAL_CLOSE 0   /* length < radius_close: planExploreTraj on the way-points */
+#define FUELMI_GOAL_MID 1     /* kinodynamicReplan to the goal */
+#define FUELMI_GOAL_FAR 2     /* length > radius_far: planExploreTraj on the truncated way-points */
+#define FUELMI_GOAL_NO_PATH 3 /* the search reached no goal node */
+typedef struct {
+  fuelmi_path_cfg path; /* lattice_res 0.2, edge_step 0.1; max_path_points = cap of a raw path (no_path_cost unused) */
+  double shorten_dist;  /* 3.0 (:301) */
+  double end_eps;       /* 1e-3 (:319) */
+  double radius_close;  /* 1.5 (:243) */
+  double radius_far;    /* 5.0 (:242) */
+  int max_way_points;   /* per problem, for way_xyz */
+} fuelmi_goal_cfg;
+/* start_xyz, goal_xyz: n_prob points each (host).  Out, per problem: status (FUELMI_GOAL_*), length (of short,
+ * before truncation), n_way and way_xyz [n_prob][max_way_points][3] (entries past n_way unspecified), next_goal
+ * [n_prob][3]; raw_len [n_prob] and raw_xyz [n_prob][max_path_points][3], the raw path, may each be NULL. */
+int fuelmi_map_goal_paths(fuelmi_map* m, const fuelmi_goal_cfg* cfg, int n_prob, const double* start_xyz,
+                          const double* goal_xyz, int* status, double* length, int* n_way, double* way_xyz,
+                          double* next_goal, int* raw_len, double* raw_xyz);
+/* device milliseconds of the last fuelmi_map_goal_paths on this map, from events on the map's stream: [0] the lattice
+ * run (with the host's looks at its work lists), [1] k_goal_shorten.  Zeros before the first call. */
+int fuelmi_map_goal_path_times(const fuelmi_map* m, double ms2[2]);
+
+/* ------------------------------------------------------------------------------------------
  * Global tour: the ATSP of FastExplorationManager::findGlobalTour (exploration_manager/src/
  * fast_exploration_manager.cpp:327-420), which the reference hands to LKH-2 as int(cost * 100) in a TSPLIB file,
  * for n_prob independent int32 matrices in one call.  Needs no map: the solver owns a stream and a workspace that
