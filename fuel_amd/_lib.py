@@ -102,6 +102,16 @@ class GoalCfg(C.Structure):
 
 
 GOAL_CLOSE, GOAL_MID, GOAL_FAR, GOAL_NO_PATH = 0, 1, 2, 3
+
+
+class WptrajCfg(C.Structure):
+    """fuelmi_wptraj_cfg: the constants of planExploreTraj's first half and the strides of the way-point / sample arrays."""
+    _fields_ = [("max_vel", C.c_double), ("ctrl_pt_dist", C.c_double), ("min_seg", C.c_int), ("seg_num", C.c_int),
+                ("max_way_points", C.c_int), ("max_samples", C.c_int)]
+
+
+WPTRAJ_OK, WPTRAJ_FEW, WPTRAJ_DEGENERATE = 0, 1, 2
+WPTRAJ_MAX_WAY, WPTRAJ_MAX_SEG, WPTRAJ_MAX_DURATION = 256, 1 << 20, 1.0e4
 REFINE_LAST_ARGMIN = 1
 REFINE_MAX_LAYERS, REFINE_MAX_NODES = 64, 256
 
@@ -222,6 +232,9 @@ SYMBOLS = {
     "fuelmi_map_refine_tours": (C.c_int, [_P, C.POINTER(RefineCfg), C.c_int, _dp, _ip, _ip, _dp, _ip, _dp, _ip, _dp]),
     "fuelmi_map_goal_paths": (C.c_int, [_P, C.POINTER(GoalCfg), C.c_int, _dp, _dp, _ip, _dp, _ip, _dp, _dp, _ip, _dp]),
     "fuelmi_map_goal_path_times": (C.c_int, [_P, _dp]),
+    "fuelmi_map_waypoint_trajs": (C.c_int, [_P, C.POINTER(WptrajCfg), C.c_int, _ip, _dp, _dp, _dp, _ip, _dp, _dp, _ip, _dp,
+                                            _ip, _dp, _dp, _dp, _dp]),
+    "fuelmi_wptraj_plan": (C.c_int, [C.POINTER(WptrajCfg), _ip]),
     "fuelmi_tsp_create": (C.c_int, [C.c_int, C.POINTER(TspCfg), _PP]),
     "fuelmi_tsp_destroy": (None, [_P]),
     "fuelmi_tsp_solve": (C.c_int, [_P, C.c_int, _ip, C.POINTER(C.c_int32), _ip, C.POINTER(C.c_int64), _ip]),
@@ -240,6 +253,7 @@ SYMBOLS = {
     "fuelmi_bspline_parameterize": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
     "fuelmi_bspline_boundary_states": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp]),
     "fuelmi_bspline_dev_load_samples": (C.c_int, [_P, C.c_int, _dp, _dp, _dp]),
+    "fuelmi_bspline_dev_load_waypoints": (C.c_int, [_P, C.POINTER(WptrajCfg), _ip, _dp, _dp, _dp, _ip, _dp]),
     "fuelmi_timer_begin": (C.c_int, [_P]),
     "fuelmi_timer_end": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "fuelmi_profile_enable": (C.c_int, [_P, C.c_uint]),

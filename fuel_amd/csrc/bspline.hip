@@ -747,6 +747,7 @@ struct FitArgs {
   double* pt_dist;       // [C]      optimize() :136-140
   double* start_state;   // [C][3][3]  getBoundaryStates(2, 0).start
   double* end_state;     // [C][3][3]  row 0 = getBoundaryStates(2, 0).end[0]
+  const int* skip;       // [C] or null: a candidate with skip[c] != 0 is left as it is
 };
 
 // value at t = 0 (at_end = false) or t = duration of the d-th derivative of the uniform B-spline with
@@ -816,6 +817,7 @@ __global__ __launch_bounds__(64) void k_bspline_fit(FitArgs F) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int c = blockIdx.x, lane = threadIdx.x;
   const int K = F.K, p = F.degree, n = K + p - 1, hb = p - 1, R = K + 4;
+  if (F.skip && F.skip[c] != 0) return;
   double* wts = reinterpret_cast<double*>(smem_raw);  // pos / vel / acc coefficients, 5 each
   double* M = wts + 16;                               // [n][5]  M(j, j-d) at [j][d]
   double* g = M + 5 * n;                              // [n][3]
@@ -1482,4 +1484,100 @@ extern "C" int fuelmi_bspline_dev_load_samples(fuelmi_bspline_dev* b, int n_poin
   F.end_state = const_cast<double*>(A.end_state);
   StageScope sc(m, FUELMI_K_BSPLINE);
   return fit_launch(m, F);
+}
+
+// way-points -> min-jerk samples (k_waypoint_traj, written into the staging) -> the fit above, all on the map's stream
+extern "C" int fuelmi_bspline_dev_load_waypoints(fuelmi_bspline_dev* b, const fuelmi_wptraj_cfg* cfg, const int* n_way,
+                                                 const double* way_xyz, const double* vel_xyz, const double* acc_xyz,
+                                                 int* status, double* duration) {
+  ARGCHK(b && cfg && status);
+  BsplineArgs& A = b->a;
+  const int degree = A.cfg.bspline_degree;
+  ARGCHK(A.dim == 3 && degree >= 3 && degree <= 5 && A.N - degree >= 1);
+  const int seg = A.N - degree, n_points = seg + 1;
+  ARGCHK(cfg->seg_num == 0 || cfg->seg_num == seg);
+  fuelmi_wptraj_cfg wc = *cfg;
+  wc.seg_num = seg, wc.max_samples = n_points;
+  {
+    const int rc = wptraj_check(&wc, A.C, n_way, way_xyz, vel_xyz, acc_xyz);
+    if (rc) return rc;
+  }
+  fuelmi_map* m = b->map;
+  ARGCHK(m);
+  HIPCHK(hipSetDevice(m->device));
+  const size_t C = (size_t)A.C, K = (size_t)n_points, maxw = (size_t)wc.max_way_points;
+  auto pad = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  const size_t b_ts = C * sizeof(double), b_pts = C * K * 3 * sizeof(double), b_der = C * 12 * sizeof(double);
+  const size_t fit_bytes = pad(b_ts + b_pts + b_der);  // the layout fuelmi_bspline_dev_load_samples stages
+  const size_t b_int = pad(C * sizeof(int)), b_dbl = pad(C * sizeof(double)), b_way = pad(C * maxw * 3 * sizeof(double)),
+               b_v3 = pad(C * 3 * sizeof(double));
+  const size_t total = fit_bytes + 4 * b_int + 2 * b_dbl + b_way + 2 * b_v3;
+  if (total > b->fit_cap) {
+    void* d = nullptr;
+    HIPCHK(hipMalloc(&d, total));
+    b->allocs.push_back(d);
+    b->fit_in = static_cast<double*>(d);
+    b->fit_cap = total;
+  }
+  unsigned char* d = reinterpret_cast<unsigned char*>(b->fit_in);
+  unsigned char* at = d + fit_bytes;
+  auto take = [&](size_t bytes) {
+    unsigned char* p = at;
+    at += bytes;
+    return p;
+  };
+  WpTrajArgs W;
+  memset(&W, 0, sizeof(W));
+  W.n_prob = A.C;
+  W.maxw = wc.max_way_points;
+  W.max_vel = wc.max_vel, W.ctrl_pt_dist = wc.ctrl_pt_dist;
+  W.min_seg = wc.min_seg, W.forced_seg = seg, W.max_samples = n_points;
+  int* d_nway = reinterpret_cast<int*>(take(b_int));
+  double* d_way = reinterpret_cast<double*>(take(b_way));
+  double* d_vel = reinterpret_cast<double*>(take(b_v3));
+  double* d_acc = reinterpret_cast<double*>(take(b_v3));
+  hipStream_t st = m->stream;
+  HIPCHK(hipMemcpyAsync(d_nway, n_way, C * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_way, way_xyz, C * maxw * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_vel, vel_xyz, C * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_acc, acc_xyz, C * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  W.n_way = d_nway, W.way = d_way, W.vel = d_vel, W.acc = d_acc;
+  W.status = reinterpret_cast<int*>(take(b_int));
+  W.seg_num = reinterpret_cast<int*>(take(b_int));
+  W.n_samples = reinterpret_cast<int*>(take(b_int));
+  W.duration = reinterpret_cast<double*>(take(b_dbl));
+  W.length = reinterpret_cast<double*>(take(b_dbl));
+  W.dt = reinterpret_cast<double*>(d);  // the fit's knot spans
+  W.samples = reinterpret_cast<double*>(d + b_ts);
+  W.derivs = reinterpret_cast<double*>(d + b_ts + b_pts);
+  FitArgs F;
+  memset(&F, 0, sizeof(F));
+  F.C = A.C, F.K = n_points, F.degree = degree;
+  F.ts = W.dt;
+  F.points = W.samples;
+  F.derivs = W.derivs;
+  F.ctrl = const_cast<double*>(A.x);
+  F.stride = A.nvar;
+  F.write_dt = (A.cost_function & FUELMI_COST_MINTIME) ? 1 : 0;
+  F.knot_span = const_cast<double*>(A.knot_span);
+  F.pt_dist = const_cast<double*>(A.pt_dist);
+  F.start_state = const_cast<double*>(A.start_state);
+  F.end_state = const_cast<double*>(A.end_state);
+  F.skip = W.status;
+  {
+    StageScope sc(m, FUELMI_K_BSPLINE);
+    const int rcw = wptraj_launch(st, W);
+    if (rcw) return rcw;
+    const int rcf = fit_launch(m, F);
+    if (rcf) return rcf;
+  }
+  HIPCHK(hipMemcpyAsync(status, W.status, C * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (duration) HIPCHK(hipMemcpyAsync(duration, W.duration, C * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(stream_wait(st));
+  for (int c = 0; c < A.C; ++c)
+    if (status[c] == -1) {
+      fuelmi_set_error("waypoint trajectories: candidate %d does not give %d samples", c, n_points);
+      return FUELMI_ELIMIT;
+    }
+  return FUELMI_OK;
 }

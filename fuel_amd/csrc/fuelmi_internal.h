@@ -503,6 +503,31 @@ size_t esdf_handover_bytes(int nx, int ny, int nz);  // esdf_tmp16 of a grid (0:
 int insert_points(fuelmi_map* m, const float* xyz, int stride_bytes, int n, const double cam[3]);
 void path_cost_release(fuelmi_map* m);  // the path and refinement scratch
 void goal_path_release(fuelmi_map* m);  // the goal-path scratch and its events (goal_path.hip)
+// k_waypoint_traj (waypoint_traj.hip): one problem per workgroup; every pointer addresses memory the device can reach
+struct WpTrajArgs {
+  int n_prob;
+  const int* n_way;    // [n]
+  const double* way;   // [n][maxw][3]
+  const double* vel;   // [n][3]
+  const double* acc;   // [n][3]
+  int maxw;
+  double max_vel, ctrl_pt_dist;
+  int min_seg, forced_seg, max_samples;
+  int* status;
+  double* duration;
+  double* length;
+  int* seg_num;
+  double* dt;
+  int* n_samples;
+  double* samples;     // [n][max_samples][3]
+  double* derivs;      // [n][4][3]
+  double* seg_times;   // [n][maxw-1] or null
+  double* coef;        // [n][maxw-1][3][6] or null
+};
+// the host checks of fuelmi_map_waypoint_trajs / fuelmi_bspline_dev_load_waypoints; the launch on stream st
+int wptraj_check(const fuelmi_wptraj_cfg* cfg, int n_prob, const int* n_way, const double* way_xyz,
+                 const double* vel_xyz, const double* acc_xyz);
+int wptraj_launch(hipStream_t st, const WpTrajArgs& W);
 // device results of one path_cost_enqueue, in the map's path scratch: length / kind / path_len per pair, paths
 // [n][maxp][3] (nullptr when maxp is 0), and the device copy of p2_xyz
 struct PathRun {

@@ -58,6 +58,20 @@ public:
                 const int& max_time_id);
   void optimize();
 
+  // addition: the body of FastPlannerManager::planExploreTraj from the way-points to the solved spline
+  // (plan_manage/src/planner_manager.cpp:270-312) in four device calls: fuelmi_map_waypoint_trajs (segment times,
+  // waypointsTraj, getLength, seg_num, samples, boundary derivatives) -> parameterizeToBspline -> getBoundaryStates(2, 0)
+  // -> setBoundaryStates, setTimeLowerBound (time_lb > 0) -> optimize(ctrl_pts, dt, cost_mask, 1, 1).
+  // Returns FUELMI_WPTRAJ_OK, or without touching ctrl_pts / dt: FUELMI_WPTRAJ_FEW (fewer than three points, the empty
+  // tour included), FUELMI_WPTRAJ_DEGENERATE (two consecutive points coincide), or the negative FUELMI_E* of a call
+  // that failed.
+  int planThroughWaypoints(const vector<Eigen::Vector3d>& tour, const Eigen::Vector3d& cur_vel,
+                           const Eigen::Vector3d& cur_acc, double max_vel, double ctrl_pt_dist, int cost_mask,
+                           double time_lb, Eigen::MatrixXd& ctrl_pts, double& dt);
+  // diagnostics of the last planThroughWaypoints: what it handed to the solve, and the solve's final cost
+  Eigen::MatrixXd init_ctrl_pts_;
+  double init_knot_span_ = 0.0, final_cost_ = 0.0;
+
   Eigen::MatrixXd getControlPoints();
   vector<Eigen::Vector3d> matrixToVectors(const Eigen::MatrixXd& ctrl_pts);
 

@@ -1089,6 +1089,64 @@ void BsplineOptimizer::optimize() {
   if (optimize_time_) knot_span_ = best_variable_[n - 1];
 }
 
+int BsplineOptimizer::planThroughWaypoints(const vector<Eigen::Vector3d>& tour, const Eigen::Vector3d& cur_vel,
+                                           const Eigen::Vector3d& cur_acc, double max_vel, double ctrl_pt_dist,
+                                           int cost_mask, double time_lb, Eigen::MatrixXd& ctrl_pts, double& dt) {
+  if (tour.empty()) {
+    ROS_ERROR("Empty path to traj planner");
+    return FUELMI_WPTRAJ_FEW;
+  }
+  fuelmi_map* m = edt_environment_->sdf_map_->device();
+  const int n_way = (int)tour.size();
+  std::vector<double> way(3 * (size_t)n_way);
+  for (int i = 0; i < n_way; ++i)
+    for (int k = 0; k < 3; ++k) way[3 * i + k] = tour[i](k);
+  const double vel[3] = {cur_vel(0), cur_vel(1), cur_vel(2)}, acc[3] = {cur_acc(0), cur_acc(1), cur_acc(2)};
+  // :270-297 -- the sample count is a result: a second call with room for it when the first guess was short
+  fuelmi_wptraj_cfg wc = {max_vel, ctrl_pt_dist, 8, 0, n_way, 256};
+  int status = 0, seg_num = 0, n_samples = 0;
+  double duration = 0.0, length = 0.0, ts = 0.0, derivs[12];
+  std::vector<double> samples;
+  for (int pass = 0; pass < 2; ++pass) {
+    samples.assign(3 * (size_t)wc.max_samples, 0.0);
+    const int rc = fuelmi_map_waypoint_trajs(m, &wc, 1, &n_way, way.data(), vel, acc, &status, &duration, &length, &seg_num,
+                                             &ts, &n_samples, samples.data(), derivs, nullptr, nullptr);
+    if (rc == FUELMI_ELIMIT && status == -1 && pass == 0 && n_samples > wc.max_samples) {
+      wc.max_samples = n_samples;
+      continue;
+    }
+    if (rc) {
+      warn("fuelmi_map_waypoint_trajs", rc);
+      return rc;
+    }
+    break;
+  }
+  if (status != FUELMI_WPTRAJ_OK) return status;
+  // :299-309
+  const int rows = n_samples + bspline_degree_ - 1;
+  std::vector<double> ctrl(3 * (size_t)rows), st(9), en(3);
+  int rc = fuelmi_bspline_parameterize(m, 1, n_samples, bspline_degree_, &ts, samples.data(), derivs, ctrl.data());
+  if (!rc) rc = fuelmi_bspline_boundary_states(m, 1, rows, bspline_degree_, &ts, ctrl.data(), 2, 0, st.data(), en.data());
+  if (rc) {
+    warn("planThroughWaypoints: spline fit", rc);
+    return rc;
+  }
+  vector<Eigen::Vector3d> start, end;
+  for (int i = 0; i < 3; ++i) start.push_back(Eigen::Vector3d(st[3 * i], st[3 * i + 1], st[3 * i + 2]));
+  end.push_back(Eigen::Vector3d(en[0], en[1], en[2]));
+  setBoundaryStates(start, end);
+  if (time_lb > 0) setTimeLowerBound(time_lb);
+  ctrl_pts = Eigen::MatrixXd(rows, 3);
+  for (int i = 0; i < rows; ++i)
+    for (int k = 0; k < 3; ++k) ctrl_pts(i, k) = ctrl[3 * i + k];
+  dt = ts;
+  init_ctrl_pts_ = ctrl_pts;
+  init_knot_span_ = dt;
+  optimize(ctrl_pts, dt, cost_mask, 1, 1);  // :312
+  final_cost_ = min_cost_;
+  return FUELMI_WPTRAJ_OK;
+}
+
 vector<Eigen::Vector3d> BsplineOptimizer::matrixToVectors(const Eigen::MatrixXd& ctrl_pts) {
   vector<Eigen::Vector3d> out;
   for (int i = 0; i < ctrl_pts.rows(); ++i) {

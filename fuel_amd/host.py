@@ -13,8 +13,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BsplineBatch, BsplineCfg, FrontierCfg, GoalCfg, MapCfg, MapInfo, PathCfg, RefineCfg, TspCfg, check,
-                   lib)
+from ._lib import (BsplineBatch, BsplineCfg, FrontierCfg, GoalCfg, MapCfg, MapInfo, PathCfg, RefineCfg, TspCfg, WptrajCfg,
+                   check, lib)
 
 # exploration.launch / algorithm.xml defaults (exploration_manager/launch/algorithm.xml:33-59,170-181)
 DEFAULT_MAP = dict(resolution=0.1, ground_height=-1.0, obstacles_inflation=0.199,
@@ -37,6 +37,22 @@ def _dp(a):
 
 def _ip(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def _pack_waypoints(ways, vels, accs, max_vel, ctrl_pt_dist, min_seg, seg_num, max_way_points, max_samples):
+    """lists of [k, 3] way-point arrays -> (n_way [n], way [n, max_way_points, 3], vel [n, 3], acc [n, 3], WptrajCfg)"""
+    ways = [np.ascontiguousarray(w, dtype=np.float64).reshape(-1, 3) for w in ways]
+    n = len(ways)
+    vel = np.ascontiguousarray(vels, dtype=np.float64).reshape(n, 3)
+    acc = np.ascontiguousarray(accs, dtype=np.float64).reshape(n, 3)
+    n_way = np.array([len(w) for w in ways], dtype=np.int32)
+    maxw = int(max_way_points) if max_way_points is not None else max([len(w) for w in ways] + [3])
+    way = np.zeros((n, max(maxw, 0), 3))
+    for b, w in enumerate(ways):
+        k = min(len(w), way.shape[1])  # (a problem longer than max_way_points: the call refuses it by n_way)
+        way[b, :k] = w[:k]
+    c = WptrajCfg(float(max_vel), float(ctrl_pt_dist), int(min_seg), int(seg_num), maxw, int(max_samples))
+    return n_way, way, vel, acc, c
 
 
 def _d3(v):
@@ -353,6 +369,47 @@ class SDFMap:
         ms = np.zeros(2)
         check(self.L.fuelmi_map_goal_path_times(self.h, _dp(ms)))
         return float(ms[0]), float(ms[1])
+
+    # --- the min-jerk initial trajectory through way-points (include/fuelmi.h fuelmi_map_waypoint_trajs) ---
+    WPTRAJ_OK, WPTRAJ_FEW, WPTRAJ_DEGENERATE = _lib.WPTRAJ_OK, _lib.WPTRAJ_FEW, _lib.WPTRAJ_DEGENERATE
+
+    def waypoint_trajs(self, ways, vels, accs, max_vel=2.0, ctrl_pt_dist=0.45, min_seg=8, seg_num=0, max_way_points=None,
+                       max_samples=128, coef=True, allow_limit=False):
+        """The first half of planExploreTraj per problem: ways is a list of [k, 3] way-point arrays (what goal_paths
+        returns as "way"), vels / accs [n, 3].  Returns a dict: status [n] (WPTRAJ_*; -1: more samples than max_samples),
+        duration, length, seg_num, dt, n_samples [n], samples (list of [k, 3] arrays, at most max_samples each), derivs
+        [n, 4, 3] (start vel, end vel, start acc, end acc), and with coef: seg_times (list of [S]) and coef (list of
+        [S, 3, 6]); limit (a sample count exceeded max_samples).  FUELMI_ELIMIT raises FuelmiError unless allow_limit."""
+        n_way, way, vel, acc, c = _pack_waypoints(ways, vels, accs, max_vel, ctrl_pt_dist, min_seg, seg_num,
+                                                  max_way_points, max_samples)
+        n, maxw, maxs = len(n_way), c.max_way_points, max(c.max_samples, 0)
+        status = np.zeros(n, dtype=np.int32)
+        segs = np.zeros(n, dtype=np.int32)
+        ns = np.zeros(n, dtype=np.int32)
+        duration, length, dt = np.zeros(n), np.zeros(n), np.zeros(n)
+        samples = np.zeros((n, maxs, 3))
+        derivs = np.zeros((n, 4, 3))
+        tim = np.zeros((n, max(maxw - 1, 0))) if coef else None
+        cf = np.zeros((n, max(maxw - 1, 0), 3, 6)) if coef else None
+        rc = self.L.fuelmi_map_waypoint_trajs(self.h, C.byref(c), n, _ip(n_way), _dp(way), _dp(vel), _dp(acc), _ip(status),
+                                              _dp(duration), _dp(length), _ip(segs), _dp(dt), _ip(ns), _dp(samples),
+                                              _dp(derivs), _dp(tim), _dp(cf))
+        if not (allow_limit and rc == -5):
+            check(rc)
+        out = {"status": status, "duration": duration, "length": length, "seg_num": segs, "dt": dt, "n_samples": ns,
+               "derivs": derivs, "limit": rc == -5, "samples": [samples[b, :min(ns[b], maxs)].copy() for b in range(n)]}
+        if coef:
+            live = [max(int(n_way[b]) - 1, 0) if status[b] in (0, -1) else 0 for b in range(n)]
+            out["seg_times"] = [tim[b, :live[b]].copy() for b in range(n)]
+            out["coef"] = [cf[b, :live[b]].copy() for b in range(n)]
+        return out
+
+    @staticmethod
+    def waypoint_traj_plan(max_way_points):
+        """(lanes per problem, LDS bytes, largest max_way_points accepted) of the way-point kernel; host only"""
+        out = (C.c_int * 3)()
+        check(lib().fuelmi_wptraj_plan(C.byref(WptrajCfg(2.0, 0.45, 8, 0, int(max_way_points), 1)), out))
+        return tuple(out)
 
     # --- measurement ---
     def timerBegin(self):
@@ -883,6 +940,23 @@ class BsplineDeviceProblem:
                 or derivs.shape != (c.n_traj, 4, 3):
             raise ValueError("loadSamples: ts [C], points [C][K][3], derivs [C][4][3]")
         check(self.L.fuelmi_bspline_dev_load_samples(self.h, points.shape[1], _dp(ts), _dp(points), _dp(derivs)))
+
+    def load_waypoints(self, ways, vels, accs, max_vel=2.0, ctrl_pt_dist=0.45, min_seg=8, max_way_points=None,
+                       allow_limit=False):
+        """way-points -> min-jerk samples -> loadSamples' fit, without leaving the device (fuelmi_bspline_dev_load_waypoints):
+        one problem per candidate, seg_num forced to point_num - bspline_degree.  Returns (status [C], duration [C]); a
+        candidate whose status is not 0 keeps its state."""
+        c = self.problem.c
+        if len(ways) != c.n_traj:
+            raise ValueError("load_waypoints: one list of way-points per candidate")
+        n_way, way, vel, acc, wc = _pack_waypoints(ways, vels, accs, max_vel, ctrl_pt_dist, min_seg, 0, max_way_points, 1)
+        status = np.zeros(c.n_traj, dtype=np.int32)
+        duration = np.zeros(c.n_traj)
+        rc = self.L.fuelmi_bspline_dev_load_waypoints(self.h, C.byref(wc), _ip(n_way), _dp(way), _dp(vel), _dp(acc),
+                                                      _ip(status), _dp(duration))
+        if not (allow_limit and rc == -5):
+            check(rc)
+        return status, duration
 
     def close(self):
         if getattr(self, "h", None):

@@ -678,6 +678,81 @@ int fuelmi_bspline_dev_load_samples(fuelmi_bspline_dev* b, int n_points, const d
                                     const double* derivs);
 
 /* ------------------------------------------------------------------------------------------
+ * Min-jerk initial trajectory through way-points: the first half of FastPlannerManager::planExploreTraj
+ * (plan_manage/src/planner_manager.cpp:266-297) for n_prob independent problems (way-points, start velocity, start
+ * acceleration) in one call.  Per problem, with n_way points and S = n_way - 1 segments:
+ *   1. times[k] = |p[k+1] - p[k]| / (max_vel * 0.5), the norm sqrt(x x + y y + z z) summed left to right; duration =
+ *      the left-to-right sum of times (getTotalTime).
+ *   2. PolynomialTraj::waypointsTraj (poly_traj/src/polynomial_traj.cpp:5-175) with end velocity = end acceleration
+ *      = 0: the min-jerk quintic per segment and axis, coef[k][axis][i] the factor of t^i.  The 6S x 6S matrices are
+ *      not formed: their blocks are known in closed form and the free derivatives solve a symmetric banded system
+ *      (DESIGN.md section 10); coefficients agree with the dense inverses to those inverses' own rounding.
+ *   3. length = getLength, literally: samples at the ACCUMULATED eval_t (eval_t = 0; while (eval_t < duration)
+ *      { ...; eval_t += 0.01; }), norms of consecutive samples (summed by a fixed tree, not left to right).
+ *      evaluate(t, k) looks its segment up as `while (times[idx] + 1e-4 < ts) ts -= times[idx++]`, idx clamped to the
+ *      last segment (the reference reads past the end there).
+ *   4. seg_num = max(min_seg, int(min(length / ctrl_pt_dist, FUELMI_WPTRAJ_MAX_SEG))) (the reference's int() is
+ *      undefined past 2^31), or cfg.seg_num when that is > 0; dt = duration / seg_num.
+ *   5. samples at the accumulated ts (for (ts = 0; ts <= duration + 1e-4; ts += dt)): n_samples of them, seg_num + 1
+ *      whenever dt > 1e-4 (the loop stops at FUELMI_WPTRAJ_MAX_SEG + 2 samples at the latest); derivs = velocity at
+ *      0 and at duration, then acceleration at 0 and at duration: fuelmi_bspline_parameterize's `derivs`.
+ * Everything is f64 + - * / sqrt in a fixed order: a result does not depend on the problem's place in the batch.
+ * Per-problem status:
+ *   FUELMI_WPTRAJ_OK.
+ *   FUELMI_WPTRAJ_FEW         n_way < 3 (for two points the reference writes outside its selection matrix; the
+ *                             manager never passes two, shortenPath inserts a mid-point).
+ *   FUELMI_WPTRAJ_DEGENERATE  a segment time that is 0 or not finite (a singular mapping matrix in the reference).
+ *   -1                        more samples than max_samples.
+ * FEW and DEGENERATE: n_samples 0 and every other output of the problem written as 0; the call is still FUELMI_OK.
+ * -1: n_samples holds the full count, the first max_samples samples are written, everything else is complete, the
+ * other problems are complete, and the call returns FUELMI_ELIMIT.
+ * Checked on the host before anything is launched (FUELMI_EINVAL): way-points (the first n_way of a problem), vel_xyz
+ * and acc_xyz finite with |coordinate| < 1e7; max_vel and ctrl_pt_dist finite and > 0; 1 <= min_seg and 0 <= seg_num
+ * <= FUELMI_WPTRAJ_MAX_SEG; max_samples >= 1; 0 <= n_way[i] <= max_way_points.  FUELMI_ELIMIT, also before any launch:
+ * max_way_points > FUELMI_WPTRAJ_MAX_WAY, or a problem whose duration exceeds FUELMI_WPTRAJ_MAX_DURATION seconds
+ * (10^6 length samples).  n_prob = 0 is FUELMI_OK.
+ * fuelmi_map_waypoint_trajs runs on a query slot of the map like fuelmi_bspline_parameterize: host arrays in, host
+ * arrays out, synchronous, re-entrant.  way_xyz [n_prob][max_way_points][3] is fuelmi_map_goal_paths' way_xyz.
+ * ---------------------------------------------------------------------------------------- */
+#define FUELMI_WPTRAJ_OK 0
+#define FUELMI_WPTRAJ_FEW 1
+#define FUELMI_WPTRAJ_DEGENERATE 2
+#define FUELMI_WPTRAJ_MAX_WAY 256         /* largest max_way_points */
+#define FUELMI_WPTRAJ_MAX_SEG (1 << 20)   /* largest seg_num */
+#define FUELMI_WPTRAJ_MAX_DURATION 1.0e4  /* seconds */
+typedef struct {
+  double max_vel;       /* pp_.max_vel_ */
+  double ctrl_pt_dist;  /* pp_.ctrl_pt_dist */
+  int min_seg;          /* 8 */
+  int seg_num;          /* 0: the reference's rule; > 0: forced (every problem gets seg_num + 1 samples) */
+  int max_way_points;   /* stride of way_xyz; same layout as fuelmi_map_goal_paths' output */
+  int max_samples;      /* stride / cap of samples */
+} fuelmi_wptraj_cfg;
+/* Out, per problem: status, duration, length, seg_num, dt, n_samples, samples [n_prob][max_samples][3] (entries past
+ * n_samples unspecified), derivs [n_prob][4][3]; seg_times [n_prob][max_way_points-1] and coef
+ * [n_prob][max_way_points-1][3][6] may each be NULL (entries past n_way - 1 unspecified). */
+int fuelmi_map_waypoint_trajs(fuelmi_map* m, const fuelmi_wptraj_cfg* cfg, int n_prob, const int* n_way,
+                              const double* way_xyz, const double* vel_xyz, const double* acc_xyz, int* status,
+                              double* duration, double* length, int* seg_num, double* dt, int* n_samples,
+                              double* samples, double* derivs, double* seg_times, double* coef);
+/* The device chain way-points -> fitted batch: refills the batch `b` exactly as fuelmi_bspline_dev_load_samples would
+ * from the same problems' samples (ts = dt), but the samples never exist on the host: the kernel above writes
+ * ts | points | derivs into the batch's staging and the spline fit follows on the map's stream.  One problem per
+ * candidate (C = the batch's n_traj; n_way [C], way_xyz [C][max_way_points][3], vel_xyz, acc_xyz [C][3]).  seg_num is
+ * forced to point_num - bspline_degree so that every candidate fits the batch: cfg->seg_num must be 0 or equal to
+ * that; cfg->max_samples is ignored (it is seg_num + 1).  A candidate whose status is not FUELMI_WPTRAJ_OK keeps the
+ * state it had in the batch.  status [C]; duration [C] or NULL.  Same host checks and return values as above.
+ * Everything is queued on the map's stream without waiting, then status (and duration) are copied back and the call
+ * waits for the map's stream once, behind the fit: when it returns the batch is loaded, and the next _dev_eval /
+ * _dev_optimize uses it. */
+int fuelmi_bspline_dev_load_waypoints(fuelmi_bspline_dev* b, const fuelmi_wptraj_cfg* cfg, const int* n_way,
+                                      const double* way_xyz, const double* vel_xyz, const double* acc_xyz, int* status,
+                                      double* duration);
+/* what the kernel needs for cfg->max_way_points (host only, no device needed): out3 = {lanes per problem, dynamic LDS
+ * bytes, largest max_way_points accepted}.  FUELMI_ELIMIT past FUELMI_WPTRAJ_MAX_WAY, like both calls above. */
+int fuelmi_wptraj_plan(const fuelmi_wptraj_cfg* cfg, int out3[3]);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): HIP events recorded on the map's own stream.
  * ---------------------------------------------------------------------------------------- */
 enum {
