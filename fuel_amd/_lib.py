@@ -112,6 +112,18 @@ class WptrajCfg(C.Structure):
 
 WPTRAJ_OK, WPTRAJ_FEW, WPTRAJ_DEGENERATE = 0, 1, 2
 WPTRAJ_MAX_WAY, WPTRAJ_MAX_SEG, WPTRAJ_MAX_DURATION = 256, 1 << 20, 1.0e4
+
+
+class YawCfg(C.Structure):
+    """fuelmi_yaw_cfg: planYawExplore's / planYaw's constants and the strides of the control-point / way-point arrays."""
+    _fields_ = [("mode", C.c_int), ("pos_degree", C.c_int), ("max_ctrl", C.c_int), ("max_seg", C.c_int),
+                ("seg_num", C.c_int), ("lookfwd", C.c_int), ("relax_time", C.c_double), ("forward_t", C.c_double),
+                ("dt_target", C.c_double), ("end_back", C.c_double)]
+
+
+YAW_EXPLORE, YAW_FOLLOW = 0, 1
+YAW_OK, YAW_DEGENERATE = 0, 1
+YAW_MAX_SEG, YAW_MAX_CTRL = 256, 1024
 REFINE_LAST_ARGMIN = 1
 REFINE_MAX_LAYERS, REFINE_MAX_NODES = 64, 256
 
@@ -235,6 +247,11 @@ SYMBOLS = {
     "fuelmi_map_waypoint_trajs": (C.c_int, [_P, C.POINTER(WptrajCfg), C.c_int, _ip, _dp, _dp, _dp, _ip, _dp, _dp, _ip, _dp,
                                             _ip, _dp, _dp, _dp, _dp]),
     "fuelmi_wptraj_plan": (C.c_int, [C.POINTER(WptrajCfg), _ip]),
+    "fuelmi_map_plan_yaws": (C.c_int, [_P, C.POINTER(BsplineCfg), C.POINTER(YawCfg), C.c_int, _ip, _dp, _dp, _dp, _dp, _ip,
+                                       _dp, _ip, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp]),
+    "fuelmi_bspline_dev_plan_yaws": (C.c_int, [_P, C.POINTER(YawCfg), _dp, _dp, _ip, _dp, _ip, _dp, _dp, _ip, _dp, _dp,
+                                               _dp, _dp, _dp]),
+    "fuelmi_yaw_plan": (C.c_int, [C.POINTER(YawCfg), _ip]),
     "fuelmi_tsp_create": (C.c_int, [C.c_int, C.POINTER(TspCfg), _PP]),
     "fuelmi_tsp_destroy": (None, [_P]),
     "fuelmi_tsp_solve": (C.c_int, [_P, C.c_int, _ip, C.POINTER(C.c_int32), _ip, C.POINTER(C.c_int64), _ip]),

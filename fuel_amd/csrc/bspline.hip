@@ -46,6 +46,9 @@ struct fuelmi_bspline_dev {
   hipEvent_t ev_out[2] = {nullptr, nullptr};
   double* fit_in = nullptr;  // fuelmi_bspline_dev_load_samples staging: ts | points | derivs
   size_t fit_cap = 0;
+  bool opt_valid = false;    // opt_x holds the solve of what the batch holds now (a reload clears it)
+  unsigned char* yaw_dev = nullptr;  // fuelmi_bspline_dev_plan_yaws: start | end | results (grow-only)
+  size_t yaw_cap = 0;
 };
 
 // 64-lane sum on the DPP data path (no LDS crossbar round trips): quads, half rows, rows, then the two
@@ -1240,6 +1243,7 @@ extern "C" int fuelmi_bspline_dev_optimize_timed(fuelmi_bspline_dev* b, int max_
   HIPCHK(hipMemcpyAsync(ev.data(), b->opt_evals, C * sizeof(int), hipMemcpyDeviceToHost, m->stream));
   HIPCHK(hipStreamSynchronize(m->stream));
   if (evals_out) memcpy(evals_out, ev.data(), C * sizeof(int));
+  b->opt_valid = true;
   return FUELMI_OK;
 }
 
@@ -1454,6 +1458,7 @@ extern "C" int fuelmi_bspline_dev_load_samples(fuelmi_bspline_dev* b, int n_poin
   BsplineArgs& A = b->a;
   const int degree = A.cfg.bspline_degree;
   ARGCHK(A.dim == 3 && degree >= 3 && degree <= 5 && n_points >= 2 && n_points + degree - 1 == A.N);
+  b->opt_valid = false;
   fuelmi_map* m = b->map;
   HIPCHK(hipSetDevice(m->device));
   const size_t C = (size_t)A.C, K = (size_t)n_points;
@@ -1504,6 +1509,7 @@ extern "C" int fuelmi_bspline_dev_load_waypoints(fuelmi_bspline_dev* b, const fu
   }
   fuelmi_map* m = b->map;
   ARGCHK(m);
+  b->opt_valid = false;
   HIPCHK(hipSetDevice(m->device));
   const size_t C = (size_t)A.C, K = (size_t)n_points, maxw = (size_t)wc.max_way_points;
   auto pad = [](size_t x) { return (x + 15) & ~(size_t)15; };
@@ -1580,4 +1586,73 @@ extern "C" int fuelmi_bspline_dev_load_waypoints(fuelmi_bspline_dev* b, const fu
       return FUELMI_ELIMIT;
     }
   return FUELMI_OK;
+}
+
+// the yaw trajectories of the batch's optimised position splines (k_yaw_plan, yaw_plan.hip) read from the variables the
+// last solve left on the device; only the yaw results travel
+extern "C" int fuelmi_bspline_dev_plan_yaws(fuelmi_bspline_dev* b, const fuelmi_yaw_cfg* cfg, const double* start_yaw,
+                                            const double* end_yaw, int* status, double* duration, int* seg_num,
+                                            double* dt_yaw, double* yaw_ctrl, int* n_waypt, double* waypts,
+                                            double* end_yaw_out, double* cost, double* yawdot_ctrl,
+                                            double* yawddot_ctrl) {
+  ARGCHK(b && cfg);
+  const BsplineArgs& A = b->a;
+  ARGCHK(A.dim == 3 && b->opt_valid && b->opt_x);
+  ARGCHK(cfg->pos_degree == A.cfg.bspline_degree);
+  fuelmi_yaw_cfg yc = *cfg;
+  yc.max_ctrl = A.N;
+  {
+    const int rc = yaw_check(&A.cfg, &yc, A.C, nullptr, nullptr, nullptr, start_yaw, end_yaw);
+    if (rc) return rc;
+  }
+  ARGCHK(A.N >= yc.pos_degree + 1);
+  ARGCHK(status && duration && seg_num && dt_yaw && yaw_ctrl && n_waypt && waypts && end_yaw_out && cost);
+  fuelmi_map* m = b->map;
+  ARGCHK(m);
+  HIPCHK(hipSetDevice(m->device));
+  const size_t C = (size_t)A.C;
+  auto pad = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  const size_t b_s3 = pad(C * 3 * sizeof(double)), b_dbl = pad(C * sizeof(double));
+  YawArgs Y;
+  memset(&Y, 0, sizeof(Y));
+  const size_t b_out = yaw_out_bytes(&yc, A.C, Y, nullptr, yawdot_ctrl != nullptr, yawddot_ctrl != nullptr);
+  if (b_s3 + b_dbl + b_out > b->yaw_cap) {
+    void* d = nullptr;
+    HIPCHK(hipMalloc(&d, b_s3 + b_dbl + b_out));
+    b->allocs.push_back(d);
+    b->yaw_dev = static_cast<unsigned char*>(d);
+    b->yaw_cap = b_s3 + b_dbl + b_out;
+  }
+  hipStream_t st = m->stream;
+  double* d_start = reinterpret_cast<double*>(b->yaw_dev);
+  double* d_end = reinterpret_cast<double*>(b->yaw_dev + b_s3);
+  unsigned char* d_out = b->yaw_dev + b_s3 + b_dbl;
+  HIPCHK(hipMemcpyAsync(d_start, start_yaw, C * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  if (end_yaw)
+    HIPCHK(hipMemcpyAsync(d_end, end_yaw, C * sizeof(double), hipMemcpyHostToDevice, st));
+  else
+    HIPCHK(hipMemsetAsync(d_end, 0, C * sizeof(double), st));
+  Y.cfg = yc;
+  Y.ld_smooth = A.cfg.ld_smooth, Y.ld_start = A.cfg.ld_start, Y.ld_end = A.cfg.ld_end, Y.ld_waypt = A.cfg.ld_waypt;
+  Y.n_prob = A.C;
+  Y.n_ctrl = nullptr, Y.n_ctrl_all = A.N;
+  Y.pos = b->opt_x, Y.pos_stride = (size_t)A.nvar;
+  if (A.cost_function & FUELMI_COST_MINTIME)
+    Y.knot = b->opt_x + (A.nvar - 1), Y.knot_stride = (size_t)A.nvar;
+  else
+    Y.knot = A.knot_span, Y.knot_stride = 1;
+  Y.start_yaw = d_start, Y.end_yaw = d_end;
+  yaw_out_bytes(&yc, A.C, Y, d_out, yawdot_ctrl != nullptr, yawddot_ctrl != nullptr);
+  {
+    StageScope sc(m, FUELMI_K_BSPLINE);
+    const int rc = yaw_launch(st, Y);
+    if (rc) return rc;
+  }
+  std::vector<unsigned char> host(b_out);
+  HIPCHK(hipMemcpyAsync(host.data(), d_out, b_out, hipMemcpyDeviceToHost, st));
+  HIPCHK(stream_wait(st));
+  YawArgs H = Y;
+  yaw_out_bytes(&yc, A.C, H, host.data(), yawdot_ctrl != nullptr, yawddot_ctrl != nullptr);
+  return yaw_copy_out(&yc, A.C, H, status, duration, seg_num, dt_yaw, yaw_ctrl, n_waypt, waypts, end_yaw_out, cost,
+                      yawdot_ctrl, yawddot_ctrl);
 }

@@ -528,6 +528,41 @@ struct WpTrajArgs {
 int wptraj_check(const fuelmi_wptraj_cfg* cfg, int n_prob, const int* n_way, const double* way_xyz,
                  const double* vel_xyz, const double* acc_xyz);
 int wptraj_launch(hipStream_t st, const WpTrajArgs& W);
+// k_yaw_plan (yaw_plan.hip): one problem per wave; every pointer addresses memory the device can reach
+struct YawArgs {
+  fuelmi_yaw_cfg cfg;
+  double ld_smooth, ld_start, ld_end, ld_waypt;
+  int n_prob;
+  const int* n_ctrl;        // [n], or null: every problem has n_ctrl_all control points
+  int n_ctrl_all;
+  const double* pos;        // problem b: [n_ctrl][3] at pos + b * pos_stride
+  size_t pos_stride;
+  const double* knot;       // problem b: knot[b * knot_stride]
+  size_t knot_stride;
+  const double* start_yaw;  // [n][3]
+  const double* end_yaw;    // [n] (EXPLORE)
+  int* status;
+  int* seg_num;
+  int* n_waypt;
+  double* duration;
+  double* dt_yaw;
+  double* end_yaw_out;
+  double* cost;
+  double* yaw_ctrl;         // [n][max_seg + 3]
+  double* waypts;           // [n][max_seg]
+  double* yawdot_ctrl;      // [n][max_seg + 2] or null
+  double* yawddot_ctrl;     // [n][max_seg + 1] or null
+};
+// the host checks of fuelmi_map_plan_yaws / fuelmi_bspline_dev_plan_yaws (n_ctrl null: a device batch, whose control
+// points and knot spans the host does not see); the result block's layout (base null: only its size); the launch on
+// stream st; the result block -> the caller's arrays (FUELMI_ELIMIT when a problem's status is -1)
+int yaw_check(const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob, const int* n_ctrl,
+              const double* pos_ctrl, const double* knot_span, const double* start_yaw, const double* end_yaw);
+size_t yaw_out_bytes(const fuelmi_yaw_cfg* cfg, int n_prob, YawArgs& Y, unsigned char* base, bool dot, bool ddot);
+int yaw_launch(hipStream_t st, const YawArgs& Y);
+int yaw_copy_out(const fuelmi_yaw_cfg* cfg, int n_prob, const YawArgs& H, int* status, double* duration, int* seg_num,
+                 double* dt_yaw, double* yaw_ctrl, int* n_waypt, double* waypts, double* end_yaw_out, double* cost,
+                 double* yawdot_ctrl, double* yawddot_ctrl);
 // device results of one path_cost_enqueue, in the map's path scratch: length / kind / path_len per pair, paths
 // [n][maxp][3] (nullptr when maxp is 0), and the device copy of p2_xyz
 struct PathRun {

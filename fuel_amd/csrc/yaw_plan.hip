@@ -1,0 +1,572 @@
+// yaw_plan.hip -- the yaw trajectory of a position spline: FastPlannerManager::planYawExplore
+// (plan_manage/src/planner_manager.cpp:774-865) and ::planYaw (:695-772) for a batch of problems (position control
+// points, knot span, start yaw state, end yaw): the knots as setUniformBspline accumulates them, the look-ahead
+// way-points (two evaluateDeBoorT and one atan2 each), calcNextYaw's unwrap chain, the initial control points, pt_dist_
+// and the minimiser of the optimiser's objective.
+//
+// With SMOOTHNESS | START | END | WAYPOINTS, dimension 1, no bounds and pt_dist_ fixed, that objective is a sum of
+// squares of linear forms of at most four neighbouring control points:
+//     ld_smooth (J . q[i..i+3] / pt_dist)^2,  J = (-1, 3, -3, 1)                       i = 0 .. N-4
+//     10 ld_start (P . q[0..2] - s0)^2 + ld_start (V . q[0..2] - s1)^2 + ld_start (A . q[0..2] - s2)^2
+//     ld_end ((P . q[N-3..] - e)^2 + (V . q[N-3..])^2 [+ (A . q[N-3..])^2 with three end entries])
+//     ld_waypt (P . q[i..i+2] - w_i)^2                                                 way-point indices i
+//     P = (1, 4, 1) / 6,  V = (-1, 0, 1) / (2 dt),  A = (1, -2, 1) / dt^2
+// so the minimiser solves H q = g with H = sum c a a^T symmetric positive definite of half-bandwidth 3 (the jerk rows
+// leave quadratics free, the three start rows pin them).  One lane per row gathers its four diagonals and its right-hand
+// side, lane 0 factors by Cholesky and substitutes: the reference's NLopt run iterates towards this point.
+//
+// One wave of YP_NT lanes per problem, one lane per way-point (looped past YP_NT), all f64, -ffp-contract=off.  The
+// knots are staged in LDS by the accumulated additions; the unwrap chain and the factorisation are serial in lane 0
+// (N <= 259).  A result does not depend on the problem's place in the batch.
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "fuelmi_internal.h"
+
+namespace {
+
+constexpr int YP_NT = 64;
+constexpr double YP_PI = 3.14159265358979323846;  // M_PI
+
+__host__ __device__ inline int yp_knots(int max_ctrl, int max_seg) {  // position knots n + p + 1 <= max_ctrl + 6; yaw knots N + p + 1
+  return max_ctrl + 6 > max_seg + 9 ? max_ctrl + 6 : max_seg + 9;
+}
+
+// FastPlannerManager::calcNextYaw (:867-885)
+__device__ __forceinline__ double yp_next_yaw(double last_yaw, double yaw) {
+  double round_last = last_yaw;
+  while (round_last < -YP_PI) round_last += 2 * YP_PI;
+  while (round_last > YP_PI) round_last -= 2 * YP_PI;
+  const double diff = yaw - round_last;
+  if (fabs(diff) <= YP_PI) return last_yaw + diff;
+  if (diff > YP_PI) return last_yaw + diff - 2 * YP_PI;
+  if (diff < -YP_PI) return last_yaw + diff + 2 * YP_PI;
+  return yaw;  // diff is not a number: the reference leaves yaw as it is
+}
+
+// NonUniformBspline::evaluateDeBoorT (non_uniform_bspline.cpp:51-75) of a spline of degree P with n control points and
+// the knots u[0 .. n + P]; ctrl(i, d) fetches control point i
+template <int P, class F>
+__device__ __forceinline__ void yp_deboor(const double* u, int n, double t, F ctrl, double out[3]) {
+  const double lo = u[P], v = t + u[P], hi = u[n];
+  double ub = lo < v ? v : lo;  // min(max(u_(p_), u), u_(m_ - p_))
+  ub = hi < ub ? hi : ub;
+  int k = P;
+  while (k < n - 1 && u[k + 1] < ub) ++k;  // (k < n - 1 holds by the clamp; it keeps a bad spline inside its arrays)
+  double d[P + 1][3];
+#pragma unroll
+  for (int i = 0; i <= P; ++i) ctrl(k - P + i, d[i]);
+#pragma unroll
+  for (int r = 1; r <= P; ++r)
+#pragma unroll
+    for (int i = P; i >= r; --i) {
+      const double alpha = (ub - u[i + k - P]) / (u[i + 1 + k - r] - u[i + k - P]);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) d[i][c] = (1 - alpha) * d[i - 1][c] + alpha * d[i][c];
+    }
+  out[0] = d[P][0], out[1] = d[P][1], out[2] = d[P][2];
+}
+
+// the position spline at time t
+__device__ __forceinline__ void yp_pos(const double* u, int p, int n, const double* C, double t, double out[3]) {
+  auto ctrl = [C](int i, double d[3]) { d[0] = C[3 * i], d[1] = C[3 * i + 1], d[2] = C[3 * i + 2]; };
+  if (p == 3)
+    yp_deboor<3>(u, n, t, ctrl, out);
+  else if (p == 4)
+    yp_deboor<4>(u, n, t, ctrl, out);
+  else
+    yp_deboor<5>(u, n, t, ctrl, out);
+}
+
+// its derivative (getDerivative :77-106) at time t: control points p (P[i+1] - P[i]) / (u[i+p+1] - u[i+1]), the knots
+// without the first and the last, degree p - 1
+__device__ __forceinline__ void yp_vel(const double* u, int p, int n, const double* C, double t, double out[3]) {
+  auto ctrl = [C, u, p](int i, double d[3]) {
+    const double den = u[i + p + 1] - u[i + 1];
+    for (int c = 0; c < 3; ++c) d[c] = (double)p * (C[3 * (i + 1) + c] - C[3 * i + c]) / den;
+  };
+  if (p == 3)
+    yp_deboor<2>(u + 1, n - 1, t, ctrl, out);
+  else if (p == 4)
+    yp_deboor<3>(u + 1, n - 1, t, ctrl, out);
+  else
+    yp_deboor<4>(u + 1, n - 1, t, ctrl, out);
+}
+
+__device__ __forceinline__ double yp_J(int k) { return k == 0 ? -1.0 : k == 1 ? 3.0 : k == 2 ? -3.0 : 1.0; }
+__device__ __forceinline__ double yp_P(int k) { return k == 1 ? 4.0 / 6.0 : 1.0 / 6.0; }
+__device__ __forceinline__ double yp_V(int k, double dt) { return (k == 0 ? -1.0 : k == 1 ? 0.0 : 1.0) / (2 * dt); }
+__device__ __forceinline__ double yp_A(int k, double dt) { return (k == 1 ? -2.0 : 1.0) / (dt * dt); }
+
+// everything a problem reports.  N = 0: no yaw spline (every array of the problem is written as 0)
+__device__ void yp_write(const YawArgs& Y, int b, int tid, int status, double duration, int seg, double dt_yaw, int N,
+                         const double* q, int nw, const double* wp, double e, double cost, const double* uy, int py) {
+  const int maxs = Y.cfg.max_seg;
+  if (tid == 0) {
+    Y.status[b] = status;
+    Y.duration[b] = duration;
+    Y.seg_num[b] = seg;
+    Y.dt_yaw[b] = dt_yaw;
+    Y.n_waypt[b] = nw;
+    Y.end_yaw_out[b] = e;
+    Y.cost[b] = cost;
+  }
+  double* oc = Y.yaw_ctrl + (size_t)b * (maxs + 3);
+  double* ow = Y.waypts + (size_t)b * maxs;
+  for (int i = tid; i < maxs + 3; i += YP_NT) oc[i] = i < N ? q[i] : 0.0;
+  for (int i = tid; i < maxs; i += YP_NT) ow[i] = i < nw ? wp[i] : 0.0;
+  // getDerivativeControlPoints (:77-86) once and twice, on the knots of setUniformBspline(yaw, py, dt_yaw)
+  if (Y.yawdot_ctrl) {
+    double* o = Y.yawdot_ctrl + (size_t)b * (maxs + 2);
+    for (int i = tid; i < maxs + 2; i += YP_NT)
+      o[i] = i < N - 1 ? (double)py * (q[i + 1] - q[i]) / (uy[i + py + 1] - uy[i + 1]) : 0.0;
+  }
+  if (Y.yawddot_ctrl) {
+    double* o = Y.yawddot_ctrl + (size_t)b * (maxs + 1);
+    for (int i = tid; i < maxs + 1; i += YP_NT) {
+      double v = 0.0;
+      if (i < N - 2) {
+        const double d0 = (double)py * (q[i + 1] - q[i]) / (uy[i + py + 1] - uy[i + 1]);
+        const double d1 = (double)py * (q[i + 2] - q[i + 1]) / (uy[i + py + 2] - uy[i + 2]);
+        v = (double)(py - 1) * (d1 - d0) / (uy[i + py + 1] - uy[i + 2]);
+      }
+      o[i] = v;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(YP_NT) k_yaw_plan(YawArgs Y) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const int maxs = Y.cfg.max_seg, maxn = maxs + 3, nu = yp_knots(Y.cfg.max_ctrl, maxs);
+  double* u = reinterpret_cast<double*>(smem_raw);  // [nu]       position knots, later the yaw spline's
+  double* wp = u + nu;                              // [maxs]     atan2 per way-point, then the unwrapped way-points
+  double* band = wp + maxs;                         // [maxn][4]  H(r, r - d) at [r][d], then its Cholesky factor
+  double* g = band + 4 * maxn;                      // [maxn]     right-hand side, then the minimiser
+  double* q0 = g + maxn;                            // [maxn]     initial control points
+  double* sh = q0 + maxn;                           // [8]
+  int* ok = reinterpret_cast<int*>(sh + 8);         // [maxs]     the way-point's |pd| > 1e-6
+
+  const bool follow = Y.cfg.mode == FUELMI_YAW_FOLLOW;
+  const int p = Y.cfg.pos_degree;
+  const int n = Y.n_ctrl ? Y.n_ctrl[b] : Y.n_ctrl_all;
+  const double dt = Y.knot[(size_t)b * Y.knot_stride];
+  const double* C = Y.pos + (size_t)b * Y.pos_stride;
+  // (the host route refuses these before any launch; the variables of a device batch are not seen by the host)
+  if (!(dt > 0.0) || !isfinite(dt) || n < p + 1 || n > Y.cfg.max_ctrl) {
+    yp_write(Y, b, tid, FUELMI_YAW_DEGENERATE, 0.0, 0, 0.0, 0, nullptr, 0, nullptr, 0.0, 0.0, nullptr, 3);
+    return;
+  }
+
+  // 1. knots (setUniformBspline :25-31), duration = getTimeSum
+  if (tid == 0) {
+    for (int i = 0; i <= p; ++i) u[i] = (double)(i - p) * dt;
+    double acc = u[p];
+    for (int i = p + 1; i <= n + p; ++i) {
+      acc = acc + dt;
+      u[i] = acc;
+    }
+  }
+  __syncthreads();
+  const double duration = u[n] - u[p];
+
+  // 2. seg_num, dt_yaw, the way-points' range
+  int seg = Y.cfg.seg_num;
+  if (follow) {
+    const double qd = ceil(duration / Y.cfg.dt_target);
+    if (!(qd >= 1.0)) {
+      yp_write(Y, b, tid, FUELMI_YAW_DEGENERATE, duration, 0, 0.0, 0, nullptr, 0, nullptr, 0.0, 0.0, nullptr, 3);
+      return;
+    }
+    if (!(qd <= (double)maxs)) {
+      seg = qd < 1073741824.0 ? (int)qd : 1073741824;
+      yp_write(Y, b, tid, -1, duration, seg, duration / (double)seg, 0, nullptr, 0, nullptr, 0.0, 0.0, nullptr, 3);
+      return;
+    }
+    seg = (int)qd;
+  }
+  const double dt_yaw = duration / (double)seg;
+  const int N = seg + 3;
+  int i0 = 0, nw = seg;
+  if (!follow) {
+    i0 = 1, nw = 0;
+    if (Y.cfg.lookfwd) {
+      double rq = Y.cfg.relax_time / dt_yaw;
+      if (!(rq < (double)seg)) rq = (double)seg;
+      const int relax_num = (int)rq;
+      nw = seg - relax_num - 1;
+      if (nw < 0) nw = 0;
+    }
+  }
+
+  // 3. one lane per way-point: pd = pos(tf) - pos(tc), its norm, atan2
+  for (int j = tid; j < nw; j += YP_NT) {
+    const double tc = (double)(i0 + j) * dt_yaw;
+    const double ts = tc + Y.cfg.forward_t;
+    const double tf = ts < duration ? ts : duration;
+    double pc[3], pf[3];
+    yp_pos(u, p, n, C, tc, pc);
+    yp_pos(u, p, n, C, tf, pf);
+    const double x = pf[0] - pc[0], y = pf[1] - pc[1], z = pf[2] - pc[2];
+    const bool far = sqrt(x * x + y * y + z * z) > 1e-6;
+    ok[j] = far ? 1 : 0;
+    wp[j] = far ? atan2(y, x) : 0.0;
+  }
+  __syncthreads();
+
+  // 4. lane 0: the unwrap chain, the end yaw, the initial control points, pt_dist_
+  if (tid == 0) {
+    double s0 = Y.start_yaw[3 * b];
+    const double s1 = Y.start_yaw[3 * b + 1], s2 = Y.start_yaw[3 * b + 2];
+    if (!follow) {
+      while (s0 < -YP_PI) s0 += 2 * YP_PI;
+      while (s0 > YP_PI) s0 -= 2 * YP_PI;
+    }
+    double last_yaw = s0;
+    for (int j = 0; j < nw; ++j) {
+      // a stalled way-point repeats its predecessor; the first one has none (the reference reads waypts.back() of an
+      // empty vector): it repeats last_yaw
+      const double w = ok[j] ? yp_next_yaw(last_yaw, wp[j]) : last_yaw;
+      wp[j] = w;
+      last_yaw = w;
+    }
+    double e;
+    if (follow) {
+      double v[3];
+      yp_vel(u, p, n, C, duration - Y.cfg.end_back, v);
+      e = atan2(v[1], v[0]);
+    } else {
+      e = Y.end_yaw[b];
+    }
+    e = yp_next_yaw(last_yaw, e);
+    for (int i = 0; i < N; ++i) q0[i] = 0.0;
+    const double m02 = (1 / 3.0) * dt_yaw * dt_yaw, m12 = -(1 / 6.0) * dt_yaw * dt_yaw;
+    q0[0] = 1.0 * s0 + (-dt_yaw) * s1 + m02 * s2;
+    q0[1] = 1.0 * s0 + 0.0 * s1 + m12 * s2;
+    q0[2] = 1.0 * s0 + dt_yaw * s1 + m02 * s2;
+    q0[seg] = 1.0 * e + (-dt_yaw) * 0.0 + m02 * 0.0;
+    q0[seg + 1] = 1.0 * e + 0.0 * 0.0 + m12 * 0.0;
+    q0[seg + 2] = 1.0 * e + dt_yaw * 0.0 + m02 * 0.0;
+    double pd = 0.0;
+    for (int i = 0; i + 1 < N; ++i) pd += fabs(q0[i + 1] - q0[i]);
+    pd /= (double)N;
+    sh[0] = s0, sh[1] = e, sh[2] = pd;
+    sh[3] = (pd == 0.0 || !isfinite(pd)) ? 1.0 : 0.0;
+  }
+  __syncthreads();
+  const double s0 = sh[0], s1 = Y.start_yaw[3 * b + 1], s2 = Y.start_yaw[3 * b + 2];
+  const double e = sh[1], pt_dist = sh[2];
+  bool degenerate = sh[3] != 0.0;
+  const bool end3 = follow;  // planYaw passes three end entries, planYawExplore two
+
+  // 5. one lane per row of the normal equations
+  if (!degenerate) {
+    const double cs = Y.ld_smooth, cp = 10.0 * Y.ld_start, cv = Y.ld_start, ce = Y.ld_end, cw = Y.ld_waypt;
+    for (int r = tid; r < N; r += YP_NT) {
+      double h[4] = {0.0, 0.0, 0.0, 0.0}, gr = 0.0;
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        const int c = r - d;
+        if (c < 0) continue;
+        double s = 0.0;
+        for (int i = max(0, r - 3); i <= min(c, N - 4); ++i) s += (yp_J(r - i) / pt_dist) * (yp_J(c - i) / pt_dist);
+        double hd = cs * s;
+        if (r <= 2)
+          hd += cp * (yp_P(r) * yp_P(c)) + cv * (yp_V(r, dt_yaw) * yp_V(c, dt_yaw)) +
+                cv * (yp_A(r, dt_yaw) * yp_A(c, dt_yaw));
+        if (c >= N - 3) {
+          const int rr = r - (N - 3), cc = c - (N - 3);
+          double t = yp_P(rr) * yp_P(cc) + yp_V(rr, dt_yaw) * yp_V(cc, dt_yaw);
+          if (end3) t += yp_A(rr, dt_yaw) * yp_A(cc, dt_yaw);
+          hd += ce * t;
+        }
+        double sw = 0.0;
+        for (int i = max(i0, r - 2); i <= min(c, i0 + nw - 1); ++i) sw += yp_P(r - i) * yp_P(c - i);
+        hd += cw * sw;
+        h[d] = hd;
+      }
+      if (r <= 2) gr += cp * (s0 * yp_P(r)) + cv * (s1 * yp_V(r, dt_yaw)) + cv * (s2 * yp_A(r, dt_yaw));
+      if (r >= N - 3) gr += ce * (e * yp_P(r - (N - 3)));
+      double sw = 0.0;
+      for (int i = max(i0, r - 2); i <= min(r, i0 + nw - 1); ++i) sw += wp[i - i0] * yp_P(r - i);
+      gr += cw * sw;
+#pragma unroll
+      for (int d = 0; d < 4; ++d) band[4 * r + d] = h[d];
+      g[r] = gr;
+    }
+    __syncthreads();
+
+    // 6. lane 0: banded Cholesky (the loops of k_waypoint_traj), both substitutions, the objective at the result
+    if (tid == 0) {
+      constexpr int hb = 3;
+      bool bad = false;
+      for (int j = 0; j < N && !bad; ++j) {
+        double s = band[4 * j];
+        for (int d = 1; d <= hb && d <= j; ++d) s -= band[4 * j + d] * band[4 * j + d];
+        if (!(s > 0.0) || !isfinite(s)) {
+          bad = true;
+          break;
+        }
+        const double ljj = sqrt(s);
+        band[4 * j] = ljj;
+        for (int i = j + 1; i <= j + hb && i < N; ++i) {
+          double t = band[4 * i + (i - j)];
+          for (int k = max(0, i - hb); k < j; ++k) t -= band[4 * i + (i - k)] * band[4 * j + (j - k)];
+          band[4 * i + (i - j)] = t / ljj;
+        }
+      }
+      double cost = 0.0;
+      if (!bad) {
+        for (int j = 0; j < N; ++j) {
+          double s = g[j];
+          for (int d = 1; d <= hb && d <= j; ++d) s -= band[4 * j + d] * g[j - d];
+          g[j] = s / band[4 * j];
+        }
+        for (int j = N - 1; j >= 0; --j) {
+          double s = g[j];
+          for (int d = 1; d <= hb; ++d)
+            if (j + d < N) s -= band[4 * (j + d) + d] * g[j + d];
+          g[j] = s / band[4 * j];
+        }
+        // combineCost (bspline_optimizer.cpp:571-630) in the reference's order
+        double fs = 0.0;
+        for (int i = 0; i + 3 < N; ++i) {
+          const double ji = (g[i + 3] - 3 * g[i + 2] + 3 * g[i + 1] - g[i]) / pt_dist;
+          fs += ji * ji;
+        }
+        double f0 = 0.0, dq;
+        dq = 1 / 6.0 * (g[0] + 4 * g[1] + g[2]) - s0;
+        f0 += 10.0 * (dq * dq);
+        dq = 1 / (2 * dt_yaw) * (g[2] - g[0]) - s1;
+        f0 += dq * dq;
+        dq = 1 / (dt_yaw * dt_yaw) * (g[0] - 2 * g[1] + g[2]) - s2;
+        f0 += dq * dq;
+        double fe = 0.0;
+        const double q3 = g[N - 3], q2 = g[N - 2], q1 = g[N - 1];
+        dq = 1 / 6.0 * (q1 + 4 * q2 + q3) - e;
+        fe += dq * dq;
+        dq = 1 / (2 * dt_yaw) * (q1 - q3) - 0.0;
+        fe += dq * dq;
+        if (end3) {
+          dq = 1 / (dt_yaw * dt_yaw) * (q1 - 2 * q2 + q3) - 0.0;
+          fe += dq * dq;
+        }
+        double fw = 0.0;
+        for (int j = 0; j < nw; ++j) {
+          const int i = i0 + j;
+          dq = 1 / 6.0 * (g[i] + 4 * g[i + 1] + g[i + 2]) - wp[j];
+          fw += dq * dq;
+        }
+        cost = 0.0;
+        cost += Y.ld_smooth * fs;
+        cost += Y.ld_start * f0;
+        cost += Y.ld_end * fe;
+        cost += Y.ld_waypt * fw;
+        if (!isfinite(cost)) bad = true;
+      }
+      sh[4] = bad ? 1.0 : 0.0;
+      sh[5] = bad ? 0.0 : cost;
+    }
+    __syncthreads();
+    degenerate = sh[4] != 0.0;
+  }
+  const double cost = degenerate ? 0.0 : sh[5];
+
+  // 7. the yaw spline's knots: setUniformBspline(yaw, 3, dt_yaw) in planYawExplore, (yaw, bspline_degree_, dt_yaw) in
+  // planYaw; then everything is written side by side
+  const int py = follow ? p : 3;
+  if (tid == 0) {
+    for (int i = 0; i <= py; ++i) u[i] = (double)(i - py) * dt_yaw;
+    double acc = u[py];
+    for (int i = py + 1; i <= N + py; ++i) {
+      acc = acc + dt_yaw;
+      u[i] = acc;
+    }
+  }
+  __syncthreads();
+  yp_write(Y, b, tid, degenerate ? FUELMI_YAW_DEGENERATE : FUELMI_YAW_OK, duration, seg, dt_yaw, N, degenerate ? q0 : g,
+           nw, wp, e, cost, u, py);
+}
+
+size_t yp_lds(int max_ctrl, int max_seg) {
+  const size_t maxs = (size_t)max_seg, maxn = maxs + 3;
+  return ((size_t)yp_knots(max_ctrl, max_seg) + maxs + 4 * maxn + maxn + maxn + 8) * sizeof(double) + maxs * sizeof(int);
+}
+
+bool fin_nonneg(double x) { return std::isfinite(x) && x >= 0.0; }
+
+int yaw_cfg_check(const fuelmi_yaw_cfg* cfg) {
+  ARGCHK(cfg);
+  ARGCHK(cfg->mode == FUELMI_YAW_EXPLORE || cfg->mode == FUELMI_YAW_FOLLOW);
+  ARGCHK(cfg->pos_degree >= 3 && cfg->pos_degree <= 5);
+  ARGCHK(cfg->max_ctrl >= cfg->pos_degree + 1);
+  ARGCHK(cfg->max_seg >= 1 && cfg->max_seg <= FUELMI_YAW_MAX_SEG);
+  if (cfg->mode == FUELMI_YAW_EXPLORE) ARGCHK(cfg->seg_num >= 1 && cfg->seg_num <= cfg->max_seg);
+  ARGCHK(fin_nonneg(cfg->forward_t) && fin_nonneg(cfg->relax_time) && fin_nonneg(cfg->dt_target) &&
+         fin_nonneg(cfg->end_back));
+  if (cfg->mode == FUELMI_YAW_FOLLOW) ARGCHK(cfg->dt_target > 0.0);
+  if (cfg->max_ctrl > FUELMI_YAW_MAX_CTRL) {
+    fuelmi_set_error("yaw plan: max_ctrl = %d exceeds %d", cfg->max_ctrl, FUELMI_YAW_MAX_CTRL);
+    return FUELMI_ELIMIT;
+  }
+  return FUELMI_OK;
+}
+
+}  // namespace
+
+int yaw_check(const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob, const int* n_ctrl,
+              const double* pos_ctrl, const double* knot_span, const double* start_yaw, const double* end_yaw) {
+  {
+    const int rc = yaw_cfg_check(cfg);
+    if (rc) return rc;
+  }
+  ARGCHK(w);
+  ARGCHK(std::isfinite(w->ld_smooth) && std::isfinite(w->ld_start) && std::isfinite(w->ld_end) &&
+         std::isfinite(w->ld_waypt));
+  ARGCHK(w->ld_smooth > 0.0 && w->ld_start > 0.0);
+  ARGCHK(n_prob >= 0);
+  if (n_prob == 0) return FUELMI_OK;
+  ARGCHK(start_yaw);
+  ARGCHK(end_yaw || cfg->mode == FUELMI_YAW_FOLLOW);
+  for (int b = 0; b < n_prob; ++b) {
+    for (int k = 0; k < 3; ++k) ARGCHK(std::fabs(start_yaw[3 * b + k]) <= 1e3);
+    if (cfg->mode == FUELMI_YAW_EXPLORE) ARGCHK(std::fabs(end_yaw[b]) <= 1e3);
+  }
+  if (!n_ctrl) return FUELMI_OK;  // a device batch: its variables are checked by the kernel
+  ARGCHK(pos_ctrl && knot_span);
+  for (int b = 0; b < n_prob; ++b) {
+    ARGCHK(n_ctrl[b] >= cfg->pos_degree + 1 && n_ctrl[b] <= cfg->max_ctrl);
+    ARGCHK(std::isfinite(knot_span[b]) && knot_span[b] > 0.0);
+    const double* P = pos_ctrl + (size_t)b * cfg->max_ctrl * 3;
+    for (int k = 0; k < 3 * n_ctrl[b]; ++k) ARGCHK(std::fabs(P[k]) < 1e7);
+  }
+  return FUELMI_OK;
+}
+
+size_t yaw_out_bytes(const fuelmi_yaw_cfg* cfg, int n_prob, YawArgs& Y, unsigned char* base, bool dot, bool ddot) {
+  const size_t n = (size_t)n_prob, maxs = (size_t)cfg->max_seg;
+  auto pad = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  size_t at = 0;
+  auto take = [&](size_t bytes) {
+    unsigned char* p = base ? base + at : nullptr;
+    at += pad(bytes);
+    return p;
+  };
+  Y.status = reinterpret_cast<int*>(take(n * sizeof(int)));
+  Y.seg_num = reinterpret_cast<int*>(take(n * sizeof(int)));
+  Y.n_waypt = reinterpret_cast<int*>(take(n * sizeof(int)));
+  Y.duration = reinterpret_cast<double*>(take(n * sizeof(double)));
+  Y.dt_yaw = reinterpret_cast<double*>(take(n * sizeof(double)));
+  Y.end_yaw_out = reinterpret_cast<double*>(take(n * sizeof(double)));
+  Y.cost = reinterpret_cast<double*>(take(n * sizeof(double)));
+  Y.yaw_ctrl = reinterpret_cast<double*>(take(n * (maxs + 3) * sizeof(double)));
+  Y.waypts = reinterpret_cast<double*>(take(n * maxs * sizeof(double)));
+  unsigned char* d1 = take(dot ? n * (maxs + 2) * sizeof(double) : 0);
+  unsigned char* d2 = take(ddot ? n * (maxs + 1) * sizeof(double) : 0);
+  Y.yawdot_ctrl = dot ? reinterpret_cast<double*>(d1) : nullptr;
+  Y.yawddot_ctrl = ddot ? reinterpret_cast<double*>(d2) : nullptr;
+  return at;
+}
+
+int yaw_copy_out(const fuelmi_yaw_cfg* cfg, int n_prob, const YawArgs& H, int* status, double* duration, int* seg_num,
+                 double* dt_yaw, double* yaw_ctrl, int* n_waypt, double* waypts, double* end_yaw_out, double* cost,
+                 double* yawdot_ctrl, double* yawddot_ctrl) {
+  const size_t n = (size_t)n_prob, maxs = (size_t)cfg->max_seg;
+  memcpy(status, H.status, n * sizeof(int));
+  memcpy(seg_num, H.seg_num, n * sizeof(int));
+  memcpy(n_waypt, H.n_waypt, n * sizeof(int));
+  memcpy(duration, H.duration, n * sizeof(double));
+  memcpy(dt_yaw, H.dt_yaw, n * sizeof(double));
+  memcpy(end_yaw_out, H.end_yaw_out, n * sizeof(double));
+  memcpy(cost, H.cost, n * sizeof(double));
+  memcpy(yaw_ctrl, H.yaw_ctrl, n * (maxs + 3) * sizeof(double));
+  memcpy(waypts, H.waypts, n * maxs * sizeof(double));
+  if (yawdot_ctrl) memcpy(yawdot_ctrl, H.yawdot_ctrl, n * (maxs + 2) * sizeof(double));
+  if (yawddot_ctrl) memcpy(yawddot_ctrl, H.yawddot_ctrl, n * (maxs + 1) * sizeof(double));
+  for (int b = 0; b < n_prob; ++b)
+    if (status[b] == -1) {
+      fuelmi_set_error("yaw plan: problem %d needs %d yaw segments, more than max_seg = %d", b, seg_num[b], cfg->max_seg);
+      return FUELMI_ELIMIT;
+    }
+  return FUELMI_OK;
+}
+
+int yaw_launch(hipStream_t st, const YawArgs& Y) {
+  const size_t lds = yp_lds(Y.cfg.max_ctrl, Y.cfg.max_seg);  // < 64 KiB at the documented limits
+  hipLaunchKernelGGL(k_yaw_plan, dim3(Y.n_prob), dim3(YP_NT), lds, st, Y);
+  HIPCHK(hipGetLastError());
+  return FUELMI_OK;
+}
+
+extern "C" int fuelmi_yaw_plan(const fuelmi_yaw_cfg* cfg, int out3[3]) {
+  ARGCHK(out3);
+  {
+    const int rc = yaw_cfg_check(cfg);
+    if (rc) return rc;
+  }
+  out3[0] = YP_NT, out3[1] = (int)yp_lds(cfg->max_ctrl, cfg->max_seg), out3[2] = FUELMI_YAW_MAX_CTRL;
+  return FUELMI_OK;
+}
+
+extern "C" int fuelmi_map_plan_yaws(fuelmi_map* m, const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob,
+                                    const int* n_ctrl, const double* pos_ctrl, const double* knot_span,
+                                    const double* start_yaw, const double* end_yaw, int* status, double* duration,
+                                    int* seg_num, double* dt_yaw, double* yaw_ctrl, int* n_waypt, double* waypts,
+                                    double* end_yaw_out, double* cost, double* yawdot_ctrl, double* yawddot_ctrl) {
+  {  // every argument on the host, before the map is touched
+    ARGCHK(n_prob <= 0 || n_ctrl);
+    const int rc = yaw_check(w, cfg, n_prob, n_ctrl, pos_ctrl, knot_span, start_yaw, end_yaw);
+    if (rc) return rc;
+  }
+  if (n_prob == 0) return FUELMI_OK;
+  ARGCHK(status && duration && seg_num && dt_yaw && yaw_ctrl && n_waypt && waypts && end_yaw_out && cost);
+  ARGCHK(m);
+  HIPCHK(hipSetDevice(m->device));
+  const size_t n = (size_t)n_prob, maxc = (size_t)cfg->max_ctrl;
+  auto pad = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  const size_t b_int = pad(n * sizeof(int)), b_dbl = pad(n * sizeof(double)), b_pos = pad(n * maxc * 3 * sizeof(double)),
+               b_s3 = pad(n * 3 * sizeof(double));
+  YawArgs Y;
+  memset(&Y, 0, sizeof(Y));
+  const size_t b_out = yaw_out_bytes(cfg, n_prob, Y, nullptr, yawdot_ctrl != nullptr, yawddot_ctrl != nullptr);
+  QuerySlotGuard q;
+  {
+    const int rcq = q.acquire(m, b_int + 2 * b_dbl + b_pos + b_s3 + b_out);
+    if (rcq) return rcq;
+  }
+  unsigned char* at = q.s->pin;
+  auto take = [&](size_t bytes) {
+    unsigned char* p = at;
+    at += bytes;
+    return p;
+  };
+  Y.cfg = *cfg;
+  Y.ld_smooth = w->ld_smooth, Y.ld_start = w->ld_start, Y.ld_end = w->ld_end, Y.ld_waypt = w->ld_waypt;
+  Y.n_prob = n_prob;
+  int* p_nc = reinterpret_cast<int*>(take(b_int));
+  double* p_knot = reinterpret_cast<double*>(take(b_dbl));
+  double* p_end = reinterpret_cast<double*>(take(b_dbl));
+  double* p_pos = reinterpret_cast<double*>(take(b_pos));
+  double* p_start = reinterpret_cast<double*>(take(b_s3));
+  memcpy(p_nc, n_ctrl, n * sizeof(int));
+  memcpy(p_knot, knot_span, n * sizeof(double));
+  if (end_yaw)
+    memcpy(p_end, end_yaw, n * sizeof(double));
+  else
+    memset(p_end, 0, n * sizeof(double));
+  memcpy(p_pos, pos_ctrl, n * maxc * 3 * sizeof(double));
+  memcpy(p_start, start_yaw, n * 3 * sizeof(double));
+  Y.n_ctrl = p_nc, Y.n_ctrl_all = 0;
+  Y.pos = p_pos, Y.pos_stride = maxc * 3;
+  Y.knot = p_knot, Y.knot_stride = 1;
+  Y.start_yaw = p_start, Y.end_yaw = p_end;
+  yaw_out_bytes(cfg, n_prob, Y, take(b_out), yawdot_ctrl != nullptr, yawddot_ctrl != nullptr);
+  {
+    const int rc = yaw_launch(q.s->st, Y);
+    if (rc) return rc;
+  }
+  HIPCHK(q.finish());
+  return yaw_copy_out(cfg, n_prob, Y, status, duration, seg_num, dt_yaw, yaw_ctrl, n_waypt, waypts, end_yaw_out, cost,
+                      yawdot_ctrl, yawddot_ctrl);
+}

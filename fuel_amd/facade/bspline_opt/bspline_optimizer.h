@@ -72,6 +72,20 @@ public:
   Eigen::MatrixXd init_ctrl_pts_;
   double init_knot_span_ = 0.0, final_cost_ = 0.0;
 
+  // additions: the bodies of FastPlannerManager::planYawExplore (plan_manage/src/planner_manager.cpp:774-853) and
+  // ::planYaw (:695-758) in one device call each (fuelmi_map_plan_yaws, include/fuelmi.h): the way-points by look-ahead
+  // on the uniform position spline (pos_ctrl rows, degree pos_degree, knot span pos_dt), the unwrap chain, the initial
+  // control points and THE MINIMISER of the yaw objective (the reference's NLopt run iterates towards it), with this
+  // optimiser's own weights and its environment's map.  yaw_ctrl ((seg_num + 3) x 1) and dt_yaw are what the caller
+  // hands to setUniformBspline(yaw, 3 / bspline_degree_, dt_yaw) and getDerivative() twice; planYaw's path_yaw (may be
+  // null) receives the way-points (plan_data_.path_yaw_).  Both return the problem's status, and touch the outputs only
+  // when it is FUELMI_YAW_OK: FUELMI_YAW_DEGENERATE (start (0, 0, 0) to end 0: the reference divides by pt_dist_ = 0)
+  // or the negative FUELMI_E* of a call that failed.
+  int planYawExplore(const Eigen::MatrixXd& pos_ctrl, int pos_degree, double pos_dt, const Eigen::Vector3d& start_yaw,
+                     double end_yaw, bool lookfwd, double relax_time, Eigen::MatrixXd& yaw_ctrl, double& dt_yaw);
+  int planYaw(const Eigen::MatrixXd& pos_ctrl, int pos_degree, double pos_dt, const Eigen::Vector3d& start_yaw,
+              Eigen::MatrixXd& yaw_ctrl, double& dt_yaw, std::vector<double>* path_yaw);
+
   Eigen::MatrixXd getControlPoints();
   vector<Eigen::Vector3d> matrixToVectors(const Eigen::MatrixXd& ctrl_pts);
 

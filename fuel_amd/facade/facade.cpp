@@ -1147,6 +1147,49 @@ int BsplineOptimizer::planThroughWaypoints(const vector<Eigen::Vector3d>& tour, 
   return FUELMI_WPTRAJ_OK;
 }
 
+// one fuelmi_map_plan_yaws problem; the outputs are touched only when its status is FUELMI_YAW_OK
+static int plan_one_yaw(fuelmi_map* m, const fuelmi_bspline_cfg& w, const fuelmi_yaw_cfg& yc, const Eigen::MatrixXd& pos_ctrl,
+                        double pos_dt, const Eigen::Vector3d& start_yaw, double end_yaw, Eigen::MatrixXd& yaw_ctrl,
+                        double& dt_yaw, std::vector<double>* path_yaw) {
+  const int n_ctrl = (int)pos_ctrl.rows();
+  if (n_ctrl < 1 || pos_ctrl.cols() != 3) return FUELMI_EINVAL;
+  std::vector<double> pos(3 * (size_t)n_ctrl);
+  for (int i = 0; i < n_ctrl; ++i)
+    for (int k = 0; k < 3; ++k) pos[3 * i + k] = pos_ctrl(i, k);
+  const double start[3] = {start_yaw(0), start_yaw(1), start_yaw(2)};
+  int status = 0, seg_num = 0, n_waypt = 0;
+  double duration = 0.0, dt = 0.0, e = 0.0, cost = 0.0;
+  std::vector<double> q((size_t)yc.max_seg + 3), wp((size_t)yc.max_seg);
+  const int rc = fuelmi_map_plan_yaws(m, &w, &yc, 1, &n_ctrl, pos.data(), &pos_dt, start, &end_yaw, &status, &duration,
+                                      &seg_num, &dt, q.data(), &n_waypt, wp.data(), &e, &cost, nullptr, nullptr);
+  if (rc) {
+    warn("fuelmi_map_plan_yaws", rc);
+    return rc;
+  }
+  if (status != FUELMI_YAW_OK) return status;
+  yaw_ctrl = Eigen::MatrixXd(seg_num + 3, 1);
+  for (int i = 0; i < seg_num + 3; ++i) yaw_ctrl(i, 0) = q[i];
+  dt_yaw = dt;
+  if (path_yaw) path_yaw->assign(wp.begin(), wp.begin() + n_waypt);
+  return FUELMI_YAW_OK;
+}
+
+int BsplineOptimizer::planYawExplore(const Eigen::MatrixXd& pos_ctrl, int pos_degree, double pos_dt,
+                                     const Eigen::Vector3d& start_yaw, double end_yaw, bool lookfwd, double relax_time,
+                                     Eigen::MatrixXd& yaw_ctrl, double& dt_yaw) {
+  fuelmi_yaw_cfg yc = {FUELMI_YAW_EXPLORE, pos_degree, (int)pos_ctrl.rows(), 12, 12, lookfwd ? 1 : 0, relax_time, 2.0, 0.3, 0.1};
+  return plan_one_yaw(edt_environment_->sdf_map_->device(), cfg_, yc, pos_ctrl, pos_dt, start_yaw, end_yaw, yaw_ctrl, dt_yaw,
+                      nullptr);
+}
+
+int BsplineOptimizer::planYaw(const Eigen::MatrixXd& pos_ctrl, int pos_degree, double pos_dt,
+                              const Eigen::Vector3d& start_yaw, Eigen::MatrixXd& yaw_ctrl, double& dt_yaw,
+                              std::vector<double>* path_yaw) {
+  fuelmi_yaw_cfg yc = {FUELMI_YAW_FOLLOW, pos_degree, (int)pos_ctrl.rows(), FUELMI_YAW_MAX_SEG, 0, 1, 0.0, 2.0, 0.3, 0.1};
+  return plan_one_yaw(edt_environment_->sdf_map_->device(), cfg_, yc, pos_ctrl, pos_dt, start_yaw, 0.0, yaw_ctrl, dt_yaw,
+                      path_yaw);
+}
+
 vector<Eigen::Vector3d> BsplineOptimizer::matrixToVectors(const Eigen::MatrixXd& ctrl_pts) {
   vector<Eigen::Vector3d> out;
   for (int i = 0; i < ctrl_pts.rows(); ++i) {

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (BsplineBatch, BsplineCfg, FrontierCfg, GoalCfg, MapCfg, MapInfo, PathCfg, RefineCfg, TspCfg, WptrajCfg,
-                   check, lib)
+                   YawCfg, check, lib)
 
 # exploration.launch / algorithm.xml defaults (exploration_manager/launch/algorithm.xml:33-59,170-181)
 DEFAULT_MAP = dict(resolution=0.1, ground_height=-1.0, obstacles_inflation=0.199,
@@ -53,6 +53,27 @@ def _pack_waypoints(ways, vels, accs, max_vel, ctrl_pt_dist, min_seg, seg_num, m
         way[b, :k] = w[:k]
     c = WptrajCfg(float(max_vel), float(ctrl_pt_dist), int(min_seg), int(seg_num), maxw, int(max_samples))
     return n_way, way, vel, acc, c
+
+
+def yaw_cfg(mode=0, pos_degree=3, max_ctrl=4, max_seg=None, seg_num=12, lookfwd=True, relax_time=1.0, forward_t=2.0,
+            dt_target=0.3, end_back=0.1):
+    """fuelmi_yaw_cfg with planYawExplore's / planYaw's constants; max_seg defaults to seg_num (EXPLORE) or the limit"""
+    if max_seg is None:
+        max_seg = seg_num if mode == _lib.YAW_EXPLORE else _lib.YAW_MAX_SEG
+    return YawCfg(int(mode), int(pos_degree), int(max_ctrl), int(max_seg), int(seg_num), 1 if lookfwd else 0,
+                  float(relax_time), float(forward_t), float(dt_target), float(end_back))
+
+
+def _yaw_outputs(n, max_seg, derivs):
+    ms = max(int(max_seg), 0)
+    o = {"status": np.zeros(n, dtype=np.int32), "duration": np.zeros(n), "seg_num": np.zeros(n, dtype=np.int32),
+         "dt_yaw": np.zeros(n), "yaw_ctrl": np.zeros((n, ms + 3)), "n_waypt": np.zeros(n, dtype=np.int32),
+         "waypts": np.zeros((n, ms)), "end_yaw": np.zeros(n), "cost": np.zeros(n),
+         "yawdot_ctrl": np.zeros((n, ms + 2)) if derivs else None, "yawddot_ctrl": np.zeros((n, ms + 1)) if derivs else None}
+    args = (_ip(o["status"]), _dp(o["duration"]), _ip(o["seg_num"]), _dp(o["dt_yaw"]), _dp(o["yaw_ctrl"]),
+            _ip(o["n_waypt"]), _dp(o["waypts"]), _dp(o["end_yaw"]), _dp(o["cost"]), _dp(o["yawdot_ctrl"]),
+            _dp(o["yawddot_ctrl"]))
+    return o, args
 
 
 def _d3(v):
@@ -409,6 +430,44 @@ class SDFMap:
         """(lanes per problem, LDS bytes, largest max_way_points accepted) of the way-point kernel; host only"""
         out = (C.c_int * 3)()
         check(lib().fuelmi_wptraj_plan(C.byref(WptrajCfg(2.0, 0.45, 8, 0, int(max_way_points), 1)), out))
+        return tuple(out)
+
+    # --- the yaw trajectory of a position spline (include/fuelmi.h fuelmi_map_plan_yaws) ---
+    YAW_EXPLORE, YAW_FOLLOW, YAW_OK, YAW_DEGENERATE = _lib.YAW_EXPLORE, _lib.YAW_FOLLOW, _lib.YAW_OK, _lib.YAW_DEGENERATE
+
+    def plan_yaws(self, pos_ctrl, knot_span, start_yaw, end_yaw=None, weights=None, derivs=True, allow_limit=False,
+                  max_ctrl=None, **cfg):
+        """planYawExplore (mode 0) / planYaw (mode 1) per problem: pos_ctrl is a list of [n_ctrl, 3] control-point arrays
+        of uniform position splines, knot_span [n], start_yaw [n, 3] (yaw, rate, acceleration), end_yaw [n] (EXPLORE).
+        weights: a BsplineCfg or a dict of ld_* (default: the launch file's); cfg: the fields of yaw_cfg().  Returns a
+        dict of arrays: status, duration, seg_num, dt_yaw, yaw_ctrl [n, max_seg+3], n_waypt, waypts [n, max_seg],
+        end_yaw, cost, yawdot_ctrl, yawddot_ctrl (with derivs), limit.  FUELMI_ELIMIT raises unless allow_limit."""
+        pos = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in pos_ctrl]
+        n = len(pos)
+        maxc = int(max_ctrl) if max_ctrl is not None else max([len(p) for p in pos] + [4])
+        c = yaw_cfg(max_ctrl=maxc, **cfg)
+        n_ctrl = np.array([len(p) for p in pos], dtype=np.int32)
+        arr = np.zeros((n, max(maxc, 0), 3))
+        for b, p in enumerate(pos):
+            k = min(len(p), arr.shape[1])
+            arr[b, :k] = p[:k]
+        knot = np.ascontiguousarray(np.broadcast_to(np.asarray(knot_span, dtype=np.float64), (n,)))
+        sy = np.ascontiguousarray(start_yaw, dtype=np.float64).reshape(n, 3)
+        ey = None if end_yaw is None else np.ascontiguousarray(np.broadcast_to(np.asarray(end_yaw, dtype=np.float64), (n,)))
+        w = weights if isinstance(weights, BsplineCfg) else BsplineCfg(**dict(DEFAULT_BSPLINE, **(weights or {})))
+        o, args = _yaw_outputs(n, c.max_seg, derivs)
+        rc = self.L.fuelmi_map_plan_yaws(self.h, C.byref(w), C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(knot), _dp(sy),
+                                         _dp(ey), *args)
+        if not (allow_limit and rc == -5):
+            check(rc)
+        o["limit"] = rc == -5
+        return o
+
+    @staticmethod
+    def yaw_plan(cfg):
+        """(lanes per problem, LDS bytes, largest max_ctrl accepted) of the yaw kernel for a YawCfg; host only"""
+        out = (C.c_int * 3)()
+        check(lib().fuelmi_yaw_plan(C.byref(cfg), out))
         return tuple(out)
 
     # --- measurement ---
@@ -957,6 +1016,22 @@ class BsplineDeviceProblem:
         if not (allow_limit and rc == -5):
             check(rc)
         return status, duration
+
+    def plan_yaws(self, start_yaw, end_yaw=None, derivs=True, allow_limit=False, **cfg):
+        """The yaw trajectories of the candidates' optimised position splines, read from what the last optimize() left
+        on the device (fuelmi_bspline_dev_plan_yaws); the batch's own weights.  Same result dict as SDFMap.plan_yaws."""
+        c = self.problem.c
+        n = c.n_traj
+        cfg.setdefault("pos_degree", 3)
+        yc = yaw_cfg(max_ctrl=c.point_num, **cfg)
+        sy = np.ascontiguousarray(start_yaw, dtype=np.float64).reshape(n, 3)
+        ey = None if end_yaw is None else np.ascontiguousarray(np.broadcast_to(np.asarray(end_yaw, dtype=np.float64), (n,)))
+        o, args = _yaw_outputs(n, yc.max_seg, derivs)
+        rc = self.L.fuelmi_bspline_dev_plan_yaws(self.h, C.byref(yc), _dp(sy), _dp(ey), *args)
+        if not (allow_limit and rc == -5):
+            check(rc)
+        o["limit"] = rc == -5
+        return o
 
     def close(self):
         if getattr(self, "h", None):

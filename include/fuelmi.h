@@ -753,6 +753,96 @@ int fuelmi_bspline_dev_load_waypoints(fuelmi_bspline_dev* b, const fuelmi_wptraj
 int fuelmi_wptraj_plan(const fuelmi_wptraj_cfg* cfg, int out3[3]);
 
 /* ------------------------------------------------------------------------------------------
+ * Yaw trajectory of a position spline: FastPlannerManager::planYawExplore (plan_manage/src/planner_manager.cpp:774-865,
+ * mode FUELMI_YAW_EXPLORE) and ::planYaw (:695-772, FUELMI_YAW_FOLLOW) for n_prob independent problems in one call.
+ * The position spline is UNIFORM (control points + one knot span, setUniformBspline): the exploration path sets no
+ * other; a spline whose knots were moved by a time reallocation (lengthenTime) is out of scope.
+ * Per problem, EXPLORE, everything f64 in this order:
+ *   1. knots as setUniformBspline builds them (non_uniform_bspline.cpp:25-31): u[i] = double(i - p) * dt for i <= p,
+ *      then ACCUMULATED u[i] = u[i-1] + dt; duration = u[n_ctrl] - u[p] (a result of the additions, not a product).
+ *   2. dt_yaw = duration / seg_num; start_yaw[0] wrapped into [-pi, pi] by the reference's two loops; last_yaw = it.
+ *   3. initial control points q[0..2] = states2pts * start (rows (1, -dt, (1/3.0) dt dt), (1, 0, -(1/6.0) dt dt),
+ *      (1, dt, (1/3.0) dt dt), products summed left to right), the rest 0.
+ *   4. with lookfwd: relax_num = int(min(relax_time / dt_yaw, seg_num)); for i = 1 .. seg_num - relax_num - 1:
+ *      tc = i dt_yaw, tf = min(duration, tc + forward_t), pd = evaluateDeBoorT(tf) - evaluateDeBoorT(tc) (the literal
+ *      clamp, knot search and alpha recursion of :51-71); if sqrt(x x + y y + z z) > 1e-6: w = atan2(pd.y, pd.x)
+ *      unwrapped by calcNextYaw(last_yaw, w) (:867-885), else w = the previous way-point.  THE FIRST WAY-POINT HAS NO
+ *      PREDECESSOR (the reference reads waypts.back() of an empty vector there): it is defined as last_yaw, the
+ *      wrapped start yaw.  last_yaw = w; the way-point's control-point index is i.
+ *   5. e = end_yaw unwrapped against last_yaw; q[seg_num .. seg_num+2] = states2pts * (e, 0, 0); end_yaw_out = e.
+ *   6. pt_dist = (sum |q[i+1] - q[i]|) / (seg_num + 3) (optimize(), bspline_optimizer.cpp:136-140).
+ *   7. yaw_ctrl = THE MINIMISER of the reference's objective SMOOTHNESS | START | END | WAYPOINTS (order 3, dimension
+ *      1, start state (s0, s1, s2), end state (e, 0)) (:255-282, 355-457, 571-630): a convex quadratic, solved exactly
+ *      by a banded Cholesky factorisation (half-bandwidth 3).  The reference's NLopt run iterates towards this point
+ *      for at most 2000 evaluations; its iterate is not reproduced, its cost is never below this one's except by
+ *      rounding.  cost = the objective at yaw_ctrl.
+ *   8. yawdot_ctrl / yawddot_ctrl = getDerivativeControlPoints (:77-86) once and twice on setUniformBspline(yaw, 3,
+ *      dt_yaw)'s accumulated knots.
+ * FOLLOW differs: seg_num = ceil(duration / dt_target); start_yaw[0] is not wrapped; way-points at i = 0 .. seg_num-1,
+ * no relax; end = atan2(v.y, v.x) with v the DERIVATIVE spline (getDerivative) evaluated by its own evaluateDeBoorT at
+ * duration - end_back, unwrapped against the last way-point; three end entries (e, 0, 0); the yaw spline (and so the
+ * derivative control points) has degree pos_degree, as planYaw sets it.
+ * Per-problem status:
+ *   FUELMI_YAW_OK.
+ *   FUELMI_YAW_DEGENERATE  pt_dist is 0 or not finite (the reference divides by it), or a Cholesky pivot is <= 0 or
+ *                          not finite, or the cost is not finite: yaw_ctrl = the initial control points, cost = 0; the
+ *                          way-points, end_yaw_out and the derivative control points (of the initial ones) are written.
+ *                          Also (device batches only, the host route refuses it): a knot span that is not finite and > 0
+ *                          -- then every output of the problem is 0.
+ *   -1                     FOLLOW: seg_num exceeds cfg.max_seg; seg_num, duration and dt_yaw are reported, the arrays
+ *                          are 0, the other problems are complete, and the call returns FUELMI_ELIMIT.
+ * Entries of yaw_ctrl past seg_num + 3, of waypts past n_waypt (and of the derivative arrays) are written as 0.
+ * Checked on the host before anything is launched (FUELMI_EINVAL): pointers; mode; pos_degree in 3..5; pos_degree + 1
+ * <= n_ctrl[i] <= max_ctrl; knot spans finite and > 0; control points finite with |coordinate| < 1e7; yaw inputs finite
+ * with |value| <= 1e3; the four weights finite, ld_start > 0 and ld_smooth > 0; forward_t, relax_time, dt_target,
+ * end_back finite and >= 0 (dt_target > 0 in FOLLOW); 1 <= max_seg <= FUELMI_YAW_MAX_SEG; 1 <= seg_num <= max_seg in
+ * EXPLORE.  max_ctrl > FUELMI_YAW_MAX_CTRL: FUELMI_ELIMIT.  n_prob = 0 is FUELMI_OK.
+ * fuelmi_map_plan_yaws runs on a query slot of the map like fuelmi_map_waypoint_trajs: host arrays in and out,
+ * synchronous, re-entrant, no device allocation once warm; a result does not depend on the problem's place in the batch.
+ * ---------------------------------------------------------------------------------------- */
+#define FUELMI_YAW_EXPLORE 0      /* FastPlannerManager::planYawExplore, planner_manager.cpp:774-865 */
+#define FUELMI_YAW_FOLLOW  1      /* FastPlannerManager::planYaw,        planner_manager.cpp:695-772 */
+#define FUELMI_YAW_OK 0
+#define FUELMI_YAW_DEGENERATE 1
+#define FUELMI_YAW_MAX_SEG  256   /* largest number of yaw segments */
+#define FUELMI_YAW_MAX_CTRL 1024  /* largest max_ctrl (position control points per problem) */
+typedef struct {
+  int mode;            /* FUELMI_YAW_EXPLORE / _FOLLOW */
+  int pos_degree;      /* degree of the position spline, 3..5 (pp_.bspline_degree_) */
+  int max_ctrl;        /* stride of pos_ctrl */
+  int max_seg;         /* stride of the outputs: yaw_ctrl [max_seg + 3], waypts [max_seg] */
+  int seg_num;         /* EXPLORE: 12 */
+  int lookfwd;         /* EXPLORE: way-points on / off */
+  double relax_time;   /* EXPLORE: exploration/relax_time */
+  double forward_t;    /* 2.0 */
+  double dt_target;    /* FOLLOW: 0.3 */
+  double end_back;     /* FOLLOW: 0.1 */
+} fuelmi_yaw_cfg;
+/* w: only ld_smooth, ld_start, ld_end, ld_waypt are read.  pos_ctrl [n_prob][max_ctrl][3], knot_span [n_prob],
+ * start_yaw [n_prob][3] (yaw, rate, acceleration), end_yaw [n_prob] (EXPLORE only, may be NULL in FOLLOW).  Out, per
+ * problem: status, duration, seg_num, dt_yaw, yaw_ctrl [n_prob][max_seg+3], n_waypt, waypts [n_prob][max_seg],
+ * end_yaw_out, cost; yawdot_ctrl [n_prob][max_seg+2] and yawddot_ctrl [n_prob][max_seg+1] may each be NULL. */
+int fuelmi_map_plan_yaws(fuelmi_map* m, const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob,
+                         const int* n_ctrl, const double* pos_ctrl, const double* knot_span, const double* start_yaw,
+                         const double* end_yaw, int* status, double* duration, int* seg_num, double* dt_yaw,
+                         double* yaw_ctrl, int* n_waypt, double* waypts, double* end_yaw_out, double* cost,
+                         double* yawdot_ctrl, double* yawddot_ctrl);
+/* The device chain optimised batch -> yaw trajectories: one problem per candidate of `b` (dim 3), read from the
+ * variables the batch's last fuelmi_bspline_dev_optimize[_timed] left in device memory: the control points are those
+ * variables, the knot span is x[nvar-1] under MINTIME and the batch's knot span otherwise; the weights are the batch's;
+ * cfg->pos_degree must be the batch's bspline_degree and cfg->max_ctrl is ignored (it is point_num).  Only the yaw
+ * results are copied back; they equal, bit for bit, fuelmi_map_plan_yaws on the x_out that solve returned.
+ * FUELMI_EINVAL when the batch is not dim 3 or has not been optimised since it was created or last (re)loaded by
+ * fuelmi_bspline_dev_load_samples / _load_waypoints.  Runs on the map's stream and waits for it. */
+int fuelmi_bspline_dev_plan_yaws(fuelmi_bspline_dev* b, const fuelmi_yaw_cfg* cfg, const double* start_yaw,
+                                 const double* end_yaw, int* status, double* duration, int* seg_num, double* dt_yaw,
+                                 double* yaw_ctrl, int* n_waypt, double* waypts, double* end_yaw_out, double* cost,
+                                 double* yawdot_ctrl, double* yawddot_ctrl);
+/* what the kernel needs for cfg->max_ctrl and cfg->max_seg (host only, no device needed): out3 = {lanes per problem,
+ * dynamic LDS bytes, largest max_ctrl accepted}.  cfg is checked like above. */
+int fuelmi_yaw_plan(const fuelmi_yaw_cfg* cfg, int out3[3]);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): HIP events recorded on the map's own stream.
  * ---------------------------------------------------------------------------------------- */
 enum {
