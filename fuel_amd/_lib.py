@@ -114,6 +114,20 @@ WPTRAJ_OK, WPTRAJ_FEW, WPTRAJ_DEGENERATE = 0, 1, 2
 WPTRAJ_MAX_WAY, WPTRAJ_MAX_SEG, WPTRAJ_MAX_DURATION = 256, 1 << 20, 1.0e4
 
 
+class KinoCfg(C.Structure):
+    """fuelmi_kino_cfg: the search/* parameters of KinodynamicAstar, the three constants of search(), getSamples' knot
+    span and segment rule, the strides of the path / sample arrays."""
+    _fields_ = [(n, C.c_double) for n in
+                ("max_tau", "init_max_tau", "max_vel", "max_acc", "w_time", "horizon", "resolution", "lambda_heu", "res",
+                 "time_res", "time_res_init", "ts")] + \
+               [(n, C.c_int) for n in
+                ("allocate_num", "check_num", "optimistic", "min_seg", "seg_num", "max_path_nodes", "max_samples")]
+
+
+KINO_REACH_HORIZON, KINO_REACH_END, KINO_NO_PATH, KINO_NEAR_END, KINO_CLOSE_GOAL = 1, 2, 3, 4, 5
+KINO_MAX_PRIMS, KINO_MAX_ALLOC, KINO_MAX_SEG = 256, 1 << 22, 1 << 20
+
+
 class YawCfg(C.Structure):
     """fuelmi_yaw_cfg: planYawExplore's / planYaw's constants and the strides of the control-point / way-point arrays."""
     _fields_ = [("mode", C.c_int), ("pos_degree", C.c_int), ("max_ctrl", C.c_int), ("max_seg", C.c_int),
@@ -247,6 +261,10 @@ SYMBOLS = {
     "fuelmi_map_waypoint_trajs": (C.c_int, [_P, C.POINTER(WptrajCfg), C.c_int, _ip, _dp, _dp, _dp, _ip, _dp, _dp, _ip, _dp,
                                             _ip, _dp, _dp, _dp, _dp]),
     "fuelmi_wptraj_plan": (C.c_int, [C.POINTER(WptrajCfg), _ip]),
+    "fuelmi_map_kino_paths": (C.c_int, [_P, C.POINTER(KinoCfg), C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip, _ip, _ip,
+                                        _dp, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp]),
+    "fuelmi_bspline_dev_load_kino": (C.c_int, [_P, C.POINTER(KinoCfg), _dp, _dp, _dp, _dp, _dp, _ip, _dp]),
+    "fuelmi_kino_plan": (C.c_int, [C.POINTER(KinoCfg), C.POINTER(C.c_longlong)]),
     "fuelmi_map_plan_yaws": (C.c_int, [_P, C.POINTER(BsplineCfg), C.POINTER(YawCfg), C.c_int, _ip, _dp, _dp, _dp, _dp, _ip,
                                        _dp, _ip, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp]),
     "fuelmi_bspline_dev_plan_yaws": (C.c_int, [_P, C.POINTER(YawCfg), _dp, _dp, _ip, _dp, _ip, _dp, _dp, _ip, _dp, _dp,

@@ -1588,6 +1588,100 @@ extern "C" int fuelmi_bspline_dev_load_waypoints(fuelmi_bspline_dev* b, const fu
   return FUELMI_OK;
 }
 
+// start / goal -> kinodynamic search -> getSamples (k_kino_path, written into the staging) -> the fit, all on the map's
+// stream: the mid-range counterpart of the call above
+extern "C" int fuelmi_bspline_dev_load_kino(fuelmi_bspline_dev* b, const fuelmi_kino_cfg* cfg, const double* start_xyz,
+                                            const double* start_vel, const double* start_acc, const double* goal_xyz,
+                                            const double* goal_vel, int* status, double* T_sum) {
+  ARGCHK(b && cfg && status);
+  BsplineArgs& A = b->a;
+  const int degree = A.cfg.bspline_degree;
+  ARGCHK(A.dim == 3 && degree >= 3 && degree <= 5 && A.N - degree >= 1);
+  const int seg = A.N - degree, n_points = seg + 1;
+  ARGCHK(cfg->seg_num == 0 || cfg->seg_num == seg);
+  fuelmi_kino_cfg kc = *cfg;
+  kc.seg_num = seg, kc.max_samples = n_points, kc.max_path_nodes = 1;
+  {
+    const int rc = kino_check(&kc, A.C, start_xyz, start_vel, start_acc, goal_xyz, goal_vel);
+    if (rc) return rc;
+  }
+  fuelmi_map* m = b->map;
+  ARGCHK(m);
+  b->opt_valid = false;
+  HIPCHK(hipSetDevice(m->device));
+  const size_t C = (size_t)A.C, K = (size_t)n_points;
+  auto pad = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  const size_t b_ts = C * sizeof(double), b_pts = C * K * 3 * sizeof(double), b_der = C * 12 * sizeof(double);
+  if (b_ts + b_pts + b_der > b->fit_cap) {
+    void* d = nullptr;
+    HIPCHK(hipMalloc(&d, b_ts + b_pts + b_der));
+    b->allocs.push_back(d);
+    b->fit_in = static_cast<double*>(d);
+    b->fit_cap = b_ts + b_pts + b_der;
+  }
+  unsigned char* d = reinterpret_cast<unsigned char*>(b->fit_in);
+  const size_t b_int = pad(C * sizeof(int)), b_dbl = pad(C * sizeof(double)), b_12 = pad(C * 12 * sizeof(double));
+  KinoArgs W;
+  unsigned char* io = nullptr;
+  {
+    const int rc = kino_prepare(m, &kc, A.C, start_xyz, start_vel, start_acc, goal_xyz, goal_vel,
+                                9 * b_int + 2 * b_dbl + b_12, W, &io);
+    if (rc) return rc;
+  }
+  auto take = [&](size_t bytes) {
+    unsigned char* p = io;
+    io += bytes;
+    return p;
+  };
+  W.load_points = n_points;
+  W.status = reinterpret_cast<int*>(take(b_int));
+  W.which = reinterpret_cast<int*>(take(b_int));
+  W.iter_num = reinterpret_cast<int*>(take(b_int));
+  W.use_node_num = reinterpret_cast<int*>(take(b_int));
+  W.n_nodes = reinterpret_cast<int*>(take(b_int));
+  W.shot = reinterpret_cast<int*>(take(b_int));
+  W.seg_num = reinterpret_cast<int*>(take(b_int));
+  W.n_samples = reinterpret_cast<int*>(take(b_int));
+  W.skip = reinterpret_cast<int*>(take(b_int));
+  W.t_shot = reinterpret_cast<double*>(take(b_dbl));
+  W.T_sum = reinterpret_cast<double*>(take(b_dbl));
+  W.coef_shot = reinterpret_cast<double*>(take(b_12));
+  W.ts_out = reinterpret_cast<double*>(d);  // the fit's knot spans
+  W.samples = reinterpret_cast<double*>(d + b_ts);
+  W.derivs = reinterpret_cast<double*>(d + b_ts + b_pts);
+  FitArgs F;
+  memset(&F, 0, sizeof(F));
+  F.C = A.C, F.K = n_points, F.degree = degree;
+  F.ts = W.ts_out;
+  F.points = W.samples;
+  F.derivs = W.derivs;
+  F.ctrl = const_cast<double*>(A.x);
+  F.stride = A.nvar;
+  F.write_dt = (A.cost_function & FUELMI_COST_MINTIME) ? 1 : 0;
+  F.knot_span = const_cast<double*>(A.knot_span);
+  F.pt_dist = const_cast<double*>(A.pt_dist);
+  F.start_state = const_cast<double*>(A.start_state);
+  F.end_state = const_cast<double*>(A.end_state);
+  F.skip = W.skip;
+  hipStream_t st = m->stream;
+  {
+    const int rck = kino_launch(m, W);  // (outside the scope: the search is no spline stage)
+    if (rck) return rck;
+    StageScope sc(m, FUELMI_K_BSPLINE);
+    const int rcf = fit_launch(m, F);
+    if (rcf) return rcf;
+  }
+  HIPCHK(hipMemcpyAsync(status, W.status, C * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (T_sum) HIPCHK(hipMemcpyAsync(T_sum, W.T_sum, C * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(stream_wait(st));
+  for (int c = 0; c < A.C; ++c)
+    if (status[c] == -1) {
+      fuelmi_set_error("kinodynamic search: candidate %d does not give %d samples", c, n_points);
+      return FUELMI_ELIMIT;
+    }
+  return FUELMI_OK;
+}
+
 // the yaw trajectories of the batch's optimised position splines (k_yaw_plan, yaw_plan.hip) read from the variables the
 // last solve left on the device; only the yaw results travel
 extern "C" int fuelmi_bspline_dev_plan_yaws(fuelmi_bspline_dev* b, const fuelmi_yaw_cfg* cfg, const double* start_yaw,

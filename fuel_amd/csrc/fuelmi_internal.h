@@ -224,6 +224,10 @@ struct fuelmi_map {
   size_t goal_dev_bytes = 0;
   hipEvent_t goal_ev[3] = {nullptr, nullptr, nullptr};
   double goal_ms[2] = {0.0, 0.0};  // fuelmi_map_goal_path_times
+  // grow-only device scratch of fuelmi_map_kino_paths (kino_path.hip): inputs, results, node pools, heaps, hashes
+  void* kino_dev = nullptr;
+  size_t kino_dev_bytes = 0;
+  std::vector<double> kino_host;  // the inputs and primitive lists of the last call, alive until its copies have run
   unsigned long long fusion_count = 0;  // fusions / uploads queued so far (a search notices one queued behind its back)
   unsigned profile_mask = 0;
   ProfileSlot prof[FUELMI_K_COUNT];
@@ -563,6 +567,55 @@ int yaw_launch(hipStream_t st, const YawArgs& Y);
 int yaw_copy_out(const fuelmi_yaw_cfg* cfg, int n_prob, const YawArgs& H, int* status, double* duration, int* seg_num,
                  double* dt_yaw, double* yaw_ctrl, int* n_waypt, double* waypts, double* end_yaw_out, double* cost,
                  double* yawdot_ctrl, double* yawddot_ctrl);
+// k_kino_path (kino_path.hip): one problem per workgroup; every pointer addresses device memory
+struct KinoArgs {
+  fuelmi_kino_cfg cfg;
+  int n_prob;
+  int n_init, n_reg;        // primitives of the two lists
+  const double* prims;      // [n_init + n_reg][4]: input, tau (the init list's input is the problem's start_acc)
+  int tolerance;            // ceil(1 / resolution)
+  double inv_res;           // 1.0 / resolution
+  double box_mind[3], box_maxd[3], map_size[3];
+  const u64* infl;
+  const u64* unk;
+  const double* in;         // [n][5][3]: start, start_vel, start_acc, goal, goal_vel
+  unsigned char* pool;      // [n][allocate_num] node records
+  int* heap;                // [n][allocate_num]
+  int* hash;                // [n][hash_cap], -1 = empty
+  int hash_cap;             // a power of two >= 2 allocate_num
+  int load_points;          // > 0: the batch route, a path must give exactly this many samples
+  int* status;
+  int* which;
+  int* iter_num;
+  int* use_node_num;
+  int* n_nodes;
+  int* shot;
+  int* seg_num;
+  int* n_samples;
+  int* skip;                // [n] 0: ts / samples / derivs hold a path, 1: they do not (the fit leaves the candidate)
+  double* t_shot;
+  double* coef_shot;        // [n][3][4]
+  double* T_sum;
+  double* ts_out;
+  double* samples;          // [n][max_samples][3]
+  double* derivs;           // [n][4][3]
+  double* node_state;       // [n][max_path_nodes][6] or null
+  double* node_input;       // [n][max_path_nodes][3] or null
+  double* node_duration;    // [n][max_path_nodes] or null
+};
+// the host checks shared by fuelmi_map_kino_paths / fuelmi_bspline_dev_load_kino; the primitive lists
+// ([n_init + n_reg][4]); bytes of one problem's workspace and its hash slots; the launch on the map's stream
+int kino_check(const fuelmi_kino_cfg* cfg, int n_prob, const double* start_xyz, const double* start_vel,
+               const double* start_acc, const double* goal_xyz, const double* goal_vel);
+int kino_prims(const fuelmi_kino_cfg* cfg, std::vector<double>& prims, int& n_init, int& n_reg);
+size_t kino_workspace(const fuelmi_kino_cfg* cfg, int* hash_cap);
+// fills geometry / lists / workspace pointers of K from the map's scratch (grown to io_bytes + the workspaces), uploads
+// the inputs and the lists, clears the hashes; *io is the start of io_bytes of device memory for the caller's results
+int kino_prepare(fuelmi_map* m, const fuelmi_kino_cfg* cfg, int n_prob, const double* start_xyz, const double* start_vel,
+                 const double* start_acc, const double* goal_xyz, const double* goal_vel, size_t io_bytes, KinoArgs& K,
+                 unsigned char** io);
+int kino_launch(fuelmi_map* m, const KinoArgs& K);
+void kino_path_release(fuelmi_map* m);
 // device results of one path_cost_enqueue, in the map's path scratch: length / kind / path_len per pair, paths
 // [n][maxp][3] (nullptr when maxp is 0), and the device copy of p2_xyz
 struct PathRun {

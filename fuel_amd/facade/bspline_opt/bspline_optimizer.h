@@ -68,6 +68,19 @@ public:
   int planThroughWaypoints(const vector<Eigen::Vector3d>& tour, const Eigen::Vector3d& cur_vel,
                            const Eigen::Vector3d& cur_acc, double max_vel, double ctrl_pt_dist, int cost_mask,
                            double time_lb, Eigen::MatrixXd& ctrl_pts, double& dt);
+  // addition: the body of FastPlannerManager::kinodynamicReplan (plan_manage/src/planner_manager.cpp:124-185) -- the
+  // mid-range branch of planExploreMotion -- without the reference's KinodynamicAstar on the host: the search with its
+  // retry and getSamples in one device call (fuelmi_map_kino_paths, include/fuelmi.h; `search` holds the search/*
+  // parameters, its ts / seg_num / max_* fields are set here: ts = ctrl_pt_dist / max_vel), then parameterizeToBspline,
+  // getBoundaryStates(2, 0), setBoundaryStates, setTimeLowerBound when time_lb > 0 and optimize(ctrl_pts, dt, cost_mask,
+  // 1, 1).  Returns the search's status (FUELMI_KINO_REACH_HORIZON / _REACH_END / _NEAR_END) with ctrl_pts / dt filled,
+  // or without touching them: FUELMI_KINO_NO_PATH, FUELMI_KINO_CLOSE_GOAL (the reference returns false for both), or the
+  // negative FUELMI_E* of a call that failed.  init_ctrl_pts_ / init_knot_span_ / final_cost_ as below.
+  int planKinodynamic(const Eigen::Vector3d& start_pt, const Eigen::Vector3d& start_vel, const Eigen::Vector3d& start_acc,
+                      const Eigen::Vector3d& end_pt, const Eigen::Vector3d& end_vel, const fuelmi_kino_cfg& search,
+                      double max_vel, double ctrl_pt_dist, int cost_mask, double time_lb, Eigen::MatrixXd& ctrl_pts,
+                      double& dt);
+  int kino_iter_num_ = 0, kino_use_node_num_ = 0, kino_which_ = 0;  // diagnostics of the last planKinodynamic
   // diagnostics of the last planThroughWaypoints: what it handed to the solve, and the solve's final cost
   Eigen::MatrixXd init_ctrl_pts_;
   double init_knot_span_ = 0.0, final_cost_ = 0.0;

@@ -1147,6 +1147,64 @@ int BsplineOptimizer::planThroughWaypoints(const vector<Eigen::Vector3d>& tour, 
   return FUELMI_WPTRAJ_OK;
 }
 
+int BsplineOptimizer::planKinodynamic(const Eigen::Vector3d& start_pt, const Eigen::Vector3d& start_vel,
+                                      const Eigen::Vector3d& start_acc, const Eigen::Vector3d& end_pt,
+                                      const Eigen::Vector3d& end_vel, const fuelmi_kino_cfg& search, double max_vel,
+                                      double ctrl_pt_dist, int cost_mask, double time_lb, Eigen::MatrixXd& ctrl_pts,
+                                      double& dt) {
+  fuelmi_map* m = edt_environment_->sdf_map_->device();
+  const double sp[3] = {start_pt(0), start_pt(1), start_pt(2)}, sv[3] = {start_vel(0), start_vel(1), start_vel(2)};
+  const double sa[3] = {start_acc(0), start_acc(1), start_acc(2)}, gp[3] = {end_pt(0), end_pt(1), end_pt(2)};
+  const double gv[3] = {end_vel(0), end_vel(1), end_vel(2)};
+  fuelmi_kino_cfg kc = search;
+  kc.ts = ctrl_pt_dist / max_vel;  // :162
+  kc.min_seg = 8, kc.seg_num = 0, kc.max_path_nodes = 1, kc.max_samples = 256;
+  int status = 0, which = 0, iter = 0, use = 0, n_nodes = 0, shot = 0, seg_num = 0, n_samples = 0;
+  double t_shot = 0.0, coef[12], T_sum = 0.0, ts = 0.0, derivs[12];
+  std::vector<double> samples;
+  // the sample count is a result: a second call with room for it when the first guess was short
+  for (int pass = 0; pass < 2; ++pass) {
+    samples.assign(3 * (size_t)kc.max_samples, 0.0);
+    const int rc = fuelmi_map_kino_paths(m, &kc, 1, sp, sv, sa, gp, gv, &status, &which, &iter, &use, &n_nodes, nullptr,
+                                         nullptr, nullptr, &shot, &t_shot, coef, &T_sum, &ts, &seg_num, &n_samples,
+                                         samples.data(), derivs);
+    if (rc == FUELMI_ELIMIT && status == -1 && pass == 0 && n_samples > kc.max_samples) {
+      kc.max_samples = n_samples;
+      continue;
+    }
+    if (rc) {
+      warn("fuelmi_map_kino_paths", rc);
+      return rc;
+    }
+    break;
+  }
+  kino_iter_num_ = iter, kino_use_node_num_ = use, kino_which_ = which;
+  if (status == FUELMI_KINO_NO_PATH || status == FUELMI_KINO_CLOSE_GOAL) return status;
+  // :171-184
+  const int rows = n_samples + bspline_degree_ - 1;
+  std::vector<double> ctrl(3 * (size_t)rows), st(9), en(3);
+  int rc = fuelmi_bspline_parameterize(m, 1, n_samples, bspline_degree_, &ts, samples.data(), derivs, ctrl.data());
+  if (!rc) rc = fuelmi_bspline_boundary_states(m, 1, rows, bspline_degree_, &ts, ctrl.data(), 2, 0, st.data(), en.data());
+  if (rc) {
+    warn("planKinodynamic: spline fit", rc);
+    return rc;
+  }
+  vector<Eigen::Vector3d> start, end;
+  for (int i = 0; i < 3; ++i) start.push_back(Eigen::Vector3d(st[3 * i], st[3 * i + 1], st[3 * i + 2]));
+  end.push_back(Eigen::Vector3d(en[0], en[1], en[2]));
+  setBoundaryStates(start, end);
+  if (time_lb > 0) setTimeLowerBound(time_lb);
+  ctrl_pts = Eigen::MatrixXd(rows, 3);
+  for (int i = 0; i < rows; ++i)
+    for (int k = 0; k < 3; ++k) ctrl_pts(i, k) = ctrl[3 * i + k];
+  dt = ts;
+  init_ctrl_pts_ = ctrl_pts;
+  init_knot_span_ = dt;
+  optimize(ctrl_pts, dt, cost_mask, 1, 1);
+  final_cost_ = min_cost_;
+  return status;
+}
+
 // one fuelmi_map_plan_yaws problem; the outputs are touched only when its status is FUELMI_YAW_OK
 static int plan_one_yaw(fuelmi_map* m, const fuelmi_bspline_cfg& w, const fuelmi_yaw_cfg& yc, const Eigen::MatrixXd& pos_ctrl,
                         double pos_dt, const Eigen::Vector3d& start_yaw, double end_yaw, Eigen::MatrixXd& yaw_ctrl,

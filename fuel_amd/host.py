@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BsplineBatch, BsplineCfg, FrontierCfg, GoalCfg, MapCfg, MapInfo, PathCfg, RefineCfg, TspCfg, WptrajCfg,
+from ._lib import (BsplineBatch, BsplineCfg, FrontierCfg, GoalCfg, KinoCfg, MapCfg, MapInfo, PathCfg, RefineCfg, TspCfg, WptrajCfg,
                    YawCfg, check, lib)
 
 # exploration.launch / algorithm.xml defaults (exploration_manager/launch/algorithm.xml:33-59,170-181)
@@ -62,6 +62,16 @@ def yaw_cfg(mode=0, pos_degree=3, max_ctrl=4, max_seg=None, seg_num=12, lookfwd=
         max_seg = seg_num if mode == _lib.YAW_EXPLORE else _lib.YAW_MAX_SEG
     return YawCfg(int(mode), int(pos_degree), int(max_ctrl), int(max_seg), int(seg_num), 1 if lookfwd else 0,
                   float(relax_time), float(forward_t), float(dt_target), float(end_back))
+
+
+def kino_cfg(max_tau=0.8, init_max_tau=1.0, max_vel=2.25, max_acc=2.0, w_time=10.0, horizon=5.0, resolution=0.025,
+             lambda_heu=10.0, res=1 / 2.0, time_res=1 / 1.0, time_res_init=1 / 20.0, ts=0.45 / 2.0, allocate_num=100000,
+             check_num=10, optimistic=False, min_seg=8, seg_num=0, max_path_nodes=64, max_samples=256):
+    """fuelmi_kino_cfg with algorithm.xml's search/* values (max_vel includes vel_margin) and search()'s constants"""
+    return KinoCfg(float(max_tau), float(init_max_tau), float(max_vel), float(max_acc), float(w_time), float(horizon),
+                   float(resolution), float(lambda_heu), float(res), float(time_res), float(time_res_init), float(ts),
+                   int(allocate_num), int(check_num), 1 if optimistic else 0, int(min_seg), int(seg_num),
+                   int(max_path_nodes), int(max_samples))
 
 
 def _yaw_outputs(n, max_seg, derivs):
@@ -431,6 +441,54 @@ class SDFMap:
         out = (C.c_int * 3)()
         check(lib().fuelmi_wptraj_plan(C.byref(WptrajCfg(2.0, 0.45, 8, 0, int(max_way_points), 1)), out))
         return tuple(out)
+
+    # --- the kinodynamic search of the mid-range branch (include/fuelmi.h fuelmi_map_kino_paths) ---
+    KINO_REACH_HORIZON, KINO_REACH_END, KINO_NO_PATH, KINO_NEAR_END, KINO_CLOSE_GOAL = (
+        _lib.KINO_REACH_HORIZON, _lib.KINO_REACH_END, _lib.KINO_NO_PATH, _lib.KINO_NEAR_END, _lib.KINO_CLOSE_GOAL)
+
+    def kino_paths(self, starts, vels, accs, goals, goal_vels, nodes=True, allow_limit=False, **cfg):
+        """KinodynamicAstar::search (init, then the retry) + getSamples per problem; cfg: the fields of kino_cfg().
+        Returns a dict: status (KINO_*; -1: over max_path_nodes / max_samples), which, iter_num, use_node_num, n_nodes,
+        shot, t_shot, coef [n, 3, 4], T_sum, ts, seg_num, n_samples [n], samples (list of [k, 3]), derivs [n, 4, 3], and
+        with nodes: node_state (list of [k, 6]), node_input (list of [k, 3]), node_duration (list of [k]); limit.
+        FUELMI_ELIMIT raises FuelmiError unless allow_limit."""
+        c = kino_cfg(**cfg)
+        arr = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3) for a in (starts, vels, accs, goals, goal_vels)]
+        n = len(arr[0])
+        assert all(len(a) == n for a in arr)
+        maxn, maxs = max(c.max_path_nodes, 0), max(c.max_samples, 0)
+        iv = {k: np.zeros(n, dtype=np.int32) for k in ("status", "which", "iter_num", "use_node_num", "n_nodes", "shot",
+                                                       "seg_num", "n_samples")}
+        dv = {k: np.zeros(n) for k in ("t_shot", "T_sum", "ts")}
+        coef, derivs, samples = np.zeros((n, 3, 4)), np.zeros((n, 4, 3)), np.zeros((n, maxs, 3))
+        ns = np.zeros((n, maxn, 6)) if nodes else None
+        ni = np.zeros((n, maxn, 3)) if nodes else None
+        nd = np.zeros((n, maxn)) if nodes else None
+        rc = self.L.fuelmi_map_kino_paths(self.h, C.byref(c), n, *[_dp(a) for a in arr], _ip(iv["status"]),
+                                          _ip(iv["which"]), _ip(iv["iter_num"]), _ip(iv["use_node_num"]),
+                                          _ip(iv["n_nodes"]), _dp(ns), _dp(ni), _dp(nd), _ip(iv["shot"]), _dp(dv["t_shot"]),
+                                          _dp(coef), _dp(dv["T_sum"]), _dp(dv["ts"]), _ip(iv["seg_num"]),
+                                          _ip(iv["n_samples"]), _dp(samples), _dp(derivs))
+        if not (allow_limit and rc == -5):
+            check(rc)
+        out = dict(iv)
+        out.update(dv)
+        out.update(coef=coef, derivs=derivs, limit=rc == -5,
+                   samples=[samples[b, :min(iv["n_samples"][b], maxs)].copy() for b in range(n)])
+        if nodes:
+            live = [min(int(iv["n_nodes"][b]), maxn) for b in range(n)]
+            out["node_state"] = [ns[b, :live[b]].copy() for b in range(n)]
+            out["node_input"] = [ni[b, :live[b]].copy() for b in range(n)]
+            out["node_duration"] = [nd[b, :live[b]].copy() for b in range(n)]
+        return out
+
+    @staticmethod
+    def kino_plan(**cfg):
+        """host only: dict(lanes, lds_bytes, workspace_bytes, n_init, n_regular, max_prims, max_alloc, hash_slots)"""
+        out = (C.c_longlong * 8)()
+        check(lib().fuelmi_kino_plan(C.byref(kino_cfg(**cfg)), out))
+        return dict(zip(("lanes", "lds_bytes", "workspace_bytes", "n_init", "n_regular", "max_prims", "max_alloc",
+                         "hash_slots"), [int(v) for v in out]))
 
     # --- the yaw trajectory of a position spline (include/fuelmi.h fuelmi_map_plan_yaws) ---
     YAW_EXPLORE, YAW_FOLLOW, YAW_OK, YAW_DEGENERATE = _lib.YAW_EXPLORE, _lib.YAW_FOLLOW, _lib.YAW_OK, _lib.YAW_DEGENERATE
@@ -1016,6 +1074,22 @@ class BsplineDeviceProblem:
         if not (allow_limit and rc == -5):
             check(rc)
         return status, duration
+
+    def load_kino(self, starts, vels, accs, goals, goal_vels, allow_limit=False, **cfg):
+        """start / goal -> kinodynamic search -> getSamples -> loadSamples' fit, without leaving the device
+        (fuelmi_bspline_dev_load_kino): one problem per candidate, seg_num forced to point_num - bspline_degree.  Returns
+        (status [C], T_sum [C]); a candidate without a path keeps its state."""
+        c = self.problem.c
+        arr = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3) for a in (starts, vels, accs, goals, goal_vels)]
+        if any(len(a) != c.n_traj for a in arr):
+            raise ValueError("load_kino: one problem per candidate")
+        kc = kino_cfg(**cfg)
+        status = np.zeros(c.n_traj, dtype=np.int32)
+        t_sum = np.zeros(c.n_traj)
+        rc = self.L.fuelmi_bspline_dev_load_kino(self.h, C.byref(kc), *[_dp(a) for a in arr], _ip(status), _dp(t_sum))
+        if not (allow_limit and rc == -5):
+            check(rc)
+        return status, t_sum
 
     def plan_yaws(self, start_yaw, end_yaw=None, derivs=True, allow_limit=False, **cfg):
         """The yaw trajectories of the candidates' optimised position splines, read from what the last optimize() left

@@ -843,6 +843,114 @@ int fuelmi_bspline_dev_plan_yaws(fuelmi_bspline_dev* b, const fuelmi_yaw_cfg* cf
 int fuelmi_yaw_plan(const fuelmi_yaw_cfg* cfg, int out3[3]);
 
 /* ------------------------------------------------------------------------------------------
+ * Kinodynamic search for the mid-range goal branch: KinodynamicAstar::search + getSamples
+ * (path_searching/src/kinodynamic_astar.cpp:15-263, 543-634) as FastPlannerManager::kinodynamicReplan calls them
+ * (plan_manage/src/planner_manager.cpp:124-164) for n_prob independent problems (start position / velocity /
+ * acceleration, goal position / velocity) in one call: static mode, first with init = true, then -- after NO_PATH --
+ * reset() and one retry with init = false, inside the same launch.  One workgroup per problem.  Per problem:
+ *   0. |start - goal| < 1e-2 (the norm sqrt(x x + y y + z z)): FUELMI_KINO_CLOSE_GOAL, nothing is searched.
+ *   1. The open set is libstdc++'s binary heap of node pointers with the comparator f1 > f2 (push_heap's sift-up,
+ *      pop_heap's hole-to-leaf walk followed by a sift-up), run on keys that may have gone stale: a node that is
+ *      re-parented while it is open has its f and g changed IN PLACE and the heap is NOT repaired, exactly as the
+ *      reference's std::priority_queue of pointers behaves.
+ *   2. Per pop: the terminal tests on the heap's top (reach_horizon: |pos - start| >= horizon; near_end: every index
+ *      difference to the goal's voxel <= tolerance = ceil(1 / resolution); on near_end estimateHeuristic and
+ *      computeShotTraj with its accumulated `time += t_d / 10` checks), then the expansion.  The first expansion of the
+ *      first search uses the `init` primitives (input = start acceleration, tau = k time_res_init init_max_tau summed
+ *      up to init_max_tau + 1e-3), every other one the regular list (ax, ay, az each summed from -max_acc in steps of
+ *      max_acc res up to max_acc + 1e-3, crossed with tau summed in steps of time_res max_tau up to max_tau).  Both
+ *      lists are built on the host with the reference's accumulating loops.
+ *   3. One lane per primitive: stateTransit, isInBox (strict on both sides), the search's own posToIndex (map origin,
+ *      cfg.resolution), the closed test, the velocity limit, the same-voxel test, check_num safety samples (inflated,
+ *      outside the box, unknown unless optimistic), g, estimateHeuristic (quartic / cubic literally, tie_breaker 1 +
+ *      1e-4, the value (1 + tie_breaker) cost), f.  One lane then replays the survivors in the reference's loop order:
+ *      a sibling landing in a voxel a sibling of this expansion created is compared by f (strict <), an older open node
+ *      by g (strict <), a new voxel takes the next pool node and is pushed; use_node_num reaching allocate_num ends the
+ *      search with NO_PATH in the middle of the expansion.
+ *   4. retrievePath, then getSamples literally: T_sum summed from the shot and from the last node back to the first,
+ *      seg_num = max(min_seg, floor(T_sum / ts)) (or cfg.seg_num when > 0), ts = T_sum / seg_num, the accumulated ti
+ *      and t with their -1e-5 carries, the points in reversed order.  derivs = start velocity, end velocity, start
+ *      acceleration, end acceleration (fuelmi_bspline_parameterize's order).  IN THE NO-SHOT BRANCH THE REFERENCE TAKES
+ *      end_vel FROM THE START NODE (its `node` has walked back to the path's first node by then): reproduced.
+ *      The shot's box test compares against the map SIZE (getRegion's second result), not the upper corner: reproduced.
+ *      getKinoTraj is visualisation only and not part of this.
+ * f64 throughout; + - * / sqrt in the reference's order with FMA contraction off, so g, the path's inputs, durations
+ * and (without a shot) T_sum are bit-equal to the reference.  cbrt, acos, cos and pow(t, 3) come from the device's
+ * libm, not glibc: h and f may differ from the reference's in the last bits.
+ * A result does not depend on the problem's place in the batch.
+ * Per-problem status: the reference's enum, FUELMI_KINO_CLOSE_GOAL, or -1 (over max_path_nodes / max_samples).
+ * NO_PATH (both searches failed) and CLOSE_GOAL: n_nodes = n_samples = 0 and every other output of the problem 0,
+ * except which / iter_num / use_node_num of the retry; the call is still FUELMI_OK.
+ * -1: n_nodes / n_samples hold the full counts, the first max_path_nodes / max_samples entries are written, everything
+ * else is complete, the other problems are complete, and the call returns FUELMI_ELIMIT.
+ * Checked on the host before the map is touched (FUELMI_EINVAL): every input finite with |coordinate| < 1e7; every
+ * double parameter finite and > 0; 2e7 / resolution < 2^31 (a voxel index of any admitted coordinate fits an int);
+ * check_num >= 1; allocate_num >= 2; min_seg >= 1; seg_num >= 0; max_path_nodes >= 1;
+ * max_samples >= 1.  FUELMI_ELIMIT, also before any launch: more than FUELMI_KINO_MAX_PRIMS primitives in the init list
+ * or in the regular list; allocate_num > FUELMI_KINO_MAX_ALLOC; n_prob x workspace bytes > FUELMI_KINO_MAX_WORKSPACE.
+ * n_prob = 0 is FUELMI_OK.
+ * Workspace (one grow-only allocation on the map): per problem a node pool of allocate_num 128-byte records, the heap
+ * array, and an open-addressing hash on the voxel triple with at least 2 allocate_num slots, cleared on the stream at
+ * every call.  fuelmi_map_kino_paths runs on the map's stream: host arrays in, host arrays out, synchronous.
+ * ---------------------------------------------------------------------------------------- */
+#define FUELMI_KINO_REACH_HORIZON 1
+#define FUELMI_KINO_REACH_END 2
+#define FUELMI_KINO_NO_PATH 3
+#define FUELMI_KINO_NEAR_END 4
+#define FUELMI_KINO_CLOSE_GOAL 5
+#define FUELMI_KINO_MAX_PRIMS 256                 /* primitives of one expansion */
+#define FUELMI_KINO_MAX_ALLOC (1 << 22)           /* largest allocate_num */
+#define FUELMI_KINO_MAX_SEG (1 << 20)             /* largest seg_num */
+#define FUELMI_KINO_MAX_WORKSPACE 8589934592.0    /* bytes, n_prob x workspace of one problem */
+typedef struct {
+  double max_tau;         /* search/max_tau 0.8 */
+  double init_max_tau;    /* search/init_max_tau 1.0 */
+  double max_vel;         /* search/max_vel + search/vel_margin */
+  double max_acc;         /* search/max_acc */
+  double w_time;          /* search/w_time 10 */
+  double horizon;         /* search/horizon 5 */
+  double resolution;      /* search/resolution_astar */
+  double lambda_heu;      /* search/lambda_heu 10 */
+  double res;             /* 1 / 2.0: input step as a fraction of max_acc */
+  double time_res;        /* 1 / 1.0 */
+  double time_res_init;   /* 1 / 20.0 */
+  double ts;              /* pp_.ctrl_pt_dist / pp_.max_vel_ */
+  int allocate_num;       /* search/allocate_num 100000 */
+  int check_num;          /* search/check_num 10 */
+  int optimistic;         /* search/optimistic */
+  int min_seg;            /* 8 */
+  int seg_num;            /* 0: the reference's rule; > 0: forced */
+  int max_path_nodes;     /* stride / cap of the node arrays */
+  int max_samples;        /* stride / cap of samples */
+} fuelmi_kino_cfg;
+/* start_xyz, start_vel, start_acc, goal_xyz, goal_vel [n_prob][3].  Out, per problem: status; which (0: the first
+ * search answered, 1: the retry); iter_num, use_node_num of the answering search; n_nodes; node_state
+ * [n_prob][max_path_nodes][6], node_input [n_prob][max_path_nodes][3], node_duration [n_prob][max_path_nodes] (each may
+ * be NULL; input and duration of the first node are written as 0, the reference leaves them unset); shot, t_shot,
+ * coef_shot [n_prob][3][4] (axis, power); T_sum; ts_out (the adjusted knot span); seg_num; n_samples; samples
+ * [n_prob][max_samples][3] (entries past n_samples unspecified); derivs [n_prob][4][3]. */
+int fuelmi_map_kino_paths(fuelmi_map* m, const fuelmi_kino_cfg* cfg, int n_prob, const double* start_xyz,
+                          const double* start_vel, const double* start_acc, const double* goal_xyz,
+                          const double* goal_vel, int* status, int* which, int* iter_num, int* use_node_num,
+                          int* n_nodes, double* node_state, double* node_input, double* node_duration, int* shot,
+                          double* t_shot, double* coef_shot, double* T_sum, double* ts_out, int* seg_num,
+                          int* n_samples, double* samples, double* derivs);
+/* The device chain search -> fitted batch, the counterpart of fuelmi_bspline_dev_load_waypoints: one problem per
+ * candidate of `b` (C = the batch's n_traj, inputs [C][3]), seg_num forced to point_num - bspline_degree (cfg->seg_num
+ * must be 0 or that; cfg->max_samples and cfg->max_path_nodes are ignored), ts | points | derivs written into the
+ * batch's staging by the kernel and the spline fit queued behind it on the map's stream.  A candidate whose status
+ * yields no path (NO_PATH, CLOSE_GOAL, -1) keeps the state it had in the batch.  status [C]; T_sum [C] or NULL.  Same
+ * host checks and return values as above; one host wait, for the statuses.  With profiling on, only the fit is counted
+ * under FUELMI_K_BSPLINE; the search kernel belongs to no stage. */
+int fuelmi_bspline_dev_load_kino(fuelmi_bspline_dev* b, const fuelmi_kino_cfg* cfg, const double* start_xyz,
+                                 const double* start_vel, const double* start_acc, const double* goal_xyz,
+                                 const double* goal_vel, int* status, double* T_sum);
+/* what the kernel needs for cfg (host only, no device needed): out8 = {lanes per problem, LDS bytes, workspace bytes per
+ * problem, primitives in the init list, primitives in the regular list, FUELMI_KINO_MAX_PRIMS, FUELMI_KINO_MAX_ALLOC,
+ * hash slots per problem}.  cfg is checked like above. */
+int fuelmi_kino_plan(const fuelmi_kino_cfg* cfg, long long out8[8]);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): HIP events recorded on the map's own stream.
  * ---------------------------------------------------------------------------------------- */
 enum {
