@@ -186,6 +186,7 @@ SYMBOLS = {
     "fuelmi_map_destroy": (None, [_P]),
     "fuelmi_map_get_info": (C.c_int, [_P, C.POINTER(MapInfo)]),
     "fuelmi_map_input_points": (C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, _dp]),
+    "fuelmi_map_insert_plan": (C.c_int, [_ip]),
     "fuelmi_map_input_depth": (C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.POINTER(DepthCfg), _dp, _dp,
                                          C.POINTER(C.c_int)]),
     "fuelmi_host_register": (C.c_int, [C.c_void_p, C.c_size_t]),

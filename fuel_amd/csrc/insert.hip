@@ -148,7 +148,22 @@ __device__ __forceinline__ long pos_adr(const Geo& g, const double p[3]) {
   return (long)id[0] * g.nyz + (long)id[1] * g.nz + id[2];
 }
 
-__global__ void __launch_bounds__(256) k_insert_classify(Geo g, InsertArgs A) {
+#ifndef RC_SPLIT
+#define RC_SPLIT 4  // lanes per ray (k_insert_raycast)
+#endif
+#ifndef RC_SLOTS
+#define RC_SLOTS 64  // point slots per workgroup of k_insert_raycast (256 threads = 64 rays x RC_SPLIT lanes at most)
+#endif
+#ifndef CUBE_XY
+#define CUBE_XY 64  // lines per side of the workgroup's LDS bitmap (x CUBE_Z voxels in z)
+#endif
+#define CUBE_Z 32      // z-neighbours per line of the bitmap: the bits of one LDS word
+#define INS_BLOCK 256  // threads of a workgroup of k_insert_classify (= its point slots) and of k_insert_raycast
+static_assert(CUBE_Z == 8 * sizeof(u32), "one LDS word per line of the cube");
+#define INS_WAVES (INS_BLOCK / 64)  // wavefronts of such a workgroup
+static_assert(RC_SLOTS * RC_SPLIT <= INS_BLOCK && INS_BLOCK % RC_SLOTS == 0, "ray slots of a workgroup");
+static_assert(INS_BLOCK % 64 == 0 && INS_WAVES <= 16, "whole waves, and a slot per wave in the block reductions");
+__global__ void __launch_bounds__(INS_BLOCK) k_insert_classify(Geo g, InsertArgs A) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   double pt[3];
   int flag = 0;
@@ -237,22 +252,13 @@ __device__ __forceinline__ double rc_intbound(double s, double ds) {
   return (1 - s) / ds;
 }
 
-#ifndef RC_SPLIT
-#define RC_SPLIT 4  // lanes per ray (k_insert_raycast)
-#endif
-#ifndef RC_SLOTS
-#define RC_SLOTS 64  // point slots per workgroup of k_insert_raycast (256 threads = 64 rays x RC_SPLIT lanes at most)
-#endif
-#ifndef CUBE_XY
-#define CUBE_XY 64  // lines per side of the workgroup's LDS bitmap (x 32 voxels in z)
-#endif
-__global__ void __launch_bounds__(256) k_insert_raycast(Geo g, InsertArgs A) {
+__global__ void __launch_bounds__(INS_BLOCK) k_insert_raycast(Geo g, InsertArgs A) {
   if (blockIdx.x == 0) {  // fold the per-block boxes of k_insert_classify (all 256 threads: a serial
                           // loop over ~300 records by six threads cost 40 us of dependent loads)
-    __shared__ u64 s_red[4][6];
+    __shared__ u64 s_red[INS_WAVES][6];
     u64 v[6] = {~0ull, ~0ull, ~0ull, 0ull, 0ull, 0ull};
     u64 cnt = 0ull;
-    for (int b = threadIdx.x; b < A.nblk; b += 256) {
+    for (int b = threadIdx.x; b < A.nblk; b += INS_BLOCK) {
       for (int k = 0; k < 6; ++k) {
         const u64 p = A.partial[(size_t)b * 8 + k];
         v[k] = k < 3 ? min(v[k], p) : max(v[k], p);
@@ -260,7 +266,7 @@ __global__ void __launch_bounds__(256) k_insert_raycast(Geo g, InsertArgs A) {
       cnt += A.partial[(size_t)b * 8 + 6];
     }
     for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
-    __shared__ u64 s_cntw[4];
+    __shared__ u64 s_cntw[INS_WAVES];
     if ((threadIdx.x & 63) == 0) s_cntw[threadIdx.x >> 6] = cnt;
     for (int k = 0; k < 6; ++k)
       for (int off = 32; off > 0; off >>= 1) {
@@ -273,10 +279,14 @@ __global__ void __launch_bounds__(256) k_insert_raycast(Geo g, InsertArgs A) {
     if (threadIdx.x < 6) {
       const int k = threadIdx.x;
       u64 r = enc_f64(A.cam[k < 3 ? k : k - 3]);  // update_min = update_max = camera_pos (:265-266)
-      for (int w = 0; w < 4; ++w) r = k < 3 ? min(r, s_red[w][k]) : max(r, s_red[w][k]);
+      for (int w = 0; w < INS_WAVES; ++w) r = k < 3 ? min(r, s_red[w][k]) : max(r, s_red[w][k]);
       A.h_out[k] = r;
     }
-    if (threadIdx.x == 6) A.h_out[6] = s_cntw[0] + s_cntw[1] + s_cntw[2] + s_cntw[3];
+    if (threadIdx.x == 6) {
+      u64 c = 0ull;
+      for (int w = 0; w < INS_WAVES; ++w) c += s_cntw[w];
+      A.h_out[6] = c;
+    }
     // the host is waiting for exactly these eight words (it sizes the next launches by the box): publish them
     // now, the ray walks of this block follow
     __syncthreads();
@@ -284,7 +294,7 @@ __global__ void __launch_bounds__(256) k_insert_raycast(Geo g, InsertArgs A) {
   }
   // Only the first point of every end voxel casts a ray (~1 point in 4): compact the casters of the
   // block into LDS first, so that the walk runs with full waves and the other waves retire at once
-  __shared__ double s_pt[256][3];
+  __shared__ double s_pt[INS_BLOCK][3];  // (RC_SLOTS of them are used)
   __shared__ u32 s_cnt;
   // The rays of a workgroup (neighbouring pixels) form a thin fan that converges on the camera and revisits the
   // same voxels over and over: the miss marks inside a CUBE_XY x CUBE_XY x 32 voxel box laid over the fan (its
@@ -293,7 +303,7 @@ __global__ void __launch_bounds__(256) k_insert_raycast(Geo g, InsertArgs A) {
   // hundred atomics instead of one per ray step.  With the walk split over four lanes per ray the global
   // atomics of the cells outside a small camera-centred cube had become the kernel's bottleneck.
   __shared__ u32 s_seen[CUBE_XY * CUBE_XY];
-  for (int t = threadIdx.x; t < CUBE_XY * CUBE_XY; t += 256) s_seen[t] = 0u;
+  for (int t = threadIdx.x; t < CUBE_XY * CUBE_XY; t += INS_BLOCK) s_seen[t] = 0u;
   if (threadIdx.x == 0) s_cnt = 0u;
   __syncthreads();
   {
@@ -319,8 +329,8 @@ __global__ void __launch_bounds__(256) k_insert_raycast(Geo g, InsertArgs A) {
   int cv[3];  // one LDS word = the 32 z-neighbours cv[2] .. cv[2]+31 of the line (cv[0] + ux, cv[1] + uy)
   for (int k = 0; k < 3; ++k) {
     // the end points of these slots: the box k_insert_classify recorded for its workgroup (256 slots: a superset)
-    const u64* rec = A.partial + (size_t)((blockIdx.x * RC_SLOTS) >> 8) * 8;
-    const int cam_c = (int)floor((A.cam[k] - g.org[k]) * g.res_inv), ext = k < 2 ? CUBE_XY : 32;
+    const u64* rec = A.partial + (size_t)((blockIdx.x * RC_SLOTS) / INS_BLOCK) * 8;
+    const int cam_c = (int)floor((A.cam[k] - g.org[k]) * g.res_inv), ext = k < 2 ? CUBE_XY : CUBE_Z;
     int lo = cam_c, hi = cam_c;
     if (rec[k] <= rec[3 + k]) {  // (an empty record: min = ~0, max = 0)
       lo = min(lo, (int)floor((dec_f64_dev(rec[k]) - g.org[k]) * g.res_inv));
@@ -335,7 +345,7 @@ __global__ void __launch_bounds__(256) k_insert_raycast(Geo g, InsertArgs A) {
   // the state the sequential walk is in when it has consumed every crossing below that parameter -- the walk
   // takes crossings in increasing tMax order (ties z, y, x).  The sequential walk was the longest dependent chain
   // of the fusion (~80 steps x ~350 ns on a lone wave).
-  for (u32 task = threadIdx.x; task < s_cnt * RC_SPLIT; task += 256) {
+  for (u32 task = threadIdx.x; task < s_cnt * RC_SPLIT; task += INS_BLOCK) {
   const u32 ray = task / RC_SPLIT, part = task % RC_SPLIT;
   const double pt[3] = {s_pt[ray][0], s_pt[ray][1], s_pt[ray][2]};
 
@@ -405,7 +415,7 @@ __global__ void __launch_bounds__(256) k_insert_raycast(Geo g, InsertArgs A) {
                                   // [0, N) the reference is undefined behaviour: dropped
     }
     const u32 ux = (u32)(ix - cv[0]), uy = (u32)(iy - cv[1]), uz = (u32)(iz - cv[2]);
-    if (send && (ux | uy) < (u32)CUBE_XY && uz < 32u) {
+    if (send && (ux | uy) < (u32)CUBE_XY && uz < (u32)CUBE_Z) {
       atomicOr(&s_seen[ux * CUBE_XY + uy], 1u << uz);  // flushed as whole words when the block is done
     } else if (raw) {
       atomicOr(&A.miss[av >> 6], 1ull << (av & 63));
@@ -418,7 +428,7 @@ __global__ void __launch_bounds__(256) k_insert_raycast(Geo g, InsertArgs A) {
   // flush the cube: every non-empty LDS word is 32 z-consecutive voxels of one line, i.e. one or two
   // words of the miss plane
   __syncthreads();
-  for (int t = threadIdx.x; t < CUBE_XY * CUBE_XY; t += 256) {
+  for (int t = threadIdx.x; t < CUBE_XY * CUBE_XY; t += INS_BLOCK) {
     const u32 bits = s_seen[t];
     if (!bits) continue;
     const int x = cv[0] + t / CUBE_XY, y = cv[1] + t % CUBE_XY;
@@ -427,7 +437,7 @@ __global__ void __launch_bounds__(256) k_insert_raycast(Geo g, InsertArgs A) {
     const int sh = (int)(a0 & 63);
     const u64 lo = (u64)bits << sh;
     if (lo) atomicOr(&A.miss[w0], lo);
-    if (sh > 32) {
+    if (sh > 64 - CUBE_Z) {
       const u64 hi = (u64)bits >> (64 - sh);
       if (hi) atomicOr(&A.miss[w0 + 1], hi);
     }
@@ -481,7 +491,7 @@ static int insert_points_dev(fuelmi_map* m, const unsigned char* d_pts, int stri
   const signed char num_before = m->raycast_num;
   m->raycast_num = (signed char)(m->raycast_num + 1);  // char wrap like the reference
   {
-    const size_t need = (size_t)((n + 255) / 256) * 8;
+    const size_t need = (size_t)((n + INS_BLOCK - 1) / INS_BLOCK) * 8;
     if (need > m->ins_partial_cap) {
       if (m->ins_partial) HIPCHK(hipFree(m->ins_partial));
       m->ins_partial = nullptr;
@@ -509,7 +519,7 @@ static int insert_points_dev(fuelmi_map* m, const unsigned char* d_pts, int stri
   A.h_out = m->h_ins;
   A.head = m->ins_head;
   A.epoch = ++m->ins_epoch;
-  int nb = (n + 255) / 256;
+  int nb = (n + INS_BLOCK - 1) / INS_BLOCK;
   A.nblk = nb;
   A.partial = m->ins_partial;
   if ((size_t)n > m->ins_rec_cap) {
@@ -520,8 +530,8 @@ static int insert_points_dev(fuelmi_map* m, const unsigned char* d_pts, int stri
     m->ins_rec_cap = (size_t)n + 1024;
   }
   A.rec = reinterpret_cast<InsRec*>(m->ins_rec);
-  k_insert_classify<<<nb, 256, 0, m->stream>>>(g, A);
-  k_insert_raycast<<<(n + RC_SLOTS - 1) / RC_SLOTS, 256, 0, m->stream>>>(g, A);
+  k_insert_classify<<<nb, INS_BLOCK, 0, m->stream>>>(g, A);
+  k_insert_raycast<<<(n + RC_SLOTS - 1) / RC_SLOTS, INS_BLOCK, 0, m->stream>>>(g, A);
   HIPCHK(hipGetLastError());
   // the end-point box sizes the next launches: poll the stamp the fusion's second kernel writes into pinned memory
   // (a blocking stream synchronisation costs ~40 us of wake-up latency per frame)
@@ -866,6 +876,14 @@ extern "C" int fuelmi_hbm_expand(int device, size_t bytes_in, int reps, double* 
 }
 extern "C" int fuelmi_device_free(void* ptr) {
   if (ptr) HIPCHK(hipFree(ptr));
+  return FUELMI_OK;
+}
+
+/* the geometry the fusion kernels above are compiled with (host only) */
+extern "C" int fuelmi_map_insert_plan(int out[8]) {
+  ARGCHK(out);
+  const int v[8] = {RC_SPLIT, RC_SLOTS, INS_BLOCK, CUBE_XY, CUBE_XY, CUBE_Z, 0, 0};
+  for (int k = 0; k < 8; ++k) out[k] = v[k];
   return FUELMI_OK;
 }
 

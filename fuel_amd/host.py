@@ -162,6 +162,14 @@ class SDFMap:
             launches.append({"kernel": name, "grid": grid, "block": block, "lds": lds, "ZC": zc, "nzc": nzc, "z0a": z0a})
         return {"family": out[1], "launches": launches}
 
+    @staticmethod
+    def insertPlan():
+        """The geometry the fusion kernels are compiled with (fuelmi_map_insert_plan, host only): lanes that share a ray
+        walk, point slots per ray-walk and per classify workgroup, voxel extents of a ray workgroup's LDS miss cube."""
+        out = (C.c_int * 8)()
+        check(lib().fuelmi_map_insert_plan(out))
+        return {"lanes_per_ray": out[0], "ray_slots": out[1], "classify_slots": out[2], "cube": (out[3], out[4], out[5])}
+
     def lastInflateKernel(self):
         """0: the fused inflation kernel ran in the last clearAndInflateLocalMap, 1: the factored pair"""
         return self.L.fuelmi_map_last_inflate_kernel(self.h)

@@ -109,6 +109,11 @@ int fuelmi_map_get_info(const fuelmi_map* m, fuelmi_map_info* info);
  * each stride_bytes record (12 for packed, 16 for pcl::PointXYZ); host memory. */
 int fuelmi_map_input_points(fuelmi_map* m, const float* xyz, int stride_bytes, int n,
                             const double camera_pos[3]);
+/* The geometry the fusion kernels are compiled with (host only, no device needed): out[0] = lanes that share one ray
+ * walk, out[1] = point slots per workgroup of the ray-walk kernel, out[2] = point slots per workgroup of the classify
+ * kernel (whose end-point box places the miss cube of the ray workgroups inside it), out[3..5] = x, y, z extent in
+ * voxels of the miss cube a ray workgroup collects in LDS, out[6..7] = 0.  For tests that aim at these edges. */
+int fuelmi_map_insert_plan(int out[8]);
 /* Depth-image front end of the fusion: MapROS::proessDepthImage (plan_env/src/map_ros.cpp:176-215) and
  * the part of MapROS::depthPoseCallback (:121-150) around it.  Parameters are the map_ros/... ROS
  * parameters of the same names (map_ros.cpp:22-30). */
