@@ -138,6 +138,16 @@ class YawCfg(C.Structure):
 YAW_EXPLORE, YAW_FOLLOW = 0, 1
 YAW_OK, YAW_DEGENERATE = 0, 1
 YAW_MAX_SEG, YAW_MAX_CTRL = 256, 1024
+
+
+class TrajChkCfg(C.Structure):
+    """fuelmi_trajchk_cfg: checkTrajCollision's two literals, the spline's degree and the stride of the control points."""
+    _fields_ = [("degree", C.c_int), ("max_ctrl", C.c_int), ("step", C.c_double), ("max_radius", C.c_double)]
+
+
+TRAJCHK_OK, TRAJCHK_NONFINITE = 0, 1
+TRAJCHK_END_HIT, TRAJCHK_END_RADIUS, TRAJCHK_END_DURATION, TRAJCHK_END_CAP, TRAJCHK_END_NONFINITE = range(5)
+TRAJCHK_MAX_CTRL, TRAJCHK_MAX_SAMPLES = 1024, 1 << 20
 REFINE_LAST_ARGMIN = 1
 REFINE_MAX_LAYERS, REFINE_MAX_NODES = 64, 256
 
@@ -271,6 +281,10 @@ SYMBOLS = {
     "fuelmi_bspline_dev_plan_yaws": (C.c_int, [_P, C.POINTER(YawCfg), _dp, _dp, _ip, _dp, _ip, _dp, _dp, _ip, _dp, _dp,
                                                _dp, _dp, _dp]),
     "fuelmi_yaw_plan": (C.c_int, [C.POINTER(YawCfg), _ip]),
+    "fuelmi_map_check_trajs": (C.c_int, [_P, C.POINTER(TrajChkCfg), C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _dp, _ip, _ip, _dp,
+                                         _dp, _ip, _dp]),
+    "fuelmi_bspline_dev_check_trajs": (C.c_int, [_P, C.POINTER(TrajChkCfg), _dp, _ip, _ip, _dp, _ip, _ip, _dp, _dp, _ip, _dp]),
+    "fuelmi_traj_check_plan": (C.c_int, [C.POINTER(TrajChkCfg), _ip]),
     "fuelmi_tsp_create": (C.c_int, [C.c_int, C.POINTER(TspCfg), _PP]),
     "fuelmi_tsp_destroy": (None, [_P]),
     "fuelmi_tsp_solve": (C.c_int, [_P, C.c_int, _ip, C.POINTER(C.c_int32), _ip, C.POINTER(C.c_int64), _ip]),

@@ -49,6 +49,8 @@ struct fuelmi_bspline_dev {
   bool opt_valid = false;    // opt_x holds the solve of what the batch holds now (a reload clears it)
   unsigned char* yaw_dev = nullptr;  // fuelmi_bspline_dev_plan_yaws: start | end | results (grow-only)
   size_t yaw_cap = 0;
+  unsigned char* chk_dev = nullptr;  // fuelmi_bspline_dev_check_trajs: t_now | results (grow-only)
+  size_t chk_cap = 0;
 };
 
 // 64-lane sum on the DPP data path (no LDS crossbar round trips): quads, half rows, rows, then the two
@@ -1749,4 +1751,63 @@ extern "C" int fuelmi_bspline_dev_plan_yaws(fuelmi_bspline_dev* b, const fuelmi_
   yaw_out_bytes(&yc, A.C, H, host.data(), yawdot_ctrl != nullptr, yawddot_ctrl != nullptr);
   return yaw_copy_out(&yc, A.C, H, status, duration, seg_num, dt_yaw, yaw_ctrl, n_waypt, waypts, end_yaw_out, cost,
                       yawdot_ctrl, yawddot_ctrl);
+}
+
+// the safety check of the batch's optimised position splines (k_traj_check, traj_check.hip) read from the variables the
+// last solve left on the device, against the batch's map; only the results travel
+extern "C" int fuelmi_bspline_dev_check_trajs(fuelmi_bspline_dev* b, const fuelmi_trajchk_cfg* cfg, const double* t_now,
+                                              int* status, int* safe, double* distance, int* n_samples, int* hit_index,
+                                              double* hit_t, double* hit_pos, int* end_reason, double* duration) {
+  ARGCHK(b && cfg);
+  const BsplineArgs& A = b->a;
+  ARGCHK(A.dim == 3 && b->opt_valid && b->opt_x);
+  ARGCHK(cfg->degree == A.cfg.bspline_degree);
+  fuelmi_trajchk_cfg tc = *cfg;
+  tc.max_ctrl = A.N;
+  {
+    const int rc = trajchk_check(&tc, A.C, nullptr, nullptr, nullptr, t_now);
+    if (rc) return rc;
+  }
+  ARGCHK(status && safe && distance && n_samples && hit_index && hit_t && hit_pos && end_reason && duration);
+  fuelmi_map* m = b->map;
+  ARGCHK(m);
+  HIPCHK(hipSetDevice(m->device));
+  const size_t C = (size_t)A.C;
+  auto pad = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  const size_t b_dbl = pad(C * sizeof(double));
+  TrajChkArgs T;
+  memset(&T, 0, sizeof(T));
+  const size_t b_out = trajchk_out_bytes(A.C, T, nullptr);
+  if (b_dbl + b_out > b->chk_cap) {
+    void* d = nullptr;
+    HIPCHK(hipMalloc(&d, b_dbl + b_out));
+    b->allocs.push_back(d);
+    b->chk_dev = static_cast<unsigned char*>(d);
+    b->chk_cap = b_dbl + b_out;
+  }
+  hipStream_t st = m->stream;
+  double* d_now = reinterpret_cast<double*>(b->chk_dev);
+  unsigned char* d_out = b->chk_dev + b_dbl;
+  HIPCHK(hipMemcpyAsync(d_now, t_now, C * sizeof(double), hipMemcpyHostToDevice, st));
+  T.cfg = tc;
+  T.n_prob = A.C;
+  T.n_ctrl = nullptr, T.n_ctrl_all = A.N;
+  T.pos = b->opt_x, T.pos_stride = (size_t)A.nvar;
+  if (A.cost_function & FUELMI_COST_MINTIME)
+    T.knot = b->opt_x + (A.nvar - 1), T.knot_stride = (size_t)A.nvar;
+  else
+    T.knot = A.knot_span, T.knot_stride = 1;
+  T.t_now = d_now;
+  T.infl = m->infl_bits.p;
+  trajchk_out_bytes(A.C, T, d_out);
+  {
+    const int rc = trajchk_launch(st, m->g, T);
+    if (rc) return rc;
+  }
+  std::vector<unsigned char> host(b_out);
+  HIPCHK(hipMemcpyAsync(host.data(), d_out, b_out, hipMemcpyDeviceToHost, st));
+  HIPCHK(stream_wait(st));
+  TrajChkArgs H = T;
+  trajchk_out_bytes(A.C, H, host.data());
+  return trajchk_copy_out(A.C, H, status, safe, distance, n_samples, hit_index, hit_t, hit_pos, end_reason, duration);
 }

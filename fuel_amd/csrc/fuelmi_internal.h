@@ -228,6 +228,9 @@ struct fuelmi_map {
   void* kino_dev = nullptr;
   size_t kino_dev_bytes = 0;
   std::vector<double> kino_host;  // the inputs and primitive lists of the last call, alive until its copies have run
+  // grow-only device scratch of fuelmi_map_check_trajs (traj_check.hip): problems in, results out
+  void* trajchk_dev = nullptr;
+  size_t trajchk_dev_bytes = 0;
   unsigned long long fusion_count = 0;  // fusions / uploads queued so far (a search notices one queued behind its back)
   unsigned profile_mask = 0;
   ProfileSlot prof[FUELMI_K_COUNT];
@@ -567,6 +570,38 @@ int yaw_launch(hipStream_t st, const YawArgs& Y);
 int yaw_copy_out(const fuelmi_yaw_cfg* cfg, int n_prob, const YawArgs& H, int* status, double* duration, int* seg_num,
                  double* dt_yaw, double* yaw_ctrl, int* n_waypt, double* waypts, double* end_yaw_out, double* cost,
                  double* yawdot_ctrl, double* yawddot_ctrl);
+// k_traj_check (traj_check.hip): one problem per wave; every pointer addresses device memory
+struct TrajChkArgs {
+  fuelmi_trajchk_cfg cfg;
+  int n_prob;
+  const int* n_ctrl;        // [n], or null: every problem has n_ctrl_all control points
+  int n_ctrl_all;
+  const double* pos;        // problem b: [n_ctrl][3] at pos + b * pos_stride
+  size_t pos_stride;
+  const double* knot;       // problem b: knot[b * knot_stride]
+  size_t knot_stride;
+  const double* t_now;      // [n]
+  const u64* infl;          // the map's inflated plane
+  int* status;
+  int* safe;
+  int* n_samples;
+  int* hit_index;
+  int* end_reason;
+  double* distance;
+  double* hit_t;
+  double* duration;
+  double* hit_pos;          // [n][3]
+};
+// the host checks of fuelmi_map_check_trajs / fuelmi_bspline_dev_check_trajs (n_ctrl null: a device batch, whose control
+// points and knot spans the host does not see); the result block's layout (base null: only its size); the launch on
+// stream st; the result block -> the caller's arrays (FUELMI_ELIMIT when a problem's status is -1)
+int trajchk_check(const fuelmi_trajchk_cfg* cfg, int n_prob, const int* n_ctrl, const double* pos_ctrl,
+                  const double* knot_span, const double* t_now);
+size_t trajchk_out_bytes(int n_prob, TrajChkArgs& T, unsigned char* base);
+int trajchk_launch(hipStream_t st, const Geo& g, const TrajChkArgs& T);
+int trajchk_copy_out(int n_prob, const TrajChkArgs& H, int* status, int* safe, double* distance, int* n_samples,
+                     int* hit_index, double* hit_t, double* hit_pos, int* end_reason, double* duration);
+void traj_check_release(fuelmi_map* m);  // the map's trajectory-check scratch
 // k_kino_path (kino_path.hip): one problem per workgroup; every pointer addresses device memory
 struct KinoArgs {
   fuelmi_kino_cfg cfg;

@@ -1,0 +1,314 @@
+// traj_check.hip -- the safety check of a flown trajectory: FastPlannerManager::checkTrajCollision
+// (plan_manage/src/planner_manager.cpp:96-118) for a batch of problems (position control points, knot span, t_now)
+// against the map's inflated plane, without a host mirror.
+//
+// The reference's loop only looks sequential.  For sample k = 1, 2, ... the time t_now + fut_t_k (fut_t summed k times),
+// the point p_k, its inflated occupancy and the radius r_k = |p_k - cur| depend on k alone.  The loop enters body k iff
+// r_(k-1) < max_radius && t_now + fut_t_k < duration held for every sample up to k (r_0 = 0), so it ends before the FIRST
+// k where that fails, and the answer is the first occupied k in front of that end with distance = r_(k-1).
+//
+// One 64-lane wave per problem, TC_WAVES problems per workgroup.  The lanes take a window of 64 consecutive samples:
+// each lane repeats the window's additions of `step` up to its own sample (lane 63's value plus one addition is the next
+// window's base), evaluates its point by the literal de Boor recursion, reads its bit and takes r_(k-1) from the lane
+// below (lane 0: lane 63 of the previous window).  Three ballots and a count of trailing zeros pick the first event.
+// Knots are staged in LDS by the accumulated additions (one block per wave); control points are read from global memory
+// through L2: a window touches p + 1 neighbouring points per lane, 24 B each, and neighbouring lanes share them, so
+// staging up to 24 KiB per problem would cost more than it saves.  All f64, -ffp-contract=off.  A result does not depend
+// on the problem's place in the batch: the only workgroup-wide step is the barrier behind the knots.
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "frontier_internal.h"
+#include "spline_internal.h"
+
+namespace {
+
+constexpr int TC_WIN = 64;   // samples per window: one per lane
+constexpr int TC_WAVES = 4;  // problems per workgroup
+constexpr int TC_CAP = FUELMI_TRAJCHK_MAX_SAMPLES;
+
+// doubles of one wave's knot block: n + p + 1 <= max_ctrl + 6 knots, kept a multiple of 16 bytes
+__host__ __device__ inline int tc_knot_stride(int max_ctrl) { return (max_ctrl + 6 + 1) & ~1; }
+
+// not finite, or |coordinate| >= 1e7: the reference's cast to int is undefined there
+__device__ __forceinline__ bool tc_bad(const double q[3]) {
+  return !(fabs(q[0]) < 1e7 && fabs(q[1]) < 1e7 && fabs(q[2]) < 1e7);
+}
+
+// SDFMap::getInflateOccupancy(Vector3d) == 1: posToIndex's floor, isInMap(Vector3i) (outside: -1, which passes), the
+// inflated plane's bit.  The range test is made on the floor's f64 result -- the same answer as pos_to_idx + idx_in_map
+// for every value an int holds, and no cast of one it does not hold (fine maps: 1e7 * resolution_inv may pass 2^31)
+__device__ __forceinline__ bool tc_inflated(const Geo& g, const u64* infl, const double q[3]) {
+  const double fx = floor((q[0] - g.org[0]) * g.res_inv), fy = floor((q[1] - g.org[1]) * g.res_inv),
+               fz = floor((q[2] - g.org[2]) * g.res_inv);
+  if (!(fx >= 0.0 && fy >= 0.0 && fz >= 0.0 && fx <= (double)(g.nx - 1) && fy <= (double)(g.ny - 1) &&
+        fz <= (double)(g.nz - 1)))
+    return false;
+  const long a = (long)(int)fx * g.nyz + (long)(int)fy * g.nz + (int)fz;
+  return bit_at(infl, a);
+}
+
+// everything a problem reports, by the one lane that knows it
+__device__ void tc_write(const TrajChkArgs& T, int b, int status, int safe, double distance, int n_samples, int hit_index,
+                         double hit_t, const double* hit_pos, int end_reason, double duration) {
+  T.status[b] = status;
+  T.safe[b] = safe;
+  T.distance[b] = distance;
+  T.n_samples[b] = n_samples;
+  T.hit_index[b] = hit_index;
+  T.hit_t[b] = hit_t;
+  for (int c = 0; c < 3; ++c) T.hit_pos[3 * b + c] = hit_pos ? hit_pos[c] : 0.0;
+  T.end_reason[b] = end_reason;
+  T.duration[b] = duration;
+}
+
+__global__ void __launch_bounds__(TC_WIN * TC_WAVES) k_traj_check(Geo g, TrajChkArgs T) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int lane = threadIdx.x & (TC_WIN - 1), wv = threadIdx.x >> 6;
+  const int b = blockIdx.x * TC_WAVES + wv;
+  double* u = reinterpret_cast<double*>(smem_raw) + (size_t)wv * tc_knot_stride(T.cfg.max_ctrl);  // [n + p + 1]
+  const int p = T.cfg.degree;
+  const bool live = b < T.n_prob;
+  int n = 0;
+  double dt = 0.0;
+  if (live) {
+    n = T.n_ctrl ? T.n_ctrl[b] : T.n_ctrl_all;
+    dt = T.knot[(size_t)b * T.knot_stride];
+  }
+  // (the host route refuses these before any launch; the variables of a device batch are not seen by the host)
+  const bool sane = live && dt > 0.0 && isfinite(dt) && n >= p + 1 && n <= T.cfg.max_ctrl;
+
+  // 1. knots (setUniformBspline :25-31); every wave of the workgroup meets at the barrier, with or without a problem
+  if (sane && lane == 0) {
+    for (int i = 0; i <= p; ++i) u[i] = (double)(i - p) * dt;
+    double acc = u[p];
+    for (int i = p + 1; i <= n + p; ++i) {
+      acc = acc + dt;
+      u[i] = acc;
+    }
+  }
+  __syncthreads();
+  if (!live) return;
+  if (!sane) {
+    if (lane == 0)
+      tc_write(T, b, FUELMI_TRAJCHK_NONFINITE, 0, 0.0, 0, 0, 0.0, nullptr, FUELMI_TRAJCHK_END_NONFINITE, 0.0);
+    return;
+  }
+  const double* C = T.pos + (size_t)b * T.pos_stride;
+  const double t_now = T.t_now[b], step = T.cfg.step, max_radius = T.cfg.max_radius;
+  const double duration = u[n] - u[p];
+
+  // 2. cur
+  double cur[3];
+  spline_pos(u, p, n, C, t_now, cur);
+  if (tc_bad(cur)) {
+    if (lane == 0)
+      tc_write(T, b, FUELMI_TRAJCHK_NONFINITE, 0, 0.0, 0, 0, t_now, nullptr, FUELMI_TRAJCHK_END_NONFINITE, duration);
+    return;
+  }
+
+  // 3. windows of TC_WIN samples; r_carry = r of the sample in front of the window, fut_base = fut_t of its first sample
+  double r_carry = 0.0, fut_base = step;
+  for (int kb = 1;; kb += TC_WIN) {
+    double acc = fut_base, fut = fut_base;
+    for (int j = 0; j < TC_WIN; ++j) {  // fut_t of sample kb + lane: the base plus `lane` additions, one at a time
+      if (j == lane) fut = acc;
+      acc = acc + step;
+    }
+    const int k = kb + lane;
+    const double t = t_now + fut;
+    double q[3];
+    spline_pos(u, p, n, C, t, q);
+    const bool bad = tc_bad(q);
+    const double dx = q[0] - cur[0], dy = q[1] - cur[1], dz = q[2] - cur[2];
+    const double r = sqrt(dx * dx + dy * dy + dz * dz);
+    double r_prev = __shfl_up(r, 1);
+    if (lane == 0) r_prev = r_carry;
+    const bool end = !(r_prev < max_radius) || !(t < duration);  // the while condition fails in front of body k
+    const bool over = k > TC_CAP;                                // body k would be one too many
+    const bool hit = !bad && tc_inflated(g, T.infl, q);
+    const unsigned long long m_end = __ballot(end), m_stop = __ballot(bad || over), m_hit = __ballot(hit);
+    const unsigned long long m = m_end | m_stop | m_hit;
+    if (m) {
+      if (lane == __builtin_ctzll(m)) {  // the first sample with an event; on one sample: end, cap, bad point, hit
+        if (end)
+          tc_write(T, b, FUELMI_TRAJCHK_OK, 1, -1.0, k - 1, 0, 0.0, nullptr,
+                   !(r_prev < max_radius) ? FUELMI_TRAJCHK_END_RADIUS : FUELMI_TRAJCHK_END_DURATION, duration);
+        else if (over)
+          tc_write(T, b, -1, 0, r_prev, TC_CAP, 0, 0.0, nullptr, FUELMI_TRAJCHK_END_CAP, duration);
+        else if (bad)
+          tc_write(T, b, FUELMI_TRAJCHK_NONFINITE, 0, 0.0, k, k, t, nullptr, FUELMI_TRAJCHK_END_NONFINITE, duration);
+        else
+          tc_write(T, b, FUELMI_TRAJCHK_OK, 0, r_prev, k, k, t, q, FUELMI_TRAJCHK_END_HIT, duration);
+      }
+      return;
+    }
+    r_carry = __shfl(r, TC_WIN - 1);
+    fut_base = acc;
+  }
+}
+
+size_t tc_lds(int max_ctrl) { return (size_t)TC_WAVES * tc_knot_stride(max_ctrl) * sizeof(double); }
+
+int trajchk_cfg_check(const fuelmi_trajchk_cfg* cfg) {
+  ARGCHK(cfg);
+  ARGCHK(cfg->degree >= 3 && cfg->degree <= 5);
+  ARGCHK(cfg->max_ctrl >= cfg->degree + 1);
+  ARGCHK(std::isfinite(cfg->step) && cfg->step >= 1e-3);
+  ARGCHK(std::isfinite(cfg->max_radius) && cfg->max_radius > 0.0);
+  if (cfg->max_ctrl > FUELMI_TRAJCHK_MAX_CTRL) {
+    fuelmi_set_error("trajectory check: max_ctrl = %d exceeds %d", cfg->max_ctrl, FUELMI_TRAJCHK_MAX_CTRL);
+    return FUELMI_ELIMIT;
+  }
+  return FUELMI_OK;
+}
+
+}  // namespace
+
+int trajchk_check(const fuelmi_trajchk_cfg* cfg, int n_prob, const int* n_ctrl, const double* pos_ctrl,
+                  const double* knot_span, const double* t_now) {
+  {
+    const int rc = trajchk_cfg_check(cfg);
+    if (rc) return rc;
+  }
+  ARGCHK(n_prob >= 0);
+  if (n_prob == 0) return FUELMI_OK;
+  ARGCHK(t_now);
+  for (int b = 0; b < n_prob; ++b) ARGCHK(std::isfinite(t_now[b]));
+  if (!n_ctrl) return FUELMI_OK;  // a device batch: its variables are checked by the kernel
+  ARGCHK(pos_ctrl && knot_span);
+  for (int b = 0; b < n_prob; ++b) {
+    ARGCHK(n_ctrl[b] >= cfg->degree + 1 && n_ctrl[b] <= cfg->max_ctrl);
+    ARGCHK(std::isfinite(knot_span[b]) && knot_span[b] > 0.0);
+    const double* P = pos_ctrl + (size_t)b * cfg->max_ctrl * 3;
+    for (int k = 0; k < 3 * n_ctrl[b]; ++k) ARGCHK(std::fabs(P[k]) < 1e7);
+  }
+  return FUELMI_OK;
+}
+
+size_t trajchk_out_bytes(int n_prob, TrajChkArgs& T, unsigned char* base) {
+  const size_t n = (size_t)n_prob;
+  auto pad = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  size_t at = 0;
+  auto take = [&](size_t bytes) {
+    unsigned char* p = base ? base + at : nullptr;
+    at += pad(bytes);
+    return p;
+  };
+  T.status = reinterpret_cast<int*>(take(n * sizeof(int)));
+  T.safe = reinterpret_cast<int*>(take(n * sizeof(int)));
+  T.n_samples = reinterpret_cast<int*>(take(n * sizeof(int)));
+  T.hit_index = reinterpret_cast<int*>(take(n * sizeof(int)));
+  T.end_reason = reinterpret_cast<int*>(take(n * sizeof(int)));
+  T.distance = reinterpret_cast<double*>(take(n * sizeof(double)));
+  T.hit_t = reinterpret_cast<double*>(take(n * sizeof(double)));
+  T.duration = reinterpret_cast<double*>(take(n * sizeof(double)));
+  T.hit_pos = reinterpret_cast<double*>(take(n * 3 * sizeof(double)));
+  return at;
+}
+
+int trajchk_copy_out(int n_prob, const TrajChkArgs& H, int* status, int* safe, double* distance, int* n_samples,
+                     int* hit_index, double* hit_t, double* hit_pos, int* end_reason, double* duration) {
+  const size_t n = (size_t)n_prob;
+  memcpy(status, H.status, n * sizeof(int));
+  memcpy(safe, H.safe, n * sizeof(int));
+  memcpy(n_samples, H.n_samples, n * sizeof(int));
+  memcpy(hit_index, H.hit_index, n * sizeof(int));
+  memcpy(end_reason, H.end_reason, n * sizeof(int));
+  memcpy(distance, H.distance, n * sizeof(double));
+  memcpy(hit_t, H.hit_t, n * sizeof(double));
+  memcpy(duration, H.duration, n * sizeof(double));
+  memcpy(hit_pos, H.hit_pos, n * 3 * sizeof(double));
+  for (int b = 0; b < n_prob; ++b)
+    if (status[b] == -1) {
+      fuelmi_set_error("trajectory check: problem %d needs more than %d samples", b, FUELMI_TRAJCHK_MAX_SAMPLES);
+      return FUELMI_ELIMIT;
+    }
+  return FUELMI_OK;
+}
+
+int trajchk_launch(hipStream_t st, const Geo& g, const TrajChkArgs& T) {
+  const size_t lds = tc_lds(T.cfg.max_ctrl);  // <= 32.2 KiB at FUELMI_TRAJCHK_MAX_CTRL
+  hipLaunchKernelGGL(k_traj_check, dim3((T.n_prob + TC_WAVES - 1) / TC_WAVES), dim3(TC_WIN * TC_WAVES), lds, st, g, T);
+  HIPCHK(hipGetLastError());
+  return FUELMI_OK;
+}
+
+void traj_check_release(fuelmi_map* m) {
+  if (m->trajchk_dev) (void)hipFree(m->trajchk_dev);
+  m->trajchk_dev = nullptr;
+  m->trajchk_dev_bytes = 0;
+}
+
+extern "C" int fuelmi_traj_check_plan(const fuelmi_trajchk_cfg* cfg, int out3[3]) {
+  ARGCHK(out3);
+  {
+    const int rc = trajchk_cfg_check(cfg);
+    if (rc) return rc;
+  }
+  out3[0] = TC_WIN, out3[1] = (int)tc_lds(cfg->max_ctrl), out3[2] = FUELMI_TRAJCHK_MAX_CTRL;
+  return FUELMI_OK;
+}
+
+extern "C" int fuelmi_map_check_trajs(fuelmi_map* m, const fuelmi_trajchk_cfg* cfg, int n_prob, const int* n_ctrl,
+                                      const double* pos_ctrl, const double* knot_span, const double* t_now, int* status,
+                                      int* safe, double* distance, int* n_samples, int* hit_index, double* hit_t,
+                                      double* hit_pos, int* end_reason, double* duration) {
+  {  // every argument on the host, before the map is touched
+    ARGCHK(n_prob <= 0 || n_ctrl);
+    const int rc = trajchk_check(cfg, n_prob, n_ctrl, pos_ctrl, knot_span, t_now);
+    if (rc) return rc;
+  }
+  if (n_prob == 0) return FUELMI_OK;
+  ARGCHK(status && safe && distance && n_samples && hit_index && hit_t && hit_pos && end_reason && duration);
+  ARGCHK(m);
+  HIPCHK(hipSetDevice(m->device));
+  hipStream_t st = m->stream;
+  const size_t n = (size_t)n_prob, maxc = (size_t)cfg->max_ctrl;
+  auto pad = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  const size_t b_int = pad(n * sizeof(int)), b_dbl = pad(n * sizeof(double)), b_pos = pad(n * maxc * 3 * sizeof(double));
+  TrajChkArgs T;
+  memset(&T, 0, sizeof(T));
+  const size_t b_out = trajchk_out_bytes(n_prob, T, nullptr);
+  const size_t need = b_int + 2 * b_dbl + b_pos + b_out;
+  if (need > m->trajchk_dev_bytes) {
+    HIPCHK(hipStreamSynchronize(st));
+    traj_check_release(m);
+    HIPCHK(hipMalloc(&m->trajchk_dev, need));
+    m->trajchk_dev_bytes = need;
+  }
+  unsigned char* at = static_cast<unsigned char*>(m->trajchk_dev);
+  auto take = [&](size_t bytes) {
+    unsigned char* p = at;
+    at += bytes;
+    return p;
+  };
+  int* d_nc = reinterpret_cast<int*>(take(b_int));
+  double* d_knot = reinterpret_cast<double*>(take(b_dbl));
+  double* d_now = reinterpret_cast<double*>(take(b_dbl));
+  double* d_pos = reinterpret_cast<double*>(take(b_pos));
+  unsigned char* d_out = take(b_out);
+  HIPCHK(hipMemcpyAsync(d_nc, n_ctrl, n * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_knot, knot_span, n * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_now, t_now, n * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_pos, pos_ctrl, n * maxc * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  T.cfg = *cfg;
+  T.n_prob = n_prob;
+  T.n_ctrl = d_nc, T.n_ctrl_all = 0;
+  T.pos = d_pos, T.pos_stride = maxc * 3;
+  T.knot = d_knot, T.knot_stride = 1;
+  T.t_now = d_now;
+  T.infl = m->infl_bits.p;
+  trajchk_out_bytes(n_prob, T, d_out);
+  {
+    const int rc = trajchk_launch(st, m->g, T);
+    if (rc) return rc;
+  }
+  std::vector<unsigned char> host(b_out);
+  HIPCHK(hipMemcpyAsync(host.data(), d_out, b_out, hipMemcpyDeviceToHost, st));
+  HIPCHK(stream_wait(st));
+  TrajChkArgs H = T;
+  trajchk_out_bytes(n_prob, H, host.data());
+  return trajchk_copy_out(n_prob, H, status, safe, distance, n_samples, hit_index, hit_t, hit_pos, end_reason, duration);
+}

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "fuelmi_internal.h"
+#include "spline_internal.h"
 
 namespace {
 
@@ -45,40 +46,6 @@ __device__ __forceinline__ double yp_next_yaw(double last_yaw, double yaw) {
   return yaw;  // diff is not a number: the reference leaves yaw as it is
 }
 
-// NonUniformBspline::evaluateDeBoorT (non_uniform_bspline.cpp:51-75) of a spline of degree P with n control points and
-// the knots u[0 .. n + P]; ctrl(i, d) fetches control point i
-template <int P, class F>
-__device__ __forceinline__ void yp_deboor(const double* u, int n, double t, F ctrl, double out[3]) {
-  const double lo = u[P], v = t + u[P], hi = u[n];
-  double ub = lo < v ? v : lo;  // min(max(u_(p_), u), u_(m_ - p_))
-  ub = hi < ub ? hi : ub;
-  int k = P;
-  while (k < n - 1 && u[k + 1] < ub) ++k;  // (k < n - 1 holds by the clamp; it keeps a bad spline inside its arrays)
-  double d[P + 1][3];
-#pragma unroll
-  for (int i = 0; i <= P; ++i) ctrl(k - P + i, d[i]);
-#pragma unroll
-  for (int r = 1; r <= P; ++r)
-#pragma unroll
-    for (int i = P; i >= r; --i) {
-      const double alpha = (ub - u[i + k - P]) / (u[i + 1 + k - r] - u[i + k - P]);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) d[i][c] = (1 - alpha) * d[i - 1][c] + alpha * d[i][c];
-    }
-  out[0] = d[P][0], out[1] = d[P][1], out[2] = d[P][2];
-}
-
-// the position spline at time t
-__device__ __forceinline__ void yp_pos(const double* u, int p, int n, const double* C, double t, double out[3]) {
-  auto ctrl = [C](int i, double d[3]) { d[0] = C[3 * i], d[1] = C[3 * i + 1], d[2] = C[3 * i + 2]; };
-  if (p == 3)
-    yp_deboor<3>(u, n, t, ctrl, out);
-  else if (p == 4)
-    yp_deboor<4>(u, n, t, ctrl, out);
-  else
-    yp_deboor<5>(u, n, t, ctrl, out);
-}
-
 // its derivative (getDerivative :77-106) at time t: control points p (P[i+1] - P[i]) / (u[i+p+1] - u[i+1]), the knots
 // without the first and the last, degree p - 1
 __device__ __forceinline__ void yp_vel(const double* u, int p, int n, const double* C, double t, double out[3]) {
@@ -87,11 +54,11 @@ __device__ __forceinline__ void yp_vel(const double* u, int p, int n, const doub
     for (int c = 0; c < 3; ++c) d[c] = (double)p * (C[3 * (i + 1) + c] - C[3 * i + c]) / den;
   };
   if (p == 3)
-    yp_deboor<2>(u + 1, n - 1, t, ctrl, out);
+    spline_deboor<2>(u + 1, n - 1, t, ctrl, out);
   else if (p == 4)
-    yp_deboor<3>(u + 1, n - 1, t, ctrl, out);
+    spline_deboor<3>(u + 1, n - 1, t, ctrl, out);
   else
-    yp_deboor<4>(u + 1, n - 1, t, ctrl, out);
+    spline_deboor<4>(u + 1, n - 1, t, ctrl, out);
 }
 
 __device__ __forceinline__ double yp_J(int k) { return k == 0 ? -1.0 : k == 1 ? 3.0 : k == 2 ? -3.0 : 1.0; }
@@ -206,8 +173,8 @@ __global__ void __launch_bounds__(YP_NT) k_yaw_plan(YawArgs Y) {
     const double ts = tc + Y.cfg.forward_t;
     const double tf = ts < duration ? ts : duration;
     double pc[3], pf[3];
-    yp_pos(u, p, n, C, tc, pc);
-    yp_pos(u, p, n, C, tf, pf);
+    spline_pos(u, p, n, C, tc, pc);
+    spline_pos(u, p, n, C, tf, pf);
     const double x = pf[0] - pc[0], y = pf[1] - pc[1], z = pf[2] - pc[2];
     const bool far = sqrt(x * x + y * y + z * z) > 1e-6;
     ok[j] = far ? 1 : 0;

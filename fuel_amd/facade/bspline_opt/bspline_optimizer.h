@@ -99,6 +99,14 @@ public:
   int planYaw(const Eigen::MatrixXd& pos_ctrl, int pos_degree, double pos_dt, const Eigen::Vector3d& start_yaw,
               Eigen::MatrixXd& yaw_ctrl, double& dt_yaw, std::vector<double>* path_yaw);
 
+  // addition: the body of FastPlannerManager::checkTrajCollision (plan_manage/src/planner_manager.cpp:96-118) in one
+  // device call (fuelmi_map_check_trajs, include/fuelmi.h) on the uniform position spline (pos_ctrl rows, degree, knot
+  // span dt) at time t_now since the trajectory's start, against the inflated plane of this optimiser's environment's
+  // map as the device holds it: no host mirror is read, so it answers with the inflate mirror switched off.  Returns
+  // the reference's value; `distance` is written only when the result is false, as the reference does.  A call that
+  // fails, or a point the reference could not index (FUELMI_TRAJCHK_NONFINITE), is reported as a collision at distance 0.
+  bool checkTrajCollision(const Eigen::MatrixXd& pos_ctrl, int degree, double dt, double t_now, double& distance);
+
   Eigen::MatrixXd getControlPoints();
   vector<Eigen::Vector3d> matrixToVectors(const Eigen::MatrixXd& ctrl_pts);
 

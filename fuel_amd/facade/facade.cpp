@@ -1248,6 +1248,28 @@ int BsplineOptimizer::planYaw(const Eigen::MatrixXd& pos_ctrl, int pos_degree, d
                       path_yaw);
 }
 
+bool BsplineOptimizer::checkTrajCollision(const Eigen::MatrixXd& pos_ctrl, int degree, double dt, double t_now,
+                                          double& distance) {
+  const int n_ctrl = (int)pos_ctrl.rows();
+  int rc = FUELMI_EINVAL, status = 0, safe = 0, n_samples = 0, hit_index = 0, end_reason = 0;
+  double dist = 0.0, hit_t = 0.0, hit_pos[3], duration = 0.0;
+  if (n_ctrl >= 1 && pos_ctrl.cols() == 3) {
+    std::vector<double> pos(3 * (size_t)n_ctrl);
+    for (int i = 0; i < n_ctrl; ++i)
+      for (int k = 0; k < 3; ++k) pos[3 * i + k] = pos_ctrl(i, k);
+    const fuelmi_trajchk_cfg tc = {degree, n_ctrl, 0.02, 6.0};  // planner_manager.cpp:102, 104
+    rc = fuelmi_map_check_trajs(edt_environment_->sdf_map_->device(), &tc, 1, &n_ctrl, pos.data(), &dt, &t_now, &status,
+                                &safe, &dist, &n_samples, &hit_index, &hit_t, hit_pos, &end_reason, &duration);
+  }
+  if (rc && rc != FUELMI_ELIMIT) {
+    warn("fuelmi_map_check_trajs", rc);
+    dist = 0.0, safe = 0;
+  }
+  if (safe) return true;
+  distance = dist;
+  return false;
+}
+
 vector<Eigen::Vector3d> BsplineOptimizer::matrixToVectors(const Eigen::MatrixXd& ctrl_pts) {
   vector<Eigen::Vector3d> out;
   for (int i = 0; i < ctrl_pts.rows(); ++i) {

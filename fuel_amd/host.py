@@ -13,8 +13,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BsplineBatch, BsplineCfg, FrontierCfg, GoalCfg, KinoCfg, MapCfg, MapInfo, PathCfg, RefineCfg, TspCfg, WptrajCfg,
-                   YawCfg, check, lib)
+from ._lib import (BsplineBatch, BsplineCfg, FrontierCfg, GoalCfg, KinoCfg, MapCfg, MapInfo, PathCfg, RefineCfg, TrajChkCfg, TspCfg,
+                   WptrajCfg, YawCfg, check, lib)
 
 # exploration.launch / algorithm.xml defaults (exploration_manager/launch/algorithm.xml:33-59,170-181)
 DEFAULT_MAP = dict(resolution=0.1, ground_height=-1.0, obstacles_inflation=0.199,
@@ -72,6 +72,20 @@ def kino_cfg(max_tau=0.8, init_max_tau=1.0, max_vel=2.25, max_acc=2.0, w_time=10
                    float(resolution), float(lambda_heu), float(res), float(time_res), float(time_res_init), float(ts),
                    int(allocate_num), int(check_num), 1 if optimistic else 0, int(min_seg), int(seg_num),
                    int(max_path_nodes), int(max_samples))
+
+
+def traj_check_cfg(degree=3, max_ctrl=4, step=0.02, max_radius=6.0):
+    """fuelmi_trajchk_cfg with checkTrajCollision's literals (planner_manager.cpp:102, 104)"""
+    return TrajChkCfg(int(degree), int(max_ctrl), float(step), float(max_radius))
+
+
+def _trajchk_outputs(n):
+    o = {"status": np.zeros(n, dtype=np.int32), "safe": np.zeros(n, dtype=np.int32), "distance": np.zeros(n),
+         "n_samples": np.zeros(n, dtype=np.int32), "hit_index": np.zeros(n, dtype=np.int32), "hit_t": np.zeros(n),
+         "hit_pos": np.zeros((n, 3)), "end_reason": np.zeros(n, dtype=np.int32), "duration": np.zeros(n)}
+    args = (_ip(o["status"]), _ip(o["safe"]), _dp(o["distance"]), _ip(o["n_samples"]), _ip(o["hit_index"]),
+            _dp(o["hit_t"]), _dp(o["hit_pos"]), _ip(o["end_reason"]), _dp(o["duration"]))
+    return o, args
 
 
 def _yaw_outputs(n, max_seg, derivs):
@@ -534,6 +548,38 @@ class SDFMap:
         """(lanes per problem, LDS bytes, largest max_ctrl accepted) of the yaw kernel for a YawCfg; host only"""
         out = (C.c_int * 3)()
         check(lib().fuelmi_yaw_plan(C.byref(cfg), out))
+        return tuple(out)
+
+    # --- the safety check of flown trajectories (include/fuelmi.h fuelmi_map_check_trajs) ---
+    def check_trajs(self, pos_ctrl, knot_span, t_now, allow_limit=False, max_ctrl=None, **cfg):
+        """checkTrajCollision per problem against the inflated plane on the device: pos_ctrl is a list of [n_ctrl, 3]
+        control-point arrays of uniform position splines, knot_span [n], t_now [n]; cfg: the fields of traj_check_cfg().
+        Returns a dict of arrays: status, safe, distance (-1 when safe), n_samples, hit_index, hit_t, hit_pos [n, 3],
+        end_reason, duration, limit.  FUELMI_ELIMIT raises unless allow_limit."""
+        pos = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in pos_ctrl]
+        n = len(pos)
+        maxc = int(max_ctrl) if max_ctrl is not None else max([len(p) for p in pos] + [4])
+        c = traj_check_cfg(max_ctrl=maxc, **cfg)
+        n_ctrl = np.array([len(p) for p in pos], dtype=np.int32)
+        arr = np.zeros((n, max(maxc, 0), 3))
+        for b, p in enumerate(pos):
+            k = min(len(p), arr.shape[1])
+            arr[b, :k] = p[:k]
+        knot = np.ascontiguousarray(np.broadcast_to(np.asarray(knot_span, dtype=np.float64), (n,)))
+        now = np.ascontiguousarray(np.broadcast_to(np.asarray(t_now, dtype=np.float64), (n,)))
+        o, args = _trajchk_outputs(n)
+        rc = self.L.fuelmi_map_check_trajs(self.h, C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(knot), _dp(now), *args)
+        if not (allow_limit and rc == -5):
+            check(rc)
+        o["limit"] = rc == -5
+        return o
+
+    @staticmethod
+    def traj_check_plan(cfg):
+        """(lanes per problem, LDS bytes of a workgroup, largest max_ctrl accepted) of the check kernel for a TrajChkCfg;
+        host only"""
+        out = (C.c_int * 3)()
+        check(lib().fuelmi_traj_check_plan(C.byref(cfg), out))
         return tuple(out)
 
     # --- measurement ---
@@ -1110,6 +1156,21 @@ class BsplineDeviceProblem:
         ey = None if end_yaw is None else np.ascontiguousarray(np.broadcast_to(np.asarray(end_yaw, dtype=np.float64), (n,)))
         o, args = _yaw_outputs(n, yc.max_seg, derivs)
         rc = self.L.fuelmi_bspline_dev_plan_yaws(self.h, C.byref(yc), _dp(sy), _dp(ey), *args)
+        if not (allow_limit and rc == -5):
+            check(rc)
+        o["limit"] = rc == -5
+        return o
+
+    def check_trajs(self, t_now, allow_limit=False, **cfg):
+        """The safety check of the candidates' optimised position splines against the batch's map, read from what the last
+        optimize() left on the device (fuelmi_bspline_dev_check_trajs).  Same result dict as SDFMap.check_trajs."""
+        c = self.problem.c
+        n = c.n_traj
+        cfg.setdefault("degree", 3)
+        tc = traj_check_cfg(max_ctrl=c.point_num, **cfg)
+        now = np.ascontiguousarray(np.broadcast_to(np.asarray(t_now, dtype=np.float64), (n,)))
+        o, args = _trajchk_outputs(n)
+        rc = self.L.fuelmi_bspline_dev_check_trajs(self.h, C.byref(tc), _dp(now), *args)
         if not (allow_limit and rc == -5):
             check(rc)
         o["limit"] = rc == -5

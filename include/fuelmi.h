@@ -956,6 +956,85 @@ int fuelmi_bspline_dev_load_kino(fuelmi_bspline_dev* b, const fuelmi_kino_cfg* c
 int fuelmi_kino_plan(const fuelmi_kino_cfg* cfg, long long out8[8]);
 
 /* ------------------------------------------------------------------------------------------
+ * Safety check of planned trajectories: FastPlannerManager::checkTrajCollision
+ * (plan_manage/src/planner_manager.cpp:96-118), which the exploration FSM's safetyCallback runs every 50 ms while a
+ * trajectory is flown (exploration_manager/src/fast_exploration_fsm.cpp:335-345), for n_prob independent problems in
+ * one call.  The position spline is UNIFORM (control points + one knot span, setUniformBspline); knots moved by a time
+ * reallocation (lengthenTime) are out of scope.  Per problem, everything f64 in this order:
+ *   1. knots as setUniformBspline builds them (non_uniform_bspline.cpp:25-31): u[i] = double(i - p) * dt for i <= p,
+ *      then ACCUMULATED u[i] = u[i-1] + dt; duration = u[n_ctrl] - u[p].
+ *   2. cur = evaluateDeBoorT(t_now) (the literal clamp, knot search and alpha recursion of :51-75).
+ *   3. radius = 0, fut_t = step; while (radius < max_radius && t_now + fut_t < duration):
+ *        p = evaluateDeBoorT(t_now + fut_t);
+ *        if getInflateOccupancy(p) == 1: UNSAFE, distance = radius, stop;
+ *        radius = sqrt(dx dx + dy dy + dz dz) of p - cur, summed left to right;  fut_t += step (ACCUMULATED, never
+ *        k * step).
+ *   4. getInflateOccupancy(Vector3d) (sdf_map.h:127-130, 163-169, 217-226): index floor((p - origin) * resolution_inv)
+ *      per axis; an index outside the map gives -1, which PASSES; otherwise the voxel of the inflated plane as the last
+ *      fuelmi_map_inflate_local (or upload) left it.  Neither the unknown nor the occupied plane is read.
+ * Sample k = 1, 2, ... is the k-th loop body; r_k is the radius it computes, r_0 = 0.  Outputs per problem:
+ *   status      FUELMI_TRAJCHK_OK, FUELMI_TRAJCHK_NONFINITE or -1 (below)
+ *   safe        1: the loop ended without a hit (the reference returns true); 0 otherwise
+ *   distance    unsafe: the reference's value r_(k-1) of the hit sample k; safe: -1 (the reference leaves the caller's
+ *               variable untouched)
+ *   n_samples   loop bodies entered
+ *   hit_index   k of the hit, 0 without one;  hit_t = t_now + fut_t of that sample, hit_pos [3] its point (0 without)
+ *   end_reason  FUELMI_TRAJCHK_END_HIT, _RADIUS (radius < max_radius failed; it is tested first), _DURATION
+ *               (t_now + fut_t < duration failed), _CAP, _NONFINITE
+ *   duration    of step 1
+ * Defined where the reference is not:
+ *   FUELMI_TRAJCHK_NONFINITE  an evaluated point (cur or a sample) is not finite or has |coordinate| >= 1e7 (the
+ *               reference casts it to int: undefined): a failure on the safe side, safe = 0, distance = 0, end_reason
+ *               _NONFINITE, hit_index / hit_t = the sample (0 / t_now for cur), hit_pos = 0, n_samples counts that
+ *               sample.  Also (device batches only, the host route refuses it): a knot span that is not finite and
+ *               > 0 -- then duration and n_samples are 0 as well.
+ *   -1          more than FUELMI_TRAJCHK_MAX_SAMPLES loop bodies would be entered: the walk ends there, end_reason
+ *               _CAP, safe = 0 (nothing was proven), distance = the radius reached, n_samples =
+ *               FUELMI_TRAJCHK_MAX_SAMPLES; the other problems are complete and the call returns FUELMI_ELIMIT.
+ * Checked on the host before anything is launched (FUELMI_EINVAL): pointers; degree in 3..5; degree + 1 <= n_ctrl[i]
+ * <= max_ctrl; knot spans finite and > 0; control points finite with |coordinate| < 1e7; t_now finite; step finite and
+ * >= 1e-3; max_radius finite and > 0.  max_ctrl > FUELMI_TRAJCHK_MAX_CTRL: FUELMI_ELIMIT.  n_prob = 0 is FUELMI_OK.
+ * fuelmi_map_check_trajs runs on the map's stream, behind whatever inflation was queued before it (like
+ * fuelmi_map_goal_paths): host arrays in and out, synchronous, one thread at a time per map (not a query-slot call);
+ * its scratch is one grow-only allocation on the map.  No host mirror is read or needed.  One 64-lane wave per
+ * problem; a result does not depend on the problem's place in the batch.
+ * ---------------------------------------------------------------------------------------- */
+#define FUELMI_TRAJCHK_OK 0
+#define FUELMI_TRAJCHK_NONFINITE 1
+#define FUELMI_TRAJCHK_END_HIT 0
+#define FUELMI_TRAJCHK_END_RADIUS 1
+#define FUELMI_TRAJCHK_END_DURATION 2
+#define FUELMI_TRAJCHK_END_CAP 3
+#define FUELMI_TRAJCHK_END_NONFINITE 4
+#define FUELMI_TRAJCHK_MAX_CTRL 1024          /* largest max_ctrl (position control points per problem) */
+#define FUELMI_TRAJCHK_MAX_SAMPLES 1048576    /* 2^20 loop bodies per problem */
+typedef struct {
+  int degree;          /* degree of the position spline, 3..5 (pp_.bspline_degree_) */
+  int max_ctrl;        /* stride of pos_ctrl */
+  double step;         /* 0.02 */
+  double max_radius;   /* 6.0 */
+} fuelmi_trajchk_cfg;
+/* pos_ctrl [n_prob][max_ctrl][3], n_ctrl / knot_span / t_now [n_prob].  Out, per problem: status, safe, distance,
+ * n_samples, hit_index, hit_t, hit_pos [n_prob][3], end_reason, duration. */
+int fuelmi_map_check_trajs(fuelmi_map* m, const fuelmi_trajchk_cfg* cfg, int n_prob, const int* n_ctrl,
+                           const double* pos_ctrl, const double* knot_span, const double* t_now, int* status, int* safe,
+                           double* distance, int* n_samples, int* hit_index, double* hit_t, double* hit_pos,
+                           int* end_reason, double* duration);
+/* The device chain optimised batch -> safety check: one problem per candidate of `b` (dim 3), read from the variables
+ * the batch's last fuelmi_bspline_dev_optimize[_timed] left in device memory (control points = those variables, knot
+ * span = x[nvar-1] under MINTIME and the batch's knot span otherwise) against the batch's map.  cfg->degree must be the
+ * batch's bspline_degree and cfg->max_ctrl is ignored (it is point_num).  t_now [n_traj].  Only the results are copied
+ * back; they equal, bit for bit, fuelmi_map_check_trajs on the x_out that solve returned.  FUELMI_EINVAL when the batch
+ * is not dim 3 or has not been optimised since it was created or last (re)loaded (the flag fuelmi_bspline_dev_plan_yaws
+ * uses).  Runs on the map's stream and waits for it. */
+int fuelmi_bspline_dev_check_trajs(fuelmi_bspline_dev* b, const fuelmi_trajchk_cfg* cfg, const double* t_now, int* status,
+                                   int* safe, double* distance, int* n_samples, int* hit_index, double* hit_t,
+                                   double* hit_pos, int* end_reason, double* duration);
+/* what the kernel needs for cfg->max_ctrl (host only, no device needed): out3 = {lanes per problem, dynamic LDS bytes of
+ * a workgroup, largest max_ctrl accepted}.  cfg is checked like above. */
+int fuelmi_traj_check_plan(const fuelmi_trajchk_cfg* cfg, int out3[3]);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): HIP events recorded on the map's own stream.
  * ---------------------------------------------------------------------------------------- */
 enum {
