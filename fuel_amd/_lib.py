@@ -149,6 +149,15 @@ TRAJCHK_OK, TRAJCHK_NONFINITE = 0, 1
 TRAJCHK_END_HIT, TRAJCHK_END_RADIUS, TRAJCHK_END_DURATION, TRAJCHK_END_CAP, TRAJCHK_END_NONFINITE = range(5)
 TRAJCHK_MAX_CTRL, TRAJCHK_MAX_SAMPLES = 1024, 1 << 20
 REFINE_LAST_ARGMIN = 1
+
+
+class CloudCfg(C.Structure):
+    """fuelmi_cloud_cfg: the kind, the inclusive voxel box and map_ros's two truncation heights."""
+    _fields_ = [("kind", C.c_int), ("lo", C.c_int * 3), ("hi", C.c_int * 3), ("z_low", C.c_double), ("z_high", C.c_double)]
+
+
+CLOUD_OCCUPIED, CLOUD_UNKNOWN, CLOUD_KNOWN, CLOUD_INFLATED = range(4)
+ELIMIT, EINVAL = -5, -1
 REFINE_MAX_LAYERS, REFINE_MAX_NODES = 64, 256
 
 
@@ -285,6 +294,9 @@ SYMBOLS = {
                                          _dp, _ip, _dp]),
     "fuelmi_bspline_dev_check_trajs": (C.c_int, [_P, C.POINTER(TrajChkCfg), _dp, _ip, _ip, _dp, _ip, _ip, _dp, _dp, _ip, _dp]),
     "fuelmi_traj_check_plan": (C.c_int, [C.POINTER(TrajChkCfg), _ip]),
+    "fuelmi_map_extract_cloud": (C.c_int, [_P, C.POINTER(CloudCfg), C.c_void_p, C.c_int, _ip]),
+    "fuelmi_cloud_plan": (C.c_int, [_ip, _ip, _ip, _ip]),
+    "fuelmi_map_cloud_times": (C.c_int, [_P, _dp]),
     "fuelmi_tsp_create": (C.c_int, [C.c_int, C.POINTER(TspCfg), _PP]),
     "fuelmi_tsp_destroy": (None, [_P]),
     "fuelmi_tsp_solve": (C.c_int, [_P, C.c_int, _ip, C.POINTER(C.c_int32), _ip, C.POINTER(C.c_int64), _ip]),

@@ -231,6 +231,13 @@ struct fuelmi_map {
   // grow-only device scratch of fuelmi_map_check_trajs (traj_check.hip): problems in, results out
   void* trajchk_dev = nullptr;
   size_t trajchk_dev_bytes = 0;
+  // grow-only device scratch of fuelmi_map_extract_cloud (map_cloud.hip): the total, the workgroup words, the points;
+  // the pinned word the scan writes the total to; the events that split its time
+  void* cloud_dev = nullptr;
+  size_t cloud_dev_bytes = 0;
+  u32* cloud_pin = nullptr;
+  hipEvent_t cloud_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  double cloud_ms[3] = {0.0, 0.0, 0.0};  // fuelmi_map_cloud_times
   unsigned long long fusion_count = 0;  // fusions / uploads queued so far (a search notices one queued behind its back)
   unsigned profile_mask = 0;
   ProfileSlot prof[FUELMI_K_COUNT];
@@ -602,6 +609,7 @@ int trajchk_launch(hipStream_t st, const Geo& g, const TrajChkArgs& T);
 int trajchk_copy_out(int n_prob, const TrajChkArgs& H, int* status, int* safe, double* distance, int* n_samples,
                      int* hit_index, double* hit_t, double* hit_pos, int* end_reason, double* duration);
 void traj_check_release(fuelmi_map* m);  // the map's trajectory-check scratch
+void map_cloud_release(fuelmi_map* m);   // the map's cloud scratch, pinned word and events (map_cloud.hip)
 // k_kino_path (kino_path.hip): one problem per workgroup; every pointer addresses device memory
 struct KinoArgs {
   fuelmi_kino_cfg cfg;

@@ -213,6 +213,40 @@ void SDFMap::resetBuffer(const Eigen::Vector3d& min_pos, const Eigen::Vector3d& 
   syncMirrors(lo, hi, false, ext_->mirror_infl, ext_->mirror_dist);
 }
 
+static fuelmi_cloud_cfg cloud_cfg(int kind, const Eigen::Vector3i& lo, const Eigen::Vector3i& hi, double z_low, double z_high) {
+  fuelmi_cloud_cfg c;
+  c.kind = kind;
+  for (int k = 0; k < 3; ++k) c.lo[k] = lo(k), c.hi[k] = hi(k);
+  c.z_low = z_low, c.z_high = z_high;
+  return c;
+}
+
+int SDFMap::extractCloud(int kind, const Eigen::Vector3i& lo, const Eigen::Vector3i& hi, double z_low, double z_high,
+                         std::vector<float>& xyz) {
+  const fuelmi_cloud_cfg c = cloud_cfg(kind, lo, hi, z_low, z_high);
+  int cap = (int)std::min<size_t>(xyz.capacity() / 3, (size_t)1 << 30), n = 0;
+  xyz.resize((size_t)cap * 3);
+  int rc = fuelmi_map_extract_cloud(ext_->dev, &c, cap ? xyz.data() : nullptr, cap, &n);
+  if (rc == FUELMI_ELIMIT || (rc == FUELMI_OK && n > cap)) {  // the full count is known: once more, with room
+    cap = n;
+    xyz.resize((size_t)cap * 3);
+    rc = fuelmi_map_extract_cloud(ext_->dev, &c, xyz.data(), cap, &n);
+  }
+  warn("fuelmi_map_extract_cloud", rc);
+  if (rc != FUELMI_OK) n = -1;
+  xyz.resize((size_t)std::max(n, 0) * 3);
+  return n;
+}
+
+int SDFMap::countVoxels(int kind, const Eigen::Vector3i& lo, const Eigen::Vector3i& hi) {
+  const double nan = std::numeric_limits<double>::quiet_NaN();  // no bound
+  const fuelmi_cloud_cfg c = cloud_cfg(kind, lo, hi, nan, nan);
+  int n = 0;
+  const int rc = fuelmi_map_extract_cloud(ext_->dev, &c, nullptr, 0, &n);
+  warn("fuelmi_map_extract_cloud", rc);
+  return rc == FUELMI_OK ? n : -1;
+}
+
 void SDFMap::setOccupied(const Eigen::Vector3d& pos, const int& occ) {
   if (!isInMap(pos)) return;
   const double p[3] = {pos(0), pos(1), pos(2)};

@@ -97,6 +97,13 @@ public:
   void setHostMirror(bool occupancy, bool inflate, bool distance);
   // batched getDistWithGrad for n positions (xyz packed), one kernel launch
   void getDistWithGradBatch(const double* pos_xyz, int n, double* dist, double* grad_xyz);
+  // the scans of MapROS::publishMapLocal / publishMapAll / publishUnknown (map_ros.cpp:217-346) on the device, with
+  // every mirror off: the voxel centres (x, y, z floats, the loops' order) of the inclusive index box lo..hi whose state
+  // is `kind`, between the two truncation heights; returns the number of points, -1 on an error.  xyz keeps its capacity
+  // between calls: a call that fits it is one device call.  countVoxels: the count alone (known_volumn's, no bounds)
+  enum CLOUD_KIND { CLOUD_OCCUPIED, CLOUD_UNKNOWN, CLOUD_KNOWN, CLOUD_INFLATED };
+  int extractCloud(int kind, const V3i& lo, const V3i& hi, double z_low, double z_high, std::vector<float>& xyz);
+  int countVoxels(int kind, const V3i& lo, const V3i& hi);
 
   EIGEN_MAKE_ALIGNED_OPERATOR_NEW
 

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BsplineBatch, BsplineCfg, FrontierCfg, GoalCfg, KinoCfg, MapCfg, MapInfo, PathCfg, RefineCfg, TrajChkCfg, TspCfg,
+from ._lib import (BsplineBatch, BsplineCfg, CloudCfg, FrontierCfg, GoalCfg, KinoCfg, MapCfg, MapInfo, PathCfg, RefineCfg, TrajChkCfg, TspCfg,
                    WptrajCfg, YawCfg, check, lib)
 
 # exploration.launch / algorithm.xml defaults (exploration_manager/launch/algorithm.xml:33-59,170-181)
@@ -77,6 +77,16 @@ def kino_cfg(max_tau=0.8, init_max_tau=1.0, max_vel=2.25, max_acc=2.0, w_time=10
 def traj_check_cfg(degree=3, max_ctrl=4, step=0.02, max_radius=6.0):
     """fuelmi_trajchk_cfg with checkTrajCollision's literals (planner_manager.cpp:102, 104)"""
     return TrajChkCfg(int(degree), int(max_ctrl), float(step), float(max_radius))
+
+
+def cloud_plan(dims, lo, hi):
+    """The geometry fuelmi_map_extract_cloud's kernels use for the inclusive box lo..hi of a dims grid
+    (fuelmi_cloud_plan, host only).  Raises FuelmiError for a box that leaves the map."""
+    out = (C.c_int * 8)()
+    check(lib().fuelmi_cloud_plan(_i3(dims), _i3(lo), _i3(hi), out))
+    keys = ("items_per_line", "lines", "items_per_workgroup", "workgroups", "scan_width", "scan_rounds", "scratch_bytes",
+            "voxels")
+    return dict(zip(keys, [int(v) for v in out]))
 
 
 def _trajchk_outputs(n):
@@ -324,6 +334,47 @@ class SDFMap:
 
     def synchronize(self):
         check(self.L.fuelmi_map_synchronize(self.h))
+
+    # --- the scans of MapROS::publishMapLocal / publishMapAll / publishUnknown (include/fuelmi.h
+    # fuelmi_map_extract_cloud) ---
+    CLOUD_OCCUPIED, CLOUD_UNKNOWN, CLOUD_KNOWN, CLOUD_INFLATED = range(4)
+
+    def _cloud_cfg(self, kind, lo, hi, z_low, z_high):
+        return CloudCfg(int(kind), _i3(lo), _i3(hi), float(z_low), float(z_high))
+
+    def count_voxels(self, kind, lo, hi, z_low=-np.inf, z_high=np.inf):
+        """Voxels of the inclusive box lo..hi that extract_cloud would return (publishMapAll's known-voxel count: kind
+        CLOUD_KNOWN, no bounds).  Nothing but the count crosses to the host."""
+        n = C.c_int(-1)
+        check(self.L.fuelmi_map_extract_cloud(self.h, C.byref(self._cloud_cfg(kind, lo, hi, z_low, z_high)), None, 0,
+                                              C.byref(n)))
+        return n.value
+
+    def extract_cloud(self, kind, lo, hi, z_low=-np.inf, z_high=np.inf, cap=None):
+        """The voxel centres (float32 [n, 3], x outermost, then y, then z) of the box's voxels of `kind` between the two
+        truncation heights.  cap=None: counts first, then fetches exactly.  With a cap: (the first min(n_total, cap)
+        points, n_total)."""
+        cfg = self._cloud_cfg(kind, lo, hi, z_low, z_high)
+        n = C.c_int(-1)
+        if cap is None:
+            k = self.count_voxels(kind, lo, hi, z_low, z_high)
+            out = np.empty((k, 3), dtype=np.float32)
+            if k:
+                check(self.L.fuelmi_map_extract_cloud(self.h, C.byref(cfg), out.ctypes.data, k, C.byref(n)))
+                assert n.value == k
+            return out
+        cap = int(cap)
+        out = np.empty((max(cap, 0), 3), dtype=np.float32)
+        rc = self.L.fuelmi_map_extract_cloud(self.h, C.byref(cfg), out.ctypes.data if cap > 0 else None, cap, C.byref(n))
+        if rc != _lib.ELIMIT:
+            check(rc)
+        return out[:min(n.value, cap)].copy(), n.value
+
+    def cloud_times(self):
+        """device milliseconds of the last extract_cloud / count_voxels: (count + scan, write, copy to the host)"""
+        ms = np.zeros(3)
+        check(self.L.fuelmi_map_cloud_times(self.h, _dp(ms)))
+        return tuple(ms)
 
     # --- ViewNode::searchPath for a batch of pairs (include/fuelmi.h fuelmi_map_path_costs) ---
     PATH_LINE, PATH_LATTICE, PATH_NONE = 0, 1, 2

@@ -1035,6 +1035,51 @@ int fuelmi_bspline_dev_check_trajs(fuelmi_bspline_dev* b, const fuelmi_trajchk_c
 int fuelmi_traj_check_plan(const fuelmi_trajchk_cfg* cfg, int out3[3]);
 
 /* ------------------------------------------------------------------------------------------
+ * Map clouds and the known-volume count: the scans of MapROS::publishMapLocal, publishMapAll and publishUnknown
+ * (plan_env/src/map_ros.cpp:217-346) as an ordered stream compaction over the state planes the device holds.  No host
+ * mirror is read or needed.
+ *   Selection   the voxels of the inclusive box lo..hi whose bit is set in the kind's plane:
+ *                 FUELMI_CLOUD_OCCUPIED  occ > min_occupancy_log             (publishMapAll :223, publishMapLocal :272)
+ *                 FUELMI_CLOUD_UNKNOWN   occ < clamp_min_log - 1e-3          (publishUnknown :328)
+ *                 FUELMI_CLOUD_KNOWN     the complement of UNKNOWN           (publishMapAll's second loop :249)
+ *                 FUELMI_CLOUD_INFLATED  occupancy_buffer_inflate_ == 1      (the lines commented out at :284-298)
+ *   Order       x outermost, then y, then z: ascending voxel address, the order of all three reference loops.
+ *   Truncation  a selected voxel is dropped iff pos_z > z_high or pos_z < z_low, pos_z = (z + 0.5) * resolution +
+ *               origin_z in f64 (indexToPos and the reference's two `continue`s).  Both comparisons are false for a NaN
+ *               bound: NaN and +-inf mean "no bound".  With z_high < z_low nothing is kept.
+ *   Points      (float)((i + 0.5) * resolution + origin_i) per axis: the f64 expression without contraction, one
+ *               rounding to float, as pcl::PointXYZ is assigned.
+ *   Count, cap  *n_total is always the full count.  n_total <= cap: all points are written, FUELMI_OK.  More: the first
+ *               `cap` points in order are written, nothing beyond them, FUELMI_ELIMIT.  xyz == NULL with cap == 0 counts
+ *               only and returns FUELMI_OK (publishMapAll's known_volumn: KNOWN, no bounds; the count is the pinned
+ *               quantity -- the reference adds 0.1 * 0.1 * 0.1 `count` times, count * 0.001 differs in the last bits).
+ *   Arguments   checked on the host before anything is launched.  lo > hi on any axis: an empty box, 0 points,
+ *               FUELMI_OK (the reference's loops do not run).  Otherwise a box that leaves the map, an unknown kind,
+ *               cap < 0, xyz == NULL with cap > 0: FUELMI_EINVAL, and neither xyz nor *n_total is written.  The caller
+ *               applies boundIndex, as the reference does.
+ * The one deviation: for KNOWN the reference tests occ > clamp_min_log - 1e-3 and the plane gives
+ * !(occ < clamp_min_log - 1e-3).  They differ only for a log-odds value exactly on the threshold, or a NaN, which this
+ * call counts as known.  Fusion produces neither; only fuelmi_map_upload_occupancy can.
+ * A mutator-class call: it runs on the map's stream behind every fusion, upload, reset and inflation queued before it,
+ * host arrays out, synchronous, one thread at a time per map.  Its scratch is one grow-only allocation on the map
+ * (workgroup words + min(cap, voxels of the box) points); nothing is allocated after the first call of a given size.
+ * ---------------------------------------------------------------------------------------- */
+enum { FUELMI_CLOUD_OCCUPIED = 0, FUELMI_CLOUD_UNKNOWN = 1, FUELMI_CLOUD_KNOWN = 2, FUELMI_CLOUD_INFLATED = 3 };
+typedef struct {
+  int kind;
+  int lo[3], hi[3];      /* inclusive voxel box */
+  double z_low, z_high;  /* visualization_truncate_low_ / _height_ */
+} fuelmi_cloud_cfg;
+int fuelmi_map_extract_cloud(fuelmi_map* m, const fuelmi_cloud_cfg* cfg, float* xyz, int cap, int* n_total);
+/* the geometry the kernels use for a box of a dims[3] map (host only, no device needed): out = {items per line (64-bit
+ * chunks of the z extent), lines, items per workgroup, workgroups, the scan's width, the scan's rounds, scratch bytes
+ * in front of the points, voxels of the box}.  An empty box gives 0 items, lines, workgroups, rounds and voxels; a box
+ * that leaves the map, dims outside 1 .. (nz: 255), or 2^31 - 64 voxels and more are FUELMI_EINVAL. */
+int fuelmi_cloud_plan(const int dims[3], const int lo[3], const int hi[3], int out[8]);
+/* device milliseconds of the last fuelmi_map_extract_cloud: count + scan, write, copy to the caller */
+int fuelmi_map_cloud_times(const fuelmi_map* m, double ms3[3]);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): HIP events recorded on the map's own stream.
  * ---------------------------------------------------------------------------------------- */
 enum {
