@@ -151,6 +151,17 @@ TRAJCHK_MAX_CTRL, TRAJCHK_MAX_SAMPLES = 1024, 1 << 20
 REFINE_LAST_ARGMIN = 1
 
 
+class TrajSmpCfg(C.Structure):
+    """fuelmi_trajsmp_cfg: the mode, the two degrees and the strides of control points, yaw control points and times."""
+    _fields_ = [("mode", C.c_int), ("degree", C.c_int), ("yaw_degree", C.c_int), ("max_ctrl", C.c_int),
+                ("max_yaw_ctrl", C.c_int), ("max_t", C.c_int)]
+
+
+TRAJSMP_COMMAND, TRAJSMP_STATE = 0, 1
+TRAJSMP_IN, TRAJSMP_PAST, TRAJSMP_INVALID, TRAJSMP_BADSPLINE = range(4)
+TRAJSMP_MAX_CTRL, TRAJSMP_MAX_T, TRAJSMP_MAX_SAMPLES = 1024, 1 << 16, 1 << 21
+
+
 class CloudCfg(C.Structure):
     """fuelmi_cloud_cfg: the kind, the inclusive voxel box and map_ros's two truncation heights."""
     _fields_ = [("kind", C.c_int), ("lo", C.c_int * 3), ("hi", C.c_int * 3), ("z_low", C.c_double), ("z_high", C.c_double)]
@@ -294,6 +305,11 @@ SYMBOLS = {
                                          _dp, _ip, _dp]),
     "fuelmi_bspline_dev_check_trajs": (C.c_int, [_P, C.POINTER(TrajChkCfg), _dp, _ip, _ip, _dp, _ip, _ip, _dp, _dp, _ip, _dp]),
     "fuelmi_traj_check_plan": (C.c_int, [C.POINTER(TrajChkCfg), _ip]),
+    "fuelmi_map_sample_trajs": (C.c_int, [_P, C.POINTER(TrajSmpCfg), C.c_int, _ip, _dp, _dp, _ip, _dp, _dp, _dp, _ip, _dp,
+                                          _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "fuelmi_bspline_dev_sample_trajs": (C.c_int, [_P, C.POINTER(TrajSmpCfg), _ip, _dp, _dp, _dp, _ip, _dp, _ip, _dp, _dp,
+                                                  _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "fuelmi_traj_sample_plan": (C.c_int, [C.POINTER(TrajSmpCfg), _ip]),
     "fuelmi_map_extract_cloud": (C.c_int, [_P, C.POINTER(CloudCfg), C.c_void_p, C.c_int, _ip]),
     "fuelmi_cloud_plan": (C.c_int, [_ip, _ip, _ip, _ip]),
     "fuelmi_map_cloud_times": (C.c_int, [_P, _dp]),

@@ -51,6 +51,8 @@ struct fuelmi_bspline_dev {
   size_t yaw_cap = 0;
   unsigned char* chk_dev = nullptr;  // fuelmi_bspline_dev_check_trajs: t_now | results (grow-only)
   size_t chk_cap = 0;
+  unsigned char* smp_dev = nullptr;  // fuelmi_bspline_dev_sample_trajs: yaw splines, times | results (grow-only)
+  size_t smp_cap = 0;
 };
 
 // 64-lane sum on the DPP data path (no LDS crossbar round trips): quads, half rows, rows, then the two
@@ -1810,4 +1812,47 @@ extern "C" int fuelmi_bspline_dev_check_trajs(fuelmi_bspline_dev* b, const fuelm
   TrajChkArgs H = T;
   trajchk_out_bytes(A.C, H, host.data());
   return trajchk_copy_out(A.C, H, status, safe, distance, n_samples, hit_index, hit_t, hit_pos, end_reason, duration);
+}
+
+// the batch's optimised position splines sampled as commands or replan states (k_traj_sample, traj_sample.hip), read from
+// the variables the last solve left on the device; the yaw splines and the times come from the host, only results travel
+extern "C" int fuelmi_bspline_dev_sample_trajs(fuelmi_bspline_dev* b, const fuelmi_trajsmp_cfg* cfg, const int* n_yaw_ctrl,
+                                               const double* yaw_ctrl, const double* yaw_dt, const double* t_stop,
+                                               const int* n_t, const double* t, int* status, double* pos, double* vel,
+                                               double* acc, double* jerk, double* yaw, double* yawdot, double* yawddot,
+                                               double* duration, double* flight) {
+  ARGCHK(b && cfg);
+  const BsplineArgs& A = b->a;
+  ARGCHK(A.dim == 3 && b->opt_valid && b->opt_x);
+  ARGCHK(cfg->degree == A.cfg.bspline_degree);
+  fuelmi_trajsmp_cfg sc = *cfg;
+  sc.max_ctrl = A.N;
+  const TrajSmpIO io = {nullptr, nullptr, nullptr, n_yaw_ctrl, yaw_ctrl, yaw_dt, t_stop, n_t,      t,     status,
+                        pos,     vel,     acc,     jerk,       yaw,      yawdot, yawddot, duration, flight};
+  bool nothing = true;
+  {
+    const int rc = trajsmp_check(&sc, A.C, false, io, &nothing);
+    if (rc) return rc;
+  }
+  if (nothing) return FUELMI_OK;
+  fuelmi_map* m = b->map;
+  ARGCHK(m);
+  HIPCHK(hipSetDevice(m->device));
+  const size_t need = trajsmp_bytes(&sc, A.C, false, io);
+  if (need > b->smp_cap) {
+    void* d = nullptr;
+    HIPCHK(hipMalloc(&d, need));
+    b->allocs.push_back(d);
+    b->smp_dev = static_cast<unsigned char*>(d);
+    b->smp_cap = need;
+  }
+  TrajSmpArgs T;
+  memset(&T, 0, sizeof(T));
+  T.n_ctrl = nullptr, T.n_ctrl_all = A.N;
+  T.pos = b->opt_x, T.pos_stride = (size_t)A.nvar;
+  if (A.cost_function & FUELMI_COST_MINTIME)
+    T.knot = b->opt_x + (A.nvar - 1), T.knot_stride = (size_t)A.nvar;
+  else
+    T.knot = A.knot_span, T.knot_stride = 1;
+  return trajsmp_run(m->stream, &sc, A.C, false, io, T, b->smp_dev);
 }

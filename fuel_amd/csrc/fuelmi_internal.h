@@ -231,6 +231,9 @@ struct fuelmi_map {
   // grow-only device scratch of fuelmi_map_check_trajs (traj_check.hip): problems in, results out
   void* trajchk_dev = nullptr;
   size_t trajchk_dev_bytes = 0;
+  // grow-only device scratch of fuelmi_map_sample_trajs (traj_sample.hip): problems in, results out
+  void* trajsmp_dev = nullptr;
+  size_t trajsmp_dev_bytes = 0;
   // grow-only device scratch of fuelmi_map_extract_cloud (map_cloud.hip): the total, the workgroup words, the points;
   // the pinned word the scan writes the total to; the events that split its time
   void* cloud_dev = nullptr;
@@ -609,6 +612,48 @@ int trajchk_launch(hipStream_t st, const Geo& g, const TrajChkArgs& T);
 int trajchk_copy_out(int n_prob, const TrajChkArgs& H, int* status, int* safe, double* distance, int* n_samples,
                      int* hit_index, double* hit_t, double* hit_pos, int* end_reason, double* duration);
 void traj_check_release(fuelmi_map* m);  // the map's trajectory-check scratch
+// k_traj_sample (traj_sample.hip): one problem per wave; every pointer addresses device memory
+struct TrajSmpArgs {
+  fuelmi_trajsmp_cfg cfg;
+  int n_prob;
+  const int* n_ctrl;        // [n], or null: every problem has n_ctrl_all control points
+  int n_ctrl_all;
+  const double* pos;        // problem b: [n_ctrl][3] at pos + b * pos_stride
+  size_t pos_stride;
+  const double* knot;       // problem b: knot[b * knot_stride]
+  size_t knot_stride;
+  const int* n_yaw;         // [n] (0: that problem has no yaw spline), or null: none has
+  const double* yaw;        // [n][max_yaw_ctrl]
+  const double* yaw_dt;     // [n]
+  const double* t_stop;     // [n] or null
+  const int* n_t;           // [n]
+  const double* t;          // [n][max_t]
+  double* flight;           // [n][8] in and out, or null
+  int* status;              // [n][max_t]
+  double *o_pos, *o_vel, *o_acc, *o_jerk;  // [n][max_t][3]
+  double *o_yaw, *o_yawdot, *o_yawddot;    // [n][max_t]
+  double* duration;         // [n]
+};
+// the caller's host arrays of fuelmi_map_sample_trajs / fuelmi_bspline_dev_sample_trajs (the first three null for a
+// device batch)
+struct TrajSmpIO {
+  const int* n_ctrl;
+  const double *pos_ctrl, *knot_span;
+  const int* n_yaw_ctrl;
+  const double *yaw_ctrl, *yaw_dt, *t_stop;
+  const int* n_t;
+  const double* t;
+  int* status;
+  double *pos, *vel, *acc, *jerk, *yaw, *yawdot, *yawddot, *duration, *flight;
+};
+// the host checks of both calls (*nothing: no problem or no sample, the call returns FUELMI_OK at once); the bytes of
+// the scratch block; uploads, the launch on stream st, the results into the caller's arrays and the wait.  A device
+// batch presets A's n_ctrl .. knot_stride.
+int trajsmp_check(const fuelmi_trajsmp_cfg* cfg, int n_prob, bool host_spline, const TrajSmpIO& io, bool* nothing);
+size_t trajsmp_bytes(const fuelmi_trajsmp_cfg* cfg, int n_prob, bool host_spline, const TrajSmpIO& io);
+int trajsmp_run(hipStream_t st, const fuelmi_trajsmp_cfg* cfg, int n_prob, bool host_spline, const TrajSmpIO& io,
+                TrajSmpArgs& A, unsigned char* scratch);
+void traj_sample_release(fuelmi_map* m);  // the map's trajectory-sampling scratch
 void map_cloud_release(fuelmi_map* m);   // the map's cloud scratch, pinned word and events (map_cloud.hip)
 // k_kino_path (kino_path.hip): one problem per workgroup; every pointer addresses device memory
 struct KinoArgs {

@@ -727,6 +727,7 @@ extern "C" void fuelmi_map_destroy(fuelmi_map* m) {
   goal_path_release(m);
   kino_path_release(m);
   traj_check_release(m);
+  traj_sample_release(m);
   map_cloud_release(m);
   void* bufs[] = {m->occ, m->dist, m->esdf_tmp, m->esdf_tmp16, m->flag_rayend, m->ray_owner, m->d_stage, m->ins_partial, m->ins_head, m->ins_rec};
   if (m->h_ins) (void)hipHostFree(m->h_ins);

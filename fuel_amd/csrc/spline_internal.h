@@ -1,28 +1,61 @@
-// spline_internal.h -- NonUniformBspline's point evaluation on the device, shared by the kernels that evaluate a
-// position spline (yaw_plan.hip, traj_check.hip).  f64, the reference's operations in the reference's order.
+// spline_internal.h -- NonUniformBspline's evaluation on the device, shared by the kernels that evaluate a uniform
+// spline (yaw_plan.hip, traj_check.hip, traj_sample.hip).  f64, the reference's operations in the reference's order.
 #ifndef FUELMI_SPLINE_INTERNAL_H_
 #define FUELMI_SPLINE_INTERNAL_H_
+
+// the clamp and the knot search of evaluateDeBoor (non_uniform_bspline.cpp:52-57) for evaluateDeBoorT(t) of a spline of
+// degree p with n control points and the knots u[0 .. n + p]: returns the span k, ub = the clamped parameter.  Every
+// derivative spline of getDerivative (:97-106) finds the same ub and, counted in these knots, the same k: its knots are
+// u without the first and the last, its degree and its number of points are one less, so its u_(p_) is u[p], its
+// u_(m_ - p_) is u[n] and its search starts on u[p + 1].
+__device__ __forceinline__ int spline_span(const double* u, int p, int n, double t, double& ub) {
+  const double lo = u[p], v = t + u[p], hi = u[n];
+  ub = lo < v ? v : lo;  // min(max(u_(p_), u), u_(m_ - p_))
+  ub = hi < ub ? hi : ub;
+  int k = p;
+  while (k < n - 1 && u[k + 1] < ub) ++k;  // (k < n - 1 holds by the clamp; it keeps a bad spline inside its arrays)
+  return k;
+}
+
+// the alpha recursion of evaluateDeBoor (:65-69) on the PD + 1 points d of span k, for a spline of degree PD or, k still
+// counted in the parent's knots u, a derivative spline of degree PD: the shift of its knots and the shift of its k cancel
+// in both indices.  The result is d[PD].
+template <int PD, int DIM>
+__device__ __forceinline__ void spline_alpha(const double* u, int k, double ub, double (*d)[DIM]) {
+#pragma unroll
+  for (int r = 1; r <= PD; ++r)
+#pragma unroll
+    for (int i = PD; i >= r; --i) {
+      const double alpha = (ub - u[i + k - PD]) / (u[i + 1 + k - r] - u[i + k - PD]);
+#pragma unroll
+      for (int c = 0; c < DIM; ++c) d[i][c] = (1 - alpha) * d[i - 1][c] + alpha * d[i][c];
+    }
+}
+
+// getDerivativeControlPoints (:77-86) on the points of span k, in place: q holds the PD + 1 points of a spline (or
+// derivative spline) of degree PD that span k reads and receives the PD points its derivative reads there,
+// Q[i] = double(PD) * (P[i+1] - P[i]) / (u_(i + PD + 1) - u_(i + 1)) in that spline's own knots -- in the parent's u
+// the two are u[k + i + 1] and u[k - PD + i + 1] at every level
+template <int PD, int DIM>
+__device__ __forceinline__ void spline_derive(const double* u, int k, double (*q)[DIM]) {
+#pragma unroll
+  for (int i = 0; i < PD; ++i) {
+    const double den = u[k + i + 1] - u[k - PD + i + 1];
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) q[i][c] = (double)PD * (q[i + 1][c] - q[i][c]) / den;
+  }
+}
 
 // NonUniformBspline::evaluateDeBoorT (non_uniform_bspline.cpp:51-75) of a spline of degree P with n control points and
 // the knots u[0 .. n + P]; ctrl(i, d) fetches control point i
 template <int P, class F>
 __device__ __forceinline__ void spline_deboor(const double* u, int n, double t, F ctrl, double out[3]) {
-  const double lo = u[P], v = t + u[P], hi = u[n];
-  double ub = lo < v ? v : lo;  // min(max(u_(p_), u), u_(m_ - p_))
-  ub = hi < ub ? hi : ub;
-  int k = P;
-  while (k < n - 1 && u[k + 1] < ub) ++k;  // (k < n - 1 holds by the clamp; it keeps a bad spline inside its arrays)
+  double ub;
+  const int k = spline_span(u, P, n, t, ub);
   double d[P + 1][3];
 #pragma unroll
   for (int i = 0; i <= P; ++i) ctrl(k - P + i, d[i]);
-#pragma unroll
-  for (int r = 1; r <= P; ++r)
-#pragma unroll
-    for (int i = P; i >= r; --i) {
-      const double alpha = (ub - u[i + k - P]) / (u[i + 1 + k - r] - u[i + k - P]);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) d[i][c] = (1 - alpha) * d[i - 1][c] + alpha * d[i][c];
-    }
+  spline_alpha<P, 3>(u, k, ub, d);
   out[0] = d[P][0], out[1] = d[P][1], out[2] = d[P][2];
 }
 

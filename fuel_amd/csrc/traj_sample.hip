@@ -1,0 +1,420 @@
+// traj_sample.hip -- what the reference does with a finished trajectory, for a batch of problems (uniform position
+// spline, optional uniform yaw spline, a tape of sample times):
+//   FUELMI_TRAJSMP_COMMAND  traj_server's cmdCallback (plan_manage/src/traj_server.cpp:257-343): position, velocity,
+//                           acceleration, jerk, yaw and yaw rate at each tick, and the flight record (:328-339)
+//   FUELMI_TRAJSMP_STATE    the FSM's replan start state (exploration_manager/src/fast_exploration_fsm.cpp:86-95)
+// The derivative splines of getDerivative (non_uniform_bspline.cpp:77-106) are never stored: the clamp and the knot search
+// of evaluateDeBoor give every derivative the same span (spline_internal.h), and the p + 1 position points of that span
+// give the points each derivative reads there by getDerivativeControlPoints' own operations.
+//
+// One 64-lane wave per problem, TS_WAVES problems per workgroup.  Lane 0 stages the knots of both splines in LDS by the
+// accumulated additions (one block per wave); control points are read from global memory through L2 (traj_check.hip
+// says why).  The lanes take a window of 64 consecutive sample times, one each.  The flight record is a chain through
+// the samples -- each is compared with the last one PUSHED -- so behind every window all lanes walk its 64 samples in
+// order by lane reads, each lane making the same additions, and lane 0 stores the record at the end: the sums are the
+// reference's, term by term.  All f64, -ffp-contract=off.  A result does not depend on the problem's place in the
+// batch: the only workgroup-wide step is the barrier behind the knots.
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "fuelmi_internal.h"
+#include "spline_internal.h"
+
+namespace {
+
+constexpr int TS_WIN = 64;   // samples per window: one per lane
+constexpr int TS_WAVES = 3;  // problems per workgroup: two knot blocks each, 48.4 KiB at the largest strides
+
+// doubles of one knot block: n + p + 1 <= max + 6 knots, kept a multiple of 16 bytes
+__host__ __device__ inline int ts_knot_stride(int max_ctrl) { return (max_ctrl + 6 + 1) & ~1; }
+__host__ __device__ inline int ts_wave_stride(const fuelmi_trajsmp_cfg& c) {
+  return ts_knot_stride(c.max_ctrl) + (c.max_yaw_ctrl > 0 ? ts_knot_stride(c.max_yaw_ctrl) : 0);
+}
+
+// setUniformBspline's knots (non_uniform_bspline.cpp:25-31)
+__device__ inline void ts_knots(double* u, int p, int n, double dt) {
+  for (int i = 0; i <= p; ++i) u[i] = (double)(i - p) * dt;
+  double acc = u[p];
+  for (int i = p + 1; i <= n + p; ++i) {
+    acc = acc + dt;
+    u[i] = acc;
+  }
+}
+
+// the spline of degree PD on the points q of span k, then LEVELS derivatives of it: out[0 .. LEVELS].  A derivative of
+// degree 0 is its one point: the knot search alone (evaluateDeBoor with p_ = 0).
+template <int PD, int DIM, int LEVELS>
+__device__ __forceinline__ void ts_levels(const double* u, int k, double ub, double (*q)[DIM], double (*out)[DIM]) {
+  double w[PD + 1][DIM];
+#pragma unroll
+  for (int i = 0; i <= PD; ++i)
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) w[i][c] = q[i][c];
+  spline_alpha<PD, DIM>(u, k, ub, w);
+#pragma unroll
+  for (int c = 0; c < DIM; ++c) out[0][c] = w[PD][c];
+  if constexpr (LEVELS > 0) {
+    spline_derive<PD, DIM>(u, k, q);
+    ts_levels<PD - 1, DIM, LEVELS - 1>(u, k, ub, q, out + 1);
+  }
+}
+
+// evaluateDeBoorT(t) of a spline (degree P, n points C [n][DIM], knots u) and of its first LEVELS derivatives
+template <int P, int DIM, int LEVELS>
+__device__ __forceinline__ void ts_eval(const double* u, int n, const double* C, double t, double (*out)[DIM]) {
+  double ub;
+  const int k = spline_span(u, P, n, t, ub);
+  double q[P + 1][DIM];
+#pragma unroll
+  for (int i = 0; i <= P; ++i)
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) q[i][c] = C[(size_t)DIM * (k - P + i) + c];
+  ts_levels<P, DIM, LEVELS>(u, k, ub, q, out);
+}
+
+__global__ void __launch_bounds__(TS_WIN * TS_WAVES) k_traj_sample(TrajSmpArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int lane = threadIdx.x & (TS_WIN - 1), wv = threadIdx.x >> 6;
+  const int b = blockIdx.x * TS_WAVES + wv;
+  double* u = reinterpret_cast<double*>(smem_raw) + (size_t)wv * ts_wave_stride(A.cfg);  // [n + p + 1]
+  double* uy = u + ts_knot_stride(A.cfg.max_ctrl);                                        // [ny + py + 1]
+  const int p = A.cfg.degree, py = A.cfg.yaw_degree, max_t = A.cfg.max_t;
+  const bool live = b < A.n_prob;
+  int n = 0, ny = 0;
+  double dt = 0.0, dty = 0.0;
+  if (live) {
+    n = A.n_ctrl ? A.n_ctrl[b] : A.n_ctrl_all;
+    dt = A.knot[(size_t)b * A.knot_stride];
+    if (A.n_yaw && A.cfg.max_yaw_ctrl > 0) ny = A.n_yaw[b];
+    if (ny > 0) dty = A.yaw_dt[b];
+  }
+  // (the host refuses these before any launch wherever it sees them; the variables of a device batch it does not see)
+  const bool sane = live && dt > 0.0 && isfinite(dt) && n >= p + 1 && n <= A.cfg.max_ctrl &&
+                    (ny <= 0 || (dty > 0.0 && isfinite(dty) && py >= 3 && py <= 5 && ny >= py + 1 && ny <= A.cfg.max_yaw_ctrl));
+
+  // 1. knots; every wave of the workgroup meets at the barrier, with or without a problem
+  if (sane && lane == 0) {
+    ts_knots(u, p, n, dt);
+    if (ny > 0) ts_knots(uy, py, ny, dty);
+  }
+  __syncthreads();
+  if (!live) return;
+
+  const bool command = A.cfg.mode == FUELMI_TRAJSMP_COMMAND;
+  const int nt_given = A.n_t[b] < max_t ? A.n_t[b] : max_t;
+  const int nt = sane ? nt_given : 0;  // a bad spline is never indexed: its samples are BADSPLINE and 0
+  const double D = sane ? u[n] - u[p] : 0.0;
+  double T = D;  // traj_duration_ as replanCallback leaves it (:171): min(t_stop, traj_duration_)
+  if (A.t_stop) {
+    const double ts = A.t_stop[b];
+    T = D < ts ? D : ts;
+  }
+  const double* C = A.pos + (size_t)b * A.pos_stride;
+  const double* Cy = ny > 0 ? A.yaw + (size_t)b * A.cfg.max_yaw_ctrl : nullptr;
+  const bool record = command && A.flight && sane;
+  double* F = A.flight ? A.flight + (size_t)b * 8 : nullptr;
+  bool have = false;
+  double lp[3] = {0.0, 0.0, 0.0}, last_t = 0.0, length = 0.0, energy = 0.0, n_cmd = 0.0;
+  if (record) {
+    have = F[0] != 0.0;
+    lp[0] = F[1], lp[1] = F[2], lp[2] = F[3];
+    last_t = F[4], length = F[5], energy = F[6], n_cmd = F[7];
+  }
+
+  // 2. windows of TS_WIN samples; the entries from n_t[b] to max_t are written as 0
+  for (int kb = 0; kb < max_t; kb += TS_WIN) {
+    const int k = kb + lane;
+    int status = k < nt_given && !sane ? FUELMI_TRAJSMP_BADSPLINE : FUELMI_TRAJSMP_IN;
+    double t = 0.0;
+    double o[4][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};  // pos, vel, acc, jerk
+    double y[3][1] = {{0.0}, {0.0}, {0.0}};                                                // yaw, yawdot, yawddot
+    if (k < nt) {
+      t = A.t[(size_t)b * max_t + k];
+      double te = t;
+      if (command) {  // cmdCallback :266, :274, :288 in that order
+        if (t < T && t >= 0.0)
+          status = FUELMI_TRAJSMP_IN;
+        else if (t >= T)
+          status = FUELMI_TRAJSMP_PAST, te = T;
+        else
+          status = FUELMI_TRAJSMP_INVALID;
+      }
+      if (status != FUELMI_TRAJSMP_INVALID) {
+        if (p == 3)
+          ts_eval<3, 3, 3>(u, n, C, te, o);
+        else if (p == 4)
+          ts_eval<4, 3, 3>(u, n, C, te, o);
+        else
+          ts_eval<5, 3, 3>(u, n, C, te, o);
+        if (ny > 0) {
+          if (py == 3)
+            ts_eval<3, 1, 2>(uy, ny, Cy, te, y);
+          else if (py == 4)
+            ts_eval<4, 1, 2>(uy, ny, Cy, te, y);
+          else
+            ts_eval<5, 1, 2>(uy, ny, Cy, te, y);
+        }
+        if (status == FUELMI_TRAJSMP_PAST) {  // the final position and yaw, everything else 0 (:277-281)
+          for (int l = 1; l < 4; ++l) o[l][0] = o[l][1] = o[l][2] = 0.0;
+          y[1][0] = y[2][0] = 0.0;
+        }
+      }
+    }
+    if (k < max_t) {
+      const size_t e = (size_t)b * max_t + k;
+      A.status[e] = status;
+      for (int c = 0; c < 3; ++c) {
+        A.o_pos[3 * e + c] = o[0][c];
+        A.o_vel[3 * e + c] = o[1][c];
+        A.o_acc[3 * e + c] = o[2][c];
+        A.o_jerk[3 * e + c] = o[3][c];
+      }
+      A.o_yaw[e] = y[0][0];
+      A.o_yawdot[e] = y[1][0];
+      A.o_yawddot[e] = y[2][0];
+    }
+    // 3. the flight record (:328-339) through this window's samples in order; every lane walks the same chain
+    if (record && kb < nt) {
+      const int cnt = nt - kb < TS_WIN ? nt - kb : TS_WIN;
+      for (int j = 0; j < cnt; ++j) {
+        const int sj = __shfl(status, j);
+        const double tj = __shfl(t, j);
+        const double px = __shfl(o[0][0], j), py_ = __shfl(o[0][1], j), pz = __shfl(o[0][2], j);
+        const double jx = __shfl(o[3][0], j), jy = __shfl(o[3][1], j), jz = __shfl(o[3][2], j);
+        if (sj != FUELMI_TRAJSMP_INVALID) {
+          if (!have) {  // traj_cmd_ is empty: the first position
+            have = true;
+            lp[0] = px, lp[1] = py_, lp[2] = pz;
+            n_cmd = 1.0;
+          } else {
+            const double dx = px - lp[0], dy = py_ - lp[1], dz = pz - lp[2];
+            const double nrm = sqrt(dx * dx + dy * dy + dz * dz);
+            if (nrm > 1e-6) {  // a new different commanded position
+              lp[0] = px, lp[1] = py_, lp[2] = pz;
+              length = length + nrm;                                         // calcPathLength (:49-56)
+              energy = energy + (jx * jx + jy * jy + jz * jz) * (tj - last_t);  // :335-336
+              n_cmd = n_cmd + 1.0;
+            }
+          }
+        }
+        last_t = tj;  // :339
+      }
+    }
+  }
+  if (lane == 0) {
+    A.duration[b] = D;
+    if (record) {
+      F[0] = have ? 1.0 : 0.0;
+      F[1] = lp[0], F[2] = lp[1], F[3] = lp[2];
+      F[4] = last_t, F[5] = length, F[6] = energy, F[7] = n_cmd;
+    }
+  }
+}
+
+size_t ts_lds(const fuelmi_trajsmp_cfg& c) { return (size_t)TS_WAVES * ts_wave_stride(c) * sizeof(double); }
+
+int trajsmp_cfg_check(const fuelmi_trajsmp_cfg* cfg) {
+  ARGCHK(cfg);
+  ARGCHK(cfg->mode == FUELMI_TRAJSMP_COMMAND || cfg->mode == FUELMI_TRAJSMP_STATE);
+  ARGCHK(cfg->degree >= 3 && cfg->degree <= 5);
+  ARGCHK(cfg->max_ctrl >= cfg->degree + 1);
+  ARGCHK(cfg->max_yaw_ctrl >= 0);
+  if (cfg->max_yaw_ctrl > 0) {
+    ARGCHK(cfg->yaw_degree >= 3 && cfg->yaw_degree <= 5);
+    ARGCHK(cfg->max_yaw_ctrl >= cfg->yaw_degree + 1);
+  }
+  ARGCHK(cfg->max_t >= 0);
+  if (cfg->max_ctrl > FUELMI_TRAJSMP_MAX_CTRL || cfg->max_yaw_ctrl > FUELMI_TRAJSMP_MAX_CTRL) {
+    fuelmi_set_error("trajectory sampling: max_ctrl = %d / max_yaw_ctrl = %d exceeds %d", cfg->max_ctrl,
+                     cfg->max_yaw_ctrl, FUELMI_TRAJSMP_MAX_CTRL);
+    return FUELMI_ELIMIT;
+  }
+  if (cfg->max_t > FUELMI_TRAJSMP_MAX_T) {
+    fuelmi_set_error("trajectory sampling: max_t = %d exceeds %d", cfg->max_t, FUELMI_TRAJSMP_MAX_T);
+    return FUELMI_ELIMIT;
+  }
+  return FUELMI_OK;
+}
+
+inline size_t ts_pad(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// the scratch block: the inputs the host hands over, the flight record (in and out), then the results.  base null: only
+// the size.
+size_t ts_layout(const fuelmi_trajsmp_cfg& c, int n_prob, bool host_spline, const TrajSmpIO& io, TrajSmpArgs& A,
+                 unsigned char* base) {
+  const size_t n = (size_t)n_prob, s = n * (size_t)c.max_t;
+  size_t at = 0;
+  auto take = [&](size_t bytes) {
+    unsigned char* p = base ? base + at : nullptr;
+    at += ts_pad(bytes);
+    return p;
+  };
+  auto dbl = [&](size_t count) { return reinterpret_cast<double*>(take(count * sizeof(double))); };
+  auto i32 = [&](size_t count) { return reinterpret_cast<int*>(take(count * sizeof(int))); };
+  if (host_spline) {
+    A.n_ctrl = i32(n), A.n_ctrl_all = 0;
+    A.knot = dbl(n), A.knot_stride = 1;
+    A.pos = dbl(n * c.max_ctrl * 3), A.pos_stride = (size_t)c.max_ctrl * 3;
+  }
+  const bool yaw = io.n_yaw_ctrl && c.max_yaw_ctrl > 0;
+  A.n_yaw = yaw ? i32(n) : nullptr;
+  A.yaw = yaw ? dbl(n * c.max_yaw_ctrl) : nullptr;
+  A.yaw_dt = yaw ? dbl(n) : nullptr;
+  A.t_stop = io.t_stop ? dbl(n) : nullptr;
+  A.n_t = i32(n);
+  A.t = dbl(s);
+  A.flight = io.flight ? dbl(n * 8) : nullptr;
+  A.status = i32(s);
+  A.o_pos = dbl(3 * s), A.o_vel = dbl(3 * s), A.o_acc = dbl(3 * s), A.o_jerk = dbl(3 * s);
+  A.o_yaw = dbl(s), A.o_yawdot = dbl(s), A.o_yawddot = dbl(s);
+  A.duration = dbl(n);
+  return at;
+}
+
+}  // namespace
+
+int trajsmp_check(const fuelmi_trajsmp_cfg* cfg, int n_prob, bool host_spline, const TrajSmpIO& io, bool* nothing) {
+  {
+    const int rc = trajsmp_cfg_check(cfg);
+    if (rc) return rc;
+  }
+  *nothing = true;
+  ARGCHK(n_prob >= 0);
+  if (n_prob == 0) return FUELMI_OK;
+  if ((long long)n_prob * cfg->max_t > FUELMI_TRAJSMP_MAX_SAMPLES) {
+    fuelmi_set_error("trajectory sampling: n_prob * max_t = %lld exceeds %d", (long long)n_prob * cfg->max_t,
+                     FUELMI_TRAJSMP_MAX_SAMPLES);
+    return FUELMI_ELIMIT;
+  }
+  ARGCHK(io.n_t);
+  ARGCHK(io.t || cfg->max_t == 0);
+  const int p = cfg->degree, py = cfg->yaw_degree;
+  if (cfg->mode == FUELMI_TRAJSMP_STATE) ARGCHK(!io.t_stop && !io.flight);  // cmdCallback's alone
+  if (host_spline) {
+    ARGCHK(io.n_ctrl && io.pos_ctrl && io.knot_span);
+    for (int b = 0; b < n_prob; ++b) {
+      ARGCHK(io.n_ctrl[b] >= p + 1 && io.n_ctrl[b] <= cfg->max_ctrl);
+      ARGCHK(std::isfinite(io.knot_span[b]) && io.knot_span[b] > 0.0);
+      const double* P = io.pos_ctrl + (size_t)b * cfg->max_ctrl * 3;
+      for (int k = 0; k < 3 * io.n_ctrl[b]; ++k) ARGCHK(std::fabs(P[k]) < 1e7);
+    }
+  }
+  if (io.n_yaw_ctrl) {
+    ARGCHK(cfg->max_yaw_ctrl > 0 && io.yaw_ctrl && io.yaw_dt);
+    for (int b = 0; b < n_prob; ++b) {
+      const int ny = io.n_yaw_ctrl[b];
+      if (ny == 0) continue;  // this problem has no yaw spline
+      ARGCHK(ny >= py + 1 && ny <= cfg->max_yaw_ctrl);
+      ARGCHK(std::isfinite(io.yaw_dt[b]) && io.yaw_dt[b] > 0.0);
+      const double* Y = io.yaw_ctrl + (size_t)b * cfg->max_yaw_ctrl;
+      for (int k = 0; k < ny; ++k) ARGCHK(std::fabs(Y[k]) < 1e7);
+    }
+  }
+  for (int b = 0; b < n_prob; ++b) {
+    ARGCHK(io.n_t[b] >= 0 && io.n_t[b] <= cfg->max_t);
+    const double* t = io.t + (size_t)b * cfg->max_t;
+    for (int k = 0; k < io.n_t[b]; ++k) ARGCHK(std::isfinite(t[k]));
+    if (io.t_stop) ARGCHK(std::isfinite(io.t_stop[b]));
+    if (io.flight)
+      for (int k = 0; k < 8; ++k) ARGCHK(std::isfinite(io.flight[(size_t)b * 8 + k]));
+    if (io.n_t[b] > 0) *nothing = false;
+  }
+  if (*nothing) return FUELMI_OK;
+  ARGCHK(io.status && io.pos && io.vel && io.acc && io.jerk && io.yaw && io.yawdot && io.yawddot && io.duration);
+  return FUELMI_OK;
+}
+
+size_t trajsmp_bytes(const fuelmi_trajsmp_cfg* cfg, int n_prob, bool host_spline, const TrajSmpIO& io) {
+  TrajSmpArgs A;
+  memset(&A, 0, sizeof(A));
+  return ts_layout(*cfg, n_prob, host_spline, io, A, nullptr);
+}
+
+int trajsmp_run(hipStream_t st, const fuelmi_trajsmp_cfg* cfg, int n_prob, bool host_spline, const TrajSmpIO& io,
+                TrajSmpArgs& A, unsigned char* scratch) {
+  const fuelmi_trajsmp_cfg& c = *cfg;
+  const size_t n = (size_t)n_prob, s = n * (size_t)c.max_t;
+  A.cfg = c;
+  A.n_prob = n_prob;
+  ts_layout(c, n_prob, host_spline, io, A, scratch);
+  auto up = [&](const void* dst, const void* src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(const_cast<void*>(dst), src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+  };
+  auto down = [&](void* dst, const void* src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
+  };
+  if (host_spline) {
+    HIPCHK(up(A.n_ctrl, io.n_ctrl, n * sizeof(int)));
+    HIPCHK(up(A.knot, io.knot_span, n * sizeof(double)));
+    HIPCHK(up(A.pos, io.pos_ctrl, n * c.max_ctrl * 3 * sizeof(double)));
+  }
+  if (A.n_yaw) {
+    HIPCHK(up(A.n_yaw, io.n_yaw_ctrl, n * sizeof(int)));
+    HIPCHK(up(A.yaw, io.yaw_ctrl, n * c.max_yaw_ctrl * sizeof(double)));
+    HIPCHK(up(A.yaw_dt, io.yaw_dt, n * sizeof(double)));
+  }
+  if (A.t_stop) HIPCHK(up(A.t_stop, io.t_stop, n * sizeof(double)));
+  HIPCHK(up(A.n_t, io.n_t, n * sizeof(int)));
+  HIPCHK(up(A.t, io.t, s * sizeof(double)));
+  if (A.flight) HIPCHK(up(A.flight, io.flight, n * 8 * sizeof(double)));
+  hipLaunchKernelGGL(k_traj_sample, dim3((n_prob + TS_WAVES - 1) / TS_WAVES), dim3(TS_WIN * TS_WAVES), ts_lds(c), st, A);
+  HIPCHK(hipGetLastError());
+  HIPCHK(down(io.status, A.status, s * sizeof(int)));
+  HIPCHK(down(io.pos, A.o_pos, 3 * s * sizeof(double)));
+  HIPCHK(down(io.vel, A.o_vel, 3 * s * sizeof(double)));
+  HIPCHK(down(io.acc, A.o_acc, 3 * s * sizeof(double)));
+  HIPCHK(down(io.jerk, A.o_jerk, 3 * s * sizeof(double)));
+  HIPCHK(down(io.yaw, A.o_yaw, s * sizeof(double)));
+  HIPCHK(down(io.yawdot, A.o_yawdot, s * sizeof(double)));
+  HIPCHK(down(io.yawddot, A.o_yawddot, s * sizeof(double)));
+  HIPCHK(down(io.duration, A.duration, n * sizeof(double)));
+  if (A.flight) HIPCHK(down(io.flight, A.flight, n * 8 * sizeof(double)));
+  HIPCHK(stream_wait(st));
+  return FUELMI_OK;
+}
+
+void traj_sample_release(fuelmi_map* m) {
+  if (m->trajsmp_dev) (void)hipFree(m->trajsmp_dev);
+  m->trajsmp_dev = nullptr;
+  m->trajsmp_dev_bytes = 0;
+}
+
+extern "C" int fuelmi_traj_sample_plan(const fuelmi_trajsmp_cfg* cfg, int out3[3]) {
+  ARGCHK(out3);
+  {
+    const int rc = trajsmp_cfg_check(cfg);
+    if (rc) return rc;
+  }
+  out3[0] = TS_WIN, out3[1] = (int)ts_lds(*cfg), out3[2] = FUELMI_TRAJSMP_MAX_CTRL;
+  return FUELMI_OK;
+}
+
+extern "C" int fuelmi_map_sample_trajs(fuelmi_map* m, const fuelmi_trajsmp_cfg* cfg, int n_prob, const int* n_ctrl,
+                                       const double* pos_ctrl, const double* knot_span, const int* n_yaw_ctrl,
+                                       const double* yaw_ctrl, const double* yaw_dt, const double* t_stop,
+                                       const int* n_t, const double* t, int* status, double* pos, double* vel,
+                                       double* acc, double* jerk, double* yaw, double* yawdot, double* yawddot,
+                                       double* duration, double* flight) {
+  const TrajSmpIO io = {n_ctrl, pos_ctrl, knot_span, n_yaw_ctrl, yaw_ctrl, yaw_dt, t_stop, n_t,     t,     status,
+                        pos,    vel,      acc,       jerk,       yaw,      yawdot, yawddot, duration, flight};
+  bool nothing = true;
+  {  // every argument on the host, before the map is touched
+    const int rc = trajsmp_check(cfg, n_prob, true, io, &nothing);
+    if (rc) return rc;
+  }
+  if (nothing) return FUELMI_OK;
+  ARGCHK(m);
+  HIPCHK(hipSetDevice(m->device));
+  hipStream_t st = m->stream;
+  const size_t need = trajsmp_bytes(cfg, n_prob, true, io);
+  if (need > m->trajsmp_dev_bytes) {
+    HIPCHK(hipStreamSynchronize(st));
+    traj_sample_release(m);
+    HIPCHK(hipMalloc(&m->trajsmp_dev, need));
+    m->trajsmp_dev_bytes = need;
+  }
+  TrajSmpArgs A;
+  memset(&A, 0, sizeof(A));
+  return trajsmp_run(st, cfg, n_prob, true, io, A, static_cast<unsigned char*>(m->trajsmp_dev));
+}

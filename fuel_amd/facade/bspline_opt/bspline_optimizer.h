@@ -107,6 +107,23 @@ public:
   // fails, or a point the reference could not index (FUELMI_TRAJCHK_NONFINITE), is reported as a collision at distance 0.
   bool checkTrajCollision(const Eigen::MatrixXd& pos_ctrl, int degree, double dt, double t_now, double& distance);
 
+  // addition: the two things the reference does with a finished trajectory, each in one device call
+  // (fuelmi_map_sample_trajs, include/fuelmi.h) on the uniform position spline (pos_ctrl rows, degree, knot span dt) and
+  // the uniform yaw spline (yaw_ctrl rows x 1, yaw_degree, yaw_dt; 0 rows: none, the yaw outputs are 0).
+  // evaluateCommand is the body of traj_server's cmdCallback (plan_manage/src/traj_server.cpp:266-290, 328-339) for a
+  // whole tape of times t since the trajectory's start: t_stop (may be null) is what replanCallback left in
+  // traj_duration_; status receives FUELMI_TRAJSMP_IN / _PAST / _INVALID per tick, pos / vel / acc / jerk one row per
+  // tick, yaw one row (yaw, yaw rate, yaw acceleration) per tick; flight8 (may be null) is the flight record, carried
+  // from call to call.  replanState is the FSM's replan start state at t_r (fast_exploration_fsm.cpp:86-95): start_yaw =
+  // (yaw, yaw rate, yaw acceleration).  Both return false, and touch no output, when the call fails.
+  bool evaluateCommand(const Eigen::MatrixXd& pos_ctrl, int degree, double dt, const Eigen::MatrixXd& yaw_ctrl,
+                       int yaw_degree, double yaw_dt, const std::vector<double>& t, const double* t_stop,
+                       std::vector<int>& status, Eigen::MatrixXd& pos, Eigen::MatrixXd& vel, Eigen::MatrixXd& acc,
+                       Eigen::MatrixXd& jerk, Eigen::MatrixXd& yaw, double* flight8);
+  bool replanState(const Eigen::MatrixXd& pos_ctrl, int degree, double dt, const Eigen::MatrixXd& yaw_ctrl, int yaw_degree,
+                   double yaw_dt, double t_r, Eigen::Vector3d& start_pt, Eigen::Vector3d& start_vel,
+                   Eigen::Vector3d& start_acc, Eigen::Vector3d& start_yaw);
+
   Eigen::MatrixXd getControlPoints();
   vector<Eigen::Vector3d> matrixToVectors(const Eigen::MatrixXd& ctrl_pts);
 

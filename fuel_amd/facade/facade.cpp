@@ -1304,6 +1304,66 @@ bool BsplineOptimizer::checkTrajCollision(const Eigen::MatrixXd& pos_ctrl, int d
   return false;
 }
 
+// one problem through fuelmi_map_sample_trajs; out = status | pos | vel | acc | jerk | yaw | yawdot | yawddot
+static int sample_one_traj(fuelmi_map* m, int mode, const Eigen::MatrixXd& pos_ctrl, int degree, double dt,
+                           const Eigen::MatrixXd& yaw_ctrl, int yaw_degree, double yaw_dt, const std::vector<double>& t,
+                           const double* t_stop, std::vector<int>& status, std::vector<double> out[7], double* flight8) {
+  const int n_ctrl = (int)pos_ctrl.rows(), n_yaw = (int)yaw_ctrl.rows(), n_t = (int)t.size();
+  if (n_ctrl < 1 || pos_ctrl.cols() != 3 || (n_yaw > 0 && yaw_ctrl.cols() < 1)) return FUELMI_EINVAL;
+  std::vector<double> pos(3 * (size_t)n_ctrl), yawc((size_t)n_yaw);
+  for (int i = 0; i < n_ctrl; ++i)
+    for (int k = 0; k < 3; ++k) pos[3 * i + k] = pos_ctrl(i, k);
+  for (int i = 0; i < n_yaw; ++i) yawc[i] = yaw_ctrl(i, 0);
+  const fuelmi_trajsmp_cfg sc = {mode, degree, yaw_degree, n_ctrl, n_yaw, n_t};
+  status.assign(n_t, 0);
+  for (int k = 0; k < 7; ++k) out[k].assign((k < 4 ? 3 : 1) * (size_t)n_t, 0.0);
+  double duration = 0.0;
+  return fuelmi_map_sample_trajs(m, &sc, 1, &n_ctrl, pos.data(), &dt, n_yaw > 0 ? &n_yaw : nullptr, yawc.data(), &yaw_dt,
+                                 t_stop, &n_t, t.data(), status.data(), out[0].data(), out[1].data(), out[2].data(),
+                                 out[3].data(), out[4].data(), out[5].data(), out[6].data(), &duration, flight8);
+}
+
+bool BsplineOptimizer::evaluateCommand(const Eigen::MatrixXd& pos_ctrl, int degree, double dt, const Eigen::MatrixXd& yaw_ctrl,
+                                       int yaw_degree, double yaw_dt, const std::vector<double>& t, const double* t_stop,
+                                       std::vector<int>& status, Eigen::MatrixXd& pos, Eigen::MatrixXd& vel,
+                                       Eigen::MatrixXd& acc, Eigen::MatrixXd& jerk, Eigen::MatrixXd& yaw, double* flight8) {
+  std::vector<int> st;
+  std::vector<double> out[7];
+  const int rc = sample_one_traj(edt_environment_->sdf_map_->device(), FUELMI_TRAJSMP_COMMAND, pos_ctrl, degree, dt, yaw_ctrl,
+                                 yaw_degree, yaw_dt, t, t_stop, st, out, flight8);
+  if (rc) {
+    warn("fuelmi_map_sample_trajs", rc);
+    return false;
+  }
+  const int n_t = (int)t.size();
+  status = st;
+  Eigen::MatrixXd* dst[4] = {&pos, &vel, &acc, &jerk};
+  for (int q = 0; q < 4; ++q) {
+    *dst[q] = Eigen::MatrixXd(n_t, 3);
+    for (int i = 0; i < n_t; ++i)
+      for (int k = 0; k < 3; ++k) (*dst[q])(i, k) = out[q][3 * (size_t)i + k];
+  }
+  yaw = Eigen::MatrixXd(n_t, 3);
+  for (int i = 0; i < n_t; ++i)
+    for (int k = 0; k < 3; ++k) yaw(i, k) = out[4 + k][i];
+  return true;
+}
+
+bool BsplineOptimizer::replanState(const Eigen::MatrixXd& pos_ctrl, int degree, double dt, const Eigen::MatrixXd& yaw_ctrl,
+                                   int yaw_degree, double yaw_dt, double t_r, Eigen::Vector3d& start_pt,
+                                   Eigen::Vector3d& start_vel, Eigen::Vector3d& start_acc, Eigen::Vector3d& start_yaw) {
+  std::vector<int> st;
+  std::vector<double> out[7];
+  const int rc = sample_one_traj(edt_environment_->sdf_map_->device(), FUELMI_TRAJSMP_STATE, pos_ctrl, degree, dt, yaw_ctrl,
+                                 yaw_degree, yaw_dt, std::vector<double>(1, t_r), nullptr, st, out, nullptr);
+  if (rc) {
+    warn("fuelmi_map_sample_trajs", rc);
+    return false;
+  }
+  for (int k = 0; k < 3; ++k) start_pt(k) = out[0][k], start_vel(k) = out[1][k], start_acc(k) = out[2][k], start_yaw(k) = out[4 + k][0];
+  return true;
+}
+
 vector<Eigen::Vector3d> BsplineOptimizer::matrixToVectors(const Eigen::MatrixXd& ctrl_pts) {
   vector<Eigen::Vector3d> out;
   for (int i = 0; i < ctrl_pts.rows(); ++i) {

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BsplineBatch, BsplineCfg, CloudCfg, FrontierCfg, GoalCfg, KinoCfg, MapCfg, MapInfo, PathCfg, RefineCfg, TrajChkCfg, TspCfg,
+from ._lib import (BsplineBatch, BsplineCfg, CloudCfg, FrontierCfg, GoalCfg, KinoCfg, MapCfg, MapInfo, PathCfg, RefineCfg, TrajChkCfg, TrajSmpCfg, TspCfg,
                    WptrajCfg, YawCfg, check, lib)
 
 # exploration.launch / algorithm.xml defaults (exploration_manager/launch/algorithm.xml:33-59,170-181)
@@ -77,6 +77,48 @@ def kino_cfg(max_tau=0.8, init_max_tau=1.0, max_vel=2.25, max_acc=2.0, w_time=10
 def traj_check_cfg(degree=3, max_ctrl=4, step=0.02, max_radius=6.0):
     """fuelmi_trajchk_cfg with checkTrajCollision's literals (planner_manager.cpp:102, 104)"""
     return TrajChkCfg(int(degree), int(max_ctrl), float(step), float(max_radius))
+
+
+def traj_sample_cfg(mode=_lib.TRAJSMP_COMMAND, degree=3, yaw_degree=3, max_ctrl=4, max_yaw_ctrl=0, max_t=0):
+    """fuelmi_trajsmp_cfg: cmdCallback (TRAJSMP_COMMAND) or the FSM's replan state (TRAJSMP_STATE); planYawExplore's yaw
+    degree"""
+    return TrajSmpCfg(int(mode), int(degree), int(yaw_degree), int(max_ctrl), int(max_yaw_ctrl), int(max_t))
+
+
+def _trajsmp_io(n, t, yaw_ctrl, yaw_dt, t_stop, flight, max_yaw_ctrl, max_t):
+    """The host arrays both sampling calls share: (arguments from n_yaw_ctrl on, the result dict, the two strides).  t
+    and yaw_ctrl are one 1-D array per problem (yaw_ctrl None, or None for a problem: no yaw spline)."""
+    ts = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in t]
+    assert len(ts) == n
+    maxt = int(max_t) if max_t is not None else max([len(v) for v in ts] + [0])
+    n_t = np.array([len(v) for v in ts], dtype=np.int32)
+    tt = np.zeros((n, max(maxt, 0)))
+    for b, v in enumerate(ts):
+        k = min(len(v), tt.shape[1])
+        tt[b, :k] = v[:k]
+    n_yaw = yaw = ydt = None
+    maxy = int(max_yaw_ctrl) if max_yaw_ctrl is not None else 0
+    if yaw_ctrl is not None:
+        ys = [np.zeros(0) if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in yaw_ctrl]
+        assert len(ys) == n
+        if max_yaw_ctrl is None:
+            maxy = max([len(v) for v in ys] + [0])
+        n_yaw = np.array([len(v) for v in ys], dtype=np.int32)
+        yaw = np.zeros((n, max(maxy, 0)))
+        for b, v in enumerate(ys):
+            k = min(len(v), yaw.shape[1])
+            yaw[b, :k] = v[:k]
+        ydt = np.ascontiguousarray(np.broadcast_to(np.asarray(yaw_dt, dtype=np.float64), (n,)))
+    stop = None if t_stop is None else np.ascontiguousarray(np.broadcast_to(np.asarray(t_stop, dtype=np.float64), (n,)))
+    fl = None if flight is None else np.array(flight, dtype=np.float64).reshape(n, 8)
+    s = (n, max(maxt, 0))
+    o = {"status": np.zeros(s, dtype=np.int32), "pos": np.zeros(s + (3,)), "vel": np.zeros(s + (3,)),
+         "acc": np.zeros(s + (3,)), "jerk": np.zeros(s + (3,)), "yaw": np.zeros(s), "yawdot": np.zeros(s),
+         "yawddot": np.zeros(s), "duration": np.zeros(n), "flight": fl, "n_t": n_t}
+    args = (_ip(n_yaw), _dp(yaw), _dp(ydt), _dp(stop), _ip(n_t), _dp(tt), _ip(o["status"]), _dp(o["pos"]), _dp(o["vel"]),
+            _dp(o["acc"]), _dp(o["jerk"]), _dp(o["yaw"]), _dp(o["yawdot"]), _dp(o["yawddot"]), _dp(o["duration"]), _dp(fl))
+    keep = (n_yaw, yaw, ydt, stop, tt)  # (the arrays behind the pointers live as long as the tuple)
+    return args, o, maxy, maxt, keep
 
 
 def cloud_plan(dims, lo, hi):
@@ -631,6 +673,37 @@ class SDFMap:
         host only"""
         out = (C.c_int * 3)()
         check(lib().fuelmi_traj_check_plan(C.byref(cfg), out))
+        return tuple(out)
+
+    # --- sampling of flown trajectories (include/fuelmi.h fuelmi_map_sample_trajs) ---
+    def sampleTrajs(self, pos_ctrl, knot_span, t, yaw_ctrl=None, yaw_dt=None, t_stop=None, flight=None, max_ctrl=None,
+                    max_yaw_ctrl=None, max_t=None, **cfg):
+        """cmdCallback (mode TRAJSMP_COMMAND, the default) or the FSM's replan state (TRAJSMP_STATE) per problem on the
+        device: pos_ctrl is a list of [n_ctrl, 3] control-point arrays of uniform position splines, knot_span [n], t a list
+        of 1-D arrays of sample times; yaw_ctrl a list of 1-D control-point arrays (None: no yaw spline) with yaw_dt [n];
+        t_stop [n] or None; flight [n, 8] or None (a copy is updated and returned); cfg: mode, degree, yaw_degree.
+        Returns a dict of arrays: status [n, max_t], pos / vel / acc / jerk [n, max_t, 3], yaw / yawdot / yawddot
+        [n, max_t], duration [n], flight, n_t."""
+        pos = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in pos_ctrl]
+        n = len(pos)
+        maxc = int(max_ctrl) if max_ctrl is not None else max([len(p) for p in pos] + [4])
+        args, o, maxy, maxt, keep = _trajsmp_io(n, t, yaw_ctrl, yaw_dt, t_stop, flight, max_yaw_ctrl, max_t)
+        c = traj_sample_cfg(max_ctrl=maxc, max_yaw_ctrl=maxy, max_t=maxt, **cfg)
+        n_ctrl = np.array([len(p) for p in pos], dtype=np.int32)
+        arr = np.zeros((n, max(maxc, 0), 3))
+        for b, p in enumerate(pos):
+            k = min(len(p), arr.shape[1])
+            arr[b, :k] = p[:k]
+        knot = np.ascontiguousarray(np.broadcast_to(np.asarray(knot_span, dtype=np.float64), (n,)))
+        check(self.L.fuelmi_map_sample_trajs(self.h, C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(knot), *args))
+        return o
+
+    @staticmethod
+    def traj_sample_plan(cfg):
+        """(lanes per problem, LDS bytes of a workgroup, largest max_ctrl accepted) of the sampling kernel for a
+        TrajSmpCfg; host only"""
+        out = (C.c_int * 3)()
+        check(lib().fuelmi_traj_sample_plan(C.byref(cfg), out))
         return tuple(out)
 
     # --- measurement ---
@@ -1225,6 +1298,18 @@ class BsplineDeviceProblem:
         if not (allow_limit and rc == -5):
             check(rc)
         o["limit"] = rc == -5
+        return o
+
+    def sample_trajs(self, t, yaw_ctrl=None, yaw_dt=None, t_stop=None, flight=None, max_yaw_ctrl=None, max_t=None, **cfg):
+        """The candidates' optimised position splines sampled as commands or replan states, read from what the last
+        optimize() left on the device (fuelmi_bspline_dev_sample_trajs).  Arguments and result dict as
+        SDFMap.sampleTrajs from t on."""
+        c = self.problem.c
+        n = c.n_traj
+        cfg.setdefault("degree", 3)
+        args, o, maxy, maxt, keep = _trajsmp_io(n, t, yaw_ctrl, yaw_dt, t_stop, flight, max_yaw_ctrl, max_t)
+        sc = traj_sample_cfg(max_ctrl=c.point_num, max_yaw_ctrl=maxy, max_t=maxt, **cfg)
+        check(self.L.fuelmi_bspline_dev_sample_trajs(self.h, C.byref(sc), *args))
         return o
 
     def close(self):

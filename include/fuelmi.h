@@ -1035,6 +1035,101 @@ int fuelmi_bspline_dev_check_trajs(fuelmi_bspline_dev* b, const fuelmi_trajchk_c
 int fuelmi_traj_check_plan(const fuelmi_trajchk_cfg* cfg, int out3[3]);
 
 /* ------------------------------------------------------------------------------------------
+ * Sampling of flown trajectories: what the reference does with a finished trajectory, for n_prob independent problems
+ * (a UNIFORM position spline, an optional UNIFORM 1-D yaw spline, n_t sample times) in one call.  Two modes:
+ *   FUELMI_TRAJSMP_COMMAND  traj_server's cmdCallback (plan_manage/src/traj_server.cpp:257-343), which runs at 100 Hz:
+ *                           position, velocity, acceleration, jerk, yaw, yaw rate, and the flight record (:328-339).
+ *   FUELMI_TRAJSMP_STATE    the FSM's replan start state (exploration_manager/src/fast_exploration_fsm.cpp:86-95):
+ *                           position, velocity, acceleration, yaw, yaw rate, yaw acceleration at t_r.
+ * Both modes write all seven quantities (jerk is an addition to the second, yaw acceleration to the first).  Everything
+ * f64, the reference's operations in the reference's order:
+ *   1. knots as setUniformBspline builds them (bspline/src/non_uniform_bspline.cpp:25-31): u[i] = double(i - p) * dt
+ *      for i <= p, then ACCUMULATED u[i] = u[i-1] + dt; duration D = u[n_ctrl] - u[p].  The yaw spline likewise from
+ *      yaw_dt and its own degree (planYawExplore sets 3, planYaw the position degree).
+ *   2. derivative splines as getDerivative builds them (:77-106), applied repeatedly (velocity, acceleration, jerk; yaw
+ *      rate, yaw acceleration): control points Q[i] = double(p) * (P[i+1] - P[i]) / (u[i+p+1] - u[i+1]), knots the
+ *      PARENT's u[1 .. m-1] (the accumulated values, not regenerated ones), degree p - 1.  A cubic's jerk spline has
+ *      degree 0: evaluateDeBoor then is the knot search `while (u[k+1] < ub) ++k` from k = 0 and returns row k, with
+ *      the strict < at a knot.
+ *   3. every evaluation is the literal evaluateDeBoorT (:51-75): clamp to [u_(p_), u_(m_ - p_)], knot search, alpha
+ *      recursion.
+ *   COMMAND (:266-290): T = t_stop ? min(t_stop[b], D) : D (what replanCallback :166-172 leaves in traj_duration_).
+ *      t < T && t >= 0: FUELMI_TRAJSMP_IN, everything at t.  Else t >= T: FUELMI_TRAJSMP_PAST, pos = S(T), yaw = Y(T),
+ *      everything else 0.  Else FUELMI_TRAJSMP_INVALID.  The tests are made in this order, the reference's, so with a
+ *      t_stop below 0 a time in [T, 0) is PAST.
+ *   STATE: everything is evaluateDeBoorT(t) with its own clamp, for any finite t; the status is always IN.
+ *   Flight record (COMMAND, optional, in and out): flight [n_prob][8] = have_last, last_pos[3], last_t, length, energy,
+ *      n_cmd.  The samples are taken in order (:328-339, calcPathLength :49-56): have_last == 0: push pos (last_pos =
+ *      pos, have_last = 1, n_cmd = 1).  Else if sqrt(dx dx + dy dy + dz dz) of pos - THE LAST PUSHED POSITION is
+ *      > 1e-6: push, length += that norm, energy += (jx jx + jy jy + jz jz) * (t[k] - last_t), n_cmd += 1; the sums run
+ *      left to right.  last_t = t[k] after every sample.  Carrying flight from call to call continues a flight across
+ *      tapes and replans; a record of zeros starts one.
+ * Defined where the reference is not:
+ *   PAST     jerk = 0 (the reference leaves jer uninitialised; with a position that moved it enters the energy).
+ *   INVALID  every output 0 (the reference prints "invalid time" and publishes uninitialised values); of the record only
+ *            last_t is touched.
+ *   no yaw spline (n_yaw_ctrl NULL, or n_yaw_ctrl[b] == 0): the three yaw outputs are 0.
+ *   FUELMI_TRAJSMP_BADSPLINE (device batches only, the host route refuses it): a knot span that is not finite and > 0.
+ *            The spline is never indexed: every sample of the problem has this status, every output is 0, duration 0,
+ *            the record untouched.
+ *   Entries from n_t[b] to max_t are written as 0 (status too).
+ * Out of scope: loop correction (:292-300), the FOV markers and all publishing, knots moved by a time reallocation.
+ * Checked on the host before anything is launched (FUELMI_EINVAL): pointers; mode; degree in 3..5 and, with max_yaw_ctrl
+ * > 0, yaw_degree in 3..5; degree + 1 <= n_ctrl[b] <= max_ctrl; n_yaw_ctrl[b] == 0 or yaw_degree + 1 <= n_yaw_ctrl[b] <=
+ * max_yaw_ctrl; spans finite and > 0; control points finite with |value| < 1e7; 0 <= n_t[b] <= max_t; every t, t_stop and
+ * flight value finite; t_stop or flight in STATE mode.  FUELMI_ELIMIT: max_ctrl or max_yaw_ctrl >
+ * FUELMI_TRAJSMP_MAX_CTRL; max_t > FUELMI_TRAJSMP_MAX_T; n_prob * max_t > FUELMI_TRAJSMP_MAX_SAMPLES (the results of a
+ * call, 124 bytes per sample, then stay below 260 MiB of device scratch).  n_prob = 0 or every n_t = 0 is FUELMI_OK:
+ * nothing is launched and nothing is written.
+ * fuelmi_map_sample_trajs takes host arrays in and out, is synchronous, runs on the map's stream, one thread at a time
+ * per map (not a query-slot call); its scratch is one grow-only allocation on the map.  It reads no plane and no
+ * mirror.  One 64-lane wave per problem, one sample per lane and window of 64; the record is walked in sample order by
+ * every lane alike, so its sums are the reference's term by term.  A result does not depend on the problem's place in
+ * the batch.
+ * ---------------------------------------------------------------------------------------- */
+#define FUELMI_TRAJSMP_COMMAND 0
+#define FUELMI_TRAJSMP_STATE 1
+#define FUELMI_TRAJSMP_IN 0
+#define FUELMI_TRAJSMP_PAST 1
+#define FUELMI_TRAJSMP_INVALID 2
+#define FUELMI_TRAJSMP_BADSPLINE 3
+#define FUELMI_TRAJSMP_MAX_CTRL 1024          /* largest max_ctrl and max_yaw_ctrl */
+#define FUELMI_TRAJSMP_MAX_T 65536            /* largest max_t: sample times per problem and call */
+#define FUELMI_TRAJSMP_MAX_SAMPLES 2097152    /* largest n_prob * max_t per call (2^21) */
+typedef struct {
+  int mode;            /* FUELMI_TRAJSMP_COMMAND or FUELMI_TRAJSMP_STATE */
+  int degree;          /* degree of the position spline, 3..5 */
+  int yaw_degree;      /* degree of the yaw spline, 3..5; not read with max_yaw_ctrl == 0 */
+  int max_ctrl;        /* stride of pos_ctrl */
+  int max_yaw_ctrl;    /* stride of yaw_ctrl; 0: no problem has a yaw spline */
+  int max_t;           /* stride of t and of every per-sample output */
+} fuelmi_trajsmp_cfg;
+/* pos_ctrl [n_prob][max_ctrl][3], n_ctrl / knot_span [n_prob]; n_yaw_ctrl / yaw_dt [n_prob] and yaw_ctrl
+ * [n_prob][max_yaw_ctrl], or n_yaw_ctrl NULL; t_stop [n_prob] or NULL; n_t [n_prob], t [n_prob][max_t].  Out, per
+ * sample: status [n_prob][max_t]; pos, vel, acc, jerk [n_prob][max_t][3]; yaw, yawdot, yawddot [n_prob][max_t].  Per
+ * problem: duration [n_prob]; flight [n_prob][8] in and out, or NULL. */
+int fuelmi_map_sample_trajs(fuelmi_map* m, const fuelmi_trajsmp_cfg* cfg, int n_prob, const int* n_ctrl,
+                            const double* pos_ctrl, const double* knot_span, const int* n_yaw_ctrl,
+                            const double* yaw_ctrl, const double* yaw_dt, const double* t_stop, const int* n_t,
+                            const double* t, int* status, double* pos, double* vel, double* acc, double* jerk,
+                            double* yaw, double* yawdot, double* yawddot, double* duration, double* flight);
+/* The device chain optimised batch -> commands / next start states: one problem per candidate of `b` (dim 3), the
+ * position spline read from the variables the batch's last fuelmi_bspline_dev_optimize[_timed] left in device memory
+ * (control points = those variables, knot span = x[nvar-1] under MINTIME and the batch's knot span otherwise).
+ * cfg->degree must be the batch's bspline_degree and cfg->max_ctrl is ignored (it is point_num).  The yaw splines and
+ * the times come from the host; only the results are copied back.  They equal, bit for bit, fuelmi_map_sample_trajs on
+ * the x_out that solve returned.  FUELMI_EINVAL when the batch is not dim 3 or has not been optimised since it was
+ * created or last (re)loaded (the preconditions of fuelmi_bspline_dev_check_trajs).  Runs on the map's stream and waits
+ * for it. */
+int fuelmi_bspline_dev_sample_trajs(fuelmi_bspline_dev* b, const fuelmi_trajsmp_cfg* cfg, const int* n_yaw_ctrl,
+                                    const double* yaw_ctrl, const double* yaw_dt, const double* t_stop, const int* n_t,
+                                    const double* t, int* status, double* pos, double* vel, double* acc, double* jerk,
+                                    double* yaw, double* yawdot, double* yawddot, double* duration, double* flight);
+/* what the kernel needs for cfg (host only, no device needed): out3 = {lanes per problem, dynamic LDS bytes of a
+ * workgroup, largest max_ctrl accepted}.  cfg is checked like above. */
+int fuelmi_traj_sample_plan(const fuelmi_trajsmp_cfg* cfg, int out3[3]);
+
+/* ------------------------------------------------------------------------------------------
  * Map clouds and the known-volume count: the scans of MapROS::publishMapLocal, publishMapAll and publishUnknown
  * (plan_env/src/map_ros.cpp:217-346) as an ordered stream compaction over the state planes the device holds.  No host
  * mirror is read or needed.

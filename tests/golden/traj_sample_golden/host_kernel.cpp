@@ -1,0 +1,156 @@
+// A host build of k_traj_sample's own text (fuel_amd/csrc/traj_sample.hip between "namespace {" and the host code, cut
+// out by tests/golden/check_traj_sample_host_build.py into kernel.inc, with fuel_amd/csrc/spline_internal.h included as
+// it is): a thread per lane, std::barrier for __syncthreads, __shfl as an exchange through a per-wave block behind a
+// per-wave barrier, the LDS block a heap block of exactly the launch's size between two guard zones.  Meant for
+// -fsanitize=address,undefined: a read or write past the knots, the control points, the times or the result arrays (each
+// a heap block of its exact size) is reported by the sanitizer, one inside a guard zone by the check below.  Reads the
+// launches check_traj_sample_host_build.py writes and prints per problem one line (the bits of the duration and of the
+// eight record numbers) and one line per sample slot (the status, then the bits of the fifteen doubles).
+//   host_kernel <in.txt>
+#define __HIP_PLATFORM_AMD__ 1
+#include "fuelmi_internal.h"
+#include <barrier>
+#include <cinttypes>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <memory>
+#include <thread>
+#include <vector>
+using namespace std;
+#undef __launch_bounds__
+#define __launch_bounds__(x)
+struct Idx { int x; };
+static thread_local Idx threadIdx_, blockIdx_;
+#define threadIdx threadIdx_
+#define blockIdx blockIdx_
+static std::barrier<>* g_bar;
+#define __syncthreads() g_bar->arrive_and_wait()
+struct WaveBlock {
+  std::barrier<> bar{64};
+  double d[64];
+  int p[64];
+};
+static WaveBlock* g_waves;
+static inline WaveBlock& my_wave() { return g_waves[threadIdx_.x >> 6]; }
+static double host_shfl(double v, int src) {
+  WaveBlock& w = my_wave();
+  w.d[threadIdx_.x & 63] = v;
+  w.bar.arrive_and_wait();
+  const double r = w.d[src];
+  w.bar.arrive_and_wait();
+  return r;
+}
+static int host_shfl(int v, int src) {
+  WaveBlock& w = my_wave();
+  w.p[threadIdx_.x & 63] = v;
+  w.bar.arrive_and_wait();
+  const int r = w.p[src];
+  w.bar.arrive_and_wait();
+  return r;
+}
+#define __shfl host_shfl
+void fuelmi_set_error(const char*, ...) {}
+static unsigned char* g_lds;  // the launch's LDS block (kernel.inc: `unsigned char* smem_raw = g_lds;`)
+#include "spline_internal.h"
+#include "kernel.inc"
+}  // namespace (kernel.inc leaves it open)
+
+static unsigned long long bits(double v) {
+  unsigned long long b;
+  memcpy(&b, &v, 8);
+  return b;
+}
+static double num(std::ifstream& in) {
+  std::string s;
+  in >> s;
+  return strtod(s.c_str(), nullptr);
+}
+
+int main(int argc, char** argv) {
+  if (argc < 2) return 1;
+  std::ifstream in(argv[1]);
+  int n_launch;
+  in >> n_launch;
+  constexpr size_t GUARD = 256;
+  for (int l = 0; l < n_launch; ++l) {
+    TrajSmpArgs A;
+    memset(&A, 0, sizeof(A));
+    fuelmi_trajsmp_cfg& c = A.cfg;
+    int n, has_yaw, has_stop, has_flight, device_batch;
+    in >> c.mode >> c.degree >> c.yaw_degree >> c.max_ctrl >> c.max_yaw_ctrl >> c.max_t >> n >> has_yaw >> has_stop >>
+        has_flight >> device_batch;
+    const size_t s = (size_t)n * c.max_t;
+    // (1e300 / -7: a read past a problem's own points or times shows in the results)
+    std::vector<int> nc(n), ny(n), nt(n), status(s, -77);
+    std::vector<double> knot(n), pos((size_t)n * c.max_ctrl * 3, 1e300), ydt(n), yaw((size_t)n * c.max_yaw_ctrl, 1e300),
+        stop(n), t(s, 1e300), flight((size_t)n * 8), dur(n, -7.0);
+    std::vector<double> o3[4], o1[3];
+    for (auto& v : o3) v.assign(3 * s, -7.0);
+    for (auto& v : o1) v.assign(s, -7.0);
+    for (int b = 0; b < n; ++b) {
+      in >> nc[b];
+      knot[b] = num(in);
+      for (int k = 0; k < 3 * nc[b] && k < 3 * c.max_ctrl; ++k) pos[(size_t)b * c.max_ctrl * 3 + k] = num(in);
+      in >> ny[b];
+      ydt[b] = num(in);
+      for (int k = 0; k < ny[b]; ++k) yaw[(size_t)b * c.max_yaw_ctrl + k] = num(in);
+      stop[b] = num(in);
+      for (int k = 0; k < 8; ++k) flight[(size_t)b * 8 + k] = num(in);
+      in >> nt[b];
+      for (int k = 0; k < nt[b]; ++k) t[(size_t)b * c.max_t + k] = num(in);
+    }
+    A.n_prob = n;
+    if (device_batch)  // every problem has the stride's number of points, as in a batch
+      A.n_ctrl = nullptr, A.n_ctrl_all = c.max_ctrl;
+    else
+      A.n_ctrl = nc.data();
+    A.pos = pos.data(), A.pos_stride = (size_t)c.max_ctrl * 3, A.knot = knot.data(), A.knot_stride = 1;
+    if (has_yaw) A.n_yaw = ny.data(), A.yaw = yaw.data(), A.yaw_dt = ydt.data();
+    if (has_stop) A.t_stop = stop.data();
+    A.n_t = nt.data(), A.t = t.data();
+    if (has_flight) A.flight = flight.data();
+    A.status = status.data(), A.o_pos = o3[0].data(), A.o_vel = o3[1].data(), A.o_acc = o3[2].data(), A.o_jerk = o3[3].data();
+    A.o_yaw = o1[0].data(), A.o_yawdot = o1[1].data(), A.o_yawddot = o1[2].data(), A.duration = dur.data();
+    const size_t lds = ts_lds(c);
+    const int nthr = TS_WIN * TS_WAVES;
+    for (int blk = 0; blk < (n + TS_WAVES - 1) / TS_WAVES; ++blk) {
+      std::unique_ptr<unsigned char[]> block(new unsigned char[lds + 2 * GUARD]);
+      memset(block.get(), 0xA5, lds + 2 * GUARD);
+      g_lds = block.get() + GUARD;
+      std::barrier<> bar(nthr);
+      g_bar = &bar;
+      std::unique_ptr<WaveBlock[]> waves(new WaveBlock[TS_WAVES]);
+      g_waves = waves.get();
+      std::vector<std::thread> th;
+      for (int i = 0; i < nthr; ++i)
+        th.emplace_back([&, i, blk] {
+          threadIdx_.x = i;
+          blockIdx_.x = blk;
+          k_traj_sample(A);
+          bar.arrive_and_drop();
+        });
+      for (auto& x : th) x.join();
+      for (size_t i = 0; i < GUARD; ++i)
+        if (block[i] != 0xA5 || block[GUARD + lds + i] != 0xA5) {
+          std::printf("GUARD HIT\n");
+          return 9;
+        }
+    }
+    for (int b = 0; b < n; ++b) {
+      std::printf("P %016llx", bits(dur[b]));
+      for (int k = 0; k < 8; ++k) std::printf(" %016llx", bits(flight[(size_t)b * 8 + k]));
+      std::printf("\n");
+      for (int k = 0; k < c.max_t; ++k) {
+        const size_t e = (size_t)b * c.max_t + k;
+        std::printf("%d", status[e]);
+        for (auto& v : o3)
+          for (int a = 0; a < 3; ++a) std::printf(" %016llx", bits(v[3 * e + a]));
+        for (auto& v : o1) std::printf(" %016llx", bits(v[e]));
+        std::printf("\n");
+      }
+    }
+  }
+  return 0;
+}
