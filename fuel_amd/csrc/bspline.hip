@@ -44,15 +44,13 @@ struct fuelmi_bspline_dev {
   // directly, and the event behind each launch
   double* pin_out[2] = {nullptr, nullptr};
   hipEvent_t ev_out[2] = {nullptr, nullptr};
-  double* fit_in = nullptr;  // fuelmi_bspline_dev_load_samples staging: ts | points | derivs
-  size_t fit_cap = 0;
   bool opt_valid = false;    // opt_x holds the solve of what the batch holds now (a reload clears it)
-  unsigned char* yaw_dev = nullptr;  // fuelmi_bspline_dev_plan_yaws: start | end | results (grow-only)
-  size_t yaw_cap = 0;
-  unsigned char* chk_dev = nullptr;  // fuelmi_bspline_dev_check_trajs: t_now | results (grow-only)
-  size_t chk_cap = 0;
-  unsigned char* smp_dev = nullptr;  // fuelmi_bspline_dev_sample_trajs: yaw splines, times | results (grow-only)
-  size_t smp_cap = 0;
+  // per-call scratch, reserved on the map's stream (every kernel that reads it runs there); no pointer into it
+  // outlives the call that carved it
+  DevScratch fit_in;   // fuelmi_bspline_dev_load_*: ts | points | derivs, then the loader's own arrays
+  DevScratch yaw_dev;  // fuelmi_bspline_dev_plan_yaws: start | end | results
+  DevScratch chk_dev;  // fuelmi_bspline_dev_check_trajs: t_now | results
+  DevScratch smp_dev;  // fuelmi_bspline_dev_sample_trajs: yaw splines, times | results
 };
 
 // 64-lane sum on the DPP data path (no LDS crossbar round trips): quads, half rows, rows, then the two
@@ -984,6 +982,7 @@ extern "C" void fuelmi_bspline_dev_destroy(fuelmi_bspline_dev* b) {
       }
   }
   for (void* p : b->allocs) (void)hipFree(p);
+  for (DevScratch* sc : {&b->fit_in, &b->yaw_dev, &b->chk_dev, &b->smp_dev}) sc->release();
   for (int k = 0; k < 2; ++k) {
     if (b->pin_out[k]) (void)hipHostFree(b->pin_out[k]);
     if (b->ev_out[k]) (void)hipEventDestroy(b->ev_out[k]);
@@ -1381,6 +1380,36 @@ int fit_launch(fuelmi_map* m, const FitArgs& F, hipStream_t st = nullptr) {
   HIPCHK(hipGetLastError());
   return FUELMI_OK;
 }
+
+// the fit of device samples (A.N - degree + 1 per candidate) into the batch's own state; skip: null, or [C] with 1
+// where a candidate is left as it is
+FitArgs fit_args(const fuelmi_bspline_dev* b, double* ts, double* points, double* derivs, int* skip) {
+  const BsplineArgs& A = b->a;
+  FitArgs F;
+  memset(&F, 0, sizeof(F));
+  F.C = A.C, F.K = A.N - A.cfg.bspline_degree + 1, F.degree = A.cfg.bspline_degree;
+  F.ts = ts;
+  F.points = points;
+  F.derivs = derivs;
+  F.ctrl = const_cast<double*>(A.x);
+  F.stride = A.nvar;
+  F.write_dt = (A.cost_function & FUELMI_COST_MINTIME) ? 1 : 0;
+  F.knot_span = const_cast<double*>(A.knot_span);
+  F.pt_dist = const_cast<double*>(A.pt_dist);
+  F.start_state = const_cast<double*>(A.start_state);
+  F.end_state = const_cast<double*>(A.end_state);
+  F.skip = skip;
+  return F;
+}
+
+// the position splines the last solve left on the device: control points in the variables, the knot span behind them
+// (MINTIME) or the batch's own
+SplineSrc opt_spline_src(const fuelmi_bspline_dev* b) {
+  const BsplineArgs& A = b->a;
+  const size_t nvar = (size_t)A.nvar;
+  if (A.cost_function & FUELMI_COST_MINTIME) return {nullptr, A.N, b->opt_x, nvar, b->opt_x + (A.nvar - 1), nvar};
+  return {nullptr, A.N, b->opt_x, nvar, A.knot_span, 1};
+}
 }  // namespace
 
 extern "C" int fuelmi_bspline_parameterize(fuelmi_map* m, int n_traj, int n_points, int degree, const double* ts,
@@ -1467,30 +1496,16 @@ extern "C" int fuelmi_bspline_dev_load_samples(fuelmi_bspline_dev* b, int n_poin
   HIPCHK(hipSetDevice(m->device));
   const size_t C = (size_t)A.C, K = (size_t)n_points;
   const size_t b_ts = C * sizeof(double), b_pts = C * K * 3 * sizeof(double), b_der = C * 12 * sizeof(double);
-  if (b_ts + b_pts + b_der > b->fit_cap) {
-    void* d = nullptr;
-    HIPCHK(hipMalloc(&d, b_ts + b_pts + b_der));
-    b->allocs.push_back(d);
-    b->fit_in = static_cast<double*>(d);
-    b->fit_cap = b_ts + b_pts + b_der;
+  {
+    const int rc = b->fit_in.reserve(m->stream, b_ts + b_pts + b_der);
+    if (rc) return rc;
   }
-  unsigned char* d = reinterpret_cast<unsigned char*>(b->fit_in);
+  unsigned char* d = b->fit_in.base();
   HIPCHK(hipMemcpyAsync(d, ts, b_ts, hipMemcpyHostToDevice, m->stream));
   HIPCHK(hipMemcpyAsync(d + b_ts, points, b_pts, hipMemcpyHostToDevice, m->stream));
   HIPCHK(hipMemcpyAsync(d + b_ts + b_pts, derivs, b_der, hipMemcpyHostToDevice, m->stream));
-  FitArgs F;
-  memset(&F, 0, sizeof(F));
-  F.C = A.C, F.K = n_points, F.degree = degree;
-  F.ts = reinterpret_cast<double*>(d);
-  F.points = reinterpret_cast<double*>(d + b_ts);
-  F.derivs = reinterpret_cast<double*>(d + b_ts + b_pts);
-  F.ctrl = const_cast<double*>(A.x);
-  F.stride = A.nvar;
-  F.write_dt = (A.cost_function & FUELMI_COST_MINTIME) ? 1 : 0;
-  F.knot_span = const_cast<double*>(A.knot_span);
-  F.pt_dist = const_cast<double*>(A.pt_dist);
-  F.start_state = const_cast<double*>(A.start_state);
-  F.end_state = const_cast<double*>(A.end_state);
+  const FitArgs F = fit_args(b, reinterpret_cast<double*>(d), reinterpret_cast<double*>(d + b_ts),
+                             reinterpret_cast<double*>(d + b_ts + b_pts), nullptr);
   StageScope sc(m, FUELMI_K_BSPLINE);
   return fit_launch(m, F);
 }
@@ -1516,64 +1531,44 @@ extern "C" int fuelmi_bspline_dev_load_waypoints(fuelmi_bspline_dev* b, const fu
   b->opt_valid = false;
   HIPCHK(hipSetDevice(m->device));
   const size_t C = (size_t)A.C, K = (size_t)n_points, maxw = (size_t)wc.max_way_points;
-  auto pad = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  const size_t b_ts = C * sizeof(double), b_pts = C * K * 3 * sizeof(double), b_der = C * 12 * sizeof(double);
-  const size_t fit_bytes = pad(b_ts + b_pts + b_der);  // the layout fuelmi_bspline_dev_load_samples stages
-  const size_t b_int = pad(C * sizeof(int)), b_dbl = pad(C * sizeof(double)), b_way = pad(C * maxw * 3 * sizeof(double)),
-               b_v3 = pad(C * 3 * sizeof(double));
-  const size_t total = fit_bytes + 4 * b_int + 2 * b_dbl + b_way + 2 * b_v3;
-  if (total > b->fit_cap) {
-    void* d = nullptr;
-    HIPCHK(hipMalloc(&d, total));
-    b->allocs.push_back(d);
-    b->fit_in = static_cast<double*>(d);
-    b->fit_cap = total;
-  }
-  unsigned char* d = reinterpret_cast<unsigned char*>(b->fit_in);
-  unsigned char* at = d + fit_bytes;
-  auto take = [&](size_t bytes) {
-    unsigned char* p = at;
-    at += bytes;
-    return p;
-  };
   WpTrajArgs W;
   memset(&W, 0, sizeof(W));
+  double* d_fit;  // ts | points | derivs: the layout fuelmi_bspline_dev_load_samples stages
+  int* d_nway;
+  double *d_way, *d_vel, *d_acc;
+  auto layout = [&](unsigned char* base) {
+    BlockLayout L(base, 16);
+    d_fit = L.take<double>(C * (1 + K * 3 + 12));
+    d_nway = L.take<int>(C);
+    d_way = L.take<double>(C * maxw * 3);
+    d_vel = L.take<double>(C * 3);
+    d_acc = L.take<double>(C * 3);
+    W.status = L.take<int>(C);
+    W.seg_num = L.take<int>(C);
+    W.n_samples = L.take<int>(C);
+    W.duration = L.take<double>(C);
+    W.length = L.take<double>(C);
+    return L.size();
+  };
+  hipStream_t st = m->stream;
+  {
+    const int rc = b->fit_in.reserve(st, layout(nullptr));
+    if (rc) return rc;
+  }
+  layout(b->fit_in.base());
   W.n_prob = A.C;
   W.maxw = wc.max_way_points;
   W.max_vel = wc.max_vel, W.ctrl_pt_dist = wc.ctrl_pt_dist;
   W.min_seg = wc.min_seg, W.forced_seg = seg, W.max_samples = n_points;
-  int* d_nway = reinterpret_cast<int*>(take(b_int));
-  double* d_way = reinterpret_cast<double*>(take(b_way));
-  double* d_vel = reinterpret_cast<double*>(take(b_v3));
-  double* d_acc = reinterpret_cast<double*>(take(b_v3));
-  hipStream_t st = m->stream;
   HIPCHK(hipMemcpyAsync(d_nway, n_way, C * sizeof(int), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_way, way_xyz, C * maxw * 3 * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_vel, vel_xyz, C * 3 * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_acc, acc_xyz, C * 3 * sizeof(double), hipMemcpyHostToDevice, st));
   W.n_way = d_nway, W.way = d_way, W.vel = d_vel, W.acc = d_acc;
-  W.status = reinterpret_cast<int*>(take(b_int));
-  W.seg_num = reinterpret_cast<int*>(take(b_int));
-  W.n_samples = reinterpret_cast<int*>(take(b_int));
-  W.duration = reinterpret_cast<double*>(take(b_dbl));
-  W.length = reinterpret_cast<double*>(take(b_dbl));
-  W.dt = reinterpret_cast<double*>(d);  // the fit's knot spans
-  W.samples = reinterpret_cast<double*>(d + b_ts);
-  W.derivs = reinterpret_cast<double*>(d + b_ts + b_pts);
-  FitArgs F;
-  memset(&F, 0, sizeof(F));
-  F.C = A.C, F.K = n_points, F.degree = degree;
-  F.ts = W.dt;
-  F.points = W.samples;
-  F.derivs = W.derivs;
-  F.ctrl = const_cast<double*>(A.x);
-  F.stride = A.nvar;
-  F.write_dt = (A.cost_function & FUELMI_COST_MINTIME) ? 1 : 0;
-  F.knot_span = const_cast<double*>(A.knot_span);
-  F.pt_dist = const_cast<double*>(A.pt_dist);
-  F.start_state = const_cast<double*>(A.start_state);
-  F.end_state = const_cast<double*>(A.end_state);
-  F.skip = W.status;
+  W.dt = d_fit;  // the fit's knot spans
+  W.samples = d_fit + C;
+  W.derivs = d_fit + C + C * K * 3;
+  const FitArgs F = fit_args(b, W.dt, W.samples, W.derivs, W.status);
   {
     StageScope sc(m, FUELMI_K_BSPLINE);
     const int rcw = wptraj_launch(st, W);
@@ -1614,60 +1609,40 @@ extern "C" int fuelmi_bspline_dev_load_kino(fuelmi_bspline_dev* b, const fuelmi_
   b->opt_valid = false;
   HIPCHK(hipSetDevice(m->device));
   const size_t C = (size_t)A.C, K = (size_t)n_points;
-  auto pad = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  const size_t b_ts = C * sizeof(double), b_pts = C * K * 3 * sizeof(double), b_der = C * 12 * sizeof(double);
-  if (b_ts + b_pts + b_der > b->fit_cap) {
-    void* d = nullptr;
-    HIPCHK(hipMalloc(&d, b_ts + b_pts + b_der));
-    b->allocs.push_back(d);
-    b->fit_in = static_cast<double*>(d);
-    b->fit_cap = b_ts + b_pts + b_der;
-  }
-  unsigned char* d = reinterpret_cast<unsigned char*>(b->fit_in);
-  const size_t b_int = pad(C * sizeof(int)), b_dbl = pad(C * sizeof(double)), b_12 = pad(C * 12 * sizeof(double));
-  KinoArgs W;
-  unsigned char* io = nullptr;
+  hipStream_t st = m->stream;
   {
-    const int rc = kino_prepare(m, &kc, A.C, start_xyz, start_vel, start_acc, goal_xyz, goal_vel,
-                                9 * b_int + 2 * b_dbl + b_12, W, &io);
+    const int rc = b->fit_in.reserve(st, C * (1 + K * 3 + 12) * sizeof(double));
     if (rc) return rc;
   }
-  auto take = [&](size_t bytes) {
-    unsigned char* p = io;
-    io += bytes;
-    return p;
+  double* d_fit = static_cast<double*>(b->fit_in.p);  // ts | points | derivs
+  KinoArgs W;
+  auto layout = [&](unsigned char* base) {  // the results that do not go to the fit
+    BlockLayout L(base, 16);
+    W.status = L.take<int>(C);
+    W.which = L.take<int>(C);
+    W.iter_num = L.take<int>(C);
+    W.use_node_num = L.take<int>(C);
+    W.n_nodes = L.take<int>(C);
+    W.shot = L.take<int>(C);
+    W.seg_num = L.take<int>(C);
+    W.n_samples = L.take<int>(C);
+    W.skip = L.take<int>(C);
+    W.t_shot = L.take<double>(C);
+    W.T_sum = L.take<double>(C);
+    W.coef_shot = L.take<double>(C * 12);
+    return L.size();
   };
+  unsigned char* io = nullptr;
+  {
+    const int rc = kino_prepare(m, &kc, A.C, start_xyz, start_vel, start_acc, goal_xyz, goal_vel, layout(nullptr), W, &io);
+    if (rc) return rc;
+  }
+  layout(io);
   W.load_points = n_points;
-  W.status = reinterpret_cast<int*>(take(b_int));
-  W.which = reinterpret_cast<int*>(take(b_int));
-  W.iter_num = reinterpret_cast<int*>(take(b_int));
-  W.use_node_num = reinterpret_cast<int*>(take(b_int));
-  W.n_nodes = reinterpret_cast<int*>(take(b_int));
-  W.shot = reinterpret_cast<int*>(take(b_int));
-  W.seg_num = reinterpret_cast<int*>(take(b_int));
-  W.n_samples = reinterpret_cast<int*>(take(b_int));
-  W.skip = reinterpret_cast<int*>(take(b_int));
-  W.t_shot = reinterpret_cast<double*>(take(b_dbl));
-  W.T_sum = reinterpret_cast<double*>(take(b_dbl));
-  W.coef_shot = reinterpret_cast<double*>(take(b_12));
-  W.ts_out = reinterpret_cast<double*>(d);  // the fit's knot spans
-  W.samples = reinterpret_cast<double*>(d + b_ts);
-  W.derivs = reinterpret_cast<double*>(d + b_ts + b_pts);
-  FitArgs F;
-  memset(&F, 0, sizeof(F));
-  F.C = A.C, F.K = n_points, F.degree = degree;
-  F.ts = W.ts_out;
-  F.points = W.samples;
-  F.derivs = W.derivs;
-  F.ctrl = const_cast<double*>(A.x);
-  F.stride = A.nvar;
-  F.write_dt = (A.cost_function & FUELMI_COST_MINTIME) ? 1 : 0;
-  F.knot_span = const_cast<double*>(A.knot_span);
-  F.pt_dist = const_cast<double*>(A.pt_dist);
-  F.start_state = const_cast<double*>(A.start_state);
-  F.end_state = const_cast<double*>(A.end_state);
-  F.skip = W.skip;
-  hipStream_t st = m->stream;
+  W.ts_out = d_fit;  // the fit's knot spans
+  W.samples = d_fit + C;
+  W.derivs = d_fit + C + C * K * 3;
+  const FitArgs F = fit_args(b, W.ts_out, W.samples, W.derivs, W.skip);
   {
     const int rck = kino_launch(m, W);  // (outside the scope: the search is no spline stage)
     if (rck) return rck;
@@ -1709,22 +1684,24 @@ extern "C" int fuelmi_bspline_dev_plan_yaws(fuelmi_bspline_dev* b, const fuelmi_
   ARGCHK(m);
   HIPCHK(hipSetDevice(m->device));
   const size_t C = (size_t)A.C;
-  auto pad = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  const size_t b_s3 = pad(C * 3 * sizeof(double)), b_dbl = pad(C * sizeof(double));
   YawArgs Y;
   memset(&Y, 0, sizeof(Y));
   const size_t b_out = yaw_out_bytes(&yc, A.C, Y, nullptr, yawdot_ctrl != nullptr, yawddot_ctrl != nullptr);
-  if (b_s3 + b_dbl + b_out > b->yaw_cap) {
-    void* d = nullptr;
-    HIPCHK(hipMalloc(&d, b_s3 + b_dbl + b_out));
-    b->allocs.push_back(d);
-    b->yaw_dev = static_cast<unsigned char*>(d);
-    b->yaw_cap = b_s3 + b_dbl + b_out;
-  }
+  double *d_start, *d_end;
+  unsigned char* d_out;
+  auto layout = [&](unsigned char* base) {
+    BlockLayout L(base, 16);
+    d_start = L.take<double>(C * 3);
+    d_end = L.take<double>(C);
+    d_out = L.take<unsigned char>(b_out);
+    return L.size();
+  };
   hipStream_t st = m->stream;
-  double* d_start = reinterpret_cast<double*>(b->yaw_dev);
-  double* d_end = reinterpret_cast<double*>(b->yaw_dev + b_s3);
-  unsigned char* d_out = b->yaw_dev + b_s3 + b_dbl;
+  {
+    const int rc = b->yaw_dev.reserve(st, layout(nullptr));
+    if (rc) return rc;
+  }
+  layout(b->yaw_dev.base());
   HIPCHK(hipMemcpyAsync(d_start, start_yaw, C * 3 * sizeof(double), hipMemcpyHostToDevice, st));
   if (end_yaw)
     HIPCHK(hipMemcpyAsync(d_end, end_yaw, C * sizeof(double), hipMemcpyHostToDevice, st));
@@ -1733,12 +1710,7 @@ extern "C" int fuelmi_bspline_dev_plan_yaws(fuelmi_bspline_dev* b, const fuelmi_
   Y.cfg = yc;
   Y.ld_smooth = A.cfg.ld_smooth, Y.ld_start = A.cfg.ld_start, Y.ld_end = A.cfg.ld_end, Y.ld_waypt = A.cfg.ld_waypt;
   Y.n_prob = A.C;
-  Y.n_ctrl = nullptr, Y.n_ctrl_all = A.N;
-  Y.pos = b->opt_x, Y.pos_stride = (size_t)A.nvar;
-  if (A.cost_function & FUELMI_COST_MINTIME)
-    Y.knot = b->opt_x + (A.nvar - 1), Y.knot_stride = (size_t)A.nvar;
-  else
-    Y.knot = A.knot_span, Y.knot_stride = 1;
+  Y.src = opt_spline_src(b);
   Y.start_yaw = d_start, Y.end_yaw = d_end;
   yaw_out_bytes(&yc, A.C, Y, d_out, yawdot_ctrl != nullptr, yawddot_ctrl != nullptr);
   {
@@ -1775,30 +1747,27 @@ extern "C" int fuelmi_bspline_dev_check_trajs(fuelmi_bspline_dev* b, const fuelm
   ARGCHK(m);
   HIPCHK(hipSetDevice(m->device));
   const size_t C = (size_t)A.C;
-  auto pad = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  const size_t b_dbl = pad(C * sizeof(double));
   TrajChkArgs T;
   memset(&T, 0, sizeof(T));
   const size_t b_out = trajchk_out_bytes(A.C, T, nullptr);
-  if (b_dbl + b_out > b->chk_cap) {
-    void* d = nullptr;
-    HIPCHK(hipMalloc(&d, b_dbl + b_out));
-    b->allocs.push_back(d);
-    b->chk_dev = static_cast<unsigned char*>(d);
-    b->chk_cap = b_dbl + b_out;
-  }
+  double* d_now;
+  unsigned char* d_out;
+  auto layout = [&](unsigned char* base) {
+    BlockLayout L(base, 16);
+    d_now = L.take<double>(C);
+    d_out = L.take<unsigned char>(b_out);
+    return L.size();
+  };
   hipStream_t st = m->stream;
-  double* d_now = reinterpret_cast<double*>(b->chk_dev);
-  unsigned char* d_out = b->chk_dev + b_dbl;
+  {
+    const int rc = b->chk_dev.reserve(st, layout(nullptr));
+    if (rc) return rc;
+  }
+  layout(b->chk_dev.base());
   HIPCHK(hipMemcpyAsync(d_now, t_now, C * sizeof(double), hipMemcpyHostToDevice, st));
   T.cfg = tc;
   T.n_prob = A.C;
-  T.n_ctrl = nullptr, T.n_ctrl_all = A.N;
-  T.pos = b->opt_x, T.pos_stride = (size_t)A.nvar;
-  if (A.cost_function & FUELMI_COST_MINTIME)
-    T.knot = b->opt_x + (A.nvar - 1), T.knot_stride = (size_t)A.nvar;
-  else
-    T.knot = A.knot_span, T.knot_stride = 1;
+  T.src = opt_spline_src(b);
   T.t_now = d_now;
   T.infl = m->infl_bits.p;
   trajchk_out_bytes(A.C, T, d_out);
@@ -1838,21 +1807,12 @@ extern "C" int fuelmi_bspline_dev_sample_trajs(fuelmi_bspline_dev* b, const fuel
   fuelmi_map* m = b->map;
   ARGCHK(m);
   HIPCHK(hipSetDevice(m->device));
-  const size_t need = trajsmp_bytes(&sc, A.C, false, io);
-  if (need > b->smp_cap) {
-    void* d = nullptr;
-    HIPCHK(hipMalloc(&d, need));
-    b->allocs.push_back(d);
-    b->smp_dev = static_cast<unsigned char*>(d);
-    b->smp_cap = need;
+  {
+    const int rc = b->smp_dev.reserve(m->stream, trajsmp_bytes(&sc, A.C, false, io));
+    if (rc) return rc;
   }
   TrajSmpArgs T;
   memset(&T, 0, sizeof(T));
-  T.n_ctrl = nullptr, T.n_ctrl_all = A.N;
-  T.pos = b->opt_x, T.pos_stride = (size_t)A.nvar;
-  if (A.cost_function & FUELMI_COST_MINTIME)
-    T.knot = b->opt_x + (A.nvar - 1), T.knot_stride = (size_t)A.nvar;
-  else
-    T.knot = A.knot_span, T.knot_stride = 1;
-  return trajsmp_run(m->stream, &sc, A.C, false, io, T, b->smp_dev);
+  T.src = opt_spline_src(b);
+  return trajsmp_run(m->stream, &sc, A.C, false, io, T, b->smp_dev.base());
 }

@@ -608,6 +608,14 @@ __device__ __forceinline__ void pos_to_idx(const Geo& g, const double p[3], int 
   for (int k = 0; k < 3; ++k) id[k] = (int)floor((p[k] - g.org[k]) * g.res_inv);
 }
 __device__ __forceinline__ bool bit_at(const u64* pl, long a) { return (pl[a >> 6] >> (a & 63)) & 1ull; }
+// the plane's bit at a position: getInflateOccupancy(pos) == 1 on the inflated plane, getOccupancy(pos) == UNKNOWN on
+// the unknown one; a position outside the map reads -1 in both and passes
+__device__ __forceinline__ bool plane_at_pos(const Geo& g, const u64* pl, const double p[3]) {
+  int id[3];
+  pos_to_idx(g, p, id);
+  if (!idx_in_map(g, id)) return false;
+  return bit_at(pl, (long)id[0] * g.nyz + (long)id[1] * g.nz + id[2]);
+}
 
 // RayCaster::input + nextId loop (plan_env/src/raycast.cpp:374-407): true iff no visited voxel is inflated or
 // unknown; the walk starts in start's voxel and stops before end's voxel.  kBox: a voxel outside the index box

@@ -41,6 +41,8 @@ void fuelmi_set_error(const char* fmt, ...);
     }                                                                       \
   } while (0)
 
+#include "scratch.h"  // DevScratch, BlockLayout
+
 // ---- grid geometry passed to kernels by value -------------------------------------------------
 struct Geo {
   int nx, ny, nz;
@@ -212,32 +214,21 @@ struct fuelmi_map {
     bool* sticky;
   };
   std::vector<LateReader> late_readers;
-  // grow-only device scratch of fuelmi_map_path_costs (path_cost.hip)
-  void* path_dev = nullptr;
-  size_t path_dev_bytes = 0;
+  // The batched planner calls' device scratch: one grow-only pool per call (DevScratch), carved per call (BlockLayout).
+  // The pools stay separate because one call's results outlive another call: goal_path.hip reads what path_cost_enqueue
+  // left in path_dev, and kino_prepare hands a part of kino_dev to a B-spline batch.
+  DevScratch path_dev;     // fuelmi_map_path_costs (path_cost.hip)
+  DevScratch refine_dev;   // fuelmi_map_refine_tours (refine.hip): problems in, choices / costs out
+  DevScratch goal_dev;     // fuelmi_map_goal_paths (goal_path.hip): results out
+  DevScratch kino_dev;     // fuelmi_map_kino_paths (kino_path.hip): inputs, results, node pools, heaps, hashes
+  DevScratch trajchk_dev;  // fuelmi_map_check_trajs (traj_check.hip): problems in, results out
+  DevScratch trajsmp_dev;  // fuelmi_map_sample_trajs (traj_sample.hip): problems in, results out
+  DevScratch cloud_dev;    // fuelmi_map_extract_cloud (map_cloud.hip): the total, the workgroup words, the points
   int path_stats[4] = {0, 0, 0, 0};  // fuelmi_map_path_stats
-  // grow-only device scratch of fuelmi_map_refine_tours (refine.hip): problems in, choices / costs out
-  void* refine_dev = nullptr;
-  size_t refine_dev_bytes = 0;
-  // grow-only device scratch of fuelmi_map_goal_paths (goal_path.hip): results out; the events that split its time
-  void* goal_dev = nullptr;
-  size_t goal_dev_bytes = 0;
-  hipEvent_t goal_ev[3] = {nullptr, nullptr, nullptr};
+  hipEvent_t goal_ev[3] = {nullptr, nullptr, nullptr};  // the events that split the goal-path call's time
   double goal_ms[2] = {0.0, 0.0};  // fuelmi_map_goal_path_times
-  // grow-only device scratch of fuelmi_map_kino_paths (kino_path.hip): inputs, results, node pools, heaps, hashes
-  void* kino_dev = nullptr;
-  size_t kino_dev_bytes = 0;
   std::vector<double> kino_host;  // the inputs and primitive lists of the last call, alive until its copies have run
-  // grow-only device scratch of fuelmi_map_check_trajs (traj_check.hip): problems in, results out
-  void* trajchk_dev = nullptr;
-  size_t trajchk_dev_bytes = 0;
-  // grow-only device scratch of fuelmi_map_sample_trajs (traj_sample.hip): problems in, results out
-  void* trajsmp_dev = nullptr;
-  size_t trajsmp_dev_bytes = 0;
-  // grow-only device scratch of fuelmi_map_extract_cloud (map_cloud.hip): the total, the workgroup words, the points;
-  // the pinned word the scan writes the total to; the events that split its time
-  void* cloud_dev = nullptr;
-  size_t cloud_dev_bytes = 0;
+  // the cloud call's pinned word the scan writes the total to; the events that split its time
   u32* cloud_pin = nullptr;
   hipEvent_t cloud_ev[4] = {nullptr, nullptr, nullptr, nullptr};
   double cloud_ms[3] = {0.0, 0.0, 0.0};  // fuelmi_map_cloud_times
@@ -518,8 +509,7 @@ __device__ __forceinline__ double dist_with_grad_dev(const Geo& g, const float* 
 int esdf_update(fuelmi_map* m);
 size_t esdf_handover_bytes(int nx, int ny, int nz);  // esdf_tmp16 of a grid (0: the packed family cannot run)
 int insert_points(fuelmi_map* m, const float* xyz, int stride_bytes, int n, const double cam[3]);
-void path_cost_release(fuelmi_map* m);  // the path and refinement scratch
-void goal_path_release(fuelmi_map* m);  // the goal-path scratch and its events (goal_path.hip)
+void goal_path_release(fuelmi_map* m);  // the goal-path call's events (goal_path.hip)
 // k_waypoint_traj (waypoint_traj.hip): one problem per workgroup; every pointer addresses memory the device can reach
 struct WpTrajArgs {
   int n_prob;
@@ -545,17 +535,21 @@ struct WpTrajArgs {
 int wptraj_check(const fuelmi_wptraj_cfg* cfg, int n_prob, const int* n_way, const double* way_xyz,
                  const double* vel_xyz, const double* acc_xyz);
 int wptraj_launch(hipStream_t st, const WpTrajArgs& W);
-// k_yaw_plan (yaw_plan.hip): one problem per wave; every pointer addresses memory the device can reach
-struct YawArgs {
-  fuelmi_yaw_cfg cfg;
-  double ld_smooth, ld_start, ld_end, ld_waypt;
-  int n_prob;
+// the position splines of a batch of problems, as k_yaw_plan, k_traj_check and k_traj_sample read them
+struct SplineSrc {
   const int* n_ctrl;        // [n], or null: every problem has n_ctrl_all control points
   int n_ctrl_all;
   const double* pos;        // problem b: [n_ctrl][3] at pos + b * pos_stride
   size_t pos_stride;
   const double* knot;       // problem b: knot[b * knot_stride]
   size_t knot_stride;
+};
+// k_yaw_plan (yaw_plan.hip): one problem per wave; every pointer addresses memory the device can reach
+struct YawArgs {
+  fuelmi_yaw_cfg cfg;
+  double ld_smooth, ld_start, ld_end, ld_waypt;
+  int n_prob;
+  SplineSrc src;
   const double* start_yaw;  // [n][3]
   const double* end_yaw;    // [n] (EXPLORE)
   int* status;
@@ -571,8 +565,8 @@ struct YawArgs {
   double* yawddot_ctrl;     // [n][max_seg + 1] or null
 };
 // the host checks of fuelmi_map_plan_yaws / fuelmi_bspline_dev_plan_yaws (n_ctrl null: a device batch, whose control
-// points and knot spans the host does not see); the result block's layout (base null: only its size); the launch on
-// stream st; the result block -> the caller's arrays (FUELMI_ELIMIT when a problem's status is -1)
+// points and knot spans the host does not see); the result block's layout (a BlockLayout; base null: only its size); the
+// launch on stream st; the result block -> the caller's arrays (FUELMI_ELIMIT when a problem's status is -1)
 int yaw_check(const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob, const int* n_ctrl,
               const double* pos_ctrl, const double* knot_span, const double* start_yaw, const double* end_yaw);
 size_t yaw_out_bytes(const fuelmi_yaw_cfg* cfg, int n_prob, YawArgs& Y, unsigned char* base, bool dot, bool ddot);
@@ -584,12 +578,7 @@ int yaw_copy_out(const fuelmi_yaw_cfg* cfg, int n_prob, const YawArgs& H, int* s
 struct TrajChkArgs {
   fuelmi_trajchk_cfg cfg;
   int n_prob;
-  const int* n_ctrl;        // [n], or null: every problem has n_ctrl_all control points
-  int n_ctrl_all;
-  const double* pos;        // problem b: [n_ctrl][3] at pos + b * pos_stride
-  size_t pos_stride;
-  const double* knot;       // problem b: knot[b * knot_stride]
-  size_t knot_stride;
+  SplineSrc src;
   const double* t_now;      // [n]
   const u64* infl;          // the map's inflated plane
   int* status;
@@ -611,17 +600,11 @@ size_t trajchk_out_bytes(int n_prob, TrajChkArgs& T, unsigned char* base);
 int trajchk_launch(hipStream_t st, const Geo& g, const TrajChkArgs& T);
 int trajchk_copy_out(int n_prob, const TrajChkArgs& H, int* status, int* safe, double* distance, int* n_samples,
                      int* hit_index, double* hit_t, double* hit_pos, int* end_reason, double* duration);
-void traj_check_release(fuelmi_map* m);  // the map's trajectory-check scratch
 // k_traj_sample (traj_sample.hip): one problem per wave; every pointer addresses device memory
 struct TrajSmpArgs {
   fuelmi_trajsmp_cfg cfg;
   int n_prob;
-  const int* n_ctrl;        // [n], or null: every problem has n_ctrl_all control points
-  int n_ctrl_all;
-  const double* pos;        // problem b: [n_ctrl][3] at pos + b * pos_stride
-  size_t pos_stride;
-  const double* knot;       // problem b: knot[b * knot_stride]
-  size_t knot_stride;
+  SplineSrc src;
   const int* n_yaw;         // [n] (0: that problem has no yaw spline), or null: none has
   const double* yaw;        // [n][max_yaw_ctrl]
   const double* yaw_dt;     // [n]
@@ -653,8 +636,7 @@ int trajsmp_check(const fuelmi_trajsmp_cfg* cfg, int n_prob, bool host_spline, c
 size_t trajsmp_bytes(const fuelmi_trajsmp_cfg* cfg, int n_prob, bool host_spline, const TrajSmpIO& io);
 int trajsmp_run(hipStream_t st, const fuelmi_trajsmp_cfg* cfg, int n_prob, bool host_spline, const TrajSmpIO& io,
                 TrajSmpArgs& A, unsigned char* scratch);
-void traj_sample_release(fuelmi_map* m);  // the map's trajectory-sampling scratch
-void map_cloud_release(fuelmi_map* m);   // the map's cloud scratch, pinned word and events (map_cloud.hip)
+void map_cloud_release(fuelmi_map* m);   // the cloud call's pinned word and events (map_cloud.hip)
 // k_kino_path (kino_path.hip): one problem per workgroup; every pointer addresses device memory
 struct KinoArgs {
   fuelmi_kino_cfg cfg;
@@ -697,14 +679,13 @@ int kino_check(const fuelmi_kino_cfg* cfg, int n_prob, const double* start_xyz, 
                const double* start_acc, const double* goal_xyz, const double* goal_vel);
 int kino_prims(const fuelmi_kino_cfg* cfg, std::vector<double>& prims, int& n_init, int& n_reg);
 size_t kino_workspace(const fuelmi_kino_cfg* cfg, int* hash_cap);
-// fills geometry / lists / workspace pointers of K from the map's scratch (grown to io_bytes + the workspaces), uploads
+// fills geometry / lists / workspace pointers of K from the map's kino_dev pool (reserved for io_bytes + the workspaces), uploads
 // the inputs and the lists, clears the hashes; *io is the start of io_bytes of device memory for the caller's results
 int kino_prepare(fuelmi_map* m, const fuelmi_kino_cfg* cfg, int n_prob, const double* start_xyz, const double* start_vel,
                  const double* start_acc, const double* goal_xyz, const double* goal_vel, size_t io_bytes, KinoArgs& K,
                  unsigned char** io);
 int kino_launch(fuelmi_map* m, const KinoArgs& K);
-void kino_path_release(fuelmi_map* m);
-// device results of one path_cost_enqueue, in the map's path scratch: length / kind / path_len per pair, paths
+// device results of one path_cost_enqueue, in the map's path pool (path_dev): length / kind / path_len per pair, paths
 // [n][maxp][3] (nullptr when maxp is 0), and the device copy of p2_xyz
 struct PathRun {
   double* length = nullptr;

@@ -139,9 +139,6 @@ bool pos_fin(double x) { return std::isfinite(x) && x > 0.0; }
 }  // namespace
 
 void goal_path_release(fuelmi_map* m) {
-  if (m->goal_dev) (void)hipFree(m->goal_dev);
-  m->goal_dev = nullptr;
-  m->goal_dev_bytes = 0;
   for (hipEvent_t& e : m->goal_ev) {
     if (e) (void)hipEventDestroy(e);
     e = nullptr;
@@ -170,32 +167,27 @@ extern "C" int fuelmi_map_goal_paths(fuelmi_map* m, const fuelmi_goal_cfg* cfg, 
     if (!e) HIPCHK(hipEventCreate(&e));
   const int maxp = pc.max_path_points, maxw = cfg->max_way_points;
   const size_t n = (size_t)n_prob;
-  auto pad = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t need = pad(sizeof(int) * n) * 3 + pad(sizeof(double) * n) + pad(sizeof(double) * 3 * n) +
-                      pad(sizeof(double) * 3 * n * maxw);
-  if (need > m->goal_dev_bytes) {
-    HIPCHK(hipStreamSynchronize(st));
-    if (m->goal_dev) HIPCHK(hipFree(m->goal_dev));
-    m->goal_dev = nullptr;
-    m->goal_dev_bytes = 0;
-    HIPCHK(hipMalloc(&m->goal_dev, need));
-    m->goal_dev_bytes = need;
-  }
+  SArgs S;
+  auto layout = [&](unsigned char* base) {  // the result block
+    BlockLayout L(base, 256);
+    S.status = L.take<int>(n);
+    S.n_way = L.take<int>(n);
+    S.raw_len = L.take<int>(n);
+    S.length = L.take<double>(n);
+    S.next_goal = L.take<double>(3 * n);
+    S.way = L.take<double>(3 * n * maxw);
+    return L.size();
+  };
+  int rc = m->goal_dev.reserve(st, layout(nullptr));
+  if (rc != FUELMI_OK) return rc;
   for (int& v : m->path_stats) v = 0;
   HIPCHK(hipEventRecord(m->goal_ev[0], st));
   PathRun run;
-  const int rc = path_cost_enqueue(m, &pc, n_prob, start_xyz, goal_xyz, maxp, run, true);
+  rc = path_cost_enqueue(m, &pc, n_prob, start_xyz, goal_xyz, maxp, run, true);
   if (rc != FUELMI_OK) return rc;
   HIPCHK(hipEventRecord(m->goal_ev[1], st));
 
-  char* base = (char*)m->goal_dev;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base + off;
-    off += pad(bytes);
-    return p;
-  };
-  SArgs S;
+  layout(m->goal_dev.base());
   S.n = n_prob;
   S.kind = run.kind;
   S.plen = run.plen;
@@ -207,12 +199,6 @@ extern "C" int fuelmi_map_goal_paths(fuelmi_map* m, const fuelmi_goal_cfg* cfg, 
   S.shorten_dist = cfg->shorten_dist, S.end_eps = cfg->end_eps;
   S.radius_close = cfg->radius_close, S.radius_far = cfg->radius_far;
   S.maxw = maxw;
-  S.status = (int*)take(sizeof(int) * n);
-  S.n_way = (int*)take(sizeof(int) * n);
-  S.raw_len = (int*)take(sizeof(int) * n);
-  S.length = (double*)take(sizeof(double) * n);
-  S.next_goal = (double*)take(sizeof(double) * 3 * n);
-  S.way = (double*)take(sizeof(double) * 3 * n * maxw);
   hipLaunchKernelGGL(k_goal_shorten, dim3((n_prob + GS_WAVES - 1) / GS_WAVES), dim3(GS_WIN * GS_WAVES), 0, st, m->g, S);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(m->goal_ev[2], st));

@@ -17,9 +17,10 @@
 // __push_heap, kn_pop is pop_heap's __adjust_heap (hole to a leaf along the preferred children, then __push_heap), the
 // comparator reads the nodes' CURRENT f, which an in-place update may have changed behind the heap's back.
 //
-// Workspace per problem, in the map's grow-only scratch: allocate_num node records of 128 B, the heap (4 B a node), an
-// open-addressing hash on the voxel triple (linear probing, >= 2 allocate_num slots of 4 B holding node numbers, -1 =
-// empty; cleared by a memset on the stream per call and by the workgroup itself before the retry).
+// Workspace per problem, in the map's kino_dev pool (a DevScratch, carved by a BlockLayout): allocate_num node records
+// of 128 B, the heap (4 B a node), an open-addressing hash on the voxel triple (linear probing, >= 2 allocate_num slots
+// of 4 B holding node numbers, -1 = empty; cleared by a memset on the stream per call and by the workgroup itself before
+// the retry).
 //
 // All f64, -ffp-contract=off, no scratch (no dynamically indexed private arrays).  LDS: the lanes' results of one
 // expansion (fuelmi_kino_plan reports the bytes).
@@ -144,13 +145,6 @@ __device__ __forceinline__ bool kn_in_box(const KinoArgs& K, const double p[3]) 
     if (p[k] <= K.box_mind[k] || p[k] >= K.box_maxd[k]) return false;
   return true;
 }
-// getInflateOccupancy(pos) == 1; getOccupancy(pos) == UNKNOWN: a position outside the map reads -1 in both
-__device__ __forceinline__ bool kn_plane_at(const Geo& g, const u64* pl, const double p[3]) {
-  int id[3];
-  pos_to_idx(g, p, id);
-  if (!idx_in_map(g, id)) return false;
-  return bit_at(pl, (long)id[0] * g.nyz + (long)id[1] * g.nz + id[2]);
-}
 // KinodynamicAstar::posToIndex (:642-650): the search's own resolution on the map's origin
 __device__ __forceinline__ void kn_idx(const Geo& g, const KinoArgs& K, const double p[3], int id[3]) {
   for (int k = 0; k < 3; ++k) id[k] = (int)floor((p[k] - g.org[k]) * K.inv_res);
@@ -232,7 +226,7 @@ __device__ bool kn_shot(const Geo& g, const KinoArgs& K, const double s1[6], con
     for (int k = 0; k < 3; ++k) c[k] = ((coef[4 * k] * 1.0 + coef[4 * k + 1] * time) + coef[4 * k + 2] * t2) + coef[4 * k + 3] * t3;
     for (int k = 0; k < 3; ++k)
       if (c[k] < g.org[k] || c[k] >= K.map_size[k]) return false;  // (the reference compares with the SIZE)
-    if (kn_plane_at(g, K.infl, c)) return false;
+    if (plane_at_pos(g, K.infl, c)) return false;
   }
   return true;
 }
@@ -353,7 +347,7 @@ __global__ void __launch_bounds__(KN_NT) k_kino_path(Geo g, KinoArgs K) {
             const double dt = tau * double(k) / double(cfg.check_num);
             double xt[6];
             kn_transit(cst, um, dt, xt);
-            if (kn_plane_at(g, K.infl, xt) || !kn_in_box(K, xt) || (!cfg.optimistic && kn_plane_at(g, K.unk, xt))) {
+            if (plane_at_pos(g, K.infl, xt) || !kn_in_box(K, xt) || (!cfg.optimistic && plane_at_pos(g, K.unk, xt))) {
               ok = false;
               break;
             }
@@ -545,15 +539,8 @@ __global__ void __launch_bounds__(KN_NT) k_kino_path(Geo g, KinoArgs K) {
 }
 
 bool pos_fin(double x) { return std::isfinite(x) && x > 0.0; }
-size_t pad256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
-
-void kino_path_release(fuelmi_map* m) {
-  if (m->kino_dev) (void)hipFree(m->kino_dev);
-  m->kino_dev = nullptr;
-  m->kino_dev_bytes = 0;
-}
 
 // the reference's accumulating loops (:107-122), literally
 int kino_prims(const fuelmi_kino_cfg* cfg, std::vector<double>& prims, int& n_init, int& n_reg) {
@@ -649,22 +636,23 @@ int kino_prepare(fuelmi_map* m, const fuelmi_kino_cfg* cfg, int n_prob, const do
   const size_t n = (size_t)n_prob, alloc = (size_t)cfg->allocate_num;
   int cap = 0;
   kino_workspace(cfg, &cap);
-  const size_t b_io = pad256(io_bytes), b_in = pad256(n * 15 * sizeof(double)), b_pr = pad256(prims.size() * sizeof(double)),
-               b_pool = pad256(n * alloc * sizeof(KNode)), b_heap = pad256(n * alloc * sizeof(int)),
-               b_hash = pad256(n * (size_t)cap * sizeof(int));
-  const size_t need = b_io + b_in + b_pr + b_pool + b_heap + b_hash;
-  if (need > m->kino_dev_bytes) {
-    HIPCHK(hipStreamSynchronize(st));
-    if (m->kino_dev) HIPCHK(hipFree(m->kino_dev));
-    m->kino_dev = nullptr;
-    m->kino_dev_bytes = 0;
-    HIPCHK(hipMalloc(&m->kino_dev, need));
-    m->kino_dev_bytes = need;
+  double *d_in, *d_pr;
+  memset(&K, 0, sizeof(K));
+  auto layout = [&](unsigned char* base) {
+    BlockLayout L(base, 256);
+    *io = L.take<unsigned char>(io_bytes);
+    d_in = L.take<double>(n * 15);
+    d_pr = L.take<double>(prims.size());
+    K.pool = reinterpret_cast<unsigned char*>(L.take<KNode>(n * alloc));
+    K.heap = L.take<int>(n * alloc);
+    K.hash = L.take<int>(n * (size_t)cap);
+    return L.size();
+  };
+  {
+    const int rc = m->kino_dev.reserve(st, layout(nullptr));
+    if (rc) return rc;
   }
-  unsigned char* base = static_cast<unsigned char*>(m->kino_dev);
-  *io = base;
-  double* d_in = reinterpret_cast<double*>(base + b_io);
-  double* d_pr = reinterpret_cast<double*>(base + b_io + b_in);
+  layout(m->kino_dev.base());
   // staged in the map: the sources must outlive this function (the copies may run after it returns)
   std::vector<double>& hin = m->kino_host;
   hin.assign(n * 15 + prims.size(), 0.0);
@@ -677,7 +665,6 @@ int kino_prepare(fuelmi_map* m, const fuelmi_kino_cfg* cfg, int n_prob, const do
   std::copy(prims.begin(), prims.end(), hin.begin() + (long)(n * 15));
   HIPCHK(hipMemcpyAsync(d_in, hin.data(), n * 15 * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_pr, hin.data() + n * 15, prims.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  memset(&K, 0, sizeof(K));
   K.cfg = *cfg;
   K.n_prob = n_prob;
   K.n_init = ni, K.n_reg = nr;
@@ -689,9 +676,6 @@ int kino_prepare(fuelmi_map* m, const fuelmi_kino_cfg* cfg, int n_prob, const do
   K.infl = m->infl_bits.p;
   K.unk = m->unk_bits.p;
   K.in = d_in;
-  K.pool = base + b_io + b_in + b_pr;
-  K.heap = reinterpret_cast<int*>(base + b_io + b_in + b_pr + b_pool);
-  K.hash = reinterpret_cast<int*>(base + b_io + b_in + b_pr + b_pool + b_heap);
   K.hash_cap = cap;
   HIPCHK(hipMemsetAsync(K.hash, 0xFF, n * (size_t)cap * sizeof(int), st));
   return FUELMI_OK;
@@ -733,44 +717,38 @@ extern "C" int fuelmi_map_kino_paths(fuelmi_map* m, const fuelmi_kino_cfg* cfg, 
   ARGCHK(m);
   HIPCHK(hipSetDevice(m->device));
   const size_t n = (size_t)n_prob, maxs = (size_t)cfg->max_samples, maxn = (size_t)cfg->max_path_nodes;
-  auto pad = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  const size_t b_int = pad(n * sizeof(int)), b_dbl = pad(n * sizeof(double)), b_12 = pad(n * 12 * sizeof(double)),
-               b_smp = pad(n * maxs * 3 * sizeof(double)), b_ns = node_state ? pad(n * maxn * 6 * sizeof(double)) : 0,
-               b_ni = node_input ? pad(n * maxn * 3 * sizeof(double)) : 0,
-               b_nd = node_duration ? pad(n * maxn * sizeof(double)) : 0;
-  const size_t io_bytes = 9 * b_int + 3 * b_dbl + 2 * b_12 + b_smp + b_ns + b_ni + b_nd;
   KinoArgs K;
+  auto layout = [&](unsigned char* base) {  // the result block
+    BlockLayout L(base, 16);
+    K.status = L.take<int>(n);
+    K.which = L.take<int>(n);
+    K.iter_num = L.take<int>(n);
+    K.use_node_num = L.take<int>(n);
+    K.n_nodes = L.take<int>(n);
+    K.shot = L.take<int>(n);
+    K.seg_num = L.take<int>(n);
+    K.n_samples = L.take<int>(n);
+    K.skip = L.take<int>(n);
+    K.t_shot = L.take<double>(n);
+    K.T_sum = L.take<double>(n);
+    K.ts_out = L.take<double>(n);
+    K.coef_shot = L.take<double>(n * 12);
+    K.derivs = L.take<double>(n * 12);
+    K.samples = L.take<double>(n * maxs * 3);
+    K.node_state = node_state ? L.take<double>(n * maxn * 6) : nullptr;
+    K.node_input = node_input ? L.take<double>(n * maxn * 3) : nullptr;
+    K.node_duration = node_duration ? L.take<double>(n * maxn) : nullptr;
+    return L.size();
+  };
+  const size_t io_bytes = layout(nullptr);
   unsigned char* io = nullptr;
   {
     const int rc = kino_prepare(m, cfg, n_prob, start_xyz, start_vel, start_acc, goal_xyz, goal_vel, io_bytes, K, &io);
     if (rc) return rc;
   }
+  layout(io);
   std::vector<unsigned char> host(io_bytes);
-  unsigned char* at = io;
-  auto take = [&](size_t bytes) {
-    unsigned char* p = at;
-    at += bytes;
-    return p;
-  };
   auto back = [&](const void* dev) { return host.data() + (static_cast<const unsigned char*>(dev) - io); };
-  K.status = reinterpret_cast<int*>(take(b_int));
-  K.which = reinterpret_cast<int*>(take(b_int));
-  K.iter_num = reinterpret_cast<int*>(take(b_int));
-  K.use_node_num = reinterpret_cast<int*>(take(b_int));
-  K.n_nodes = reinterpret_cast<int*>(take(b_int));
-  K.shot = reinterpret_cast<int*>(take(b_int));
-  K.seg_num = reinterpret_cast<int*>(take(b_int));
-  K.n_samples = reinterpret_cast<int*>(take(b_int));
-  K.skip = reinterpret_cast<int*>(take(b_int));
-  K.t_shot = reinterpret_cast<double*>(take(b_dbl));
-  K.T_sum = reinterpret_cast<double*>(take(b_dbl));
-  K.ts_out = reinterpret_cast<double*>(take(b_dbl));
-  K.coef_shot = reinterpret_cast<double*>(take(b_12));
-  K.derivs = reinterpret_cast<double*>(take(b_12));
-  K.samples = reinterpret_cast<double*>(take(b_smp));
-  K.node_state = node_state ? reinterpret_cast<double*>(take(b_ns)) : nullptr;
-  K.node_input = node_input ? reinterpret_cast<double*>(take(b_ni)) : nullptr;
-  K.node_duration = node_duration ? reinterpret_cast<double*>(take(b_nd)) : nullptr;
   hipStream_t st = m->stream;
   {
     const int rc = kino_launch(m, K);

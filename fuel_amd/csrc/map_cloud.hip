@@ -184,9 +184,6 @@ int cl_plan(const int dims[3], const int lo[3], const int hi[3], int P[8]) {
 }  // namespace
 
 void map_cloud_release(fuelmi_map* m) {
-  if (m->cloud_dev) (void)hipFree(m->cloud_dev);
-  m->cloud_dev = nullptr;
-  m->cloud_dev_bytes = 0;
   if (m->cloud_pin) (void)hipHostFree(m->cloud_pin);
   m->cloud_pin = nullptr;
   for (hipEvent_t& e : m->cloud_ev) {
@@ -229,15 +226,11 @@ extern "C" int fuelmi_map_extract_cloud(fuelmi_map* m, const fuelmi_cloud_cfg* c
     for (hipEvent_t& e : m->cloud_ev) HIPCHK(hipEventCreate(&e));
   }
   const size_t n_out = std::min((size_t)cap, (size_t)P[7]);
-  const size_t need = (size_t)P[6] + n_out * 3 * sizeof(float);
-  if (need > m->cloud_dev_bytes) {
-    HIPCHK(hipStreamSynchronize(st));
-    if (m->cloud_dev) (void)hipFree(m->cloud_dev);
-    m->cloud_dev = nullptr, m->cloud_dev_bytes = 0;
-    HIPCHK(hipMalloc(&m->cloud_dev, need));
-    m->cloud_dev_bytes = need;
+  {
+    const int rc = m->cloud_dev.reserve(st, (size_t)P[6] + n_out * 3 * sizeof(float));
+    if (rc) return rc;
   }
-  unsigned char* base = static_cast<unsigned char*>(m->cloud_dev);
+  unsigned char* base = m->cloud_dev.base();
   CloudArgs C;
   memset(&C, 0, sizeof(C));
   switch (cfg->kind) {

@@ -723,11 +723,10 @@ extern "C" void fuelmi_map_destroy(fuelmi_map* m) {
                      &m->tmp2_bits, &m->hit_bits, &m->miss_bits};
   for (Plane* p : planes)
     if (p->base) (void)hipFree(p->base);
-  path_cost_release(m);
+  for (DevScratch* s : {&m->path_dev, &m->refine_dev, &m->goal_dev, &m->kino_dev, &m->trajchk_dev, &m->trajsmp_dev,
+                        &m->cloud_dev})
+    s->release();
   goal_path_release(m);
-  kino_path_release(m);
-  traj_check_release(m);
-  traj_sample_release(m);
   map_cloud_release(m);
   void* bufs[] = {m->occ, m->dist, m->esdf_tmp, m->esdf_tmp16, m->flag_rayend, m->ray_owner, m->d_stage, m->ins_partial, m->ins_head, m->ins_rec};
   if (m->h_ins) (void)hipHostFree(m->h_ins);

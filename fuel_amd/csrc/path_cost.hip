@@ -64,13 +64,9 @@ __device__ __forceinline__ bool in_box_d(const PArgs& A, const double p[3]) {
     if (p[k] <= A.box_mind[k] || p[k] >= A.box_maxd[k]) return false;
   return true;
 }
-// getInflateOccupancy(pos) == 1 || getOccupancy(pos) == UNKNOWN; a position outside the map reads -1 and passes
+// getInflateOccupancy(pos) == 1 || getOccupancy(pos) == UNKNOWN
 __device__ __forceinline__ bool blocked_at(const Geo& g, const PArgs& A, const double p[3]) {
-  int id[3];
-  pos_to_idx(g, p, id);
-  if (!idx_in_map(g, id)) return false;
-  const long a = (long)id[0] * g.nyz + (long)id[1] * g.nz + id[2];
-  return bit_at(A.infl, a) || bit_at(A.unk, a);
+  return plane_at_pos(g, A.infl, p) || plane_at_pos(g, A.unk, p);
 }
 __device__ __forceinline__ void node_pos(const PSrc& S, const int n[3], double res, double p[3]) {
   for (int k = 0; k < 3; ++k) p[k] = S.p1[k] + (double)n[k] * res;
@@ -416,35 +412,15 @@ void axis_range(double p1, double res, double lo, double hi, int& nlo, int& nhi)
   nlo = (int)a, nhi = (int)b;
 }
 
-struct Scratch {  // carved from one grow-only device buffer per map
-  char* base = nullptr;
-  size_t off = 0;
-  template <class T>
-  T* take(size_t count) {
-    T* p = (T*)(base + off);
-    off += (count * sizeof(T) + 255) & ~(size_t)255;
-    return p;
-  }
-};
-
 constexpr size_t CHUNK_NODE_BUDGET = (size_t)48 << 20;  // lattice nodes per chunk of sources (12 B each)
 constexpr int POLL_EVERY = 8;
 
 }  // namespace
 
-void path_cost_release(fuelmi_map* m) {
-  if (m->path_dev) (void)hipFree(m->path_dev);
-  m->path_dev = nullptr;
-  m->path_dev_bytes = 0;
-  if (m->refine_dev) (void)hipFree(m->refine_dev);
-  m->refine_dev = nullptr;
-  m->refine_dev_bytes = 0;
-}
-
 // The searches of n pairs queued on the map's stream: source dedup, chunks, k_path_los / _mask / _relax / _goal.  The
-// results stay in the map's path scratch (valid until the next enqueue); fuelmi_map_path_stats' counters accumulate.
-// The caller has checked the arguments (finite, |coordinate| < 1e7) and n > 0.  always_lattice: k_path_los is skipped
-// and every pair is searched on its source's lattice.
+// results stay in the map's path pool (path_dev, a DevScratch carved by a BlockLayout; valid until the next enqueue);
+// fuelmi_map_path_stats' counters accumulate.  The caller has checked the arguments (finite, |coordinate| < 1e7) and
+// n > 0.  always_lattice: k_path_los is skipped and every pair is searched on its source's lattice.
 
 int path_cost_enqueue(fuelmi_map* m, const fuelmi_path_cfg* cfg, int n, const double* p1_xyz, const double* p2_xyz,
                       int maxp, PathRun& out, bool always_lattice) {
@@ -522,31 +498,31 @@ int path_cost_enqueue(fuelmi_map* m, const fuelmi_path_cfg* cfg, int n, const do
   // launches a chunk may take: the work lists settle after at most (tile segments of a shortest path) + 1 launches,
   // and a shortest path has fewer segments than its source has nodes -- a bound, not a guess
   const long cap_max = max_nodes + 2;
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t need = pad(24 * (size_t)n) * 2 + pad(8 * (size_t)n) + pad(4 * (size_t)n) * 4 +
-                      (maxp > 0 ? pad((size_t)n * maxp * 24) : 0) + pad(sizeof(PSrc) * lat.size()) + pad(4 * chunk_nodes) +
-                      pad(8 * chunk_nodes) + pad(4 * chunk_tiles) + pad(8 * chunk_tiles) + pad(4 * (size_t)(cap_max + 2));
-  if (need > m->path_dev_bytes) {  // one allocation per call at most, sized above
-    HIPCHK(hipStreamSynchronize(m->stream));
-    path_cost_release(m);
-    HIPCHK(hipMalloc(&m->path_dev, need));
-    m->path_dev_bytes = need;
-  }
-  Scratch sc{(char*)m->path_dev, 0};
-  double* d_p1 = sc.take<double>(3 * (size_t)n);
-  double* d_p2 = sc.take<double>(3 * (size_t)n);
-  double* d_len = sc.take<double>(n);
-  int* d_kind = sc.take<int>(n);
-  int* d_plen = sc.take<int>(n);
-  int* d_pair = sc.take<int>(n);
-  int* d_src = sc.take<int>(n);
-  double* d_path = maxp > 0 ? sc.take<double>((size_t)n * maxp * 3) : nullptr;
-  PSrc* d_lat = sc.take<PSrc>(lat.size());
-  u32* d_mask = sc.take<u32>(chunk_nodes);
-  double* d_dist = sc.take<double>(chunk_nodes);
-  u32* d_stamp = sc.take<u32>(chunk_tiles);
-  u32* d_lists = sc.take<u32>(2 * chunk_tiles);
-  u32* d_cnt = sc.take<u32>(cap_max + 2);
+  double *d_p1, *d_p2, *d_len, *d_path, *d_dist;
+  int *d_kind, *d_plen, *d_pair, *d_src;
+  PSrc* d_lat;
+  u32 *d_mask, *d_stamp, *d_lists, *d_cnt;
+  auto layout = [&](unsigned char* base) {
+    BlockLayout L(base, 256);
+    d_p1 = L.take<double>(3 * (size_t)n);
+    d_p2 = L.take<double>(3 * (size_t)n);
+    d_len = L.take<double>(n);
+    d_kind = L.take<int>(n);
+    d_plen = L.take<int>(n);
+    d_pair = L.take<int>(n);
+    d_src = L.take<int>(n);
+    d_path = maxp > 0 ? L.take<double>((size_t)n * maxp * 3) : nullptr;
+    d_lat = L.take<PSrc>(lat.size());
+    d_mask = L.take<u32>(chunk_nodes);
+    d_dist = L.take<double>(chunk_nodes);
+    d_stamp = L.take<u32>(chunk_tiles);
+    d_lists = L.take<u32>(2 * chunk_tiles);
+    d_cnt = L.take<u32>(cap_max + 2);
+    return L.size();
+  };
+  const int grow = m->path_dev.reserve(m->stream, layout(nullptr));  // one allocation per call at most
+  if (grow != FUELMI_OK) return grow;
+  layout(m->path_dev.base());
 
   hipStream_t st = m->stream;
   HIPCHK(hipMemcpyAsync(d_p1, p1_xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));

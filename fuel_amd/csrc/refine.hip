@@ -229,34 +229,24 @@ extern "C" int fuelmi_map_refine_tours(fuelmi_map* m, const fuelmi_refine_cfg* c
   if (rc != FUELMI_OK) return rc;
 
   // ---- problems to the device, k_refine, choices and costs back ----
-  auto pad = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t need = pad(sizeof(double) * 7 * n_prob) + pad(sizeof(int) * (n_prob + 1)) +
-                      pad(sizeof(int) * (n_layers + 1)) + pad(sizeof(double) * 4 * (size_t)n_nodes) +
-                      pad(sizeof(int) * n_layers) * 2 + pad(sizeof(double) * n_prob) + pad(sizeof(int));
-  hipStream_t st = m->stream;
-  if (need > m->refine_dev_bytes) {
-    HIPCHK(hipStreamSynchronize(st));
-    if (m->refine_dev) HIPCHK(hipFree(m->refine_dev));
-    m->refine_dev = nullptr;
-    m->refine_dev_bytes = 0;
-    HIPCHK(hipMalloc(&m->refine_dev, need));
-    m->refine_dev_bytes = need;
-  }
-  char* base = (char*)m->refine_dev;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base + off;
-    off += pad(bytes);
-    return p;
+  double *d_start, *d_nodes, *d_cost;
+  int *d_lptr, *d_nptr, *d_eoff, *d_choice, *d_err;
+  auto layout = [&](unsigned char* base) {
+    BlockLayout L(base, 256);
+    d_start = L.take<double>(7 * (size_t)n_prob);
+    d_lptr = L.take<int>(n_prob + 1);
+    d_nptr = L.take<int>(n_layers + 1);
+    d_nodes = L.take<double>(4 * (size_t)n_nodes);
+    d_eoff = L.take<int>(n_layers);
+    d_choice = L.take<int>(n_layers);
+    d_cost = L.take<double>(n_prob);
+    d_err = L.take<int>(1);
+    return L.size();
   };
-  double* d_start = (double*)take(sizeof(double) * 7 * n_prob);
-  int* d_lptr = (int*)take(sizeof(int) * (n_prob + 1));
-  int* d_nptr = (int*)take(sizeof(int) * (n_layers + 1));
-  double* d_nodes = (double*)take(sizeof(double) * 4 * (size_t)n_nodes);
-  int* d_eoff = (int*)take(sizeof(int) * n_layers);
-  int* d_choice = (int*)take(sizeof(int) * n_layers);
-  double* d_cost = (double*)take(sizeof(double) * n_prob);
-  int* d_err = (int*)take(sizeof(int));
+  hipStream_t st = m->stream;
+  rc = m->refine_dev.reserve(st, layout(nullptr));
+  if (rc != FUELMI_OK) return rc;
+  layout(m->refine_dev.base());
   HIPCHK(hipMemcpyAsync(d_start, start, sizeof(double) * 7 * n_prob, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_lptr, layer_ptr, sizeof(int) * (n_prob + 1), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_nptr, node_ptr, sizeof(int) * (n_layers + 1), hipMemcpyHostToDevice, st));

@@ -3,6 +3,9 @@
 #ifndef FUELMI_SPLINE_INTERNAL_H_
 #define FUELMI_SPLINE_INTERNAL_H_
 
+// doubles of one wave's knot block in LDS: n + p + 1 <= max_ctrl + 6 knots, kept a multiple of 16 bytes
+__host__ __device__ inline int spline_knot_stride(int max_ctrl) { return (max_ctrl + 6 + 1) & ~1; }
+
 // the clamp and the knot search of evaluateDeBoor (non_uniform_bspline.cpp:52-57) for evaluateDeBoorT(t) of a spline of
 // degree p with n control points and the knots u[0 .. n + p]: returns the span k, ub = the clamped parameter.  Every
 // derivative spline of getDerivative (:97-106) finds the same ub and, counted in these knots, the same k: its knots are

@@ -28,9 +28,6 @@ constexpr int TC_WIN = 64;   // samples per window: one per lane
 constexpr int TC_WAVES = 4;  // problems per workgroup
 constexpr int TC_CAP = FUELMI_TRAJCHK_MAX_SAMPLES;
 
-// doubles of one wave's knot block: n + p + 1 <= max_ctrl + 6 knots, kept a multiple of 16 bytes
-__host__ __device__ inline int tc_knot_stride(int max_ctrl) { return (max_ctrl + 6 + 1) & ~1; }
-
 // not finite, or |coordinate| >= 1e7: the reference's cast to int is undefined there
 __device__ __forceinline__ bool tc_bad(const double q[3]) {
   return !(fabs(q[0]) < 1e7 && fabs(q[1]) < 1e7 && fabs(q[2]) < 1e7);
@@ -67,14 +64,14 @@ __global__ void __launch_bounds__(TC_WIN * TC_WAVES) k_traj_check(Geo g, TrajChk
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int lane = threadIdx.x & (TC_WIN - 1), wv = threadIdx.x >> 6;
   const int b = blockIdx.x * TC_WAVES + wv;
-  double* u = reinterpret_cast<double*>(smem_raw) + (size_t)wv * tc_knot_stride(T.cfg.max_ctrl);  // [n + p + 1]
+  double* u = reinterpret_cast<double*>(smem_raw) + (size_t)wv * spline_knot_stride(T.cfg.max_ctrl);  // [n + p + 1]
   const int p = T.cfg.degree;
   const bool live = b < T.n_prob;
   int n = 0;
   double dt = 0.0;
   if (live) {
-    n = T.n_ctrl ? T.n_ctrl[b] : T.n_ctrl_all;
-    dt = T.knot[(size_t)b * T.knot_stride];
+    n = T.src.n_ctrl ? T.src.n_ctrl[b] : T.src.n_ctrl_all;
+    dt = T.src.knot[(size_t)b * T.src.knot_stride];
   }
   // (the host route refuses these before any launch; the variables of a device batch are not seen by the host)
   const bool sane = live && dt > 0.0 && isfinite(dt) && n >= p + 1 && n <= T.cfg.max_ctrl;
@@ -95,7 +92,7 @@ __global__ void __launch_bounds__(TC_WIN * TC_WAVES) k_traj_check(Geo g, TrajChk
       tc_write(T, b, FUELMI_TRAJCHK_NONFINITE, 0, 0.0, 0, 0, 0.0, nullptr, FUELMI_TRAJCHK_END_NONFINITE, 0.0);
     return;
   }
-  const double* C = T.pos + (size_t)b * T.pos_stride;
+  const double* C = T.src.pos + (size_t)b * T.src.pos_stride;
   const double t_now = T.t_now[b], step = T.cfg.step, max_radius = T.cfg.max_radius;
   const double duration = u[n] - u[p];
 
@@ -149,7 +146,7 @@ __global__ void __launch_bounds__(TC_WIN * TC_WAVES) k_traj_check(Geo g, TrajChk
   }
 }
 
-size_t tc_lds(int max_ctrl) { return (size_t)TC_WAVES * tc_knot_stride(max_ctrl) * sizeof(double); }
+size_t tc_lds(int max_ctrl) { return (size_t)TC_WAVES * spline_knot_stride(max_ctrl) * sizeof(double); }
 
 int trajchk_cfg_check(const fuelmi_trajchk_cfg* cfg) {
   ARGCHK(cfg);
@@ -189,23 +186,17 @@ int trajchk_check(const fuelmi_trajchk_cfg* cfg, int n_prob, const int* n_ctrl, 
 
 size_t trajchk_out_bytes(int n_prob, TrajChkArgs& T, unsigned char* base) {
   const size_t n = (size_t)n_prob;
-  auto pad = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    unsigned char* p = base ? base + at : nullptr;
-    at += pad(bytes);
-    return p;
-  };
-  T.status = reinterpret_cast<int*>(take(n * sizeof(int)));
-  T.safe = reinterpret_cast<int*>(take(n * sizeof(int)));
-  T.n_samples = reinterpret_cast<int*>(take(n * sizeof(int)));
-  T.hit_index = reinterpret_cast<int*>(take(n * sizeof(int)));
-  T.end_reason = reinterpret_cast<int*>(take(n * sizeof(int)));
-  T.distance = reinterpret_cast<double*>(take(n * sizeof(double)));
-  T.hit_t = reinterpret_cast<double*>(take(n * sizeof(double)));
-  T.duration = reinterpret_cast<double*>(take(n * sizeof(double)));
-  T.hit_pos = reinterpret_cast<double*>(take(n * 3 * sizeof(double)));
-  return at;
+  BlockLayout L(base, 16);
+  T.status = L.take<int>(n);
+  T.safe = L.take<int>(n);
+  T.n_samples = L.take<int>(n);
+  T.hit_index = L.take<int>(n);
+  T.end_reason = L.take<int>(n);
+  T.distance = L.take<double>(n);
+  T.hit_t = L.take<double>(n);
+  T.duration = L.take<double>(n);
+  T.hit_pos = L.take<double>(n * 3);
+  return L.size();
 }
 
 int trajchk_copy_out(int n_prob, const TrajChkArgs& H, int* status, int* safe, double* distance, int* n_samples,
@@ -235,12 +226,6 @@ int trajchk_launch(hipStream_t st, const Geo& g, const TrajChkArgs& T) {
   return FUELMI_OK;
 }
 
-void traj_check_release(fuelmi_map* m) {
-  if (m->trajchk_dev) (void)hipFree(m->trajchk_dev);
-  m->trajchk_dev = nullptr;
-  m->trajchk_dev_bytes = 0;
-}
-
 extern "C" int fuelmi_traj_check_plan(const fuelmi_trajchk_cfg* cfg, int out3[3]) {
   ARGCHK(out3);
   {
@@ -266,38 +251,33 @@ extern "C" int fuelmi_map_check_trajs(fuelmi_map* m, const fuelmi_trajchk_cfg* c
   HIPCHK(hipSetDevice(m->device));
   hipStream_t st = m->stream;
   const size_t n = (size_t)n_prob, maxc = (size_t)cfg->max_ctrl;
-  auto pad = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  const size_t b_int = pad(n * sizeof(int)), b_dbl = pad(n * sizeof(double)), b_pos = pad(n * maxc * 3 * sizeof(double));
   TrajChkArgs T;
   memset(&T, 0, sizeof(T));
   const size_t b_out = trajchk_out_bytes(n_prob, T, nullptr);
-  const size_t need = b_int + 2 * b_dbl + b_pos + b_out;
-  if (need > m->trajchk_dev_bytes) {
-    HIPCHK(hipStreamSynchronize(st));
-    traj_check_release(m);
-    HIPCHK(hipMalloc(&m->trajchk_dev, need));
-    m->trajchk_dev_bytes = need;
-  }
-  unsigned char* at = static_cast<unsigned char*>(m->trajchk_dev);
-  auto take = [&](size_t bytes) {
-    unsigned char* p = at;
-    at += bytes;
-    return p;
+  int* d_nc;
+  double *d_knot, *d_now, *d_pos;
+  unsigned char* d_out;
+  auto layout = [&](unsigned char* base) {
+    BlockLayout L(base, 16);
+    d_nc = L.take<int>(n);
+    d_knot = L.take<double>(n);
+    d_now = L.take<double>(n);
+    d_pos = L.take<double>(n * maxc * 3);
+    d_out = L.take<unsigned char>(b_out);
+    return L.size();
   };
-  int* d_nc = reinterpret_cast<int*>(take(b_int));
-  double* d_knot = reinterpret_cast<double*>(take(b_dbl));
-  double* d_now = reinterpret_cast<double*>(take(b_dbl));
-  double* d_pos = reinterpret_cast<double*>(take(b_pos));
-  unsigned char* d_out = take(b_out);
+  {
+    const int rc = m->trajchk_dev.reserve(st, layout(nullptr));
+    if (rc) return rc;
+  }
+  layout(m->trajchk_dev.base());
   HIPCHK(hipMemcpyAsync(d_nc, n_ctrl, n * sizeof(int), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_knot, knot_span, n * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_now, t_now, n * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_pos, pos_ctrl, n * maxc * 3 * sizeof(double), hipMemcpyHostToDevice, st));
   T.cfg = *cfg;
   T.n_prob = n_prob;
-  T.n_ctrl = d_nc, T.n_ctrl_all = 0;
-  T.pos = d_pos, T.pos_stride = maxc * 3;
-  T.knot = d_knot, T.knot_stride = 1;
+  T.src = {d_nc, 0, d_pos, maxc * 3, d_knot, 1};
   T.t_now = d_now;
   T.infl = m->infl_bits.p;
   trajchk_out_bytes(n_prob, T, d_out);

@@ -26,10 +26,8 @@ namespace {
 constexpr int TS_WIN = 64;   // samples per window: one per lane
 constexpr int TS_WAVES = 3;  // problems per workgroup: two knot blocks each, 48.4 KiB at the largest strides
 
-// doubles of one knot block: n + p + 1 <= max + 6 knots, kept a multiple of 16 bytes
-__host__ __device__ inline int ts_knot_stride(int max_ctrl) { return (max_ctrl + 6 + 1) & ~1; }
 __host__ __device__ inline int ts_wave_stride(const fuelmi_trajsmp_cfg& c) {
-  return ts_knot_stride(c.max_ctrl) + (c.max_yaw_ctrl > 0 ? ts_knot_stride(c.max_yaw_ctrl) : 0);
+  return spline_knot_stride(c.max_ctrl) + (c.max_yaw_ctrl > 0 ? spline_knot_stride(c.max_yaw_ctrl) : 0);
 }
 
 // setUniformBspline's knots (non_uniform_bspline.cpp:25-31)
@@ -78,14 +76,14 @@ __global__ void __launch_bounds__(TS_WIN * TS_WAVES) k_traj_sample(TrajSmpArgs A
   const int lane = threadIdx.x & (TS_WIN - 1), wv = threadIdx.x >> 6;
   const int b = blockIdx.x * TS_WAVES + wv;
   double* u = reinterpret_cast<double*>(smem_raw) + (size_t)wv * ts_wave_stride(A.cfg);  // [n + p + 1]
-  double* uy = u + ts_knot_stride(A.cfg.max_ctrl);                                        // [ny + py + 1]
+  double* uy = u + spline_knot_stride(A.cfg.max_ctrl);                                        // [ny + py + 1]
   const int p = A.cfg.degree, py = A.cfg.yaw_degree, max_t = A.cfg.max_t;
   const bool live = b < A.n_prob;
   int n = 0, ny = 0;
   double dt = 0.0, dty = 0.0;
   if (live) {
-    n = A.n_ctrl ? A.n_ctrl[b] : A.n_ctrl_all;
-    dt = A.knot[(size_t)b * A.knot_stride];
+    n = A.src.n_ctrl ? A.src.n_ctrl[b] : A.src.n_ctrl_all;
+    dt = A.src.knot[(size_t)b * A.src.knot_stride];
     if (A.n_yaw && A.cfg.max_yaw_ctrl > 0) ny = A.n_yaw[b];
     if (ny > 0) dty = A.yaw_dt[b];
   }
@@ -110,7 +108,7 @@ __global__ void __launch_bounds__(TS_WIN * TS_WAVES) k_traj_sample(TrajSmpArgs A
     const double ts = A.t_stop[b];
     T = D < ts ? D : ts;
   }
-  const double* C = A.pos + (size_t)b * A.pos_stride;
+  const double* C = A.src.pos + (size_t)b * A.src.pos_stride;
   const double* Cy = ny > 0 ? A.yaw + (size_t)b * A.cfg.max_yaw_ctrl : nullptr;
   const bool record = command && A.flight && sane;
   double* F = A.flight ? A.flight + (size_t)b * 8 : nullptr;
@@ -237,39 +235,31 @@ int trajsmp_cfg_check(const fuelmi_trajsmp_cfg* cfg) {
   return FUELMI_OK;
 }
 
-inline size_t ts_pad(size_t x) { return (x + 15) & ~(size_t)15; }
-
-// the scratch block: the inputs the host hands over, the flight record (in and out), then the results.  base null: only
-// the size.
+// the scratch block (a BlockLayout over the map's or the batch's DevScratch): the inputs the host hands over, the
+// flight record (in and out), then the results.  base null: only the size.
 size_t ts_layout(const fuelmi_trajsmp_cfg& c, int n_prob, bool host_spline, const TrajSmpIO& io, TrajSmpArgs& A,
                  unsigned char* base) {
   const size_t n = (size_t)n_prob, s = n * (size_t)c.max_t;
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    unsigned char* p = base ? base + at : nullptr;
-    at += ts_pad(bytes);
-    return p;
-  };
-  auto dbl = [&](size_t count) { return reinterpret_cast<double*>(take(count * sizeof(double))); };
-  auto i32 = [&](size_t count) { return reinterpret_cast<int*>(take(count * sizeof(int))); };
+  BlockLayout L(base, 16);
   if (host_spline) {
-    A.n_ctrl = i32(n), A.n_ctrl_all = 0;
-    A.knot = dbl(n), A.knot_stride = 1;
-    A.pos = dbl(n * c.max_ctrl * 3), A.pos_stride = (size_t)c.max_ctrl * 3;
+    A.src.n_ctrl = L.take<int>(n), A.src.n_ctrl_all = 0;
+    A.src.knot = L.take<double>(n), A.src.knot_stride = 1;
+    A.src.pos = L.take<double>(n * c.max_ctrl * 3), A.src.pos_stride = (size_t)c.max_ctrl * 3;
   }
   const bool yaw = io.n_yaw_ctrl && c.max_yaw_ctrl > 0;
-  A.n_yaw = yaw ? i32(n) : nullptr;
-  A.yaw = yaw ? dbl(n * c.max_yaw_ctrl) : nullptr;
-  A.yaw_dt = yaw ? dbl(n) : nullptr;
-  A.t_stop = io.t_stop ? dbl(n) : nullptr;
-  A.n_t = i32(n);
-  A.t = dbl(s);
-  A.flight = io.flight ? dbl(n * 8) : nullptr;
-  A.status = i32(s);
-  A.o_pos = dbl(3 * s), A.o_vel = dbl(3 * s), A.o_acc = dbl(3 * s), A.o_jerk = dbl(3 * s);
-  A.o_yaw = dbl(s), A.o_yawdot = dbl(s), A.o_yawddot = dbl(s);
-  A.duration = dbl(n);
-  return at;
+  A.n_yaw = yaw ? L.take<int>(n) : nullptr;
+  A.yaw = yaw ? L.take<double>(n * c.max_yaw_ctrl) : nullptr;
+  A.yaw_dt = yaw ? L.take<double>(n) : nullptr;
+  A.t_stop = io.t_stop ? L.take<double>(n) : nullptr;
+  A.n_t = L.take<int>(n);
+  A.t = L.take<double>(s);
+  A.flight = io.flight ? L.take<double>(n * 8) : nullptr;
+  A.status = L.take<int>(s);
+  A.o_pos = L.take<double>(3 * s), A.o_vel = L.take<double>(3 * s);
+  A.o_acc = L.take<double>(3 * s), A.o_jerk = L.take<double>(3 * s);
+  A.o_yaw = L.take<double>(s), A.o_yawdot = L.take<double>(s), A.o_yawddot = L.take<double>(s);
+  A.duration = L.take<double>(n);
+  return L.size();
 }
 
 }  // namespace
@@ -345,9 +335,9 @@ int trajsmp_run(hipStream_t st, const fuelmi_trajsmp_cfg* cfg, int n_prob, bool 
     return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
   };
   if (host_spline) {
-    HIPCHK(up(A.n_ctrl, io.n_ctrl, n * sizeof(int)));
-    HIPCHK(up(A.knot, io.knot_span, n * sizeof(double)));
-    HIPCHK(up(A.pos, io.pos_ctrl, n * c.max_ctrl * 3 * sizeof(double)));
+    HIPCHK(up(A.src.n_ctrl, io.n_ctrl, n * sizeof(int)));
+    HIPCHK(up(A.src.knot, io.knot_span, n * sizeof(double)));
+    HIPCHK(up(A.src.pos, io.pos_ctrl, n * c.max_ctrl * 3 * sizeof(double)));
   }
   if (A.n_yaw) {
     HIPCHK(up(A.n_yaw, io.n_yaw_ctrl, n * sizeof(int)));
@@ -372,12 +362,6 @@ int trajsmp_run(hipStream_t st, const fuelmi_trajsmp_cfg* cfg, int n_prob, bool 
   if (A.flight) HIPCHK(down(io.flight, A.flight, n * 8 * sizeof(double)));
   HIPCHK(stream_wait(st));
   return FUELMI_OK;
-}
-
-void traj_sample_release(fuelmi_map* m) {
-  if (m->trajsmp_dev) (void)hipFree(m->trajsmp_dev);
-  m->trajsmp_dev = nullptr;
-  m->trajsmp_dev_bytes = 0;
 }
 
 extern "C" int fuelmi_traj_sample_plan(const fuelmi_trajsmp_cfg* cfg, int out3[3]) {
@@ -407,14 +391,11 @@ extern "C" int fuelmi_map_sample_trajs(fuelmi_map* m, const fuelmi_trajsmp_cfg* 
   ARGCHK(m);
   HIPCHK(hipSetDevice(m->device));
   hipStream_t st = m->stream;
-  const size_t need = trajsmp_bytes(cfg, n_prob, true, io);
-  if (need > m->trajsmp_dev_bytes) {
-    HIPCHK(hipStreamSynchronize(st));
-    traj_sample_release(m);
-    HIPCHK(hipMalloc(&m->trajsmp_dev, need));
-    m->trajsmp_dev_bytes = need;
+  {
+    const int rc = m->trajsmp_dev.reserve(st, trajsmp_bytes(cfg, n_prob, true, io));
+    if (rc) return rc;
   }
   TrajSmpArgs A;
   memset(&A, 0, sizeof(A));
-  return trajsmp_run(st, cfg, n_prob, true, io, A, static_cast<unsigned char*>(m->trajsmp_dev));
+  return trajsmp_run(st, cfg, n_prob, true, io, A, m->trajsmp_dev.base());
 }

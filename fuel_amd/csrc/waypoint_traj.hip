@@ -380,47 +380,43 @@ extern "C" int fuelmi_map_waypoint_trajs(fuelmi_map* m, const fuelmi_wptraj_cfg*
   HIPCHK(hipSetDevice(m->device));
   const size_t n = (size_t)n_prob, maxw = (size_t)cfg->max_way_points, maxs = (size_t)cfg->max_samples;
   const size_t rows = maxw - 1;
-  auto pad = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  const size_t b_int = pad(n * sizeof(int)), b_dbl = pad(n * sizeof(double)), b_way = pad(n * maxw * 3 * sizeof(double)),
-               b_v3 = pad(n * 3 * sizeof(double)), b_smp = pad(n * maxs * 3 * sizeof(double)),
-               b_der = pad(n * 12 * sizeof(double)), b_tim = seg_times ? pad(n * rows * sizeof(double)) : 0,
-               b_cf = coef ? pad(n * rows * 18 * sizeof(double)) : 0;
-  QuerySlotGuard q;
-  {
-    const int rcq = q.acquire(m, 4 * b_int + 3 * b_dbl + b_way + 2 * b_v3 + b_smp + b_der + b_tim + b_cf);
-    if (rcq) return rcq;
-  }
-  unsigned char* at = q.s->pin;
-  auto take = [&](size_t bytes) {
-    unsigned char* p = at;
-    at += bytes;
-    return p;
-  };
   WpTrajArgs W;
   memset(&W, 0, sizeof(W));
+  int* p_nway;
+  double *p_way, *p_vel, *p_acc;
+  auto layout = [&](unsigned char* base) {  // the slot's pinned block: the inputs, then the results
+    BlockLayout L(base, 16);
+    p_nway = L.take<int>(n);
+    p_way = L.take<double>(n * maxw * 3);
+    p_vel = L.take<double>(n * 3);
+    p_acc = L.take<double>(n * 3);
+    W.status = L.take<int>(n);
+    W.seg_num = L.take<int>(n);
+    W.n_samples = L.take<int>(n);
+    W.duration = L.take<double>(n);
+    W.length = L.take<double>(n);
+    W.dt = L.take<double>(n);
+    W.samples = L.take<double>(n * maxs * 3);
+    W.derivs = L.take<double>(n * 12);
+    W.seg_times = seg_times ? L.take<double>(n * rows) : nullptr;
+    W.coef = coef ? L.take<double>(n * rows * 18) : nullptr;
+    return L.size();
+  };
+  QuerySlotGuard q;
+  {
+    const int rcq = q.acquire(m, layout(nullptr));
+    if (rcq) return rcq;
+  }
+  layout(q.s->pin);
   W.n_prob = n_prob;
   W.maxw = cfg->max_way_points;
   W.max_vel = cfg->max_vel, W.ctrl_pt_dist = cfg->ctrl_pt_dist;
   W.min_seg = cfg->min_seg, W.forced_seg = cfg->seg_num, W.max_samples = cfg->max_samples;
-  int* p_nway = reinterpret_cast<int*>(take(b_int));
-  double* p_way = reinterpret_cast<double*>(take(b_way));
-  double* p_vel = reinterpret_cast<double*>(take(b_v3));
-  double* p_acc = reinterpret_cast<double*>(take(b_v3));
   memcpy(p_nway, n_way, n * sizeof(int));
   memcpy(p_way, way_xyz, n * maxw * 3 * sizeof(double));
   memcpy(p_vel, vel_xyz, n * 3 * sizeof(double));
   memcpy(p_acc, acc_xyz, n * 3 * sizeof(double));
   W.n_way = p_nway, W.way = p_way, W.vel = p_vel, W.acc = p_acc;
-  W.status = reinterpret_cast<int*>(take(b_int));
-  W.seg_num = reinterpret_cast<int*>(take(b_int));
-  W.n_samples = reinterpret_cast<int*>(take(b_int));
-  W.duration = reinterpret_cast<double*>(take(b_dbl));
-  W.length = reinterpret_cast<double*>(take(b_dbl));
-  W.dt = reinterpret_cast<double*>(take(b_dbl));
-  W.samples = reinterpret_cast<double*>(take(b_smp));
-  W.derivs = reinterpret_cast<double*>(take(b_der));
-  W.seg_times = seg_times ? reinterpret_cast<double*>(take(b_tim)) : nullptr;
-  W.coef = coef ? reinterpret_cast<double*>(take(b_cf)) : nullptr;
   {
     const int rc = wptraj_launch(q.s->st, W);
     if (rc) return rc;

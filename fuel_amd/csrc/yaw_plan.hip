@@ -117,9 +117,9 @@ __global__ void __launch_bounds__(YP_NT) k_yaw_plan(YawArgs Y) {
 
   const bool follow = Y.cfg.mode == FUELMI_YAW_FOLLOW;
   const int p = Y.cfg.pos_degree;
-  const int n = Y.n_ctrl ? Y.n_ctrl[b] : Y.n_ctrl_all;
-  const double dt = Y.knot[(size_t)b * Y.knot_stride];
-  const double* C = Y.pos + (size_t)b * Y.pos_stride;
+  const int n = Y.src.n_ctrl ? Y.src.n_ctrl[b] : Y.src.n_ctrl_all;
+  const double dt = Y.src.knot[(size_t)b * Y.src.knot_stride];
+  const double* C = Y.src.pos + (size_t)b * Y.src.pos_stride;
   // (the host route refuses these before any launch; the variables of a device batch are not seen by the host)
   if (!(dt > 0.0) || !isfinite(dt) || n < p + 1 || n > Y.cfg.max_ctrl) {
     yp_write(Y, b, tid, FUELMI_YAW_DEGENERATE, 0.0, 0, 0.0, 0, nullptr, 0, nullptr, 0.0, 0.0, nullptr, 3);
@@ -413,27 +413,19 @@ int yaw_check(const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob
 
 size_t yaw_out_bytes(const fuelmi_yaw_cfg* cfg, int n_prob, YawArgs& Y, unsigned char* base, bool dot, bool ddot) {
   const size_t n = (size_t)n_prob, maxs = (size_t)cfg->max_seg;
-  auto pad = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    unsigned char* p = base ? base + at : nullptr;
-    at += pad(bytes);
-    return p;
-  };
-  Y.status = reinterpret_cast<int*>(take(n * sizeof(int)));
-  Y.seg_num = reinterpret_cast<int*>(take(n * sizeof(int)));
-  Y.n_waypt = reinterpret_cast<int*>(take(n * sizeof(int)));
-  Y.duration = reinterpret_cast<double*>(take(n * sizeof(double)));
-  Y.dt_yaw = reinterpret_cast<double*>(take(n * sizeof(double)));
-  Y.end_yaw_out = reinterpret_cast<double*>(take(n * sizeof(double)));
-  Y.cost = reinterpret_cast<double*>(take(n * sizeof(double)));
-  Y.yaw_ctrl = reinterpret_cast<double*>(take(n * (maxs + 3) * sizeof(double)));
-  Y.waypts = reinterpret_cast<double*>(take(n * maxs * sizeof(double)));
-  unsigned char* d1 = take(dot ? n * (maxs + 2) * sizeof(double) : 0);
-  unsigned char* d2 = take(ddot ? n * (maxs + 1) * sizeof(double) : 0);
-  Y.yawdot_ctrl = dot ? reinterpret_cast<double*>(d1) : nullptr;
-  Y.yawddot_ctrl = ddot ? reinterpret_cast<double*>(d2) : nullptr;
-  return at;
+  BlockLayout L(base, 16);
+  Y.status = L.take<int>(n);
+  Y.seg_num = L.take<int>(n);
+  Y.n_waypt = L.take<int>(n);
+  Y.duration = L.take<double>(n);
+  Y.dt_yaw = L.take<double>(n);
+  Y.end_yaw_out = L.take<double>(n);
+  Y.cost = L.take<double>(n);
+  Y.yaw_ctrl = L.take<double>(n * (maxs + 3));
+  Y.waypts = L.take<double>(n * maxs);
+  Y.yawdot_ctrl = dot ? L.take<double>(n * (maxs + 2)) : nullptr;
+  Y.yawddot_ctrl = ddot ? L.take<double>(n * (maxs + 1)) : nullptr;
+  return L.size();
 }
 
 int yaw_copy_out(const fuelmi_yaw_cfg* cfg, int n_prob, const YawArgs& H, int* status, double* duration, int* seg_num,
@@ -491,31 +483,31 @@ extern "C" int fuelmi_map_plan_yaws(fuelmi_map* m, const fuelmi_bspline_cfg* w, 
   ARGCHK(m);
   HIPCHK(hipSetDevice(m->device));
   const size_t n = (size_t)n_prob, maxc = (size_t)cfg->max_ctrl;
-  auto pad = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  const size_t b_int = pad(n * sizeof(int)), b_dbl = pad(n * sizeof(double)), b_pos = pad(n * maxc * 3 * sizeof(double)),
-               b_s3 = pad(n * 3 * sizeof(double));
   YawArgs Y;
   memset(&Y, 0, sizeof(Y));
   const size_t b_out = yaw_out_bytes(cfg, n_prob, Y, nullptr, yawdot_ctrl != nullptr, yawddot_ctrl != nullptr);
+  int* p_nc;
+  double *p_knot, *p_end, *p_pos, *p_start;
+  unsigned char* p_out;
+  auto layout = [&](unsigned char* base) {  // the slot's pinned block: the inputs, then the results
+    BlockLayout L(base, 16);
+    p_nc = L.take<int>(n);
+    p_knot = L.take<double>(n);
+    p_end = L.take<double>(n);
+    p_pos = L.take<double>(n * maxc * 3);
+    p_start = L.take<double>(n * 3);
+    p_out = L.take<unsigned char>(b_out);
+    return L.size();
+  };
   QuerySlotGuard q;
   {
-    const int rcq = q.acquire(m, b_int + 2 * b_dbl + b_pos + b_s3 + b_out);
+    const int rcq = q.acquire(m, layout(nullptr));
     if (rcq) return rcq;
   }
-  unsigned char* at = q.s->pin;
-  auto take = [&](size_t bytes) {
-    unsigned char* p = at;
-    at += bytes;
-    return p;
-  };
+  layout(q.s->pin);
   Y.cfg = *cfg;
   Y.ld_smooth = w->ld_smooth, Y.ld_start = w->ld_start, Y.ld_end = w->ld_end, Y.ld_waypt = w->ld_waypt;
   Y.n_prob = n_prob;
-  int* p_nc = reinterpret_cast<int*>(take(b_int));
-  double* p_knot = reinterpret_cast<double*>(take(b_dbl));
-  double* p_end = reinterpret_cast<double*>(take(b_dbl));
-  double* p_pos = reinterpret_cast<double*>(take(b_pos));
-  double* p_start = reinterpret_cast<double*>(take(b_s3));
   memcpy(p_nc, n_ctrl, n * sizeof(int));
   memcpy(p_knot, knot_span, n * sizeof(double));
   if (end_yaw)
@@ -524,11 +516,9 @@ extern "C" int fuelmi_map_plan_yaws(fuelmi_map* m, const fuelmi_bspline_cfg* w, 
     memset(p_end, 0, n * sizeof(double));
   memcpy(p_pos, pos_ctrl, n * maxc * 3 * sizeof(double));
   memcpy(p_start, start_yaw, n * 3 * sizeof(double));
-  Y.n_ctrl = p_nc, Y.n_ctrl_all = 0;
-  Y.pos = p_pos, Y.pos_stride = maxc * 3;
-  Y.knot = p_knot, Y.knot_stride = 1;
+  Y.src = {p_nc, 0, p_pos, maxc * 3, p_knot, 1};
   Y.start_yaw = p_start, Y.end_yaw = p_end;
-  yaw_out_bytes(cfg, n_prob, Y, take(b_out), yawdot_ctrl != nullptr, yawddot_ctrl != nullptr);
+  yaw_out_bytes(cfg, n_prob, Y, p_out, yawdot_ctrl != nullptr, yawddot_ctrl != nullptr);
   {
     const int rc = yaw_launch(q.s->st, Y);
     if (rc) return rc;
