@@ -181,6 +181,16 @@ TSP_MAX_DIM, TSP_EXACT_CAP = 1024, 16
 TSP_DEFAULT_RESTARTS, TSP_DEFAULT_KICKS, TSP_DEFAULT_EXACT_MAX = 64, 8, 12
 
 
+class RenderCfg(C.Structure):
+    """fuelmi_render_cfg: the device, the image and its pinhole intrinsics, the node restated, HOST_NODE's range cull, the
+    frames kept on the device."""
+    _fields_ = [("device", C.c_int), ("rows", C.c_int), ("cols", C.c_int), ("fx", C.c_double), ("fy", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double), ("model", C.c_int), ("range", C.c_double), ("max_poses", C.c_int)]
+
+
+RENDER_HOST_NODE, RENDER_CUDA_NODE = 0, 1
+
+
 class BsplineCfg(C.Structure):
     _fields_ = [(n, C.c_double) for n in
                 ("ld_smooth", "ld_dist", "ld_feasi", "ld_start", "ld_end", "ld_guide", "ld_waypt",
@@ -316,6 +326,14 @@ SYMBOLS = {
     "fuelmi_tsp_create": (C.c_int, [C.c_int, C.POINTER(TspCfg), _PP]),
     "fuelmi_tsp_destroy": (None, [_P]),
     "fuelmi_tsp_solve": (C.c_int, [_P, C.c_int, _ip, C.POINTER(C.c_int32), _ip, C.POINTER(C.c_int64), _ip]),
+    "fuelmi_render_create": (C.c_int, [C.POINTER(RenderCfg), _PP]),
+    "fuelmi_render_destroy": (C.c_int, [_P]),
+    "fuelmi_render_set_cloud": (C.c_int, [_P, C.c_void_p, C.c_int]),
+    "fuelmi_render_depth": (C.c_int, [_P, C.c_int, _dp, _dp, C.c_double, C.c_void_p, C.c_void_p, _ip]),
+    "fuelmi_render_frame_raw": (C.c_void_p, [_P, C.c_int]),
+    "fuelmi_render_frame_metres": (C.c_void_p, [_P, C.c_int]),
+    "fuelmi_render_plan": (C.c_int, [C.POINTER(RenderCfg), C.c_int, _ip]),
+    "fuelmi_render_times": (C.c_int, [_P, _dp]),
     "fuelmi_bspline_cost_grad": (C.c_int, [_P, C.POINTER(BsplineCfg), C.POINTER(BsplineBatch), _dp, _dp]),
     "fuelmi_bspline_optimize": (C.c_int, [_P, C.POINTER(BsplineCfg), C.POINTER(BsplineBatch), C.c_int, C.c_double, _dp, _dp,
                                 C.POINTER(C.c_int)]),

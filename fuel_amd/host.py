@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BsplineBatch, BsplineCfg, CloudCfg, FrontierCfg, GoalCfg, KinoCfg, MapCfg, MapInfo, PathCfg, RefineCfg, TrajChkCfg, TrajSmpCfg, TspCfg,
+from ._lib import (BsplineBatch, BsplineCfg, CloudCfg, FrontierCfg, GoalCfg, KinoCfg, MapCfg, MapInfo, PathCfg, RefineCfg, RenderCfg, TrajChkCfg, TrajSmpCfg, TspCfg,
                    WptrajCfg, YawCfg, check, lib)
 
 # exploration.launch / algorithm.xml defaults (exploration_manager/launch/algorithm.xml:33-59,170-181)
@@ -786,6 +786,103 @@ class TourSolver:
     def close(self):
         if self._h:
             lib().fuelmi_tsp_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DepthRenderer:
+    """fuelmi_render: the simulated depth camera pcl_render_node (uav_simulator/local_sensing) for a batch of poses, the
+    frames left on the device.  model: _lib.RENDER_HOST_NODE (depth_render_node.cpp, the node built by default; `range`
+    is its 5.0 m cull, inf switches it off) or _lib.RENDER_CUDA_NODE (depth_render.cu).  The rules are include/fuelmi.h's;
+    tests/depth_render_ref.py restates them."""
+
+    PLAN_KEYS = ("segment_lanes", "wave_min_size", "project_points", "project_workgroups", "splat_workgroups",
+                 "convert_workgroups")
+
+    def __init__(self, rows, cols, fx, fy, cx, cy, model=_lib.RENDER_HOST_NODE, range=5.0, max_poses=1, device=0):
+        self.cfg = self.config(rows, cols, fx, fy, cx, cy, model, range, max_poses, device)
+        self.rows, self.cols, self.max_poses = int(rows), int(cols), int(max_poses)
+        self._h = C.c_void_p()
+        check(lib().fuelmi_render_create(C.byref(self.cfg), C.byref(self._h)))
+
+    @staticmethod
+    def config(rows, cols, fx, fy, cx, cy, model=_lib.RENDER_HOST_NODE, range=5.0, max_poses=1, device=0):
+        return RenderCfg(int(device), int(rows), int(cols), float(fx), float(fy), float(cx), float(cy), int(model),
+                         float(range), int(max_poses))
+
+    @staticmethod
+    def pose_transform(pos, q_wxyz):
+        """(T_cw, cam_pos) of a camera at `pos` with orientation (w, x, y, z): cam2world = [R(q) | pos], T_cw the first
+        three rows of its general 4 x 4 inverse (the node's cam2world.inverse()), cam_pos its translation column."""
+        w, x, y, z = (float(v) for v in q_wxyz)
+        c2w = np.eye(4)
+        c2w[:3, :3] = [[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                       [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                       [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]]
+        c2w[:3, 3] = np.asarray(pos, dtype=np.float64)
+        return np.ascontiguousarray(np.linalg.inv(c2w)[:3, :]), c2w[:3, 3].copy()
+
+    def set_cloud(self, xyz, n_points=None):
+        """xyz: an array of n x 3 floats, or (with n_points) the address of as many floats in host or device memory."""
+        if n_points is None:
+            pts = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+            check(lib().fuelmi_render_set_cloud(self._h, C.c_void_p(pts.ctypes.data), len(pts)))
+        else:
+            check(lib().fuelmi_render_set_cloud(self._h, C.c_void_p(int(xyz)), int(n_points)))
+
+    def render(self, T_cw, cam_pos, scaling=1000.0, metres=True, raw=True):
+        """-> (metres [n, rows, cols] float32 or None, raw [n, rows, cols] uint16 or None, stats [n, 4] int32)"""
+        T = np.ascontiguousarray(T_cw, dtype=np.float64).reshape(-1, 12)
+        p = np.ascontiguousarray(cam_pos, dtype=np.float64).reshape(-1, 3)
+        if len(T) != len(p):
+            raise ValueError("DepthRenderer.render: %d transforms, %d camera positions" % (len(T), len(p)))
+        n = len(T)
+        m = np.empty((n, self.rows, self.cols), dtype=np.float32) if metres else None
+        r = np.empty((n, self.rows, self.cols), dtype=np.uint16) if raw else None
+        stats = np.zeros((max(n, 1), 4), dtype=np.int32)
+        check(lib().fuelmi_render_depth(self._h, n, _dp(T), _dp(p), float(scaling), None if m is None else m.ctypes.data,
+                                        None if r is None else r.ctypes.data, _ip(stats)))
+        return m, r, stats[:n]
+
+    def frame_raw_ptr(self, k):
+        """device address of frame k's uint16 image (for SDFMap.inputDepthImageAt): valid until the next render, set_cloud
+        or close"""
+        p = lib().fuelmi_render_frame_raw(self._h, int(k))
+        if not p:
+            check(_lib.EINVAL)
+        return p
+
+    def frame_metres_ptr(self, k):
+        p = lib().fuelmi_render_frame_metres(self._h, int(k))
+        if not p:
+            check(_lib.EINVAL)
+        return p
+
+    @classmethod
+    def plan_for(cls, cfg, n_points):
+        out = np.zeros(8, dtype=np.int32)
+        check(lib().fuelmi_render_plan(C.byref(cfg), int(n_points), _ip(out)))
+        d = dict(zip(cls.PLAN_KEYS, (int(v) for v in out[:6])))
+        d["scratch_bytes"] = int(out[6]) + (int(out[7]) << 31)
+        return d
+
+    def plan(self, n_points=0):
+        return self.plan_for(self.cfg, n_points)
+
+    def times(self):
+        """device milliseconds of the last render: cull + project, splat, convert"""
+        ms = np.zeros(3)
+        check(lib().fuelmi_render_times(self._h, _dp(ms)))
+        return ms
+
+    def close(self):
+        if self._h:
+            lib().fuelmi_render_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

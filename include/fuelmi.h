@@ -1175,6 +1175,79 @@ int fuelmi_cloud_plan(const int dims[3], const int lo[3], const int hi[3], int o
 int fuelmi_map_cloud_times(const fuelmi_map* m, double ms3[3]);
 
 /* ------------------------------------------------------------------------------------------
+ * Depth renderer: the simulated depth camera pcl_render_node (uav_simulator/local_sensing) for a batch of poses.  A
+ * renderer is not tied to a map: it owns a stream, a copy of the world cloud, the frames of max_poses poses and a
+ * grow-only scratch (the records of n_pose * n_points); nothing is allocated after the first call of a given size.
+ * Per pixel both of the reference's nodes take the minimum depth over the square windows that the points splat; each
+ * model restates its node's arithmetic literally, with the usual C++ conversions and without FMA contraction.
+ *   FUELMI_RENDER_HOST_NODE  (src/depth_render_node.cpp:112-161, the node built by default).  Per point, in this order:
+ *     pw = the point as double; dropped if sqrt(dx^2 + dy^2 + dz^2) > range (f64, summed left to right, d = cam_pos - pw);
+ *     pc = R pw + t in f64, each row ((r0 x + r1 y) + r2 z) + t; dropped if pc.z <= 0;
+ *     float px = pc.x / pc.z * fx + cx (f64, rounded once), py likewise; dropped if px < 0 || px >= cols || py < 0 ||
+ *     py >= rows (compared as float); float dist = pc.z; int r = 0.0573 * fx / dist + 0.5 (f64, truncated);
+ *     window x from max(int(px - r), 0) to min(int(px + r), cols - 1) (float arithmetic, truncated toward zero), y
+ *     likewise with the same r; the pixel is the smallest dist, an empty pixel 0.0f.
+ *   FUELMI_RENDER_CUDA_NODE  (src/depth_render.cu:2-43 and the conversion of src/pcl_render_node.cpp:300-310).  fx, fy,
+ *     cx, cy, R, t rounded to float once; the transform in f32, each row ((x r0 + y r1) + z r2) + t; dropped if
+ *     z <= 0.0f; int u = x / z * fx + cx + 0.5 (f32 up to the sum, + 0.5 in f64, truncated), v likewise; dropped if u
+ *     or v is outside the image; int mm = z * 1000.0f + 0.5f (f32); int r = 0.0573 * fx / z + 0.5f (f64); window
+ *     u +- r, v +- r clipped to the image; the pixel is the minimum of mm and 999999, published as
+ *     float d = (float)mm / 1000.0f; d = d < 500.0f ? d : 0.  range is ignored.
+ *   The raw frame is what MapROS::depthPoseCallback makes of the published image (plan_env/src/map_ros.cpp:132-133,
+ *     convertTo(CV_16UC1, k)): saturate_u16(round_half_even(metres * (float)k)), OpenCV's rule for 32F -> 16U.
+ * Deviations, each counted in stats[1]:
+ *   1. a point that passed the culls with (float)dist < 1e-3f is dropped.  The reference's `value < 1e-3` test makes the
+ *      result depend on the cloud's order for such a point, its window covers the whole image and its `int r` conversion
+ *      is undefined for a tiny dist.  Without such a point the sequential update equals the order-free minimum with 0 as
+ *      "empty": the result does not depend on the schedule or on the cloud's order.
+ *   2. a point with a non-finite coordinate is dropped before the culls; so is a point whose camera depth or projection
+ *      is NaN, or (CUDA_NODE) whose u, v or mm would leave int before the truncation.  The reference's conversions are
+ *      undefined there; every such point is off the image or beyond 500 m.  HOST_NODE: where float(r) rounds px + r up
+ *      to 2^31 the window ends at the border.
+ *   3. an nvcc build contracts CUDA_NODE's f32 transform into FMAs; this restates the source text without contraction.
+ *   4. the summation order of norm() and of the 3 x 3 product is the one stated above (Eigen's own is the stand-in's).
+ * fuelmi_render_depth: T_cw [n_pose][12] are the first three rows of world->camera (the node's cam2world.inverse(),
+ * computed by the caller), cam_pos [n_pose][3] is cam2world's translation.  Synchronous: when it returns all n_pose
+ * frames are complete on the device (fuelmi_render_frame_raw / _metres: device pointers, valid until the next render,
+ * set_cloud or destroy of this renderer; frame k of the last call) and copied to the host arrays that were given
+ * (metres [n_pose][rows][cols] f32, raw likewise u16; either may be NULL).  A raw frame pointer can go straight into
+ * fuelmi_map_input_depth of any map on the same device.  stats [n_pose][4] (may be NULL): points that passed the culls,
+ * points dropped as undefined, pixels whose metres value is not 0, 0.
+ * Refused before anything is launched: rows or cols < 1, fx or fy not finite or <= 0, cx or cy not finite, an unknown
+ * model, range < 0 or NaN (HOST_NODE), max_poses < 1, n_points < 0, n_pose < 1, a non-finite T_cw or cam_pos entry, a
+ * render before any set_cloud (an empty cloud is legal: all-zero frames), k_depth_scaling_factor not finite or <= 0, a
+ * renderer that is null or was destroyed (FUELMI_EINVAL); rows * cols > 2^24, 57.3 * max(fx, fy) + 1 >= 2^31 (the
+ * radius of the closest point kept), max_poses > 4096 or max_poses * rows * cols > 2^28, n_points > 2^27, n_pose >
+ * max_poses, n_pose * n_points > 2^28 (FUELMI_ELIMIT).  fuelmi_render_create returns FUELMI_ENODEV without a gfx950
+ * device, after the checks of cfg.  One thread per renderer at a time.
+ * ---------------------------------------------------------------------------------------- */
+enum { FUELMI_RENDER_HOST_NODE = 0, FUELMI_RENDER_CUDA_NODE = 1 };
+typedef struct {
+  int device, rows, cols;
+  double fx, fy, cx, cy;
+  int model;     /* which of the reference's two nodes is restated */
+  double range;  /* HOST_NODE: the node's 5.0 m cull around the camera; +inf switches it off; ignored by CUDA_NODE */
+  int max_poses; /* frames the renderer keeps on the device */
+} fuelmi_render_cfg;
+typedef struct fuelmi_render fuelmi_render;
+int fuelmi_render_create(const fuelmi_render_cfg* cfg, fuelmi_render** out);
+int fuelmi_render_destroy(fuelmi_render* r);
+/* xyz: n_points * 3 floats in host or device memory; copied */
+int fuelmi_render_set_cloud(fuelmi_render* r, const float* xyz, int n_points);
+int fuelmi_render_depth(fuelmi_render* r, int n_pose, const double* T_cw, const double* cam_pos,
+                        double k_depth_scaling_factor, float* metres, unsigned short* raw, int* stats);
+/* NULL (with a message) for a renderer that is not live or k outside 0 .. max_poses - 1 */
+const unsigned short* fuelmi_render_frame_raw(const fuelmi_render* r, int k);
+const float* fuelmi_render_frame_metres(const fuelmi_render* r, int k);
+/* the kernels' geometry for cfg and a cloud of n_points (host only, no device needed): out = {lanes of a small window's
+ * segment, the size (larger side of the clipped window, pixels) from which a window is spread over a wave, points of a
+ * projection workgroup, projection workgroups per pose, splat workgroups per pose, convert workgroups per pose, scratch
+ * bytes of max_poses poses modulo 2^31, the same divided by 2^31}.  cfg and n_points are checked like above. */
+int fuelmi_render_plan(const fuelmi_render_cfg* cfg, int n_points, int out[8]);
+/* device milliseconds of the last fuelmi_render_depth: cull + project, splat, convert */
+int fuelmi_render_times(const fuelmi_render* r, double ms3[3]);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): HIP events recorded on the map's own stream.
  * ---------------------------------------------------------------------------------------- */
 enum {
