@@ -6,52 +6,13 @@
 // the stencils it belongs to) so no atomics are needed; cost and the knot-span gradient are
 // wave-reduced with DPP shuffles.  All arithmetic is f64 like the reference; the ESDF is read
 // as 8 f32 gathers per control point (trilinear, SDFMap::getDistWithGrad sdf_map.cpp:497-536).
+// Also here: the L-BFGS solves, the spline glue (fit, boundary states) and the entries of the optimiser and the fit.  What
+// the planner stages' own fuelmi_bspline_dev_* entries (in the stages' files) need of this file is in bspline_batch.h.
 #include <cmath>
 #include <cstring>
 #include <vector>
 
-#include "fuelmi_internal.h"
-
-struct BsplineArgs {
-  fuelmi_bspline_cfg cfg;
-  int cost_function, dim, N, C, end_n, n_waypt, nvar, order, n_guide;
-  const double* x;
-  const double* pt_dist;
-  const double* knot_span;
-  const double* time_lb;
-  const double* start_state;
-  const double* end_state;
-  const double* guide_pts;
-  const double* waypoints;
-  const int* waypt_idx;
-  const double* view_pt;
-  const double* view_dir;
-  const int* view_idx;
-  double* cost;
-  double* grad;
-};
-
-struct fuelmi_bspline_dev {
-  fuelmi_map* map;  // cleared if the map is destroyed first (then only _destroy is legal)
-  int device = 0;
-  BsplineArgs a;
-  std::vector<void*> allocs;
-  size_t lds;       // evaluation scratch of one wave (the solves build on it)
-  size_t lds_eval4; // ... plus the partial gradients / costs of the four-wave cost kernel
-  double *opt_x = nullptr, *opt_cost = nullptr;  // fuelmi_bspline_dev_optimize outputs
-  int* opt_evals = nullptr;
-  // fuelmi_bspline_dev_eval_pinned: two pinned result slots (cost [C] | grad [C][nvar]) the cost kernel writes
-  // directly, and the event behind each launch
-  double* pin_out[2] = {nullptr, nullptr};
-  hipEvent_t ev_out[2] = {nullptr, nullptr};
-  bool opt_valid = false;    // opt_x holds the solve of what the batch holds now (a reload clears it)
-  // per-call scratch, reserved on the map's stream (every kernel that reads it runs there); no pointer into it
-  // outlives the call that carved it
-  DevScratch fit_in;   // fuelmi_bspline_dev_load_*: ts | points | derivs, then the loader's own arrays
-  DevScratch yaw_dev;  // fuelmi_bspline_dev_plan_yaws: start | end | results
-  DevScratch chk_dev;  // fuelmi_bspline_dev_check_trajs: t_now | results
-  DevScratch smp_dev;  // fuelmi_bspline_dev_sample_trajs: yaw splines, times | results
-};
+#include "bspline_batch.h"
 
 // 64-lane sum on the DPP data path (no LDS crossbar round trips): quads, half rows, rows, then the two
 // row broadcasts of GFX9; lane 63 ends with the total.  All 64 lanes must be active.
@@ -739,22 +700,6 @@ k_bspline_optimize_r(Geo g, const float* __restrict__ dist, BsplineArgs A, Lbfgs
 // Every row touches `degree` consecutive unknowns, so the normal matrix is banded (half-bandwidth
 // degree-1): banded Cholesky plus one step of iterative refinement against the original rows, which
 // brings the solution back to QR accuracy (cond(A) < 1e3).
-struct FitArgs {
-  int C, K, degree;
-  const double* ts;      // [C]
-  const double* points;  // [C][K][3]
-  const double* derivs;  // [C][4][3]  start vel, end vel, start acc, end acc
-  double* ctrl;          // candidate c: ctrl + c * stride, (K + degree - 1) rows of 3
-  long stride;
-  // planner glue (all optional): what setBoundaryStates / optimize() derive from the fitted spline
-  int write_dt;          // ctrl[c * stride + 3 n] = ts[c]   (trailing knot-span variable)
-  double* knot_span;     // [C]
-  double* pt_dist;       // [C]      optimize() :136-140
-  double* start_state;   // [C][3][3]  getBoundaryStates(2, 0).start
-  double* end_state;     // [C][3][3]  row 0 = getBoundaryStates(2, 0).end[0]
-  const int* skip;       // [C] or null: a candidate with skip[c] != 0 is left as it is
-};
-
 // value at t = 0 (at_end = false) or t = duration of the d-th derivative of the uniform B-spline with
 // control points q[n][3], degree p, knots u[n + p + 1]  (evaluateDeBoorT of computeDerivatives()[d-1];
 // the derivative's knot vector is the parent's without its first and last knot, :99-103)
@@ -1365,9 +1310,8 @@ extern "C" int fuelmi_bspline_optimize(fuelmi_map* m, const fuelmi_bspline_cfg* 
   return bspline_oneshot(m, cfg, batch, max_eval, max_time_s, cost_out, x_out, evals_out);
 }
 
-// ---- spline glue entry points ----
-namespace {
-int fit_launch(fuelmi_map* m, const FitArgs& F, hipStream_t st = nullptr) {
+// ---- spline glue entry points (fit_launch, fit_args and opt_spline_src are declared in bspline_batch.h) ----
+int fit_launch(fuelmi_map* m, const FitArgs& F, hipStream_t st) {
   const size_t lds = fit_lds(F.K, F.degree);
   if (lds > 160 * 1024) {
     fuelmi_set_error("%d samples exceed the LDS budget of the spline fit", F.K);
@@ -1410,7 +1354,6 @@ SplineSrc opt_spline_src(const fuelmi_bspline_dev* b) {
   if (A.cost_function & FUELMI_COST_MINTIME) return {nullptr, A.N, b->opt_x, nvar, b->opt_x + (A.nvar - 1), nvar};
   return {nullptr, A.N, b->opt_x, nvar, A.knot_span, 1};
 }
-}  // namespace
 
 extern "C" int fuelmi_bspline_parameterize(fuelmi_map* m, int n_traj, int n_points, int degree, const double* ts,
                                            const double* points, const double* derivs, double* ctrl) {
@@ -1508,311 +1451,4 @@ extern "C" int fuelmi_bspline_dev_load_samples(fuelmi_bspline_dev* b, int n_poin
                              reinterpret_cast<double*>(d + b_ts + b_pts), nullptr);
   StageScope sc(m, FUELMI_K_BSPLINE);
   return fit_launch(m, F);
-}
-
-// way-points -> min-jerk samples (k_waypoint_traj, written into the staging) -> the fit above, all on the map's stream
-extern "C" int fuelmi_bspline_dev_load_waypoints(fuelmi_bspline_dev* b, const fuelmi_wptraj_cfg* cfg, const int* n_way,
-                                                 const double* way_xyz, const double* vel_xyz, const double* acc_xyz,
-                                                 int* status, double* duration) {
-  ARGCHK(b && cfg && status);
-  BsplineArgs& A = b->a;
-  const int degree = A.cfg.bspline_degree;
-  ARGCHK(A.dim == 3 && degree >= 3 && degree <= 5 && A.N - degree >= 1);
-  const int seg = A.N - degree, n_points = seg + 1;
-  ARGCHK(cfg->seg_num == 0 || cfg->seg_num == seg);
-  fuelmi_wptraj_cfg wc = *cfg;
-  wc.seg_num = seg, wc.max_samples = n_points;
-  {
-    const int rc = wptraj_check(&wc, A.C, n_way, way_xyz, vel_xyz, acc_xyz);
-    if (rc) return rc;
-  }
-  fuelmi_map* m = b->map;
-  ARGCHK(m);
-  b->opt_valid = false;
-  HIPCHK(hipSetDevice(m->device));
-  const size_t C = (size_t)A.C, K = (size_t)n_points, maxw = (size_t)wc.max_way_points;
-  WpTrajArgs W;
-  memset(&W, 0, sizeof(W));
-  double* d_fit;  // ts | points | derivs: the layout fuelmi_bspline_dev_load_samples stages
-  int* d_nway;
-  double *d_way, *d_vel, *d_acc;
-  auto layout = [&](unsigned char* base) {
-    BlockLayout L(base, 16);
-    d_fit = L.take<double>(C * (1 + K * 3 + 12));
-    d_nway = L.take<int>(C);
-    d_way = L.take<double>(C * maxw * 3);
-    d_vel = L.take<double>(C * 3);
-    d_acc = L.take<double>(C * 3);
-    W.status = L.take<int>(C);
-    W.seg_num = L.take<int>(C);
-    W.n_samples = L.take<int>(C);
-    W.duration = L.take<double>(C);
-    W.length = L.take<double>(C);
-    return L.size();
-  };
-  hipStream_t st = m->stream;
-  {
-    const int rc = b->fit_in.reserve(st, layout(nullptr));
-    if (rc) return rc;
-  }
-  layout(b->fit_in.base());
-  W.n_prob = A.C;
-  W.maxw = wc.max_way_points;
-  W.max_vel = wc.max_vel, W.ctrl_pt_dist = wc.ctrl_pt_dist;
-  W.min_seg = wc.min_seg, W.forced_seg = seg, W.max_samples = n_points;
-  HIPCHK(hipMemcpyAsync(d_nway, n_way, C * sizeof(int), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_way, way_xyz, C * maxw * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_vel, vel_xyz, C * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_acc, acc_xyz, C * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-  W.n_way = d_nway, W.way = d_way, W.vel = d_vel, W.acc = d_acc;
-  W.dt = d_fit;  // the fit's knot spans
-  W.samples = d_fit + C;
-  W.derivs = d_fit + C + C * K * 3;
-  const FitArgs F = fit_args(b, W.dt, W.samples, W.derivs, W.status);
-  {
-    StageScope sc(m, FUELMI_K_BSPLINE);
-    const int rcw = wptraj_launch(st, W);
-    if (rcw) return rcw;
-    const int rcf = fit_launch(m, F);
-    if (rcf) return rcf;
-  }
-  HIPCHK(hipMemcpyAsync(status, W.status, C * sizeof(int), hipMemcpyDeviceToHost, st));
-  if (duration) HIPCHK(hipMemcpyAsync(duration, W.duration, C * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(stream_wait(st));
-  for (int c = 0; c < A.C; ++c)
-    if (status[c] == -1) {
-      fuelmi_set_error("waypoint trajectories: candidate %d does not give %d samples", c, n_points);
-      return FUELMI_ELIMIT;
-    }
-  return FUELMI_OK;
-}
-
-// start / goal -> kinodynamic search -> getSamples (k_kino_path, written into the staging) -> the fit, all on the map's
-// stream: the mid-range counterpart of the call above
-extern "C" int fuelmi_bspline_dev_load_kino(fuelmi_bspline_dev* b, const fuelmi_kino_cfg* cfg, const double* start_xyz,
-                                            const double* start_vel, const double* start_acc, const double* goal_xyz,
-                                            const double* goal_vel, int* status, double* T_sum) {
-  ARGCHK(b && cfg && status);
-  BsplineArgs& A = b->a;
-  const int degree = A.cfg.bspline_degree;
-  ARGCHK(A.dim == 3 && degree >= 3 && degree <= 5 && A.N - degree >= 1);
-  const int seg = A.N - degree, n_points = seg + 1;
-  ARGCHK(cfg->seg_num == 0 || cfg->seg_num == seg);
-  fuelmi_kino_cfg kc = *cfg;
-  kc.seg_num = seg, kc.max_samples = n_points, kc.max_path_nodes = 1;
-  {
-    const int rc = kino_check(&kc, A.C, start_xyz, start_vel, start_acc, goal_xyz, goal_vel);
-    if (rc) return rc;
-  }
-  fuelmi_map* m = b->map;
-  ARGCHK(m);
-  b->opt_valid = false;
-  HIPCHK(hipSetDevice(m->device));
-  const size_t C = (size_t)A.C, K = (size_t)n_points;
-  hipStream_t st = m->stream;
-  {
-    const int rc = b->fit_in.reserve(st, C * (1 + K * 3 + 12) * sizeof(double));
-    if (rc) return rc;
-  }
-  double* d_fit = static_cast<double*>(b->fit_in.p);  // ts | points | derivs
-  KinoArgs W;
-  auto layout = [&](unsigned char* base) {  // the results that do not go to the fit
-    BlockLayout L(base, 16);
-    W.status = L.take<int>(C);
-    W.which = L.take<int>(C);
-    W.iter_num = L.take<int>(C);
-    W.use_node_num = L.take<int>(C);
-    W.n_nodes = L.take<int>(C);
-    W.shot = L.take<int>(C);
-    W.seg_num = L.take<int>(C);
-    W.n_samples = L.take<int>(C);
-    W.skip = L.take<int>(C);
-    W.t_shot = L.take<double>(C);
-    W.T_sum = L.take<double>(C);
-    W.coef_shot = L.take<double>(C * 12);
-    return L.size();
-  };
-  unsigned char* io = nullptr;
-  {
-    const int rc = kino_prepare(m, &kc, A.C, start_xyz, start_vel, start_acc, goal_xyz, goal_vel, layout(nullptr), W, &io);
-    if (rc) return rc;
-  }
-  layout(io);
-  W.load_points = n_points;
-  W.ts_out = d_fit;  // the fit's knot spans
-  W.samples = d_fit + C;
-  W.derivs = d_fit + C + C * K * 3;
-  const FitArgs F = fit_args(b, W.ts_out, W.samples, W.derivs, W.skip);
-  {
-    const int rck = kino_launch(m, W);  // (outside the scope: the search is no spline stage)
-    if (rck) return rck;
-    StageScope sc(m, FUELMI_K_BSPLINE);
-    const int rcf = fit_launch(m, F);
-    if (rcf) return rcf;
-  }
-  HIPCHK(hipMemcpyAsync(status, W.status, C * sizeof(int), hipMemcpyDeviceToHost, st));
-  if (T_sum) HIPCHK(hipMemcpyAsync(T_sum, W.T_sum, C * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(stream_wait(st));
-  for (int c = 0; c < A.C; ++c)
-    if (status[c] == -1) {
-      fuelmi_set_error("kinodynamic search: candidate %d does not give %d samples", c, n_points);
-      return FUELMI_ELIMIT;
-    }
-  return FUELMI_OK;
-}
-
-// the yaw trajectories of the batch's optimised position splines (k_yaw_plan, yaw_plan.hip) read from the variables the
-// last solve left on the device; only the yaw results travel
-extern "C" int fuelmi_bspline_dev_plan_yaws(fuelmi_bspline_dev* b, const fuelmi_yaw_cfg* cfg, const double* start_yaw,
-                                            const double* end_yaw, int* status, double* duration, int* seg_num,
-                                            double* dt_yaw, double* yaw_ctrl, int* n_waypt, double* waypts,
-                                            double* end_yaw_out, double* cost, double* yawdot_ctrl,
-                                            double* yawddot_ctrl) {
-  ARGCHK(b && cfg);
-  const BsplineArgs& A = b->a;
-  ARGCHK(A.dim == 3 && b->opt_valid && b->opt_x);
-  ARGCHK(cfg->pos_degree == A.cfg.bspline_degree);
-  fuelmi_yaw_cfg yc = *cfg;
-  yc.max_ctrl = A.N;
-  {
-    const int rc = yaw_check(&A.cfg, &yc, A.C, nullptr, nullptr, nullptr, start_yaw, end_yaw);
-    if (rc) return rc;
-  }
-  ARGCHK(A.N >= yc.pos_degree + 1);
-  ARGCHK(status && duration && seg_num && dt_yaw && yaw_ctrl && n_waypt && waypts && end_yaw_out && cost);
-  fuelmi_map* m = b->map;
-  ARGCHK(m);
-  HIPCHK(hipSetDevice(m->device));
-  const size_t C = (size_t)A.C;
-  YawArgs Y;
-  memset(&Y, 0, sizeof(Y));
-  const size_t b_out = yaw_out_bytes(&yc, A.C, Y, nullptr, yawdot_ctrl != nullptr, yawddot_ctrl != nullptr);
-  double *d_start, *d_end;
-  unsigned char* d_out;
-  auto layout = [&](unsigned char* base) {
-    BlockLayout L(base, 16);
-    d_start = L.take<double>(C * 3);
-    d_end = L.take<double>(C);
-    d_out = L.take<unsigned char>(b_out);
-    return L.size();
-  };
-  hipStream_t st = m->stream;
-  {
-    const int rc = b->yaw_dev.reserve(st, layout(nullptr));
-    if (rc) return rc;
-  }
-  layout(b->yaw_dev.base());
-  HIPCHK(hipMemcpyAsync(d_start, start_yaw, C * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-  if (end_yaw)
-    HIPCHK(hipMemcpyAsync(d_end, end_yaw, C * sizeof(double), hipMemcpyHostToDevice, st));
-  else
-    HIPCHK(hipMemsetAsync(d_end, 0, C * sizeof(double), st));
-  Y.cfg = yc;
-  Y.ld_smooth = A.cfg.ld_smooth, Y.ld_start = A.cfg.ld_start, Y.ld_end = A.cfg.ld_end, Y.ld_waypt = A.cfg.ld_waypt;
-  Y.n_prob = A.C;
-  Y.src = opt_spline_src(b);
-  Y.start_yaw = d_start, Y.end_yaw = d_end;
-  yaw_out_bytes(&yc, A.C, Y, d_out, yawdot_ctrl != nullptr, yawddot_ctrl != nullptr);
-  {
-    StageScope sc(m, FUELMI_K_BSPLINE);
-    const int rc = yaw_launch(st, Y);
-    if (rc) return rc;
-  }
-  std::vector<unsigned char> host(b_out);
-  HIPCHK(hipMemcpyAsync(host.data(), d_out, b_out, hipMemcpyDeviceToHost, st));
-  HIPCHK(stream_wait(st));
-  YawArgs H = Y;
-  yaw_out_bytes(&yc, A.C, H, host.data(), yawdot_ctrl != nullptr, yawddot_ctrl != nullptr);
-  return yaw_copy_out(&yc, A.C, H, status, duration, seg_num, dt_yaw, yaw_ctrl, n_waypt, waypts, end_yaw_out, cost,
-                      yawdot_ctrl, yawddot_ctrl);
-}
-
-// the safety check of the batch's optimised position splines (k_traj_check, traj_check.hip) read from the variables the
-// last solve left on the device, against the batch's map; only the results travel
-extern "C" int fuelmi_bspline_dev_check_trajs(fuelmi_bspline_dev* b, const fuelmi_trajchk_cfg* cfg, const double* t_now,
-                                              int* status, int* safe, double* distance, int* n_samples, int* hit_index,
-                                              double* hit_t, double* hit_pos, int* end_reason, double* duration) {
-  ARGCHK(b && cfg);
-  const BsplineArgs& A = b->a;
-  ARGCHK(A.dim == 3 && b->opt_valid && b->opt_x);
-  ARGCHK(cfg->degree == A.cfg.bspline_degree);
-  fuelmi_trajchk_cfg tc = *cfg;
-  tc.max_ctrl = A.N;
-  {
-    const int rc = trajchk_check(&tc, A.C, nullptr, nullptr, nullptr, t_now);
-    if (rc) return rc;
-  }
-  ARGCHK(status && safe && distance && n_samples && hit_index && hit_t && hit_pos && end_reason && duration);
-  fuelmi_map* m = b->map;
-  ARGCHK(m);
-  HIPCHK(hipSetDevice(m->device));
-  const size_t C = (size_t)A.C;
-  TrajChkArgs T;
-  memset(&T, 0, sizeof(T));
-  const size_t b_out = trajchk_out_bytes(A.C, T, nullptr);
-  double* d_now;
-  unsigned char* d_out;
-  auto layout = [&](unsigned char* base) {
-    BlockLayout L(base, 16);
-    d_now = L.take<double>(C);
-    d_out = L.take<unsigned char>(b_out);
-    return L.size();
-  };
-  hipStream_t st = m->stream;
-  {
-    const int rc = b->chk_dev.reserve(st, layout(nullptr));
-    if (rc) return rc;
-  }
-  layout(b->chk_dev.base());
-  HIPCHK(hipMemcpyAsync(d_now, t_now, C * sizeof(double), hipMemcpyHostToDevice, st));
-  T.cfg = tc;
-  T.n_prob = A.C;
-  T.src = opt_spline_src(b);
-  T.t_now = d_now;
-  T.infl = m->infl_bits.p;
-  trajchk_out_bytes(A.C, T, d_out);
-  {
-    const int rc = trajchk_launch(st, m->g, T);
-    if (rc) return rc;
-  }
-  std::vector<unsigned char> host(b_out);
-  HIPCHK(hipMemcpyAsync(host.data(), d_out, b_out, hipMemcpyDeviceToHost, st));
-  HIPCHK(stream_wait(st));
-  TrajChkArgs H = T;
-  trajchk_out_bytes(A.C, H, host.data());
-  return trajchk_copy_out(A.C, H, status, safe, distance, n_samples, hit_index, hit_t, hit_pos, end_reason, duration);
-}
-
-// the batch's optimised position splines sampled as commands or replan states (k_traj_sample, traj_sample.hip), read from
-// the variables the last solve left on the device; the yaw splines and the times come from the host, only results travel
-extern "C" int fuelmi_bspline_dev_sample_trajs(fuelmi_bspline_dev* b, const fuelmi_trajsmp_cfg* cfg, const int* n_yaw_ctrl,
-                                               const double* yaw_ctrl, const double* yaw_dt, const double* t_stop,
-                                               const int* n_t, const double* t, int* status, double* pos, double* vel,
-                                               double* acc, double* jerk, double* yaw, double* yawdot, double* yawddot,
-                                               double* duration, double* flight) {
-  ARGCHK(b && cfg);
-  const BsplineArgs& A = b->a;
-  ARGCHK(A.dim == 3 && b->opt_valid && b->opt_x);
-  ARGCHK(cfg->degree == A.cfg.bspline_degree);
-  fuelmi_trajsmp_cfg sc = *cfg;
-  sc.max_ctrl = A.N;
-  const TrajSmpIO io = {nullptr, nullptr, nullptr, n_yaw_ctrl, yaw_ctrl, yaw_dt, t_stop, n_t,      t,     status,
-                        pos,     vel,     acc,     jerk,       yaw,      yawdot, yawddot, duration, flight};
-  bool nothing = true;
-  {
-    const int rc = trajsmp_check(&sc, A.C, false, io, &nothing);
-    if (rc) return rc;
-  }
-  if (nothing) return FUELMI_OK;
-  fuelmi_map* m = b->map;
-  ARGCHK(m);
-  HIPCHK(hipSetDevice(m->device));
-  {
-    const int rc = b->smp_dev.reserve(m->stream, trajsmp_bytes(&sc, A.C, false, io));
-    if (rc) return rc;
-  }
-  TrajSmpArgs T;
-  memset(&T, 0, sizeof(T));
-  T.src = opt_spline_src(b);
-  return trajsmp_run(m->stream, &sc, A.C, false, io, T, b->smp_dev.base());
 }

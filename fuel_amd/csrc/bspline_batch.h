@@ -1,0 +1,71 @@
+// bspline_batch.h -- what bspline.hip shows the planner stages that have a fuelmi_bspline_dev_* entry: the device batch's
+// state, the fit's argument record and three glue functions (all defined in bspline.hip, which shows nothing else).
+#ifndef FUELMI_BSPLINE_BATCH_H_
+#define FUELMI_BSPLINE_BATCH_H_
+
+#include "fuelmi_internal.h"
+
+struct BsplineArgs {
+  fuelmi_bspline_cfg cfg;
+  int cost_function, dim, N, C, end_n, n_waypt, nvar, order, n_guide;
+  const double* x;
+  const double* pt_dist;
+  const double* knot_span;
+  const double* time_lb;
+  const double* start_state;
+  const double* end_state;
+  const double* guide_pts;
+  const double* waypoints;
+  const int* waypt_idx;
+  const double* view_pt;
+  const double* view_dir;
+  const int* view_idx;
+  double* cost;
+  double* grad;
+};
+
+struct fuelmi_bspline_dev {
+  fuelmi_map* map;  // cleared if the map is destroyed first (then only _destroy is legal)
+  int device = 0;
+  BsplineArgs a;
+  std::vector<void*> allocs;
+  size_t lds;       // evaluation scratch of one wave (the solves build on it)
+  size_t lds_eval4; // ... plus the partial gradients / costs of the four-wave cost kernel
+  double *opt_x = nullptr, *opt_cost = nullptr;  // fuelmi_bspline_dev_optimize outputs
+  int* opt_evals = nullptr;
+  // fuelmi_bspline_dev_eval_pinned: two pinned result slots (cost [C] | grad [C][nvar]) the cost kernel writes
+  // directly, and the event behind each launch
+  double* pin_out[2] = {nullptr, nullptr};
+  hipEvent_t ev_out[2] = {nullptr, nullptr};
+  bool opt_valid = false;    // opt_x holds the solve of what the batch holds now (a reload clears it)
+  // per-call scratch, reserved on the map's stream (every kernel that reads it runs there); no pointer into it
+  // outlives the call that carved it
+  DevScratch fit_in;   // fuelmi_bspline_dev_load_*: ts | points | derivs, then the loader's own arrays
+  DevScratch yaw_dev;  // fuelmi_bspline_dev_plan_yaws: start | end | results
+  DevScratch chk_dev;  // fuelmi_bspline_dev_check_trajs: t_now | results
+  DevScratch smp_dev;  // fuelmi_bspline_dev_sample_trajs: yaw splines, times | results
+};
+
+struct FitArgs {
+  int C, K, degree;
+  const double* ts;      // [C]
+  const double* points;  // [C][K][3]
+  const double* derivs;  // [C][4][3]  start vel, end vel, start acc, end acc
+  double* ctrl;          // candidate c: ctrl + c * stride, (K + degree - 1) rows of 3
+  long stride;
+  // planner glue (all optional): what setBoundaryStates / optimize() derive from the fitted spline
+  int write_dt;          // ctrl[c * stride + 3 n] = ts[c]   (trailing knot-span variable)
+  double* knot_span;     // [C]
+  double* pt_dist;       // [C]      optimize() :136-140
+  double* start_state;   // [C][3][3]  getBoundaryStates(2, 0).start
+  double* end_state;     // [C][3][3]  row 0 = getBoundaryStates(2, 0).end[0]
+  const int* skip;       // [C] or null: a candidate with skip[c] != 0 is left as it is
+};
+
+// the fit of device samples into the batch's own state; its launch (st null: the map's stream); the position splines
+// the last solve left on the device
+FitArgs fit_args(const fuelmi_bspline_dev* b, double* ts, double* points, double* derivs, int* skip);
+int fit_launch(fuelmi_map* m, const FitArgs& F, hipStream_t st = nullptr);
+SplineSrc opt_spline_src(const fuelmi_bspline_dev* b);
+
+#endif

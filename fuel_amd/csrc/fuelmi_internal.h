@@ -216,7 +216,7 @@ struct fuelmi_map {
   std::vector<LateReader> late_readers;
   // The batched planner calls' device scratch: one grow-only pool per call (DevScratch), carved per call (BlockLayout).
   // The pools stay separate because one call's results outlive another call: goal_path.hip reads what path_cost_enqueue
-  // left in path_dev, and kino_prepare hands a part of kino_dev to a B-spline batch.
+  // left in path_dev, and kino_path.hip hands a part of kino_dev to a B-spline batch.
   DevScratch path_dev;     // fuelmi_map_path_costs (path_cost.hip)
   DevScratch refine_dev;   // fuelmi_map_refine_tours (refine.hip): problems in, choices / costs out
   DevScratch goal_dev;     // fuelmi_map_goal_paths (goal_path.hip): results out
@@ -531,10 +531,6 @@ struct WpTrajArgs {
   double* seg_times;   // [n][maxw-1] or null
   double* coef;        // [n][maxw-1][3][6] or null
 };
-// the host checks of fuelmi_map_waypoint_trajs / fuelmi_bspline_dev_load_waypoints; the launch on stream st
-int wptraj_check(const fuelmi_wptraj_cfg* cfg, int n_prob, const int* n_way, const double* way_xyz,
-                 const double* vel_xyz, const double* acc_xyz);
-int wptraj_launch(hipStream_t st, const WpTrajArgs& W);
 // the position splines of a batch of problems, as k_yaw_plan, k_traj_check and k_traj_sample read them
 struct SplineSrc {
   const int* n_ctrl;        // [n], or null: every problem has n_ctrl_all control points
@@ -564,16 +560,6 @@ struct YawArgs {
   double* yawdot_ctrl;      // [n][max_seg + 2] or null
   double* yawddot_ctrl;     // [n][max_seg + 1] or null
 };
-// the host checks of fuelmi_map_plan_yaws / fuelmi_bspline_dev_plan_yaws (n_ctrl null: a device batch, whose control
-// points and knot spans the host does not see); the result block's layout (a BlockLayout; base null: only its size); the
-// launch on stream st; the result block -> the caller's arrays (FUELMI_ELIMIT when a problem's status is -1)
-int yaw_check(const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob, const int* n_ctrl,
-              const double* pos_ctrl, const double* knot_span, const double* start_yaw, const double* end_yaw);
-size_t yaw_out_bytes(const fuelmi_yaw_cfg* cfg, int n_prob, YawArgs& Y, unsigned char* base, bool dot, bool ddot);
-int yaw_launch(hipStream_t st, const YawArgs& Y);
-int yaw_copy_out(const fuelmi_yaw_cfg* cfg, int n_prob, const YawArgs& H, int* status, double* duration, int* seg_num,
-                 double* dt_yaw, double* yaw_ctrl, int* n_waypt, double* waypts, double* end_yaw_out, double* cost,
-                 double* yawdot_ctrl, double* yawddot_ctrl);
 // k_traj_check (traj_check.hip): one problem per wave; every pointer addresses device memory
 struct TrajChkArgs {
   fuelmi_trajchk_cfg cfg;
@@ -591,15 +577,6 @@ struct TrajChkArgs {
   double* duration;
   double* hit_pos;          // [n][3]
 };
-// the host checks of fuelmi_map_check_trajs / fuelmi_bspline_dev_check_trajs (n_ctrl null: a device batch, whose control
-// points and knot spans the host does not see); the result block's layout (base null: only its size); the launch on
-// stream st; the result block -> the caller's arrays (FUELMI_ELIMIT when a problem's status is -1)
-int trajchk_check(const fuelmi_trajchk_cfg* cfg, int n_prob, const int* n_ctrl, const double* pos_ctrl,
-                  const double* knot_span, const double* t_now);
-size_t trajchk_out_bytes(int n_prob, TrajChkArgs& T, unsigned char* base);
-int trajchk_launch(hipStream_t st, const Geo& g, const TrajChkArgs& T);
-int trajchk_copy_out(int n_prob, const TrajChkArgs& H, int* status, int* safe, double* distance, int* n_samples,
-                     int* hit_index, double* hit_t, double* hit_pos, int* end_reason, double* duration);
 // k_traj_sample (traj_sample.hip): one problem per wave; every pointer addresses device memory
 struct TrajSmpArgs {
   fuelmi_trajsmp_cfg cfg;
@@ -617,25 +594,6 @@ struct TrajSmpArgs {
   double *o_yaw, *o_yawdot, *o_yawddot;    // [n][max_t]
   double* duration;         // [n]
 };
-// the caller's host arrays of fuelmi_map_sample_trajs / fuelmi_bspline_dev_sample_trajs (the first three null for a
-// device batch)
-struct TrajSmpIO {
-  const int* n_ctrl;
-  const double *pos_ctrl, *knot_span;
-  const int* n_yaw_ctrl;
-  const double *yaw_ctrl, *yaw_dt, *t_stop;
-  const int* n_t;
-  const double* t;
-  int* status;
-  double *pos, *vel, *acc, *jerk, *yaw, *yawdot, *yawddot, *duration, *flight;
-};
-// the host checks of both calls (*nothing: no problem or no sample, the call returns FUELMI_OK at once); the bytes of
-// the scratch block; uploads, the launch on stream st, the results into the caller's arrays and the wait.  A device
-// batch presets A's n_ctrl .. knot_stride.
-int trajsmp_check(const fuelmi_trajsmp_cfg* cfg, int n_prob, bool host_spline, const TrajSmpIO& io, bool* nothing);
-size_t trajsmp_bytes(const fuelmi_trajsmp_cfg* cfg, int n_prob, bool host_spline, const TrajSmpIO& io);
-int trajsmp_run(hipStream_t st, const fuelmi_trajsmp_cfg* cfg, int n_prob, bool host_spline, const TrajSmpIO& io,
-                TrajSmpArgs& A, unsigned char* scratch);
 void map_cloud_release(fuelmi_map* m);   // the cloud call's pinned word and events (map_cloud.hip)
 // k_kino_path (kino_path.hip): one problem per workgroup; every pointer addresses device memory
 struct KinoArgs {
@@ -673,18 +631,6 @@ struct KinoArgs {
   double* node_input;       // [n][max_path_nodes][3] or null
   double* node_duration;    // [n][max_path_nodes] or null
 };
-// the host checks shared by fuelmi_map_kino_paths / fuelmi_bspline_dev_load_kino; the primitive lists
-// ([n_init + n_reg][4]); bytes of one problem's workspace and its hash slots; the launch on the map's stream
-int kino_check(const fuelmi_kino_cfg* cfg, int n_prob, const double* start_xyz, const double* start_vel,
-               const double* start_acc, const double* goal_xyz, const double* goal_vel);
-int kino_prims(const fuelmi_kino_cfg* cfg, std::vector<double>& prims, int& n_init, int& n_reg);
-size_t kino_workspace(const fuelmi_kino_cfg* cfg, int* hash_cap);
-// fills geometry / lists / workspace pointers of K from the map's kino_dev pool (reserved for io_bytes + the workspaces), uploads
-// the inputs and the lists, clears the hashes; *io is the start of io_bytes of device memory for the caller's results
-int kino_prepare(fuelmi_map* m, const fuelmi_kino_cfg* cfg, int n_prob, const double* start_xyz, const double* start_vel,
-                 const double* start_acc, const double* goal_xyz, const double* goal_vel, size_t io_bytes, KinoArgs& K,
-                 unsigned char** io);
-int kino_launch(fuelmi_map* m, const KinoArgs& K);
 // device results of one path_cost_enqueue, in the map's path pool (path_dev): length / kind / path_len per pair, paths
 // [n][maxp][3] (nullptr when maxp is 0), and the device copy of p2_xyz
 struct PathRun {

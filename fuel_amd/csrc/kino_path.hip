@@ -24,11 +24,14 @@
 //
 // All f64, -ffp-contract=off, no scratch (no dynamically indexed private arrays).  LDS: the lanes' results of one
 // expansion (fuelmi_kino_plan reports the bytes).
+// Behind the kernel, the two entries that share its lists, checks, workspace and launch: fuelmi_map_kino_paths (all to
+// the host) and fuelmi_bspline_dev_load_kino (samples straight into a device batch's fit, bspline_batch.h).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
+#include "bspline_batch.h"
 #include "frontier_internal.h"
 
 namespace {
@@ -540,8 +543,6 @@ __global__ void __launch_bounds__(KN_NT) k_kino_path(Geo g, KinoArgs K) {
 
 bool pos_fin(double x) { return std::isfinite(x) && x > 0.0; }
 
-}  // namespace
-
 // the reference's accumulating loops (:107-122), literally
 int kino_prims(const fuelmi_kino_cfg* cfg, std::vector<double>& prims, int& n_init, int& n_reg) {
   prims.clear();
@@ -583,7 +584,7 @@ size_t kino_workspace(const fuelmi_kino_cfg* cfg, int* hash_cap) {
   return (size_t)cfg->allocate_num * (sizeof(KNode) + sizeof(int)) + (size_t)cap * sizeof(int);
 }
 
-static int kino_check_cfg(const fuelmi_kino_cfg* cfg) {
+int kino_check_cfg(const fuelmi_kino_cfg* cfg) {
   ARGCHK(cfg);
   ARGCHK(pos_fin(cfg->max_tau) && pos_fin(cfg->init_max_tau) && pos_fin(cfg->max_vel) && pos_fin(cfg->max_acc));
   ARGCHK(pos_fin(cfg->w_time) && pos_fin(cfg->horizon) && pos_fin(cfg->resolution) && pos_fin(cfg->lambda_heu));
@@ -623,6 +624,8 @@ int kino_check(const fuelmi_kino_cfg* cfg, int n_prob, const double* start_xyz, 
   return FUELMI_OK;
 }
 
+// fills geometry / lists / workspace pointers of K from the map's kino_dev pool (reserved for io_bytes + the workspaces),
+// uploads the inputs and the lists, clears the hashes; *io is the start of io_bytes of device memory for the caller's results
 int kino_prepare(fuelmi_map* m, const fuelmi_kino_cfg* cfg, int n_prob, const double* start_xyz, const double* start_vel,
                  const double* start_acc, const double* goal_xyz, const double* goal_vel, size_t io_bytes, KinoArgs& K,
                  unsigned char** io) {
@@ -686,6 +689,8 @@ int kino_launch(fuelmi_map* m, const KinoArgs& K) {
   HIPCHK(hipGetLastError());
   return FUELMI_OK;
 }
+
+}  // namespace
 
 extern "C" int fuelmi_kino_plan(const fuelmi_kino_cfg* cfg, long long out8[8]) {
   ARGCHK(out8);
@@ -777,6 +782,80 @@ extern "C" int fuelmi_map_kino_paths(fuelmi_map* m, const fuelmi_kino_cfg* cfg, 
     if (status[b] == -1) {
       fuelmi_set_error("kinodynamic search: problem %d has %d path nodes / %d samples, more than max_path_nodes = %d / "
                        "max_samples = %d", b, n_nodes[b], n_samples[b], cfg->max_path_nodes, cfg->max_samples);
+      return FUELMI_ELIMIT;
+    }
+  return FUELMI_OK;
+}
+
+// start / goal -> kinodynamic search -> getSamples (k_kino_path, written into the staging) -> the fit, all on the map's
+// stream: the mid-range counterpart of fuelmi_bspline_dev_load_waypoints (waypoint_traj.hip)
+extern "C" int fuelmi_bspline_dev_load_kino(fuelmi_bspline_dev* b, const fuelmi_kino_cfg* cfg, const double* start_xyz,
+                                            const double* start_vel, const double* start_acc, const double* goal_xyz,
+                                            const double* goal_vel, int* status, double* T_sum) {
+  ARGCHK(b && cfg && status);
+  BsplineArgs& A = b->a;
+  const int degree = A.cfg.bspline_degree;
+  ARGCHK(A.dim == 3 && degree >= 3 && degree <= 5 && A.N - degree >= 1);
+  const int seg = A.N - degree, n_points = seg + 1;
+  ARGCHK(cfg->seg_num == 0 || cfg->seg_num == seg);
+  fuelmi_kino_cfg kc = *cfg;
+  kc.seg_num = seg, kc.max_samples = n_points, kc.max_path_nodes = 1;
+  {
+    const int rc = kino_check(&kc, A.C, start_xyz, start_vel, start_acc, goal_xyz, goal_vel);
+    if (rc) return rc;
+  }
+  fuelmi_map* m = b->map;
+  ARGCHK(m);
+  b->opt_valid = false;
+  HIPCHK(hipSetDevice(m->device));
+  const size_t C = (size_t)A.C, K = (size_t)n_points;
+  hipStream_t st = m->stream;
+  {
+    const int rc = b->fit_in.reserve(st, C * (1 + K * 3 + 12) * sizeof(double));
+    if (rc) return rc;
+  }
+  double* d_fit = static_cast<double*>(b->fit_in.p);  // ts | points | derivs
+  KinoArgs W;
+  auto layout = [&](unsigned char* base) {  // the results that do not go to the fit
+    BlockLayout L(base, 16);
+    W.status = L.take<int>(C);
+    W.which = L.take<int>(C);
+    W.iter_num = L.take<int>(C);
+    W.use_node_num = L.take<int>(C);
+    W.n_nodes = L.take<int>(C);
+    W.shot = L.take<int>(C);
+    W.seg_num = L.take<int>(C);
+    W.n_samples = L.take<int>(C);
+    W.skip = L.take<int>(C);
+    W.t_shot = L.take<double>(C);
+    W.T_sum = L.take<double>(C);
+    W.coef_shot = L.take<double>(C * 12);
+    return L.size();
+  };
+  unsigned char* io = nullptr;
+  {
+    const int rc = kino_prepare(m, &kc, A.C, start_xyz, start_vel, start_acc, goal_xyz, goal_vel, layout(nullptr), W, &io);
+    if (rc) return rc;
+  }
+  layout(io);
+  W.load_points = n_points;
+  W.ts_out = d_fit;  // the fit's knot spans
+  W.samples = d_fit + C;
+  W.derivs = d_fit + C + C * K * 3;
+  const FitArgs F = fit_args(b, W.ts_out, W.samples, W.derivs, W.skip);
+  {
+    const int rck = kino_launch(m, W);  // (outside the scope: the search is no spline stage)
+    if (rck) return rck;
+    StageScope sc(m, FUELMI_K_BSPLINE);
+    const int rcf = fit_launch(m, F);
+    if (rcf) return rcf;
+  }
+  HIPCHK(hipMemcpyAsync(status, W.status, C * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (T_sum) HIPCHK(hipMemcpyAsync(T_sum, W.T_sum, C * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(stream_wait(st));
+  for (int c = 0; c < A.C; ++c)
+    if (status[c] == -1) {
+      fuelmi_set_error("kinodynamic search: candidate %d does not give %d samples", c, n_points);
       return FUELMI_ELIMIT;
     }
   return FUELMI_OK;

@@ -15,10 +15,13 @@
 // through L2: a window touches p + 1 neighbouring points per lane, 24 B each, and neighbouring lanes share them, so
 // staging up to 24 KiB per problem would cost more than it saves.  All f64, -ffp-contract=off.  A result does not depend
 // on the problem's place in the batch: the only workgroup-wide step is the barrier behind the knots.
+// Behind the kernel, the two entries that share its checks, layout and trajchk_run: fuelmi_map_check_trajs (splines from
+// the host) and fuelmi_bspline_dev_check_trajs (the splines a device batch's last solve left, bspline_batch.h).
 #include <cmath>
 #include <cstring>
 #include <vector>
 
+#include "bspline_batch.h"
 #include "frontier_internal.h"
 #include "spline_internal.h"
 
@@ -161,29 +164,38 @@ int trajchk_cfg_check(const fuelmi_trajchk_cfg* cfg) {
   return FUELMI_OK;
 }
 
-}  // namespace
+// the caller's host arrays of both entries (the first three null for a device batch: the host does not see its splines)
+struct TrajChkIO {
+  const int* n_ctrl;
+  const double *pos_ctrl, *knot_span, *t_now;
+  int *status, *safe, *n_samples, *hit_index, *end_reason;
+  double *distance, *hit_t, *hit_pos, *duration;
+};
 
-int trajchk_check(const fuelmi_trajchk_cfg* cfg, int n_prob, const int* n_ctrl, const double* pos_ctrl,
-                  const double* knot_span, const double* t_now) {
+int trajchk_check(const fuelmi_trajchk_cfg* cfg, int n_prob, const TrajChkIO& io) {
   {
     const int rc = trajchk_cfg_check(cfg);
     if (rc) return rc;
   }
   ARGCHK(n_prob >= 0);
   if (n_prob == 0) return FUELMI_OK;
-  ARGCHK(t_now);
-  for (int b = 0; b < n_prob; ++b) ARGCHK(std::isfinite(t_now[b]));
-  if (!n_ctrl) return FUELMI_OK;  // a device batch: its variables are checked by the kernel
-  ARGCHK(pos_ctrl && knot_span);
-  for (int b = 0; b < n_prob; ++b) {
-    ARGCHK(n_ctrl[b] >= cfg->degree + 1 && n_ctrl[b] <= cfg->max_ctrl);
-    ARGCHK(std::isfinite(knot_span[b]) && knot_span[b] > 0.0);
-    const double* P = pos_ctrl + (size_t)b * cfg->max_ctrl * 3;
-    for (int k = 0; k < 3 * n_ctrl[b]; ++k) ARGCHK(std::fabs(P[k]) < 1e7);
+  ARGCHK(io.t_now);
+  for (int b = 0; b < n_prob; ++b) ARGCHK(std::isfinite(io.t_now[b]));
+  if (io.n_ctrl) {  // (a device batch: its variables are checked by the kernel)
+    ARGCHK(io.pos_ctrl && io.knot_span);
+    for (int b = 0; b < n_prob; ++b) {
+      ARGCHK(io.n_ctrl[b] >= cfg->degree + 1 && io.n_ctrl[b] <= cfg->max_ctrl);
+      ARGCHK(std::isfinite(io.knot_span[b]) && io.knot_span[b] > 0.0);
+      const double* P = io.pos_ctrl + (size_t)b * cfg->max_ctrl * 3;
+      for (int k = 0; k < 3 * io.n_ctrl[b]; ++k) ARGCHK(std::fabs(P[k]) < 1e7);
+    }
   }
+  ARGCHK(io.status && io.safe && io.distance && io.n_samples && io.hit_index && io.hit_t && io.hit_pos && io.end_reason &&
+         io.duration);
   return FUELMI_OK;
 }
 
+// the result block's layout (base null: only its size)
 size_t trajchk_out_bytes(int n_prob, TrajChkArgs& T, unsigned char* base) {
   const size_t n = (size_t)n_prob;
   BlockLayout L(base, 16);
@@ -199,32 +211,40 @@ size_t trajchk_out_bytes(int n_prob, TrajChkArgs& T, unsigned char* base) {
   return L.size();
 }
 
-int trajchk_copy_out(int n_prob, const TrajChkArgs& H, int* status, int* safe, double* distance, int* n_samples,
-                     int* hit_index, double* hit_t, double* hit_pos, int* end_reason, double* duration) {
+// both entries behind their uploads (T holds cfg, n_prob, src, t_now), on the map's stream: results carved at d_out, launch,
+// download, wait, the results into the caller's arrays (FUELMI_ELIMIT when a problem's status is -1)
+int trajchk_run(fuelmi_map* m, TrajChkArgs& T, unsigned char* d_out, const TrajChkIO& io) {
+  hipStream_t st = m->stream;
+  const int n_prob = T.n_prob;
   const size_t n = (size_t)n_prob;
-  memcpy(status, H.status, n * sizeof(int));
-  memcpy(safe, H.safe, n * sizeof(int));
-  memcpy(n_samples, H.n_samples, n * sizeof(int));
-  memcpy(hit_index, H.hit_index, n * sizeof(int));
-  memcpy(end_reason, H.end_reason, n * sizeof(int));
-  memcpy(distance, H.distance, n * sizeof(double));
-  memcpy(hit_t, H.hit_t, n * sizeof(double));
-  memcpy(duration, H.duration, n * sizeof(double));
-  memcpy(hit_pos, H.hit_pos, n * 3 * sizeof(double));
+  T.infl = m->infl_bits.p;
+  const size_t b_out = trajchk_out_bytes(n_prob, T, d_out);
+  const size_t lds = tc_lds(T.cfg.max_ctrl);  // <= 32.2 KiB at FUELMI_TRAJCHK_MAX_CTRL
+  hipLaunchKernelGGL(k_traj_check, dim3((n_prob + TC_WAVES - 1) / TC_WAVES), dim3(TC_WIN * TC_WAVES), lds, st, m->g, T);
+  HIPCHK(hipGetLastError());
+  std::vector<unsigned char> host(b_out);
+  HIPCHK(hipMemcpyAsync(host.data(), d_out, b_out, hipMemcpyDeviceToHost, st));
+  HIPCHK(stream_wait(st));
+  TrajChkArgs H = T;
+  trajchk_out_bytes(n_prob, H, host.data());
+  memcpy(io.status, H.status, n * sizeof(int));
+  memcpy(io.safe, H.safe, n * sizeof(int));
+  memcpy(io.n_samples, H.n_samples, n * sizeof(int));
+  memcpy(io.hit_index, H.hit_index, n * sizeof(int));
+  memcpy(io.end_reason, H.end_reason, n * sizeof(int));
+  memcpy(io.distance, H.distance, n * sizeof(double));
+  memcpy(io.hit_t, H.hit_t, n * sizeof(double));
+  memcpy(io.duration, H.duration, n * sizeof(double));
+  memcpy(io.hit_pos, H.hit_pos, n * 3 * sizeof(double));
   for (int b = 0; b < n_prob; ++b)
-    if (status[b] == -1) {
+    if (io.status[b] == -1) {
       fuelmi_set_error("trajectory check: problem %d needs more than %d samples", b, FUELMI_TRAJCHK_MAX_SAMPLES);
       return FUELMI_ELIMIT;
     }
   return FUELMI_OK;
 }
 
-int trajchk_launch(hipStream_t st, const Geo& g, const TrajChkArgs& T) {
-  const size_t lds = tc_lds(T.cfg.max_ctrl);  // <= 32.2 KiB at FUELMI_TRAJCHK_MAX_CTRL
-  hipLaunchKernelGGL(k_traj_check, dim3((T.n_prob + TC_WAVES - 1) / TC_WAVES), dim3(TC_WIN * TC_WAVES), lds, st, g, T);
-  HIPCHK(hipGetLastError());
-  return FUELMI_OK;
-}
+}  // namespace
 
 extern "C" int fuelmi_traj_check_plan(const fuelmi_trajchk_cfg* cfg, int out3[3]) {
   ARGCHK(out3);
@@ -240,13 +260,14 @@ extern "C" int fuelmi_map_check_trajs(fuelmi_map* m, const fuelmi_trajchk_cfg* c
                                       const double* pos_ctrl, const double* knot_span, const double* t_now, int* status,
                                       int* safe, double* distance, int* n_samples, int* hit_index, double* hit_t,
                                       double* hit_pos, int* end_reason, double* duration) {
+  const TrajChkIO io = {n_ctrl,    pos_ctrl,   knot_span, t_now, status,  safe,    n_samples,
+                        hit_index, end_reason, distance,  hit_t, hit_pos, duration};
   {  // every argument on the host, before the map is touched
     ARGCHK(n_prob <= 0 || n_ctrl);
-    const int rc = trajchk_check(cfg, n_prob, n_ctrl, pos_ctrl, knot_span, t_now);
+    const int rc = trajchk_check(cfg, n_prob, io);
     if (rc) return rc;
   }
   if (n_prob == 0) return FUELMI_OK;
-  ARGCHK(status && safe && distance && n_samples && hit_index && hit_t && hit_pos && end_reason && duration);
   ARGCHK(m);
   HIPCHK(hipSetDevice(m->device));
   hipStream_t st = m->stream;
@@ -279,16 +300,51 @@ extern "C" int fuelmi_map_check_trajs(fuelmi_map* m, const fuelmi_trajchk_cfg* c
   T.n_prob = n_prob;
   T.src = {d_nc, 0, d_pos, maxc * 3, d_knot, 1};
   T.t_now = d_now;
-  T.infl = m->infl_bits.p;
-  trajchk_out_bytes(n_prob, T, d_out);
+  return trajchk_run(m, T, d_out, io);
+}
+
+// the safety check of a device batch's optimised position splines, read from the variables the last solve left on the
+// device, against the batch's map; only the results travel
+extern "C" int fuelmi_bspline_dev_check_trajs(fuelmi_bspline_dev* b, const fuelmi_trajchk_cfg* cfg, const double* t_now,
+                                              int* status, int* safe, double* distance, int* n_samples, int* hit_index,
+                                              double* hit_t, double* hit_pos, int* end_reason, double* duration) {
+  ARGCHK(b && cfg);
+  const BsplineArgs& A = b->a;
+  ARGCHK(A.dim == 3 && b->opt_valid && b->opt_x);
+  ARGCHK(cfg->degree == A.cfg.bspline_degree);
+  fuelmi_trajchk_cfg tc = *cfg;
+  tc.max_ctrl = A.N;
+  const TrajChkIO io = {nullptr,   nullptr,    nullptr,  t_now, status,  safe,    n_samples,
+                        hit_index, end_reason, distance, hit_t, hit_pos, duration};
   {
-    const int rc = trajchk_launch(st, m->g, T);
+    const int rc = trajchk_check(&tc, A.C, io);
     if (rc) return rc;
   }
-  std::vector<unsigned char> host(b_out);
-  HIPCHK(hipMemcpyAsync(host.data(), d_out, b_out, hipMemcpyDeviceToHost, st));
-  HIPCHK(stream_wait(st));
-  TrajChkArgs H = T;
-  trajchk_out_bytes(n_prob, H, host.data());
-  return trajchk_copy_out(n_prob, H, status, safe, distance, n_samples, hit_index, hit_t, hit_pos, end_reason, duration);
+  fuelmi_map* m = b->map;
+  ARGCHK(m);
+  HIPCHK(hipSetDevice(m->device));
+  const size_t C = (size_t)A.C;
+  TrajChkArgs T;
+  memset(&T, 0, sizeof(T));
+  const size_t b_out = trajchk_out_bytes(A.C, T, nullptr);
+  double* d_now;
+  unsigned char* d_out;
+  auto layout = [&](unsigned char* base) {
+    BlockLayout L(base, 16);
+    d_now = L.take<double>(C);
+    d_out = L.take<unsigned char>(b_out);
+    return L.size();
+  };
+  hipStream_t st = m->stream;
+  {
+    const int rc = b->chk_dev.reserve(st, layout(nullptr));
+    if (rc) return rc;
+  }
+  layout(b->chk_dev.base());
+  HIPCHK(hipMemcpyAsync(d_now, t_now, C * sizeof(double), hipMemcpyHostToDevice, st));
+  T.cfg = tc;
+  T.n_prob = A.C;
+  T.src = opt_spline_src(b);
+  T.t_now = d_now;
+  return trajchk_run(m, T, d_out, io);
 }

@@ -14,11 +14,13 @@
 // order by lane reads, each lane making the same additions, and lane 0 stores the record at the end: the sums are the
 // reference's, term by term.  All f64, -ffp-contract=off.  A result does not depend on the problem's place in the
 // batch: the only workgroup-wide step is the barrier behind the knots.
+// Behind the kernel, the two entries that share its checks, layout and trajsmp_run: fuelmi_map_sample_trajs (splines from
+// the host) and fuelmi_bspline_dev_sample_trajs (the splines a device batch's last solve left, bspline_batch.h).
 #include <cmath>
 #include <cstring>
 #include <vector>
 
-#include "fuelmi_internal.h"
+#include "bspline_batch.h"
 #include "spline_internal.h"
 
 namespace {
@@ -235,6 +237,18 @@ int trajsmp_cfg_check(const fuelmi_trajsmp_cfg* cfg) {
   return FUELMI_OK;
 }
 
+// the caller's host arrays of both entries (the first three null for a device batch)
+struct TrajSmpIO {
+  const int* n_ctrl;
+  const double *pos_ctrl, *knot_span;
+  const int* n_yaw_ctrl;
+  const double *yaw_ctrl, *yaw_dt, *t_stop;
+  const int* n_t;
+  const double* t;
+  int* status;
+  double *pos, *vel, *acc, *jerk, *yaw, *yawdot, *yawddot, *duration, *flight;
+};
+
 // the scratch block (a BlockLayout over the map's or the batch's DevScratch): the inputs the host hands over, the
 // flight record (in and out), then the results.  base null: only the size.
 size_t ts_layout(const fuelmi_trajsmp_cfg& c, int n_prob, bool host_spline, const TrajSmpIO& io, TrajSmpArgs& A,
@@ -262,8 +276,9 @@ size_t ts_layout(const fuelmi_trajsmp_cfg& c, int n_prob, bool host_spline, cons
   return L.size();
 }
 
-}  // namespace
-
+// the host checks of both entries (*nothing: no problem or no sample, the call returns FUELMI_OK at once); the bytes of
+// the scratch block; uploads, the launch on stream st, the results into the caller's arrays and the wait.  A device
+// batch presets A's n_ctrl .. knot_stride.
 int trajsmp_check(const fuelmi_trajsmp_cfg* cfg, int n_prob, bool host_spline, const TrajSmpIO& io, bool* nothing) {
   {
     const int rc = trajsmp_cfg_check(cfg);
@@ -364,6 +379,8 @@ int trajsmp_run(hipStream_t st, const fuelmi_trajsmp_cfg* cfg, int n_prob, bool 
   return FUELMI_OK;
 }
 
+}  // namespace
+
 extern "C" int fuelmi_traj_sample_plan(const fuelmi_trajsmp_cfg* cfg, int out3[3]) {
   ARGCHK(out3);
   {
@@ -398,4 +415,38 @@ extern "C" int fuelmi_map_sample_trajs(fuelmi_map* m, const fuelmi_trajsmp_cfg* 
   TrajSmpArgs A;
   memset(&A, 0, sizeof(A));
   return trajsmp_run(st, cfg, n_prob, true, io, A, m->trajsmp_dev.base());
+}
+
+// the batch route: a device batch's optimised position splines sampled as commands or replan states, read from
+// the variables the last solve left on the device; the yaw splines and the times come from the host, only results travel
+extern "C" int fuelmi_bspline_dev_sample_trajs(fuelmi_bspline_dev* b, const fuelmi_trajsmp_cfg* cfg, const int* n_yaw_ctrl,
+                                               const double* yaw_ctrl, const double* yaw_dt, const double* t_stop,
+                                               const int* n_t, const double* t, int* status, double* pos, double* vel,
+                                               double* acc, double* jerk, double* yaw, double* yawdot, double* yawddot,
+                                               double* duration, double* flight) {
+  ARGCHK(b && cfg);
+  const BsplineArgs& A = b->a;
+  ARGCHK(A.dim == 3 && b->opt_valid && b->opt_x);
+  ARGCHK(cfg->degree == A.cfg.bspline_degree);
+  fuelmi_trajsmp_cfg sc = *cfg;
+  sc.max_ctrl = A.N;
+  const TrajSmpIO io = {nullptr, nullptr, nullptr, n_yaw_ctrl, yaw_ctrl, yaw_dt, t_stop, n_t,      t,     status,
+                        pos,     vel,     acc,     jerk,       yaw,      yawdot, yawddot, duration, flight};
+  bool nothing = true;
+  {
+    const int rc = trajsmp_check(&sc, A.C, false, io, &nothing);
+    if (rc) return rc;
+  }
+  if (nothing) return FUELMI_OK;
+  fuelmi_map* m = b->map;
+  ARGCHK(m);
+  HIPCHK(hipSetDevice(m->device));
+  {
+    const int rc = b->smp_dev.reserve(m->stream, trajsmp_bytes(&sc, A.C, false, io));
+    if (rc) return rc;
+  }
+  TrajSmpArgs T;
+  memset(&T, 0, sizeof(T));
+  T.src = opt_spline_src(b);
+  return trajsmp_run(m->stream, &sc, A.C, false, io, T, b->smp_dev.base());
 }

@@ -27,11 +27,13 @@
 //
 // One workgroup of WT_NT lanes per problem, all f64, -ffp-contract=off.  LDS: times, band, right-hand sides,
 // coefficients, one chunk of points, the reduction (fuelmi_wptraj_plan reports the bytes).
+// Behind the kernel, the two entries that share its checks and launch: fuelmi_map_waypoint_trajs (through a query slot)
+// and fuelmi_bspline_dev_load_waypoints (samples straight into a device batch's fit, bspline_batch.h).
 #include <cmath>
 #include <cstring>
 #include <vector>
 
-#include "fuelmi_internal.h"
+#include "bspline_batch.h"
 
 namespace {
 
@@ -309,8 +311,6 @@ size_t wt_lds(int maxw) {
   return (Smax + 4 * 2 * Smax + 3 * 2 * Smax + 18 * Smax + 3 * (WT_NT + 1) + WT_NT + 2) * sizeof(double);
 }
 
-}  // namespace
-
 int wptraj_check(const fuelmi_wptraj_cfg* cfg, int n_prob, const int* n_way, const double* way_xyz,
                  const double* vel_xyz, const double* acc_xyz) {
   ARGCHK(cfg);
@@ -353,6 +353,8 @@ int wptraj_launch(hipStream_t st, const WpTrajArgs& W) {
   HIPCHK(hipGetLastError());
   return FUELMI_OK;
 }
+
+}  // namespace
 
 extern "C" int fuelmi_wptraj_plan(const fuelmi_wptraj_cfg* cfg, int out3[3]) {
   ARGCHK(cfg && out3);
@@ -436,6 +438,84 @@ extern "C" int fuelmi_map_waypoint_trajs(fuelmi_map* m, const fuelmi_wptraj_cfg*
     if (status[b] == -1) {
       fuelmi_set_error("waypoint trajectories: problem %d has %d samples, more than max_samples = %d", b, n_samples[b],
                        cfg->max_samples);
+      return FUELMI_ELIMIT;
+    }
+  return FUELMI_OK;
+}
+
+// the batch route: way-points -> min-jerk samples (k_waypoint_traj, written into the batch's staging) -> the fit
+// (k_bspline_fit, bspline.hip), all on the map's stream
+extern "C" int fuelmi_bspline_dev_load_waypoints(fuelmi_bspline_dev* b, const fuelmi_wptraj_cfg* cfg, const int* n_way,
+                                                 const double* way_xyz, const double* vel_xyz, const double* acc_xyz,
+                                                 int* status, double* duration) {
+  ARGCHK(b && cfg && status);
+  BsplineArgs& A = b->a;
+  const int degree = A.cfg.bspline_degree;
+  ARGCHK(A.dim == 3 && degree >= 3 && degree <= 5 && A.N - degree >= 1);
+  const int seg = A.N - degree, n_points = seg + 1;
+  ARGCHK(cfg->seg_num == 0 || cfg->seg_num == seg);
+  fuelmi_wptraj_cfg wc = *cfg;
+  wc.seg_num = seg, wc.max_samples = n_points;
+  {
+    const int rc = wptraj_check(&wc, A.C, n_way, way_xyz, vel_xyz, acc_xyz);
+    if (rc) return rc;
+  }
+  fuelmi_map* m = b->map;
+  ARGCHK(m);
+  b->opt_valid = false;
+  HIPCHK(hipSetDevice(m->device));
+  const size_t C = (size_t)A.C, K = (size_t)n_points, maxw = (size_t)wc.max_way_points;
+  WpTrajArgs W;
+  memset(&W, 0, sizeof(W));
+  double* d_fit;  // ts | points | derivs: the layout fuelmi_bspline_dev_load_samples stages
+  int* d_nway;
+  double *d_way, *d_vel, *d_acc;
+  auto layout = [&](unsigned char* base) {
+    BlockLayout L(base, 16);
+    d_fit = L.take<double>(C * (1 + K * 3 + 12));
+    d_nway = L.take<int>(C);
+    d_way = L.take<double>(C * maxw * 3);
+    d_vel = L.take<double>(C * 3);
+    d_acc = L.take<double>(C * 3);
+    W.status = L.take<int>(C);
+    W.seg_num = L.take<int>(C);
+    W.n_samples = L.take<int>(C);
+    W.duration = L.take<double>(C);
+    W.length = L.take<double>(C);
+    return L.size();
+  };
+  hipStream_t st = m->stream;
+  {
+    const int rc = b->fit_in.reserve(st, layout(nullptr));
+    if (rc) return rc;
+  }
+  layout(b->fit_in.base());
+  W.n_prob = A.C;
+  W.maxw = wc.max_way_points;
+  W.max_vel = wc.max_vel, W.ctrl_pt_dist = wc.ctrl_pt_dist;
+  W.min_seg = wc.min_seg, W.forced_seg = seg, W.max_samples = n_points;
+  HIPCHK(hipMemcpyAsync(d_nway, n_way, C * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_way, way_xyz, C * maxw * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_vel, vel_xyz, C * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_acc, acc_xyz, C * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  W.n_way = d_nway, W.way = d_way, W.vel = d_vel, W.acc = d_acc;
+  W.dt = d_fit;  // the fit's knot spans
+  W.samples = d_fit + C;
+  W.derivs = d_fit + C + C * K * 3;
+  const FitArgs F = fit_args(b, W.dt, W.samples, W.derivs, W.status);
+  {
+    StageScope sc(m, FUELMI_K_BSPLINE);
+    const int rcw = wptraj_launch(st, W);
+    if (rcw) return rcw;
+    const int rcf = fit_launch(m, F);
+    if (rcf) return rcf;
+  }
+  HIPCHK(hipMemcpyAsync(status, W.status, C * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (duration) HIPCHK(hipMemcpyAsync(duration, W.duration, C * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(stream_wait(st));
+  for (int c = 0; c < A.C; ++c)
+    if (status[c] == -1) {
+      fuelmi_set_error("waypoint trajectories: candidate %d does not give %d samples", c, n_points);
       return FUELMI_ELIMIT;
     }
   return FUELMI_OK;

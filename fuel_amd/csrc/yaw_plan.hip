@@ -18,11 +18,13 @@
 // One wave of YP_NT lanes per problem, one lane per way-point (looped past YP_NT), all f64, -ffp-contract=off.  The
 // knots are staged in LDS by the accumulated additions; the unwrap chain and the factorisation are serial in lane 0
 // (N <= 259).  A result does not depend on the problem's place in the batch.
+// Behind the kernel, the two entries that share its checks, argument fill, result layout and copy-out: fuelmi_map_plan_yaws
+// (through a query slot) and fuelmi_bspline_dev_plan_yaws (the splines a device batch's last solve left, bspline_batch.h).
 #include <cmath>
 #include <cstring>
 #include <vector>
 
-#include "fuelmi_internal.h"
+#include "bspline_batch.h"
 #include "spline_internal.h"
 
 namespace {
@@ -380,10 +382,15 @@ int yaw_cfg_check(const fuelmi_yaw_cfg* cfg) {
   return FUELMI_OK;
 }
 
-}  // namespace
+// the caller's host arrays of both entries (the first three null for a device batch: the host does not see its splines)
+struct YawIO {
+  const int* n_ctrl;
+  const double *pos_ctrl, *knot_span, *start_yaw, *end_yaw;
+  int *status, *seg_num, *n_waypt;
+  double *duration, *dt_yaw, *yaw_ctrl, *waypts, *end_yaw_out, *cost, *yawdot_ctrl, *yawddot_ctrl;  // the last two or null
+};
 
-int yaw_check(const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob, const int* n_ctrl,
-              const double* pos_ctrl, const double* knot_span, const double* start_yaw, const double* end_yaw) {
+int yaw_check(const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob, const YawIO& io) {
   {
     const int rc = yaw_cfg_check(cfg);
     if (rc) return rc;
@@ -394,25 +401,37 @@ int yaw_check(const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob
   ARGCHK(w->ld_smooth > 0.0 && w->ld_start > 0.0);
   ARGCHK(n_prob >= 0);
   if (n_prob == 0) return FUELMI_OK;
-  ARGCHK(start_yaw);
-  ARGCHK(end_yaw || cfg->mode == FUELMI_YAW_FOLLOW);
+  ARGCHK(io.start_yaw);
+  ARGCHK(io.end_yaw || cfg->mode == FUELMI_YAW_FOLLOW);
   for (int b = 0; b < n_prob; ++b) {
-    for (int k = 0; k < 3; ++k) ARGCHK(std::fabs(start_yaw[3 * b + k]) <= 1e3);
-    if (cfg->mode == FUELMI_YAW_EXPLORE) ARGCHK(std::fabs(end_yaw[b]) <= 1e3);
+    for (int k = 0; k < 3; ++k) ARGCHK(std::fabs(io.start_yaw[3 * b + k]) <= 1e3);
+    if (cfg->mode == FUELMI_YAW_EXPLORE) ARGCHK(std::fabs(io.end_yaw[b]) <= 1e3);
   }
-  if (!n_ctrl) return FUELMI_OK;  // a device batch: its variables are checked by the kernel
-  ARGCHK(pos_ctrl && knot_span);
-  for (int b = 0; b < n_prob; ++b) {
-    ARGCHK(n_ctrl[b] >= cfg->pos_degree + 1 && n_ctrl[b] <= cfg->max_ctrl);
-    ARGCHK(std::isfinite(knot_span[b]) && knot_span[b] > 0.0);
-    const double* P = pos_ctrl + (size_t)b * cfg->max_ctrl * 3;
-    for (int k = 0; k < 3 * n_ctrl[b]; ++k) ARGCHK(std::fabs(P[k]) < 1e7);
+  if (io.n_ctrl) {  // (a device batch: its variables are checked by the kernel)
+    ARGCHK(io.pos_ctrl && io.knot_span);
+    for (int b = 0; b < n_prob; ++b) {
+      ARGCHK(io.n_ctrl[b] >= cfg->pos_degree + 1 && io.n_ctrl[b] <= cfg->max_ctrl);
+      ARGCHK(std::isfinite(io.knot_span[b]) && io.knot_span[b] > 0.0);
+      const double* P = io.pos_ctrl + (size_t)b * cfg->max_ctrl * 3;
+      for (int k = 0; k < 3 * io.n_ctrl[b]; ++k) ARGCHK(std::fabs(P[k]) < 1e7);
+    }
   }
+  ARGCHK(io.status && io.duration && io.seg_num && io.dt_yaw && io.yaw_ctrl && io.n_waypt && io.waypts &&
+         io.end_yaw_out && io.cost);
   return FUELMI_OK;
 }
 
-size_t yaw_out_bytes(const fuelmi_yaw_cfg* cfg, int n_prob, YawArgs& Y, unsigned char* base, bool dot, bool ddot) {
-  const size_t n = (size_t)n_prob, maxs = (size_t)cfg->max_seg;
+// Y cleared, then its part that comes from the two configs
+void yaw_args(const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob, YawArgs& Y) {
+  memset(&Y, 0, sizeof(Y));
+  Y.cfg = *cfg;
+  Y.ld_smooth = w->ld_smooth, Y.ld_start = w->ld_start, Y.ld_end = w->ld_end, Y.ld_waypt = w->ld_waypt;
+  Y.n_prob = n_prob;
+}
+
+// the result block's layout (base null: only its size); the derivatives' control points only where the caller asks
+size_t yaw_out_bytes(YawArgs& Y, unsigned char* base, const YawIO& io) {
+  const size_t n = (size_t)Y.n_prob, maxs = (size_t)Y.cfg.max_seg;
   BlockLayout L(base, 16);
   Y.status = L.take<int>(n);
   Y.seg_num = L.take<int>(n);
@@ -423,29 +442,29 @@ size_t yaw_out_bytes(const fuelmi_yaw_cfg* cfg, int n_prob, YawArgs& Y, unsigned
   Y.cost = L.take<double>(n);
   Y.yaw_ctrl = L.take<double>(n * (maxs + 3));
   Y.waypts = L.take<double>(n * maxs);
-  Y.yawdot_ctrl = dot ? L.take<double>(n * (maxs + 2)) : nullptr;
-  Y.yawddot_ctrl = ddot ? L.take<double>(n * (maxs + 1)) : nullptr;
+  Y.yawdot_ctrl = io.yawdot_ctrl ? L.take<double>(n * (maxs + 2)) : nullptr;
+  Y.yawddot_ctrl = io.yawddot_ctrl ? L.take<double>(n * (maxs + 1)) : nullptr;
   return L.size();
 }
 
-int yaw_copy_out(const fuelmi_yaw_cfg* cfg, int n_prob, const YawArgs& H, int* status, double* duration, int* seg_num,
-                 double* dt_yaw, double* yaw_ctrl, int* n_waypt, double* waypts, double* end_yaw_out, double* cost,
-                 double* yawdot_ctrl, double* yawddot_ctrl) {
-  const size_t n = (size_t)n_prob, maxs = (size_t)cfg->max_seg;
-  memcpy(status, H.status, n * sizeof(int));
-  memcpy(seg_num, H.seg_num, n * sizeof(int));
-  memcpy(n_waypt, H.n_waypt, n * sizeof(int));
-  memcpy(duration, H.duration, n * sizeof(double));
-  memcpy(dt_yaw, H.dt_yaw, n * sizeof(double));
-  memcpy(end_yaw_out, H.end_yaw_out, n * sizeof(double));
-  memcpy(cost, H.cost, n * sizeof(double));
-  memcpy(yaw_ctrl, H.yaw_ctrl, n * (maxs + 3) * sizeof(double));
-  memcpy(waypts, H.waypts, n * maxs * sizeof(double));
-  if (yawdot_ctrl) memcpy(yawdot_ctrl, H.yawdot_ctrl, n * (maxs + 2) * sizeof(double));
-  if (yawddot_ctrl) memcpy(yawddot_ctrl, H.yawddot_ctrl, n * (maxs + 1) * sizeof(double));
-  for (int b = 0; b < n_prob; ++b)
-    if (status[b] == -1) {
-      fuelmi_set_error("yaw plan: problem %d needs %d yaw segments, more than max_seg = %d", b, seg_num[b], cfg->max_seg);
+// the result block in host-readable memory -> the caller's arrays (FUELMI_ELIMIT when a problem's status is -1)
+int yaw_copy_out(const YawArgs& H, const YawIO& io) {
+  const size_t n = (size_t)H.n_prob, maxs = (size_t)H.cfg.max_seg;
+  memcpy(io.status, H.status, n * sizeof(int));
+  memcpy(io.seg_num, H.seg_num, n * sizeof(int));
+  memcpy(io.n_waypt, H.n_waypt, n * sizeof(int));
+  memcpy(io.duration, H.duration, n * sizeof(double));
+  memcpy(io.dt_yaw, H.dt_yaw, n * sizeof(double));
+  memcpy(io.end_yaw_out, H.end_yaw_out, n * sizeof(double));
+  memcpy(io.cost, H.cost, n * sizeof(double));
+  memcpy(io.yaw_ctrl, H.yaw_ctrl, n * (maxs + 3) * sizeof(double));
+  memcpy(io.waypts, H.waypts, n * maxs * sizeof(double));
+  if (io.yawdot_ctrl) memcpy(io.yawdot_ctrl, H.yawdot_ctrl, n * (maxs + 2) * sizeof(double));
+  if (io.yawddot_ctrl) memcpy(io.yawddot_ctrl, H.yawddot_ctrl, n * (maxs + 1) * sizeof(double));
+  for (int b = 0; b < H.n_prob; ++b)
+    if (io.status[b] == -1) {
+      fuelmi_set_error("yaw plan: problem %d needs %d yaw segments, more than max_seg = %d", b, io.seg_num[b],
+                       H.cfg.max_seg);
       return FUELMI_ELIMIT;
     }
   return FUELMI_OK;
@@ -458,6 +477,8 @@ int yaw_launch(hipStream_t st, const YawArgs& Y) {
   return FUELMI_OK;
 }
 
+}  // namespace
+
 extern "C" int fuelmi_yaw_plan(const fuelmi_yaw_cfg* cfg, int out3[3]) {
   ARGCHK(out3);
   {
@@ -468,24 +489,26 @@ extern "C" int fuelmi_yaw_plan(const fuelmi_yaw_cfg* cfg, int out3[3]) {
   return FUELMI_OK;
 }
 
+// the host route: staged in a query slot's pinned block, launched on the slot's stream, copied out of the pinned block
 extern "C" int fuelmi_map_plan_yaws(fuelmi_map* m, const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob,
                                     const int* n_ctrl, const double* pos_ctrl, const double* knot_span,
                                     const double* start_yaw, const double* end_yaw, int* status, double* duration,
                                     int* seg_num, double* dt_yaw, double* yaw_ctrl, int* n_waypt, double* waypts,
                                     double* end_yaw_out, double* cost, double* yawdot_ctrl, double* yawddot_ctrl) {
+  const YawIO io = {n_ctrl, pos_ctrl, knot_span, start_yaw, end_yaw,     status, seg_num,     n_waypt,
+                    duration, dt_yaw, yaw_ctrl,  waypts,    end_yaw_out, cost,   yawdot_ctrl, yawddot_ctrl};
   {  // every argument on the host, before the map is touched
     ARGCHK(n_prob <= 0 || n_ctrl);
-    const int rc = yaw_check(w, cfg, n_prob, n_ctrl, pos_ctrl, knot_span, start_yaw, end_yaw);
+    const int rc = yaw_check(w, cfg, n_prob, io);
     if (rc) return rc;
   }
   if (n_prob == 0) return FUELMI_OK;
-  ARGCHK(status && duration && seg_num && dt_yaw && yaw_ctrl && n_waypt && waypts && end_yaw_out && cost);
   ARGCHK(m);
   HIPCHK(hipSetDevice(m->device));
   const size_t n = (size_t)n_prob, maxc = (size_t)cfg->max_ctrl;
   YawArgs Y;
-  memset(&Y, 0, sizeof(Y));
-  const size_t b_out = yaw_out_bytes(cfg, n_prob, Y, nullptr, yawdot_ctrl != nullptr, yawddot_ctrl != nullptr);
+  yaw_args(w, cfg, n_prob, Y);
+  const size_t b_out = yaw_out_bytes(Y, nullptr, io);
   int* p_nc;
   double *p_knot, *p_end, *p_pos, *p_start;
   unsigned char* p_out;
@@ -505,9 +528,6 @@ extern "C" int fuelmi_map_plan_yaws(fuelmi_map* m, const fuelmi_bspline_cfg* w, 
     if (rcq) return rcq;
   }
   layout(q.s->pin);
-  Y.cfg = *cfg;
-  Y.ld_smooth = w->ld_smooth, Y.ld_start = w->ld_start, Y.ld_end = w->ld_end, Y.ld_waypt = w->ld_waypt;
-  Y.n_prob = n_prob;
   memcpy(p_nc, n_ctrl, n * sizeof(int));
   memcpy(p_knot, knot_span, n * sizeof(double));
   if (end_yaw)
@@ -518,12 +538,72 @@ extern "C" int fuelmi_map_plan_yaws(fuelmi_map* m, const fuelmi_bspline_cfg* w, 
   memcpy(p_start, start_yaw, n * 3 * sizeof(double));
   Y.src = {p_nc, 0, p_pos, maxc * 3, p_knot, 1};
   Y.start_yaw = p_start, Y.end_yaw = p_end;
-  yaw_out_bytes(cfg, n_prob, Y, p_out, yawdot_ctrl != nullptr, yawddot_ctrl != nullptr);
+  yaw_out_bytes(Y, p_out, io);
   {
     const int rc = yaw_launch(q.s->st, Y);
     if (rc) return rc;
   }
   HIPCHK(q.finish());
-  return yaw_copy_out(cfg, n_prob, Y, status, duration, seg_num, dt_yaw, yaw_ctrl, n_waypt, waypts, end_yaw_out, cost,
-                      yawdot_ctrl, yawddot_ctrl);
+  return yaw_copy_out(Y, io);
+}
+
+// the batch route: the splines the batch's last solve left on the device; staged in yaw_dev on the map's stream, downloaded
+extern "C" int fuelmi_bspline_dev_plan_yaws(fuelmi_bspline_dev* b, const fuelmi_yaw_cfg* cfg, const double* start_yaw,
+                                            const double* end_yaw, int* status, double* duration, int* seg_num,
+                                            double* dt_yaw, double* yaw_ctrl, int* n_waypt, double* waypts,
+                                            double* end_yaw_out, double* cost, double* yawdot_ctrl,
+                                            double* yawddot_ctrl) {
+  ARGCHK(b && cfg);
+  const BsplineArgs& A = b->a;
+  ARGCHK(A.dim == 3 && b->opt_valid && b->opt_x);
+  ARGCHK(cfg->pos_degree == A.cfg.bspline_degree);
+  fuelmi_yaw_cfg yc = *cfg;
+  yc.max_ctrl = A.N;  // (yaw_cfg_check's max_ctrl >= pos_degree + 1 is the batch's N >= degree + 1)
+  const YawIO io = {nullptr,  nullptr, nullptr,  start_yaw, end_yaw,     status, seg_num,     n_waypt,
+                    duration, dt_yaw,  yaw_ctrl, waypts,    end_yaw_out, cost,   yawdot_ctrl, yawddot_ctrl};
+  {
+    const int rc = yaw_check(&A.cfg, &yc, A.C, io);
+    if (rc) return rc;
+  }
+  fuelmi_map* m = b->map;
+  ARGCHK(m);
+  HIPCHK(hipSetDevice(m->device));
+  const size_t C = (size_t)A.C;
+  YawArgs Y;
+  yaw_args(&A.cfg, &yc, A.C, Y);
+  const size_t b_out = yaw_out_bytes(Y, nullptr, io);
+  double *d_start, *d_end;
+  unsigned char* d_out;
+  auto layout = [&](unsigned char* base) {
+    BlockLayout L(base, 16);
+    d_start = L.take<double>(C * 3);
+    d_end = L.take<double>(C);
+    d_out = L.take<unsigned char>(b_out);
+    return L.size();
+  };
+  hipStream_t st = m->stream;
+  {
+    const int rc = b->yaw_dev.reserve(st, layout(nullptr));
+    if (rc) return rc;
+  }
+  layout(b->yaw_dev.base());
+  HIPCHK(hipMemcpyAsync(d_start, start_yaw, C * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  if (end_yaw)
+    HIPCHK(hipMemcpyAsync(d_end, end_yaw, C * sizeof(double), hipMemcpyHostToDevice, st));
+  else
+    HIPCHK(hipMemsetAsync(d_end, 0, C * sizeof(double), st));
+  Y.src = opt_spline_src(b);
+  Y.start_yaw = d_start, Y.end_yaw = d_end;
+  yaw_out_bytes(Y, d_out, io);
+  {
+    StageScope sc(m, FUELMI_K_BSPLINE);
+    const int rc = yaw_launch(st, Y);
+    if (rc) return rc;
+  }
+  std::vector<unsigned char> host(b_out);
+  HIPCHK(hipMemcpyAsync(host.data(), d_out, b_out, hipMemcpyDeviceToHost, st));
+  HIPCHK(stream_wait(st));
+  YawArgs H = Y;
+  yaw_out_bytes(H, host.data(), io);
+  return yaw_copy_out(H, io);
 }

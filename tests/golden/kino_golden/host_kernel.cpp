@@ -31,6 +31,12 @@ static inline void pos_to_idx(const Geo& g, const double p[3], int id[3]) {
   for (int k = 0; k < 3; ++k) id[k] = (int)floor((p[k] - g.org[k]) * g.res_inv);
 }
 static inline bool bit_at(const u64* pl, long a) { return (pl[a >> 6] >> (a & 63)) & 1ull; }
+static inline bool plane_at_pos(const Geo& g, const u64* pl, const double p[3]) {
+  int id[3];
+  pos_to_idx(g, p, id);
+  if (!idx_in_map(g, id)) return false;
+  return bit_at(pl, (long)id[0] * g.nyz + (long)id[1] * g.nz + id[2]);
+}
 void fuelmi_set_error(const char*, ...) {}
 #include "kernel.inc"
 

@@ -128,8 +128,8 @@ int main(int argc, char** argv) {
     std::vector<double> dv[3], hp((size_t)n * 3, -7.0);
     for (auto& v : iv) v.assign(n, -77);
     for (auto& v : dv) v.assign(n, -7.0);
-    T.n_prob = n, T.n_ctrl = nc.data(), T.pos = pos.data(), T.pos_stride = (size_t)maxc * 3, T.knot = knot.data();
-    T.knot_stride = 1, T.t_now = now.data(), T.infl = plane[map].data();
+    T.n_prob = n, T.src = {nc.data(), 0, pos.data(), (size_t)maxc * 3, knot.data(), 1};
+    T.t_now = now.data(), T.infl = plane[map].data();
     T.status = iv[0].data(), T.safe = iv[1].data(), T.n_samples = iv[2].data(), T.hit_index = iv[3].data();
     T.end_reason = iv[4].data(), T.distance = dv[0].data(), T.hit_t = dv[1].data(), T.duration = dv[2].data();
     T.hit_pos = hp.data();

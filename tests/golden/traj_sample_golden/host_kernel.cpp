@@ -103,10 +103,10 @@ int main(int argc, char** argv) {
     }
     A.n_prob = n;
     if (device_batch)  // every problem has the stride's number of points, as in a batch
-      A.n_ctrl = nullptr, A.n_ctrl_all = c.max_ctrl;
+      A.src.n_ctrl = nullptr, A.src.n_ctrl_all = c.max_ctrl;
     else
-      A.n_ctrl = nc.data();
-    A.pos = pos.data(), A.pos_stride = (size_t)c.max_ctrl * 3, A.knot = knot.data(), A.knot_stride = 1;
+      A.src.n_ctrl = nc.data();
+    A.src.pos = pos.data(), A.src.pos_stride = (size_t)c.max_ctrl * 3, A.src.knot = knot.data(), A.src.knot_stride = 1;
     if (has_yaw) A.n_yaw = ny.data(), A.yaw = yaw.data(), A.yaw_dt = ydt.data();
     if (has_stop) A.t_stop = stop.data();
     A.n_t = nt.data(), A.t = t.data();
