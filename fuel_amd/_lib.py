@@ -162,6 +162,24 @@ TRAJSMP_IN, TRAJSMP_PAST, TRAJSMP_INVALID, TRAJSMP_BADSPLINE = range(4)
 TRAJSMP_MAX_CTRL, TRAJSMP_MAX_T, TRAJSMP_MAX_SAMPLES = 1024, 1 << 16, 1 << 21
 
 
+class TrajAdjCfg(C.Structure):
+    """fuelmi_trajadj_cfg: the stages, the degree, the strides, the reallocation loop's bound, the groups, setPhysicalLimits'
+    values, lengthenTime's cap and the two step sizes."""
+    _fields_ = [("ops", C.c_int), ("degree", C.c_int), ("max_ctrl", C.c_int), ("max_samples", C.c_int),
+                ("realloc_iters", C.c_int), ("n_group", C.c_int), ("limit_vel", C.c_double), ("limit_acc", C.c_double),
+                ("limit_ratio", C.c_double), ("lengthen_cap", C.c_double), ("length_res", C.c_double),
+                ("stat_step", C.c_double)]
+
+
+TRAJADJ_LENGTHEN, TRAJADJ_REALLOC, TRAJADJ_RESAMPLE, TRAJADJ_SELECT = 1, 2, 4, 8
+TRAJADJ_OK, TRAJADJ_BADSPLINE, TRAJADJ_LONG = range(3)
+TRAJADJ_MAX_CTRL, TRAJADJ_MAX_SAMPLES, TRAJADJ_MAX_PROB, TRAJADJ_MAX_STEPS = 1024, 4096, 1 << 16, 1 << 16
+TRAJADJ_INFO = ("status", "feasible_in", "iters", "feasible", "feasible_out", "num_vel", "num_acc", "n_samples")
+TRAJADJ_METRICS = ("duration_in", "ratio", "duration_out", "length", "jerk", "mean_vel", "max_vel", "mean_acc", "max_acc",
+                   "dt_out", "time_inc")
+TRAJADJ_NI, TRAJADJ_NM = 8, 12
+
+
 class CloudCfg(C.Structure):
     """fuelmi_cloud_cfg: the kind, the inclusive voxel box and map_ros's two truncation heights."""
     _fields_ = [("kind", C.c_int), ("lo", C.c_int * 3), ("hi", C.c_int * 3), ("z_low", C.c_double), ("z_high", C.c_double)]
@@ -320,6 +338,10 @@ SYMBOLS = {
     "fuelmi_bspline_dev_sample_trajs": (C.c_int, [_P, C.POINTER(TrajSmpCfg), _ip, _dp, _dp, _dp, _ip, _dp, _ip, _dp, _dp,
                                                   _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "fuelmi_traj_sample_plan": (C.c_int, [C.POINTER(TrajSmpCfg), _ip]),
+    "fuelmi_map_adjust_trajs": (C.c_int, [_P, C.POINTER(TrajAdjCfg), C.c_int, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp,
+                                          _ip]),
+    "fuelmi_bspline_dev_adjust_trajs": (C.c_int, [_P, C.POINTER(TrajAdjCfg), _dp, _dp, _ip, _ip, _dp, _dp, _dp, _ip]),
+    "fuelmi_traj_adjust_plan": (C.c_int, [C.POINTER(TrajAdjCfg), _ip]),
     "fuelmi_map_extract_cloud": (C.c_int, [_P, C.POINTER(CloudCfg), C.c_void_p, C.c_int, _ip]),
     "fuelmi_cloud_plan": (C.c_int, [_ip, _ip, _ip, _ip]),
     "fuelmi_map_cloud_times": (C.c_int, [_P, _dp]),

@@ -44,6 +44,7 @@ struct fuelmi_bspline_dev {
   DevScratch yaw_dev;  // fuelmi_bspline_dev_plan_yaws: start | end | results
   DevScratch chk_dev;  // fuelmi_bspline_dev_check_trajs: t_now | results
   DevScratch smp_dev;  // fuelmi_bspline_dev_sample_trajs: yaw splines, times | results
+  DevScratch adj_dev;  // fuelmi_bspline_dev_adjust_trajs: knots, ratios, groups | results
 };
 
 struct FitArgs {

@@ -223,6 +223,7 @@ struct fuelmi_map {
   DevScratch kino_dev;     // fuelmi_map_kino_paths (kino_path.hip): inputs, results, node pools, heaps, hashes
   DevScratch trajchk_dev;  // fuelmi_map_check_trajs (traj_check.hip): problems in, results out
   DevScratch trajsmp_dev;  // fuelmi_map_sample_trajs (traj_sample.hip): problems in, results out
+  DevScratch trajadj_dev;  // fuelmi_map_adjust_trajs (traj_adjust.hip): problems in, results out
   DevScratch cloud_dev;    // fuelmi_map_extract_cloud (map_cloud.hip): the total, the workgroup words, the points
   int path_stats[4] = {0, 0, 0, 0};  // fuelmi_map_path_stats
   hipEvent_t goal_ev[3] = {nullptr, nullptr, nullptr};  // the events that split the goal-path call's time

@@ -124,6 +124,42 @@ public:
                    double yaw_dt, double t_r, Eigen::Vector3d& start_pt, Eigen::Vector3d& start_vel,
                    Eigen::Vector3d& start_acc, Eigen::Vector3d& start_yaw);
 
+  // addition: the half of NonUniformBspline that moves knots and measures a spline (bspline/src/non_uniform_bspline.cpp
+  // :135-176, :267-487), each in one device call (fuelmi_map_adjust_trajs, include/fuelmi.h) on the position spline
+  // (pos_ctrl rows, degree) with the knots in `knots`: pos_ctrl.rows() + degree + 1 of them, or an EMPTY vector for the
+  // uniform knots of the span dt.  The limits are setPhysicalLimits' (the reference's callers pass max_vel_ / max_acc_,
+  // the defaults here) and the constants both reference callers use.
+  struct TrajAdjust {
+    double limit_vel = 2.0, limit_acc = 2.0, limit_ratio = 1.1, lengthen_cap = 1.01, length_res = 0.01, stat_step = 0.01;
+    int realloc_iters = 3;
+  };
+  // what one spline comes back with: info[FUELMI_TRAJADJ_I_*] and metrics[FUELMI_TRAJADJ_M_*]
+  struct TrajMetrics {
+    int info[FUELMI_TRAJADJ_NI];
+    double metrics[FUELMI_TRAJADJ_NM];
+    int status() const { return info[FUELMI_TRAJADJ_I_STATUS]; }
+    bool feasible() const { return info[FUELMI_TRAJADJ_I_FEASIBLE_OUT] != 0; }
+    double duration() const { return metrics[FUELMI_TRAJADJ_M_DURATION_OUT]; }
+    double length() const { return metrics[FUELMI_TRAJADJ_M_LENGTH]; }
+    double jerk() const { return metrics[FUELMI_TRAJADJ_M_JERK]; }
+  };
+  // adjustTime: ops = FUELMI_TRAJADJ_LENGTHEN (lengthenTime(min(cap, ratio_in ? *ratio_in : checkRatio())), the first
+  // half of reparamBspline, planner_manager.cpp:534-536) | FUELMI_TRAJADJ_REALLOC (the checkFeasibility /
+  // reallocateTime loop, :222-230) | FUELMI_TRAJADJ_RESAMPLE (the points of :541-543 into samples, one row each; their
+  // step is metrics[FUELMI_TRAJADJ_M_DT_OUT], what parameterizeToBspline takes next).  knots receives the adjusted
+  // knots (setKnot on the reference's class continues from them), samples may be null.  trajectoryMetrics measures the
+  // spline as it is: getTimeSum, checkRatio, checkFeasibility, getLength, getJerk, getMeanAndMaxVel / Acc.  Both return
+  // false, and touch no output, when the call fails.
+  bool adjustTime(const Eigen::MatrixXd& pos_ctrl, int degree, double dt, Eigen::VectorXd& knots, int ops,
+                  const double* ratio_in, const TrajAdjust& cfg, TrajMetrics& out, Eigen::MatrixXd* samples);
+  bool trajectoryMetrics(const Eigen::MatrixXd& pos_ctrl, int degree, double dt, const Eigen::VectorXd& knots,
+                         const TrajAdjust& cfg, TrajMetrics& out);
+  // selectBestTraj (planner_manager.cpp:476-482) over uniform splines (control points, knot span) of one degree: the index
+  // of the smallest getJerk(), the smallest index on a tie, never a jerk that is not a number; -1: no candidate (or
+  // the call failed).  All splines are measured in one device call and ranked there.
+  int selectBestTraj(const std::vector<Eigen::MatrixXd>& pos_ctrl, int degree, const std::vector<double>& dt,
+                     const TrajAdjust& cfg, std::vector<TrajMetrics>* all);
+
   Eigen::MatrixXd getControlPoints();
   vector<Eigen::Vector3d> matrixToVectors(const Eigen::MatrixXd& ctrl_pts);
 

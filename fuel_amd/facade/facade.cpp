@@ -1364,6 +1364,91 @@ bool BsplineOptimizer::replanState(const Eigen::MatrixXd& pos_ctrl, int degree, 
   return true;
 }
 
+static fuelmi_trajadj_cfg trajadj_cfg(const BsplineOptimizer::TrajAdjust& c, int ops, int degree, int max_ctrl, int n_group) {
+  fuelmi_trajadj_cfg a;
+  a.ops = ops, a.degree = degree, a.max_ctrl = max_ctrl, a.max_samples = max_ctrl - degree + 2;
+  a.realloc_iters = c.realloc_iters, a.n_group = n_group;
+  a.limit_vel = c.limit_vel, a.limit_acc = c.limit_acc, a.limit_ratio = c.limit_ratio, a.lengthen_cap = c.lengthen_cap;
+  a.length_res = c.length_res, a.stat_step = c.stat_step;
+  return a;
+}
+
+bool BsplineOptimizer::adjustTime(const Eigen::MatrixXd& pos_ctrl, int degree, double dt, Eigen::VectorXd& knots, int ops,
+                                  const double* ratio_in, const TrajAdjust& cfg, TrajMetrics& out, Eigen::MatrixXd* samples) {
+  const int n_ctrl = (int)pos_ctrl.rows(), nk = n_ctrl + degree + 1;
+  const int mask = FUELMI_TRAJADJ_LENGTHEN | FUELMI_TRAJADJ_REALLOC | FUELMI_TRAJADJ_RESAMPLE;
+  if (n_ctrl < 1 || pos_ctrl.cols() != 3 || (ops & ~mask) || (knots.rows() != 0 && knots.rows() != nk)) {
+    warn("adjustTime (arguments)", FUELMI_EINVAL);
+    return false;
+  }
+  if (!samples) ops &= ~FUELMI_TRAJADJ_RESAMPLE;
+  std::vector<double> pos(3 * (size_t)n_ctrl), kin((size_t)knots.rows()), kout((size_t)nk, 0.0);
+  for (int i = 0; i < n_ctrl; ++i)
+    for (int k = 0; k < 3; ++k) pos[3 * i + k] = pos_ctrl(i, k);
+  for (int i = 0; i < (int)kin.size(); ++i) kin[i] = knots(i);
+  const fuelmi_trajadj_cfg ac = trajadj_cfg(cfg, ops, degree, n_ctrl, 0);
+  std::vector<double> smp(3 * (size_t)std::max(ac.max_samples, 1), 0.0);
+  TrajMetrics r;
+  const int rc = fuelmi_map_adjust_trajs(edt_environment_->sdf_map_->device(), &ac, 1, &n_ctrl, pos.data(), &dt,
+                                         kin.empty() ? nullptr : kin.data(), ratio_in, nullptr, r.info, r.metrics,
+                                         kout.data(), (ops & FUELMI_TRAJADJ_RESAMPLE) ? smp.data() : nullptr, nullptr);
+  if (rc) {
+    warn("fuelmi_map_adjust_trajs", rc);
+    return false;
+  }
+  out = r;
+  knots = Eigen::VectorXd(nk);
+  for (int i = 0; i < nk; ++i) knots(i) = kout[i];
+  if (samples) {
+    const int ns = r.info[FUELMI_TRAJADJ_I_N_SAMPLES];
+    *samples = Eigen::MatrixXd(ns, 3);
+    for (int i = 0; i < ns; ++i)
+      for (int k = 0; k < 3; ++k) (*samples)(i, k) = smp[3 * (size_t)i + k];
+  }
+  return true;
+}
+
+bool BsplineOptimizer::trajectoryMetrics(const Eigen::MatrixXd& pos_ctrl, int degree, double dt, const Eigen::VectorXd& knots,
+                                         const TrajAdjust& cfg, TrajMetrics& out) {
+  Eigen::VectorXd u = knots;
+  return adjustTime(pos_ctrl, degree, dt, u, 0, nullptr, cfg, out, nullptr);
+}
+
+int BsplineOptimizer::selectBestTraj(const std::vector<Eigen::MatrixXd>& pos_ctrl, int degree, const std::vector<double>& dt,
+                                     const TrajAdjust& cfg, std::vector<TrajMetrics>* all) {
+  const int n = (int)pos_ctrl.size();
+  if (n == 0 || dt.size() != pos_ctrl.size()) return -1;
+  int max_ctrl = degree + 1;
+  for (const auto& c : pos_ctrl) {
+    if (c.rows() < 1 || c.cols() != 3) return -1;
+    max_ctrl = std::max(max_ctrl, (int)c.rows());
+  }
+  std::vector<int> n_ctrl(n), group(n, 0), info((size_t)n * FUELMI_TRAJADJ_NI);
+  std::vector<double> pos((size_t)n * max_ctrl * 3, 0.0), met((size_t)n * FUELMI_TRAJADJ_NM);
+  std::vector<double> kout((size_t)n * (max_ctrl + degree + 1));
+  for (int b = 0; b < n; ++b) {
+    n_ctrl[b] = (int)pos_ctrl[b].rows();
+    for (int i = 0; i < n_ctrl[b]; ++i)
+      for (int k = 0; k < 3; ++k) pos[((size_t)b * max_ctrl + i) * 3 + k] = pos_ctrl[b](i, k);
+  }
+  const fuelmi_trajadj_cfg ac = trajadj_cfg(cfg, FUELMI_TRAJADJ_SELECT, degree, max_ctrl, 1);
+  int best = -1;
+  const int rc = fuelmi_map_adjust_trajs(edt_environment_->sdf_map_->device(), &ac, n, n_ctrl.data(), pos.data(), dt.data(),
+                                         nullptr, nullptr, group.data(), info.data(), met.data(), kout.data(), nullptr, &best);
+  if (rc) {
+    warn("fuelmi_map_adjust_trajs", rc);
+    return -1;
+  }
+  if (all) {
+    all->resize(n);
+    for (int b = 0; b < n; ++b) {
+      std::copy(info.begin() + (size_t)b * FUELMI_TRAJADJ_NI, info.begin() + (size_t)(b + 1) * FUELMI_TRAJADJ_NI, (*all)[b].info);
+      std::copy(met.begin() + (size_t)b * FUELMI_TRAJADJ_NM, met.begin() + (size_t)(b + 1) * FUELMI_TRAJADJ_NM, (*all)[b].metrics);
+    }
+  }
+  return best;
+}
+
 vector<Eigen::Vector3d> BsplineOptimizer::matrixToVectors(const Eigen::MatrixXd& ctrl_pts) {
   vector<Eigen::Vector3d> out;
   for (int i = 0; i < ctrl_pts.rows(); ++i) {

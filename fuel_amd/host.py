@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BsplineBatch, BsplineCfg, CloudCfg, FrontierCfg, GoalCfg, KinoCfg, MapCfg, MapInfo, PathCfg, RefineCfg, RenderCfg, TrajChkCfg, TrajSmpCfg, TspCfg,
+from ._lib import (BsplineBatch, BsplineCfg, CloudCfg, FrontierCfg, GoalCfg, KinoCfg, MapCfg, MapInfo, PathCfg, RefineCfg, RenderCfg, TrajAdjCfg, TrajChkCfg, TrajSmpCfg, TspCfg,
                    WptrajCfg, YawCfg, check, lib)
 
 # exploration.launch / algorithm.xml defaults (exploration_manager/launch/algorithm.xml:33-59,170-181)
@@ -119,6 +119,54 @@ def _trajsmp_io(n, t, yaw_ctrl, yaw_dt, t_stop, flight, max_yaw_ctrl, max_t):
             _dp(o["acc"]), _dp(o["jerk"]), _dp(o["yaw"]), _dp(o["yawdot"]), _dp(o["yawddot"]), _dp(o["duration"]), _dp(fl))
     keep = (n_yaw, yaw, ydt, stop, tt)  # (the arrays behind the pointers live as long as the tuple)
     return args, o, maxy, maxt, keep
+
+
+def traj_adjust_cfg(ops=0, degree=3, max_ctrl=4, max_samples=0, realloc_iters=3, n_group=0, limit_vel=2.0, limit_acc=2.0,
+                    limit_ratio=1.1, lengthen_cap=1.01, length_res=0.01, stat_step=0.01):
+    """fuelmi_trajadj_cfg with the reference's values: setPhysicalLimits' limit_ratio, both callers' lengthenTime cap,
+    the three passes of the reallocation loop, getMeanAndMaxVel's step"""
+    return TrajAdjCfg(int(ops), int(degree), int(max_ctrl), int(max_samples), int(realloc_iters), int(n_group),
+                      float(limit_vel), float(limit_acc), float(limit_ratio), float(lengthen_cap), float(length_res),
+                      float(stat_step))
+
+
+def _trajadj_io(n, n_ctrl, degree, maxc, knots_in, ratio_in, group, ops, max_samples, n_group):
+    """The host arrays both adjustment calls share: (arguments from knots_in on, the result dict, max_samples, n_group,
+    the arrays behind the pointers).  knots_in is one 1-D array per problem."""
+    ks = maxc + degree + 1
+    kin = None
+    if knots_in is not None:
+        kin = np.zeros((n, ks))
+        for b, v in enumerate(knots_in):
+            v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+            k = min(len(v), ks)
+            kin[b, :k] = v[:k]
+    rin = None if ratio_in is None else np.ascontiguousarray(np.broadcast_to(np.asarray(ratio_in, dtype=np.float64), (n,)))
+    grp = best = smp = None
+    if ops & _lib.TRAJADJ_SELECT:
+        grp = np.ascontiguousarray(np.broadcast_to(np.asarray(0 if group is None else group, dtype=np.int32), (n,)))
+        if n_group is None:
+            n_group = int(grp.max()) + 1 if n else 1
+        best = np.full(max(int(n_group), 0), -1, dtype=np.int32)
+    if ops & _lib.TRAJADJ_RESAMPLE:
+        if max_samples is None:
+            max_samples = maxc - degree + 2
+        smp = np.zeros((n, max(int(max_samples), 0), 3))
+    info = np.zeros((n, _lib.TRAJADJ_NI), dtype=np.int32)
+    met = np.zeros((n, _lib.TRAJADJ_NM))
+    kout = np.zeros((n, ks))
+    o = {"info": info, "metrics": met, "knots_out": kout, "samples": smp, "best": best, "n_ctrl": n_ctrl}
+    args = (_dp(kin), _dp(rin), _ip(grp), _ip(info), _dp(met), _dp(kout), _dp(smp), _ip(best))
+    return args, o, int(max_samples or 0), int(n_group or 0), (kin, rin, grp)
+
+
+def _trajadj_named(o):
+    """the columns of info and metrics under their names (views)"""
+    for k, name in enumerate(_lib.TRAJADJ_INFO):
+        o[name] = o["info"][:, k]
+    for k, name in enumerate(_lib.TRAJADJ_METRICS):
+        o[name] = o["metrics"][:, k]
+    return o
 
 
 def cloud_plan(dims, lo, hi):
@@ -704,6 +752,39 @@ class SDFMap:
         TrajSmpCfg; host only"""
         out = (C.c_int * 3)()
         check(lib().fuelmi_traj_sample_plan(C.byref(cfg), out))
+        return tuple(out)
+
+    # --- time adjustment and metrics of trajectories (include/fuelmi.h fuelmi_map_adjust_trajs) ---
+    def adjust_trajs(self, pos_ctrl, knot_span=None, knots_in=None, ratio_in=None, group=None, ops=0, max_ctrl=None,
+                     max_samples=None, n_group=None, **cfg):
+        """checkRatio / checkFeasibility, then optionally lengthenTime (TRAJADJ_LENGTHEN), the reallocateTime loop
+        (TRAJADJ_REALLOC), the metrics, reparamBspline's samples (TRAJADJ_RESAMPLE) and selectBestTraj per group
+        (TRAJADJ_SELECT), per problem on the device: pos_ctrl is a list of [n_ctrl, 3] control-point arrays, with knot_span
+        [n] or knots_in, a list of 1-D arrays of n_ctrl + degree + 1 knots; ratio_in [n] or None; group [n]; cfg: the
+        other fields of traj_adjust_cfg.  Returns a dict of arrays: info [n, 8] and metrics [n, 12] and each of their
+        columns under its name (status, iters, jerk, ...), knots_out [n, max_ctrl + degree + 1], samples
+        [n, max_samples, 3] or None, best [n_group] or None, n_ctrl."""
+        pos = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in pos_ctrl]
+        n = len(pos)
+        degree = int(cfg.get("degree", 3))
+        maxc = int(max_ctrl) if max_ctrl is not None else max([len(p) for p in pos] + [degree + 1])
+        n_ctrl = np.array([len(p) for p in pos], dtype=np.int32)
+        args, o, maxs, ng, keep = _trajadj_io(n, n_ctrl, degree, maxc, knots_in, ratio_in, group, int(ops), max_samples, n_group)
+        c = traj_adjust_cfg(ops=ops, max_ctrl=maxc, max_samples=maxs, n_group=ng, **cfg)
+        arr = np.zeros((n, max(maxc, 0), 3))
+        for b, p in enumerate(pos):
+            k = min(len(p), arr.shape[1])
+            arr[b, :k] = p[:k]
+        knot = None if knot_span is None else np.ascontiguousarray(np.broadcast_to(np.asarray(knot_span, dtype=np.float64), (n,)))
+        check(self.L.fuelmi_map_adjust_trajs(self.h, C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(knot), *args))
+        return _trajadj_named(o)
+
+    @staticmethod
+    def traj_adjust_plan(cfg):
+        """(lanes per problem, LDS bytes of a workgroup, largest max_ctrl accepted) of the adjustment kernel for a
+        TrajAdjCfg; host only"""
+        out = (C.c_int * 3)()
+        check(lib().fuelmi_traj_adjust_plan(C.byref(cfg), out))
         return tuple(out)
 
     # --- measurement ---
@@ -1408,6 +1489,20 @@ class BsplineDeviceProblem:
         sc = traj_sample_cfg(max_ctrl=c.point_num, max_yaw_ctrl=maxy, max_t=maxt, **cfg)
         check(self.L.fuelmi_bspline_dev_sample_trajs(self.h, C.byref(sc), *args))
         return o
+
+    def adjust_trajs(self, knots_in=None, ratio_in=None, group=None, ops=0, max_samples=None, n_group=None, **cfg):
+        """The candidates' optimised position splines adjusted, measured and ranked, read from what the last optimize()
+        left on the device (fuelmi_bspline_dev_adjust_trajs).  Arguments and result dict as SDFMap.adjust_trajs from
+        knots_in on."""
+        c = self.problem.c
+        n = c.n_traj
+        degree = int(cfg.setdefault("degree", 3))
+        n_ctrl = np.full(n, c.point_num, dtype=np.int32)
+        args, o, maxs, ng, keep = _trajadj_io(n, n_ctrl, degree, c.point_num, knots_in, ratio_in, group, int(ops), max_samples,
+                                              n_group)
+        ac = traj_adjust_cfg(ops=ops, max_ctrl=c.point_num, max_samples=maxs, n_group=ng, **cfg)
+        check(self.L.fuelmi_bspline_dev_adjust_trajs(self.h, C.byref(ac), *args))
+        return _trajadj_named(o)
 
     def close(self):
         if getattr(self, "h", None):

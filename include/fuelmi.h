@@ -761,7 +761,8 @@ int fuelmi_wptraj_plan(const fuelmi_wptraj_cfg* cfg, int out3[3]);
  * Yaw trajectory of a position spline: FastPlannerManager::planYawExplore (plan_manage/src/planner_manager.cpp:774-865,
  * mode FUELMI_YAW_EXPLORE) and ::planYaw (:695-772, FUELMI_YAW_FOLLOW) for n_prob independent problems in one call.
  * The position spline is UNIFORM (control points + one knot span, setUniformBspline): the exploration path sets no
- * other; a spline whose knots were moved by a time reallocation (lengthenTime) is out of scope.
+ * other.  Moving knots (lengthenTime, reallocateTime) is fuelmi_map_adjust_trajs, below; feeding the moved knots into
+ * this call is out of scope.
  * Per problem, EXPLORE, everything f64 in this order:
  *   1. knots as setUniformBspline builds them (non_uniform_bspline.cpp:25-31): u[i] = double(i - p) * dt for i <= p,
  *      then ACCUMULATED u[i] = u[i-1] + dt; duration = u[n_ctrl] - u[p] (a result of the additions, not a product).
@@ -959,8 +960,8 @@ int fuelmi_kino_plan(const fuelmi_kino_cfg* cfg, long long out8[8]);
  * Safety check of planned trajectories: FastPlannerManager::checkTrajCollision
  * (plan_manage/src/planner_manager.cpp:96-118), which the exploration FSM's safetyCallback runs every 50 ms while a
  * trajectory is flown (exploration_manager/src/fast_exploration_fsm.cpp:335-345), for n_prob independent problems in
- * one call.  The position spline is UNIFORM (control points + one knot span, setUniformBspline); knots moved by a time
- * reallocation (lengthenTime) are out of scope.  Per problem, everything f64 in this order:
+ * one call.  The position spline is UNIFORM (control points + one knot span, setUniformBspline); a time
+ * reallocation is fuelmi_map_adjust_trajs, below, and feeding the knots it moved into this call is out of scope.  Per problem, everything f64 in this order:
  *   1. knots as setUniformBspline builds them (non_uniform_bspline.cpp:25-31): u[i] = double(i - p) * dt for i <= p,
  *      then ACCUMULATED u[i] = u[i-1] + dt; duration = u[n_ctrl] - u[p].
  *   2. cur = evaluateDeBoorT(t_now) (the literal clamp, knot search and alpha recursion of :51-75).
@@ -1073,7 +1074,8 @@ int fuelmi_traj_check_plan(const fuelmi_trajchk_cfg* cfg, int out3[3]);
  *            The spline is never indexed: every sample of the problem has this status, every output is 0, duration 0,
  *            the record untouched.
  *   Entries from n_t[b] to max_t are written as 0 (status too).
- * Out of scope: loop correction (:292-300), the FOV markers and all publishing, knots moved by a time reallocation.
+ * Out of scope: loop correction (:292-300), the FOV markers and all publishing, and sampling on knots moved by a time
+ * reallocation (moving and measuring them is fuelmi_map_adjust_trajs, below; this call takes uniform splines).
  * Checked on the host before anything is launched (FUELMI_EINVAL): pointers; mode; degree in 3..5 and, with max_yaw_ctrl
  * > 0, yaw_degree in 3..5; degree + 1 <= n_ctrl[b] <= max_ctrl; n_yaw_ctrl[b] == 0 or yaw_degree + 1 <= n_yaw_ctrl[b] <=
  * max_yaw_ctrl; spans finite and > 0; control points finite with |value| < 1e7; 0 <= n_t[b] <= max_t; every t, t_stop and
@@ -1128,6 +1130,130 @@ int fuelmi_bspline_dev_sample_trajs(fuelmi_bspline_dev* b, const fuelmi_trajsmp_
 /* what the kernel needs for cfg (host only, no device needed): out3 = {lanes per problem, dynamic LDS bytes of a
  * workgroup, largest max_ctrl accepted}.  cfg is checked like above. */
 int fuelmi_traj_sample_plan(const fuelmi_trajsmp_cfg* cfg, int out3[3]);
+
+/* ------------------------------------------------------------------------------------------
+ * Time adjustment and metrics of B-spline trajectories: the half of the reference's NonUniformBspline
+ * (bspline/src/non_uniform_bspline.cpp) that moves knots and measures a spline, for n_prob independent position splines
+ * (degree 3..5, dimension 3) in one call.  Everything f64, the reference's operations in the reference's order; the
+ * stages run in this order:
+ *   a. Knots.  knots_in NULL: as setUniformBspline builds them (:25-31) from knot_span[b]: u[i] = double(i - p) * dt for
+ *      i <= p, then ACCUMULATED u[i] = u[i-1] + dt.  Else the caller's n_ctrl[b] + p + 1 knots as given (setKnot), so a
+ *      second call continues from the first call's knots_out.
+ *   b. Always, on the input knots: DURATION_IN = u[n_ctrl] - u[p] (getTimeSum :267); RATIO = checkRatio() (:135-160,
+ *      without the logging); FEASIBLE_IN = checkFeasibility() (:443-487; strict > against limit + 1e-4 per axis).
+ *   c. FUELMI_TRAJADJ_LENGTHEN: lengthenTime(r) (:162-176), r = min(cfg.lengthen_cap, ratio_in ? ratio_in[b] : RATIO)
+ *      (the cap is 1.01 in both reference callers).  num1 = 2p - 1 >= num2 = n_ctrl - p + 1: the knots stay untouched.
+ *   d. FUELMI_TRAJADJ_REALLOC: the loop of plan_manage/src/planner_manager.cpp:222-230 on the current knots:
+ *        feasible = checkFeasibility(); while (!feasible) { feasible = reallocateTime(); if (++iter >= realloc_iters) break; }
+ *      reallocateTime is :346-441 literally: the velocity pass over i, then the acceleration pass; every infeasible i
+ *      moves knots that the test of the next i reads; ratio = max / limit + 1e-4, resp. sqrt(max_acc / limit_acc) + 1e-4,
+ *      capped at limit_ratio; t_inc = delta_t / double(p), resp. double(p - 1); the acceleration pass's branch for
+ *      i == 1 || i == 2 (:416-424) moves u(2..5) and adds 4.0 * t_inc to every knot from 6 on.  Every knot receives its
+ *      additions one at a time in the order of i.  ITERS and FEASIBLE are what the loop left; without REALLOC they are 0
+ *      and checkFeasibility() of the current knots.  FEASIBLE_OUT = checkFeasibility() on the final knots (an addition).
+ *   e. Metrics on the final knots, always: DURATION_OUT; LENGTH = getLength(length_res) (:271-281: the accumulated
+ *      t += res while t <= dur + 1e-4, norms summed left to right); JERK = getJerk() (:283-298: three getDerivative, then
+ *      jerk += (times(i+1) - times(i)) * c * c over rows, then axes); MEAN_VEL / MAX_VEL / NUM_VEL and MEAN_ACC /
+ *      MAX_ACC / NUM_ACC = getMeanAndMaxVel / Acc (:300-344) with the step cfg.stat_step (0.01 in the reference): the
+ *      accumulated t from u_(p_) while t <= u_(m_ - p_) of the derivative spline, evaluateDeBoor(t) with the ABSOLUTE
+ *      parameter, and the sample counts the reference divides by.
+ *   f. FUELMI_TRAJADJ_RESAMPLE: the sampling half of reparamBspline (planner_manager.cpp:533-543): seg_num = n_ctrl - p,
+ *      DT_OUT = DURATION_OUT / double(seg_num), TIME_INC = DURATION_OUT - DURATION_IN (both always written), points
+ *      evaluateDeBoorT(time) for the accumulated time += DT_OUT from 0 while time <= DURATION_OUT + 1e-4: N_SAMPLES and
+ *      samples -- what fuelmi_bspline_parameterize / fuelmi_bspline_dev_load_samples take next, with DT_OUT as ts.
+ *   g. FUELMI_TRAJADJ_SELECT (selectBestTraj, planner_manager.cpp:476-482): best[g] = the index of the smallest JERK
+ *      among the problems with group[b] == g and status OK.  std::sort leaves ties open; here the smallest index wins.
+ *      A JERK that is not a number is never chosen; -1: the group has no candidate.  On the device, after the metrics.
+ * Defined where the reference is not: a status per problem.
+ *   FUELMI_TRAJADJ_BADSPLINE (device batches only, the host route refuses it): a knot span that is not finite and > 0.
+ *            Nothing is indexed: every other output of the problem is 0, knots_out and samples too.
+ *   FUELMI_TRAJADJ_LONG      one of the loops of e and f would take more than FUELMI_TRAJADJ_MAX_STEPS steps (or the
+ *            resampling more than max_samples): the adjusted knots, the durations, RATIO, the feasibility flags, ITERS,
+ *            JERK, DT_OUT and TIME_INC are returned, LENGTH, the mean / max / num values, N_SAMPLES and samples are 0.
+ *   Knots from n_ctrl[b] + p + 1 to the stride and samples from N_SAMPLES to max_samples are written as 0.  No loop on the
+ *   device is unbounded.
+ * Checked on the host before anything is launched (FUELMI_EINVAL): pointers; ops a mask of the four; degree in 3..5;
+ * degree + 1 <= n_ctrl[b] <= max_ctrl; spans finite and > 0; control points finite with |value| < 1e7; knots_in finite
+ * and strictly increasing; ratio_in finite; limit_vel, limit_acc finite and > 0; limit_ratio finite and > 1;
+ * lengthen_cap finite and >= 1; realloc_iters in 1..16; length_res, stat_step finite and > 0; with SELECT n_group >= 1,
+ * group and best given and every group[b] in 0..n_group-1; with RESAMPLE samples given and max_samples >=
+ * max_ctrl - degree + 2.  FUELMI_ELIMIT: max_ctrl > FUELMI_TRAJADJ_MAX_CTRL, max_samples > FUELMI_TRAJADJ_MAX_SAMPLES,
+ * n_prob or n_group > FUELMI_TRAJADJ_MAX_PROB.  n_prob == 0 is FUELMI_OK: nothing is launched, nothing is written.
+ * Out of scope: feeding moved knots into fuelmi_map_sample_trajs, _check_trajs, _plan_yaws or the kinodynamic loader
+ * (those take uniform splines); a device-to-device hand-over of the resampled points to load_samples; yaw (1-D)
+ * splines; the reference's ROS_INFO output; the commented-out VIEWCONS path of refineTraj.
+ * fuelmi_map_adjust_trajs takes host arrays in and out, is synchronous, runs on the map's stream, one thread at a time
+ * per map; its scratch is one grow-only allocation on the map.  It reads no plane and no mirror.  One 64-lane wave per
+ * problem, knots and control points in LDS; the serial passes are walked by every lane alike, the lanes own the knots; the
+ * sums are taken in sample order.  A result does not depend on the problem's place in the batch.
+ * ---------------------------------------------------------------------------------------- */
+#define FUELMI_TRAJADJ_LENGTHEN 1
+#define FUELMI_TRAJADJ_REALLOC 2
+#define FUELMI_TRAJADJ_RESAMPLE 4
+#define FUELMI_TRAJADJ_SELECT 8
+#define FUELMI_TRAJADJ_OK 0
+#define FUELMI_TRAJADJ_BADSPLINE 1
+#define FUELMI_TRAJADJ_LONG 2
+#define FUELMI_TRAJADJ_MAX_CTRL 1024      /* largest max_ctrl */
+#define FUELMI_TRAJADJ_MAX_SAMPLES 4096   /* largest max_samples */
+#define FUELMI_TRAJADJ_MAX_PROB 65536     /* largest n_prob and n_group */
+#define FUELMI_TRAJADJ_MAX_STEPS 65536    /* steps of one metric or resample loop */
+/* info [n_prob][FUELMI_TRAJADJ_NI] */
+#define FUELMI_TRAJADJ_NI 8
+#define FUELMI_TRAJADJ_I_STATUS 0
+#define FUELMI_TRAJADJ_I_FEASIBLE_IN 1
+#define FUELMI_TRAJADJ_I_ITERS 2
+#define FUELMI_TRAJADJ_I_FEASIBLE 3
+#define FUELMI_TRAJADJ_I_FEASIBLE_OUT 4
+#define FUELMI_TRAJADJ_I_NUM_VEL 5
+#define FUELMI_TRAJADJ_I_NUM_ACC 6
+#define FUELMI_TRAJADJ_I_N_SAMPLES 7
+/* metrics [n_prob][FUELMI_TRAJADJ_NM]; the last entry is 0 */
+#define FUELMI_TRAJADJ_NM 12
+#define FUELMI_TRAJADJ_M_DURATION_IN 0
+#define FUELMI_TRAJADJ_M_RATIO 1
+#define FUELMI_TRAJADJ_M_DURATION_OUT 2
+#define FUELMI_TRAJADJ_M_LENGTH 3
+#define FUELMI_TRAJADJ_M_JERK 4
+#define FUELMI_TRAJADJ_M_MEAN_VEL 5
+#define FUELMI_TRAJADJ_M_MAX_VEL 6
+#define FUELMI_TRAJADJ_M_MEAN_ACC 7
+#define FUELMI_TRAJADJ_M_MAX_ACC 8
+#define FUELMI_TRAJADJ_M_DT_OUT 9
+#define FUELMI_TRAJADJ_M_TIME_INC 10
+typedef struct {
+  int ops;              /* FUELMI_TRAJADJ_LENGTHEN | _REALLOC | _RESAMPLE | _SELECT, or 0: measure only */
+  int degree;           /* 3..5 */
+  int max_ctrl;         /* stride of pos_ctrl; knots_in / knots_out have the stride max_ctrl + degree + 1 */
+  int max_samples;      /* stride of samples (RESAMPLE) */
+  int realloc_iters;    /* 1..16; the reference: 3 */
+  int n_group;          /* groups of SELECT */
+  double limit_vel, limit_acc, limit_ratio;  /* setPhysicalLimits; the reference's limit_ratio is 1.1 */
+  double lengthen_cap;  /* the reference: 1.01 */
+  double length_res;    /* getLength's res */
+  double stat_step;     /* the step of getMeanAndMaxVel / Acc; the reference: 0.01 */
+} fuelmi_trajadj_cfg;
+/* In: n_ctrl [n_prob]; pos_ctrl [n_prob][max_ctrl][3]; knot_span [n_prob] (not read with knots_in) or knots_in
+ * [n_prob][max_ctrl + degree + 1]; ratio_in [n_prob] or NULL; group [n_prob] (SELECT).  Out: info
+ * [n_prob][FUELMI_TRAJADJ_NI]; metrics [n_prob][FUELMI_TRAJADJ_NM]; knots_out [n_prob][max_ctrl + degree + 1]; samples
+ * [n_prob][max_samples][3] (RESAMPLE, else NULL); best [n_group] (SELECT, else NULL). */
+int fuelmi_map_adjust_trajs(fuelmi_map* m, const fuelmi_trajadj_cfg* cfg, int n_prob, const int* n_ctrl,
+                            const double* pos_ctrl, const double* knot_span, const double* knots_in,
+                            const double* ratio_in, const int* group, int* info, double* metrics, double* knots_out,
+                            double* samples, int* best);
+/* The device chain optimised batch -> adjusted, measured and ranked candidates: one problem per candidate of `b` (dim
+ * 3), the control points read from the variables the batch's last fuelmi_bspline_dev_optimize[_timed] left in device
+ * memory, the knot span x[nvar-1] under MINTIME and the batch's knot span otherwise (knots_in, a host array, replaces
+ * the span).  cfg->degree must be the batch's bspline_degree and cfg->max_ctrl is ignored (it is point_num).  Only the
+ * results are copied back; they equal, bit for bit, fuelmi_map_adjust_trajs on the x_out that solve returned.
+ * FUELMI_EINVAL when the batch is not dim 3 or has not been optimised since it was created or last (re)loaded (the
+ * preconditions of fuelmi_bspline_dev_check_trajs).  Runs on the map's stream and waits for it. */
+int fuelmi_bspline_dev_adjust_trajs(fuelmi_bspline_dev* b, const fuelmi_trajadj_cfg* cfg, const double* knots_in,
+                                    const double* ratio_in, const int* group, int* info, double* metrics,
+                                    double* knots_out, double* samples, int* best);
+/* what the kernel needs for cfg (host only, no device needed): out3 = {lanes per problem, dynamic LDS bytes of a
+ * workgroup, largest max_ctrl accepted}.  cfg is checked like above. */
+int fuelmi_traj_adjust_plan(const fuelmi_trajadj_cfg* cfg, int out3[3]);
 
 /* ------------------------------------------------------------------------------------------
  * Map clouds and the known-volume count: the scans of MapROS::publishMapLocal, publishMapAll and publishUnknown
