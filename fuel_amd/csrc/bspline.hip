@@ -731,8 +731,9 @@ __device__ void spline_boundary_value(const double* q, int n, int p, const doubl
   for (int a = 0; a < 3; ++a) out[a] = w[pd][a];
 }
 
-// setUniformBspline's knot vector (:15-32): cumulative sums from -p * ts
-__device__ void spline_uniform_knots(double* u, int n, int p, double ts) {
+// setUniformBspline's knot vector (:15-32): cumulative sums from -p * ts.  (The values of spline_internal.h's
+// spline_uniform_knots; the fit and the boundary kernels keep the form their code was generated and timed with.)
+__device__ void fit_uniform_knots(double* u, int n, int p, double ts) {
   const int m = n + p;
   for (int i = 0; i <= m; ++i) u[i] = (i <= p) ? double(-p + i) * ts : u[i - 1] + ts;
 }
@@ -863,7 +864,7 @@ __global__ __launch_bounds__(64) void k_bspline_fit(FitArgs F) {
   if (F.write_dt && lane == 0) out[3 * n] = ts;
   if (F.knot_span && lane == 0) F.knot_span[c] = ts;
   if (!F.start_state && !F.end_state && !F.pt_dist) return;
-  if (lane == 0) spline_uniform_knots(u, n, p, ts);
+  if (lane == 0) fit_uniform_knots(u, n, p, ts);
   __syncthreads();
   if (lane < 3 && F.start_state) spline_boundary_value(x, n, p, u, lane, false, F.start_state + (size_t)c * 9 + 3 * lane);
   if (lane == 3 && F.end_state) spline_boundary_value(x, n, p, u, 0, true, F.end_state + (size_t)c * 9);
@@ -891,7 +892,7 @@ __global__ __launch_bounds__(64) void k_bspline_boundary(int n, int p, const dou
   double* u = q + 3 * n;
   const int c = blockIdx.x, lane = threadIdx.x;
   for (int i = lane; i < 3 * n; i += 64) q[i] = ctrl[(size_t)c * 3 * n + i];
-  if (lane == 0) spline_uniform_knots(u, n, p, ts[c]);
+  if (lane == 0) fit_uniform_knots(u, n, p, ts[c]);
   __syncthreads();
   if (lane <= ks) spline_boundary_value(q, n, p, u, lane, false, start + ((size_t)c * (ks + 1) + lane) * 3);
   else if (lane <= ks + 1 + ke)

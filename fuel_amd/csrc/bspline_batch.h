@@ -1,9 +1,13 @@
 // bspline_batch.h -- what bspline.hip shows the planner stages that have a fuelmi_bspline_dev_* entry: the device batch's
-// state, the fit's argument record and three glue functions (all defined in bspline.hip, which shows nothing else).
+// state, the fit's argument record and three glue functions (all defined in bspline.hip, which shows nothing else); and
+// the host half of a SplineSrc that the caller gives in host arrays.
 #ifndef FUELMI_BSPLINE_BATCH_H_
 #define FUELMI_BSPLINE_BATCH_H_
 
+#include <cmath>
+
 #include "fuelmi_internal.h"
+#include "spline_internal.h"
 
 struct BsplineArgs {
   fuelmi_bspline_cfg cfg;
@@ -68,5 +72,37 @@ struct FitArgs {
 FitArgs fit_args(const fuelmi_bspline_dev* b, double* ts, double* points, double* derivs, int* skip);
 int fit_launch(fuelmi_map* m, const FitArgs& F, hipStream_t st = nullptr);
 SplineSrc opt_spline_src(const fuelmi_bspline_dev* b);
+
+// ---- a SplineSrc from the caller's host arrays n_ctrl [n], pos_ctrl [n][max_ctrl][3], knot_span [n] -----------------
+// the arguments: every n_ctrl in degree + 1 .. max_ctrl, every knot span finite and positive (knots_given: the entry
+// takes whole knot vectors, the spans are not read and may be null), every coordinate the spline reads below 1e7
+inline int spline_src_check(int n_prob, int degree, int max_ctrl, const int* n_ctrl, const double* pos_ctrl,
+                            const double* knot_span, bool knots_given = false) {
+  ARGCHK(n_ctrl && pos_ctrl && (knot_span || knots_given));
+  for (int b = 0; b < n_prob; ++b) {
+    ARGCHK(n_ctrl[b] >= degree + 1 && n_ctrl[b] <= max_ctrl);
+    if (!knots_given) ARGCHK(std::isfinite(knot_span[b]) && knot_span[b] > 0.0);
+    const double* P = pos_ctrl + (size_t)b * max_ctrl * 3;
+    for (int k = 0; k < 3 * n_ctrl[b]; ++k) ARGCHK(std::fabs(P[k]) < 1e7);
+  }
+  return FUELMI_OK;
+}
+// its three arrays in a block
+inline void spline_src_take(BlockLayout& L, size_t n, int max_ctrl, SplineSrc& s) {
+  s.n_ctrl = L.take<int>(n), s.n_ctrl_all = 0;
+  s.knot = L.take<double>(n), s.knot_stride = 1;
+  s.pos = L.take<double>(n * max_ctrl * 3), s.pos_stride = (size_t)max_ctrl * 3;
+}
+// ... filled from the caller's on stream st (knot_span null: zeros, for a kernel that does not read them)
+inline int spline_src_upload(hipStream_t st, const SplineSrc& s, size_t n, int max_ctrl, const int* n_ctrl,
+                             const double* pos_ctrl, const double* knot_span) {
+  HIPCHK(hipMemcpyAsync(const_cast<int*>(s.n_ctrl), n_ctrl, n * sizeof(int), hipMemcpyHostToDevice, st));
+  if (knot_span)
+    HIPCHK(hipMemcpyAsync(const_cast<double*>(s.knot), knot_span, n * sizeof(double), hipMemcpyHostToDevice, st));
+  else
+    HIPCHK(hipMemsetAsync(const_cast<double*>(s.knot), 0, n * sizeof(double), st));
+  HIPCHK(hipMemcpyAsync(const_cast<double*>(s.pos), pos_ctrl, n * max_ctrl * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  return FUELMI_OK;
+}
 
 #endif

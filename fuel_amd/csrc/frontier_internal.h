@@ -599,24 +599,9 @@ int frontier_split_run(fuelmi_frontier* f, u32 nq, u32 nkept, u32 n_out, int fin
                        std::vector<std::vector<float>>* filtered);
 
 
-// ---- voxel walks shared by the viewpoint scoring (frontier_view.hip) and the path costs (path_cost.hip) ----------
+// ---- the voxel walk shared by the viewpoint scoring (frontier_view.hip) and the path costs (path_cost.hip); its
+// look-ups are voxel_internal.h's ---------------------------------------------------------------------------------
 #ifdef __HIPCC__
-__device__ __forceinline__ bool idx_in_map(const Geo& g, const int id[3]) {
-  return !(id[0] < 0 || id[1] < 0 || id[2] < 0 || id[0] > g.nx - 1 || id[1] > g.ny - 1 || id[2] > g.nz - 1);
-}
-__device__ __forceinline__ void pos_to_idx(const Geo& g, const double p[3], int id[3]) {
-  for (int k = 0; k < 3; ++k) id[k] = (int)floor((p[k] - g.org[k]) * g.res_inv);
-}
-__device__ __forceinline__ bool bit_at(const u64* pl, long a) { return (pl[a >> 6] >> (a & 63)) & 1ull; }
-// the plane's bit at a position: getInflateOccupancy(pos) == 1 on the inflated plane, getOccupancy(pos) == UNKNOWN on
-// the unknown one; a position outside the map reads -1 in both and passes
-__device__ __forceinline__ bool plane_at_pos(const Geo& g, const u64* pl, const double p[3]) {
-  int id[3];
-  pos_to_idx(g, p, id);
-  if (!idx_in_map(g, id)) return false;
-  return bit_at(pl, (long)id[0] * g.nyz + (long)id[1] * g.nz + id[2]);
-}
-
 // RayCaster::input + nextId loop (plan_env/src/raycast.cpp:374-407): true iff no visited voxel is inflated or
 // unknown; the walk starts in start's voxel and stops before end's voxel.  kBox: a voxel outside the index box
 // bmin <= id < bmax (SDFMap::isInBox(Vector3i)) also ends the walk unsafe -- ViewNode::searchPath's test

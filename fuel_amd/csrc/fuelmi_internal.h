@@ -385,17 +385,8 @@ static inline void map_drop_plane_reader(fuelmi_map* m, hipEvent_t ev) {
 }
 
 // ---- device helpers ---------------------------------------------------------------------------
+#include "voxel_internal.h"  // idx_in_map, pos_to_idx, bit_at, plane_at_pos, plane_window (host and device)
 #ifdef __HIPCC__
-__device__ __forceinline__ u64 plane_window(const u64* __restrict__ p, long bit) {
-  // 64 bits of the plane starting at (signed) bit index `bit`
-  long wi = bit >> 6;
-  int sh = (int)(bit & 63);
-  u64 lo = p[wi];
-  if (sh == 0) return lo;
-  u64 hi = p[wi + 1];
-  return (lo >> sh) | (hi << (64 - sh));
-}
-
 __device__ __forceinline__ u64 bit_range(int first, int count) {
   // `count` ones starting at bit `first` (0 <= first, first+count <= 64)
   if (count <= 0) return 0ull;
@@ -511,127 +502,7 @@ int esdf_update(fuelmi_map* m);
 size_t esdf_handover_bytes(int nx, int ny, int nz);  // esdf_tmp16 of a grid (0: the packed family cannot run)
 int insert_points(fuelmi_map* m, const float* xyz, int stride_bytes, int n, const double cam[3]);
 void goal_path_release(fuelmi_map* m);  // the goal-path call's events (goal_path.hip)
-// k_waypoint_traj (waypoint_traj.hip): one problem per workgroup; every pointer addresses memory the device can reach
-struct WpTrajArgs {
-  int n_prob;
-  const int* n_way;    // [n]
-  const double* way;   // [n][maxw][3]
-  const double* vel;   // [n][3]
-  const double* acc;   // [n][3]
-  int maxw;
-  double max_vel, ctrl_pt_dist;
-  int min_seg, forced_seg, max_samples;
-  int* status;
-  double* duration;
-  double* length;
-  int* seg_num;
-  double* dt;
-  int* n_samples;
-  double* samples;     // [n][max_samples][3]
-  double* derivs;      // [n][4][3]
-  double* seg_times;   // [n][maxw-1] or null
-  double* coef;        // [n][maxw-1][3][6] or null
-};
-// the position splines of a batch of problems, as k_yaw_plan, k_traj_check and k_traj_sample read them
-struct SplineSrc {
-  const int* n_ctrl;        // [n], or null: every problem has n_ctrl_all control points
-  int n_ctrl_all;
-  const double* pos;        // problem b: [n_ctrl][3] at pos + b * pos_stride
-  size_t pos_stride;
-  const double* knot;       // problem b: knot[b * knot_stride]
-  size_t knot_stride;
-};
-// k_yaw_plan (yaw_plan.hip): one problem per wave; every pointer addresses memory the device can reach
-struct YawArgs {
-  fuelmi_yaw_cfg cfg;
-  double ld_smooth, ld_start, ld_end, ld_waypt;
-  int n_prob;
-  SplineSrc src;
-  const double* start_yaw;  // [n][3]
-  const double* end_yaw;    // [n] (EXPLORE)
-  int* status;
-  int* seg_num;
-  int* n_waypt;
-  double* duration;
-  double* dt_yaw;
-  double* end_yaw_out;
-  double* cost;
-  double* yaw_ctrl;         // [n][max_seg + 3]
-  double* waypts;           // [n][max_seg]
-  double* yawdot_ctrl;      // [n][max_seg + 2] or null
-  double* yawddot_ctrl;     // [n][max_seg + 1] or null
-};
-// k_traj_check (traj_check.hip): one problem per wave; every pointer addresses device memory
-struct TrajChkArgs {
-  fuelmi_trajchk_cfg cfg;
-  int n_prob;
-  SplineSrc src;
-  const double* t_now;      // [n]
-  const u64* infl;          // the map's inflated plane
-  int* status;
-  int* safe;
-  int* n_samples;
-  int* hit_index;
-  int* end_reason;
-  double* distance;
-  double* hit_t;
-  double* duration;
-  double* hit_pos;          // [n][3]
-};
-// k_traj_sample (traj_sample.hip): one problem per wave; every pointer addresses device memory
-struct TrajSmpArgs {
-  fuelmi_trajsmp_cfg cfg;
-  int n_prob;
-  SplineSrc src;
-  const int* n_yaw;         // [n] (0: that problem has no yaw spline), or null: none has
-  const double* yaw;        // [n][max_yaw_ctrl]
-  const double* yaw_dt;     // [n]
-  const double* t_stop;     // [n] or null
-  const int* n_t;           // [n]
-  const double* t;          // [n][max_t]
-  double* flight;           // [n][8] in and out, or null
-  int* status;              // [n][max_t]
-  double *o_pos, *o_vel, *o_acc, *o_jerk;  // [n][max_t][3]
-  double *o_yaw, *o_yawdot, *o_yawddot;    // [n][max_t]
-  double* duration;         // [n]
-};
 void map_cloud_release(fuelmi_map* m);   // the cloud call's pinned word and events (map_cloud.hip)
-// k_kino_path (kino_path.hip): one problem per workgroup; every pointer addresses device memory
-struct KinoArgs {
-  fuelmi_kino_cfg cfg;
-  int n_prob;
-  int n_init, n_reg;        // primitives of the two lists
-  const double* prims;      // [n_init + n_reg][4]: input, tau (the init list's input is the problem's start_acc)
-  int tolerance;            // ceil(1 / resolution)
-  double inv_res;           // 1.0 / resolution
-  double box_mind[3], box_maxd[3], map_size[3];
-  const u64* infl;
-  const u64* unk;
-  const double* in;         // [n][5][3]: start, start_vel, start_acc, goal, goal_vel
-  unsigned char* pool;      // [n][allocate_num] node records
-  int* heap;                // [n][allocate_num]
-  int* hash;                // [n][hash_cap], -1 = empty
-  int hash_cap;             // a power of two >= 2 allocate_num
-  int load_points;          // > 0: the batch route, a path must give exactly this many samples
-  int* status;
-  int* which;
-  int* iter_num;
-  int* use_node_num;
-  int* n_nodes;
-  int* shot;
-  int* seg_num;
-  int* n_samples;
-  int* skip;                // [n] 0: ts / samples / derivs hold a path, 1: they do not (the fit leaves the candidate)
-  double* t_shot;
-  double* coef_shot;        // [n][3][4]
-  double* T_sum;
-  double* ts_out;
-  double* samples;          // [n][max_samples][3]
-  double* derivs;           // [n][4][3]
-  double* node_state;       // [n][max_path_nodes][6] or null
-  double* node_input;       // [n][max_path_nodes][3] or null
-  double* node_duration;    // [n][max_path_nodes] or null
-};
 // device results of one path_cost_enqueue, in the map's path pool (path_dev): length / kind / path_len per pair, paths
 // [n][maxp][3] (nullptr when maxp is 0), and the device copy of p2_xyz
 struct PathRun {

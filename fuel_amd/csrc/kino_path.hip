@@ -32,7 +32,6 @@
 #include <vector>
 
 #include "bspline_batch.h"
-#include "frontier_internal.h"
 
 namespace {
 
@@ -40,6 +39,43 @@ constexpr int KN_NT = 256;
 constexpr int KN_DEAD = -2, KN_NEW = -1;  // a lane's verdict: pruned / no node in its voxel yet / >= 0: that open node
 constexpr int KN_OPEN = 1, KN_CLOSED = 2;
 constexpr int KN_EXPAND = 0;              // lane 0's decision at the top of a pop; otherwise the search's status
+
+// k_kino_path: one problem per workgroup; every pointer addresses device memory
+struct KinoArgs {
+  fuelmi_kino_cfg cfg;
+  int n_prob;
+  int n_init, n_reg;        // primitives of the two lists
+  const double* prims;      // [n_init + n_reg][4]: input, tau (the init list's input is the problem's start_acc)
+  int tolerance;            // ceil(1 / resolution)
+  double inv_res;           // 1.0 / resolution
+  double box_mind[3], box_maxd[3], map_size[3];
+  const u64* infl;
+  const u64* unk;
+  const double* in;         // [n][5][3]: start, start_vel, start_acc, goal, goal_vel
+  unsigned char* pool;      // [n][allocate_num] node records
+  int* heap;                // [n][allocate_num]
+  int* hash;                // [n][hash_cap], -1 = empty
+  int hash_cap;             // a power of two >= 2 allocate_num
+  int load_points;          // > 0: the batch route, a path must give exactly this many samples
+  int* status;
+  int* which;
+  int* iter_num;
+  int* use_node_num;
+  int* n_nodes;
+  int* shot;
+  int* seg_num;
+  int* n_samples;
+  int* skip;                // [n] 0: ts / samples / derivs hold a path, 1: they do not (the fit leaves the candidate)
+  double* t_shot;
+  double* coef_shot;        // [n][3][4]
+  double* T_sum;
+  double* ts_out;
+  double* samples;          // [n][max_samples][3]
+  double* derivs;           // [n][4][3]
+  double* node_state;       // [n][max_path_nodes][6] or null
+  double* node_input;       // [n][max_path_nodes][3] or null
+  double* node_duration;    // [n][max_path_nodes] or null
+};
 
 struct alignas(16) KNode {
   double st[6];

@@ -1,10 +1,47 @@
-// spline_internal.h -- NonUniformBspline's evaluation on the device, shared by the kernels that evaluate a uniform
-// spline (yaw_plan.hip, traj_check.hip, traj_sample.hip).  f64, the reference's operations in the reference's order.
+// spline_internal.h -- NonUniformBspline's evaluation on the device, shared by the kernels that read a batch of uniform
+// position splines (yaw_plan.hip, traj_check.hip, traj_sample.hip, traj_adjust.hip): where a problem's spline lies, its
+// knots, its evaluation.  f64, the reference's operations in the reference's order.
 #ifndef FUELMI_SPLINE_INTERNAL_H_
 #define FUELMI_SPLINE_INTERNAL_H_
 
+#include <cstddef>
+
+// the position splines of a batch of problems, as the four kernels read them
+struct SplineSrc {
+  const int* n_ctrl;        // [n], or null: every problem has n_ctrl_all control points
+  int n_ctrl_all;
+  const double* pos;        // problem b: [n_ctrl][3] at pos + b * pos_stride
+  size_t pos_stride;
+  const double* knot;       // problem b: knot[b * knot_stride]
+  size_t knot_stride;
+};
+
+// problem b of a batch: its number of control points, its knot span, its control points [n][3].  Three reads, so that a
+// kernel makes each where it needs it (the first two load, and only for a b below n_prob).
+__device__ __forceinline__ int spline_n(const SplineSrc& s, int b) { return s.n_ctrl ? s.n_ctrl[b] : s.n_ctrl_all; }
+__device__ __forceinline__ double spline_dt(const SplineSrc& s, int b) { return s.knot[(size_t)b * s.knot_stride]; }
+__device__ __forceinline__ const double* spline_ctrl(const SplineSrc& s, int b) { return s.pos + (size_t)b * s.pos_stride; }
+
+// what a kernel asks of a problem before it indexes anything by it.  (The host refuses the others before any launch
+// wherever it sees them; the variables of a device batch it does not see.)
+__device__ __forceinline__ bool spline_sane(double dt, int n, int p, int max_ctrl) {
+  return dt > 0.0 && isfinite(dt) && n >= p + 1 && n <= max_ctrl;
+}
+
 // doubles of one wave's knot block in LDS: n + p + 1 <= max_ctrl + 6 knots, kept a multiple of 16 bytes
 __host__ __device__ inline int spline_knot_stride(int max_ctrl) { return (max_ctrl + 6 + 1) & ~1; }
+
+// setUniformBspline's knots (non_uniform_bspline.cpp:25-31): u[0 .. n + p] of a spline of degree p with n control
+// points and the span dt.  The knots behind u[p] are a running sum, not i * dt: every result is bit-equal to the
+// reference's only in this order.
+__device__ __forceinline__ void spline_uniform_knots(double* u, int p, int n, double dt) {
+  for (int i = 0; i <= p; ++i) u[i] = (double)(i - p) * dt;
+  double acc = u[p];
+  for (int i = p + 1; i <= n + p; ++i) {
+    acc = acc + dt;
+    u[i] = acc;
+  }
+}
 
 // the clamp and the knot search of evaluateDeBoor (non_uniform_bspline.cpp:52-57) for evaluateDeBoorT(t) of a spline of
 // degree p with n control points and the knots u[0 .. n + p]: returns the span k, ub = the clamped parameter.  Every

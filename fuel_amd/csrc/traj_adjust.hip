@@ -18,7 +18,6 @@
 #include <vector>
 
 #include "bspline_batch.h"
-#include "spline_internal.h"
 
 // the lanes of one wave meet: what every lane wrote to the wave's LDS block before is what every lane reads behind
 __device__ __forceinline__ void ta_wave_sync() {
@@ -349,10 +348,9 @@ __global__ void __launch_bounds__(TA_WIN * TA_MAX_WAVES) k_traj_adjust(TrajAdjAr
   double* u = reinterpret_cast<double*>(smem_raw) + (size_t)wv * ta_wave_stride(cfg.max_ctrl);  // [n + p + 1]
   double* P = u + spline_knot_stride(cfg.max_ctrl);                                               // [n][3]
   const int p = cfg.degree, kstride = cfg.max_ctrl + p + 1;
-  const int n = A.src.n_ctrl ? A.src.n_ctrl[b] : A.src.n_ctrl_all;
-  const double dt = A.knots_in ? 1.0 : A.src.knot[(size_t)b * A.src.knot_stride];
-  // (the host refuses these before any launch wherever it sees them; the variables of a device batch it does not see)
-  const bool sane = dt > 0.0 && isfinite(dt) && n >= p + 1 && n <= cfg.max_ctrl;
+  const int n = spline_n(A.src, b);
+  const double dt = A.knots_in ? 1.0 : spline_dt(A.src, b);
+  const bool sane = spline_sane(dt, n, p, cfg.max_ctrl);
   int* info = A.info + (size_t)b * FUELMI_TRAJADJ_NI;
   double* met = A.metrics + (size_t)b * FUELMI_TRAJADJ_NM;
   double* ko = A.knots_out + (size_t)b * kstride;
@@ -369,18 +367,13 @@ __global__ void __launch_bounds__(TA_WIN * TA_MAX_WAVES) k_traj_adjust(TrajAdjAr
 
   // a. control points and knots into the wave's block
   {
-    const double* src = A.src.pos + (size_t)b * A.src.pos_stride;
+    const double* src = spline_ctrl(A.src, b);
     for (int j = lane; j < 3 * n; j += TA_WIN) P[j] = src[j];
     if (A.knots_in) {
       const double* kin = A.knots_in + (size_t)b * kstride;
       for (int j = lane; j <= m; j += TA_WIN) u[j] = kin[j];
-    } else if (lane == 0) {  // setUniformBspline's knots (:25-31)
-      for (int i = 0; i <= p; ++i) u[i] = (double)(i - p) * dt;
-      double acc = u[p];
-      for (int i = p + 1; i <= m; ++i) {
-        acc = acc + dt;
-        u[i] = acc;
-      }
+    } else if (lane == 0) {
+      spline_uniform_knots(u, p, n, dt);
     }
   }
   ta_wave_sync();
@@ -526,11 +519,7 @@ struct TrajAdjIO {
 size_t ta_layout(const fuelmi_trajadj_cfg& c, int n_prob, bool host_spline, const TrajAdjIO& io, TrajAdjArgs& A, unsigned char* base) {
   const size_t n = (size_t)n_prob, ks = (size_t)c.max_ctrl + c.degree + 1;
   BlockLayout L(base, 16);
-  if (host_spline) {
-    A.src.n_ctrl = L.take<int>(n), A.src.n_ctrl_all = 0;
-    A.src.knot = L.take<double>(n), A.src.knot_stride = 1;
-    A.src.pos = L.take<double>(n * c.max_ctrl * 3), A.src.pos_stride = (size_t)c.max_ctrl * 3;
-  }
+  if (host_spline) spline_src_take(L, n, c.max_ctrl, A.src);
   A.knots_in = io.knots_in ? L.take<double>(n * ks) : nullptr;
   A.ratio_in = io.ratio_in ? L.take<double>(n) : nullptr;
   A.group = (c.ops & FUELMI_TRAJADJ_SELECT) ? L.take<int>(n) : nullptr;
@@ -559,13 +548,8 @@ int trajadj_check(const fuelmi_trajadj_cfg* cfg, int n_prob, bool host_spline, i
   if (cfg->ops & FUELMI_TRAJADJ_RESAMPLE) ARGCHK(io.samples);
   if (cfg->ops & FUELMI_TRAJADJ_SELECT) ARGCHK(io.group && io.best);
   if (host_spline) {
-    ARGCHK(io.n_ctrl && io.pos_ctrl && (io.knot_span || io.knots_in));
-    for (int b = 0; b < n_prob; ++b) {
-      ARGCHK(io.n_ctrl[b] >= p + 1 && io.n_ctrl[b] <= cfg->max_ctrl);
-      if (!io.knots_in) ARGCHK(std::isfinite(io.knot_span[b]) && io.knot_span[b] > 0.0);
-      const double* P = io.pos_ctrl + (size_t)b * cfg->max_ctrl * 3;
-      for (int k = 0; k < 3 * io.n_ctrl[b]; ++k) ARGCHK(std::fabs(P[k]) < 1e7);
-    }
+    const int rc = spline_src_check(n_prob, p, cfg->max_ctrl, io.n_ctrl, io.pos_ctrl, io.knot_span, io.knots_in != nullptr);
+    if (rc) return rc;
   }
   if (io.knots_in) {
     const size_t ks = (size_t)cfg->max_ctrl + p + 1;
@@ -603,13 +587,9 @@ int trajadj_run(hipStream_t st, const fuelmi_trajadj_cfg* cfg, int n_prob, bool 
   auto down = [&](void* dst, const void* src, size_t bytes) {
     return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
   };
-  if (host_spline) {
-    HIPCHK(up(A.src.n_ctrl, io.n_ctrl, n * sizeof(int)));
-    if (io.knot_span)
-      HIPCHK(up(A.src.knot, io.knot_span, n * sizeof(double)));
-    else
-      HIPCHK(hipMemsetAsync(const_cast<double*>(A.src.knot), 0, n * sizeof(double), st));  // (not read with knots_in)
-    HIPCHK(up(A.src.pos, io.pos_ctrl, n * c.max_ctrl * 3 * sizeof(double)));
+  if (host_spline) {  // (knot_span may be null with knots_in: the kernel does not read the spans then)
+    const int rc = spline_src_upload(st, A.src, n, c.max_ctrl, io.n_ctrl, io.pos_ctrl, io.knot_span);
+    if (rc) return rc;
   }
   if (A.knots_in) HIPCHK(up(A.knots_in, io.knots_in, n * ks * sizeof(double)));
   if (A.ratio_in) HIPCHK(up(A.ratio_in, io.ratio_in, n * sizeof(double)));

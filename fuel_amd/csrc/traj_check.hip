@@ -22,14 +22,30 @@
 #include <vector>
 
 #include "bspline_batch.h"
-#include "frontier_internal.h"
-#include "spline_internal.h"
 
 namespace {
 
 constexpr int TC_WIN = 64;   // samples per window: one per lane
 constexpr int TC_WAVES = 4;  // problems per workgroup
 constexpr int TC_CAP = FUELMI_TRAJCHK_MAX_SAMPLES;
+
+// k_traj_check: one problem per wave; every pointer addresses device memory
+struct TrajChkArgs {
+  fuelmi_trajchk_cfg cfg;
+  int n_prob;
+  SplineSrc src;
+  const double* t_now;      // [n]
+  const u64* infl;          // the map's inflated plane
+  int* status;
+  int* safe;
+  int* n_samples;
+  int* hit_index;
+  int* end_reason;
+  double* distance;
+  double* hit_t;
+  double* duration;
+  double* hit_pos;          // [n][3]
+};
 
 // not finite, or |coordinate| >= 1e7: the reference's cast to int is undefined there
 __device__ __forceinline__ bool tc_bad(const double q[3]) {
@@ -73,21 +89,13 @@ __global__ void __launch_bounds__(TC_WIN * TC_WAVES) k_traj_check(Geo g, TrajChk
   int n = 0;
   double dt = 0.0;
   if (live) {
-    n = T.src.n_ctrl ? T.src.n_ctrl[b] : T.src.n_ctrl_all;
-    dt = T.src.knot[(size_t)b * T.src.knot_stride];
+    n = spline_n(T.src, b);
+    dt = spline_dt(T.src, b);
   }
-  // (the host route refuses these before any launch; the variables of a device batch are not seen by the host)
-  const bool sane = live && dt > 0.0 && isfinite(dt) && n >= p + 1 && n <= T.cfg.max_ctrl;
+  const bool sane = live && spline_sane(dt, n, p, T.cfg.max_ctrl);
 
-  // 1. knots (setUniformBspline :25-31); every wave of the workgroup meets at the barrier, with or without a problem
-  if (sane && lane == 0) {
-    for (int i = 0; i <= p; ++i) u[i] = (double)(i - p) * dt;
-    double acc = u[p];
-    for (int i = p + 1; i <= n + p; ++i) {
-      acc = acc + dt;
-      u[i] = acc;
-    }
-  }
+  // 1. knots; every wave of the workgroup meets at the barrier, with or without a problem
+  if (sane && lane == 0) spline_uniform_knots(u, p, n, dt);
   __syncthreads();
   if (!live) return;
   if (!sane) {
@@ -95,7 +103,7 @@ __global__ void __launch_bounds__(TC_WIN * TC_WAVES) k_traj_check(Geo g, TrajChk
       tc_write(T, b, FUELMI_TRAJCHK_NONFINITE, 0, 0.0, 0, 0, 0.0, nullptr, FUELMI_TRAJCHK_END_NONFINITE, 0.0);
     return;
   }
-  const double* C = T.src.pos + (size_t)b * T.src.pos_stride;
+  const double* C = spline_ctrl(T.src, b);
   const double t_now = T.t_now[b], step = T.cfg.step, max_radius = T.cfg.max_radius;
   const double duration = u[n] - u[p];
 
@@ -182,13 +190,8 @@ int trajchk_check(const fuelmi_trajchk_cfg* cfg, int n_prob, const TrajChkIO& io
   ARGCHK(io.t_now);
   for (int b = 0; b < n_prob; ++b) ARGCHK(std::isfinite(io.t_now[b]));
   if (io.n_ctrl) {  // (a device batch: its variables are checked by the kernel)
-    ARGCHK(io.pos_ctrl && io.knot_span);
-    for (int b = 0; b < n_prob; ++b) {
-      ARGCHK(io.n_ctrl[b] >= cfg->degree + 1 && io.n_ctrl[b] <= cfg->max_ctrl);
-      ARGCHK(std::isfinite(io.knot_span[b]) && io.knot_span[b] > 0.0);
-      const double* P = io.pos_ctrl + (size_t)b * cfg->max_ctrl * 3;
-      for (int k = 0; k < 3 * io.n_ctrl[b]; ++k) ARGCHK(std::fabs(P[k]) < 1e7);
-    }
+    const int rc = spline_src_check(n_prob, cfg->degree, cfg->max_ctrl, io.n_ctrl, io.pos_ctrl, io.knot_span);
+    if (rc) return rc;
   }
   ARGCHK(io.status && io.safe && io.distance && io.n_samples && io.hit_index && io.hit_t && io.hit_pos && io.end_reason &&
          io.duration);
@@ -271,19 +274,16 @@ extern "C" int fuelmi_map_check_trajs(fuelmi_map* m, const fuelmi_trajchk_cfg* c
   ARGCHK(m);
   HIPCHK(hipSetDevice(m->device));
   hipStream_t st = m->stream;
-  const size_t n = (size_t)n_prob, maxc = (size_t)cfg->max_ctrl;
+  const size_t n = (size_t)n_prob;
   TrajChkArgs T;
   memset(&T, 0, sizeof(T));
   const size_t b_out = trajchk_out_bytes(n_prob, T, nullptr);
-  int* d_nc;
-  double *d_knot, *d_now, *d_pos;
+  double* d_now;
   unsigned char* d_out;
   auto layout = [&](unsigned char* base) {
     BlockLayout L(base, 16);
-    d_nc = L.take<int>(n);
-    d_knot = L.take<double>(n);
+    spline_src_take(L, n, cfg->max_ctrl, T.src);
     d_now = L.take<double>(n);
-    d_pos = L.take<double>(n * maxc * 3);
     d_out = L.take<unsigned char>(b_out);
     return L.size();
   };
@@ -292,13 +292,13 @@ extern "C" int fuelmi_map_check_trajs(fuelmi_map* m, const fuelmi_trajchk_cfg* c
     if (rc) return rc;
   }
   layout(m->trajchk_dev.base());
-  HIPCHK(hipMemcpyAsync(d_nc, n_ctrl, n * sizeof(int), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_knot, knot_span, n * sizeof(double), hipMemcpyHostToDevice, st));
+  {
+    const int rc = spline_src_upload(st, T.src, n, cfg->max_ctrl, n_ctrl, pos_ctrl, knot_span);
+    if (rc) return rc;
+  }
   HIPCHK(hipMemcpyAsync(d_now, t_now, n * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_pos, pos_ctrl, n * maxc * 3 * sizeof(double), hipMemcpyHostToDevice, st));
   T.cfg = *cfg;
   T.n_prob = n_prob;
-  T.src = {d_nc, 0, d_pos, maxc * 3, d_knot, 1};
   T.t_now = d_now;
   return trajchk_run(m, T, d_out, io);
 }

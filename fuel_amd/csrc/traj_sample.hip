@@ -21,25 +21,32 @@
 #include <vector>
 
 #include "bspline_batch.h"
-#include "spline_internal.h"
 
 namespace {
 
 constexpr int TS_WIN = 64;   // samples per window: one per lane
 constexpr int TS_WAVES = 3;  // problems per workgroup: two knot blocks each, 48.4 KiB at the largest strides
 
+// k_traj_sample: one problem per wave; every pointer addresses device memory
+struct TrajSmpArgs {
+  fuelmi_trajsmp_cfg cfg;
+  int n_prob;
+  SplineSrc src;
+  const int* n_yaw;         // [n] (0: that problem has no yaw spline), or null: none has
+  const double* yaw;        // [n][max_yaw_ctrl]
+  const double* yaw_dt;     // [n]
+  const double* t_stop;     // [n] or null
+  const int* n_t;           // [n]
+  const double* t;          // [n][max_t]
+  double* flight;           // [n][8] in and out, or null
+  int* status;              // [n][max_t]
+  double *o_pos, *o_vel, *o_acc, *o_jerk;  // [n][max_t][3]
+  double *o_yaw, *o_yawdot, *o_yawddot;    // [n][max_t]
+  double* duration;         // [n]
+};
+
 __host__ __device__ inline int ts_wave_stride(const fuelmi_trajsmp_cfg& c) {
   return spline_knot_stride(c.max_ctrl) + (c.max_yaw_ctrl > 0 ? spline_knot_stride(c.max_yaw_ctrl) : 0);
-}
-
-// setUniformBspline's knots (non_uniform_bspline.cpp:25-31)
-__device__ inline void ts_knots(double* u, int p, int n, double dt) {
-  for (int i = 0; i <= p; ++i) u[i] = (double)(i - p) * dt;
-  double acc = u[p];
-  for (int i = p + 1; i <= n + p; ++i) {
-    acc = acc + dt;
-    u[i] = acc;
-  }
 }
 
 // the spline of degree PD on the points q of span k, then LEVELS derivatives of it: out[0 .. LEVELS].  A derivative of
@@ -84,19 +91,18 @@ __global__ void __launch_bounds__(TS_WIN * TS_WAVES) k_traj_sample(TrajSmpArgs A
   int n = 0, ny = 0;
   double dt = 0.0, dty = 0.0;
   if (live) {
-    n = A.src.n_ctrl ? A.src.n_ctrl[b] : A.src.n_ctrl_all;
-    dt = A.src.knot[(size_t)b * A.src.knot_stride];
+    n = spline_n(A.src, b);
+    dt = spline_dt(A.src, b);
     if (A.n_yaw && A.cfg.max_yaw_ctrl > 0) ny = A.n_yaw[b];
     if (ny > 0) dty = A.yaw_dt[b];
   }
-  // (the host refuses these before any launch wherever it sees them; the variables of a device batch it does not see)
-  const bool sane = live && dt > 0.0 && isfinite(dt) && n >= p + 1 && n <= A.cfg.max_ctrl &&
+  const bool sane = live && spline_sane(dt, n, p, A.cfg.max_ctrl) &&
                     (ny <= 0 || (dty > 0.0 && isfinite(dty) && py >= 3 && py <= 5 && ny >= py + 1 && ny <= A.cfg.max_yaw_ctrl));
 
   // 1. knots; every wave of the workgroup meets at the barrier, with or without a problem
   if (sane && lane == 0) {
-    ts_knots(u, p, n, dt);
-    if (ny > 0) ts_knots(uy, py, ny, dty);
+    spline_uniform_knots(u, p, n, dt);
+    if (ny > 0) spline_uniform_knots(uy, py, ny, dty);
   }
   __syncthreads();
   if (!live) return;
@@ -110,7 +116,7 @@ __global__ void __launch_bounds__(TS_WIN * TS_WAVES) k_traj_sample(TrajSmpArgs A
     const double ts = A.t_stop[b];
     T = D < ts ? D : ts;
   }
-  const double* C = A.src.pos + (size_t)b * A.src.pos_stride;
+  const double* C = spline_ctrl(A.src, b);
   const double* Cy = ny > 0 ? A.yaw + (size_t)b * A.cfg.max_yaw_ctrl : nullptr;
   const bool record = command && A.flight && sane;
   double* F = A.flight ? A.flight + (size_t)b * 8 : nullptr;
@@ -255,11 +261,7 @@ size_t ts_layout(const fuelmi_trajsmp_cfg& c, int n_prob, bool host_spline, cons
                  unsigned char* base) {
   const size_t n = (size_t)n_prob, s = n * (size_t)c.max_t;
   BlockLayout L(base, 16);
-  if (host_spline) {
-    A.src.n_ctrl = L.take<int>(n), A.src.n_ctrl_all = 0;
-    A.src.knot = L.take<double>(n), A.src.knot_stride = 1;
-    A.src.pos = L.take<double>(n * c.max_ctrl * 3), A.src.pos_stride = (size_t)c.max_ctrl * 3;
-  }
+  if (host_spline) spline_src_take(L, n, c.max_ctrl, A.src);
   const bool yaw = io.n_yaw_ctrl && c.max_yaw_ctrl > 0;
   A.n_yaw = yaw ? L.take<int>(n) : nullptr;
   A.yaw = yaw ? L.take<double>(n * c.max_yaw_ctrl) : nullptr;
@@ -297,13 +299,8 @@ int trajsmp_check(const fuelmi_trajsmp_cfg* cfg, int n_prob, bool host_spline, c
   const int p = cfg->degree, py = cfg->yaw_degree;
   if (cfg->mode == FUELMI_TRAJSMP_STATE) ARGCHK(!io.t_stop && !io.flight);  // cmdCallback's alone
   if (host_spline) {
-    ARGCHK(io.n_ctrl && io.pos_ctrl && io.knot_span);
-    for (int b = 0; b < n_prob; ++b) {
-      ARGCHK(io.n_ctrl[b] >= p + 1 && io.n_ctrl[b] <= cfg->max_ctrl);
-      ARGCHK(std::isfinite(io.knot_span[b]) && io.knot_span[b] > 0.0);
-      const double* P = io.pos_ctrl + (size_t)b * cfg->max_ctrl * 3;
-      for (int k = 0; k < 3 * io.n_ctrl[b]; ++k) ARGCHK(std::fabs(P[k]) < 1e7);
-    }
+    const int rc = spline_src_check(n_prob, p, cfg->max_ctrl, io.n_ctrl, io.pos_ctrl, io.knot_span);
+    if (rc) return rc;
   }
   if (io.n_yaw_ctrl) {
     ARGCHK(cfg->max_yaw_ctrl > 0 && io.yaw_ctrl && io.yaw_dt);
@@ -350,9 +347,8 @@ int trajsmp_run(hipStream_t st, const fuelmi_trajsmp_cfg* cfg, int n_prob, bool 
     return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
   };
   if (host_spline) {
-    HIPCHK(up(A.src.n_ctrl, io.n_ctrl, n * sizeof(int)));
-    HIPCHK(up(A.src.knot, io.knot_span, n * sizeof(double)));
-    HIPCHK(up(A.src.pos, io.pos_ctrl, n * c.max_ctrl * 3 * sizeof(double)));
+    const int rc = spline_src_upload(st, A.src, n, c.max_ctrl, io.n_ctrl, io.pos_ctrl, io.knot_span);
+    if (rc) return rc;
   }
   if (A.n_yaw) {
     HIPCHK(up(A.n_yaw, io.n_yaw_ctrl, n * sizeof(int)));

@@ -40,6 +40,28 @@ namespace {
 constexpr int WT_NT = 256;
 constexpr int WT_LEN_CAP = 1 << 21;  // length samples: the host admits duration <= FUELMI_WPTRAJ_MAX_DURATION only
 
+// k_waypoint_traj: one problem per workgroup; every pointer addresses memory the device can reach
+struct WpTrajArgs {
+  int n_prob;
+  const int* n_way;    // [n]
+  const double* way;   // [n][maxw][3]
+  const double* vel;   // [n][3]
+  const double* acc;   // [n][3]
+  int maxw;
+  double max_vel, ctrl_pt_dist;
+  int min_seg, forced_seg, max_samples;
+  int* status;
+  double* duration;
+  double* length;
+  int* seg_num;
+  double* dt;
+  int* n_samples;
+  double* samples;     // [n][max_samples][3]
+  double* derivs;      // [n][4][3]
+  double* seg_times;   // [n][maxw-1] or null
+  double* coef;        // [n][maxw-1][3][6] or null
+};
+
 // PolynomialTraj::evaluate(t, k): the lookup (idx clamped to the last segment), then tv . c with
 // tv[i] = i (i-1) .. (i-k+1) ts^(i-k), summed from the lowest power
 __device__ __forceinline__ void wt_eval(const double* cf, const double* T, int S, double t, int k, double out[3]) {

@@ -25,12 +25,32 @@
 #include <vector>
 
 #include "bspline_batch.h"
-#include "spline_internal.h"
 
 namespace {
 
 constexpr int YP_NT = 64;
 constexpr double YP_PI = 3.14159265358979323846;  // M_PI
+
+// k_yaw_plan: one problem per wave; every pointer addresses memory the device can reach
+struct YawArgs {
+  fuelmi_yaw_cfg cfg;
+  double ld_smooth, ld_start, ld_end, ld_waypt;
+  int n_prob;
+  SplineSrc src;
+  const double* start_yaw;  // [n][3]
+  const double* end_yaw;    // [n] (EXPLORE)
+  int* status;
+  int* seg_num;
+  int* n_waypt;
+  double* duration;
+  double* dt_yaw;
+  double* end_yaw_out;
+  double* cost;
+  double* yaw_ctrl;         // [n][max_seg + 3]
+  double* waypts;           // [n][max_seg]
+  double* yawdot_ctrl;      // [n][max_seg + 2] or null
+  double* yawddot_ctrl;     // [n][max_seg + 1] or null
+};
 
 __host__ __device__ inline int yp_knots(int max_ctrl, int max_seg) {  // position knots n + p + 1 <= max_ctrl + 6; yaw knots N + p + 1
   return max_ctrl + 6 > max_seg + 9 ? max_ctrl + 6 : max_seg + 9;
@@ -119,24 +139,16 @@ __global__ void __launch_bounds__(YP_NT) k_yaw_plan(YawArgs Y) {
 
   const bool follow = Y.cfg.mode == FUELMI_YAW_FOLLOW;
   const int p = Y.cfg.pos_degree;
-  const int n = Y.src.n_ctrl ? Y.src.n_ctrl[b] : Y.src.n_ctrl_all;
-  const double dt = Y.src.knot[(size_t)b * Y.src.knot_stride];
-  const double* C = Y.src.pos + (size_t)b * Y.src.pos_stride;
-  // (the host route refuses these before any launch; the variables of a device batch are not seen by the host)
-  if (!(dt > 0.0) || !isfinite(dt) || n < p + 1 || n > Y.cfg.max_ctrl) {
+  const int n = spline_n(Y.src, b);
+  const double dt = spline_dt(Y.src, b);
+  const double* C = spline_ctrl(Y.src, b);
+  if (!spline_sane(dt, n, p, Y.cfg.max_ctrl)) {
     yp_write(Y, b, tid, FUELMI_YAW_DEGENERATE, 0.0, 0, 0.0, 0, nullptr, 0, nullptr, 0.0, 0.0, nullptr, 3);
     return;
   }
 
-  // 1. knots (setUniformBspline :25-31), duration = getTimeSum
-  if (tid == 0) {
-    for (int i = 0; i <= p; ++i) u[i] = (double)(i - p) * dt;
-    double acc = u[p];
-    for (int i = p + 1; i <= n + p; ++i) {
-      acc = acc + dt;
-      u[i] = acc;
-    }
-  }
+  // 1. knots, duration = getTimeSum
+  if (tid == 0) spline_uniform_knots(u, p, n, dt);
   __syncthreads();
   const double duration = u[n] - u[p];
 
@@ -345,14 +357,7 @@ __global__ void __launch_bounds__(YP_NT) k_yaw_plan(YawArgs Y) {
   // 7. the yaw spline's knots: setUniformBspline(yaw, 3, dt_yaw) in planYawExplore, (yaw, bspline_degree_, dt_yaw) in
   // planYaw; then everything is written side by side
   const int py = follow ? p : 3;
-  if (tid == 0) {
-    for (int i = 0; i <= py; ++i) u[i] = (double)(i - py) * dt_yaw;
-    double acc = u[py];
-    for (int i = py + 1; i <= N + py; ++i) {
-      acc = acc + dt_yaw;
-      u[i] = acc;
-    }
-  }
+  if (tid == 0) spline_uniform_knots(u, py, N, dt_yaw);
   __syncthreads();
   yp_write(Y, b, tid, degenerate ? FUELMI_YAW_DEGENERATE : FUELMI_YAW_OK, duration, seg, dt_yaw, N, degenerate ? q0 : g,
            nw, wp, e, cost, u, py);
@@ -408,13 +413,8 @@ int yaw_check(const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob
     if (cfg->mode == FUELMI_YAW_EXPLORE) ARGCHK(std::fabs(io.end_yaw[b]) <= 1e3);
   }
   if (io.n_ctrl) {  // (a device batch: its variables are checked by the kernel)
-    ARGCHK(io.pos_ctrl && io.knot_span);
-    for (int b = 0; b < n_prob; ++b) {
-      ARGCHK(io.n_ctrl[b] >= cfg->pos_degree + 1 && io.n_ctrl[b] <= cfg->max_ctrl);
-      ARGCHK(std::isfinite(io.knot_span[b]) && io.knot_span[b] > 0.0);
-      const double* P = io.pos_ctrl + (size_t)b * cfg->max_ctrl * 3;
-      for (int k = 0; k < 3 * io.n_ctrl[b]; ++k) ARGCHK(std::fabs(P[k]) < 1e7);
-    }
+    const int rc = spline_src_check(n_prob, cfg->pos_degree, cfg->max_ctrl, io.n_ctrl, io.pos_ctrl, io.knot_span);
+    if (rc) return rc;
   }
   ARGCHK(io.status && io.duration && io.seg_num && io.dt_yaw && io.yaw_ctrl && io.n_waypt && io.waypts &&
          io.end_yaw_out && io.cost);

@@ -1,45 +1,31 @@
-"""Builds k_kino_path's own text for the host (tests/golden/kino_golden/host_kernel.cpp: a thread per lane, a barrier for
-__syncthreads, glibc's libm, the undefined-behaviour sanitizer) and compares what it writes for every recorded scene with
+"""Builds k_kino_path's own text for the host (tests/golden/kino_golden/host_kernel.cpp on tests/golden/host_lanes.h: a
+thread per lane, glibc's libm, the undefined-behaviour sanitizer) and compares what it writes for every recorded scene with
 what the reference's KinodynamicAstar wrote: the two output files must be identical byte for byte (every double is
 printed as a hexadecimal float), except the close-goal problem the manager refuses before the search.  Run
 tests/golden/make_kino_golden.py first: it leaves the inputs and the reference's outputs under build/kino_golden/.
-Needs g++ with C++20 and the HIP headers (ROCM_PATH, default /opt/rocm) for the shared declarations; no GPU."""
+The cut, the build and the run are tests/golden/host_build.py's."""
 import glob
 import os
-import subprocess
 import sys
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-OUT = os.path.join(ROOT, "build", "kino_golden")
+import host_build as hb
 
 
 def build():
-    src = open(os.path.join(ROOT, "fuel_amd", "csrc", "kino_path.hip")).read()
-    text = src[src.index("namespace {") + len("namespace {"):src.index("bool pos_fin(")]
-    os.makedirs(OUT, exist_ok=True)
-    with open(os.path.join(OUT, "kernel.inc"), "w") as f:
-        f.write(text)
-    exe = os.path.join(OUT, "host_kernel")
-    subprocess.check_call(["g++", "-O1", "-std=c++20", "-ffp-contract=off", "-fsanitize=undefined", "-w",
-                           "-I", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include"),
-                           "-I", os.path.join(ROOT, "fuel_amd", "csrc"), "-I", OUT,
-                           os.path.join(HERE, "kino_golden", "host_kernel.cpp"), "-o", exe, "-lpthread"])
-    return exe
+    return hb.compile("kino", hb.cut("kino_path.hip", "namespace {", "bool pos_fin(", keep_start=False), sanitizers="undefined")
 
 
 def main():
     exe = build()
-    ins = sorted(glob.glob(os.path.join(OUT, "*.in")))
+    ins = sorted(glob.glob(os.path.join(hb.out_dir("kino"), "*.in")))
     if not ins:
         raise SystemExit("no inputs under build/kino_golden/: run tests/golden/make_kino_golden.py first")
     bad = 0
     for path in ins:
         base = path[:-3]
         name = os.path.basename(base)
-        p = subprocess.run([exe, path, base + ".infl", base + ".unk", base + ".host"], capture_output=True, text=True)
-        if p.returncode or p.stderr.strip():
-            print(name, "FAILED", p.returncode, p.stderr[-500:])
+        if hb.run(exe, [path, base + ".infl", base + ".unk", base + ".host"], fatal=False) is None:
+            print(name, "FAILED")
             bad += 1
             continue
         ref, got = open(base + ".out").read().splitlines(), open(base + ".host").read().splitlines()

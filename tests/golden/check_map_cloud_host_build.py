@@ -1,23 +1,21 @@
-"""Builds the cloud kernels' own text for the host (tests/golden/map_cloud_golden/host_kernel.cpp: a thread per lane, a
-barrier for __syncthreads, exchanges for the wave operations, every array a heap block of its exact size, one margin word
+"""Builds the cloud kernels' own text for the host (tests/golden/map_cloud_golden/host_kernel.cpp on
+tests/golden/host_lanes.h: a thread per lane, every array a heap block of its exact size, one margin word
 behind each plane) as a stand-alone program with the address and the undefined-behaviour sanitizers, runs it once on every
 scene of tests/map_cloud_cases.py with every kind -- plus the cap scenes, whose buffers must keep their fill behind the
 points, and map E's full box, whose scan takes two rounds -- and compares counts and points with the restatement
 (tests/map_cloud_ref.py) bit for bit.  The planes are packed here from the scenes' log-odds with the comparisons of
-k_state_planes, which is not under test.  Everything stays under build/map_cloud_golden/.  Needs g++ with C++20 and the
-HIP headers (ROCM_PATH, default /opt/rocm) for the shared declarations; no GPU.  `--quick` leaves map E out."""
+k_state_planes, which is not under test.  Everything stays under build/map_cloud_golden/; the cut, the build and
+the run are tests/golden/host_build.py's.  `--quick` leaves map E out."""
 import os
 import struct
-import subprocess
 import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-OUT = os.path.join(ROOT, "build", "map_cloud_golden")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, ROOT)
+import host_build as hb
+
+sys.path.insert(0, os.path.join(hb.ROOT, "tests"))
+sys.path.insert(0, hb.ROOT)
 
 import map_cloud_cases as mc  # noqa: E402
 import map_cloud_ref as mr  # noqa: E402
@@ -26,21 +24,7 @@ FILL = b"\xA5\xA5\xA5\xA5"
 
 
 def build():
-    src = open(os.path.join(ROOT, "fuel_amd", "csrc", "map_cloud.hip")).read()
-    hdr = open(os.path.join(ROOT, "fuel_amd", "csrc", "fuelmi_internal.h")).read()
-    a = hdr.index("__device__ __forceinline__ u64 plane_window(")
-    text = hdr[a:hdr.index("__device__ __forceinline__ u64 bit_range(")]
-    text += src[src.index("namespace {"):src.index("// the geometry of a box:")]
-    os.makedirs(OUT, exist_ok=True)
-    with open(os.path.join(OUT, "kernel.inc"), "w") as f:
-        f.write(text)
-    exe = os.path.join(OUT, "host_kernel")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++20", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-w",
-                           "-I", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include"),
-                           "-I", os.path.join(ROOT, "fuel_amd", "csrc"), "-I", OUT,
-                           os.path.join(HERE, "map_cloud_golden", "host_kernel.cpp"), "-o", exe, "-lpthread"])
-    return exe
+    return hb.compile("map_cloud", hb.cut("map_cloud.hip", "namespace {", "// the geometry of a box:"))
 
 
 def pack(bits3):
@@ -79,7 +63,7 @@ def main():
         sc = mc.scene("map_e", "e", "e", *mc.full_box(e.nvox))
         jobs.append((si, sc, mr.OCCUPIED, 1 << 40, e, occ, infl))
         jobs.append((si, sc, mr.KNOWN, 1000, e, occ, infl))
-    p_planes, p_scenes, p_out = (os.path.join(OUT, n) for n in ("planes.bin", "scenes.txt", "out.bin"))
+    p_planes, p_scenes, p_out = (os.path.join(hb.out_dir("map_cloud"), n) for n in ("planes.bin", "scenes.txt", "out.bin"))
     with open(p_planes, "wb") as f:
         f.write(struct.pack("<i", len(blobs)) + b"".join(blobs))
     with open(p_scenes, "w") as f:
@@ -87,10 +71,7 @@ def main():
         for si, sc, kind, cap, *_ in jobs:
             f.write("%d %d %d %d %d %d %d %d %s %s %d\n" % ((si, kind) + sc["lo"] + sc["hi"]
                                                             + (float(sc["z_low"]).hex(), float(sc["z_high"]).hex(), cap)))
-    p = subprocess.run([exe, p_planes, p_scenes, p_out], capture_output=True, text=True)
-    if p.returncode or p.stderr.strip():
-        print("FAILED", p.returncode, p.stdout[-300:], p.stderr[-3000:])
-        sys.exit(1)
+    hb.run(exe, [p_planes, p_scenes, p_out])
     raw = open(p_out, "rb").read()
     at, bad = 0, 0
     for si, sc, kind, cap, m, occ, infl in jobs:

@@ -1,56 +1,34 @@
-"""Builds k_traj_adjust's and k_traj_select's own text for the host (tests/golden/traj_adjust_golden/host_kernel.cpp: a
-thread per lane, a barrier for the wave's meeting point, an exchange for __shfl, guard zones round the LDS block) with the
-address and the undefined-behaviour sanitizers as a stand-alone program, runs it once on every scene of
+"""Builds k_traj_adjust's and k_traj_select's own text for the host (tests/golden/traj_adjust_golden/host_kernel.cpp on
+tests/golden/host_lanes.h: a thread per lane, guard zones round the LDS block) with the address and the
+undefined-behaviour sanitizers as a stand-alone program, runs it once on every scene of
 tests/traj_adjust_cases.py -- grouped into launches by degree, stages and configuration, so that problems of different
 sizes share workgroups, each launch with SELECT over three groups -- plus a launch laid out like a device batch with bad
 knot spans among good neighbours, and compares every output with the restatement (tests/traj_adjust_ref.py) bit for bit.
-Everything stays under build/traj_adjust_golden/.  Needs g++ with C++20 and the HIP headers (ROCM_PATH, default
-/opt/rocm) for the shared declarations; no GPU.  With an argument (a substring of scene tags) only those scenes run.
+Everything stays under build/traj_adjust_golden/; the cut, the build and the run are tests/golden/host_build.py's.  With
+an argument (a substring of scene tags) only those scenes run.
 
 The restatement takes norm() as the Eigen stand-in of compat/ does; against real Eigen's that is the project's standing
 caveat."""
 import os
-import struct
-import subprocess
 import sys
 
-import numpy as np
+import host_build as hb
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-OUT = os.path.join(ROOT, "build", "traj_adjust_golden")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(hb.ROOT, "tests"))
 
 import traj_adjust_cases as tc  # noqa: E402
 import traj_adjust_ref as ar  # noqa: E402
 
-DECL = "extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];"
-
 
 def build():
-    src = open(os.path.join(ROOT, "fuel_amd", "csrc", "traj_adjust.hip")).read()
-    text = src[src.index("namespace {"):src.index("int trajadj_cfg_check(")]
-    assert text.count(DECL) == 1
-    text = text.replace(DECL, "unsigned char* smem_raw = g_lds;")  # the one line that differs: the block's address
-    os.makedirs(OUT, exist_ok=True)
-    with open(os.path.join(OUT, "kernel.inc"), "w") as f:
-        f.write(text)
-    exe = os.path.join(OUT, "host_kernel")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++20", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-w",
-                           "-I", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include"),
-                           "-I", os.path.join(ROOT, "fuel_amd", "csrc"), "-I", OUT,
-                           os.path.join(HERE, "traj_adjust_golden", "host_kernel.cpp"), "-o", exe, "-lpthread"])
-    return exe
+    return hb.compile("traj_adjust", hb.lds_from_host(hb.cut("traj_adjust.hip", "namespace {", "int trajadj_cfg_check(")))
 
 
 def bits(v):
-    b = struct.unpack("<Q", struct.pack("<d", float(v)))[0]
-    return "%016x" % (0x7ff8000000000000 if v != v else b)  # (the sign of a generated NaN is the processor's choice)
+    return hb.bits(v, one_nan=True)
 
 
-def hexes(a):
-    return " ".join(float(v).hex() for v in np.asarray(a, dtype=np.float64).reshape(-1))
+hexes = hb.hexes
 
 
 def batch_scenes():
@@ -70,7 +48,7 @@ def main():
         launches.append(([s for s in scenes if s["tag"] in big], False))
     if not pick:
         launches.append((batch_scenes(), True))
-    path = os.path.join(OUT, "scenes.in")
+    path = os.path.join(hb.out_dir("traj_adjust"), "scenes.in")
     plan = []
     with open(path, "w") as f:
         f.write("%d\n" % len(launches))
@@ -92,11 +70,7 @@ def main():
                 if s["knots"] is not None:
                     f.write(hexes(s["knots"]) + "\n")
             plan.append((grp, group, maxc + p + 1, maxs))
-    proc = subprocess.run([exe, path], capture_output=True, text=True)
-    if proc.returncode or proc.stderr.strip():
-        print("FAILED", proc.returncode, proc.stdout[-300:], proc.stderr[-3000:])
-        sys.exit(1)
-    lines = proc.stdout.splitlines()
+    lines = hb.run(exe, [path]).splitlines()
     assert len(lines) == sum(4 * len(g) + 1 for g, _, _, _ in plan), (len(lines), len(plan))
     bad = at = count = 0
     for grp, group, ks, maxs in plan:
@@ -107,7 +81,7 @@ def main():
             info, met, ko, smp = tc.want_arrays(r, len(s["ctrl"]), s["degree"], ks, maxs)
             want = [" ".join(str(int(v)) for v in info), " ".join(bits(v) for v in met), " ".join(bits(v) for v in ko),
                     " ".join(bits(v) for v in smp.reshape(-1))]
-            got = [" ".join(bits(struct.unpack("<d", struct.pack("<Q", int(t, 16)))[0]) for t in ln.split()) if i else ln
+            got = [" ".join(bits(hb.from_bits(t)) for t in ln.split()) if i else ln
                    for i, ln in enumerate(lines[at:at + 4])]
             at += 4
             count += 1

@@ -1,46 +1,25 @@
-"""Builds k_traj_check's own text for the host (tests/golden/traj_check_golden/host_kernel.cpp: a thread per lane, a
-barrier for __syncthreads, exchanges for the wave operations, guard zones round the LDS block) with the address and the
+"""Builds k_traj_check's own text for the host (tests/golden/traj_check_golden/host_kernel.cpp on
+tests/golden/host_lanes.h: a thread per lane, guard zones round the LDS block) with the address and the
 undefined-behaviour sanitizers, runs it once on every scene of tests/traj_check_cases.py -- grouped into launches by map
 and configuration, so that problems of different sizes share workgroups -- and compares every output with the restatement
-(tests/traj_check_ref.py) bit for bit.  Everything stays under build/traj_check_golden/.  Needs g++ with C++20 and the HIP
-headers (ROCM_PATH, default /opt/rocm) for the shared declarations; no GPU.  `--long` adds the two 2^20-sample scenes."""
+(tests/traj_check_ref.py) bit for bit.  Everything stays under build/traj_check_golden/; the cut, the build and the run are
+tests/golden/host_build.py's.  `--long` adds the two 2^20-sample scenes."""
 import os
-import struct
-import subprocess
 import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-OUT = os.path.join(ROOT, "build", "traj_check_golden")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import host_build as hb
+from host_build import bits
+
+sys.path.insert(0, os.path.join(hb.ROOT, "tests"))
 
 import traj_check_cases as tc  # noqa: E402
 
-DECL = "extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];"
-
 
 def build():
-    src = open(os.path.join(ROOT, "fuel_amd", "csrc", "traj_check.hip")).read()
-    text = src[src.index("namespace {"):src.index("size_t tc_lds(")]
-    assert text.count(DECL) == 1
-    text = text.replace(DECL, "unsigned char* smem_raw = g_lds;")  # the one line that differs: the block's address
-    text += src[src.index("size_t tc_lds("):src.index("int trajchk_cfg_check(")]
-    os.makedirs(OUT, exist_ok=True)
-    with open(os.path.join(OUT, "kernel.inc"), "w") as f:
-        f.write(text)
-    exe = os.path.join(OUT, "host_kernel")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++20", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-w",
-                           "-I", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include"),
-                           "-I", os.path.join(ROOT, "fuel_amd", "csrc"), "-I", OUT,
-                           os.path.join(HERE, "traj_check_golden", "host_kernel.cpp"), "-o", exe, "-lpthread"])
-    return exe
-
-
-def bits(v):
-    return "%016x" % struct.unpack("<Q", struct.pack("<d", float(v)))[0]
+    text = hb.lds_from_host(hb.cut("traj_check.hip", "namespace {", "size_t tc_lds("))
+    return hb.compile("traj_check", text + hb.cut("traj_check.hip", "size_t tc_lds(", "int trajchk_cfg_check("))
 
 
 def main():
@@ -50,7 +29,7 @@ def main():
     groups = {}
     for sc in scenes:
         groups.setdefault((names.index(sc["map"]), sc["degree"], sc["step"], sc["max_radius"]), []).append(sc)
-    path = os.path.join(OUT, "scenes.in")
+    path = os.path.join(hb.out_dir("traj_check"), "scenes.in")
     order = []
     with open(path, "w") as f:
         f.write("%d\n" % len(names))
@@ -67,11 +46,7 @@ def main():
                 f.write("%d %s %s %s\n" % (len(sc["ctrl"]), float(sc["dt"]).hex(), float(sc["t_now"]).hex(),
                                            " ".join(float(v).hex() for v in sc["ctrl"].reshape(-1))))
                 order.append(sc)
-    p = subprocess.run([exe, path], capture_output=True, text=True)
-    if p.returncode or p.stderr.strip():
-        print("FAILED", p.returncode, p.stdout[-300:], p.stderr[-3000:])
-        sys.exit(1)
-    lines = p.stdout.splitlines()
+    lines = hb.run(exe, [path]).splitlines()
     assert len(lines) == len(order), (len(lines), len(order))
     bad = 0
     for sc, line in zip(order, lines):

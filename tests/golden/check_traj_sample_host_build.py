@@ -1,52 +1,27 @@
-"""Builds k_traj_sample's own text for the host (tests/golden/traj_sample_golden/host_kernel.cpp: a thread per lane, a
-barrier for __syncthreads, an exchange for __shfl, guard zones round the LDS block) with the address and the
+"""Builds k_traj_sample's own text for the host (tests/golden/traj_sample_golden/host_kernel.cpp on
+tests/golden/host_lanes.h: a thread per lane, guard zones round the LDS block) with the address and the
 undefined-behaviour sanitizers, runs it once on every scene of tests/traj_sample_cases.py -- grouped into launches by
 mode and degrees, so that problems of different sizes share workgroups -- plus a launch laid out like a device batch
 with a bad knot span among good neighbours, and compares every output with the restatement (tests/traj_sample_ref.py)
-bit for bit.  Everything stays under build/traj_sample_golden/.  Needs g++ with C++20 and the HIP headers (ROCM_PATH,
-default /opt/rocm) for the shared declarations; no GPU."""
+bit for bit.  Everything stays under build/traj_sample_golden/; the cut, the build and the run are
+tests/golden/host_build.py's."""
 import os
-import struct
-import subprocess
 import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-OUT = os.path.join(ROOT, "build", "traj_sample_golden")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import host_build as hb
+from host_build import bits, hexes
+
+sys.path.insert(0, os.path.join(hb.ROOT, "tests"))
 
 import traj_sample_cases as tc  # noqa: E402
 import traj_sample_ref as sr  # noqa: E402
 
-DECL = "extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];"
-
 
 def build():
-    src = open(os.path.join(ROOT, "fuel_amd", "csrc", "traj_sample.hip")).read()
-    text = src[src.index("namespace {"):src.index("size_t ts_lds(")]
-    assert text.count(DECL) == 1
-    text = text.replace(DECL, "unsigned char* smem_raw = g_lds;")  # the one line that differs: the block's address
-    text += src[src.index("size_t ts_lds("):src.index("int trajsmp_cfg_check(")]
-    os.makedirs(OUT, exist_ok=True)
-    with open(os.path.join(OUT, "kernel.inc"), "w") as f:
-        f.write(text)
-    exe = os.path.join(OUT, "host_kernel")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++20", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-w",
-                           "-I", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include"),
-                           "-I", os.path.join(ROOT, "fuel_amd", "csrc"), "-I", OUT,
-                           os.path.join(HERE, "traj_sample_golden", "host_kernel.cpp"), "-o", exe, "-lpthread"])
-    return exe
-
-
-def bits(v):
-    return "%016x" % struct.unpack("<Q", struct.pack("<d", float(v)))[0]
-
-
-def hexes(a):
-    return " ".join(float(v).hex() for v in np.asarray(a, dtype=np.float64).reshape(-1))
+    text = hb.lds_from_host(hb.cut("traj_sample.hip", "namespace {", "size_t ts_lds("))
+    return hb.compile("traj_sample", text + hb.cut("traj_sample.hip", "size_t ts_lds(", "int trajsmp_cfg_check("))
 
 
 def batch_scenes():
@@ -65,7 +40,7 @@ def main():
     launches = [(k, g, False) for k, g in tc.groups(tc.quick_scenes()).items()]
     launches.append(((sr.COMMAND, 3, 3), tc.big_scenes(), False))
     launches.append(((sr.COMMAND, 3, 0), batch_scenes(), True))
-    path = os.path.join(OUT, "scenes.in")
+    path = os.path.join(hb.out_dir("traj_sample"), "scenes.in")
     order = []
     with open(path, "w") as f:
         f.write("%d\n" % len(launches))
@@ -84,11 +59,7 @@ def main():
                 f.write("%s %s\n" % (float(sc["t_stop"] if sc["t_stop"] is not None else 1e300).hex(), hexes(sc.get("flight0", [0.0] * 8))))
                 f.write("%d %s\n" % (len(sc["t"]), hexes(sc["t"])))
                 order.append((sc, maxt))
-    p = subprocess.run([exe, path], capture_output=True, text=True)
-    if p.returncode or p.stderr.strip():
-        print("FAILED", p.returncode, p.stdout[-300:], p.stderr[-3000:])
-        sys.exit(1)
-    lines = p.stdout.splitlines()
+    lines = hb.run(exe, [path]).splitlines()
     assert len(lines) == sum(1 + maxt for _, maxt in order), (len(lines), len(order))
     bad = at = 0
     for sc, maxt in order:

@@ -1,43 +1,11 @@
 // A host build of k_kino_path's own text (fuel_amd/csrc/kino_path.hip between "namespace {" and the host code, cut out by
-// tests/golden/check_kino_host_build.py into kernel.inc): a thread per lane, std::barrier for __syncthreads, the shared
-// block a static, glibc's libm.  Reads the input files tests/golden/make_kino_golden.py writes for the reference's driver
-// and writes the same output format, so the two output files can be compared byte for byte.  With RAW=1 it prints every
-// result instead; FORCE_SEG / MAX_SAMPLES / MAX_NODES / LOAD_POINTS set the corresponding fields; guard zones behind the
-// output arrays catch a write past a cap.
+// tests/golden/check_kino_host_build.py into kernel.inc) on the lanes of tests/golden/host_lanes.h, with glibc's libm.
+// Reads the input files tests/golden/make_kino_golden.py writes for the reference's driver and writes the same output
+// format, so the two output files can be compared byte for byte.  With RAW=1 it prints every result instead; FORCE_SEG /
+// MAX_SAMPLES / MAX_NODES / LOAD_POINTS set the corresponding fields; guard zones behind the output arrays catch a write
+// past a cap.
 //   host_kernel <in.txt> <infl.bin> <unk.bin> <out.txt>
-#define __HIP_PLATFORM_AMD__ 1
-#include "fuelmi_internal.h"
-#include <barrier>
-#include <cmath>
-#include <cstdio>
-#include <fstream>
-#include <thread>
-#include <vector>
-using namespace std;
-#undef __shared__
-#define __shared__ static
-#undef __launch_bounds__
-#define __launch_bounds__(x)
-struct Idx { int x; };
-static thread_local Idx threadIdx_, blockIdx_;
-#define threadIdx threadIdx_
-#define blockIdx blockIdx_
-static std::barrier<>* g_bar;
-#define __syncthreads() g_bar->arrive_and_wait()
-static inline bool idx_in_map(const Geo& g, const int id[3]) {
-  return !(id[0] < 0 || id[1] < 0 || id[2] < 0 || id[0] > g.nx - 1 || id[1] > g.ny - 1 || id[2] > g.nz - 1);
-}
-static inline void pos_to_idx(const Geo& g, const double p[3], int id[3]) {
-  for (int k = 0; k < 3; ++k) id[k] = (int)floor((p[k] - g.org[k]) * g.res_inv);
-}
-static inline bool bit_at(const u64* pl, long a) { return (pl[a >> 6] >> (a & 63)) & 1ull; }
-static inline bool plane_at_pos(const Geo& g, const u64* pl, const double p[3]) {
-  int id[3];
-  pos_to_idx(g, p, id);
-  if (!idx_in_map(g, id)) return false;
-  return bit_at(pl, (long)id[0] * g.nyz + (long)id[1] * g.nz + id[2]);
-}
-void fuelmi_set_error(const char*, ...) {}
+#include "host_lanes.h"
 #include "kernel.inc"
 
 static void put(FILE* f, double v) { std::fprintf(f, " %a", v); }
@@ -103,13 +71,7 @@ int main(int argc, char** argv) {
   K.t_shot = &dv[0], K.T_sum = &dv[n], K.ts_out = &dv[2 * n], K.coef_shot = coef.data(), K.derivs = der.data(), K.samples = smp.data();
   K.node_state = ns.data(), K.node_input = nin.data(), K.node_duration = nd.data();
   if (getenv("LOAD_POINTS")) K.load_points = atoi(getenv("LOAD_POINTS")), K.cfg.seg_num = K.load_points - 1;
-  for (int b = 0; b < n; ++b) {
-    std::barrier<> bar(KN_NT);
-    g_bar = &bar;
-    std::vector<std::thread> th;
-    for (int t = 0; t < KN_NT; ++t) th.emplace_back([&, t, b] { threadIdx_.x = t; blockIdx_.x = b; k_kino_path(g, K); bar.arrive_and_drop(); });
-    for (auto& t : th) t.join();
-  }
+  launch(n, KN_NT, 0, [&] { k_kino_path(g, K); });
   for (size_t i = 0; i < 64; ++i)  // guard zones behind the arrays
     if (smp[(size_t)n * MS * 3 + i] != -7.0 || ns[(size_t)n * MN * 6 + i] != -7.0 || nin[(size_t)n * MN * 3 + i] != -7.0 || nd[(size_t)n * MN + i] != -7.0) { std::printf("GUARD HIT\n"); return 9; }
   if (getenv("RAW")) {

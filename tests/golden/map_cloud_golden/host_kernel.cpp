@@ -1,83 +1,12 @@
-// A host build of the three cloud kernels' own text (fuel_amd/csrc/map_cloud.hip from "namespace {" to the host code, and
-// plane_window from fuel_amd/csrc/fuelmi_internal.h, cut out by tests/golden/check_map_cloud_host_build.py into
-// kernel.inc): a thread per lane, std::barrier for __syncthreads, the wave operations (__ballot, __shfl_up) as exchanges
-// through a per-wave block behind a per-wave barrier, __shared__ arrays as statics (the address sanitizer puts red zones
-// round them).  Meant for -fsanitize=address,undefined: every device array is a heap block of its exact size -- the
-// workgroup words [nwg], the total, the pinned word, the points [min(cap, voxels)][3] -- and a plane is the W words that
-// cover the map followed by exactly ONE word of its zero margin, the one a chunk that ends in the plane's last word may
-// load; a read past it is reported.  The lanes of a launch are created once and walk the workgroups together.
+// A host build of the three cloud kernels' own text (fuel_amd/csrc/map_cloud.hip from "namespace {" to the host code, cut
+// out by tests/golden/check_map_cloud_host_build.py into kernel.inc) on the lanes of tests/golden/host_lanes.h.  Every
+// device array is a heap block of its exact size -- the workgroup words [nwg], the total, the pinned word, the points
+// [min(cap, voxels)][3] -- and a plane is the W words that cover the map followed by exactly ONE word of its zero
+// margin, the one a chunk that ends in the plane's last word may load; a read past it is reported.
 //   host_kernel <planes.bin> <scenes.txt> <out.bin>
-#define __HIP_PLATFORM_AMD__ 1
-#include "fuelmi_internal.h"
-#include <barrier>
-#include <cstdio>
-#include <cstring>
-#include <fstream>
-#include <memory>
-#include <thread>
-#include <vector>
-using namespace std;
-#undef __launch_bounds__
-#define __launch_bounds__(x)
-#undef __shared__
-#define __shared__ static
-struct Idx { int x; };
-static thread_local Idx threadIdx_, blockIdx_;
-#define threadIdx threadIdx_
-#define blockIdx blockIdx_
-static std::barrier<>* g_bar;
-#define __syncthreads() g_bar->arrive_and_wait()
-struct WaveBlock {
-  std::barrier<> bar{64};
-  u32 v[64];
-  int p[64];
-};
-static WaveBlock* g_waves;
-static inline WaveBlock& my_wave() { return g_waves[threadIdx_.x >> 6]; }
-static unsigned long long host_ballot(bool p) {
-  WaveBlock& w = my_wave();
-  w.p[threadIdx_.x & 63] = p ? 1 : 0;
-  w.bar.arrive_and_wait();
-  unsigned long long m = 0;
-  for (int i = 0; i < 64; ++i) m |= (unsigned long long)w.p[i] << i;
-  w.bar.arrive_and_wait();
-  return m;
-}
-static u32 host_shfl_up(u32 v, int delta) {
-  WaveBlock& w = my_wave();
-  const int lane = threadIdx_.x & 63;
-  w.v[lane] = v;
-  w.bar.arrive_and_wait();
-  const u32 r = lane >= delta ? w.v[lane - delta] : v;
-  w.bar.arrive_and_wait();
-  return r;
-}
-#define __ballot host_ballot
-#define __shfl_up host_shfl_up
-#define __popcll __builtin_popcountll
-void fuelmi_set_error(const char*, ...) {}
+#include "host_lanes.h"
 #include "kernel.inc"
 }  // namespace (kernel.inc leaves it open)
-
-// all workgroups of a launch, one after the other, on `nt` lanes created once
-template <class F>
-static void launch(int nblk, int nt, F kernel) {
-  std::barrier<> bar(nt);
-  g_bar = &bar;
-  std::unique_ptr<WaveBlock[]> waves(new WaveBlock[nt / 64]);
-  g_waves = waves.get();
-  std::vector<std::thread> th;
-  for (int t = 0; t < nt; ++t)
-    th.emplace_back([&, t] {
-      threadIdx_.x = t;
-      for (int blk = 0; blk < nblk; ++blk) {
-        blockIdx_.x = blk;
-        kernel();
-        bar.arrive_and_wait();  // the workgroup is over: its statics are free for the next one
-      }
-    });
-  for (auto& t : th) t.join();
-}
 
 struct State {
   Geo g;
@@ -138,9 +67,9 @@ int main(int argc, char** argv) {
     for (long k = 0; k < n_out * 3; ++k) memcpy(&pts[k], "\xA5\xA5\xA5\xA5", 4);
     *total = *total_pin = 0x7FFFFFFFu;
     C.wg = wg.get(), C.total = total.get(), C.total_pin = total_pin.get(), C.out = pts.get(), C.cap = (u32)n_out;
-    launch(C.nwg, CL_WG, [&] { k_cloud_count(s.g, C); });
-    launch(1, CL_SCAN, [&] { k_cloud_scan(C); });
-    if (n_out) launch(C.nwg, CL_WG, [&] { k_cloud_write(s.g, C); });
+    launch(C.nwg, CL_WG, 0, [&] { k_cloud_count(s.g, C); });
+    launch(1, CL_SCAN, 0, [&] { k_cloud_scan(C); });
+    if (n_out) launch(C.nwg, CL_WG, 0, [&] { k_cloud_write(s.g, C); });
     if (*total != *total_pin) return 3;
     const int tot = (int)*total, nw = (int)n_out;
     fwrite(&tot, 4, 1, out);

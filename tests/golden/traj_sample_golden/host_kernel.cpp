@@ -1,79 +1,19 @@
 // A host build of k_traj_sample's own text (fuel_amd/csrc/traj_sample.hip between "namespace {" and the host code, cut
-// out by tests/golden/check_traj_sample_host_build.py into kernel.inc, with fuel_amd/csrc/spline_internal.h included as
-// it is): a thread per lane, std::barrier for __syncthreads, __shfl as an exchange through a per-wave block behind a
-// per-wave barrier, the LDS block a heap block of exactly the launch's size between two guard zones.  Meant for
-// -fsanitize=address,undefined: a read or write past the knots, the control points, the times or the result arrays (each
-// a heap block of its exact size) is reported by the sanitizer, one inside a guard zone by the check below.  Reads the
-// launches check_traj_sample_host_build.py writes and prints per problem one line (the bits of the duration and of the
-// eight record numbers) and one line per sample slot (the status, then the bits of the fifteen doubles).
+// out by tests/golden/check_traj_sample_host_build.py into kernel.inc) on the lanes of tests/golden/host_lanes.h.  The
+// knots, the control points, the times and every result array are heap blocks of their exact size.  Reads the launches
+// check_traj_sample_host_build.py writes and prints per problem one line (the bits of the duration and of the eight
+// record numbers) and one line per sample slot (the status, then the bits of the fifteen doubles).
 //   host_kernel <in.txt>
-#define __HIP_PLATFORM_AMD__ 1
-#include "fuelmi_internal.h"
-#include <barrier>
-#include <cinttypes>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <fstream>
-#include <memory>
-#include <thread>
-#include <vector>
-using namespace std;
-#undef __launch_bounds__
-#define __launch_bounds__(x)
-struct Idx { int x; };
-static thread_local Idx threadIdx_, blockIdx_;
-#define threadIdx threadIdx_
-#define blockIdx blockIdx_
-static std::barrier<>* g_bar;
-#define __syncthreads() g_bar->arrive_and_wait()
-struct WaveBlock {
-  std::barrier<> bar{64};
-  double d[64];
-  int p[64];
-};
-static WaveBlock* g_waves;
-static inline WaveBlock& my_wave() { return g_waves[threadIdx_.x >> 6]; }
-static double host_shfl(double v, int src) {
-  WaveBlock& w = my_wave();
-  w.d[threadIdx_.x & 63] = v;
-  w.bar.arrive_and_wait();
-  const double r = w.d[src];
-  w.bar.arrive_and_wait();
-  return r;
-}
-static int host_shfl(int v, int src) {
-  WaveBlock& w = my_wave();
-  w.p[threadIdx_.x & 63] = v;
-  w.bar.arrive_and_wait();
-  const int r = w.p[src];
-  w.bar.arrive_and_wait();
-  return r;
-}
-#define __shfl host_shfl
-void fuelmi_set_error(const char*, ...) {}
-static unsigned char* g_lds;  // the launch's LDS block (kernel.inc: `unsigned char* smem_raw = g_lds;`)
+#include "host_lanes.h"
 #include "spline_internal.h"
 #include "kernel.inc"
 }  // namespace (kernel.inc leaves it open)
-
-static unsigned long long bits(double v) {
-  unsigned long long b;
-  memcpy(&b, &v, 8);
-  return b;
-}
-static double num(std::ifstream& in) {
-  std::string s;
-  in >> s;
-  return strtod(s.c_str(), nullptr);
-}
 
 int main(int argc, char** argv) {
   if (argc < 2) return 1;
   std::ifstream in(argv[1]);
   int n_launch;
   in >> n_launch;
-  constexpr size_t GUARD = 256;
   for (int l = 0; l < n_launch; ++l) {
     TrajSmpArgs A;
     memset(&A, 0, sizeof(A));
@@ -113,31 +53,7 @@ int main(int argc, char** argv) {
     if (has_flight) A.flight = flight.data();
     A.status = status.data(), A.o_pos = o3[0].data(), A.o_vel = o3[1].data(), A.o_acc = o3[2].data(), A.o_jerk = o3[3].data();
     A.o_yaw = o1[0].data(), A.o_yawdot = o1[1].data(), A.o_yawddot = o1[2].data(), A.duration = dur.data();
-    const size_t lds = ts_lds(c);
-    const int nthr = TS_WIN * TS_WAVES;
-    for (int blk = 0; blk < (n + TS_WAVES - 1) / TS_WAVES; ++blk) {
-      std::unique_ptr<unsigned char[]> block(new unsigned char[lds + 2 * GUARD]);
-      memset(block.get(), 0xA5, lds + 2 * GUARD);
-      g_lds = block.get() + GUARD;
-      std::barrier<> bar(nthr);
-      g_bar = &bar;
-      std::unique_ptr<WaveBlock[]> waves(new WaveBlock[TS_WAVES]);
-      g_waves = waves.get();
-      std::vector<std::thread> th;
-      for (int i = 0; i < nthr; ++i)
-        th.emplace_back([&, i, blk] {
-          threadIdx_.x = i;
-          blockIdx_.x = blk;
-          k_traj_sample(A);
-          bar.arrive_and_drop();
-        });
-      for (auto& x : th) x.join();
-      for (size_t i = 0; i < GUARD; ++i)
-        if (block[i] != 0xA5 || block[GUARD + lds + i] != 0xA5) {
-          std::printf("GUARD HIT\n");
-          return 9;
-        }
-    }
+    if (const int rc = launch((n + TS_WAVES - 1) / TS_WAVES, TS_WIN * TS_WAVES, ts_lds(c), [&] { k_traj_sample(A); })) return rc;
     for (int b = 0; b < n; ++b) {
       std::printf("P %016llx", bits(dur[b]));
       for (int k = 0; k < 8; ++k) std::printf(" %016llx", bits(flight[(size_t)b * 8 + k]));
