@@ -128,6 +128,17 @@ KINO_REACH_HORIZON, KINO_REACH_END, KINO_NO_PATH, KINO_NEAR_END, KINO_CLOSE_GOAL
 KINO_MAX_PRIMS, KINO_MAX_ALLOC, KINO_MAX_SEG = 256, 1 << 22, 1 << 20
 
 
+class TopoCfg(C.Structure):
+    """fuelmi_topo_cfg: the topo_prm/* parameters of TopologyPRM and the strides of the path / node arrays."""
+    _fields_ = [("sample_inflate", C.c_double * 3), ("clearance", C.c_double), ("ratio_to_short", C.c_double)] + \
+               [(n, C.c_int) for n in
+                ("max_sample_num", "max_raw_path", "max_raw_path2", "reserve_num", "max_path_points", "max_nodes")]
+
+
+TOPO_OK, TOPO_NO_PATH, TOPO_UNDEFINED = 0, 1, 2
+TOPO_MAX_SAMPLES, TOPO_MAX_RAW, TOPO_MAX_PATH_POINTS, TOPO_MAX_POINTS_IN = 8190, 4096, 256, 64
+
+
 class YawCfg(C.Structure):
     """fuelmi_yaw_cfg: planYawExplore's / planYaw's constants and the strides of the control-point / way-point arrays."""
     _fields_ = [("mode", C.c_int), ("pos_degree", C.c_int), ("max_ctrl", C.c_int), ("max_seg", C.c_int),
@@ -324,6 +335,10 @@ SYMBOLS = {
                                         _dp, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp]),
     "fuelmi_bspline_dev_load_kino": (C.c_int, [_P, C.POINTER(KinoCfg), _dp, _dp, _dp, _dp, _dp, _ip, _dp]),
     "fuelmi_kino_plan": (C.c_int, [C.POINTER(KinoCfg), C.POINTER(C.c_longlong)]),
+    "fuelmi_map_topo_paths": (C.c_int, [_P, C.POINTER(TopoCfg), C.c_int, _dp, _dp, C.c_int, _ip, _dp, C.c_int, _ip, _dp, _dp,
+                                        _ip, _ip, _ip, _ip, _ip, _ip, _dp, _ip, _ip, _dp, _ip, _dp, _ip, _dp, _ip, _dp]),
+    "fuelmi_topo_plan": (C.c_int, [C.POINTER(TopoCfg), C.POINTER(C.c_longlong)]),
+    "fuelmi_map_topo_pool_bytes": (C.c_longlong, [_P]),
     "fuelmi_map_plan_yaws": (C.c_int, [_P, C.POINTER(BsplineCfg), C.POINTER(YawCfg), C.c_int, _ip, _dp, _dp, _dp, _dp, _ip,
                                        _dp, _ip, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp]),
     "fuelmi_bspline_dev_plan_yaws": (C.c_int, [_P, C.POINTER(YawCfg), _dp, _dp, _ip, _dp, _ip, _dp, _dp, _ip, _dp, _dp,

@@ -225,10 +225,12 @@ struct fuelmi_map {
   DevScratch trajsmp_dev;  // fuelmi_map_sample_trajs (traj_sample.hip): problems in, results out
   DevScratch trajadj_dev;  // fuelmi_map_adjust_trajs (traj_adjust.hip): problems in, results out
   DevScratch cloud_dev;    // fuelmi_map_extract_cloud (map_cloud.hip): the total, the workgroup words, the points
+  DevScratch topo_dev;     // fuelmi_map_topo_paths (topo_path.hip): results, inputs, graphs, path sets
   int path_stats[4] = {0, 0, 0, 0};  // fuelmi_map_path_stats
   hipEvent_t goal_ev[3] = {nullptr, nullptr, nullptr};  // the events that split the goal-path call's time
   double goal_ms[2] = {0.0, 0.0};  // fuelmi_map_goal_path_times
   std::vector<double> kino_host;  // the inputs and primitive lists of the last call, alive until its copies have run
+  std::vector<unsigned char> topo_host;  // the inputs of the last topological search, likewise
   // the cloud call's pinned word the scan writes the total to; the events that split its time
   u32* cloud_pin = nullptr;
   hipEvent_t cloud_ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -420,6 +422,12 @@ __device__ __forceinline__ u64 box_mask_word(const Geo& g, int w, const Box3& b)
   }
   return mask;
 }
+#endif  // __HIPCC__
+// The distance look-ups below are plain C++: a host build of kernel text (tests/golden/host_lanes.h) compiles them too.
+#ifndef __HIPCC__
+#include <cmath>
+using std::isinf;
+#endif
 __device__ __forceinline__ double dist_to_f64(float d, double res) {
   // "no source in the box": the reference stores res*sqrt(DBL_MAX) (sdf_map.cpp:196 with
   // fillESDF's DBL_MAX sentinel); the device keeps +inf in f32
@@ -495,7 +503,6 @@ __device__ __forceinline__ double dist_with_grad_dev(const Geo& g, const float* 
   dist_gather_issue(g, dist, pos, G);
   return dist_gather_finish(g, G, grad);
 }
-#endif  // __HIPCC__
 
 // ---- kernels' host launchers (defined in the .hip files) ---------------------------------------
 int esdf_update(fuelmi_map* m);

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BsplineBatch, BsplineCfg, CloudCfg, FrontierCfg, GoalCfg, KinoCfg, MapCfg, MapInfo, PathCfg, RefineCfg, RenderCfg, TrajAdjCfg, TrajChkCfg, TrajSmpCfg, TspCfg,
+from ._lib import (BsplineBatch, BsplineCfg, CloudCfg, FrontierCfg, GoalCfg, KinoCfg, MapCfg, MapInfo, PathCfg, RefineCfg, RenderCfg, TopoCfg, TrajAdjCfg, TrajChkCfg, TrajSmpCfg, TspCfg,
                    WptrajCfg, YawCfg, check, lib)
 
 # exploration.launch / algorithm.xml defaults (exploration_manager/launch/algorithm.xml:33-59,170-181)
@@ -72,6 +72,14 @@ def kino_cfg(max_tau=0.8, init_max_tau=1.0, max_vel=2.25, max_acc=2.0, w_time=10
                    float(resolution), float(lambda_heu), float(res), float(time_res), float(time_res_init), float(ts),
                    int(allocate_num), int(check_num), 1 if optimistic else 0, int(min_seg), int(seg_num),
                    int(max_path_nodes), int(max_samples))
+
+
+def topo_cfg(sample_inflate=(1.0, 3.5, 1.0), clearance=0.2, ratio_to_short=5.5, max_sample_num=2000, max_raw_path=300,
+             max_raw_path2=25, reserve_num=6, max_path_points=64, max_nodes=256):
+    """fuelmi_topo_cfg with topo_algorithm.xml's topo_prm/* values (plan_manage/launch/topo_algorithm.xml:110-121)"""
+    return TopoCfg((C.c_double * 3)(*[float(v) for v in sample_inflate]), float(clearance), float(ratio_to_short),
+                   int(max_sample_num), int(max_raw_path), int(max_raw_path2), int(reserve_num), int(max_path_points),
+                   int(max_nodes))
 
 
 def traj_check_cfg(degree=3, max_ctrl=4, step=0.02, max_radius=6.0):
@@ -652,6 +660,71 @@ class SDFMap:
         check(lib().fuelmi_kino_plan(C.byref(kino_cfg(**cfg)), out))
         return dict(zip(("lanes", "lds_bytes", "workspace_bytes", "n_init", "n_regular", "max_prims", "max_alloc",
                          "hash_slots"), [int(v) for v in out]))
+
+    # --- the topological path search of guided replanning (include/fuelmi.h fuelmi_map_topo_paths) ---
+    TOPO_OK, TOPO_NO_PATH, TOPO_UNDEFINED = _lib.TOPO_OK, _lib.TOPO_NO_PATH, _lib.TOPO_UNDEFINED
+
+    def topo_paths(self, starts, ends, samples, start_pts=None, end_pts=None, allow_limit=False, **cfg):
+        """TopologyPRM::findTopoPaths per problem over the given sample streams (samples [n, max_sample_num, 3], raw
+        numbers in [-1, 1)); start_pts / end_pts: per problem a [k, 3] array (or None); cfg: the fields of topo_cfg(),
+        max_sample_num taken from `samples`.  Returns a dict: status (TOPO_*; -1: over max_nodes / max_path_points / a
+        cap), counts [n, 4], events [n, 6], n_nodes [n], per problem nodes (list of (id, type, xyz, neighbour ids),
+        complete only up to max_nodes), raw / filt / sel (lists of [k, 3] arrays, cut at max_path_points) with their full
+        lengths raw_len / filt_len / sel_len, sel_length (pathLength of each select path); limit.
+        FUELMI_ELIMIT raises FuelmiError unless allow_limit."""
+        st = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+        en = np.ascontiguousarray(ends, dtype=np.float64).reshape(-1, 3)
+        n = len(st)
+        smp = np.ascontiguousarray(samples, dtype=np.float64).reshape(n, -1, 3) if n else np.zeros((0, 0, 3))
+        c = topo_cfg(**dict(cfg, max_sample_num=smp.shape[1]))
+
+        def pack(lists):
+            lists = [np.zeros((0, 3)) if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3)
+                     for a in (lists if lists is not None else [None] * n)]
+            cap = max([len(a) for a in lists] + [0])
+            cnt = np.array([len(a) for a in lists], dtype=np.int32)
+            arr = np.zeros((n, cap, 3))
+            for b, a in enumerate(lists):
+                arr[b, :len(a)] = a
+            return cap, cnt, arr
+        ms, nsp, sp = pack(start_pts)
+        me, nep, ep = pack(end_pts)
+        maxn, mpp, r2, rs = max(c.max_nodes, 0), max(c.max_path_points, 0), max(c.max_raw_path2, 0), max(c.reserve_num, 0)
+        iv = dict(status=np.zeros(n, dtype=np.int32), counts=np.zeros((n, 4), dtype=np.int32),
+                  events=np.zeros((n, 6), dtype=np.int32), n_nodes=np.zeros(n, dtype=np.int32))
+        nid, nty = np.zeros((n, maxn), dtype=np.int32), np.zeros((n, maxn), dtype=np.int32)
+        nxyz, off, ids = np.zeros((n, maxn, 3)), np.zeros((n, maxn + 1), dtype=np.int32), np.zeros((n, 4 * maxn), dtype=np.int32)
+        raw, filt, sel = np.zeros((n, r2, mpp, 3)), np.zeros((n, r2, mpp, 3)), np.zeros((n, rs, mpp, 3))
+        rl, fl, sl = np.zeros((n, r2), dtype=np.int32), np.zeros((n, r2), dtype=np.int32), np.zeros((n, rs), dtype=np.int32)
+        slen = np.zeros((n, rs))
+        rc = self.L.fuelmi_map_topo_paths(self.h, C.byref(c), n, _dp(st), _dp(en), ms, _ip(nsp), _dp(sp), me, _ip(nep),
+                                          _dp(ep), _dp(smp), _ip(iv["status"]), _ip(iv["counts"]), _ip(iv["events"]),
+                                          _ip(iv["n_nodes"]), _ip(nid), _ip(nty), _dp(nxyz), _ip(off), _ip(ids), _dp(raw),
+                                          _ip(rl), _dp(filt), _ip(fl), _dp(sel), _ip(sl), _dp(slen))
+        if not (allow_limit and rc == -5):
+            check(rc)
+        out = dict(iv)
+        out.update(limit=rc == -5, raw_len=rl, filt_len=fl, sel_len=sl, sel_length=slen)
+        out["nodes"] = [[(int(nid[b, i]), int(nty[b, i]), nxyz[b, i].copy(), ids[b, off[b, i]:off[b, i + 1]].copy())
+                         for i in range(min(int(iv["n_nodes"][b]), maxn))] for b in range(n)]
+        for key, arr, ln in (("raw", raw, rl), ("filt", filt, fl), ("sel", sel, sl)):
+            out[key] = [[arr[b, r, :min(int(ln[b, r]), mpp)].copy() for r in range(ln.shape[1]) if ln[b, r] > 0]
+                        for b in range(n)]
+        return out
+
+    @staticmethod
+    def topo_plan(**cfg):
+        """host only: dict(lanes, lds_bytes, workspace_bytes, guard_chunk, max_samples, max_raw, max_path_points,
+        max_dis_points, max_neighbors, undefined_raw_nodes, max_points_in, max_workspace)"""
+        out = (C.c_longlong * 12)()
+        check(lib().fuelmi_topo_plan(C.byref(topo_cfg(**cfg)), out))
+        return dict(zip(("lanes", "lds_bytes", "workspace_bytes", "guard_chunk", "max_samples", "max_raw", "max_path_points",
+                         "max_dis_points", "max_neighbors", "undefined_raw_nodes", "max_points_in", "max_workspace"),
+                        [int(v) for v in out]))
+
+    def topo_pool_bytes(self):
+        """bytes of the map's grow-only workspace of topo_paths"""
+        return int(self.L.fuelmi_map_topo_pool_bytes(self.h))
 
     # --- the yaw trajectory of a position spline (include/fuelmi.h fuelmi_map_plan_yaws) ---
     YAW_EXPLORE, YAW_FOLLOW, YAW_OK, YAW_DEGENERATE = _lib.YAW_EXPLORE, _lib.YAW_FOLLOW, _lib.YAW_OK, _lib.YAW_DEGENERATE

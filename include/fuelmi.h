@@ -957,6 +957,86 @@ int fuelmi_bspline_dev_load_kino(fuelmi_bspline_dev* b, const fuelmi_kino_cfg* c
 int fuelmi_kino_plan(const fuelmi_kino_cfg* cfg, long long out8[8]);
 
 /* ------------------------------------------------------------------------------------------
+ * Topological path search of guided replanning: TopologyPRM::findTopoPaths (path_searching/src/topo_prm.cpp:43-98),
+ * the producer of the guide paths of FastPlannerManager::topoReplan (plan_manage/src/planner_manager.cpp:425-466), for
+ * n_prob independent problems on one map in one call.  Per problem, everything f64 in the reference's order:
+ *   1. createGraph (:100-188) over the problem's SAMPLE STREAM: samples [max_sample_num][3] are the raw numbers
+ *      rand_pos_(eng_) would have returned, in [-1, 1); the kernel applies sample_r_, rotation_ and translation_
+ *      (:113-128, :240-250).  There is no wall-clock cap (max_sample_time does not exist): exactly max_sample_num samples
+ *      are taken, so a result never depends on the machine's speed.  A sample with evaluateCoarseEDT <= clearance is
+ *      dropped; findVisibGuard walks the guards in list order up to the third visible one; no visible guard: a new
+ *      guard; exactly two: needConnection (:210-238, with the move of an existing connector to the shorter position);
+ *      one or three: nothing.
+ *   2. pruneGraph (:272-299); searchPaths / depthFirstSearch (:606-684): neighbour order, the stop at max_raw_path, the
+ *      bucket-by-node-count filter up to max_raw_path2.
+ *   3. shortcutPaths (:516-531, one iteration a path), pruneEquivalent (:301-337), selectShortPaths (:339-377: reserve_num,
+ *      ratio_to_short, the merge with start_pts / end_pts, five shortcut iterations, the second prune).
+ * lineVisib (:252-270) is RayCaster::setInput / step (plan_env/src/raycast.cpp:228-321): the start voxel is tested, the
+ * end voxel is not, the index is int(ray_pt + offset_), a voxel outside the map reads -1 and blocks the ray.
+ * Decisions on the distance field (`dist <= thresh` for resolution, 0 and clearance) are the reference's: the positive
+ * part of its field is res * sqrt(k) for an integer k, so each threshold becomes the largest k the f64 comparison
+ * accepts, and the kernel compares the device's f32 field with a cut between its values for k and k + 1.  Only the
+ * gradient push of shortcutPath uses the f32 values as numbers (trilinear getDistWithGrad).
+ * Per-problem status: FUELMI_TOPO_OK; FUELMI_TOPO_NO_PATH (the select set is empty); FUELMI_TOPO_UNDEFINED where the
+ * reference's behaviour is undefined (discretizePath(path, pt_num) with pt_num < 2 or without a segment for a point, a
+ * raw path of 100 nodes or more, a point that is not finite: nothing is read out of bounds, no path outputs are written,
+ * the other problems complete and the call stays FUELMI_OK); -1: over max_nodes / max_path_points (full counts and
+ * lengths, truncated arrays) or over one of the kernel's own caps below (no path outputs), call status FUELMI_ELIMIT.
+ * FUELMI_EINVAL before any launch: a coordinate that is not finite or >= 1e7 in magnitude, |end - start| <= resolution,
+ * a sample outside [-1, 1), clearance < 0, counts < 1.  FUELMI_ELIMIT before any launch: a cfg field over its cap,
+ * n_prob x workspace bytes > FUELMI_TOPO_MAX_WORKSPACE.  n_prob = 0 is FUELMI_OK.  A result does not depend on the
+ * problem's place in the batch.  Runs on the map's stream: host arrays in, host arrays out, synchronous; the
+ * workspace is one grow-only allocation on the map (fuelmi_map_topo_pool_bytes).
+ * ---------------------------------------------------------------------------------------- */
+#define FUELMI_TOPO_OK 0
+#define FUELMI_TOPO_NO_PATH 1
+#define FUELMI_TOPO_UNDEFINED 2
+#define FUELMI_TOPO_MAX_SAMPLES 8190              /* largest max_sample_num: a graph holds max_sample_num + 2 nodes */
+#define FUELMI_TOPO_MAX_RAW 4096                  /* largest max_raw_path / max_raw_path2 / reserve_num */
+#define FUELMI_TOPO_MAX_PATH_POINTS 256           /* points of a shortened or merged path; largest max_path_points */
+#define FUELMI_TOPO_MAX_DIS_POINTS 4096           /* points of discretizePath(path) */
+#define FUELMI_TOPO_MAX_NEIGHBORS 64              /* neighbours of one node */
+#define FUELMI_TOPO_MAX_POINTS_IN 64              /* largest max_start / max_end */
+#define FUELMI_TOPO_MAX_WORKSPACE 8589934592.0    /* bytes, n_prob x workspace of one problem */
+typedef struct {
+  double sample_inflate[3];  /* topo_prm/sample_inflate_x, _y, _z */
+  double clearance;          /* topo_prm/clearance */
+  double ratio_to_short;     /* topo_prm/ratio_to_short */
+  int max_sample_num;        /* topo_prm/max_sample_num: the length of a problem's sample stream */
+  int max_raw_path;          /* topo_prm/max_raw_path */
+  int max_raw_path2;         /* topo_prm/max_raw_path2: also the rows of the raw / filtered path sets */
+  int reserve_num;           /* topo_prm/reserve_num: also the rows of the select set */
+  int max_path_points;       /* stride / cap of a path's points */
+  int max_nodes;             /* stride / cap of the graph's nodes */
+} fuelmi_topo_cfg;
+/* In: start_xyz, end_xyz [n_prob][3]; start_pts [n_prob][max_start][3] with n_start [n_prob], end_pts likewise (the
+ * pointers may be NULL when the stride is 0); samples [n_prob][max_sample_num][3].
+ * Out (status, counts, events required, the others may be NULL): status [n_prob]; counts [n_prob][4]: raw paths found by
+ * the depth-first search, kept by the bucket filter, left by the first pruneEquivalent, selected; events [n_prob][6]: samples rejected by
+ * clearance, guards added, connectors added, connectors moved, samples that saw three guards, shortcut roll-backs;
+ * the pruned graph in list order: n_nodes, node_id / node_type (GraphNode::Guard = 1, Connector = 2) [n_prob][max_nodes],
+ * node_xyz [n_prob][max_nodes][3], nb_off [n_prob][max_nodes + 1] and nb_ids [n_prob][4 max_nodes] (node i's neighbours,
+ * as ids in the reference's order, are nb_ids[nb_off[i] .. nb_off[i + 1]); a problem over max_nodes (status -1) holds
+ * its first max_nodes nodes, and their neighbour ids only as far as the 4 max_nodes slots reach: nb_off never points
+ * past them); the path sets raw_paths / filt_paths
+ * [n_prob][max_raw_path2][max_path_points][3] with raw_len / filt_len [n_prob][max_raw_path2] (the filtered set is
+ * what the caller of findTopoPaths gets back: selectShortPaths erases the paths it takes from it), sel_paths
+ * [n_prob][reserve_num][max_path_points][3] with sel_len and sel_length (pathLength) [n_prob][reserve_num]. */
+int fuelmi_map_topo_paths(fuelmi_map* m, const fuelmi_topo_cfg* cfg, int n_prob, const double* start_xyz,
+                          const double* end_xyz, int max_start, const int* n_start, const double* start_pts, int max_end,
+                          const int* n_end, const double* end_pts, const double* samples, int* status, int* counts,
+                          int* events, int* n_nodes, int* node_id, int* node_type, double* node_xyz, int* nb_off,
+                          int* nb_ids, double* raw_paths, int* raw_len, double* filt_paths, int* filt_len,
+                          double* sel_paths, int* sel_len, double* sel_length);
+/* the kernel's shape for cfg (host only, no device needed): out = {lanes per problem, LDS bytes, workspace bytes per
+ * problem, the guard chunk (guards tested in one step of findVisibGuard), FUELMI_TOPO_MAX_SAMPLES, _MAX_RAW,
+ * _MAX_PATH_POINTS, _MAX_DIS_POINTS, _MAX_NEIGHBORS, nodes of a raw path from which on the problem is UNDEFINED (100),
+ * _MAX_POINTS_IN, _MAX_WORKSPACE}.  cfg is checked like above.  (The neighbour stride is 4 max_nodes, see above.) */
+int fuelmi_topo_plan(const fuelmi_topo_cfg* cfg, long long out[12]);
+/* bytes of the map's grow-only workspace of the topological search (0 before the first call) */
+long long fuelmi_map_topo_pool_bytes(const fuelmi_map* m);
+
+/* ------------------------------------------------------------------------------------------
  * Safety check of planned trajectories: FastPlannerManager::checkTrajCollision
  * (plan_manage/src/planner_manager.cpp:96-118), which the exploration FSM's safetyCallback runs every 50 ms while a
  * trajectory is flown (exploration_manager/src/fast_exploration_fsm.cpp:335-345), for n_prob independent problems in
