@@ -139,6 +139,16 @@ TOPO_OK, TOPO_NO_PATH, TOPO_UNDEFINED = 0, 1, 2
 TOPO_MAX_SAMPLES, TOPO_MAX_RAW, TOPO_MAX_PATH_POINTS, TOPO_MAX_POINTS_IN = 8190, 4096, 256, 64
 
 
+class ColRangeCfg(C.Structure):
+    """fuelmi_colrange_cfg: the spline's degree, TopologyPRM::clearance_ and the strides of control points, events, points."""
+    _fields_ = [("degree", C.c_int), ("max_ctrl", C.c_int), ("max_events", C.c_int), ("max_pts", C.c_int),
+                ("clearance", C.c_double)]
+
+
+COLRANGE_OK, COLRANGE_NO_COLLISION, COLRANGE_ENDS_IN_OBSTACLE, COLRANGE_NONFINITE = 0, 1, 2, 3
+COLRANGE_MAX_EVENTS, GUIDE_MAX_PTS = 4096, 65536
+
+
 class YawCfg(C.Structure):
     """fuelmi_yaw_cfg: planYawExplore's / planYaw's constants and the strides of the control-point / way-point arrays."""
     _fields_ = [("mode", C.c_int), ("pos_degree", C.c_int), ("max_ctrl", C.c_int), ("max_seg", C.c_int),
@@ -339,6 +349,11 @@ SYMBOLS = {
                                         _ip, _ip, _ip, _ip, _ip, _ip, _dp, _ip, _ip, _dp, _ip, _dp, _ip, _dp, _ip, _dp]),
     "fuelmi_topo_plan": (C.c_int, [C.POINTER(TopoCfg), C.POINTER(C.c_longlong)]),
     "fuelmi_map_topo_pool_bytes": (C.c_longlong, [_P]),
+    "fuelmi_map_collision_ranges": (C.c_int, [_P, C.POINTER(ColRangeCfg), C.c_int, _ip, _dp, _dp, _ip, _ip, _ip, _ip, _dp,
+                                              _dp, _dp, _dp, _ip, _dp, _ip, _dp, _dp, _dp]),
+    "fuelmi_colrange_plan": (C.c_int, [C.POINTER(ColRangeCfg), _ip]),
+    "fuelmi_map_guide_points": (C.c_int, [_P, C.c_int, C.c_int, _dp, _ip, _dp, C.c_double, C.c_int, C.c_int, _ip, _ip, _dp,
+                                          _ip, _ip, _ip, _dp]),
     "fuelmi_map_plan_yaws": (C.c_int, [_P, C.POINTER(BsplineCfg), C.POINTER(YawCfg), C.c_int, _ip, _dp, _dp, _dp, _dp, _ip,
                                        _dp, _ip, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp]),
     "fuelmi_bspline_dev_plan_yaws": (C.c_int, [_P, C.POINTER(YawCfg), _dp, _dp, _ip, _dp, _ip, _dp, _dp, _ip, _dp, _dp,

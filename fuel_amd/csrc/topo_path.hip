@@ -196,21 +196,10 @@ __device__ void tp_copy(double* dst, const double* src, int n) {
   __syncthreads();
 }
 
-// point i of discretizePath(path, pt_num) (:427-461); false: no segment found, or the point is not finite (a
-// segment of length zero at the path's head divides 0 by 0)
+// point i of discretizePath(path, pt_num) (:427-461, path_internal.h); false: no segment found, or the point is not
+// finite (a segment of length zero at the path's head divides 0 by 0)
 __device__ bool tp_disc_point(const double* path, int n, const double* len, int pt_num, int i, double o[3]) {
-  const double dl = len[n - 1] / double(pt_num - 1);
-  const double cur_l = double(i) * dl;
-  int idx = -1;
-  for (int j = 0; j < n - 1; ++j)
-    if (cur_l >= len[j] - 1e-4 && cur_l <= len[j + 1] + 1e-4) {
-      idx = j;
-      break;
-    }
-  if (idx < 0) return false;
-  const double lambda = (cur_l - len[idx]) / (len[idx + 1] - len[idx]);
-  for (int k = 0; k < 3; ++k) o[k] = (1 - lambda) * path[3 * idx + k] + lambda * path[3 * idx + 3 + k];
-  return tp_fin3(o);
+  return path_disc_point(path, n, len, pt_num, i, o) && tp_fin3(o);
 }
 
 // sameTopoPath (:379-402): 1 / 0, or TP_UNDEF where the reference's behaviour is undefined
@@ -793,13 +782,7 @@ __global__ void __launch_bounds__(TP_NT) k_topo_path(Geo g, TopoArgs T) {
 
 // the largest k for which the reference's f64 `res * sqrt(k) <= thresh` holds, as an f32 cut between the device's
 // values for k and k + 1 (esdf.hip: f32 res times an approximate f32 square root, a few ulp from either)
-float topo_cut(double res, double thresh) {
-  long k = (long)std::floor((thresh / res) * (thresh / res));
-  if (k < 0) k = 0;
-  while (res * std::sqrt((double)(k + 1)) <= thresh) ++k;
-  while (k > 0 && !(res * std::sqrt((double)k) <= thresh)) --k;
-  return (float)((double)(float)res * std::sqrt((double)k + 0.5));
-}
+float topo_cut(double res, double thresh) { return field_cut(res, thresh, false); }  // (path_internal.h)
 
 // the workspace of n problems, carved from `base` (null: the sizing pass)
 size_t topo_workspace(const fuelmi_topo_cfg* cfg, size_t n, unsigned char* base, TopoArgs* T) {

@@ -5,6 +5,9 @@
 // default_random_engine, seeded from random_device like the reference's, or from topo_prm/seed when that is >= 0.
 // Dropped: topo_prm/max_sample_time (exactly max_sample_num samples are taken), short_cut_num (read and never used by the
 // reference) and parallel_shortcut (threading only).  pathLength and pathToGuidePts are host loops.
+// Added for the rest of topoReplan's chain, both on the device: findCollisionRange (the reference keeps it private in
+// FastPlannerManager, :636-691, where it reads the host's distance buffer; here it takes the local segment's control
+// points and needs no ESDF mirror) and guidePoints (the head of optimizeTopoBspline, :553-577).
 #ifndef _TOPO_PRM_H
 #define _TOPO_PRM_H
 
@@ -123,6 +126,63 @@ public:
     take(raw, raw_len, r2, raw_paths);
     take(filt, filt_len, r2, filtered_paths);
     take(sel, sel_len, rs, select_paths);
+  }
+
+  // FastPlannerManager::findCollisionRange for the uniform position spline (ctrl_pts [n][3], knot span dt) against the
+  // device's distance field with clearance_ (fuelmi_map_collision_ranges, one problem).  Returns the problem's status:
+  // FUELMI_COLRANGE_OK (the four vectors as the reference fills them), _NO_COLLISION (all empty), _ENDS_IN_OBSTACLE
+  // (colli_start has its one point), _NONFINITE, -1 over a cap (the vectors hold what fitted), or, where the library
+  // refuses the call, its negative return value (fuelmi_last_error() says why; the vectors are empty).
+  int findCollisionRange(const Eigen::MatrixXd& ctrl_pts, double dt, int degree, vector<Eigen::Vector3d>& colli_start,
+                         vector<Eigen::Vector3d>& colli_end, vector<Eigen::Vector3d>& start_pts,
+                         vector<Eigen::Vector3d>& end_pts) {
+    colli_start.clear(), colli_end.clear(), start_pts.clear(), end_pts.clear();
+    const int n = (int)ctrl_pts.rows();
+    fuelmi_colrange_cfg c;
+    c.degree = degree, c.max_ctrl = n > degree + 1 ? n : degree + 1, c.max_events = 64, c.max_pts = FUELMI_TOPO_MAX_POINTS_IN;
+    c.clearance = clearance_;
+    vector<double> pos(3 * (size_t)c.max_ctrl);
+    for (int i = 0; i < n; ++i)
+      for (int k = 0; k < 3; ++k) pos[3 * i + k] = ctrl_pts(i, k);
+    const size_t ev = c.max_events, mp = c.max_pts;
+    vector<double> cs(3 * ev), ce(3 * ev), sp(3 * mp), ep(3 * mp);
+    int status = 0, n_ticks = 0, n_se = 0, n_ee = 0, n_sp = 0, n_ep = 0;
+    double t_s = 0.0, t_e = 0.0, first[3], last[3];
+    const int rc = fuelmi_map_collision_ranges(edt_environment_->sdf_map_->device(), &c, 1, &n, pos.data(), &dt, &status,
+                                               &n_ticks, &n_se, &n_ee, &t_s, &t_e, cs.data(), ce.data(), &n_sp, sp.data(),
+                                               &n_ep, ep.data(), first, last);
+    if (rc != FUELMI_OK && rc != FUELMI_ELIMIT) {
+      ROS_ERROR("[Topo]: fuelmi_map_collision_ranges: %s", fuelmi_last_error());
+      return rc;
+    }
+    auto take = [](const vector<double>& a, int count, size_t cap, vector<Eigen::Vector3d>& out) {
+      for (size_t i = 0; i < (size_t)count && i < cap; ++i) out.push_back(Eigen::Vector3d(a[3 * i], a[3 * i + 1], a[3 * i + 2]));
+    };
+    take(cs, n_se, ev, colli_start), take(ce, n_ee, ev, colli_end), take(sp, n_sp, mp, start_pts), take(ep, n_ep, mp, end_pts);
+    return status;
+  }
+
+  // Lines 553-577 of optimizeTopoBspline for one guide path (fuelmi_map_guide_points): seg_num, the knot span dt, the rows
+  // n_ctrl of the control points reparamLocalTraj would return for `duration`, and the guide points of `degree` (3 and
+  // 5: n_ctrl - 6 of them, 4: n_ctrl - 8).  Returns FUELMI_TOPO_OK, FUELMI_TOPO_UNDEFINED (guide_pts empty), -1 over a
+  // cap, or the library's negative return value where it refuses the call.
+  int guidePoints(const vector<Eigen::Vector3d>& path, double duration, double ctrl_pt_dist, int degree, int& seg_num,
+                  double& dt, int& n_ctrl, vector<Eigen::Vector3d>& guide_pts) {
+    guide_pts.clear();
+    seg_num = 0, dt = 0.0, n_ctrl = 0;
+    const int len = (int)path.size(), mpp = len > 0 ? len : 1, max_guide = 1024;
+    vector<double> p(3 * (size_t)mpp), g(3 * (size_t)max_guide);
+    for (int i = 0; i < len; ++i)
+      for (int k = 0; k < 3; ++k) p[3 * i + k] = path[i](k);
+    int status = 0, n_pts = 0, n_guide = 0;
+    const int rc = fuelmi_map_guide_points(edt_environment_->sdf_map_->device(), 1, mpp, p.data(), &len, &duration, ctrl_pt_dist,
+                                           degree, max_guide, &status, &seg_num, &dt, &n_pts, &n_ctrl, &n_guide, g.data());
+    if (rc != FUELMI_OK && rc != FUELMI_ELIMIT) {
+      ROS_ERROR("[Topo]: fuelmi_map_guide_points: %s", fuelmi_last_error());
+      return rc;
+    }
+    for (int i = 0; i < n_guide && i < max_guide; ++i) guide_pts.push_back(Eigen::Vector3d(g[3 * i], g[3 * i + 1], g[3 * i + 2]));
+    return status;
   }
 
   double pathLength(const vector<Eigen::Vector3d>& path) {

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BsplineBatch, BsplineCfg, CloudCfg, FrontierCfg, GoalCfg, KinoCfg, MapCfg, MapInfo, PathCfg, RefineCfg, RenderCfg, TopoCfg, TrajAdjCfg, TrajChkCfg, TrajSmpCfg, TspCfg,
+from ._lib import (BsplineBatch, BsplineCfg, CloudCfg, ColRangeCfg, FrontierCfg, GoalCfg, KinoCfg, MapCfg, MapInfo, PathCfg, RefineCfg, RenderCfg, TopoCfg, TrajAdjCfg, TrajChkCfg, TrajSmpCfg, TspCfg,
                    WptrajCfg, YawCfg, check, lib)
 
 # exploration.launch / algorithm.xml defaults (exploration_manager/launch/algorithm.xml:33-59,170-181)
@@ -80,6 +80,11 @@ def topo_cfg(sample_inflate=(1.0, 3.5, 1.0), clearance=0.2, ratio_to_short=5.5, 
     return TopoCfg((C.c_double * 3)(*[float(v) for v in sample_inflate]), float(clearance), float(ratio_to_short),
                    int(max_sample_num), int(max_raw_path), int(max_raw_path2), int(reserve_num), int(max_path_points),
                    int(max_nodes))
+
+
+def colrange_cfg(degree=3, max_ctrl=4, max_events=8, max_pts=_lib.TOPO_MAX_POINTS_IN, clearance=0.2):
+    """fuelmi_colrange_cfg: the spline's degree, topo_prm/clearance and the strides of the event and point arrays"""
+    return ColRangeCfg(int(degree), int(max_ctrl), int(max_events), int(max_pts), float(clearance))
 
 
 def traj_check_cfg(degree=3, max_ctrl=4, step=0.02, max_radius=6.0):
@@ -725,6 +730,77 @@ class SDFMap:
     def topo_pool_bytes(self):
         """bytes of the map's grow-only workspace of topo_paths"""
         return int(self.L.fuelmi_map_topo_pool_bytes(self.h))
+
+    # --- collision ranges and guide points of guided replanning (include/fuelmi.h fuelmi_map_collision_ranges) ---
+    COLRANGE_OK, COLRANGE_NO_COLLISION = _lib.COLRANGE_OK, _lib.COLRANGE_NO_COLLISION
+    COLRANGE_ENDS_IN_OBSTACLE, COLRANGE_NONFINITE = _lib.COLRANGE_ENDS_IN_OBSTACLE, _lib.COLRANGE_NONFINITE
+
+    def collision_ranges(self, pos_ctrl, knot_span, allow_limit=False, max_ctrl=None, **cfg):
+        """findCollisionRange per problem against the distance field on the device: pos_ctrl is a list of [n_ctrl, 3]
+        control-point arrays of uniform position splines, knot_span [n]; cfg: the fields of colrange_cfg().  Returns a
+        dict of arrays: status (COLRANGE_*; -1: over max_events / max_pts / the tick cap), n_ticks, n_start_events,
+        n_end_events, t_s, t_e, colli_start / colli_end [n, max_events, 3], n_start_pts / n_end_pts, start_pts / end_pts
+        [n, max_pts, 3] (the layout topo_paths' C entry takes), first_start / last_end [n, 3]; limit.  FUELMI_ELIMIT
+        raises FuelmiError unless allow_limit."""
+        pos = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in pos_ctrl]
+        n = len(pos)
+        maxc = int(max_ctrl) if max_ctrl is not None else max([len(p) for p in pos] + [4])
+        c = colrange_cfg(max_ctrl=maxc, **cfg)
+        n_ctrl = np.array([len(p) for p in pos], dtype=np.int32)
+        arr = np.zeros((n, max(maxc, 0), 3))
+        for b, p in enumerate(pos):
+            k = min(len(p), arr.shape[1])
+            arr[b, :k] = p[:k]
+        knot = np.ascontiguousarray(np.broadcast_to(np.asarray(knot_span, dtype=np.float64), (n,)))
+        ev, mp = max(c.max_events, 0), max(c.max_pts, 0)
+        o = {k: np.zeros(n, dtype=np.int32) for k in ("status", "n_ticks", "n_start_events", "n_end_events", "n_start_pts",
+                                                      "n_end_pts")}
+        o.update(t_s=np.zeros(n), t_e=np.zeros(n), colli_start=np.zeros((n, ev, 3)), colli_end=np.zeros((n, ev, 3)),
+                 start_pts=np.zeros((n, mp, 3)), end_pts=np.zeros((n, mp, 3)), first_start=np.zeros((n, 3)),
+                 last_end=np.zeros((n, 3)))
+        rc = self.L.fuelmi_map_collision_ranges(
+            self.h, C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(knot), _ip(o["status"]), _ip(o["n_ticks"]),
+            _ip(o["n_start_events"]), _ip(o["n_end_events"]), _dp(o["t_s"]), _dp(o["t_e"]), _dp(o["colli_start"]),
+            _dp(o["colli_end"]), _ip(o["n_start_pts"]), _dp(o["start_pts"]), _ip(o["n_end_pts"]), _dp(o["end_pts"]),
+            _dp(o["first_start"]), _dp(o["last_end"]))
+        if not (allow_limit and rc == -5):
+            check(rc)
+        o["limit"] = rc == -5
+        return o
+
+    @staticmethod
+    def colrange_plan(cfg):
+        """host only: dict(lanes, lds_bytes, waves, max_ticks, max_ctrl, max_pts) of the collision-range kernel for a
+        ColRangeCfg"""
+        out = (C.c_int * 6)()
+        check(lib().fuelmi_colrange_plan(C.byref(cfg), out))
+        return dict(zip(("lanes", "lds_bytes", "waves", "max_ticks", "max_ctrl", "max_pts"), [int(v) for v in out]))
+
+    def guide_points(self, paths, duration, ctrl_pt_dist=0.5, degree=3, max_guide=64, max_path_points=None,
+                     allow_limit=False):
+        """the head of optimizeTopoBspline per guide path: paths is a list of [k, 3] arrays (topo_paths' "sel"),
+        duration [n] the local segment's duration.  Returns a dict of arrays: status (TOPO_OK, TOPO_UNDEFINED; -1: over
+        max_guide or the point cap), seg_num, dt, n_pts, n_ctrl, n_guide, guide_pts [n, max_guide, 3] (rows as
+        BsplineBatchProblem's guide_pts takes them for degrees 3 and 4); limit."""
+        ps = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in paths]
+        n = len(ps)
+        mpp = int(max_path_points) if max_path_points is not None else max([len(p) for p in ps] + [1])
+        arr = np.zeros((n, max(mpp, 0), 3))
+        for b, p in enumerate(ps):
+            k = min(len(p), arr.shape[1])
+            arr[b, :k] = p[:k]
+        plen = np.array([len(p) for p in ps], dtype=np.int32)
+        dur = np.ascontiguousarray(np.broadcast_to(np.asarray(duration, dtype=np.float64), (n,)))
+        mg = max(int(max_guide), 0)
+        o = {k: np.zeros(n, dtype=np.int32) for k in ("status", "seg_num", "n_pts", "n_ctrl", "n_guide")}
+        o.update(dt=np.zeros(n), guide_pts=np.zeros((n, mg, 3)))
+        rc = self.L.fuelmi_map_guide_points(self.h, n, mpp, _dp(arr), _ip(plen), _dp(dur), float(ctrl_pt_dist), int(degree),
+                                            int(max_guide), _ip(o["status"]), _ip(o["seg_num"]), _dp(o["dt"]),
+                                            _ip(o["n_pts"]), _ip(o["n_ctrl"]), _ip(o["n_guide"]), _dp(o["guide_pts"]))
+        if not (allow_limit and rc == -5):
+            check(rc)
+        o["limit"] = rc == -5
+        return o
 
     # --- the yaw trajectory of a position spline (include/fuelmi.h fuelmi_map_plan_yaws) ---
     YAW_EXPLORE, YAW_FOLLOW, YAW_OK, YAW_DEGENERATE = _lib.YAW_EXPLORE, _lib.YAW_FOLLOW, _lib.YAW_OK, _lib.YAW_DEGENERATE

@@ -1037,6 +1037,104 @@ int fuelmi_topo_plan(const fuelmi_topo_cfg* cfg, long long out[12]);
 long long fuelmi_map_topo_pool_bytes(const fuelmi_map* m);
 
 /* ------------------------------------------------------------------------------------------
+ * Collision ranges of the initial local segment: FastPlannerManager::findCollisionRange
+ * (plan_manage/src/planner_manager.cpp:636-691), the producer of colli_start.front(), colli_end.back(), start_pts and
+ * end_pts that topoReplan (:418-432) hands to findTopoPaths, for n_prob UNIFORM position splines on one map in one call.
+ * The reference's copy is private and reads the host's distance_buffer_; this one reads the device's field, no host
+ * mirror is read or needed.  Per problem, everything f64 in this order:
+ *   1. knots as setUniformBspline builds them (see fuelmi_map_check_trajs: accumulated); t_m = u[p], t_mp = u[m - p].
+ *   2. tick k = 0, 1, ...: tc starts at t_m and is ACCUMULATED by += 0.05 (never k * 0.05), while tc <= t_mp + 1e-4;
+ *      the point is evaluateDeBoor(tc) with its clamp; safe = !(getDistance(point) < clearance), where getDistance reads
+ *      the voxel of floor((p - origin) * resolution_inv) and an index outside the map reads -1: UNSAFE for every accepted
+ *      clearance.  The comparison is the reference's f64 `res * sqrt(k) < clearance`, STRICT, taken on the device's f32
+ *      field through a host-computed cut (as the topological search takes its `<=`, above).
+ *   3. events, last_safe = true at first: safe -> unsafe pushes evaluateDeBoor(tc - 0.05) to colli_start (the time is
+ *      recomputed from this tick's tc) and `if (t_s < 0) t_s = tc - 0.05`, t_s = -1 at first -- an unsafe tick 0 leaves
+ *      t_s = -0.05 < 0, so the NEXT start event overwrites it; unsafe -> safe pushes the point to colli_end, t_e = tc.
+ *   4. status FUELMI_COLRANGE_NO_COLLISION without a start event; FUELMI_COLRANGE_ENDS_IN_OBSTACLE with one start event
+ *      and no end event (topoReplan does not replan then); otherwise FUELMI_COLRANGE_OK and start_pts / end_pts as
+ *      :665-690: sn = ceil((t_s - t_m) / dt), dt' = (t_s - t_m) / sn, points at tc = t_m, += dt' (accumulated) while
+ *      tc <= t_s + 1e-4; the end side from t_e to t_mp likewise when its dt' > 1e-4, else the single point at t_mp.
+ *      sn = 0 is what IEEE makes of it: 0 / 0 = NaN step, exactly one start point; negative / 0 = -inf, no start point;
+ *      on the end side both fall to the single point.
+ * Outputs per problem: status; n_ticks (loop bodies); n_start_events / n_end_events (the sizes of colli_start /
+ * colli_end); t_s (-1 without a start event), t_e (0 without an end event); colli_start / colli_end [max_events][3];
+ * start_pts / end_pts [max_pts][3] with n_start_pts / n_end_pts, in the layout fuelmi_map_topo_paths takes for
+ * max_start = max_end = max_pts; first_start = colli_start.front() and last_end = colli_end.back() [3], the two points
+ * topoReplan passes on (zeros where there is none).  Rows that are not written are zero.
+ * Defined where the reference is not:
+ *   FUELMI_COLRANGE_NONFINITE  a control point or the knot span is not finite (or the knots overflow): nothing is
+ *               evaluated, every other output of the problem is zero, the other problems complete.
+ *   -1          more than max_events start or end events, more than max_pts start or end points, or more than
+ *               FUELMI_TRAJCHK_MAX_SAMPLES ticks: the counts are full (n_ticks stops at the cap, and a problem over the
+ *               tick cap has no start_pts / end_pts), the arrays hold their first rows, the call returns FUELMI_ELIMIT.
+ * FUELMI_EINVAL before any launch: pointers; degree outside 3..5; clearance < 0 or not finite; max_events or max_pts < 1;
+ * n_ctrl[i] < degree + 1 or > max_ctrl; knot span <= 0; a finite coordinate with |coordinate| >= 1e7.  FUELMI_ELIMIT
+ * before any launch: max_ctrl > FUELMI_TRAJCHK_MAX_CTRL, max_events > FUELMI_COLRANGE_MAX_EVENTS, max_pts >
+ * FUELMI_TOPO_MAX_POINTS_IN.  n_prob = 0 is FUELMI_OK.  Runs on the map's stream behind whatever ESDF update was queued
+ * before it: host arrays in and out, synchronous, one thread at a time per map; its scratch is one grow-only allocation
+ * on the map.  One 64-lane wave per problem, 64 ticks a window; a result does not depend on the problem's place in the
+ * batch.  Out of scope: paramLocalTraj / reparamLocalTraj (the caller supplies the control points), evaluateCoarseEDT
+ * with time >= 0, moved knots as input, chaining the outputs on the device.
+ * ---------------------------------------------------------------------------------------- */
+#define FUELMI_COLRANGE_OK 0
+#define FUELMI_COLRANGE_NO_COLLISION 1
+#define FUELMI_COLRANGE_ENDS_IN_OBSTACLE 2
+#define FUELMI_COLRANGE_NONFINITE 3
+#define FUELMI_COLRANGE_MAX_EVENTS 4096       /* largest max_events */
+typedef struct {
+  int degree;          /* degree of the position spline, 3..5 (pp_.bspline_degree_) */
+  int max_ctrl;        /* stride of pos_ctrl */
+  int max_events;      /* stride / cap of colli_start and colli_end */
+  int max_pts;         /* stride / cap of start_pts and end_pts */
+  double clearance;    /* topo_prm/clearance (TopologyPRM::clearance_) */
+} fuelmi_colrange_cfg;
+/* pos_ctrl [n_prob][max_ctrl][3], n_ctrl / knot_span [n_prob].  Out, per problem, all required: see above. */
+int fuelmi_map_collision_ranges(fuelmi_map* m, const fuelmi_colrange_cfg* cfg, int n_prob, const int* n_ctrl,
+                                const double* pos_ctrl, const double* knot_span, int* status, int* n_ticks,
+                                int* n_start_events, int* n_end_events, double* t_s, double* t_e, double* colli_start,
+                                double* colli_end, int* n_start_pts, double* start_pts, int* n_end_pts, double* end_pts,
+                                double* first_start, double* last_end);
+/* the kernel's shape for cfg (host only, no device needed): out6 = {lanes per problem (= ticks per window), dynamic LDS
+ * bytes of a workgroup, problems per workgroup, the tick cap, largest max_ctrl, largest max_pts}.  cfg is checked like
+ * above. */
+int fuelmi_colrange_plan(const fuelmi_colrange_cfg* cfg, int out6[6]);
+
+/* ------------------------------------------------------------------------------------------
+ * Guide points of a topological guide path: the head of FastPlannerManager::optimizeTopoBspline
+ * (plan_manage/src/planner_manager.cpp:553-577) for n_path paths in one call -- sel_paths / sel_len of
+ * fuelmi_map_topo_paths as they stand.  It hangs on the map for its stream and scratch and reads no voxel.  Per path,
+ * everything f64 in this order:
+ *   1. seg_num = max(6, int(pathLength(path) / ctrl_pt_dist)), the length summed left to right (topo_prm.cpp:417-425);
+ *   2. dt = duration / double(seg_num);
+ *   3. n_pts = the bodies of `for (tp = 0; tp <= duration + 1e-4; tp += dt)`, tp ACCUMULATED (getTrajInfoInDuration,
+ *      plan_container.hpp:77): the points reparamLocalTraj samples;
+ *   4. n_ctrl = n_pts + 2, the rows parameterizeToBspline returns;
+ *   5. degree 3 or 5: discretizePath(path, n_ctrl - 2) without its first two and last two points, n_guide = n_ctrl - 6
+ *      (for degree 5 this is the reference's count, NOT the N - 2 order = n_ctrl - 10 rows fuelmi_bspline_problem's guide
+ *      layout holds, so a degree-5 result does not fit that layout as it stands); degree 4: discretizePath(path, 2 n_ctrl - 7), the odd i with 5 <= i <= size - 6,
+ *      n_guide = n_ctrl - 8.  For degrees 3 and 4 the rows are what fuelmi_bspline_problem.guide_pts takes.
+ *   discretizePath(path, pt_num) is topo_prm.cpp:427-461, literal: the FIRST segment whose +-1e-4 range holds the
+ *   point's arc length; lambda may leave [0, 1]; a chosen segment of length zero gives the NaN or inf IEEE gives, and it
+ *   is written out.
+ * Outputs per path: status, seg_num, dt, n_pts, n_ctrl, n_guide, guide_pts [max_guide][3] (rows not written are zero).
+ * Status: FUELMI_TOPO_OK; FUELMI_TOPO_UNDEFINED where the reference's behaviour is undefined -- path_len < 2, a length /
+ * ctrl_pt_dist that is not finite (the cast to int), a discretised point without a segment (every point of
+ * discretizePath counts, kept or not): n_guide = 0 and no guide point is written, what was computed before that stays
+ * (seg_num .. n_ctrl; all zero for the first two causes), the other paths complete and the call stays FUELMI_OK;
+ * -1: seg_num or n_pts over FUELMI_GUIDE_MAX_PTS (nothing further is computed) or n_guide > max_guide (full count, the
+ * first max_guide rows), call status FUELMI_ELIMIT.  Path coordinates are NOT checked: every value is defined above.
+ * FUELMI_EINVAL before any launch: pointers, degree outside 3..5, ctrl_pt_dist or a duration not finite or <= 0,
+ * max_path_points < 1, path_len[i] outside 0 .. max_path_points, max_guide < 1.  FUELMI_ELIMIT before any launch:
+ * max_path_points > FUELMI_TOPO_MAX_PATH_POINTS, max_guide > FUELMI_GUIDE_MAX_PTS.  n_path = 0 is FUELMI_OK.  One
+ * 64-lane wave per path, one lane per discretised point; synchronous on the map's stream.
+ * ---------------------------------------------------------------------------------------- */
+#define FUELMI_GUIDE_MAX_PTS 65536            /* largest seg_num, n_pts and max_guide */
+int fuelmi_map_guide_points(fuelmi_map* m, int n_path, int max_path_points, const double* paths, const int* path_len,
+                            const double* duration, double ctrl_pt_dist, int degree, int max_guide, int* status,
+                            int* seg_num, double* dt, int* n_pts, int* n_ctrl, int* n_guide, double* guide_pts);
+
+/* ------------------------------------------------------------------------------------------
  * Safety check of planned trajectories: FastPlannerManager::checkTrajCollision
  * (plan_manage/src/planner_manager.cpp:96-118), which the exploration FSM's safetyCallback runs every 50 ms while a
  * trajectory is flown (exploration_manager/src/fast_exploration_fsm.cpp:335-345), for n_prob independent problems in
