@@ -1,8 +1,8 @@
 // A host build of k_topo_path's own text and topo_cut (fuel_amd/csrc/topo_path.hip between "namespace {" and the
 // workspace's sizing, cut out by tests/golden/check_topo_host_build.py into kernel.inc) on the lanes of
 // tests/golden/host_lanes.h.  Reads the input file tests/golden/make_topo_golden.py writes for the reference's driver,
-// the field as f32 and the sample stream as f64, and prints every result; every array the kernel sees is a heap block
-// of its exact size.
+// the field as f32 and the sample stream as f64 (one stream that every problem takes, or one per problem), and prints
+// every result; every array the kernel sees is a heap block of its exact size.
 //   host_kernel <in.txt> <field.f32> <samples.f64> <max_path_points> <max_nodes>
 #include "host_lanes.h"
 #include "kernel.inc"
@@ -38,11 +38,16 @@ int main(int argc, char** argv) {
   float* dist = block<float>(g.N);
   std::ifstream(argv[2], std::ios::binary).read((char*)dist, (size_t)g.N * 4);
   const size_t S = c.max_sample_num, nn = n;
-  double* one = block<double>(S * 3);
-  std::ifstream(argv[3], std::ios::binary).read((char*)one, S * 3 * 8);
   double* smp = block<double>(nn * S * 3);
-  for (size_t b = 0; b < nn; ++b) memcpy(smp + b * S * 3, one, S * 3 * 8);
-  const int MS = 8, ME = 8;
+  {
+    std::ifstream f(argv[3], std::ios::binary);
+    f.read((char*)smp, nn * S * 3 * 8);
+    const size_t got = (size_t)f.gcount();
+    if (got != nn * S * 3 * 8 && got != S * 3 * 8) return 2;
+    if (got == S * 3 * 8)
+      for (size_t b = 1; b < nn; ++b) memcpy(smp + b * S * 3, smp, S * 3 * 8);
+  }
+  const int MS = FUELMI_TOPO_MAX_POINTS_IN, ME = FUELMI_TOPO_MAX_POINTS_IN;
   double *inp = block<double>(nn * 6), *sp = block<double>(nn * MS * 3), *ep = block<double>(nn * ME * 3);
   int *nsp = block<int>(nn), *nep = block<int>(nn);
   for (int b = 0; b < n; ++b) {

@@ -209,10 +209,12 @@ def test_new_symbols_exported_and_declared(tmp_path):
 
 def test_kernel_text_on_the_host_under_the_sanitizers():
     """tests/golden/check_topo_host_build.py as a child process: k_topo_path's own text, a thread per lane, under the address
-    and undefined-behaviour sanitizers, equals the restatement in `cut` mode on every scene, on the f32 field and on it
-    moved by +2 ulp (the only check of the kernel's barriers that needs no device)"""
+    and undefined-behaviour sanitizers, equals the restatement in `cut` mode on every scene and every edge scene
+    (topo_cases.edge_scenes), on the f32 field and on it moved by +2 ulp, and on `forest10` cut at two more max_nodes (the
+    only check of the kernel's barriers that needs no device)"""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "golden", "check_topo_host_build.py")],
                        capture_output=True, text=True, cwd=ROOT)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-2000:])
     lines = p.stdout.splitlines()
-    assert len(lines) == 2 * len(SCENES) and all(l.endswith("identical") for l in lines), lines
+    want = 2 * (len(SCENES) + len(tc.edge_scenes())) + len(tc.FOREST10_MAX_NODES)
+    assert len(lines) == want and all(l.endswith("identical") for l in lines), lines

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import topo_cases as tc
+import topo_device as td
 import topo_ref as tr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,53 +24,14 @@ if ROOT not in sys.path:
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(ROOT, "tests", "golden", "topo")
 SCENES = tc.scenes()
-_maps, _refs = {}, {}
-
-
-def _device_map(blocks):
-    """(the device map of the blocks, its distance field as an [nx, ny, nz] f64 array)"""
-    import fuel_amd
-    key = repr(blocks)
-    if key not in _maps:
-        gm = fuel_amd.SDFMap(tc.MAP_SIZE, device=0)
-        assert gm.nvox == tc.NVOX and np.array_equal(gm.origin, tc.ORIGIN) and gm.res == tc.RES
-        gm.uploadOccupancy(tc.occupancy(blocks))
-        gm.setLocalBound((0, 0, 0), tuple(v - 1 for v in tc.NVOX))
-        gm.clearAndInflateLocalMap()
-        gm.updateESDF3d()
-        h = gm.syncHost(inflate=True, distance=True)
-        assert np.array_equal(h["inflate"].reshape(tc.NVOX) == 1, tc.sources(blocks))
-        dist = h["distance"].reshape(tc.NVOX)
-        k = tc.squared_distance(tc.sources(blocks))
-        if (k < 0).all():
-            assert (dist > 1e30).all()
-        else:
-            want = tc.RES * np.sqrt(k.astype(np.float64))
-            with np.errstate(over="ignore"):
-                d32 = dist.astype(np.float32)
-            assert np.array_equal(d32.astype(np.float64), dist)  # the mirror holds the device's f32 values
-            assert np.all(np.abs(dist - want) <= 2 * np.spacing(want.astype(np.float32)).astype(np.float64))
-        _maps[key] = (gm, dist)
-    return _maps[key]
+_refs = {}
+_device_map, _run, _bits, _assert_equal = td.device_map, td.run, td.bits, td.assert_equal
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _close_maps():
     yield
-    for gm, _ in _maps.values():
-        gm.close()
-    _maps.clear()
-
-
-def _cfg(sc):
-    return {k: v for k, v in sc["cfg"].items() if k != "max_sample_num"}
-
-
-def _run(gm, sc, probs=None, **kw):
-    probs = sc["probs"] if probs is None else probs
-    return gm.topo_paths([p["start"] for p in probs], [p["end"] for p in probs], [sc["samples"]] * len(probs),
-                         [p["start_pts"] or None for p in probs], [p["end_pts"] or None for p in probs],
-                         **dict(_cfg(sc), **kw))
+    td.close_maps()
 
 
 def _restated(name):
@@ -77,27 +39,6 @@ def _restated(name):
         sc = SCENES[name]
         _refs[name] = tc.run_ref(sc, "cut", _device_map(sc["blocks"])[1])
     return _refs[name]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).tobytes()
-
-
-def _assert_equal(out, b, r, cfg):
-    """problem b of a device result against a result of the restatement, bit for bit"""
-    mpp, maxn = cfg["max_path_points"], cfg["max_nodes"]
-    over = any(len(p) > mpp for k in ("raw", "filt", "sel") for p in r[k]) or len(r["nodes"]) > maxn
-    assert out["status"][b] == (-1 if over and r["status"] in (tr.OK, tr.NO_PATH) else r["status"])
-    assert list(out["counts"][b]) == list(r["counts"]) and list(out["events"][b]) == list(r["events"])
-    assert out["n_nodes"][b] == len(r["nodes"])
-    for got, want in zip(out["nodes"][b], r["nodes"][:maxn]):
-        assert (got[0], got[1]) == (want[0], want[1]) and _bits(got[2]) == _bits(want[2]) and list(got[3]) == list(want[3])
-    for key in ("raw", "filt", "sel"):
-        lens = [int(v) for v in out[key + "_len"][b] if v > 0]
-        assert lens == [len(p) for p in r[key]], key
-        for got, want in zip(out[key][b], r[key]):
-            assert _bits(got) == _bits(want[:mpp]), key
-    assert _bits(out["sel_length"][b][:len(r["sel"])]) == _bits(r["sel_length"])
 
 
 @pytest.mark.parametrize("name", list(SCENES))

@@ -7,7 +7,20 @@ as an array and a decision mode:
         values for kmax and kmax + 1, kmax the largest k with res * sqrt(k) <= thresh in f64
 Returns what fuelmi_map_topo_paths returns (status, counts, events, the pruned graph, the three path sets, pathLength of
 the select paths) plus, per path point, whether a gradient push produced it.  The kernel's own caps are restated too
-(status -1 without path outputs); max_nodes / max_path_points are the caller's business (the lists here are complete)."""
+(status -1 without path outputs); max_nodes / max_path_points are the caller's business (the lists here are complete).
+
+A witness trace (TopoPRM(..., trace={}), off by default; it changes no result) records what the kernel's lane windows, rounds
+and caps would see of a problem, so that a test can assert that a scene reaches the edge it was made for:
+  trace["shortcut"]   per pass of shortcutPath: nd, the windows of the kernel's loop as (first point, live lanes, lane of the
+                      first blocked point or None), the blocked points committed, whether the pass was rolled back
+  trace["same_topo"]  per sameTopoPath call: pt_num, the index of the first pair that is not visible (or None)
+  trace["graph"]      per createGraph: the graph before pruneGraph as (id, kind, neighbour ids), its nodes and guards, the
+                      largest neighbour count, the largest place in the guard list of a visible guard, the rounds of the
+                      kernel's synchronous prune (prune_rounds), the surviving nodes
+  trace["search"]     per searchPaths: the deepest stack of the depth-first search, the raw paths found, and per raw length
+                      (nodes, paths of that length, those the filter kept)
+prune_restart / prune_rounds are pruneGraph on plain (id, neighbour ids) lists: the reference's restart after every erase,
+and the kernel's rounds."""
 import math
 
 import numpy as np
@@ -151,14 +164,87 @@ def path_length(path):
     return length
 
 
+LANES = 64  # the kernel's lanes: the width of a window of shortcutPath, a stride of sameTopoPath and pruneGraph
+
+
+def windows_of(blocked):
+    """the windows k_topo_path's shortcut loop walks over the verdicts of dis[1:] (blocked[i - 1]: point i is not visible
+    from the back it was tested against): (first point, live lanes, lane of the first blocked point or None)"""
+    nd, out, i = len(blocked) + 1, [], 1
+    while i < nd:
+        live = min(LANES, nd - i)
+        first = next((t for t in range(live) if blocked[i + t - 1]), None)
+        out.append((i, live, first))
+        i += LANES if first is None else first + 1
+    return out
+
+
+def prune_restart(nodes):
+    """pruneGraph (:272-299) on [(id, [neighbour ids])]: the reference's scan, restarted after every erase"""
+    graph = [(i, list(nb)) for i, nb in nodes]
+    if len(graph) > 2:
+        i = 0
+        while i < len(graph) and len(graph) > 2:
+            ident, nb = graph[i]
+            if ident <= 1:
+                i += 1
+                continue
+            if len(nb) <= 1:
+                for _, onb in graph:
+                    if ident in onb:
+                        onb.remove(ident)
+                del graph[i]
+                i = 0
+            i += 1
+    return graph
+
+
+def prune_rounds(nodes):
+    """pruneGraph the way k_topo_path does it: in a round every live node past the first two with at most one neighbour
+    is marked, then every live node's neighbour list is compacted in place, front to back, over the marked ones, then
+    the marked ones are erased; until a round marks nothing.  -> (the graph, the rounds that marked something)"""
+    ids = [i for i, _ in nodes]
+    at = {ident: k for k, ident in enumerate(ids)}
+    nb = [list(v) for _, v in nodes]
+    alive = [1] * len(ids)
+    rounds = 0
+    while True:
+        marked = False
+        for n in range(len(ids)):
+            if ids[n] > 1 and alive[n] == 1 and len(nb[n]) <= 1:
+                alive[n], marked = 2, True
+        if not marked:
+            break
+        rounds += 1
+        for n in range(len(ids)):
+            if alive[n] != 1:
+                continue
+            kept = 0
+            for i in range(len(nb[n])):
+                o = nb[n][i]
+                if alive[at[o]] == 2:
+                    continue
+                nb[n][kept] = o
+                kept += 1
+            del nb[n][kept:]
+        for n in range(len(ids)):
+            if alive[n] == 2:
+                alive[n] = 0
+    return [(ids[n], nb[n]) for n in range(len(ids)) if alive[n]], rounds
+
+
 class Node:
     def __init__(self, pos, kind, ident):
         self.pos, self.kind, self.id, self.nb = list(pos), kind, ident, []
 
 
 class TopoPRM:
-    def __init__(self, field, cfg):
+    def __init__(self, field, cfg, trace=None):
         self.f, self.cfg = field, dict(DEFAULTS, **cfg)
+        self.trace = trace
+        if trace is not None:
+            for key in ("shortcut", "same_topo", "graph", "search"):
+                trace.setdefault(key, [])
         self.res = field.res
         self.ev = dict.fromkeys(EVENTS, 0)
         self.far_visible = 0  # visible guards found at place 64 or later of the guard list (not an output of the library)
@@ -226,8 +312,14 @@ class TopoPRM:
         if pt_num < 2:
             raise Undefined("pt_num < 2")
         pts1, pts2 = self.discretize_n(path1, pt_num), self.discretize_n(path2, pt_num)
+        rec = None
+        if self.trace is not None:
+            rec = dict(pt_num=pt_num, first_invisible=None)
+            self.trace["same_topo"].append(rec)
         for i in range(pt_num):
             if not self.line_visib(pts1[i], pts2[i], thresh)[0]:
+                if rec:
+                    rec["first_invisible"] = i
                 return False
         return True
 
@@ -246,6 +338,8 @@ class TopoPRM:
             if i != len(path) - 2:
                 dis.pop()
             if len(dis) > MAX_DIS_POINTS:
+                if self.trace is not None:  # the pass ends here, before its first window
+                    self.trace["shortcut"].append(dict(nd=len(dis), blocked=[], committed=0, rolled_back=False))
                 raise OverCap()
         return dis
 
@@ -269,8 +363,13 @@ class TopoPRM:
             if len(dis) < 2:
                 return dis, [False] * len(dis)
             short, flags = [dis[0]], [False]
+            verdicts = []
+            rec = dict(nd=len(dis), blocked=verdicts, committed=0, rolled_back=False)
+            if self.trace is not None:  # (filled as the pass goes: a pass that ends at a cap keeps what it saw)
+                self.trace["shortcut"].append(rec)
             for i in range(1, len(dis)):
                 vis, colli = self.line_visib(short[-1], dis[i], res)
+                verdicts.append(not vis)
                 if vis:
                     continue
                 if len(short) + 2 > MAX_PATH_POINTS:
@@ -291,12 +390,14 @@ class TopoPRM:
                     raise Undefined("a pushed point that is not finite")
                 short.append(colli)
                 flags.append(pushed)
+                rec["committed"] += 1
             if len(short) + 1 > MAX_PATH_POINTS:
                 raise OverCap()
             short.append(dis[-1])
             flags.append(self._tail_pushed(last, last_flags))
             if path_length(short) > path_length(last):
                 self.ev["rollbacks"] += 1
+                rec["rolled_back"] = True
                 short, flags = last, last_flags
                 break
         return short, flags
@@ -332,6 +433,7 @@ class TopoPRM:
         if not (_finite(xtf) and _finite(ytf) and _finite(ztf)):
             raise Undefined("a vertical start -> end")
         node_id = 1
+        far_place = -1
         for s in range(cfg["max_sample_num"]):
             loc = [float(samples[s][k]) * r[k] for k in range(3)]
             pt = [((xtf[k] * loc[0] + ytf[k] * loc[1]) + ztf[k] * loc[2]) + tr[k] for k in range(3)]
@@ -348,6 +450,7 @@ class TopoPRM:
                 if self.line_visib(pt, n.pos, self.res)[0]:
                     visib.append(n)
                     self.far_visible += place >= 64
+                    far_place = max(far_place, place)
                     if len(visib) > 2:
                         break
             if len(visib) == 0:
@@ -368,6 +471,12 @@ class TopoPRM:
                 self.ev["connectors"] += 1
             elif len(visib) == 3:
                 self.ev["three"] += 1
+        if self.trace is not None:
+            before = [(n.id, n.kind, [q.id for q in n.nb]) for n in graph]
+            pruned, rounds = prune_rounds([(i, nb) for i, _, nb in before])
+            self.trace["graph"].append(dict(before=before, nodes=len(before), guards=sum(k == GUARD for _, k, _ in before),
+                                            max_nb=max(len(nb) for _, _, nb in before), far_place=far_place,
+                                            rounds=rounds, survivors=len(pruned)))
         # pruneGraph (:272-299), with its restart
         if len(graph) > 2:
             i = 0
@@ -405,8 +514,10 @@ class TopoPRM:
     def search_paths(self, graph):
         cfg = self.cfg
         raw = []
+        deepest = [0]
 
         def dfs(vis):
+            deepest[0] = max(deepest[0], len(vis))
             cur = vis[-1]
             for n in cur.nb:
                 if n.id == 1:
@@ -445,6 +556,10 @@ class TopoPRM:
                     break
             if reach_max:
                 break
+        if self.trace is not None:
+            sizes = sorted(set(len(p) for p in raw))
+            self.trace["search"].append(dict(depth=deepest[0], found=len(raw), buckets=[
+                (n, sum(len(p) == n for p in raw), sum(len(p) == n for p in kept)) for n in sizes]))
         return len(raw), kept
 
     # findTopoPaths (:43-98) with selectShortPaths (:339-377)
@@ -504,5 +619,9 @@ class TopoPRM:
         return out
 
 
-def find_topo_paths(field, cfg, start, end, samples, start_pts=(), end_pts=()):
-    return TopoPRM(field, cfg).find(start, end, list(start_pts), list(end_pts), samples)
+def find_topo_paths(field, cfg, start, end, samples, start_pts=(), end_pts=(), trace=None):
+    out = TopoPRM(field, cfg, trace).find(start, end, list(start_pts), list(end_pts), samples)
+    if trace is not None:
+        for rec in trace["shortcut"]:
+            rec["windows"] = windows_of(rec["blocked"])
+    return out
