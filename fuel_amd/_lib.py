@@ -149,6 +149,16 @@ COLRANGE_OK, COLRANGE_NO_COLLISION, COLRANGE_ENDS_IN_OBSTACLE, COLRANGE_NONFINIT
 COLRANGE_MAX_EVENTS, GUIDE_MAX_PTS = 4096, 65536
 
 
+class LocalSegCfg(C.Structure):
+    """fuelmi_localseg_cfg: the degree of the local spline and the fit, the strides of segments, local control points, points."""
+    _fields_ = [("degree", C.c_int), ("max_seg", C.c_int), ("max_ctrl", C.c_int), ("max_points", C.c_int)]
+
+
+LOCALSEG_SPHERE, LOCALSEG_DURATION = 0, 1
+LOCALSEG_OK, LOCALSEG_DEGENERATE, LOCALSEG_NO_LOCAL, LOCALSEG_MISFIT = range(4)
+LOCALSEG_MAX_POINTS = 1024
+
+
 class YawCfg(C.Structure):
     """fuelmi_yaw_cfg: planYawExplore's / planYaw's constants and the strides of the control-point / way-point arrays."""
     _fields_ = [("mode", C.c_int), ("pos_degree", C.c_int), ("max_ctrl", C.c_int), ("max_seg", C.c_int),
@@ -354,6 +364,12 @@ SYMBOLS = {
     "fuelmi_colrange_plan": (C.c_int, [C.POINTER(ColRangeCfg), _ip]),
     "fuelmi_map_guide_points": (C.c_int, [_P, C.c_int, C.c_int, _dp, _ip, _dp, C.c_double, C.c_int, C.c_int, _ip, _ip, _dp,
                                           _ip, _ip, _ip, _dp]),
+    "fuelmi_map_local_segments": (C.c_int, [_P, C.POINTER(LocalSegCfg), C.c_int, _ip, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _dp,
+                                            _dp, _dp, C.c_int, _ip, _ip, _dp, _dp, _dp, _ip, _ip, _dp, _ip, _dp, _dp, _ip,
+                                            _dp, _dp, _ip, _dp]),
+    "fuelmi_localseg_plan": (C.c_int, [C.POINTER(LocalSegCfg), _ip]),
+    "fuelmi_bspline_dev_load_local_segments": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _ip, _dp, _dp,
+                                                         _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _ip, _dp]),
     "fuelmi_map_plan_yaws": (C.c_int, [_P, C.POINTER(BsplineCfg), C.POINTER(YawCfg), C.c_int, _ip, _dp, _dp, _dp, _dp, _ip,
                                        _dp, _ip, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp]),
     "fuelmi_bspline_dev_plan_yaws": (C.c_int, [_P, C.POINTER(YawCfg), _dp, _dp, _ip, _dp, _ip, _dp, _dp, _ip, _dp, _dp,

@@ -767,8 +767,8 @@ __device__ void fit_solve(const double* L, int n, int hb, double* g, int lane) {
 __global__ __launch_bounds__(64) void k_bspline_fit(FitArgs F) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int c = blockIdx.x, lane = threadIdx.x;
-  const int K = F.K, p = F.degree, n = K + p - 1, hb = p - 1, R = K + 4;
-  if (F.skip && F.skip[c] != 0) return;
+  const int K = F.Ks ? F.Ks[c] : F.K, p = F.degree, n = K + p - 1, hb = p - 1, R = K + 4;
+  if ((F.skip && F.skip[c] != 0) || K < 2) return;
   double* wts = reinterpret_cast<double*>(smem_raw);  // pos / vel / acc coefficients, 5 each
   double* M = wts + 16;                               // [n][5]  M(j, j-d) at [j][d]
   double* g = M + 5 * n;                              // [n][3]
@@ -776,7 +776,7 @@ __global__ __launch_bounds__(64) void k_bspline_fit(FitArgs F) {
   double* res = x + 3 * n;                            // [R][3]
   double* u = res + 3 * R;                            // [n + p + 1]
   const double ts = F.ts[c];
-  const double* pts = F.points + (size_t)c * K * 3;
+  const double* pts = F.points + (size_t)c * (F.pt_stride ? (size_t)F.pt_stride : (size_t)K) * 3;
   const double* der = F.derivs + (size_t)c * 12;
   if (lane == 0) {  // coefficient rows as the reference writes them (:199-236)
     for (int i = 0; i < 15; ++i) wts[i] = 0.0;

@@ -65,6 +65,9 @@ struct FitArgs {
   double* start_state;   // [C][3][3]  getBoundaryStates(2, 0).start
   double* end_state;     // [C][3][3]  row 0 = getBoundaryStates(2, 0).end[0]
   const int* skip;       // [C] or null: a candidate with skip[c] != 0 is left as it is
+  // a ragged batch (local_segment.hip): each candidate its own number of points, K the largest of them
+  const int* Ks;         // [C] or null: candidate c fits Ks[c] <= K points (below 2: left as it is)
+  long pt_stride;        // rows between two candidates' points; 0: the candidate's own count
 };
 
 // the fit of device samples into the batch's own state; its launch (st null: the map's stream); the position splines

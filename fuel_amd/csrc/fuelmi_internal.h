@@ -227,6 +227,7 @@ struct fuelmi_map {
   DevScratch cloud_dev;    // fuelmi_map_extract_cloud (map_cloud.hip): the total, the workgroup words, the points
   DevScratch topo_dev;     // fuelmi_map_topo_paths (topo_path.hip): results, inputs, graphs, path sets
   DevScratch colrange_dev; // fuelmi_map_collision_ranges / _guide_points (collide_range.hip): problems in, results out
+  DevScratch localseg_dev; // fuelmi_map_local_segments (local_segment.hip): states and problems in, results out
   int path_stats[4] = {0, 0, 0, 0};  // fuelmi_map_path_stats
   hipEvent_t goal_ev[3] = {nullptr, nullptr, nullptr};  // the events that split the goal-path call's time
   double goal_ms[2] = {0.0, 0.0};  // fuelmi_map_goal_path_times

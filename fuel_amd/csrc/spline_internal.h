@@ -1,6 +1,7 @@
 // spline_internal.h -- NonUniformBspline's evaluation on the device, shared by the kernels that read a batch of uniform
-// position splines (yaw_plan.hip, traj_check.hip, traj_sample.hip, traj_adjust.hip): where a problem's spline lies, its
-// knots, its evaluation.  f64, the reference's operations in the reference's order.
+// position splines (yaw_plan.hip, traj_check.hip, traj_sample.hip, traj_adjust.hip, collide_range.hip) or one spline a
+// state (local_segment.hip): where a problem's spline lies, its knots, its evaluation, its derivative splines.  f64, the
+// reference's operations in the reference's order.
 #ifndef FUELMI_SPLINE_INTERNAL_H_
 #define FUELMI_SPLINE_INTERNAL_H_
 
@@ -108,6 +109,37 @@ __device__ __forceinline__ void spline_pos(const double* u, int p, int n, const 
     spline_deboor<4>(u, n, t, ctrl, out);
   else
     spline_deboor<5>(u, n, t, ctrl, out);
+}
+
+// the spline of degree PD on the points q of span k, then LEVELS derivatives of it: out[0 .. LEVELS].  A derivative of
+// degree 0 is its one point: the knot search alone (evaluateDeBoor with p_ = 0).
+template <int PD, int DIM, int LEVELS>
+__device__ __forceinline__ void spline_levels(const double* u, int k, double ub, double (*q)[DIM], double (*out)[DIM]) {
+  double w[PD + 1][DIM];
+#pragma unroll
+  for (int i = 0; i <= PD; ++i)
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) w[i][c] = q[i][c];
+  spline_alpha<PD, DIM>(u, k, ub, w);
+#pragma unroll
+  for (int c = 0; c < DIM; ++c) out[0][c] = w[PD][c];
+  if constexpr (LEVELS > 0) {
+    spline_derive<PD, DIM>(u, k, q);
+    spline_levels<PD - 1, DIM, LEVELS - 1>(u, k, ub, q, out + 1);
+  }
+}
+
+// evaluateDeBoorT(t) of a spline (degree P, n points C [n][DIM], knots u) and of its first LEVELS derivatives
+template <int P, int DIM, int LEVELS>
+__device__ __forceinline__ void spline_eval_levels(const double* u, int n, const double* C, double t, double (*out)[DIM]) {
+  double ub;
+  const int k = spline_span(u, P, n, t, ub);
+  double q[P + 1][DIM];
+#pragma unroll
+  for (int i = 0; i <= P; ++i)
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) q[i][c] = C[(size_t)DIM * (k - P + i) + c];
+  spline_levels<P, DIM, LEVELS>(u, k, ub, q, out);
 }
 
 #endif

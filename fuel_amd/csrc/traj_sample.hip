@@ -49,37 +49,6 @@ __host__ __device__ inline int ts_wave_stride(const fuelmi_trajsmp_cfg& c) {
   return spline_knot_stride(c.max_ctrl) + (c.max_yaw_ctrl > 0 ? spline_knot_stride(c.max_yaw_ctrl) : 0);
 }
 
-// the spline of degree PD on the points q of span k, then LEVELS derivatives of it: out[0 .. LEVELS].  A derivative of
-// degree 0 is its one point: the knot search alone (evaluateDeBoor with p_ = 0).
-template <int PD, int DIM, int LEVELS>
-__device__ __forceinline__ void ts_levels(const double* u, int k, double ub, double (*q)[DIM], double (*out)[DIM]) {
-  double w[PD + 1][DIM];
-#pragma unroll
-  for (int i = 0; i <= PD; ++i)
-#pragma unroll
-    for (int c = 0; c < DIM; ++c) w[i][c] = q[i][c];
-  spline_alpha<PD, DIM>(u, k, ub, w);
-#pragma unroll
-  for (int c = 0; c < DIM; ++c) out[0][c] = w[PD][c];
-  if constexpr (LEVELS > 0) {
-    spline_derive<PD, DIM>(u, k, q);
-    ts_levels<PD - 1, DIM, LEVELS - 1>(u, k, ub, q, out + 1);
-  }
-}
-
-// evaluateDeBoorT(t) of a spline (degree P, n points C [n][DIM], knots u) and of its first LEVELS derivatives
-template <int P, int DIM, int LEVELS>
-__device__ __forceinline__ void ts_eval(const double* u, int n, const double* C, double t, double (*out)[DIM]) {
-  double ub;
-  const int k = spline_span(u, P, n, t, ub);
-  double q[P + 1][DIM];
-#pragma unroll
-  for (int i = 0; i <= P; ++i)
-#pragma unroll
-    for (int c = 0; c < DIM; ++c) q[i][c] = C[(size_t)DIM * (k - P + i) + c];
-  ts_levels<P, DIM, LEVELS>(u, k, ub, q, out);
-}
-
 __global__ void __launch_bounds__(TS_WIN * TS_WAVES) k_traj_sample(TrajSmpArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int lane = threadIdx.x & (TS_WIN - 1), wv = threadIdx.x >> 6;
@@ -148,18 +117,18 @@ __global__ void __launch_bounds__(TS_WIN * TS_WAVES) k_traj_sample(TrajSmpArgs A
       }
       if (status != FUELMI_TRAJSMP_INVALID) {
         if (p == 3)
-          ts_eval<3, 3, 3>(u, n, C, te, o);
+          spline_eval_levels<3, 3, 3>(u, n, C, te, o);
         else if (p == 4)
-          ts_eval<4, 3, 3>(u, n, C, te, o);
+          spline_eval_levels<4, 3, 3>(u, n, C, te, o);
         else
-          ts_eval<5, 3, 3>(u, n, C, te, o);
+          spline_eval_levels<5, 3, 3>(u, n, C, te, o);
         if (ny > 0) {
           if (py == 3)
-            ts_eval<3, 1, 2>(uy, ny, Cy, te, y);
+            spline_eval_levels<3, 1, 2>(uy, ny, Cy, te, y);
           else if (py == 4)
-            ts_eval<4, 1, 2>(uy, ny, Cy, te, y);
+            spline_eval_levels<4, 1, 2>(uy, ny, Cy, te, y);
           else
-            ts_eval<5, 1, 2>(uy, ny, Cy, te, y);
+            spline_eval_levels<5, 1, 2>(uy, ny, Cy, te, y);
         }
         if (status == FUELMI_TRAJSMP_PAST) {  // the final position and yaw, everything else 0 (:277-281)
           for (int l = 1; l < 4; ++l) o[l][0] = o[l][1] = o[l][2] = 0.0;

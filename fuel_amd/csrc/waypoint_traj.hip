@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "bspline_batch.h"
+#include "poly_internal.h"
 
 namespace {
 
@@ -61,29 +62,6 @@ struct WpTrajArgs {
   double* seg_times;   // [n][maxw-1] or null
   double* coef;        // [n][maxw-1][3][6] or null
 };
-
-// PolynomialTraj::evaluate(t, k): the lookup (idx clamped to the last segment), then tv . c with
-// tv[i] = i (i-1) .. (i-k+1) ts^(i-k), summed from the lowest power
-__device__ __forceinline__ void wt_eval(const double* cf, const double* T, int S, double t, int k, double out[3]) {
-  int idx = 0;
-  double ts = t;
-  while (idx < S - 1 && T[idx] + 1e-4 < ts) {
-    ts -= T[idx];
-    ++idx;
-  }
-  const double* c = cf + 18 * idx;
-  double o0 = 0.0, o1 = 0.0, o2 = 0.0, pw = 1.0;
-  for (int i = k; i < 6; ++i) {
-    int m = 1;
-    for (int q = i; q > i - k; --q) m *= q;
-    const double tv = (double)m * pw;
-    pw = pw * ts;
-    o0 += tv * c[i];
-    o1 += tv * c[6 + i];
-    o2 += tv * c[12 + i];
-  }
-  out[0] = o0, out[1] = o1, out[2] = o2;
-}
 
 // a problem without a trajectory: every output of it is 0
 __device__ void wt_zero(const WpTrajArgs& W, int b, int status, int tid) {
@@ -252,7 +230,7 @@ __global__ void __launch_bounds__(WT_NT) k_waypoint_traj(WpTrajArgs W) {
       const bool have = tid < cnt;
       double p[3] = {0.0, 0.0, 0.0};
       if (have) {
-        wt_eval(cf, T, S, mine, 0, p);
+        poly_eval(cf, T, S, mine, 0, p);
         for (int a = 0; a < 3; ++a) pbuf[3 * (tid + 1) + a] = p[a];
       }
       __syncthreads();
@@ -302,7 +280,7 @@ __global__ void __launch_bounds__(WT_NT) k_waypoint_traj(WpTrajArgs W) {
       }
       if (tid < cnt && count + tid < W.max_samples) {
         double p[3];
-        wt_eval(cf, T, S, mine, 0, p);
+        poly_eval(cf, T, S, mine, 0, p);
         for (int a = 0; a < 3; ++a) smp[3 * (count + tid) + a] = p[a];
       }
       count += cnt;
@@ -313,7 +291,7 @@ __global__ void __launch_bounds__(WT_NT) k_waypoint_traj(WpTrajArgs W) {
   // 8. boundary derivatives (:294-297) and the scalars
   if (tid < 4) {
     double p[3];
-    wt_eval(cf, T, S, (tid & 1) ? dur : 0.0, tid < 2 ? 1 : 2, p);
+    poly_eval(cf, T, S, (tid & 1) ? dur : 0.0, tid < 2 ? 1 : 2, p);
     for (int a = 0; a < 3; ++a) W.derivs[(size_t)b * 12 + 3 * tid + a] = p[a];
   }
   if (tid == 0) {

@@ -160,6 +160,34 @@ public:
   int selectBestTraj(const std::vector<Eigen::MatrixXd>& pos_ctrl, int degree, const std::vector<double>& dt,
                      const TrajAdjust& cfg, std::vector<TrajMetrics>* all);
 
+  // addition: FastPlannerManager::paramLocalTraj / reparamLocalTraj (planner_manager.cpp:605-634) on the device
+  // (fuelmi_map_local_segments, include/fuelmi.h).  The state is what GlobalTrajData holds, as plain data: the
+  // polynomial global trajectory (PolynomialTraj's segment times and coefficients, lowest power first), the uniform
+  // local spline of this optimiser's degree (no rows: none yet) and the four times setGlobalTraj / setLocalTraj keep.
+  struct GlobalTrajState {
+    std::vector<double> seg_times;                  // [S]
+    std::vector<double> coef;                       // [S][3][6]: segment, axis, power
+    double global_duration = 0.0;
+    Eigen::MatrixXd local_ctrl;                     // [n][3], or empty
+    double local_knot_span = 0.0;
+    double local_start_time = -1.0, local_end_time = -1.0, time_change = 0.0, last_time_inc = 0.0;
+  };
+  // what one call comes back with: the control points parameterizeToBspline returns, dt / duration, the boundary
+  // derivatives (plan_data_.local_start_end_derivative_) and the sampled points; status is FUELMI_LOCALSEG_*
+  struct LocalSegment {
+    int status = 0, n_steps = 0, seg_num = 0;
+    double segment_len = 0.0, dt = 0.0, duration = 0.0;
+    Eigen::MatrixXd ctrl_pts;
+    vector<Eigen::Vector3d> points, start_end_derivative;
+  };
+  // paramLocalTraj(start_t, dt, duration) with pp_.local_traj_len_ = radius and pp_.ctrl_pt_dist = dist_pt.
+  // reparamLocalTraj(start_t, duration, dt) for every dt of `dts` in ONE device call: optimizeTopoBspline makes one
+  // call per guide path, each with its own dt and therefore its own number of points.  Both return false, and touch no
+  // output, when the call fails; a problem's own failure is its status.
+  bool paramLocalTraj(const GlobalTrajState& state, double start_t, double radius, double dist_pt, LocalSegment& out);
+  bool reparamLocalTraj(const GlobalTrajState& state, double start_t, double duration, const std::vector<double>& dts,
+                        std::vector<LocalSegment>& out);
+
   Eigen::MatrixXd getControlPoints();
   vector<Eigen::Vector3d> matrixToVectors(const Eigen::MatrixXd& ctrl_pts);
 

@@ -1449,6 +1449,75 @@ int BsplineOptimizer::selectBestTraj(const std::vector<Eigen::MatrixXd>& pos_ctr
   return best;
 }
 
+// n problems (mode, start_t, arg0, arg1) on one state in one fuelmi_map_local_segments call
+static bool local_segments(fuelmi_map* m, int degree, const BsplineOptimizer::GlobalTrajState& st, int n, const int* mode,
+                           const double* start_t, const double* arg0, const double* arg1,
+                           std::vector<BsplineOptimizer::LocalSegment>& out) {
+  const int S = (int)st.seg_times.size(), nl = (int)st.local_ctrl.rows();
+  if (n < 1 || S < 1 || st.coef.size() != 18 * st.seg_times.size() || (nl > 0 && st.local_ctrl.cols() != 3)) return false;
+  fuelmi_localseg_cfg cfg;
+  cfg.degree = degree, cfg.max_seg = S, cfg.max_ctrl = std::max(nl, degree + 1), cfg.max_points = FUELMI_LOCALSEG_MAX_POINTS;
+  const int mp = cfg.max_points, rows = mp + degree - 1;
+  std::vector<double> local((size_t)cfg.max_ctrl * 3, 0.0);
+  for (int i = 0; i < nl; ++i)
+    for (int k = 0; k < 3; ++k) local[(size_t)i * 3 + k] = st.local_ctrl(i, k);
+  std::vector<int> traj_of(n, 0), iv((size_t)n * 5);
+  std::vector<double> dv((size_t)n * 3), points((size_t)n * mp * 3), derivs((size_t)n * 12), ctrl((size_t)n * rows * 3);
+  int *status = iv.data(), *n_steps = status + n, *seg_num = n_steps + n, *n_points = seg_num + n, *n_ctrl = n_points + n;
+  double *segment_len = dv.data(), *duration = segment_len + n, *dt = duration + n;
+  const int rc = fuelmi_map_local_segments(m, &cfg, 1, &S, st.seg_times.data(), st.coef.data(), &st.global_duration, &nl,
+                                           local.data(), &st.local_knot_span, &st.local_start_time, &st.local_end_time,
+                                           &st.time_change, &st.last_time_inc, n, traj_of.data(), mode, start_t, arg0, arg1,
+                                           status, n_steps, segment_len, seg_num, duration, dt, n_points, points.data(),
+                                           derivs.data(), n_ctrl, ctrl.data());
+  if (rc) {
+    warn("fuelmi_map_local_segments", rc);
+    return false;
+  }
+  out.assign(n, BsplineOptimizer::LocalSegment());
+  for (int b = 0; b < n; ++b) {
+    BsplineOptimizer::LocalSegment& o = out[b];
+    o.status = status[b], o.n_steps = n_steps[b], o.seg_num = seg_num[b];
+    o.segment_len = segment_len[b], o.dt = dt[b], o.duration = duration[b];
+    o.ctrl_pts.resize(n_ctrl[b], 3);
+    for (int i = 0; i < n_ctrl[b]; ++i)
+      for (int k = 0; k < 3; ++k) o.ctrl_pts(i, k) = ctrl[((size_t)b * rows + i) * 3 + k];
+    for (int i = 0; i < n_points[b]; ++i) {
+      const double* q = &points[((size_t)b * mp + i) * 3];
+      o.points.push_back(Eigen::Vector3d(q[0], q[1], q[2]));
+    }
+    if (status[b] == FUELMI_LOCALSEG_OK)
+      for (int i = 0; i < 4; ++i) {
+        const double* q = &derivs[(size_t)b * 12 + 3 * i];
+        o.start_end_derivative.push_back(Eigen::Vector3d(q[0], q[1], q[2]));
+      }
+  }
+  return true;
+}
+
+bool BsplineOptimizer::paramLocalTraj(const GlobalTrajState& state, double start_t, double radius, double dist_pt,
+                                      LocalSegment& out) {
+  const int mode = FUELMI_LOCALSEG_SPHERE;
+  std::vector<LocalSegment> one;
+  if (!local_segments(edt_environment_->sdf_map_->device(), bspline_degree_, state, 1, &mode, &start_t, &radius, &dist_pt, one))
+    return false;
+  out = one[0];
+  return true;
+}
+
+bool BsplineOptimizer::reparamLocalTraj(const GlobalTrajState& state, double start_t, double duration,
+                                        const std::vector<double>& dts, std::vector<LocalSegment>& out) {
+  const int n = (int)dts.size();
+  const std::vector<int> mode(n, FUELMI_LOCALSEG_DURATION);
+  const std::vector<double> t0(n, start_t), dur(n, duration);
+  std::vector<LocalSegment> all;
+  if (!local_segments(edt_environment_->sdf_map_->device(), bspline_degree_, state, n, mode.data(), t0.data(), dur.data(),
+                      dts.data(), all))
+    return false;
+  out.swap(all);
+  return true;
+}
+
 vector<Eigen::Vector3d> BsplineOptimizer::matrixToVectors(const Eigen::MatrixXd& ctrl_pts) {
   vector<Eigen::Vector3d> out;
   for (int i = 0; i < ctrl_pts.rows(); ++i) {

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BsplineBatch, BsplineCfg, CloudCfg, ColRangeCfg, FrontierCfg, GoalCfg, KinoCfg, MapCfg, MapInfo, PathCfg, RefineCfg, RenderCfg, TopoCfg, TrajAdjCfg, TrajChkCfg, TrajSmpCfg, TspCfg,
+from ._lib import (BsplineBatch, BsplineCfg, CloudCfg, ColRangeCfg, FrontierCfg, GoalCfg, KinoCfg, LocalSegCfg, MapCfg, MapInfo, PathCfg, RefineCfg, RenderCfg, TopoCfg, TrajAdjCfg, TrajChkCfg, TrajSmpCfg, TspCfg,
                    WptrajCfg, YawCfg, check, lib)
 
 # exploration.launch / algorithm.xml defaults (exploration_manager/launch/algorithm.xml:33-59,170-181)
@@ -85,6 +85,45 @@ def topo_cfg(sample_inflate=(1.0, 3.5, 1.0), clearance=0.2, ratio_to_short=5.5, 
 def colrange_cfg(degree=3, max_ctrl=4, max_events=8, max_pts=_lib.TOPO_MAX_POINTS_IN, clearance=0.2):
     """fuelmi_colrange_cfg: the spline's degree, topo_prm/clearance and the strides of the event and point arrays"""
     return ColRangeCfg(int(degree), int(max_ctrl), int(max_events), int(max_pts), float(clearance))
+
+
+def _pack_localseg(states, problems, degree, max_seg, max_ctrl):
+    """The host arrays fuelmi_map_local_segments and the batch loader share: (LocalSegCfg without max_points, n_traj,
+    the state arrays, n_prob, the problem arrays).  A state is a dict: seg_times [S], coef [S, 3, 6], global_duration,
+    and -- all optional, as setGlobalTraj leaves them -- local_ctrl [n, 3] with local_knot_span, local_ts (-1),
+    local_te (-1), time_change (0), last_time_inc (0).  A problem is (state index, mode, start_t, arg0, arg1)."""
+    nt, n = len(states), len(problems)
+    T = [np.ascontiguousarray(st["seg_times"], dtype=np.float64).reshape(-1) for st in states]
+    cf = [np.ascontiguousarray(st["coef"], dtype=np.float64).reshape(-1, 3, 6) for st in states]
+    lc = [np.zeros((0, 3)) if st.get("local_ctrl") is None else
+          np.ascontiguousarray(st["local_ctrl"], dtype=np.float64).reshape(-1, 3) for st in states]
+    ms = int(max_seg) if max_seg is not None else max([len(v) for v in T] + [1])
+    mc = int(max_ctrl) if max_ctrl is not None else max([len(v) for v in lc] + [int(degree) + 1])
+    c = LocalSegCfg(int(degree), ms, mc, 0)
+    n_seg = np.array([len(v) for v in T], dtype=np.int32)
+    n_loc = np.array([len(v) for v in lc], dtype=np.int32)
+    a_T, a_cf, a_lc = np.zeros((nt, max(ms, 0))), np.zeros((nt, max(ms, 0), 3, 6)), np.zeros((nt, max(mc, 0), 3))
+    for i in range(nt):
+        if len(cf[i]) != len(T[i]):
+            raise ValueError("local segments: state %d has %d segment times and %d coefficient blocks" %
+                             (i, len(T[i]), len(cf[i])))
+        k = min(len(T[i]), a_T.shape[1])
+        a_T[i, :k], a_cf[i, :k] = T[i][:k], cf[i][:k]
+        k = min(len(lc[i]), a_lc.shape[1])
+        a_lc[i, :k] = lc[i][:k]
+
+    def col(key, default):
+        return np.array([float(st.get(key, default)) for st in states], dtype=np.float64)
+    st_arr = [n_seg, a_T, a_cf, col("global_duration", 0.0), n_loc, a_lc, col("local_knot_span", 0.0), col("local_ts", -1.0),
+              col("local_te", -1.0), col("time_change", 0.0), col("last_time_inc", 0.0)]
+    pr = [tuple(q) for q in problems]
+    pr_arr = [np.array([int(q[0]) for q in pr], dtype=np.int32), np.array([int(q[1]) for q in pr], dtype=np.int32)] + \
+        [np.array([float(q[k]) for q in pr], dtype=np.float64) for k in (2, 3, 4)]
+    return c, nt, st_arr, n, pr_arr
+
+
+def _ptr(a):
+    return _ip(a) if a.dtype == np.int32 else _dp(a)
 
 
 def traj_check_cfg(degree=3, max_ctrl=4, step=0.02, max_radius=6.0):
@@ -802,6 +841,43 @@ class SDFMap:
         o["limit"] = rc == -5
         return o
 
+    # --- local segments of the global trajectory (include/fuelmi.h fuelmi_map_local_segments) ---
+    LOCALSEG_SPHERE, LOCALSEG_DURATION = _lib.LOCALSEG_SPHERE, _lib.LOCALSEG_DURATION
+    LOCALSEG_OK, LOCALSEG_DEGENERATE = _lib.LOCALSEG_OK, _lib.LOCALSEG_DEGENERATE
+    LOCALSEG_NO_LOCAL, LOCALSEG_MISFIT = _lib.LOCALSEG_NO_LOCAL, _lib.LOCALSEG_MISFIT
+
+    def local_segments(self, states, problems, degree=3, max_points=64, max_seg=None, max_ctrl=None, allow_limit=False):
+        """paramLocalTraj (LOCALSEG_SPHERE: arg0 = radius, arg1 = dist_pt) / reparamLocalTraj (LOCALSEG_DURATION: arg0 =
+        duration, arg1 = dt) per problem on the states' global trajectories: states is a list of dicts (seg_times [S],
+        coef [S, 3, 6], global_duration, and optionally local_ctrl [n, 3] with local_knot_span, local_ts, local_te,
+        time_change, last_time_inc), problems a list of (state index, mode, start_t, arg0, arg1).  Returns a dict of
+        arrays: status (LOCALSEG_*; -1: more than max_points points), n_steps, segment_len, seg_num, duration, dt,
+        n_points, points [n, max_points, 3], derivs [n, 4, 3], n_ctrl, ctrl [n, max_points + degree - 1, 3]; limit.
+        FUELMI_ELIMIT raises FuelmiError unless allow_limit."""
+        c, nt, st_arr, n, pr_arr = _pack_localseg(states, problems, degree, max_seg, max_ctrl)
+        c.max_points = int(max_points)
+        mp = max(c.max_points, 0)
+        o = {k: np.zeros(n, dtype=np.int32) for k in ("status", "n_steps", "seg_num", "n_points", "n_ctrl")}
+        o.update(segment_len=np.zeros(n), duration=np.zeros(n), dt=np.zeros(n), points=np.zeros((n, mp, 3)),
+                 derivs=np.zeros((n, 4, 3)), ctrl=np.zeros((n, mp + max(c.degree, 1) - 1, 3)))
+        rc = self.L.fuelmi_map_local_segments(
+            self.h, C.byref(c), nt, *[_ptr(a) for a in st_arr], n, *[_ptr(a) for a in pr_arr], _ip(o["status"]),
+            _ip(o["n_steps"]), _dp(o["segment_len"]), _ip(o["seg_num"]), _dp(o["duration"]), _dp(o["dt"]),
+            _ip(o["n_points"]), _dp(o["points"]), _dp(o["derivs"]), _ip(o["n_ctrl"]), _dp(o["ctrl"]))
+        if not (allow_limit and rc == -5):
+            check(rc)
+        o["limit"] = rc == -5
+        return o
+
+    @staticmethod
+    def localseg_plan(degree=3, max_seg=1, max_ctrl=4, max_points=64):
+        """host only: dict(lanes, lds_bytes, waves, max_seg, max_ctrl, max_points, count_cap, fit_lds_bytes) of the
+        local-segment kernel"""
+        out = (C.c_int * 8)()
+        check(lib().fuelmi_localseg_plan(C.byref(LocalSegCfg(int(degree), int(max_seg), int(max_ctrl), int(max_points))), out))
+        return dict(zip(("lanes", "lds_bytes", "waves", "max_seg", "max_ctrl", "max_points", "count_cap", "fit_lds_bytes"),
+                        [int(v) for v in out]))
+
     # --- the yaw trajectory of a position spline (include/fuelmi.h fuelmi_map_plan_yaws) ---
     YAW_EXPLORE, YAW_FOLLOW, YAW_OK, YAW_DEGENERATE = _lib.YAW_EXPLORE, _lib.YAW_FOLLOW, _lib.YAW_OK, _lib.YAW_DEGENERATE
 
@@ -1517,6 +1593,7 @@ class BsplineDeviceProblem:
     def __init__(self, opt, problem):
         self.L = opt.L
         self.problem = problem
+        self.degree = int(opt.cfg.bspline_degree)
         self.map = opt._map()
         h = C.c_void_p()
         check(self.L.fuelmi_bspline_dev_create(self.map.h, C.byref(opt.cfg), C.byref(problem.c), C.byref(h)))
@@ -1578,6 +1655,21 @@ class BsplineDeviceProblem:
                                                       _ip(status), _dp(duration))
         if not (allow_limit and rc == -5):
             check(rc)
+        return status, duration
+
+    def load_local_segments(self, states, problems, max_seg=None, max_ctrl=None):
+        """the global trajectory's local segment -> loadSamples' fit, without leaving the device
+        (fuelmi_bspline_dev_load_local_segments): one problem per candidate, states / problems as SDFMap.local_segments
+        takes them, the degree and the point count the batch's.  Returns (status [C], duration [C]); a candidate whose
+        status is not LOCALSEG_OK (LOCALSEG_MISFIT: another point count than the batch's) keeps its state."""
+        c = self.problem.c
+        if len(problems) != c.n_traj:
+            raise ValueError("load_local_segments: one problem per candidate")
+        lc, nt, st_arr, n, pr_arr = _pack_localseg(states, problems, self.degree, max_seg, max_ctrl)
+        status = np.zeros(c.n_traj, dtype=np.int32)
+        duration = np.zeros(c.n_traj)
+        check(self.L.fuelmi_bspline_dev_load_local_segments(self.h, lc.max_seg, lc.max_ctrl, nt, *[_ptr(a) for a in st_arr],
+                                                            *[_ptr(a) for a in pr_arr], _ip(status), _dp(duration)))
         return status, duration
 
     def load_kino(self, starts, vels, accs, goals, goal_vels, allow_limit=False, **cfg):

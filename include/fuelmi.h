@@ -1074,8 +1074,8 @@ long long fuelmi_map_topo_pool_bytes(const fuelmi_map* m);
  * FUELMI_TOPO_MAX_POINTS_IN.  n_prob = 0 is FUELMI_OK.  Runs on the map's stream behind whatever ESDF update was queued
  * before it: host arrays in and out, synchronous, one thread at a time per map; its scratch is one grow-only allocation
  * on the map.  One 64-lane wave per problem, 64 ticks a window; a result does not depend on the problem's place in the
- * batch.  Out of scope: paramLocalTraj / reparamLocalTraj (the caller supplies the control points), evaluateCoarseEDT
- * with time >= 0, moved knots as input, chaining the outputs on the device.
+ * batch.  The control points come from fuelmi_map_local_segments (below).  Out of scope: evaluateCoarseEDT with
+ * time >= 0, moved knots as input, chaining the outputs on the device.
  * ---------------------------------------------------------------------------------------- */
 #define FUELMI_COLRANGE_OK 0
 #define FUELMI_COLRANGE_NO_COLLISION 1
@@ -1133,6 +1133,105 @@ int fuelmi_colrange_plan(const fuelmi_colrange_cfg* cfg, int out6[6]);
 int fuelmi_map_guide_points(fuelmi_map* m, int n_path, int max_path_points, const double* paths, const int* path_len,
                             const double* duration, double ctrl_pt_dist, int degree, int max_guide, int* status,
                             int* seg_num, double* dt, int* n_pts, int* n_ctrl, int* n_guide, double* guide_pts);
+
+/* ------------------------------------------------------------------------------------------
+ * Local segments of the global trajectory: FastPlannerManager::paramLocalTraj / reparamLocalTraj
+ * (plan_manage/src/planner_manager.cpp:605-634), the producers of the control points every call of the guided-replanning
+ * chain above starts from, for n_prob problems on n_traj trajectory states in one call.  A state is what GlobalTrajData
+ * (plan_manage/include/plan_manage/plan_container.hpp) holds: the polynomial global trajectory (n_seg segments,
+ * seg_times / coef as fuelmi_map_waypoint_trajs returns them), global_duration, the uniform local spline (n_local_ctrl
+ * control points of the call's degree with local_knot_span; 0: none yet, as setGlobalTraj leaves it with
+ * local_ts = local_te = -1) and local_ts, local_te, time_change, last_time_inc.  A problem names its state (traj_of),
+ * a mode, start_t and two arguments; several problems may name one state.  It hangs on the map for its stream and
+ * scratch and reads no voxel.  Per problem, everything f64 `+ - * / sqrt floor` in this order:
+ *   getState(t, k) (:64-71), the three branches literal, the comparisons inclusive:
+ *     t >= -1e-3 && t <= local_ts:                      the polynomial at (t - time_change) + last_time_inc
+ *     else t >= local_te && t <= global_duration + 1e-3: the polynomial at t - time_change
+ *     else:                                             evaluateDeBoorT(t - local_ts) of the local spline's k-th
+ *                                                       derivative spline (setUniformBspline's accumulated knots,
+ *                                                       getDerivative, the clamp: see fuelmi_map_sample_trajs)
+ *     The polynomial is PolynomialTraj::evaluate as fuelmi_map_waypoint_trajs has it: `times[idx] + 1e-4 < ts` walks the
+ *     segments, idx clamped to the last one where the reference reads past its vector; powers as repeated products,
+ *     summed from the lowest power.
+ *   FUELMI_LOCALSEG_SPHERE (arg0 = radius, arg1 = dist_pt): getTrajInfoInSphere (:88-112), i.e. paramLocalTraj.
+ *     first = getState(start_t, 0); while |cur - first| < radius && start_t + segment_time < global_duration - 1e-3:
+ *     segment_time = min(segment_time + 0.2, global_duration - start_t) (the 0.2 ACCUMULATED), cur = getState(start_t +
+ *     segment_time, 0), segment_len += |cur - prev| in step order; the norms are sqrt(x x + y y + z z).  n_steps = the
+ *     bodies run.  seg_num = max(6, int(min(floor(segment_len / dist_pt), FUELMI_WPTRAJ_MAX_SEG))), duration =
+ *     segment_time, dt = duration / seg_num; then as DURATION.
+ *   FUELMI_LOCALSEG_DURATION (arg0 = duration, arg1 = dt): getTrajInfoInDuration (:74-85), i.e. reparamLocalTraj;
+ *     n_steps = 0, segment_len = 0, seg_num = 0.  points = getState(start_t + tp, 0) for (tp = 0; tp <= duration + 1e-4;
+ *     tp += dt), tp ACCUMULATED: n_points is the result of that accumulation, not seg_num + 1 (it stops counting at the
+ *     first multiple of 64 above FUELMI_WPTRAJ_MAX_SEG + 2).  derivs [4][3] = getState(start_t, 1), getState(start_t +
+ *     duration, 1), then the same two with k = 2: the layout fuelmi_bspline_parameterize takes.
+ *   ctrl = parameterizeToBspline of the problem's n_points points with ts = dt, bit for bit what
+ *     fuelmi_bspline_parameterize returns for them; n_ctrl = n_points + degree - 1.  Each problem has its own count.
+ * Outputs per problem: status, n_steps, segment_len, seg_num, duration, dt, n_points, points [max_points][3], derivs,
+ * n_ctrl, ctrl [max_points + degree - 1][3].  Rows that are not written are zero.
+ * Status, defined where the reference is not:
+ *   FUELMI_LOCALSEG_OK
+ *   FUELMI_LOCALSEG_DEGENERATE  dt is not finite or <= 0 (SPHERE with start_t >= global_duration - 1e-3 has duration 0 and
+ *               the reference loops forever on tp += 0), or fewer than 2 points; parameterizeToBspline rejects both.
+ *               n_steps, segment_len, seg_num, duration and dt are as computed; n_points = 0, no points, derivs, ctrl.
+ *   FUELMI_LOCALSEG_NO_LOCAL    a getState of the problem falls to the local branch of a state with n_local_ctrl = 0
+ *               (the reference indexes an empty vector): every output of the problem is zero.
+ *   -1          more than max_points points: n_points is the full count, the first max_points rows and derivs are
+ *               written, n_ctrl = 0 and no ctrl; the call returns FUELMI_ELIMIT; the other problems complete.
+ * FUELMI_EINVAL before any launch: pointers; degree outside 3..5; max_seg < 1, max_ctrl < degree + 1 or max_points < 2;
+ * n_seg[i] outside 1..max_seg; n_local_ctrl[i] not 0 and outside degree + 1 .. max_ctrl; a local knot span <= 0 (where
+ * there is a local spline); traj_of outside 0 .. n_traj - 1; an unknown mode; any value read that is not finite or with
+ * |value| >= 1e7; SPHERE with radius or dist_pt not > 0.  FUELMI_ELIMIT before any launch: max_seg >
+ * FUELMI_WPTRAJ_MAX_WAY - 1, max_ctrl > FUELMI_TRAJCHK_MAX_CTRL, max_points > FUELMI_LOCALSEG_MAX_POINTS, a
+ * global_duration > FUELMI_WPTRAJ_MAX_DURATION (with start_t >= 0 that bounds the step loop at 50 001 bodies).
+ * n_prob = 0 is FUELMI_OK.  Host arrays in and out, synchronous on the map's stream, one thread at a time per map; its
+ * scratch is one grow-only allocation on the map.  One 64-lane wave per problem, 64 steps / points a window; a result
+ * does not depend on the problem's place in the batch.  Out of scope: planGlobalTraj's way-point insertion and end ramps
+ * (the polynomial is an input), setLocalTraj's bookkeeping (the four times are inputs), non-uniform local knots.
+ * ---------------------------------------------------------------------------------------- */
+#define FUELMI_LOCALSEG_SPHERE 0
+#define FUELMI_LOCALSEG_DURATION 1
+#define FUELMI_LOCALSEG_OK 0
+#define FUELMI_LOCALSEG_DEGENERATE 1
+#define FUELMI_LOCALSEG_NO_LOCAL 2
+#define FUELMI_LOCALSEG_MAX_POINTS 1024       /* largest max_points (the fit's LDS) */
+typedef struct {
+  int degree;          /* 3..5: the local spline's and the fit's (pp_.bspline_degree_) */
+  int max_seg;         /* stride of seg_times / coef, <= FUELMI_WPTRAJ_MAX_WAY - 1 */
+  int max_ctrl;        /* stride of local_ctrl, <= FUELMI_TRAJCHK_MAX_CTRL */
+  int max_points;      /* stride / cap of points; ctrl has max_points + degree - 1 rows */
+} fuelmi_localseg_cfg;
+/* states: n_seg / global_duration / n_local_ctrl / local_knot_span / local_ts / local_te / time_change / last_time_inc
+ * [n_traj], seg_times [n_traj][max_seg], coef [n_traj][max_seg][3][6], local_ctrl [n_traj][max_ctrl][3].  problems:
+ * traj_of / mode / start_t / arg0 / arg1 [n_prob].  Out, per problem, all required: see above. */
+int fuelmi_map_local_segments(fuelmi_map* m, const fuelmi_localseg_cfg* cfg, int n_traj, const int* n_seg,
+                              const double* seg_times, const double* coef, const double* global_duration,
+                              const int* n_local_ctrl, const double* local_ctrl, const double* local_knot_span,
+                              const double* local_ts, const double* local_te, const double* time_change,
+                              const double* last_time_inc, int n_prob, const int* traj_of, const int* mode,
+                              const double* start_t, const double* arg0, const double* arg1, int* status, int* n_steps,
+                              double* segment_len, int* seg_num, double* duration, double* dt, int* n_points,
+                              double* points, double* derivs, int* n_ctrl, double* ctrl);
+/* the kernel's shape for cfg (host only, no device needed): out8 = {lanes per problem (= steps / points per window),
+ * dynamic LDS bytes of a workgroup, problems per workgroup, largest max_seg, largest max_ctrl, largest max_points, the
+ * point count at which counting stops at the latest, dynamic LDS bytes of the fit for max_points}.  cfg is checked like
+ * above. */
+int fuelmi_localseg_plan(const fuelmi_localseg_cfg* cfg, int out8[8]);
+/* The batch route: one problem per candidate of a device batch (fuelmi_bspline_dev_create), the load_waypoints pattern.
+ * The same kernel writes knot span | points | derivatives into the batch's staging and the fit follows on the map's
+ * stream, so the batch afterwards holds what fuelmi_bspline_dev_load_samples would have been given: the call above
+ * without its host round trip.  degree and the point count are the batch's (max_points = N - degree + 1); the states
+ * and problems are as above, with n_prob = the batch's candidates.  status [C] as above, and
+ *   FUELMI_LOCALSEG_MISFIT  the problem's n_points + degree - 1 is not the batch's point_num.
+ * A candidate whose status is not FUELMI_LOCALSEG_OK keeps the state it had; the call stays FUELMI_OK.  duration [C]
+ * may be null.  Checks as above.  Synchronous. */
+#define FUELMI_LOCALSEG_MISFIT 3
+int fuelmi_bspline_dev_load_local_segments(fuelmi_bspline_dev* b, int max_seg, int max_ctrl, int n_traj, const int* n_seg,
+                                           const double* seg_times, const double* coef, const double* global_duration,
+                                           const int* n_local_ctrl, const double* local_ctrl,
+                                           const double* local_knot_span, const double* local_ts, const double* local_te,
+                                           const double* time_change, const double* last_time_inc, const int* traj_of,
+                                           const int* mode, const double* start_t, const double* arg0, const double* arg1,
+                                           int* status, double* duration);
 
 /* ------------------------------------------------------------------------------------------
  * Safety check of planned trajectories: FastPlannerManager::checkTrajCollision
