@@ -149,6 +149,23 @@ COLRANGE_OK, COLRANGE_NO_COLLISION, COLRANGE_ENDS_IN_OBSTACLE, COLRANGE_NONFINIT
 COLRANGE_MAX_EVENTS, GUIDE_MAX_PTS = 4096, 65536
 
 
+class GainCfg(C.Structure):
+    """fuelmi_gain_cfg: HeadingPlanner's weight type, frustum and lambdas, and the strides of yaws and control points."""
+    _fields_ = [("weight_type", C.c_int), ("in_box", C.c_int), ("factor", C.c_int), ("max_yaw", C.c_int),
+                ("max_ctrl", C.c_int), ("far", C.c_double), ("top_ang", C.c_double), ("left_ang", C.c_double),
+                ("right_ang", C.c_double), ("lambda1", C.c_double), ("lambda2", C.c_double)]
+
+
+class YawPathCfg(C.Structure):
+    """fuelmi_yawpath_cfg: searchPathOfYaw's heading_planner/* parameters round a GainCfg, and the stride of the layers."""
+    _fields_ = [("gain", GainCfg), ("half_vert_num", C.c_int), ("max_layer", C.c_int), ("yaw_diff", C.c_double),
+                ("max_yaw_rate", C.c_double), ("w", C.c_double)]
+
+
+GAIN_NON_UNIFORM, GAIN_UNIFORM = 0, 1
+GAIN_MAX_YAW, GAIN_MAX_CELLS, GAIN_MAX_CTRL, YAWPATH_MAX_LAYER = 31, 12288, 256, 64
+
+
 class LocalSegCfg(C.Structure):
     """fuelmi_localseg_cfg: the degree of the local spline and the fit, the strides of segments, local control points, points."""
     _fields_ = [("degree", C.c_int), ("max_seg", C.c_int), ("max_ctrl", C.c_int), ("max_points", C.c_int)]
@@ -370,6 +387,11 @@ SYMBOLS = {
     "fuelmi_localseg_plan": (C.c_int, [C.POINTER(LocalSegCfg), _ip]),
     "fuelmi_bspline_dev_load_local_segments": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _ip, _dp, _dp,
                                                          _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _ip, _dp]),
+    "fuelmi_map_info_gains": (C.c_int, [_P, C.POINTER(GainCfg), C.c_int, _dp, _ip, _dp, C.c_int, _ip, _dp, _ip, _ip, _dp, _ip,
+                                        _ip, _ip]),
+    "fuelmi_map_yaw_paths": (C.c_int, [_P, C.POINTER(YawPathCfg), C.c_int, _ip, _dp, _dp, _dp, _ip, _dp, _dp, _ip, _dp, _ip,
+                                       _dp, _dp, _ip]),
+    "fuelmi_yawpath_plan": (C.c_int, [C.POINTER(YawPathCfg), _ip]),
     "fuelmi_map_plan_yaws": (C.c_int, [_P, C.POINTER(BsplineCfg), C.POINTER(YawCfg), C.c_int, _ip, _dp, _dp, _dp, _dp, _ip,
                                        _dp, _ip, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp]),
     "fuelmi_bspline_dev_plan_yaws": (C.c_int, [_P, C.POINTER(YawCfg), _dp, _dp, _ip, _dp, _ip, _dp, _dp, _ip, _dp, _dp,

@@ -228,6 +228,7 @@ struct fuelmi_map {
   DevScratch topo_dev;     // fuelmi_map_topo_paths (topo_path.hip): results, inputs, graphs, path sets
   DevScratch colrange_dev; // fuelmi_map_collision_ranges / _guide_points (collide_range.hip): problems in, results out
   DevScratch localseg_dev; // fuelmi_map_local_segments (local_segment.hip): states and problems in, results out
+  DevScratch heading_dev;  // fuelmi_map_info_gains / _yaw_paths (info_gain.hip): views and problems in, results out
   int path_stats[4] = {0, 0, 0, 0};  // fuelmi_map_path_stats
   hipEvent_t goal_ev[3] = {nullptr, nullptr, nullptr};  // the events that split the goal-path call's time
   double goal_ms[2] = {0.0, 0.0};  // fuelmi_map_goal_path_times
@@ -391,6 +392,7 @@ static inline void map_drop_plane_reader(fuelmi_map* m, hipEvent_t ev) {
 // ---- device helpers ---------------------------------------------------------------------------
 #include "voxel_internal.h"  // idx_in_map, pos_to_idx, bit_at, plane_at_pos, plane_window (host and device)
 #include "path_internal.h"   // path_prefix_lengths, path_disc_point, field_cut (host and device)
+#include "ray_internal.h"    // ray_intbound, RayWalk: RayCaster::setInput / step (host and device)
 #ifdef __HIPCC__
 __device__ __forceinline__ u64 bit_range(int first, int count) {
   // `count` ones starting at bit `first` (0 <= first, first+count <= 64)

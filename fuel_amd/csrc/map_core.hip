@@ -724,7 +724,7 @@ extern "C" void fuelmi_map_destroy(fuelmi_map* m) {
   for (Plane* p : planes)
     if (p->base) (void)hipFree(p->base);
   for (DevScratch* s : {&m->path_dev, &m->refine_dev, &m->goal_dev, &m->kino_dev, &m->trajchk_dev, &m->trajsmp_dev,
-                        &m->trajadj_dev, &m->cloud_dev, &m->topo_dev, &m->colrange_dev, &m->localseg_dev})
+                        &m->trajadj_dev, &m->cloud_dev, &m->topo_dev, &m->colrange_dev, &m->localseg_dev, &m->heading_dev})
     s->release();
   goal_path_release(m);
   map_cloud_release(m);

@@ -122,50 +122,25 @@ struct TWork {
 
 __device__ __forceinline__ bool tp_fin3(const double* p) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
 
-// raycast.cpp:10-23: mod(value, 1) is fmod(fmod(value, 1) + 1, 1); fmod(v, 1) of a finite v is v - trunc(v), exactly
-__device__ __forceinline__ double tp_intbound(double s, double ds) {
-  if (ds < 0) s = -s, ds = -ds;
-  const double a = s - trunc(s);
-  const double t = a + 1.0;
-  s = t - trunc(t);
-  return (1 - s) / ds;
-}
-
 // SDFMap::getDistance(id) <= thresh, on k (see above): a voxel outside the map reads -1 and blocks
 __device__ __forceinline__ bool tp_blocked(const Geo& g, const float* __restrict__ dist, int x, int y, int z, float cut) {
   if (x < 0 || y < 0 || z < 0 || x > g.nx - 1 || y > g.ny - 1 || z > g.nz - 1) return true;
   return dist[(long)x * g.nyz + (long)y * g.nz + z] <= cut;
 }
 
-// lineVisib (:252-270): the start voxel is tested, the end voxel is not; setInput's return value is ignored; an axis
-// without a step has tMax = +inf and tDelta = NaN and is never chosen while another axis still steps
+// lineVisib (:252-270): the start voxel is tested, the end voxel is not; the walk itself (setInput / step) is
+// ray_internal.h's
 __device__ bool tp_visib(const Geo& g, const TopoArgs& T, const double* p1, const double* p2, float cut, double pc[3]) {
-  const double sx = p1[0] / g.res, sy = p1[1] / g.res, sz = p1[2] / g.res;
-  const double ex = p2[0] / g.res, ey = p2[1] / g.res, ez = p2[2] / g.res;
-  int x = (int)floor(sx), y = (int)floor(sy), z = (int)floor(sz);
-  const int endx = (int)floor(ex), endy = (int)floor(ey), endz = (int)floor(ez);
-  const double dx = endx - x, dy = endy - y, dz = endz - z;
-  const int stx = dx == 0 ? 0 : (dx < 0 ? -1 : 1), sty = dy == 0 ? 0 : (dy < 0 ? -1 : 1), stz = dz == 0 ? 0 : (dz < 0 ? -1 : 1);
-  double tmx = tp_intbound(sx, dx), tmy = tp_intbound(sy, dy), tmz = tp_intbound(sz, dz);
-  const double tdx = (double)stx / dx, tdy = (double)sty / dy, tdz = (double)stz / dz;
+  RayWalk r;
+  ray_set_input(r, p1[0] / g.res, p1[1] / g.res, p1[2] / g.res, p2[0] / g.res, p2[1] / g.res, p2[2] / g.res);
   // a walk that stays in the map takes fewer steps than this; one that leaves it is blocked there
   const int limit = g.nx + g.ny + g.nz + 8;
   int ix = 0, iy = 0, iz = 0;
   for (int n = 0; n < limit; ++n) {
-    if (x == endx && y == endy && z == endz) return true;
-    ix = (int)((double)x + T.off[0]), iy = (int)((double)y + T.off[1]), iz = (int)((double)z + T.off[2]);
+    if (ray_at_end(r)) return true;
+    ix = (int)((double)r.x + T.off[0]), iy = (int)((double)r.y + T.off[1]), iz = (int)((double)r.z + T.off[2]);
     if (tp_blocked(g, T.dist, ix, iy, iz, cut)) break;
-    if (tmx < tmy) {
-      if (tmx < tmz)
-        x += stx, tmx += tdx;
-      else
-        z += stz, tmz += tdz;
-    } else {
-      if (tmy < tmz)
-        y += sty, tmy += tdy;
-      else
-        z += stz, tmz += tdz;
-    }
+    ray_advance(r);
   }
   pc[0] = (ix + 0.5) * g.res + g.org[0], pc[1] = (iy + 0.5) * g.res + g.org[1], pc[2] = (iz + 0.5) * g.res + g.org[2];
   return false;

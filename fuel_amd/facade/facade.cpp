@@ -12,6 +12,7 @@
 #include "plan_env/edt_environment.h"
 #include "active_perception/frontier_finder.h"
 #include "active_perception/graph_node.h"
+#include "active_perception/heading_planner.h"
 #include "active_perception/perception_utils.h"
 #include "bspline_opt/bspline_optimizer.h"
 
@@ -1530,6 +1531,110 @@ vector<Eigen::Vector3d> BsplineOptimizer::matrixToVectors(const Eigen::MatrixXd&
 Eigen::MatrixXd BsplineOptimizer::getControlPoints() { return control_points_; }
 bool BsplineOptimizer::isQuadratic() {
   return cost_function_ == GUIDE_PHASE || cost_function_ == SMOOTHNESS || cost_function_ == (SMOOTHNESS | WAYPOINTS);
+}
+
+// ------------------------------------------------------------------------------------------------
+// HeadingPlanner (active_perception/heading_planner.h): fuelmi_map_yaw_paths / fuelmi_map_info_gains
+// ------------------------------------------------------------------------------------------------
+HeadingPlanner::HeadingPlanner(ros::NodeHandle& nh) {
+  nh.param("heading_planner/yaw_diff", yaw_diff_, -1.0);
+  nh.param("heading_planner/lambda1", lambda1_, -1.0);
+  nh.param("heading_planner/lambda2", lambda2_, -1.0);
+  nh.param("heading_planner/half_vert_num", half_vert_num_, -1);
+  nh.param("heading_planner/max_yaw_rate", max_yaw_rate_, -1.0);
+  nh.param("heading_planner/w", w_, -1.0);
+  nh.param("heading_planner/weight_type", weight_type_, -1);
+  far_ = 4.5, top_ang_ = 0.56125, left_ang_ = 0.69222, right_ang_ = 0.68901;  // heading_planner.cpp:119-126
+}
+HeadingPlanner::~HeadingPlanner() {}
+void HeadingPlanner::setMap(const shared_ptr<SDFMap>& map) { sdf_map_ = map; }
+
+static fuelmi_gain_cfg heading_gain_cfg(const HeadingPlanner& hp, int weight_type, int in_box, int max_yaw, int max_ctrl) {
+  fuelmi_gain_cfg g;
+  g.weight_type = weight_type, g.in_box = in_box, g.factor = 4, g.max_yaw = max_yaw, g.max_ctrl = max_ctrl;
+  g.far = hp.far_, g.top_ang = hp.top_ang_, g.left_ang = hp.left_ang_, g.right_ang = hp.right_ang_;
+  g.lambda1 = hp.lambda1_, g.lambda2 = hp.lambda2_;
+  return g;
+}
+
+int HeadingPlanner::searchPathsOfYaw(const vector<vector<Eigen::Vector3d>>& pts, const vector<vector<double>>& yaws,
+                                     const vector<double>& dts, const vector<Eigen::MatrixXd>& ctrl_pts,
+                                     vector<vector<double>>& paths) {
+  const size_t n = yaws.size();
+  paths.assign(n, vector<double>());
+  last_status_.assign(n, 0), last_path_vertex_.assign(n, vector<int>()), last_gains_.assign(n, vector<double>());
+  last_g_value_.assign(n, vector<double>());
+  if (pts.size() != n || dts.size() != n || ctrl_pts.size() != n || half_vert_num_ < 0) return last_rc_ = FUELMI_EINVAL;
+  size_t ml = 1, mc = 1;
+  for (size_t b = 0; b < n; ++b) {
+    if (pts[b].size() != yaws[b].size()) return last_rc_ = FUELMI_EINVAL;
+    ml = std::max(ml, yaws[b].size()), mc = std::max(mc, (size_t)ctrl_pts[b].rows());
+  }
+  const size_t nv = 2 * (size_t)half_vert_num_ + 1;
+  fuelmi_yawpath_cfg c;
+  c.gain = heading_gain_cfg(*this, weight_type_, 1, (int)nv, (int)mc);
+  c.half_vert_num = half_vert_num_, c.max_layer = (int)ml;
+  c.yaw_diff = yaw_diff_, c.max_yaw_rate = max_yaw_rate_, c.w = w_;
+  vector<int> n_layer(n), n_ctrl(n), status(n), pv(n * ml), n_rays(n * ml);
+  vector<double> P(n * ml * 3), Y(n * ml), C(n * mc * 3), path(n * ml), gains(n * ml * nv), gv(n * ml * nv);
+  for (size_t b = 0; b < n; ++b) {
+    n_layer[b] = (int)yaws[b].size(), n_ctrl[b] = (int)ctrl_pts[b].rows();
+    for (size_t i = 0; i < yaws[b].size(); ++i) {
+      Y[b * ml + i] = yaws[b][i];
+      for (int k = 0; k < 3; ++k) P[(b * ml + i) * 3 + k] = pts[b][i](k);
+    }
+    for (int i = 0; i < n_ctrl[b]; ++i)
+      for (int k = 0; k < 3; ++k) C[(b * mc + i) * 3 + k] = ctrl_pts[b](i, k);
+  }
+  last_rc_ = fuelmi_map_yaw_paths(sdf_map_ ? sdf_map_->device() : nullptr, &c, (int)n, n_layer.data(), P.data(), Y.data(),
+                                  dts.data(), n_ctrl.data(), C.data(), nullptr, status.data(), path.data(), pv.data(),
+                                  gains.data(), gv.data(), n_rays.data());
+  if (last_rc_ != FUELMI_OK && last_rc_ != FUELMI_ELIMIT) {
+    ROS_ERROR("[Heading]: fuelmi_map_yaw_paths: %s", fuelmi_last_error());
+    return last_rc_;
+  }
+  for (size_t b = 0; b < n; ++b) {
+    last_status_[b] = status[b];
+    if (status[b] != 0) continue;
+    paths[b].assign(path.begin() + b * ml, path.begin() + b * ml + n_layer[b]);
+    last_path_vertex_[b].assign(pv.begin() + b * ml, pv.begin() + b * ml + n_layer[b]);
+    for (int i = 0; i < n_layer[b]; ++i) {
+      last_gains_[b].insert(last_gains_[b].end(), gains.begin() + (b * ml + i) * nv, gains.begin() + (b * ml + i + 1) * nv);
+      last_g_value_[b].insert(last_g_value_[b].end(), gv.begin() + (b * ml + i) * nv, gv.begin() + (b * ml + i + 1) * nv);
+    }
+  }
+  return last_rc_;
+}
+
+void HeadingPlanner::searchPathOfYaw(const vector<Eigen::Vector3d>& pts, const vector<double>& yaws, const double& dt,
+                                     const Eigen::MatrixXd& ctrl_pts, vector<double>& path) {
+  vector<vector<double>> paths;
+  searchPathsOfYaw({pts}, {yaws}, {dt}, {ctrl_pts}, paths);
+  // (the reference appends to `path`)
+  if (!paths.empty()) path.insert(path.end(), paths[0].begin(), paths[0].end());
+}
+
+int HeadingPlanner::calcInfoGains(const vector<Eigen::Vector3d>& pts, const vector<double>& yaws, vector<double>& gains) {
+  const size_t n = pts.size();
+  gains.assign(n, 0.0);
+  if (yaws.size() != n) return last_rc_ = FUELMI_EINVAL;
+  const fuelmi_gain_cfg c = heading_gain_cfg(*this, FUELMI_GAIN_UNIFORM, 0, 1, 1);  // calcInfoGain: no isInBox, counts
+  vector<double> P(n * 3 + 1);
+  vector<int> n_yaw(n + 1, 1), status(n + 1), n_cand(n + 1), n_vis(n + 1), n_rays(n + 1);
+  for (size_t b = 0; b < n; ++b)
+    for (int k = 0; k < 3; ++k) P[b * 3 + k] = pts[b](k);
+  last_rc_ = fuelmi_map_info_gains(sdf_map_ ? sdf_map_->device() : nullptr, &c, (int)n, P.data(), n_yaw.data(), yaws.data(),
+                                   0, nullptr, nullptr, nullptr, status.data(), gains.data(), n_cand.data(), n_vis.data(),
+                                   n_rays.data());
+  last_status_.assign(status.begin(), status.begin() + n);
+  if (last_rc_ != FUELMI_OK && last_rc_ != FUELMI_ELIMIT) ROS_ERROR("[Heading]: fuelmi_map_info_gains: %s", fuelmi_last_error());
+  return last_rc_;
+}
+
+double HeadingPlanner::calcInfoGain(const Eigen::Vector3d& pt, const double& yaw, const int&) {
+  vector<double> gains;
+  calcInfoGains({pt}, {yaw}, gains);
+  return gains.empty() ? 0.0 : gains[0];
 }
 
 }  // namespace fast_planner

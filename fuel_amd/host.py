@@ -13,8 +13,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BsplineBatch, BsplineCfg, CloudCfg, ColRangeCfg, FrontierCfg, GoalCfg, KinoCfg, LocalSegCfg, MapCfg, MapInfo, PathCfg, RefineCfg, RenderCfg, TopoCfg, TrajAdjCfg, TrajChkCfg, TrajSmpCfg, TspCfg,
-                   WptrajCfg, YawCfg, check, lib)
+from ._lib import (BsplineBatch, BsplineCfg, CloudCfg, ColRangeCfg, FrontierCfg, GainCfg, GoalCfg, KinoCfg, LocalSegCfg, MapCfg, MapInfo, PathCfg, RefineCfg, RenderCfg, TopoCfg, TrajAdjCfg, TrajChkCfg, TrajSmpCfg, TspCfg,
+                   WptrajCfg, YawCfg, YawPathCfg, check, lib)
 
 # exploration.launch / algorithm.xml defaults (exploration_manager/launch/algorithm.xml:33-59,170-181)
 DEFAULT_MAP = dict(resolution=0.1, ground_height=-1.0, obstacles_inflation=0.199,
@@ -85,6 +85,41 @@ def topo_cfg(sample_inflate=(1.0, 3.5, 1.0), clearance=0.2, ratio_to_short=5.5, 
 def colrange_cfg(degree=3, max_ctrl=4, max_events=8, max_pts=_lib.TOPO_MAX_POINTS_IN, clearance=0.2):
     """fuelmi_colrange_cfg: the spline's degree, topo_prm/clearance and the strides of the event and point arrays"""
     return ColRangeCfg(int(degree), int(max_ctrl), int(max_events), int(max_pts), float(clearance))
+
+
+def gain_cfg(weight_type=_lib.GAIN_UNIFORM, in_box=True, factor=4, max_yaw=1, max_ctrl=1, far=4.5, top_ang=0.56125,
+             left_ang=0.69222, right_ang=0.68901, lambda1=2.0, lambda2=1.0):
+    """fuelmi_gain_cfg with HeadingPlanner's constants (heading_planner.cpp:119-128, :265) and algorithm.xml's lambdas"""
+    return GainCfg(int(weight_type), 1 if in_box else 0, int(factor), int(max_yaw), int(max_ctrl), float(far),
+                   float(top_ang), float(left_ang), float(right_ang), float(lambda1), float(lambda2))
+
+
+def yawpath_cfg(half_vert_num=3, max_layer=7, yaw_diff=5 * 3.1415926 / 180.0, max_yaw_rate=60 * 3.1415926 / 180.0, w=10.0,
+                **gain):
+    """fuelmi_yawpath_cfg with topo_algorithm.xml's heading_planner/* values (plan_manage/launch/topo_algorithm.xml:151-157);
+    gain: the fields of gain_cfg(), NON_UNIFORM unless said otherwise as in that file"""
+    gain.setdefault("weight_type", _lib.GAIN_NON_UNIFORM)
+    g = gain_cfg(**dict(gain, max_yaw=2 * int(half_vert_num) + 1))
+    return YawPathCfg(g, int(half_vert_num), int(max_layer), float(yaw_diff), float(max_yaw_rate), float(w))
+
+
+def yawpath_plan(cfg=None):
+    """host only: the shape of the gain and search kernels for a YawPathCfg (fuelmi_yawpath_plan)"""
+    out = (C.c_int * 10)()
+    check(lib().fuelmi_yawpath_plan(C.byref(cfg if cfg is not None else yawpath_cfg()), out))
+    return dict(zip(("lanes", "lds_bytes", "groups_per_workgroup", "max_cells", "max_yaw", "max_ctrl", "search_lanes",
+                     "search_lds_bytes", "search_problems_per_workgroup", "max_layer"), [int(v) for v in out]))
+
+
+def _pack_ctrl(ctrl, max_ctrl):
+    """a list of [n, 3] control-point arrays as (n_ctrl [k], ctrl [k, max_ctrl, 3], max_ctrl)"""
+    cs = [np.ascontiguousarray(c, dtype=np.float64).reshape(-1, 3) for c in ctrl]
+    mc = int(max_ctrl) if max_ctrl is not None else max([len(c) for c in cs] + [1])
+    arr = np.zeros((len(cs), max(mc, 0), 3))
+    for i, c in enumerate(cs):
+        k = min(len(c), arr.shape[1])
+        arr[i, :k] = c[:k]
+    return np.array([len(c) for c in cs], dtype=np.int32), arr, mc
 
 
 def _pack_localseg(states, problems, degree, max_seg, max_ctrl):
@@ -877,6 +912,81 @@ class SDFMap:
         check(lib().fuelmi_localseg_plan(C.byref(LocalSegCfg(int(degree), int(max_seg), int(max_ctrl), int(max_points))), out))
         return dict(zip(("lanes", "lds_bytes", "waves", "max_seg", "max_ctrl", "max_points", "count_cap", "fit_lds_bytes"),
                         [int(v) for v in out]))
+
+    # --- information gain and yaw search of HeadingPlanner (include/fuelmi.h fuelmi_map_info_gains) ---
+    GAIN_NON_UNIFORM, GAIN_UNIFORM = _lib.GAIN_NON_UNIFORM, _lib.GAIN_UNIFORM
+
+    def info_gains(self, pos, yaws, ctrl=None, path_of=None, allow_limit=False, max_yaw=None, max_ctrl=None, **cfg):
+        """calcInformationGain / calcInfoGain for view groups on the device's unknown and occupied planes: pos [n, 3],
+        yaws a list of yaw lists (one per group); NON_UNIFORM: ctrl a list of [k, 3] control-point arrays and path_of [n]
+        the array each group weighs with (default 0).  cfg: the fields of gain_cfg().  Returns a dict of arrays: status
+        (-1: over the cell cap), gain / n_cand / n_visible [n, max_yaw], n_rays [n]; limit."""
+        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+        n = len(pos)
+        ys = [np.atleast_1d(np.asarray(y, dtype=np.float64)) for y in yaws]
+        assert len(ys) == n
+        my = int(max_yaw) if max_yaw is not None else max([len(y) for y in ys] + [1])
+        c = gain_cfg(**dict(cfg, max_yaw=my))
+        n_yaw = np.array([len(y) for y in ys], dtype=np.int32)
+        ya = np.zeros((n, max(my, 0)))
+        for b, y in enumerate(ys):
+            k = min(len(y), ya.shape[1])
+            ya[b, :k] = y[:k]
+        n_ctrl = carr = pof = None
+        n_path = 0
+        if ctrl is not None:
+            n_ctrl, carr, c.max_ctrl = _pack_ctrl(ctrl, max_ctrl)
+            n_path = len(n_ctrl)
+            pof = np.ascontiguousarray(np.broadcast_to(np.asarray(0 if path_of is None else path_of, dtype=np.int32), (n,)))
+        o = dict(status=np.zeros(n, dtype=np.int32), gain=np.zeros((n, my)), n_cand=np.zeros((n, my), dtype=np.int32),
+                 n_visible=np.zeros((n, my), dtype=np.int32), n_rays=np.zeros(n, dtype=np.int32))
+        rc = self.L.fuelmi_map_info_gains(self.h, C.byref(c), n, _dp(pos), _ip(n_yaw), _dp(ya), n_path, _ip(n_ctrl),
+                                          _dp(carr), _ip(pof), _ip(o["status"]), _dp(o["gain"]), _ip(o["n_cand"]),
+                                          _ip(o["n_visible"]), _ip(o["n_rays"]))
+        if not (allow_limit and rc == -5):
+            check(rc)
+        o["limit"] = rc == -5
+        return o
+
+    def yaw_paths(self, pts, yaws, dt, ctrl=None, gains_in=None, allow_limit=False, max_layer=None, max_ctrl=None, **cfg):
+        """searchPathOfYaw per problem: pts a list of [L, 3] way-points, yaws a list of [L] yaws, dt [n]; ctrl a list of
+        [k, 3] control-point arrays, one per problem (NON_UNIFORM); gains_in a list of [L, 2h + 1] arrays: the search
+        runs on those gains and no ray is walked.  cfg: the fields of yawpath_cfg().  Returns a dict of arrays: status
+        (-1: a layer over the cell cap), n_layer, path / path_vertex [n, max_layer], gains / g_value
+        [n, max_layer, 2h + 1], n_rays [n, max_layer]; limit."""
+        ps = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in pts]
+        ys = [np.atleast_1d(np.asarray(y, dtype=np.float64)) for y in yaws]
+        n = len(ps)
+        assert len(ys) == n and all(len(p) == len(y) for p, y in zip(ps, ys))
+        ml = int(max_layer) if max_layer is not None else max([len(y) for y in ys] + [1])
+        c = yawpath_cfg(**dict(cfg, max_layer=ml))
+        nv = 2 * c.half_vert_num + 1
+        n_layer = np.array([len(y) for y in ys], dtype=np.int32)
+        pa, ya = np.zeros((n, max(ml, 0), 3)), np.zeros((n, max(ml, 0)))
+        for b in range(n):
+            k = min(len(ys[b]), ya.shape[1])
+            pa[b, :k], ya[b, :k] = ps[b][:k], ys[b][:k]
+        dta = np.ascontiguousarray(np.broadcast_to(np.asarray(dt, dtype=np.float64), (n,)))
+        n_ctrl = carr = gin = None
+        if ctrl is not None:
+            n_ctrl, carr, c.gain.max_ctrl = _pack_ctrl(ctrl, max_ctrl)
+            assert len(n_ctrl) == n
+        if gains_in is not None:
+            gin = np.zeros((n, max(ml, 0), max(nv, 0)))
+            for b, gi in enumerate(gains_in):
+                gi = np.asarray(gi, dtype=np.float64).reshape(-1, nv)
+                k = min(len(gi), gin.shape[1])
+                gin[b, :k] = gi[:k]
+        o = dict(status=np.zeros(n, dtype=np.int32), n_layer=n_layer, path=np.zeros((n, ml)),
+                 path_vertex=np.zeros((n, ml), dtype=np.int32), gains=np.zeros((n, ml, max(nv, 0))),
+                 g_value=np.zeros((n, ml, max(nv, 0))), n_rays=np.zeros((n, ml), dtype=np.int32))
+        rc = self.L.fuelmi_map_yaw_paths(self.h, C.byref(c), n, _ip(n_layer), _dp(pa), _dp(ya), _dp(dta), _ip(n_ctrl),
+                                         _dp(carr), _dp(gin), _ip(o["status"]), _dp(o["path"]), _ip(o["path_vertex"]),
+                                         _dp(o["gains"]), _dp(o["g_value"]), _ip(o["n_rays"]))
+        if not (allow_limit and rc == -5):
+            check(rc)
+        o["limit"] = rc == -5
+        return o
 
     # --- the yaw trajectory of a position spline (include/fuelmi.h fuelmi_map_plan_yaws) ---
     YAW_EXPLORE, YAW_FOLLOW, YAW_OK, YAW_DEGENERATE = _lib.YAW_EXPLORE, _lib.YAW_FOLLOW, _lib.YAW_OK, _lib.YAW_DEGENERATE

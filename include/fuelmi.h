@@ -1234,6 +1234,118 @@ int fuelmi_bspline_dev_load_local_segments(fuelmi_bspline_dev* b, int max_seg, i
                                            int* status, double* duration);
 
 /* ------------------------------------------------------------------------------------------
+ * Information gain of camera views and the yaw search of HeadingPlanner
+ * (active_perception/src/heading_planner.cpp), the hot part of FastPlannerManager::planYawActMap
+ * (plan_manage/src/planner_manager_dev.cpp:7-113) and of localExplore (:128-247), on the device's own unknown and
+ * occupied bit planes: no host mirror is read or needed.
+ *
+ * fuelmi_map_info_gains: n_group view groups; a group is one camera position and n_yaw[g] <= max_yaw yaws.
+ * calcInfoGain (:324-391) is a group of one yaw with in_box = 0 and UNIFORM; one layer of searchPathOfYaw (:187-203) is
+ * a group of 2 * half_vert_num + 1 yaws with in_box = 1.  Per view, kept literally:
+ *   1. The camera transform (:240-248): R_wb = Rz(yaw), T_wc = T_wb * T_bc with T_bc = T_cb^-1 (:151-152), so
+ *      R_wc = [[sin, 0, cos], [-cos, 0, sin], [0, 1, 0]] and t_wc = pt.  The four plane normals (:121-128, built from
+ *      sin / cos of pi/2 - the half angle) rotated by R_wc (:251-253).
+ *   2. calcFovAABB (:401-418): the five vertices R_wc * v + t_wc of :136-139 -- lefttop's x is -far * TAN(left_ang), the
+ *      other three are sines -- and t_wc; their bounding box; SDFMap::boundBox against the exploration box
+ *      (sdf_map.h:189-194); posToIndex (floor) of both corners.
+ *   3. The loops x, y, z over the index box (:268-270) with `x % factor == 0 && y % factor == 0 && z % factor == 0` on
+ *      the INDEX (:272).
+ *   4. `if (!sdf_map_->getOccupancy(pt_idx) == SDFMap::UNKNOWN) continue;` (:275).  As written `!` binds first:
+ *      (!occ) == 0, which is true for every occ != 0 -- FREE, OCCUPIED and the -1 of an index outside the map.  So the
+ *      line skips every KNOWN cell and every cell outside the map, and only unknown cells go on.
+ *   5. in_box: isInBox(Vector3i) (sdf_map.h:171-178), box_min <= id < box_max (:276; calcInfoGain has no such line).
+ *   6. insideFoV (:475-487) of indexToPos(id): |p - pt| > far is outside, then dot(p - pt, n) < 0.1 is outside per
+ *      normal in the order top, bottom, left, right.  A cell that passes is a CANDIDATE (n_cand).
+ *   7. The ray (:290-299): RayCaster::setInput(check_pt / resolution, pt / resolution), divisions by the resolution;
+ *      every voxel step() hands out is read at int(ray + offset), offset = 0.5 - origin / resolution, the cast
+ *      truncating toward zero; a voxel outside the map is not occupied; the start voxel is tested, the end voxel is
+ *      not.  A candidate whose ray met no occupied voxel is VISIBLE (n_visible).
+ *   8. UNIFORM: gain = n_visible.  NON_UNIFORM: gain = sum over the visible cells of exp(-lambda1 * d1 - lambda2 * d2),
+ *      distToPathAndCurPos (:452-473): d1 the distance to the FIRST nearest control point (strict <), d2 the polyline
+ *      length up to it summed from index 0.
+ * Each view's rotation, rotated normals and index box are computed on the host inside the call, with libm and f64 in
+ * the reference's order, so every frustum decision is the reference's; cells, rays, weights and sums run on the device.
+ * The CastFlags cache (:280-308) is a memo -- a cell's ray depends on the position, not the yaw -- and is restated as
+ * one: the rays of a group are walked once (n_rays [n_group]: the cells that are a candidate of at least one view)
+ * and shared by its yaws.  A group of K yaws equals K groups of one yaw bit for bit.  The reference's races on that
+ * array and its fixed 1 000 000 entries are not reproduced.  UNIFORM gains are exact counts; a NON_UNIFORM sum is
+ * taken in an order fixed by the cells' own indices (not the reference's x, y, z order): the same bits on every run and
+ * at every place in a batch, within tests/heading_ref.py parity_tolerance of the reference's sum.
+ * Defined where the reference is not: a ray that has not met its end voxel after |dx| + |dy| + |dz| + 2 steps (the
+ * reference would walk on for ever) counts as blocked.
+ *   status -1   the group's subsampled union box holds more than FUELMI_GAIN_MAX_CELLS cells: its outputs are zero, the
+ *               other groups complete, the call returns FUELMI_ELIMIT.
+ * FUELMI_EINVAL before any launch: pointers; weight_type; factor < 1; far / angles / lambdas not finite, far <= 0 or
+ * > 1e3; n_yaw[g] outside 0 .. max_yaw; a position or yaw that is not finite or a coordinate with |.| >= 1e7; under
+ * NON_UNIFORM path_of[g] outside 0 .. n_path - 1, n_ctrl[p] outside 1 .. max_ctrl, a control point not finite.
+ * FUELMI_ELIMIT before any launch: max_yaw > FUELMI_GAIN_MAX_YAW, max_ctrl > FUELMI_GAIN_MAX_CTRL.  n_group = 0 is
+ * FUELMI_OK.  Runs on the map's stream behind the mutators queued before it: host arrays in and out, synchronous, one
+ * thread at a time per map; its scratch is one grow-only allocation on the map.  One workgroup per group; a result
+ * does not depend on the group's place in the batch.
+ *
+ * fuelmi_map_yaw_paths: n_prob problems of searchPathOfYaw (:170-234).  Layer 0 and layer n_layer - 1 hold the one
+ * vertex (yaws[i], gain 0); an inner layer i holds the 2h + 1 vertices yaws[i] + double(j - h) * yaw_diff with the
+ * gain of the view (pts[i], that yaw), in_box and weight type as cfg.gain says.  gains_in given: no ray is walked, the
+ * search runs on those numbers (n_rays = 0).  Graph::dijkstraSearch (:52-100) is a FIFO label update on a layered
+ * complete graph -- all of layer i is popped before any of layer i + 1 -- so it is this recurrence: g of the start is
+ * 0; for a vertex b of layer i + 1 the predecessors c of layer i are taken in layer order, g_tmp = g_c - gain_b +
+ * w * penal(|yaw_c - yaw_b|), penal(d) = 0 for yr = d / dt <= max_yaw_rate, else (yr - max_yaw_rate)^2 (:42-49); the
+ * first predecessor sets g and the parent unconditionally, a later one replaces them unless g_tmp > g (:87-94: a tie
+ * goes to the LATER predecessor).  Out per problem: status; path [max_layer] the yaws from start to goal; path_vertex
+ * [max_layer] the index j per layer (0 for the first and last); gains and g_value [max_layer][2h + 1] (rows 0 and
+ * n_layer - 1 use entry 0; what is not written is zero); n_rays [max_layer].
+ * Defined where the reference is not: n_layer = 1: the path is the one yaw.  status -1: a layer's group is over
+ * FUELMI_GAIN_MAX_CELLS; the problem's other outputs are zero, the others complete, FUELMI_ELIMIT.
+ * FUELMI_EINVAL before any launch: as above, and n_layer[i] outside 1 .. max_layer, dt not finite or <= 0, yaw_diff /
+ * max_yaw_rate / w or a gains_in entry not finite, half_vert_num < 0.  FUELMI_ELIMIT before any launch: 2h + 1 >
+ * FUELMI_GAIN_MAX_YAW, max_layer > FUELMI_YAWPATH_MAX_LAYER, max_ctrl > FUELMI_GAIN_MAX_CTRL.  cfg.gain.max_yaw is
+ * ignored (it is 2h + 1).  One wave per problem, one lane per candidate of the current layer.
+ * Out of scope: the way-point sampling at the head of planYawActMap (fuelmi_map_plan_yaws' step 4 with other
+ * constants) and its closing BsplineOptimizer::optimize; setFrontier / calcVisibFrontier / showVisibFrontier;
+ * VisibilityUtil.
+ * ---------------------------------------------------------------------------------------- */
+#define FUELMI_GAIN_NON_UNIFORM 0  /* HeadingPlanner's enum (heading_planner.h) */
+#define FUELMI_GAIN_UNIFORM 1
+#define FUELMI_GAIN_MAX_YAW 31        /* largest max_yaw and 2 * half_vert_num + 1 */
+#define FUELMI_GAIN_MAX_CELLS 12288   /* subsampled cells of a group's union box */
+#define FUELMI_GAIN_MAX_CTRL 256      /* largest max_ctrl */
+#define FUELMI_YAWPATH_MAX_LAYER 64   /* largest max_layer */
+typedef struct {
+  int weight_type;     /* FUELMI_GAIN_* (heading_planner/weight_type) */
+  int in_box;          /* 1: calcInformationGain's isInBox test, 0: calcInfoGain */
+  int factor;          /* the subsampling factor, 4 in the reference */
+  int max_yaw;         /* stride of yaws / gain / n_cand / n_visible */
+  int max_ctrl;        /* stride of ctrl */
+  double far;          /* far_, 4.5 */
+  double top_ang, left_ang, right_ang; /* 0.56125, 0.69222, 0.68901 */
+  double lambda1, lambda2;             /* heading_planner/lambda1, lambda2 */
+} fuelmi_gain_cfg;
+typedef struct {
+  fuelmi_gain_cfg gain;
+  int half_vert_num;   /* heading_planner/half_vert_num */
+  int max_layer;       /* stride of pts / yaws and of every per-layer output */
+  double yaw_diff, max_yaw_rate, w; /* heading_planner/yaw_diff, max_yaw_rate, w */
+} fuelmi_yawpath_cfg;
+/* pos [n_group][3], n_yaw [n_group], yaws [n_group][max_yaw]; n_ctrl [n_path], ctrl [n_path][max_ctrl][3], path_of
+ * [n_group] (all three may be null under UNIFORM).  Out: status / n_rays [n_group]; gain / n_cand / n_visible
+ * [n_group][max_yaw], all required. */
+int fuelmi_map_info_gains(fuelmi_map* m, const fuelmi_gain_cfg* cfg, int n_group, const double* pos, const int* n_yaw,
+                          const double* yaws, int n_path, const int* n_ctrl, const double* ctrl, const int* path_of,
+                          int* status, double* gain, int* n_cand, int* n_visible, int* n_rays);
+/* n_layer / dt [n_prob], pts [n_prob][max_layer][3], yaws [n_prob][max_layer]; n_ctrl [n_prob], ctrl
+ * [n_prob][max_ctrl][3] (problem i's own control points; may be null under UNIFORM or with gains_in); gains_in
+ * [n_prob][max_layer][2h + 1] or null.  Out, all required: see above. */
+int fuelmi_map_yaw_paths(fuelmi_map* m, const fuelmi_yawpath_cfg* cfg, int n_prob, const int* n_layer, const double* pts,
+                         const double* yaws, const double* dt, const int* n_ctrl, const double* ctrl,
+                         const double* gains_in, int* status, double* path, int* path_vertex, double* gains,
+                         double* g_value, int* n_rays);
+/* the kernels' shape for cfg (host only, no device needed): out10 = {lanes of a gain workgroup, its dynamic LDS bytes
+ * for a group of FUELMI_GAIN_MAX_CELLS cells, groups per workgroup, FUELMI_GAIN_MAX_CELLS, FUELMI_GAIN_MAX_YAW,
+ * FUELMI_GAIN_MAX_CTRL, lanes of a search problem, static LDS bytes of a search workgroup, search problems per
+ * workgroup, FUELMI_YAWPATH_MAX_LAYER}.  cfg is checked like above. */
+int fuelmi_yawpath_plan(const fuelmi_yawpath_cfg* cfg, int out10[10]);
+
+/* ------------------------------------------------------------------------------------------
  * Safety check of planned trajectories: FastPlannerManager::checkTrajCollision
  * (plan_manage/src/planner_manager.cpp:96-118), which the exploration FSM's safetyCallback runs every 50 ms while a
  * trajectory is flown (exploration_manager/src/fast_exploration_fsm.cpp:335-345), for n_prob independent problems in
