@@ -6,7 +6,8 @@ Needs the reference checkout (REF=... or /root/reference/fuel_planner).  The ref
 tests/golden/kino_golden/driver.cpp against the Eigen / ROS stand-ins of compat/, tests/dropin/shim and a dense-array
 stand-in for the five SDFMap members it uses (tests/golden/kino_golden/plan_env/); the build goes to build/kino_golden/
 (git-ignored).  -O2: the reference's pow(tau, 2) is then the product the compiler folds it into, as in a release build.
-Scenes that change res / time_res / time_res_init are not recorded: those are constants of the reference's search()."""
+Scenes that change what the reference holds constant (kino_ref.NOT_IN_REFERENCE: res / time_res / time_res_init of
+search(), seg_num and the 8 of getSamples) are not recorded.  Arguments: the scenes to record; none records all."""
 import os
 import subprocess
 import sys
@@ -92,7 +93,7 @@ def run(exe, name, sc):
 if __name__ == "__main__":
     exe = build()
     for name, sc in kr.scenes().items():
-        if any(k in sc.get("cfg", {}) for k in ("res", "time_res", "time_res_init", "seg_num")):
+        if not kr.has_fixture(sc) or (sys.argv[1:] and name not in sys.argv[1:]):
             continue
         run(exe, name, sc)
         print("recorded", name)

@@ -9,7 +9,11 @@ stale, the accumulating loops that build the primitive lists, the shot's accumul
 of one expansion's primitives (stateTransit, the tests, estimateHeuristic) is evaluated for all primitives at once with
 numpy: every operation is an IEEE f64 + - * / sqrt in the reference's order, element by element.  Every libm result
 (cbrt, acos, cos, pow(., 3)) goes through Search.lm: the plain run calls glibc, a seeded run nudges each result by a
-random -4 .. +4 ulp -- the stand-in for another libm (the device's)."""
+random -4 .. +4 ulp -- the stand-in for another libm (the device's).
+
+count=True adds counters that describe what the DEVICE does for the same sequence and change nothing of the above: a model
+of the kernel's open-addressing table (TableModel: displaced inserts, longest probe, wraps, look-ups that pass another
+node's slot) and the order-dependent events by the wave of their lane (wave_counts)."""
 import ctypes
 import math
 import struct
@@ -147,7 +151,67 @@ def heap_pop(heap):
 
 
 class Node:
-    __slots__ = ("index", "state", "g", "f", "input", "duration", "parent", "closed", "serial")
+    __slots__ = ("index", "state", "g", "f", "input", "duration", "parent", "closed", "serial", "lane")
+
+
+WAVE, LANES = 64, 256
+
+
+def voxel_hash(key):
+    """the device's hash of a voxel triple: 32-bit unsigned arithmetic, so a negative index counts as its two's
+    complement"""
+    m = 0xFFFFFFFF
+    x, y, z = (int(v) & m for v in key)  # (Python integers: the products pass 64 bits)
+    return (x * 73856093 & m) ^ (y * 19349663 & m) ^ (z * 83492791 & m)
+
+
+def table_slots(allocate_num):
+    """the smallest power of two that is at least 2 allocate_num and at least 16"""
+    cap = 16
+    while cap < 2 * allocate_num:
+        cap <<= 1
+    return cap
+
+
+class TableModel:
+    """What the device's open-addressing table (linear probing, cleared per search) does for the sequence of inserts and
+    lookups of one search.  It describes, it decides nothing: the restatement keeps its nodes in a dict."""
+
+    def __init__(self, allocate_num):
+        self.cap = table_slots(allocate_num)
+        self.slot = {}
+        self.c = dict(slots=self.cap, inserts=0, negative=0, displaced=0, longest_probe=0, wraps=0, lookups=0, lookup_wraps=0,
+                      found_closed_displaced=0, found_open_displaced=0)
+
+    def insert(self, node):
+        h, steps = voxel_hash(node.index) & (self.cap - 1), 0
+        while h in self.slot:
+            h, steps = (h + 1) & (self.cap - 1), steps + 1
+            self.c["wraps"] += h == 0
+        self.slot[h] = node
+        self.c["inserts"] += 1
+        self.c["negative"] += min(node.index) < 0  # a voxel outside the map, below its origin
+        self.c["displaced"] += steps > 0
+        self.c["longest_probe"] = max(self.c["longest_probe"], steps)
+
+    def lookup(self, key):
+        h, passed = voxel_hash(key) & (self.cap - 1), 0
+        self.c["lookups"] += 1
+        while h in self.slot and passed < self.cap:
+            n = self.slot[h]
+            if n.index == key:
+                if passed:
+                    self.c["found_closed_displaced" if n.closed else "found_open_displaced"] += 1
+                return n
+            h, passed = (h + 1) & (self.cap - 1), passed + 1
+            self.c["lookup_wraps"] += h == 0
+        return None
+
+
+def wave_counts():
+    """order-dependent events by the wave (lane // 64) of the primitive; sibling_f_cross: those sibling_f events whose
+    first lane (the one that created the sibling) lies in an earlier wave"""
+    return {k: [0] * (LANES // WAVE) for k in ("sibling_f", "sibling_f_cross", "open_g")}
 
 
 class Search:
@@ -157,7 +221,9 @@ class Search:
         self.cfg.update(cfg or {})
         self.rng = None if seed is None else np.random.default_rng(seed)
         self.count = count
-        self.counts = dict(sibling_f=0, open_g=0, stale_pop=0)
+        # tables: one dict per search (TableModel.c); waves: the order-dependent events of the init and of the regular
+        # expansions by the wave of their lane
+        self.counts = dict(sibling_f=0, open_g=0, stale_pop=0, tables=[], waves=dict(init=wave_counts(), reg=wave_counts()))
         self.prims = primitives(self.cfg)
         self.inv_res = 1.0 / self.cfg["resolution"]
         self.tolerance = math.ceil(1 / self.cfg["resolution"])
@@ -282,7 +348,7 @@ class Search:
         cur.state = np.concatenate([start_pt, start_v])
         cur.index = tuple(self.pos_to_index(start_pt))
         cur.g = 0.0
-        cur.input, cur.duration, cur.serial = np.zeros(3), 0.0, 0
+        cur.input, cur.duration, cur.serial, cur.lane = np.zeros(3), 0.0, 0, 0
         end_state = np.concatenate([end_pt, end_v])
         end_index = self.pos_to_index(end_pt)
         h, _ = self.heuristic(cur.state[None, :], end_state)
@@ -291,6 +357,11 @@ class Search:
         heap_push(heap, cur)
         self.use_node_num += 1
         expanded = {cur.index: cur}
+        table = None
+        if self.count:
+            table = TableModel(alloc)
+            table.insert(cur)
+            self.counts["tables"].append(table.c)
         init_search = init
         init_d, inputs, durs = self.prims
         while heap:
@@ -316,6 +387,7 @@ class Search:
             heap_pop(heap)
             cur.closed = True
             self.iter_num += 1
+            waves = self.counts["waves"]["init" if init_search else "reg"]
             if init_search:
                 um = np.repeat(np.asarray(start_a, dtype=np.float64)[None, :], len(init_d), axis=0)
                 tau = np.array(init_d)
@@ -327,6 +399,9 @@ class Search:
             pro = self.transit(cur.state, um, tau)
             ok = km.in_box(pro[:, :3])
             pid = self.pos_to_index(pro[:, :3])
+            if table is not None:  # the device looks up every primitive that ends inside the box, before anything changes
+                for p in np.nonzero(ok)[0]:
+                    assert table.lookup(tuple(pid[p])) is expanded.get(tuple(pid[p]))
             ok &= ~np.any(np.abs(pro[:, 3:]) > cfg["max_vel"], axis=1)
             ok &= ~np.all(pid == np.array(cur.index), axis=1)
             for k in range(1, cfg["check_num"] + 1):
@@ -356,6 +431,8 @@ class Search:
                         if tmp_f < e.f:
                             e.f, e.g, e.state, e.input, e.duration = tmp_f, tmp_g, pro[p].copy(), um[p].copy(), float(tau[p])
                             self.counts["sibling_f"] += 1
+                            waves["sibling_f"][p // WAVE] += 1
+                            waves["sibling_f_cross"][p // WAVE] += e.lane // WAVE < p // WAVE
                         break
                 if prune:
                     continue
@@ -364,7 +441,9 @@ class Search:
                     n.index, n.state, n.f, n.g = key, pro[p].copy(), tmp_f, tmp_g
                     n.input, n.duration, n.parent, n.closed = um[p].copy(), float(tau[p]), cur, False
                     serial += 1
-                    n.serial = serial
+                    n.serial, n.lane = serial, int(p)
+                    if table is not None:
+                        table.insert(n)
                     heap_push(heap, n)
                     expanded[key] = n
                     tmp_expand.append(n)
@@ -376,6 +455,7 @@ class Search:
                         pro_node.state, pro_node.f, pro_node.g = pro[p].copy(), tmp_f, tmp_g
                         pro_node.input, pro_node.duration, pro_node.parent = um[p].copy(), float(tau[p]), cur
                         self.counts["open_g"] += 1
+                        waves["open_g"][p // WAVE] += 1
         return NO_PATH
 
     def retrieve(self, end_node):
@@ -575,13 +655,14 @@ def face_value():
 
 def scenes():
     """every scene of tests/test_kino_path_gpu.py: occupied / unknown blocks, the box where it is not BOX, cfg overrides,
-    problems.  Every problem has a start velocity and a goal offset with three distinct non-zero components."""
+    problems ("over": the scene is over max_samples, the call reports the limit).  Every problem has a start velocity and
+    a goal offset with three distinct non-zero components."""
     far = (1.1, 0.8, 0.4)
     fx = face_value()
     wall = [((38, 41), (3, 50), (3, 27)), ((38, 41), (58, 77), (3, 27))]
     cell = [((14, 16), (16, 30), (5, 20)), ((24, 26), (16, 30), (5, 20)), ((14, 26), (16, 18), (5, 20)),
             ((14, 26), (28, 30), (5, 20)), ((14, 26), (16, 30), (5, 7)), ((14, 26), (16, 30), (18, 20))]
-    return {
+    out = {
         "open": dict(probs=[_prob(far)]),                                      # init 1 x 20, then 125 x 1; REACH_END by shot
         "near_start": dict(probs=[_prob((-1.5, -1.2, 0.2))]),                  # one-node path, start_acc from the shot
         "pillar_start": dict(blocks=[((22, 25), (24, 30), (3, 27))], probs=[_prob((-1.25, -1.1, 0.2))]),  # NO_PATH twice
@@ -598,6 +679,86 @@ def scenes():
         "close_goal": dict(probs=[_prob((-2.0 + 0.008, -1.5 + 0.005, 0.003)), _prob((-2.0 + 0.008, -1.5 + 0.005, 0.0034))]),
         "forced_seg": dict(cfg=dict(seg_num=12), probs=[_prob(far), _prob((-1.5, -1.2, 0.2))]),
     }
+    out.update(edge_scenes(out))
+    return out
+
+
+# the wall map's problem the other way round, from the far side back through the gap: the primitives of the last wave
+# of a four-wave list (the largest x input) then brake, and land in voxels that are open already
+BACK = dict(start=(2.0, -1.5, 0.0), goal=(-1.9, 0.8, 0.5))
+# a box that reaches past the map's low x face: a start in it has negative voxel indices
+BOX_PAST_MAP = ((-4.6, BOX[0][1], BOX[0][2]), BOX[1])
+INIT_LISTS = (1, 63, 64, 65, 255, 256)
+# regular lists by their number of primitives: name -> (primitives, cfg); the wall map unless said otherwise
+REG_LISTS = {
+    "reg1x8": (8, dict(res=2.5, time_res=1 / 8.0)),
+    "reg27x2": (54, dict(res=1.0, time_res=1 / 2.0)),
+    "reg64": (64, dict(res=2 / 3.0)),
+    "reg128": (128, dict(res=2 / 3.0, time_res=1 / 2.0, allocate_num=1024)),
+    "reg216": (216, dict(res=0.4)),
+    "reg216_back": (216, dict(res=0.4)),
+    "reg216_tau": (216, dict(res=0.4, max_tau=0.4, allocate_num=512)),
+    "reg250": (250, dict(time_res=1 / 2.0, allocate_num=1024)),
+    "reg256": (256, dict(res=2 / 3.0, time_res=1 / 4.0, allocate_num=1024)),
+    "reg256_open": (256, dict(res=2 / 3.0, time_res=1 / 4.0)),
+}
+REG216_NODES = 2029   # use_node_num of reg216
+TIGHT = ("tight216", "tight_near_end", "tight16", "tight2", "tight8", "tight9", "retry_short_table")
+REFUSED = ("start_out_of_box", "start_out_of_map", "goal_out_of_map", "goal_past_size", "check1")
+SAMPLING = tuple("%s_%s" % (k, w) for w in ("shot", "noshot")
+                 for k in ("seg1", "seg2", "seg1000_at", "seg1000_over", "minseg_above", "minseg_below", "ts_long"))
+
+
+def edge_scenes(base):
+    """the scenes at the lane, hash and sample-count edges ("What the kinodynamic scenes hold")"""
+    far = (1.1, 0.8, 0.4)
+    wall, book = base["bookkeeping"]["blocks"], base["bookkeeping"]["probs"][0]
+    back = _prob(BACK["goal"], start=BACK["start"])
+    fence = base["near_end"]["blocks"]
+    sc = {}
+    for n in INIT_LISTS:  # the init expansion up to, at and past a wave, and at the workgroup
+        sc["init%d" % n] = dict(blocks=wall, cfg=dict(time_res_init=1.0 / n), probs=[dict(book)])
+    for name, (_, cfg) in REG_LISTS.items():
+        sc[name] = dict(blocks=wall, cfg=dict(cfg), probs=[dict(book)])
+    for name in ("reg216_back", "reg216_tau", "reg250", "reg256"):
+        sc[name]["probs"] = [dict(back)]
+    sc["reg256_open"] = dict(cfg=dict(REG_LISTS["reg256_open"][1]), probs=[_prob(far)])  # three pops: easy to read
+    # the pool runs out in the middle of a later, four-wave expansion / one node later it does not
+    sc["reg216_at"] = dict(blocks=wall, cfg=dict(res=0.4, allocate_num=REG216_NODES), probs=[dict(book)])
+    sc["reg216_over"] = dict(blocks=wall, cfg=dict(res=0.4, allocate_num=REG216_NODES + 1), probs=[dict(book)])
+    # tight tables: 4096 slots for 2029 nodes, 512 for 143, 32 and 16 for a pool that runs out in the init expansion
+    sc["tight216"] = dict(blocks=wall, cfg=dict(res=0.4, allocate_num=2040), probs=[dict(book)])
+    sc["tight_near_end"] = dict(blocks=fence, cfg=dict(allocate_num=200), probs=[_prob(far)])
+    for a in (16, 2, 8, 9):
+        sc["tight%d" % a] = dict(cfg=dict(allocate_num=a), probs=[_prob(far)])
+    # the retry answers, on a table of 128 slots that the first search left with 64 entries: what the workgroup's own
+    # clear of fewer slots than lanes left behind would be found
+    sc["retry_short_table"] = dict(cfg=dict(res=1.0, allocate_num=64, time_res_init=1 / 64.0),
+                                   probs=[_prob((0.1, 2.73, 0.25), start=(2.7, -1.1, 0.3), vel=(0.79, -0.22, 0.12))])
+    # starts and goals the search refuses by itself
+    sc["start_out_of_box"] = dict(probs=[_prob(far, start=(-3.95, -1.5, 0.0), vel=(-0.3, -0.2, 0.1))])
+    sc["start_out_of_map"] = dict(box=BOX_PAST_MAP, probs=[_prob((-1.1, 0.8, 0.4), start=(-4.35, -1.5, 0.0))])
+    sc["goal_out_of_map"] = dict(probs=[_prob((-4.3, -0.7, 0.4))])        # below the origin: no shot passes
+    sc["goal_past_size"] = dict(probs=[_prob((4.3, 0.8, 0.4))])           # (the reference compares with the SIZE)
+    sc["check1"] = dict(blocks=wall, cfg=dict(check_num=1), probs=[dict(book)])
+    # getSamples on a multi-node path with the shot and on one without
+    for w, blocks, p in (("shot", wall, book), ("noshot", fence, _prob(far))):
+        for k, cfg in (("seg1", dict(seg_num=1)), ("seg2", dict(seg_num=2)), ("seg1000_at", dict(seg_num=1000, max_samples=1001)),
+                       ("seg1000_over", dict(seg_num=1000, max_samples=1000)), ("minseg_above", dict(min_seg=40)),
+                       ("minseg_below", dict(min_seg=5)), ("ts_long", dict(ts=1.0))):
+            sc["%s_%s" % (k, w)] = dict(blocks=blocks, cfg=cfg, probs=[dict(p)])
+    for name in ("seg1000_over_shot", "seg1000_over_noshot"):
+        sc[name]["over"] = True  # status -1: the call reports FUELMI_ELIMIT, the counts are still reported
+    return sc
+
+
+# what the reference holds constant: a scene whose cfg sets one of these has no recorded fixture.  The first four are
+# constants of search(), min_seg is the 8 of getSamples.
+NOT_IN_REFERENCE = ("res", "time_res", "time_res_init", "seg_num", "min_seg")
+
+
+def has_fixture(sc):
+    return not any(k in sc.get("cfg", {}) for k in NOT_IN_REFERENCE)
 
 
 def batch65():
@@ -610,10 +771,40 @@ def batch65():
     return [first] + [dict(mid[i % 7]) for i in range(63)] + [dict(first)]
 
 
+# one launch with every outcome, on the wall map: ten distinct problems seven times over and the first two once more (72:
+# more than one problem per workgroup slot).  max_samples = OUTCOME_CFG's: exactly the problems "back" are over it.
+OUTCOME_SCENE, OUTCOME_CFG = "bookkeeping", dict(max_samples=32)
+
+
+def outcome_problems():
+    """(names, the ten problems): REACH_END (four of them, one a one-node path, one over max_samples), NEAR_END,
+    REACH_HORIZON twice (a goal past the horizon, a goal outside the map), NO_PATH after the retry twice (a start inside
+    the inflation: no primitive survives; a start next to a goal across the wall: the first pop ends the search),
+    CLOSE_GOAL (returns before the first barrier)"""
+    named = [("book", _prob((1.9, 0.8, 0.5))), ("back", _prob(BACK["goal"], start=BACK["start"])),
+             ("behind_wall", _prob((0.5, -1.2, 0.5))), ("horizon_far", _prob((2.9, 2.3, 0.6), start=(-3.0, -2.5, 0.0))),
+             ("horizon_out", _prob((4.3, 0.8, 0.4))), ("in_inflation", _prob((1.9, 0.8, 0.5), start=(-0.35, -1.5, 0.0))),
+             ("across_wall", _prob((0.5, -1.27, 0.45), start=(-0.5, -1.2, 0.5))),
+             ("close", _prob((-2.0 + 0.004, -1.5 + 0.003, 0.002))), ("short", _prob((-1.5, -1.2, 0.2))),
+             ("left", _prob((-1.1, 2.8, 0.9)))]
+    return [n for n, _ in named], [p for _, p in named]
+
+
+def outcome_batch():
+    names, probs = outcome_problems()
+    order = [i % 10 for i in range(72)]
+    return [names[i] for i in order], [dict(probs[i]) for i in order]
+
+
 # the problems of the GPU test's device chain (tests/test_kino_path_gpu.py, load_kino) on the near_end scene's map, with
 # seg_num forced to LOAD_SEG: a first load, then a second one whose candidate 1 finds no path (the shot from its start
 # crosses the wall, twice) and whose candidate 3 is refused as a close goal
 LOAD_SCENE, LOAD_CTRL, LOAD_SEG = "near_end", 14, 11
+
+
+# (degree, control points) of the other batches the chain is run for: degrees 4 and 5, and the smallest batch of each
+# degree, one segment and two samples
+LOAD_SIZES = ((4, 15), (5, 16), (3, 4), (4, 5), (5, 6))
 
 
 def load_problems():

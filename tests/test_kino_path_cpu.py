@@ -3,7 +3,10 @@ the new calls: the recorded results of the reference's KinodynamicAstar (tests/g
 tests/golden/make_kino_golden.py) equal the restatement's bit for bit; every scene tests/test_kino_path_gpu.py uses keeps
 its discrete outputs when every libm result is nudged by -4 .. +4 ulp (the largest disagreement of each continuous output
 is printed: the GPU test takes 100 x that as its tolerance); the two heap routines equal std::push_heap / std::pop_heap on
-keys that are changed in place; the scenes hold what they claim; the host refusals and fuelmi_kino_plan."""
+keys that are changed in place; the scenes hold what they claim -- the edge scenes on the restatement's counters (the
+init and regular lists at their wave and workgroup edges, tables that collide and wrap, a pool that runs out in a
+four-wave expansion, starts and goals the search refuses, getSamples at its sample-count edges), fixtures by rule; the host
+refusals and fuelmi_kino_plan."""
 import ctypes as C
 import glob
 import math
@@ -43,8 +46,14 @@ FIXTURES = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "kino", "*.npz
 
 def test_fixtures_cover_the_scenes():
     names = {os.path.basename(f)[:-4] for f in FIXTURES}
-    # forced_seg changes getSamples' rule, which the reference does not have: the restatement stands alone there
-    assert names == set(kr.scenes()) - {"forced_seg"}
+    # by rule: a scene that changes what the reference holds constant -- res, time_res, time_res_init of search(), seg_num
+    # (getSamples has no such argument) and min_seg (a literal 8 in getSamples) -- has no fixture, the restatement
+    # stands alone there; every other scene has one
+    assert kr.NOT_IN_REFERENCE == ("res", "time_res", "time_res_init", "seg_num", "min_seg")
+    sc = kr.scenes()
+    assert names == {n for n in sc if not any(k in sc[n].get("cfg", {}) for k in kr.NOT_IN_REFERENCE)}
+    assert names >= {"tight_near_end", "tight16", "tight2", "tight8", "tight9", "check1", "ts_long_shot", "ts_long_noshot"}
+    assert names >= set(kr.REFUSED) and "forced_seg" not in names and len(names) == 26
     for f in FIXTURES:
         assert os.path.getsize(f) < 64 * 1024
 
@@ -163,6 +172,244 @@ def test_scenes_hold_what_they_claim():
     assert counts["sibling_f"] > 0 and counts["open_g"] > 0 and counts["stale_pop"] > 0
     # map sizes and searches stay small
     assert max(r["iter_num"] for v in res.values() for r in v) <= 300
+
+
+# ---- the edges: lanes and waves, the hash table, the pool, getSamples -----------------------------------------------------
+_counted = {}
+
+
+def _counts(name):
+    """(result, counters) of a scene's first problem, run once more with the counters on"""
+    if name not in _counted:
+        sc = kr.scenes()[name]
+        r = kr.solve(kr.scene_map(sc), sc["probs"][0], sc.get("cfg"), count=True)
+        plain = kr.scene_results(name)[0][0]
+        # the counters and the table model change nothing: the same result bit for bit
+        assert kr.discrete(r) == kr.discrete(plain) and all(v == 0.0 for v in kr.disagreement(r, plain).values()), name
+        _counted[name] = (r, r["counts"])
+    return _counted[name]
+
+
+def test_table_model_is_the_kernels_table():
+    """the hash in 32-bit unsigned arithmetic (negative indices included), the table size against fuelmi_kino_plan, and
+    linear probing with its wrap on a table filled by hand"""
+    import fuel_amd
+    rng = np.random.default_rng(3)
+    keys = np.concatenate([rng.integers(-2000, 2000, (200, 3)), [[-1, -1, -1], [0, 0, 0], [-44, 25, 10], [2 ** 31 - 1, -2 ** 31, 7]]])
+    with np.errstate(over="ignore"):
+        u = keys.astype(np.int64).astype(np.uint32)
+        want = (u[:, 0] * np.uint32(73856093)) ^ (u[:, 1] * np.uint32(19349663)) ^ (u[:, 2] * np.uint32(83492791))
+    assert [kr.voxel_hash(tuple(k)) for k in keys] == [int(v) for v in want]
+    for alloc in (2, 8, 9, 16, 17, 200, 256, 257, 512, 1024, 2029, 2040, 2048, 2049, 4096):
+        assert kr.table_slots(alloc) == fuel_amd.SDFMap.kino_plan(allocate_num=alloc)["hash_slots"], alloc
+    assert [kr.table_slots(a) for a in (2, 8, 9, 16, 200, 2040)] == [16, 16, 32, 32, 512, 4096]
+    # three keys with the last slot as their home: the second wraps to slot 0, the third to slot 1
+    t = kr.TableModel(8)
+    home = [k for k in ((x, y, 0) for x in range(-40, 40) for y in range(-40, 40)) if kr.voxel_hash(k) & 15 == 15][:3]
+    nodes = []
+    for k in home:
+        n = kr.Node()
+        n.index, n.closed = k, len(nodes) == 1
+        nodes.append(n)
+        t.insert(n)
+    assert [t.slot[15], t.slot[0], t.slot[1]] == nodes
+    assert (t.c["displaced"], t.c["longest_probe"], t.c["wraps"]) == (2, 2, 2)
+    assert [t.lookup(k) for k in home] == nodes and t.lookup((1000, 1000, 1000)) in (None,)
+    assert (t.c["found_closed_displaced"], t.c["found_open_displaced"], t.c["lookup_wraps"]) == (1, 1, 2)
+
+
+def test_init_lists_reach_their_wave_edges():
+    book = _counts("bookkeeping")[0]
+    for n in kr.INIT_LISTS:
+        name = "init%d" % n
+        sc = kr.scenes()[name]
+        r, c = _counts(name)
+        w = c["waves"]["init"]
+        print("%s: %d pops, %d nodes, init expansion %s" % (name, r["iter_num"], r["use_node_num"], w))
+        assert len(kr.primitives(dict(kr.DEFAULTS, **sc["cfg"]))[0]) == n
+        assert sc["probs"] == kr.scenes()["bookkeeping"]["probs"] and sc["blocks"] == kr.scenes()["bookkeeping"]["blocks"]
+        assert r["status"] == kr.REACH_END and 353 <= r["use_node_num"] <= 387 and r["n_nodes"] == book["n_nodes"]
+        if n in (64, 65, 256):
+            assert 368 <= r["use_node_num"] <= 387
+        last = (n - 1) // kr.WAVE
+        assert all(v == 0 for v in w["sibling_f"][last + 1:]) and w["open_g"] == [0, 0, 0, 0]
+        assert w["sibling_f_cross"][0] == 0
+        if n > 1:
+            assert w["sibling_f"][last] > 0  # the list's last wave takes part
+        for k in range(1, last + 1):     # and in every wave past the first a sibling's first lane is in an earlier wave
+            assert w["sibling_f_cross"][k] >= 1, (name, k)
+    assert sum(_counts("init256")[1]["waves"]["init"]["sibling_f"]) == 252
+    assert _counts("init1")[1]["waves"]["init"]["sibling_f"] == [0, 0, 0, 0]
+
+
+def test_regular_lists_reach_their_wave_edges():
+    import fuel_amd
+    for name, (n, cfg) in kr.REG_LISTS.items():
+        sc = kr.scenes()[name]
+        assert sc["cfg"] == cfg
+        _, inputs, durs = kr.primitives(dict(kr.DEFAULTS, **cfg))
+        plan_cfg = {k: v for k, v in cfg.items() if k != "allocate_num"}
+        assert len(inputs) * len(durs) == n == fuel_amd.SDFMap.kino_plan(**plan_cfg)["n_regular"], name
+        r, c = _counts(name)
+        w = c["waves"]["reg"]
+        print("%s: status %d, search %d, %d pops, %d nodes, regular expansions %s, tables %s" %
+              (name, r["status"], r["which"], r["iter_num"], r["use_node_num"], w, c["tables"]))
+        last = (n - 1) // kr.WAVE
+        assert all(v == 0 for k in w for v in w[k][last + 1:])
+    assert [len(kr.primitives(dict(kr.DEFAULTS, **kr.REG_LISTS[k][1]))[2]) for k in ("reg1x8", "reg27x2")] == [8, 2]
+    head = lambda name: tuple(_counts(name)[0][k] for k in ("status", "which", "iter_num", "use_node_num"))  # noqa: E731
+    assert head("reg64") == (kr.REACH_END, 0, 70, 523) and head("reg216") == (kr.REACH_END, 0, 117, kr.REG216_NODES)
+    assert head("reg256_open") == (kr.REACH_END, 0, 3, 276)
+    # full pool, deep heap: both searches of these run until the pool of 1024 is used up
+    for name in ("reg128", "reg250", "reg256"):
+        r, c = _counts(name)
+        assert (r["status"], r["which"], r["use_node_num"]) == (kr.NO_PATH, 1, 1024) and r["iter_num"] > 100
+        assert [t["inserts"] for t in c["tables"]] == [1024, 1024]
+    # both order-dependent events occur for primitives in the last wave the list reaches.  With one duration of 0.8 s
+    # and inputs 0.8 m/s^2 apart two primitives of reg216 end 0.256 m apart, never in one voxel: it has no sibling_f at
+    # all, and its last wave (the largest x input) finds no open node with a larger g on the way out.  reg216_back (the
+    # way back: that wave brakes) has the open_g events, reg216_tau (durations of 0.4 s) both kinds.
+    for name in ("reg128", "reg216_tau", "reg250", "reg256"):
+        w = _counts(name)[1]["waves"]["reg"]
+        last = (kr.REG_LISTS[name][0] - 1) // kr.WAVE
+        assert w["sibling_f"][last] > 0 and w["open_g"][last] > 0, (name, w)
+        assert w["sibling_f_cross"][last] > 0, (name, w)
+    assert _counts("reg216_back")[1]["waves"]["reg"]["open_g"][3] > 0
+    assert _counts("reg216")[1]["waves"]["reg"]["sibling_f"] == [0, 0, 0, 0]
+    assert _counts("reg216")[1]["waves"]["reg"]["open_g"][2] > 0
+    w = _counts("reg256_open")[1]["waves"]["reg"]
+    assert all(v > 0 for v in w["sibling_f"]) and w["sibling_f_cross"][3] > 0
+    # the pool runs out in the middle of a later four-wave expansion, and one node later it does not
+    at, over, full = _counts("reg216_at"), _counts("reg216_over")[0], _counts("reg216")[0]
+    assert at[1]["tables"][0]["inserts"] == kr.REG216_NODES and at[0]["which"] == 1
+    assert kr.scenes()["reg216_at"]["cfg"]["allocate_num"] + 1 == kr.scenes()["reg216_over"]["cfg"]["allocate_num"]
+    assert kr.discrete(over) == kr.discrete(full) and over["use_node_num"] == kr.REG216_NODES
+
+
+def test_tight_tables_collide_and_wrap():
+    tab = {}
+    for name in kr.TIGHT:
+        r, c = _counts(name)
+        tab[name] = c["tables"]
+        print("%s: status %d, search %d, %d nodes, tables %s" % (name, r["status"], r["which"], r["use_node_num"], c["tables"]))
+    t, = tab["tight216"]
+    assert (t["slots"], t["inserts"], t["displaced"], t["longest_probe"], t["wraps"]) == (4096, kr.REG216_NODES, 502, 22, 1)
+    assert t["wraps"] >= 1 and t["longest_probe"] >= 8 and t["displaced"] > 0.1 * t["inserts"]
+    assert kr.REG216_NODES < kr.scenes()["tight216"]["cfg"]["allocate_num"] <= 2048
+    t, = tab["tight_near_end"]
+    assert (t["slots"], t["inserts"], t["displaced"], t["longest_probe"]) == (512, 143, 37, 3)
+    assert 144 <= kr.scenes()["tight_near_end"]["cfg"]["allocate_num"] <= 256
+    first, retry = tab["tight16"]
+    assert (retry["slots"], retry["inserts"], retry["displaced"], retry["longest_probe"], retry["wraps"]) == (32, 16, 4, 3, 1)
+    for a, slots in ((2, 16), (8, 16), (9, 32), (16, 32)):  # fewer slots than lanes; the pool runs out in the first expansion
+        r = _counts("tight%d" % a)[0]
+        assert (r["status"], r["which"], r["iter_num"], r["use_node_num"]) == (kr.NO_PATH, 1, 1, a)
+        assert [t["slots"] for t in tab["tight%d" % a]] == [slots, slots] and slots < kr.LANES
+        assert [t["inserts"] for t in tab["tight%d" % a]] == [a, a]
+    # the retry finds a path on a table shorter than the workgroup that the first search had filled to its pool's end
+    r = _counts("retry_short_table")[0]
+    first, retry = tab["retry_short_table"]
+    assert (r["status"], r["which"], r["shot"]) == (kr.REACH_END, 1, 1) and r["n_nodes"] >= 4
+    assert first["slots"] == 128 < kr.LANES and first["inserts"] == 64 and 32 < retry["inserts"] == r["use_node_num"] < 64
+    assert retry["displaced"] >= 4 and retry["longest_probe"] >= 4
+    closed = sum(t["found_closed_displaced"] for v in tab.values() for t in v)
+    opened = sum(t["found_open_displaced"] for v in tab.values() for t in v)
+    print("lookups through a displaced slot in the tight scenes: %d find a closed node, %d an open one" % (closed, opened))
+    assert closed >= 1 and opened >= 1
+    # (what the scenes from before hold, for the record)
+    old = [t for n in ("open", "near_end", "bookkeeping", "alloc_at") for t in _counts(n)[1]["tables"]]
+    print("open, near_end, bookkeeping, alloc_at: longest probe %d, %d wraps" %
+          (max(t["longest_probe"] for t in old), sum(t["wraps"] for t in old)))
+    assert sum(t["wraps"] for t in old) == 0
+
+
+def test_refused_starts_and_goals():
+    res = {n: _counts(n) for n in kr.REFUSED}
+    org_x = -kr.MAP_SIZE[0] / 2.0
+    r, c = res["start_out_of_box"]   # no primitive survives, twice
+    assert (r["status"], r["which"], r["iter_num"], r["use_node_num"]) == (kr.NO_PATH, 1, 1, 1)
+    assert c["tables"][0]["lookups"] == 0  # the init list: every primitive ends outside the box
+    p = kr.scenes()["start_out_of_box"]["probs"][0]
+    assert org_x < p["start"][0] < kr.BOX[0][0]
+    r, c = res["start_out_of_map"]   # negative voxel indices in the table and on the path
+    p = kr.scenes()["start_out_of_map"]
+    assert p["box"][0][0] < p["probs"][0]["start"][0] < org_x
+    assert r["status"] == kr.REACH_END and r["nodes"][0]["index"][0] < 0 <= r["nodes"][1]["index"][0]
+    assert c["tables"][0]["lookups"] > 0 and c["tables"][0]["negative"] > 1  # the start and nodes of the init expansion
+    r, _ = res["goal_out_of_map"]    # below the origin no shot passes
+    assert kr.scenes()["goal_out_of_map"]["probs"][0]["goal"][0] < org_x
+    assert (r["status"], r["shot"]) == (kr.NEAR_END, 0)
+    r, _ = res["goal_past_size"]     # past the far face, below the SIZE: the reference lets the shot pass
+    assert -org_x < kr.scenes()["goal_past_size"]["probs"][0]["goal"][0] < kr.MAP_SIZE[0]
+    assert (r["status"], r["shot"]) == (kr.REACH_END, 1)
+    r, _ = res["check1"]             # only the primitive's end is tested: the path crosses the wall
+    assert r["status"] == kr.REACH_END and r["iter_num"] < _counts("bookkeeping")[0]["iter_num"]
+    sc = kr.scenes()["check1"]
+    km = kr.scene_map(sc)
+    hit = False
+    for a, b in zip(r["nodes"][:-1], r["nodes"][1:]):
+        dt = np.linspace(0.0, b["duration"], 41)
+        hit |= bool(km.inflated(kr.Search.transit(a["state"], np.repeat(b["input"][None, :], 41, axis=0), dt)[:, :3]).any())
+    assert hit
+
+
+def test_get_samples_edges():
+    for w, base in (("shot", "bookkeeping"), ("noshot", "near_end")):
+        full = kr.scene_results(base)[0][0]
+        assert full["shot"] == (w == "shot") and full["n_nodes"] >= 4
+        dur = [n["duration"] for n in full["nodes"]]
+        res = {k: kr.scene_results("%s_%s" % (k, w))[0][0] for k in
+               ("seg1", "seg2", "seg1000_at", "seg1000_over", "minseg_above", "minseg_below", "ts_long")}
+        for k, r in res.items():  # the search is the same; only the sampling differs
+            assert kr.discrete(r)[1:5] == kr.discrete(full)[1:5] and r["T_sum"] == full["T_sum"], (k, w)
+        assert (res["seg1"]["seg_num"], res["seg1"]["n_samples"]) == (1, 2)
+        assert (res["seg2"]["seg_num"], res["seg2"]["n_samples"]) == (2, 3)
+        # one sample spans several path nodes: the step is longer than two whole nodes and the shot, so the time stays
+        # negative after one node's duration is added; with two segments it is longer than the last node and the shot
+        assert res["seg1"]["ts"] == full["T_sum"] > dur[-1] + dur[-2] + full["t_shot"] + 0.5
+        assert res["seg2"]["ts"] > dur[-1] + full["t_shot"] + 0.4
+        at, over = res["seg1000_at"], res["seg1000_over"]
+        assert (at["status"], at["n_samples"]) == (full["status"], 1001) and at["ts"] * 3 < min(dur[1:])  # many samples a node
+        assert (over["status"], over["n_samples"], over["seg_num"]) == (kr.OVER, 1001, 1000)
+        assert np.array_equal(over["samples"], at["samples"])
+        q = math.floor(full["T_sum"] / kr.DEFAULTS["ts"])
+        above, below = res["minseg_above"], res["minseg_below"]
+        assert kr.scenes()["minseg_below_" + w]["cfg"]["min_seg"] < q < kr.scenes()["minseg_above_" + w]["cfg"]["min_seg"]
+        assert above["seg_num"] == 40 and below["seg_num"] == q == full["seg_num"]
+        assert res["ts_long"]["seg_num"] == 8 > math.floor(full["T_sum"] / 1.0)  # the reference's own 8 decides
+        print("getSamples, %s: T_sum %.4f, durations %s, t_shot %.4f, floor(T_sum / ts) %d" % (w, full["T_sum"], dur, full["t_shot"], q))
+
+
+def test_outcome_batch_has_every_outcome():
+    names, probs = kr.outcome_problems()
+    res = kr.problem_results(kr.OUTCOME_SCENE, probs, kr.OUTCOME_CFG)
+    _assert_robust("outcomes", probs, res)
+    st = {n: (r["status"], r["which"]) for n, (r, _, _) in zip(names, res)}
+    print(st)
+    assert st["book"] == st["left"] == st["short"] == (kr.REACH_END, 0) and st["back"] == (kr.OVER, 0)
+    assert st["behind_wall"] == (kr.NEAR_END, 0) and st["horizon_far"] == st["horizon_out"] == (kr.REACH_HORIZON, 0)
+    assert st["in_inflation"] == st["across_wall"] == (kr.NO_PATH, 1) and st["close"] == (kr.CLOSE_GOAL, 0)
+    over = [n for n, (r, _, _) in zip(names, res) if r["n_samples"] > kr.OUTCOME_CFG["max_samples"]]
+    assert over == ["back"] and res[1][0]["shot"] == 1 and res[8][0]["n_nodes"] == 1
+    bn, bp = kr.outcome_batch()
+    assert len(bp) == 72 > 64 and set(bn) == set(names) and bn[64:] == names[4:10] + names[:2]
+
+
+def test_load_sizes_and_layout_calls():
+    """what the GPU test's other chain sizes and its calls of changing layout rely on"""
+    pa, _ = kr.load_problems()
+    assert {n - d for d, n in kr.LOAD_SIZES} == {1, kr.LOAD_SEG} and {d for d, _ in kr.LOAD_SIZES} == {3, 4, 5}
+    for seg in sorted({n - d for d, n in kr.LOAD_SIZES}):
+        res = kr.problem_results(kr.LOAD_SCENE, pa, dict(seg_num=seg))
+        _assert_robust("load, %d segments" % seg, pa, res)
+        assert all(r["n_samples"] == seg + 1 and r["n_nodes"] > 1 for r, _, _ in res)
+    names, probs = kr.outcome_problems()
+    km = kr.scene_map(kr.scenes()[kr.OUTCOME_SCENE])
+    first = [kr.solve(km, p, dict(allocate_num=4096))["status"] for p in probs[:3]]
+    assert set(first) == {kr.REACH_END, kr.NEAR_END}
+    small = [kr.solve(km, p, dict(allocate_num=16)) for p in probs]
+    assert {r["status"] for r in small} <= {kr.NO_PATH, kr.CLOSE_GOAL, kr.REACH_END}
+    assert {r["use_node_num"] for r in small} >= {0, 1, 16}
 
 
 def test_heap_routines_are_libstdcxx(tmp_path):

@@ -4,7 +4,11 @@ search, iter_num, use_node_num, the path's voxels, inputs and durations, shot fl
 output that involves no libm bit for bit (the path's states, T_sum and the samples without a shot).  The device's libm
 is not glibc's: outputs behind cbrt / acos / cos / pow(., 3) are compared within 100 x the largest disagreement between
 the restatement's plain run and its eight runs with every libm result nudged by -4 .. +4 ulp (kino_ref.robustness); the
-CPU test asserts that every scene used here keeps its discrete outputs under those nudges."""
+CPU test asserts that every scene used here keeps its discrete outputs under those nudges, and that the edge scenes reach
+their edges (lists of 1 .. 256 primitives, colliding and wrapping tables, a full pool, refused starts and goals, the
+sample-count edges of getSamples).  Beside the scenes: one launch with every outcome, calls of changing workspace layout
+on one map, the device chain at other degrees and at its smallest batch."""
+import faulthandler
 import os
 import sys
 
@@ -51,6 +55,37 @@ def _close_maps():
     _maps.clear()
 
 
+@pytest.fixture
+def time_limit():
+    """a search that does not return ends the run (with every thread's stack) instead of holding the device"""
+    faulthandler.dump_traceback_later(120, exit=True, file=sys.__stderr__)
+    yield
+    faulthandler.cancel_dump_traceback_later()
+
+
+def _fresh_map(sc):
+    """a device map of a scene that nothing has been called on (the caller closes it)"""
+    import fuel_amd
+    box = sc.get("box", kr.BOX)
+    gm = fuel_amd.SDFMap(kr.MAP_SIZE, box[0], box[1], device=0)
+    gm.uploadOccupancy(kr.occupancy(sc.get("blocks", ()), sc.get("unknown", ())))
+    nv = gm.nvox
+    gm.setLocalBound((0, 0, 0), (nv[0] - 1, nv[1] - 1, nv[2] - 1))
+    gm.clearAndInflateLocalMap()
+    return gm
+
+
+KEYS_I = ("status", "which", "iter_num", "use_node_num", "n_nodes", "shot", "seg_num", "n_samples")
+KEYS_D = ("t_shot", "T_sum", "ts", "coef", "derivs", "samples", "node_state", "node_input", "node_duration")
+
+
+def _assert_same_bits(a, ia, b, ib, where):
+    for k in KEYS_I:
+        assert a[k][ia] == b[k][ib], (where, k, a[k][ia], b[k][ib])
+    for k in KEYS_D:
+        assert _bits(a[k][ia]) == _bits(b[k][ib]), (where, k)
+
+
 def _cfg(sc, **kw):
     c = dict(kr.DEFAULTS)
     c.update(sc.get("cfg", {}))
@@ -85,6 +120,9 @@ def _assert_problem(out, b, r, worst, tag=""):
                samples=out["samples"][b], derivs=out["derivs"][b])
     for k in kr.CONTINUOUS:
         x, y = np.asarray(got[k], dtype=np.float64), np.asarray(r[k], dtype=np.float64)
+        if k == "samples" and r["status"] == kr.OVER and len(y) > len(x):  # over max_samples: the first max_samples are kept
+            assert len(x) == len(y) - 1, (where, len(x), len(y))
+            y = y[:len(x)]
         assert x.shape == y.shape, (where, k, x.shape, y.shape)
         if x.size == 0:
             continue
@@ -95,17 +133,19 @@ def _assert_problem(out, b, r, worst, tag=""):
         else:
             assert err <= tol[k], (where, k, err, tol[k])
     if not r["shot"]:  # g-derived: no libm
-        assert _bits(out["T_sum"][b]) == _bits(r["T_sum"]) and _bits(out["samples"][b]) == _bits(r["samples"]), where
+        n = len(out["samples"][b])
+        assert _bits(out["T_sum"][b]) == _bits(r["T_sum"]) and _bits(out["samples"][b]) == _bits(r["samples"][:n]), where
 
 
 # ---- 1. every scene against the restatement --------------------------------------------------------------------------
 @pytest.mark.parametrize("name", sorted(kr.scenes()))
-def test_scene(name):
+def test_scene(name, time_limit):
     sc = kr.scenes()[name]
     gm = _device_map(sc)
-    out = _run(gm, sc["probs"], _cfg(sc))
+    over = sc.get("over", False)  # a scene over max_samples: the call reports the limit, everything else is compared
+    out = _run(gm, sc["probs"], _cfg(sc), allow_limit=over)
     ref = kr.scene_results(name, sc)
-    assert len(ref) == len(out["status"]) > 0 and not out["limit"]
+    assert len(ref) == len(out["status"]) > 0 and out["limit"] == over
     for b, (r, robust, worst) in enumerate(ref):
         assert robust, (name, b)
         _assert_problem(out, b, r, worst, name)
@@ -196,15 +236,73 @@ def test_batch_invariance():
         assert _bits(again["samples"][b]) == _bits(out["samples"][b]) and again["use_node_num"][b] == out["use_node_num"][b]
 
 
+# ---- 3b. one launch with every outcome; calls of another layout on one map ----------------------------------------------
+def test_outcome_batch(time_limit):
+    """72 problems on the wall map in one launch: REACH_END, NEAR_END, REACH_HORIZON, NO_PATH after the retry, CLOSE_GOAL
+    (its workgroup returns before the first barrier) and one problem over max_samples side by side -- each against the
+    restatement, and bit for bit what the same problem gives alone"""
+    sc = kr.scenes()[kr.OUTCOME_SCENE]
+    gm = _device_map(sc)
+    cfg = _cfg(sc, **kr.OUTCOME_CFG)
+    names, distinct = kr.outcome_problems()
+    ref = dict(zip(names, kr.problem_results(kr.OUTCOME_SCENE, distinct, kr.OUTCOME_CFG)))
+    bn, probs = kr.outcome_batch()
+    assert len(probs) == 72
+    out = _run(gm, probs, cfg, allow_limit=True)
+    assert out["limit"] and {int(v) for v in out["status"]} == {kr.REACH_END, kr.NEAR_END, kr.REACH_HORIZON, kr.NO_PATH,
+                                                                 kr.CLOSE_GOAL, kr.OVER}
+    alone = {n: _run(gm, [p], cfg, allow_limit=True) for n, p in zip(names, distinct)}
+    assert [n for n in names if alone[n]["limit"]] == ["back"]
+    for b, n in enumerate(bn):
+        r, robust, worst = ref[n]
+        assert robust, n
+        _assert_problem(out, b, r, worst, "outcomes/" + n)
+        _assert_same_bits(out, b, alone[n], 0, (n, b))
+
+
+def test_layout_change_between_calls(time_limit):
+    """the workspace is laid out anew per call in the map's pool: a call with 4096 nodes a problem, then 70 problems of 16
+    nodes (their tables lie where node records were), then a 256-primitive list -- each bit for bit the same call on a
+    map nothing else has run on"""
+    sc = kr.scenes()["bookkeeping"]
+    names, distinct = kr.outcome_problems()
+    calls = [(distinct[:3], _cfg(sc, allocate_num=4096)),
+             ([dict(distinct[i % 10]) for i in range(70)], _cfg(sc, allocate_num=16)),
+             (distinct[:2], _cfg(sc, **dict(kr.REG_LISTS["reg256"][1])))]
+    gm = _fresh_map(sc)
+    fresh = []
+    try:
+        seq = [_run(gm, p, c) for p, c in calls]
+        for p, c in calls:
+            fresh.append(_fresh_map(sc))
+            want = _run(fresh[-1], p, c)
+            got = seq[len(fresh) - 1]
+            assert len(got["status"]) == len(p)
+            for b in range(len(p)):
+                _assert_same_bits(got, b, want, b, (len(fresh) - 1, b))
+        # the calls did what they are here for: paths in the first, every pool of 16 used up or unused in the second
+        assert set(seq[0]["status"].tolist()) == {kr.REACH_END, kr.NEAR_END}
+        assert set(seq[1]["status"].tolist()) <= {kr.NO_PATH, kr.CLOSE_GOAL, kr.REACH_END}
+        assert set(seq[1]["use_node_num"].tolist()) >= {0, 1, 16}
+        # and the sequence once more on the same map, in reverse
+        for (p, c), want in list(zip(calls, seq))[::-1]:
+            again = _run(gm, p, c)
+            for b in range(len(p)):
+                _assert_same_bits(again, b, want, b, ("again", b))
+    finally:
+        for m in [gm] + fresh:
+            m.close()
+
+
 # ---- 4. the device chain into the spline fit -----------------------------------------------------------------------------
-def _batch(gm, n_cand, N=14):
+def _batch(gm, n_cand, N=14, degree=3):
     import fuel_amd
     rng = np.random.default_rng(9)
     lo, hi = np.array(kr.BOX[0]), np.array(kr.BOX[1])
     ctrl = lo + 0.5 + (hi - lo - 1.0) * rng.random((n_cand, N, 3))
     x = np.concatenate([ctrl.reshape(n_cand, 3 * N), np.full((n_cand, 1), 0.2)], axis=1)
     cf = fuel_amd.NORMAL_PHASE | fuel_amd.MINTIME
-    opt = fuel_amd.BsplineOptimizer()
+    opt = fuel_amd.BsplineOptimizer() if degree == 3 else fuel_amd.BsplineOptimizer(bspline_degree=degree)
     opt.setEnvironment(gm)
     prob = fuel_amd.BsplineBatchProblem(x, N, cf, np.full(n_cand, 0.3), rng.normal(size=(n_cand, 3, 3)),
                                         rng.normal(size=(n_cand, 3, 3)), 3, 3, 0.2)
@@ -265,6 +363,36 @@ def test_load_kino_equals_load_samples():
         dev.load_kino(*_cols(pa), **dict(load_cfg, seg_num=seg + 1))
     for d in (dev, dev2, dev3, dev4):
         d.close()
+
+
+@pytest.mark.parametrize("degree,N", kr.LOAD_SIZES)
+def test_load_kino_other_sizes(degree, N, time_limit):
+    """degrees 4 and 5, and the smallest batch N = degree + 1 (one segment, two samples): load_kino leaves the state
+    kino_paths + loadSamples leave, and the samples it is compared through are the restatement's"""
+    import fuel_amd
+    sc = kr.scenes()[kr.LOAD_SCENE]
+    gm = _device_map(sc, esdf=True)
+    seg, n_cand = N - degree, 4
+    pa, _ = kr.load_problems()
+    ref = kr.problem_results(kr.LOAD_SCENE, pa, dict(seg_num=seg))
+    assert all(robust for _, robust, _ in ref) and all(r["n_samples"] == seg + 1 for r, _, _ in ref)
+    cfg = _cfg(sc)
+    load_cfg = {k: v for k, v in cfg.items() if k not in ("seg_num", "max_samples", "max_path_nodes")}
+    dev, dev2 = _batch(gm, n_cand, N, degree), _batch(gm, n_cand, N, degree)
+    try:
+        status, t_sum = dev.load_kino(*_cols(pa), **load_cfg)
+        assert status.tolist() == [r["status"] for r, _, _ in ref]
+        host = _run(gm, pa, cfg, seg_num=seg, max_samples=seg + 1)
+        assert host["n_samples"].tolist() == [seg + 1] * n_cand and _bits(host["T_sum"]) == _bits(t_sum)
+        for b, (r, _, worst) in enumerate(ref):
+            _assert_problem(host, b, r, worst, "load, degree %d, N %d" % (degree, N))
+        dev2.loadSamples(host["ts"], np.array(host["samples"]), host["derivs"])
+        assert _state(dev, max_eval=8) == _state(dev2, max_eval=8)
+        with pytest.raises(fuel_amd.FuelmiError):  # a seg_num the batch cannot hold
+            dev.load_kino(*_cols(pa), **dict(load_cfg, seg_num=seg + 1))
+    finally:
+        dev.close()
+        dev2.close()
 
 
 # ---- 5. the facade: a MID problem out of planPathToViewpoint takes planKinodynamic -----------------------------------------
