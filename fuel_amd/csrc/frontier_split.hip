@@ -27,7 +27,11 @@
 // FLOAT accumulation, over the member cells in ascending voxel address (k_sp_centroid) -- the
 // reference feeds PCL the cells in BFS order, so its last float bit can differ; see DESIGN.md.  The
 // principal direction uses the closed-form symmetric 2x2 decomposition with the sign convention of
-// the oracle (Eigen::EigenSolver is third-party; its sign is unpinned).
+// the oracle (Eigen::EigenSolver is third-party; its sign is unpinned): v = normalise(b,
+// lambda - a) where that is well conditioned.  Where b is rounding residue next to |a - d| (a straight
+// frontier along x or y) or b and a - d both are next to the trace (a square), both components of that
+// expression are residue of the order in which k_sp_stats' f64 atomics arrived; there the direction is
+// the exact axis: (1, 0) for a > d and for the isotropic case, (0, 1) for a < d (kPcSnapTau).
 #include <cmath>
 #include <cstdlib>
 
@@ -36,6 +40,11 @@
 namespace {
 
 enum : u32 { N_ACTIVE = 0, N_SPLIT = 1, N_FINAL = 2, N_DEAD = 3 };
+
+// |b| <= tau * |a - d|, or |a - d| and |b| <= tau * trace: the principal direction is snapped to its axis (k_sp_decide).
+// The geometric mean of the largest ratio that is rounding residue on axis-aligned clusters (1.03e-7) and the smallest
+// ratio of a split node of an explored world (1.03e-3); the oracle and compat/Eigen/Eigenvalues carry the same number.
+constexpr double kPcSnapTau = 1.03e-5;
 
 struct SNode {
   u32 orig;    // rank of the region-grown cluster this piece comes from
@@ -391,20 +400,28 @@ __global__ void __launch_bounds__(256) k_sp_decide(SArgs S, u32 level, u32 n_nod
   const double nf = (double)N.nfilt;
   const double c00 = N.cov[0] / nf, c01 = N.cov[1] / nf, c10 = N.cov[2] / nf, c11 = N.cov[3] / nf;
   const double a = c00, b = 0.5 * (c01 + c10), d = c11;
-  const double tr = a + d, det = a * d - b * b, disc = sqrt(fmax(tr * tr / 4 - det, 0.0));
-  const double l = tr / 2 + disc;
-  double vx = b, vy = l - a;
-  if (fabs(vx) + fabs(vy) < 1e-300) {
-    vx = l - d;
-    vy = b;
+  const double tr = a + d, gap = fabs(a - d), ab = fabs(b);
+  const bool iso = gap <= kPcSnapTau * tr && ab <= kPcSnapTau * tr;
+  if (iso || ab <= kPcSnapTau * gap) {  // b (or b and a - d) is rounding residue of the atomics' order: exact axis
+    const bool along_y = !iso && a < d;
+    N.pc[0] = along_y ? 0.0 : 1.0;
+    N.pc[1] = along_y ? 1.0 : 0.0;
+  } else {
+    const double det = a * d - b * b, disc = sqrt(fmax(tr * tr / 4 - det, 0.0));
+    const double l = tr / 2 + disc;
+    double vx = b, vy = l - a;
+    if (fabs(vx) + fabs(vy) < 1e-300) {
+      vx = l - d;
+      vy = b;
+    }
+    if (fabs(vx) + fabs(vy) < 1e-300) {
+      vx = 1;
+      vy = 0;
+    }
+    const double nn = sqrt(vx * vx + vy * vy);
+    N.pc[0] = vx / nn;
+    N.pc[1] = vy / nn;
   }
-  if (fabs(vx) + fabs(vy) < 1e-300) {
-    vx = 1;
-    vy = 0;
-  }
-  const double nn = sqrt(vx * vx + vy * vy);
-  N.pc[0] = vx / nn;
-  N.pc[1] = vy / nn;
   const u32 c0 = atomicAdd(&S.ctr[0], 2u);
   if (c0 + 2u > S.cap_nodes) {
     S.ctr[3] = 1u;

@@ -683,6 +683,12 @@ struct fo_frontier {
   int split = 0;
   int canonical_order = 0;
   int flip_pc = 0;
+  // split trace (fo_frontier_split_trace): FO_TRACE_REC doubles per splitHorizontally call in recursion order, and
+  // the (dx, dy) of every down-sampled cell of the nodes that split, in the order the covariance sums them.
+  // Written from the const split recursion (hence mutable): a finder that is being traced is not re-entrant --
+  // one search at a time, and the trace is read or switched only between searches.
+  mutable bool trace_on = false;
+  mutable std::vector<double> trace_rec, trace_terms;
   fo_viewpoint_cfg vp{};
   // PerceptionUtils state (perception_utils.cpp:6-19 constructor, :49-69 setPose)
   V3d pu_pos;
@@ -859,9 +865,24 @@ struct fo_frontier {
   // in the reference (Eigen: third-party, absent); restated as the closed-form symmetric 2x2
   // decomposition with the convention v = normalise(b, lambda_max - a) (fallbacks for b == 0) -- the
   // SIGN of the eigenvector decides which half is emitted first and is UNPINNED against Eigen.
+  //
+  // Axis-aligned and isotropic clusters: where b is rounding residue next to |a - d| (a straight frontier along
+  // x or y), or where b and a - d both are next to the trace (a square), both components of that expression
+  // are residue too -- a random unit vector that changes with the summation order of the covariance.  Inside
+  // these zones the direction is the exact axis instead: (1, 0) for a > d and for the isotropic case, (0, 1)
+  // for a < d.  Outside them the expression is untouched.  PC_SNAP_TAU and its two bounds: DESIGN.md.
+  static constexpr double PC_SNAP_TAU = 1.03e-5;
   static void principal_dir(double c00, double c01, double c10, double c11, double pc[2]) {
     const double a = c00, b = 0.5 * (c01 + c10), d = c11;
-    const double tr = a + d, det = a * d - b * b, disc = std::sqrt(std::fmax(tr * tr / 4 - det, 0.0));
+    const double tr = a + d, gap = std::fabs(a - d), ab = std::fabs(b);
+    const bool iso = gap <= PC_SNAP_TAU * tr && ab <= PC_SNAP_TAU * tr;
+    if (iso || ab <= PC_SNAP_TAU * gap) {
+      const bool along_y = !iso && a < d;
+      pc[0] = along_y ? 0.0 : 1.0;
+      pc[1] = along_y ? 1.0 : 0.0;
+      return;
+    }
+    const double det = a * d - b * b, disc = std::sqrt(std::fmax(tr * tr / 4 - det, 0.0));
     const double l = tr / 2 + disc;
     double vx = b, vy = l - a;
     if (std::fabs(vx) + std::fabs(vy) < 1e-300) {
@@ -876,8 +897,16 @@ struct fo_frontier {
     pc[0] = vx / n;
     pc[1] = vy / n;
   }
-  bool splitHorizontally(const Cluster& ftr, std::list<Cluster>& splits) const {
+  bool splitHorizontally(const Cluster& ftr, std::list<Cluster>& splits, int depth = 0) const {
     const double mean[2] = {ftr.average[0], ftr.average[1]};
+    size_t rec = 0;
+    if (trace_on) {
+      rec = trace_rec.size();
+      trace_rec.resize(rec + FO_TRACE_REC, 0.0);
+      double* r = &trace_rec[rec];
+      r[0] = double(ftr.cells.size()), r[1] = mean[0], r[2] = mean[1], r[3] = double(ftr.filtered.size());
+      r[12] = depth;
+    }
     bool need_split = false;
     for (auto& cell : ftr.filtered) {
       const double dx = cell[0] - mean[0], dy = cell[1] - mean[1];
@@ -907,6 +936,25 @@ struct fo_frontier {
       else
         f2.cells.push_back(cell);
     }
+    if (trace_on) {
+      double* r = &trace_rec[rec];
+      r[4] = 1.0;
+      r[9] = pc[0], r[10] = pc[1];
+      double lo = HUGE_VAL;
+      for (auto& cell : ftr.cells)
+        lo = std::fmin(lo, std::fabs((cell[0] - mean[0]) * pc[0] + (cell[1] - mean[1]) * pc[1]));
+      r[11] = lo;
+      r[13] = double(trace_terms.size() / 2);
+      r[14] = double(f1.cells.size()), r[15] = double(f2.cells.size());
+      double s[4] = {0, 0, 0, 0};
+      for (auto& cell : ftr.filtered) {
+        const double dx = cell[0] - mean[0], dy = cell[1] - mean[1];
+        trace_terms.push_back(dx);
+        trace_terms.push_back(dy);
+        s[0] += dx * dx, s[1] += dx * dy, s[2] += dy * dx, s[3] += dy * dy;
+      }
+      for (int k = 0; k < 4; ++k) r[5 + k] = s[k];
+    }
     // (the reference would dereference cells_.front() of an empty half: cannot happen for a cluster
     // whose cells straddle their own mean along pc, which need_split implies)
     Cluster* halves[2] = {&f1, &f2};
@@ -914,7 +962,7 @@ struct fo_frontier {
       if (h->cells.empty()) continue;
       computeInfo(*h);
       std::list<Cluster> sub;
-      if (splitHorizontally(*h, sub))
+      if (splitHorizontally(*h, sub, depth + 1))
         splits.insert(splits.end(), sub.begin(), sub.end());
       else
         splits.push_back(*h);
@@ -1121,6 +1169,35 @@ void fo_frontier_cluster_filtered(const fo_frontier* f, int which, int k, double
   const Cluster& c = nth(pick(f, which), k);
   for (size_t i = 0; i < c.filtered.size(); ++i)
     for (int q = 0; q < 3; ++q) xyz[3 * i + q] = c.filtered[i][q];
+}
+int fo_frontier_split_trace(fo_frontier* f, int op, double* io, int cap) {
+  switch (op) {
+    case FO_TRACE_OFF:
+    case FO_TRACE_ON:
+      f->trace_on = op == FO_TRACE_ON;
+      f->trace_rec.clear();
+      f->trace_terms.clear();
+      return 0;
+    case FO_TRACE_COUNT:
+      return (int)(f->trace_rec.size() / FO_TRACE_REC);
+    case FO_TRACE_READ: {
+      const int n = std::min((int)f->trace_rec.size(), cap);
+      std::copy(f->trace_rec.begin(), f->trace_rec.begin() + n, io);
+      return n / FO_TRACE_REC;
+    }
+    case FO_TRACE_TERM_COUNT:
+      return (int)(f->trace_terms.size() / 2);
+    case FO_TRACE_TERMS: {
+      const int n = std::min((int)f->trace_terms.size(), cap);
+      std::copy(f->trace_terms.begin(), f->trace_terms.begin() + n, io);
+      return n / 2;
+    }
+    case FO_TRACE_DIR:  // io[0..3] = c00, c01, c10, c11 (already divided by nf) -> io[4..5]; f may be null
+      if (cap < 6) return -1;
+      fo_frontier::principal_dir(io[0], io[1], io[2], io[3], io + 4);
+      return 0;
+  }
+  return -1;
 }
 int fo_frontier_removed_count(const fo_frontier* f) { return (int)f->removed_ids.size(); }
 void fo_frontier_removed_ids(const fo_frontier* f, int* ids) {

@@ -156,6 +156,24 @@ int fo_frontier_cluster_size(const fo_frontier* f, int which, int k);
 void fo_frontier_cluster_cells(const fo_frontier* f, int which, int k, int* adr);
 /* average_, box_min_, box_max_ (computeFrontierInfo) -> out[9] */
 void fo_frontier_cluster_info(const fo_frontier* f, int which, int k, double* out9);
+/* Split trace: off by default, changes no result.  One entry point, selected by op:
+     FO_TRACE_ON / FO_TRACE_OFF  start (and clear) / stop recording; the next search fills the trace
+     FO_TRACE_COUNT              number of records
+     FO_TRACE_READ               copies up to cap doubles of records into io, returns the records copied
+     FO_TRACE_TERM_COUNT / FO_TRACE_TERMS  the same for the covariance terms, (dx, dy) pairs
+     FO_TRACE_DIR                splitHorizontally's principal direction as a callable: io[0..3] = the covariance
+                                 c00, c01, c10, c11 -> io[4..5]; f may be NULL, cap >= 6
+   One record of FO_TRACE_REC doubles per splitHorizontally call (every node of the recursion, depth first, the
+   "dot >= 0" half first):
+     [0] cells  [1..2] mean xy  [3] nf (down-sampled cells)  [4] 1 if the node was split, else 0  [12] depth
+   and for the nodes that were split:
+     [5..8] sums of dx*dx, dx*dy, dy*dx, dy*dy over the down-sampled cells (divide by nf for the covariance)
+     [9..10] the direction used (after flip_principal_dir)  [11] smallest |dot| over the node's cells
+     [13] index of the node's first (dx, dy) pair among the terms; it owns nf of them, in summation order
+     [14..15] cells of the "dot >= 0" half and of the other half */
+enum { FO_TRACE_OFF = 0, FO_TRACE_ON = 1, FO_TRACE_COUNT = 2, FO_TRACE_READ = 3, FO_TRACE_TERM_COUNT = 4,
+       FO_TRACE_TERMS = 5, FO_TRACE_DIR = 6, FO_TRACE_REC = 16 };
+int fo_frontier_split_trace(fo_frontier* f, int op, double* io, int cap);
 int fo_frontier_removed_count(const fo_frontier* f);
 void fo_frontier_removed_ids(const fo_frontier* f, int* ids);
 

@@ -400,12 +400,49 @@ class OracleFrontier:
             self.L.fo_frontier_cluster_filtered(self.h, which, k, _dp(o))
         return o
 
+    def trace_splits(self, on=True):
+        """start (and clear) or stop the split trace; the next search() fills it.  Changes no result."""
+        _split_trace(self.L)(self.h, TRACE_ON if on else TRACE_OFF, None, 0)
+
+    def split_trace(self):
+        """(records [n, TRACE_REC], terms [m, 2]) of the last traced search: one record per splitHorizontally call in
+        recursion order (TRACE_FIELDS names the columns), and the (dx, dy) of the down-sampled cells of every node that
+        split, in the order its covariance sums them (record columns term0 / nf locate a node's own)."""
+        fn = _split_trace(self.L)
+        rec = np.zeros((fn(self.h, TRACE_COUNT, None, 0), TRACE_REC))
+        terms = np.zeros((fn(self.h, TRACE_TERM_COUNT, None, 0), 2))
+        if rec.size:
+            fn(self.h, TRACE_READ, _dp(rec), rec.size)
+        if terms.size:
+            fn(self.h, TRACE_TERMS, _dp(terms), terms.size)
+        return rec, terms
+
     def removed_ids(self):
         n = self.L.fo_frontier_removed_count(self.h)
         a = np.empty(n, dtype=np.int32)
         if n:
             self.L.fo_frontier_removed_ids(self.h, _ip(a))
         return a
+
+
+# fo_frontier_split_trace's ops and record width (oracle/fuel_oracle.h)
+TRACE_OFF, TRACE_ON, TRACE_COUNT, TRACE_READ, TRACE_TERM_COUNT, TRACE_TERMS, TRACE_DIR, TRACE_REC = 0, 1, 2, 3, 4, 5, 6, 16
+TRACE_FIELDS = dict(cells=0, mean_x=1, mean_y=2, nf=3, split=4, sxx=5, sxy=6, syx=7, syy=8, pc_x=9, pc_y=10,
+                    min_abs_dot=11, depth=12, term0=13, n_pos=14, n_neg=15)
+
+
+def _split_trace(L):
+    L.fo_frontier_split_trace.restype = C.c_int
+    L.fo_frontier_split_trace.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_int]
+    return L.fo_frontier_split_trace
+
+
+def principal_dir(c00, c01, c10, c11):
+    """splitHorizontally's first principal direction of the covariance [[c00, c01], [c10, c11]]: (x, y) floats"""
+    io = np.array([c00, c01, c10, c11, 0.0, 0.0])
+    if _split_trace(lib())(None, TRACE_DIR, _dp(io), 6):
+        raise ValueError("principal_dir")
+    return float(io[4]), float(io[5])
 
 
 COST = dict(SMOOTHNESS=1, DISTANCE=2, FEASIBILITY=4, START=8, END=16, GUIDE=32, WAYPOINTS=64,

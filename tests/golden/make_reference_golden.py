@@ -8,7 +8,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-MODULES = ("test_oracle_vs_reference_cpu.py", "test_fusion_edges_cpu.py")
+MODULES = ("test_oracle_vs_reference_cpu.py", "test_fusion_edges_cpu.py", "test_frontier_split_cpu.py")
 
 
 def main():
