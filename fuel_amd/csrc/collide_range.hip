@@ -332,40 +332,6 @@ int colrange_cfg_check(const fuelmi_colrange_cfg* cfg) {
   return FUELMI_OK;
 }
 
-// the result block's layout (base null: only its size)
-size_t colrange_out_bytes(const fuelmi_colrange_cfg& cfg, int n_prob, ColRangeArgs& T, unsigned char* base) {
-  const size_t n = (size_t)n_prob, ev = (size_t)cfg.max_events, mp = (size_t)cfg.max_pts;
-  BlockLayout L(base, 16);
-  T.status = L.take<int>(n);
-  T.n_ticks = L.take<int>(n);
-  T.n_start_events = L.take<int>(n);
-  T.n_end_events = L.take<int>(n);
-  T.n_start_pts = L.take<int>(n);
-  T.n_end_pts = L.take<int>(n);
-  T.t_s = L.take<double>(n);
-  T.t_e = L.take<double>(n);
-  T.colli_start = L.take<double>(n * ev * 3);
-  T.colli_end = L.take<double>(n * ev * 3);
-  T.start_pts = L.take<double>(n * mp * 3);
-  T.end_pts = L.take<double>(n * mp * 3);
-  T.first_start = L.take<double>(n * 3);
-  T.last_end = L.take<double>(n * 3);
-  return L.size();
-}
-
-size_t guide_out_bytes(int n_path, int max_guide, GuideArgs& G, unsigned char* base) {
-  const size_t n = (size_t)n_path;
-  BlockLayout L(base, 16);
-  G.status = L.take<int>(n);
-  G.seg_num = L.take<int>(n);
-  G.n_pts = L.take<int>(n);
-  G.n_ctrl = L.take<int>(n);
-  G.n_guide = L.take<int>(n);
-  G.dt = L.take<double>(n);
-  G.guide_pts = L.take<double>(n * (size_t)max_guide * 3);
-  return L.size();
-}
-
 }  // namespace
 
 extern "C" int fuelmi_colrange_plan(const fuelmi_colrange_cfg* cfg, int out6[6]) {
@@ -406,25 +372,37 @@ extern "C" int fuelmi_map_collision_ranges(fuelmi_map* m, const fuelmi_colrange_
   const size_t n = (size_t)n_prob, ev = (size_t)cfg->max_events, mp = (size_t)cfg->max_pts;
   ColRangeArgs T;
   memset(&T, 0, sizeof(T));
-  const size_t b_out = colrange_out_bytes(*cfg, n_prob, T, nullptr);
-  unsigned char* d_out;
+  ResultBlock R(16);
+  R.add(T.status, status, n);
+  R.add(T.n_ticks, n_ticks, n);
+  R.add(T.n_start_events, n_start_events, n);
+  R.add(T.n_end_events, n_end_events, n);
+  R.add(T.n_start_pts, n_start_pts, n);
+  R.add(T.n_end_pts, n_end_pts, n);
+  R.add(T.t_s, t_s, n);
+  R.add(T.t_e, t_e, n);
+  R.add(T.colli_start, colli_start, n * ev * 3);
+  R.add(T.colli_end, colli_end, n * ev * 3);
+  R.add(T.start_pts, start_pts, n * mp * 3);
+  R.add(T.end_pts, end_pts, n * mp * 3);
+  R.add(T.first_start, first_start, n * 3);
+  R.add(T.last_end, last_end, n * 3);
+  ARGCHK(!R.overflow);
   auto layout = [&](unsigned char* base) {
     BlockLayout L(base, 16);
     spline_src_take(L, n, cfg->max_ctrl, T.src);
-    d_out = L.take<unsigned char>(b_out);
+    R.place(L);
     return L.size();
   };
   {
-    const int rc = m->colrange_dev.reserve(st, layout(nullptr));
+    const int rc = m->colrange_dev.carve(st, layout);
     if (rc) return rc;
   }
-  layout(m->colrange_dev.base());
   {
     const int rc = spline_src_upload(st, T.src, n, cfg->max_ctrl, n_ctrl, pos_ctrl, knot_span);
     if (rc) return rc;
   }
-  HIPCHK(hipMemsetAsync(d_out, 0, b_out, st));
-  colrange_out_bytes(*cfg, n_prob, T, d_out);
+  HIPCHK(hipMemsetAsync(R.base, 0, R.size(), st));
   T.cfg = *cfg;
   T.n_prob = n_prob;
   T.cut = field_cut(m->g.res, cfg->clearance, true);
@@ -432,32 +410,15 @@ extern "C" int fuelmi_map_collision_ranges(fuelmi_map* m, const fuelmi_colrange_
   hipLaunchKernelGGL(k_collide_range, dim3((n_prob + CR_WAVES - 1) / CR_WAVES), dim3(CR_WIN * CR_WAVES),
                      cr_lds(cfg->max_ctrl), st, m->g, T);
   HIPCHK(hipGetLastError());
-  std::vector<unsigned char> host(b_out);
-  HIPCHK(hipMemcpyAsync(host.data(), d_out, b_out, hipMemcpyDeviceToHost, st));
-  HIPCHK(stream_wait(st));
-  ColRangeArgs H = T;
-  colrange_out_bytes(*cfg, n_prob, H, host.data());
-  memcpy(status, H.status, n * sizeof(int));
-  memcpy(n_ticks, H.n_ticks, n * sizeof(int));
-  memcpy(n_start_events, H.n_start_events, n * sizeof(int));
-  memcpy(n_end_events, H.n_end_events, n * sizeof(int));
-  memcpy(n_start_pts, H.n_start_pts, n * sizeof(int));
-  memcpy(n_end_pts, H.n_end_pts, n * sizeof(int));
-  memcpy(t_s, H.t_s, n * sizeof(double));
-  memcpy(t_e, H.t_e, n * sizeof(double));
-  memcpy(colli_start, H.colli_start, n * ev * 3 * sizeof(double));
-  memcpy(colli_end, H.colli_end, n * ev * 3 * sizeof(double));
-  memcpy(start_pts, H.start_pts, n * mp * 3 * sizeof(double));
-  memcpy(end_pts, H.end_pts, n * mp * 3 * sizeof(double));
-  memcpy(first_start, H.first_start, n * 3 * sizeof(double));
-  memcpy(last_end, H.last_end, n * 3 * sizeof(double));
-  for (int b = 0; b < n_prob; ++b)
-    if (status[b] == -1) {
-      fuelmi_set_error("collision ranges: problem %d is over max_events = %d / max_pts = %d or %d ticks", b,
-                       cfg->max_events, cfg->max_pts, CR_CAP);
-      return FUELMI_ELIMIT;
-    }
-  return FUELMI_OK;
+  {
+    const int rc = result_fetch(R, st);
+    if (rc) return rc;
+  }
+  const int b = first_over_limit(status, n_prob);
+  if (b < 0) return FUELMI_OK;
+  fuelmi_set_error("collision ranges: problem %d is over max_events = %d / max_pts = %d or %d ticks", b,
+                   cfg->max_events, cfg->max_pts, CR_CAP);
+  return FUELMI_ELIMIT;
 }
 
 extern "C" int fuelmi_map_guide_points(fuelmi_map* m, int n_path, int max_path_points, const double* paths,
@@ -485,49 +446,44 @@ extern "C" int fuelmi_map_guide_points(fuelmi_map* m, int n_path, int max_path_p
   const size_t n = (size_t)n_path, mpp = (size_t)max_path_points;
   GuideArgs G;
   memset(&G, 0, sizeof(G));
-  const size_t b_out = guide_out_bytes(n_path, max_guide, G, nullptr);
+  ResultBlock R(16);
+  R.add(G.status, status, n);
+  R.add(G.seg_num, seg_num, n);
+  R.add(G.n_pts, n_pts, n);
+  R.add(G.n_ctrl, n_ctrl, n);
+  R.add(G.n_guide, n_guide, n);
+  R.add(G.dt, dt, n);
+  R.add(G.guide_pts, guide_pts, n * (size_t)max_guide * 3);
+  ARGCHK(!R.overflow);
   double *d_paths, *d_dur;
   int* d_len;
-  unsigned char* d_out;
   auto layout = [&](unsigned char* base) {
     BlockLayout L(base, 16);
     d_paths = L.take<double>(n * mpp * 3);
     d_dur = L.take<double>(n);
     d_len = L.take<int>(n);
-    d_out = L.take<unsigned char>(b_out);
+    R.place(L);
     return L.size();
   };
   {
-    const int rc = m->colrange_dev.reserve(st, layout(nullptr));
+    const int rc = m->colrange_dev.carve(st, layout);
     if (rc) return rc;
   }
-  layout(m->colrange_dev.base());
   HIPCHK(hipMemcpyAsync(d_paths, paths, n * mpp * 3 * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_dur, duration, n * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_len, path_len, n * sizeof(int), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(d_out, 0, b_out, st));
-  guide_out_bytes(n_path, max_guide, G, d_out);
+  HIPCHK(hipMemsetAsync(R.base, 0, R.size(), st));
   G.n_path = n_path, G.max_path_points = max_path_points, G.degree = degree, G.max_guide = max_guide;
   G.ctrl_pt_dist = ctrl_pt_dist;
   G.paths = d_paths, G.path_len = d_len, G.duration = d_dur;
   hipLaunchKernelGGL(k_guide_points, dim3(n_path), dim3(GP_NT), 0, st, G);
   HIPCHK(hipGetLastError());
-  std::vector<unsigned char> host(b_out);
-  HIPCHK(hipMemcpyAsync(host.data(), d_out, b_out, hipMemcpyDeviceToHost, st));
-  HIPCHK(stream_wait(st));
-  GuideArgs H = G;
-  guide_out_bytes(n_path, max_guide, H, host.data());
-  memcpy(status, H.status, n * sizeof(int));
-  memcpy(seg_num, H.seg_num, n * sizeof(int));
-  memcpy(n_pts, H.n_pts, n * sizeof(int));
-  memcpy(n_ctrl, H.n_ctrl, n * sizeof(int));
-  memcpy(n_guide, H.n_guide, n * sizeof(int));
-  memcpy(dt, H.dt, n * sizeof(double));
-  memcpy(guide_pts, H.guide_pts, n * (size_t)max_guide * 3 * sizeof(double));
-  for (int b = 0; b < n_path; ++b)
-    if (status[b] == -1) {
-      fuelmi_set_error("guide points: path %d is over max_guide = %d or %d points", b, max_guide, FUELMI_GUIDE_MAX_PTS);
-      return FUELMI_ELIMIT;
-    }
-  return FUELMI_OK;
+  {
+    const int rc = result_fetch(R, st);
+    if (rc) return rc;
+  }
+  const int b = first_over_limit(status, n_path);
+  if (b < 0) return FUELMI_OK;
+  fuelmi_set_error("guide points: path %d is over max_guide = %d or %d points", b, max_guide, FUELMI_GUIDE_MAX_PTS);
+  return FUELMI_ELIMIT;
 }

@@ -41,7 +41,7 @@ void fuelmi_set_error(const char* fmt, ...);
     }                                                                       \
   } while (0)
 
-#include "scratch.h"  // DevScratch, BlockLayout
+#include "scratch.h"  // DevScratch, BlockLayout, ResultBlock
 
 // ---- grid geometry passed to kernels by value -------------------------------------------------
 struct Geo {
@@ -303,6 +303,15 @@ static inline hipError_t stream_wait(hipStream_t s) {
     if (yld) std::this_thread::yield();
   }
   return hipStreamSynchronize(s);
+}
+// a batched call's results (block_layout.h), bound on the device, behind the work queued on st: the block in one copy into a
+// staging buffer, the wait, then every array into the caller's
+static inline int result_fetch(const ResultBlock& R, hipStream_t st) {
+  std::vector<unsigned char> host(R.size());
+  HIPCHK(hipMemcpyAsync(host.data(), R.base, R.size(), hipMemcpyDeviceToHost, st));
+  HIPCHK(stream_wait(st));
+  R.scatter(host.data());
+  return FUELMI_OK;
 }
 // poll a stream / an event until its work is done, never blocking (work that has usually finished when anybody asks)
 static inline hipError_t stream_poll(hipStream_t s) {

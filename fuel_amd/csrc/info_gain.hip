@@ -427,21 +427,16 @@ int heading_run(fuelmi_map* m, const fuelmi_gain_cfg& gc, const std::vector<Gain
   GainView* d_views;
   int *d_nctrl, *d_nlayer, *d_over;
   double *d_ctrl, *d_yaws, *d_dt;
-  unsigned char* d_out;
-  size_t b_out = 0;
-  auto out_layout = [&](GainArgs& A, YawPathArgs& Y, unsigned char* base) {
-    BlockLayout L(base, 16);
-    A.gain = L.take<double>(ng * my);
-    A.n_cand = L.take<int>(ng * my);
-    A.n_visible = L.take<int>(ng * my);
-    A.n_rays = L.take<int>(ng);
-    Y.status = L.take<int>(n);
-    Y.path = L.take<double>(n * ml);
-    Y.path_vertex = L.take<int>(n * ml);
-    Y.g_value = L.take<double>(n * ml * my);
-    return L.size();
-  };
-  b_out = out_layout(A, Y, nullptr);
+  ResultBlock R(16);  // n_cand / n_visible are always in the block and copied where the caller asks; no search: n = 0
+  R.add(A.gain, gain, ng * my);
+  R.add(A.n_cand, n_cand, ng * my);
+  R.add(A.n_visible, n_visible, ng * my);
+  R.add(A.n_rays, n_rays, ng);
+  R.add(Y.status, yp ? yp->status : nullptr, n);
+  R.add(Y.path, yp ? yp->path : nullptr, n * ml);
+  R.add(Y.path_vertex, yp ? yp->path_vertex : nullptr, n * ml);
+  R.add(Y.g_value, yp ? yp->g_value : nullptr, n * ml * my);
+  ARGCHK(!R.overflow);
   auto layout = [&](unsigned char* base) {
     BlockLayout L(base, 16);
     d_groups = L.take<GainGroup>(ng);
@@ -452,16 +447,14 @@ int heading_run(fuelmi_map* m, const fuelmi_gain_cfg& gc, const std::vector<Gain
     d_over = L.take<int>(n);
     d_yaws = L.take<double>(n * ml);
     d_dt = L.take<double>(n);
-    d_out = L.take<unsigned char>(b_out);
+    R.place(L);
     return L.size();
   };
   {
-    const int rc = m->heading_dev.reserve(st, layout(nullptr));
+    const int rc = m->heading_dev.carve(st, layout);
     if (rc) return rc;
   }
-  layout(m->heading_dev.base());
-  out_layout(A, Y, d_out);
-  HIPCHK(hipMemsetAsync(d_out, 0, b_out, st));
+  HIPCHK(hipMemsetAsync(R.base, 0, R.size(), st));
   if (walk) {
     HIPCHK(hipMemcpyAsync(d_groups, groups.data(), ng * sizeof(GainGroup), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_views, views.data(), ng * my * sizeof(GainView), hipMemcpyHostToDevice, st));
@@ -502,23 +495,7 @@ int heading_run(fuelmi_map* m, const fuelmi_gain_cfg& gc, const std::vector<Gain
     hipLaunchKernelGGL(k_yaw_path, dim3((unsigned)n), dim3(YP_NT), 0, st, Y);
     HIPCHK(hipGetLastError());
   }
-  std::vector<unsigned char> host(b_out);
-  HIPCHK(hipMemcpyAsync(host.data(), d_out, b_out, hipMemcpyDeviceToHost, st));
-  HIPCHK(stream_wait(st));
-  GainArgs HA = A;
-  YawPathArgs HY = Y;
-  out_layout(HA, HY, host.data());
-  memcpy(gain, HA.gain, ng * my * sizeof(double));
-  if (n_cand) memcpy(n_cand, HA.n_cand, ng * my * sizeof(int));
-  if (n_visible) memcpy(n_visible, HA.n_visible, ng * my * sizeof(int));
-  memcpy(n_rays, HA.n_rays, ng * sizeof(int));
-  if (yp) {
-    memcpy(yp->status, HY.status, n * sizeof(int));
-    memcpy(yp->path, HY.path, n * ml * sizeof(double));
-    memcpy(yp->path_vertex, HY.path_vertex, n * ml * sizeof(int));
-    memcpy(yp->g_value, HY.g_value, n * ml * my * sizeof(double));
-  }
-  return FUELMI_OK;
+  return result_fetch(R, st);
 }
 
 }  // namespace
@@ -646,10 +623,8 @@ extern "C" int fuelmi_map_yaw_paths(fuelmi_map* m, const fuelmi_yawpath_cfg* cfg
     const int rc = heading_run(m, gc, groups, views, n_prob, n_ctrl, ctrl, gains, nullptr, nullptr, n_rays, &yp);
     if (rc) return rc;
   }
-  for (int b = 0; b < n_prob; ++b)
-    if (status[b] == -1) {
-      fuelmi_set_error("yaw paths: a layer of problem %d holds more than %d subsampled cells", b, IG_CAP);
-      return FUELMI_ELIMIT;
-    }
-  return FUELMI_OK;
+  const int b = first_over_limit(status, n_prob);
+  if (b < 0) return FUELMI_OK;
+  fuelmi_set_error("yaw paths: a layer of problem %d holds more than %d subsampled cells", b, IG_CAP);
+  return FUELMI_ELIMIT;
 }

@@ -688,10 +688,9 @@ int kino_prepare(fuelmi_map* m, const fuelmi_kino_cfg* cfg, int n_prob, const do
     return L.size();
   };
   {
-    const int rc = m->kino_dev.reserve(st, layout(nullptr));
+    const int rc = m->kino_dev.carve(st, layout);
     if (rc) return rc;
   }
-  layout(m->kino_dev.base());
   // staged in the map: the sources must outlive this function (the copies may run after it returns)
   std::vector<double>& hin = m->kino_host;
   hin.assign(n * 15 + prims.size(), 0.0);
@@ -759,68 +758,45 @@ extern "C" int fuelmi_map_kino_paths(fuelmi_map* m, const fuelmi_kino_cfg* cfg, 
   HIPCHK(hipSetDevice(m->device));
   const size_t n = (size_t)n_prob, maxs = (size_t)cfg->max_samples, maxn = (size_t)cfg->max_path_nodes;
   KinoArgs K;
-  auto layout = [&](unsigned char* base) {  // the result block
-    BlockLayout L(base, 16);
-    K.status = L.take<int>(n);
-    K.which = L.take<int>(n);
-    K.iter_num = L.take<int>(n);
-    K.use_node_num = L.take<int>(n);
-    K.n_nodes = L.take<int>(n);
-    K.shot = L.take<int>(n);
-    K.seg_num = L.take<int>(n);
-    K.n_samples = L.take<int>(n);
-    K.skip = L.take<int>(n);
-    K.t_shot = L.take<double>(n);
-    K.T_sum = L.take<double>(n);
-    K.ts_out = L.take<double>(n);
-    K.coef_shot = L.take<double>(n * 12);
-    K.derivs = L.take<double>(n * 12);
-    K.samples = L.take<double>(n * maxs * 3);
-    K.node_state = node_state ? L.take<double>(n * maxn * 6) : nullptr;
-    K.node_input = node_input ? L.take<double>(n * maxn * 3) : nullptr;
-    K.node_duration = node_duration ? L.take<double>(n * maxn) : nullptr;
-    return L.size();
-  };
-  const size_t io_bytes = layout(nullptr);
+  ResultBlock R(16);  // skip is the kernel's own; the path nodes only where the caller asks
+  R.add(K.status, status, n);
+  R.add(K.which, which, n);
+  R.add(K.iter_num, iter_num, n);
+  R.add(K.use_node_num, use_node_num, n);
+  R.add(K.n_nodes, n_nodes, n);
+  R.add(K.shot, shot, n);
+  R.add(K.seg_num, seg_num, n);
+  R.add(K.n_samples, n_samples, n);
+  R.hold(K.skip, n);
+  R.add(K.t_shot, t_shot, n);
+  R.add(K.T_sum, T_sum, n);
+  R.add(K.ts_out, ts_out, n);
+  R.add(K.coef_shot, coef_shot, n * 12);
+  R.add(K.derivs, derivs, n * 12);
+  R.add(K.samples, samples, n * maxs * 3);
+  R.opt(K.node_state, node_state, n * maxn * 6);
+  R.opt(K.node_input, node_input, n * maxn * 3);
+  R.opt(K.node_duration, node_duration, n * maxn);
+  ARGCHK(!R.overflow);
   unsigned char* io = nullptr;
   {
-    const int rc = kino_prepare(m, cfg, n_prob, start_xyz, start_vel, start_acc, goal_xyz, goal_vel, io_bytes, K, &io);
+    const int rc = kino_prepare(m, cfg, n_prob, start_xyz, start_vel, start_acc, goal_xyz, goal_vel, R.size(), K, &io);
     if (rc) return rc;
   }
-  layout(io);
-  std::vector<unsigned char> host(io_bytes);
-  auto back = [&](const void* dev) { return host.data() + (static_cast<const unsigned char*>(dev) - io); };
-  hipStream_t st = m->stream;
+  R.bind(io);
   {
     const int rc = kino_launch(m, K);
     if (rc) return rc;
   }
-  HIPCHK(hipMemcpyAsync(host.data(), io, io_bytes, hipMemcpyDeviceToHost, st));
-  HIPCHK(stream_wait(st));
-  memcpy(status, back(K.status), n * sizeof(int));
-  memcpy(which, back(K.which), n * sizeof(int));
-  memcpy(iter_num, back(K.iter_num), n * sizeof(int));
-  memcpy(use_node_num, back(K.use_node_num), n * sizeof(int));
-  memcpy(n_nodes, back(K.n_nodes), n * sizeof(int));
-  memcpy(shot, back(K.shot), n * sizeof(int));
-  memcpy(seg_num, back(K.seg_num), n * sizeof(int));
-  memcpy(n_samples, back(K.n_samples), n * sizeof(int));
-  memcpy(t_shot, back(K.t_shot), n * sizeof(double));
-  memcpy(T_sum, back(K.T_sum), n * sizeof(double));
-  memcpy(ts_out, back(K.ts_out), n * sizeof(double));
-  memcpy(coef_shot, back(K.coef_shot), n * 12 * sizeof(double));
-  memcpy(derivs, back(K.derivs), n * 12 * sizeof(double));
-  memcpy(samples, back(K.samples), n * maxs * 3 * sizeof(double));
-  if (node_state) memcpy(node_state, back(K.node_state), n * maxn * 6 * sizeof(double));
-  if (node_input) memcpy(node_input, back(K.node_input), n * maxn * 3 * sizeof(double));
-  if (node_duration) memcpy(node_duration, back(K.node_duration), n * maxn * sizeof(double));
-  for (int b = 0; b < n_prob; ++b)
-    if (status[b] == -1) {
-      fuelmi_set_error("kinodynamic search: problem %d has %d path nodes / %d samples, more than max_path_nodes = %d / "
-                       "max_samples = %d", b, n_nodes[b], n_samples[b], cfg->max_path_nodes, cfg->max_samples);
-      return FUELMI_ELIMIT;
-    }
-  return FUELMI_OK;
+  {
+    const int rc = result_fetch(R, m->stream);
+    if (rc) return rc;
+  }
+  const int b = first_over_limit(status, n_prob);
+  if (b < 0) return FUELMI_OK;
+  fuelmi_set_error("kinodynamic search: problem %d has %d path nodes / %d samples, more than max_path_nodes = %d / "
+                   "max_samples = %d", b, n_nodes[b], n_samples[b], cfg->max_path_nodes, cfg->max_samples);
+  return FUELMI_ELIMIT;
 }
 
 // start / goal -> kinodynamic search -> getSamples (k_kino_path, written into the staging) -> the fit, all on the map's

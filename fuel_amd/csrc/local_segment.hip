@@ -384,18 +384,17 @@ int localseg_launch(hipStream_t st, const LocalSegArgs& A) {
   return FUELMI_OK;
 }
 
-// the scalar results of n problems in a block (base null: only its size)
-size_t ls_scalars(size_t n, LocalSegArgs& A, unsigned char* base) {
-  BlockLayout L(base, 16);
-  A.status = L.take<int>(n);
-  A.n_steps = L.take<int>(n);
-  A.seg_num = L.take<int>(n);
-  A.n_points = L.take<int>(n);
-  A.n_ctrl = L.take<int>(n);
-  A.fit_k = L.take<int>(n);
-  A.segment_len = L.take<double>(n);
-  A.duration = L.take<double>(n);
-  return L.size();
+// the scalar results of n problems, each declared once (a null destination: in the block, fetched by the caller itself)
+void ls_scalars(ResultBlock& R, size_t n, LocalSegArgs& A, int* status, int* n_steps, int* seg_num, int* n_points,
+                int* n_ctrl, double* segment_len, double* duration) {
+  R.add(A.status, status, n);
+  R.add(A.n_steps, n_steps, n);
+  R.add(A.seg_num, seg_num, n);
+  R.add(A.n_points, n_points, n);
+  R.add(A.n_ctrl, n_ctrl, n);
+  R.hold(A.fit_k, n);
+  R.add(A.segment_len, segment_len, n);
+  R.add(A.duration, duration, n);
 }
 
 }  // namespace
@@ -442,77 +441,55 @@ extern "C" int fuelmi_map_local_segments(fuelmi_map* m, const fuelmi_localseg_cf
   LocalSegArgs A;
   memset(&A, 0, sizeof(A));
   LsIn I;
-  const size_t b_sc = ls_scalars(n, A, nullptr);
-  const size_t b_out = b_sc + (n + n * mp * 3 + n * 12 + n * rows * 3) * sizeof(double);
-  unsigned char* d_out;
+  FitArgs F;  // each problem's own count; a problem without points (fit_k = 0) is left zero
+  memset(&F, 0, sizeof(F));
+  ResultBlock R(16);  // the fit reads dt, points, derivs and writes ctrl in the block
+  ls_scalars(R, n, A, status, n_steps, seg_num, n_points, n_ctrl, segment_len, duration);
+  R.add(A.dt, dt, n);
+  R.add(A.points, points, n * mp * 3);
+  R.add(A.derivs, derivs, n * 12);
+  R.add(F.ctrl, ctrl, n * rows * 3);
+  ARGCHK(!R.overflow);
   auto layout = [&](unsigned char* base) {
     BlockLayout L(base, 16);
     ls_in_take(L, *cfg, nt, n, I);
-    d_out = L.take<unsigned char>(b_out);
+    R.place(L);
     return L.size();
   };
   {
-    const int rc = m->localseg_dev.reserve(st, layout(nullptr));
+    const int rc = m->localseg_dev.carve(st, layout);
     if (rc) return rc;
   }
-  layout(m->localseg_dev.base());
   {
     const int rc = ls_in_upload(st, *cfg, nt, n, I, A, n_seg, seg_times, coef, global_duration, n_local_ctrl, local_ctrl,
                                 local_knot_span, local_ts, local_te, time_change, last_time_inc, traj_of, mode, start_t,
                                 arg0, arg1);
     if (rc) return rc;
   }
-  HIPCHK(hipMemsetAsync(d_out, 0, b_out, st));
-  // the result block: scalars | dt | points | derivs | ctrl
-  auto carve = [&](LocalSegArgs& R, unsigned char* base, double*& r_ctrl) {
-    ls_scalars(n, R, base);
-    R.dt = reinterpret_cast<double*>(base + b_sc);
-    R.points = R.dt + n;
-    R.derivs = R.points + n * mp * 3;
-    r_ctrl = R.derivs + n * 12;
-  };
-  double* d_ctrl;
-  carve(A, d_out, d_ctrl);
+  HIPCHK(hipMemsetAsync(R.base, 0, R.size(), st));
   A.cfg = *cfg;
   A.n_prob = n_prob;
   {
     const int rc = localseg_launch(st, A);
     if (rc) return rc;
   }
-  FitArgs F;  // each problem's own count; a problem without points (fit_k = 0) is left zero
-  memset(&F, 0, sizeof(F));
   F.C = n_prob, F.K = cfg->max_points, F.degree = cfg->degree;
   F.ts = A.dt, F.points = A.points, F.derivs = A.derivs;
-  F.ctrl = d_ctrl, F.stride = (long)(rows * 3);
+  F.stride = (long)(rows * 3);
   F.Ks = A.fit_k, F.pt_stride = (long)mp;
   {
     const int rc = fit_launch(m, F, st);
     if (rc) return rc;
   }
-  std::vector<unsigned char> host(b_out);
-  HIPCHK(hipMemcpyAsync(host.data(), d_out, b_out, hipMemcpyDeviceToHost, st));
-  HIPCHK(stream_wait(st));
-  LocalSegArgs H = A;
-  double* h_ctrl;
-  carve(H, host.data(), h_ctrl);
-  memcpy(status, H.status, n * sizeof(int));
-  memcpy(n_steps, H.n_steps, n * sizeof(int));
-  memcpy(seg_num, H.seg_num, n * sizeof(int));
-  memcpy(n_points, H.n_points, n * sizeof(int));
-  memcpy(n_ctrl, H.n_ctrl, n * sizeof(int));
-  memcpy(segment_len, H.segment_len, n * sizeof(double));
-  memcpy(duration, H.duration, n * sizeof(double));
-  memcpy(dt, H.dt, n * sizeof(double));
-  memcpy(points, H.points, n * mp * 3 * sizeof(double));
-  memcpy(derivs, H.derivs, n * 12 * sizeof(double));
-  memcpy(ctrl, h_ctrl, n * rows * 3 * sizeof(double));
-  for (int b = 0; b < n_prob; ++b)
-    if (status[b] == -1) {
-      fuelmi_set_error("local segments: problem %d has %d points, more than max_points = %d", b, n_points[b],
-                       cfg->max_points);
-      return FUELMI_ELIMIT;
-    }
-  return FUELMI_OK;
+  {
+    const int rc = result_fetch(R, st);
+    if (rc) return rc;
+  }
+  const int b = first_over_limit(status, n_prob);
+  if (b < 0) return FUELMI_OK;
+  fuelmi_set_error("local segments: problem %d has %d points, more than max_points = %d", b, n_points[b],
+                   cfg->max_points);
+  return FUELMI_ELIMIT;
 }
 
 // the batch route: one problem per candidate -> points, derivatives and knot spans (k_local_segment, written into the
@@ -549,21 +526,21 @@ extern "C" int fuelmi_bspline_dev_load_local_segments(
   LocalSegArgs A;
   memset(&A, 0, sizeof(A));
   LsIn I;
-  const size_t b_sc = ls_scalars(C, A, nullptr);
+  ResultBlock R(16);  // only status and duration come back, in copies of their own
+  ls_scalars(R, C, A, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  ARGCHK(!R.overflow);
   double* d_fit;  // ts | points | derivs: the layout fuelmi_bspline_dev_load_samples stages
-  unsigned char* d_sc;
   auto layout = [&](unsigned char* base) {
     BlockLayout L(base, 16);
     d_fit = L.take<double>(C * (1 + K * 3 + 12));
     ls_in_take(L, cfg, nt, C, I);
-    d_sc = L.take<unsigned char>(b_sc);
+    R.place(L);
     return L.size();
   };
   {
-    const int rc = b->fit_in.reserve(st, layout(nullptr));
+    const int rc = b->fit_in.carve(st, layout);
     if (rc) return rc;
   }
-  layout(b->fit_in.base());
   {
     const int rc = ls_in_upload(st, cfg, nt, C, I, A, n_seg, seg_times, coef, global_duration, n_local_ctrl, local_ctrl,
                                 local_knot_span, local_ts, local_te, time_change, last_time_inc, traj_of, mode, start_t,
@@ -571,8 +548,7 @@ extern "C" int fuelmi_bspline_dev_load_local_segments(
     if (rc) return rc;
   }
   HIPCHK(hipMemsetAsync(d_fit, 0, C * (1 + K * 3 + 12) * sizeof(double), st));
-  HIPCHK(hipMemsetAsync(d_sc, 0, b_sc, st));
-  ls_scalars(C, A, d_sc);
+  HIPCHK(hipMemsetAsync(R.base, 0, R.size(), st));
   A.dt = d_fit;  // the fit's knot spans
   A.points = d_fit + C;
   A.derivs = d_fit + C + C * K * 3;

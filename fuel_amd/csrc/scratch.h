@@ -1,9 +1,12 @@
-// scratch.h -- the device scratch of the batched calls (host code only): a grow-only pool, and the carver that lays
-// typed arrays out in one block.  Included by fuelmi_internal.h, below HIPCHK.
+// scratch.h -- the device scratch of the batched calls (host code only): a grow-only pool; with it, from
+// block_layout.h, the carver that lays typed arrays out in one block (BlockLayout) and the descriptor of the arrays a
+// call brings back from it (ResultBlock).  Included by fuelmi_internal.h, below HIPCHK.
 #ifndef FUELMI_SCRATCH_H_
 #define FUELMI_SCRATCH_H_
 
 #include <cstddef>
+
+#include "block_layout.h"
 
 // One grow-only device block.  A call sizes its arrays (BlockLayout on a null base), reserves, and carves; what it
 // carved is valid until the next reserve of the same pool.
@@ -29,23 +32,14 @@ struct DevScratch {
     bytes = 0;
   }
   unsigned char* base() const { return static_cast<unsigned char*>(p); }
-};
-
-// Arrays taken one after the other from a block whose base is aligned to `align` (a power of two); every array's
-// size is padded to `align`, so every array starts aligned.  A null base is the sizing pass: take() returns null and
-// size() is what the same takes need.
-struct BlockLayout {
-  unsigned char* base;
-  size_t align;
-  size_t at = 0;
-  BlockLayout(unsigned char* base_, size_t align_) : base(base_), align(align_) {}
-  template <class T>
-  T* take(size_t count) {
-    T* p = base ? reinterpret_cast<T*>(base + at) : nullptr;
-    at += (count * sizeof(T) + align - 1) & ~(align - 1);
-    return p;
+  // `layout(base)` carves a call's arrays and returns their size: sized on a null base, reserved, carved on the block
+  template <class F>
+  int carve(hipStream_t st, F&& layout) {
+    const int rc = reserve(st, layout(nullptr));
+    if (rc) return rc;
+    layout(base());
+    return FUELMI_OK;
   }
-  size_t size() const { return at; }
 };
 
 #endif

@@ -883,29 +883,31 @@ extern "C" int fuelmi_map_topo_paths(fuelmi_map* m, const fuelmi_topo_cfg* cfg, 
                rs = (size_t)cfg->reserve_num;
   TopoArgs T;
   memset(&T, 0, sizeof(T));
+  ResultBlock R(256);  // everything behind events only where the caller asks
+  R.add(T.status, status, n);
+  R.add(T.counts, counts, n * 4);
+  R.add(T.events, events, n * 6);
+  R.opt(T.n_nodes, n_nodes, n);
+  R.opt(T.node_id, node_id, n * maxn);
+  R.opt(T.node_kind, node_type, n * maxn);
+  R.opt(T.node_xyz, node_xyz, n * maxn * 3);
+  R.opt(T.nb_off, nb_off, n * (maxn + 1));
+  R.opt(T.nb_ids, nb_ids, n * 4 * maxn);
+  R.opt(T.raw_paths, raw_paths, n * r2 * mpp * 3);
+  R.opt(T.raw_plen, raw_len, n * r2);
+  R.opt(T.filt_paths, filt_paths, n * r2 * mpp * 3);
+  R.opt(T.filt_plen, filt_len, n * r2);
+  R.opt(T.sel_paths, sel_paths, n * rs * mpp * 3);
+  R.opt(T.sel_plen, sel_len, n * rs);
+  R.opt(T.sel_length, sel_length, n * rs);
+  ARGCHK(!R.overflow);
   // the block: results | inputs | workspace
   double *d_in, *d_sp, *d_ep, *d_smp;
   int *d_nsp, *d_nep;
-  size_t out_bytes = 0, in_at = 0, in_bytes = 0;
+  size_t in_at = 0, in_bytes = 0;
   auto layout = [&](unsigned char* base) {
     BlockLayout L(base, 256);
-    T.status = L.take<int>(n);
-    T.counts = L.take<int>(n * 4);
-    T.events = L.take<int>(n * 6);
-    T.n_nodes = n_nodes ? L.take<int>(n) : nullptr;
-    T.node_id = node_id ? L.take<int>(n * maxn) : nullptr;
-    T.node_kind = node_type ? L.take<int>(n * maxn) : nullptr;
-    T.node_xyz = node_xyz ? L.take<double>(n * maxn * 3) : nullptr;
-    T.nb_off = nb_off ? L.take<int>(n * (maxn + 1)) : nullptr;
-    T.nb_ids = nb_ids ? L.take<int>(n * 4 * maxn) : nullptr;
-    T.raw_paths = raw_paths ? L.take<double>(n * r2 * mpp * 3) : nullptr;
-    T.raw_plen = raw_len ? L.take<int>(n * r2) : nullptr;
-    T.filt_paths = filt_paths ? L.take<double>(n * r2 * mpp * 3) : nullptr;
-    T.filt_plen = filt_len ? L.take<int>(n * r2) : nullptr;
-    T.sel_paths = sel_paths ? L.take<double>(n * rs * mpp * 3) : nullptr;
-    T.sel_plen = sel_len ? L.take<int>(n * rs) : nullptr;
-    T.sel_length = sel_length ? L.take<double>(n * rs) : nullptr;
-    out_bytes = L.size();
+    R.place(L);
     in_at = L.size();
     d_in = L.take<double>(n * 6);
     d_sp = L.take<double>(n * ms * 3 + 1);
@@ -918,11 +920,10 @@ extern "C" int fuelmi_map_topo_paths(fuelmi_map* m, const fuelmi_topo_cfg* cfg, 
     return head + topo_workspace(cfg, n, base ? base + head : nullptr, &T);
   };
   {
-    const int rc = m->topo_dev.reserve(st, layout(nullptr));
+    const int rc = m->topo_dev.carve(st, layout);
     if (rc) return rc;
   }
   unsigned char* base = m->topo_dev.base();
-  layout(base);
   // the inputs, staged in the map: the source must outlive the copy
   std::vector<unsigned char>& hin = m->topo_host;
   hin.assign(in_bytes, 0);
@@ -951,34 +952,13 @@ extern "C" int fuelmi_map_topo_paths(fuelmi_map* m, const fuelmi_topo_cfg* cfg, 
   T.in = d_in, T.spts = d_sp, T.epts = d_ep, T.n_spts = d_nsp, T.n_epts = d_nep, T.samples = d_smp;
   hipLaunchKernelGGL(k_topo_path, dim3(n_prob), dim3(TP_NT), 0, st, m->g, T);
   HIPCHK(hipGetLastError());
-  std::vector<unsigned char> host(out_bytes);
-  HIPCHK(hipMemcpyAsync(host.data(), base, out_bytes, hipMemcpyDeviceToHost, st));
-  HIPCHK(stream_wait(st));
-  auto back = [&](const void* dev) { return host.data() + (static_cast<const unsigned char*>(dev) - base); };
-  auto take = [&](void* dst, const void* dev, size_t bytes) {
-    if (dst) memcpy(dst, back(dev), bytes);
-  };
-  take(status, T.status, n * sizeof(int));
-  take(counts, T.counts, n * 4 * sizeof(int));
-  take(events, T.events, n * 6 * sizeof(int));
-  take(n_nodes, T.n_nodes, n * sizeof(int));
-  take(node_id, T.node_id, n * maxn * sizeof(int));
-  take(node_type, T.node_kind, n * maxn * sizeof(int));
-  take(node_xyz, T.node_xyz, n * maxn * 3 * sizeof(double));
-  take(nb_off, T.nb_off, n * (maxn + 1) * sizeof(int));
-  take(nb_ids, T.nb_ids, n * 4 * maxn * sizeof(int));
-  take(raw_paths, T.raw_paths, n * r2 * mpp * 3 * sizeof(double));
-  take(raw_len, T.raw_plen, n * r2 * sizeof(int));
-  take(filt_paths, T.filt_paths, n * r2 * mpp * 3 * sizeof(double));
-  take(filt_len, T.filt_plen, n * r2 * sizeof(int));
-  take(sel_paths, T.sel_paths, n * rs * mpp * 3 * sizeof(double));
-  take(sel_len, T.sel_plen, n * rs * sizeof(int));
-  take(sel_length, T.sel_length, n * rs * sizeof(double));
-  for (int b = 0; b < n_prob; ++b)
-    if (status[b] == -1) {
-      fuelmi_set_error("topological search: problem %d is over max_nodes = %d / max_path_points = %d or one of the "
-                       "kernel's caps (fuelmi_topo_plan)", b, cfg->max_nodes, cfg->max_path_points);
-      return FUELMI_ELIMIT;
-    }
-  return FUELMI_OK;
+  {
+    const int rc = result_fetch(R, st);
+    if (rc) return rc;
+  }
+  const int b = first_over_limit(status, n_prob);
+  if (b < 0) return FUELMI_OK;
+  fuelmi_set_error("topological search: problem %d is over max_nodes = %d / max_path_points = %d or one of the "
+                   "kernel's caps (fuelmi_topo_plan)", b, cfg->max_nodes, cfg->max_path_points);
+  return FUELMI_ELIMIT;
 }

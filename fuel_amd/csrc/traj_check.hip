@@ -198,53 +198,37 @@ int trajchk_check(const fuelmi_trajchk_cfg* cfg, int n_prob, const TrajChkIO& io
   return FUELMI_OK;
 }
 
-// the result block's layout (base null: only its size)
-size_t trajchk_out_bytes(int n_prob, TrajChkArgs& T, unsigned char* base) {
+// the result arrays, each declared once
+void trajchk_results(ResultBlock& R, TrajChkArgs& T, int n_prob, const TrajChkIO& io) {
   const size_t n = (size_t)n_prob;
-  BlockLayout L(base, 16);
-  T.status = L.take<int>(n);
-  T.safe = L.take<int>(n);
-  T.n_samples = L.take<int>(n);
-  T.hit_index = L.take<int>(n);
-  T.end_reason = L.take<int>(n);
-  T.distance = L.take<double>(n);
-  T.hit_t = L.take<double>(n);
-  T.duration = L.take<double>(n);
-  T.hit_pos = L.take<double>(n * 3);
-  return L.size();
+  R.add(T.status, io.status, n);
+  R.add(T.safe, io.safe, n);
+  R.add(T.n_samples, io.n_samples, n);
+  R.add(T.hit_index, io.hit_index, n);
+  R.add(T.end_reason, io.end_reason, n);
+  R.add(T.distance, io.distance, n);
+  R.add(T.hit_t, io.hit_t, n);
+  R.add(T.duration, io.duration, n);
+  R.add(T.hit_pos, io.hit_pos, n * 3);
 }
 
-// both entries behind their uploads (T holds cfg, n_prob, src, t_now), on the map's stream: results carved at d_out, launch,
-// download, wait, the results into the caller's arrays (FUELMI_ELIMIT when a problem's status is -1)
-int trajchk_run(fuelmi_map* m, TrajChkArgs& T, unsigned char* d_out, const TrajChkIO& io) {
+// both entries behind their uploads (T holds cfg, n_prob, src, t_now and the results R bound on the device), on the map's
+// stream: launch, download, wait, the results into the caller's arrays (FUELMI_ELIMIT when a problem's status is -1)
+int trajchk_run(fuelmi_map* m, TrajChkArgs& T, const ResultBlock& R, const TrajChkIO& io) {
   hipStream_t st = m->stream;
   const int n_prob = T.n_prob;
-  const size_t n = (size_t)n_prob;
   T.infl = m->infl_bits.p;
-  const size_t b_out = trajchk_out_bytes(n_prob, T, d_out);
   const size_t lds = tc_lds(T.cfg.max_ctrl);  // <= 32.2 KiB at FUELMI_TRAJCHK_MAX_CTRL
   hipLaunchKernelGGL(k_traj_check, dim3((n_prob + TC_WAVES - 1) / TC_WAVES), dim3(TC_WIN * TC_WAVES), lds, st, m->g, T);
   HIPCHK(hipGetLastError());
-  std::vector<unsigned char> host(b_out);
-  HIPCHK(hipMemcpyAsync(host.data(), d_out, b_out, hipMemcpyDeviceToHost, st));
-  HIPCHK(stream_wait(st));
-  TrajChkArgs H = T;
-  trajchk_out_bytes(n_prob, H, host.data());
-  memcpy(io.status, H.status, n * sizeof(int));
-  memcpy(io.safe, H.safe, n * sizeof(int));
-  memcpy(io.n_samples, H.n_samples, n * sizeof(int));
-  memcpy(io.hit_index, H.hit_index, n * sizeof(int));
-  memcpy(io.end_reason, H.end_reason, n * sizeof(int));
-  memcpy(io.distance, H.distance, n * sizeof(double));
-  memcpy(io.hit_t, H.hit_t, n * sizeof(double));
-  memcpy(io.duration, H.duration, n * sizeof(double));
-  memcpy(io.hit_pos, H.hit_pos, n * 3 * sizeof(double));
-  for (int b = 0; b < n_prob; ++b)
-    if (io.status[b] == -1) {
-      fuelmi_set_error("trajectory check: problem %d needs more than %d samples", b, FUELMI_TRAJCHK_MAX_SAMPLES);
-      return FUELMI_ELIMIT;
-    }
-  return FUELMI_OK;
+  {
+    const int rc = result_fetch(R, st);
+    if (rc) return rc;
+  }
+  const int b = first_over_limit(io.status, n_prob);
+  if (b < 0) return FUELMI_OK;
+  fuelmi_set_error("trajectory check: problem %d needs more than %d samples", b, FUELMI_TRAJCHK_MAX_SAMPLES);
+  return FUELMI_ELIMIT;
 }
 
 }  // namespace
@@ -277,21 +261,21 @@ extern "C" int fuelmi_map_check_trajs(fuelmi_map* m, const fuelmi_trajchk_cfg* c
   const size_t n = (size_t)n_prob;
   TrajChkArgs T;
   memset(&T, 0, sizeof(T));
-  const size_t b_out = trajchk_out_bytes(n_prob, T, nullptr);
+  ResultBlock R(16);
+  trajchk_results(R, T, n_prob, io);
+  ARGCHK(!R.overflow);
   double* d_now;
-  unsigned char* d_out;
   auto layout = [&](unsigned char* base) {
     BlockLayout L(base, 16);
     spline_src_take(L, n, cfg->max_ctrl, T.src);
     d_now = L.take<double>(n);
-    d_out = L.take<unsigned char>(b_out);
+    R.place(L);
     return L.size();
   };
   {
-    const int rc = m->trajchk_dev.reserve(st, layout(nullptr));
+    const int rc = m->trajchk_dev.carve(st, layout);
     if (rc) return rc;
   }
-  layout(m->trajchk_dev.base());
   {
     const int rc = spline_src_upload(st, T.src, n, cfg->max_ctrl, n_ctrl, pos_ctrl, knot_span);
     if (rc) return rc;
@@ -300,7 +284,7 @@ extern "C" int fuelmi_map_check_trajs(fuelmi_map* m, const fuelmi_trajchk_cfg* c
   T.cfg = *cfg;
   T.n_prob = n_prob;
   T.t_now = d_now;
-  return trajchk_run(m, T, d_out, io);
+  return trajchk_run(m, T, R, io);
 }
 
 // the safety check of a device batch's optimised position splines, read from the variables the last solve left on the
@@ -326,25 +310,25 @@ extern "C" int fuelmi_bspline_dev_check_trajs(fuelmi_bspline_dev* b, const fuelm
   const size_t C = (size_t)A.C;
   TrajChkArgs T;
   memset(&T, 0, sizeof(T));
-  const size_t b_out = trajchk_out_bytes(A.C, T, nullptr);
+  ResultBlock R(16);
+  trajchk_results(R, T, A.C, io);
+  ARGCHK(!R.overflow);
   double* d_now;
-  unsigned char* d_out;
   auto layout = [&](unsigned char* base) {
     BlockLayout L(base, 16);
     d_now = L.take<double>(C);
-    d_out = L.take<unsigned char>(b_out);
+    R.place(L);
     return L.size();
   };
   hipStream_t st = m->stream;
   {
-    const int rc = b->chk_dev.reserve(st, layout(nullptr));
+    const int rc = b->chk_dev.carve(st, layout);
     if (rc) return rc;
   }
-  layout(b->chk_dev.base());
   HIPCHK(hipMemcpyAsync(d_now, t_now, C * sizeof(double), hipMemcpyHostToDevice, st));
   T.cfg = tc;
   T.n_prob = A.C;
   T.src = opt_spline_src(b);
   T.t_now = d_now;
-  return trajchk_run(m, T, d_out, io);
+  return trajchk_run(m, T, R, io);
 }

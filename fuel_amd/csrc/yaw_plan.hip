@@ -429,45 +429,29 @@ void yaw_args(const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob
   Y.n_prob = n_prob;
 }
 
-// the result block's layout (base null: only its size); the derivatives' control points only where the caller asks
-size_t yaw_out_bytes(YawArgs& Y, unsigned char* base, const YawIO& io) {
+// the result arrays, each declared once; the derivatives' control points only where the caller asks
+void yaw_results(ResultBlock& R, YawArgs& Y, const YawIO& io) {
   const size_t n = (size_t)Y.n_prob, maxs = (size_t)Y.cfg.max_seg;
-  BlockLayout L(base, 16);
-  Y.status = L.take<int>(n);
-  Y.seg_num = L.take<int>(n);
-  Y.n_waypt = L.take<int>(n);
-  Y.duration = L.take<double>(n);
-  Y.dt_yaw = L.take<double>(n);
-  Y.end_yaw_out = L.take<double>(n);
-  Y.cost = L.take<double>(n);
-  Y.yaw_ctrl = L.take<double>(n * (maxs + 3));
-  Y.waypts = L.take<double>(n * maxs);
-  Y.yawdot_ctrl = io.yawdot_ctrl ? L.take<double>(n * (maxs + 2)) : nullptr;
-  Y.yawddot_ctrl = io.yawddot_ctrl ? L.take<double>(n * (maxs + 1)) : nullptr;
-  return L.size();
+  R.add(Y.status, io.status, n);
+  R.add(Y.seg_num, io.seg_num, n);
+  R.add(Y.n_waypt, io.n_waypt, n);
+  R.add(Y.duration, io.duration, n);
+  R.add(Y.dt_yaw, io.dt_yaw, n);
+  R.add(Y.end_yaw_out, io.end_yaw_out, n);
+  R.add(Y.cost, io.cost, n);
+  R.add(Y.yaw_ctrl, io.yaw_ctrl, n * (maxs + 3));
+  R.add(Y.waypts, io.waypts, n * maxs);
+  R.opt(Y.yawdot_ctrl, io.yawdot_ctrl, n * (maxs + 2));
+  R.opt(Y.yawddot_ctrl, io.yawddot_ctrl, n * (maxs + 1));
 }
 
-// the result block in host-readable memory -> the caller's arrays (FUELMI_ELIMIT when a problem's status is -1)
-int yaw_copy_out(const YawArgs& H, const YawIO& io) {
-  const size_t n = (size_t)H.n_prob, maxs = (size_t)H.cfg.max_seg;
-  memcpy(io.status, H.status, n * sizeof(int));
-  memcpy(io.seg_num, H.seg_num, n * sizeof(int));
-  memcpy(io.n_waypt, H.n_waypt, n * sizeof(int));
-  memcpy(io.duration, H.duration, n * sizeof(double));
-  memcpy(io.dt_yaw, H.dt_yaw, n * sizeof(double));
-  memcpy(io.end_yaw_out, H.end_yaw_out, n * sizeof(double));
-  memcpy(io.cost, H.cost, n * sizeof(double));
-  memcpy(io.yaw_ctrl, H.yaw_ctrl, n * (maxs + 3) * sizeof(double));
-  memcpy(io.waypts, H.waypts, n * maxs * sizeof(double));
-  if (io.yawdot_ctrl) memcpy(io.yawdot_ctrl, H.yawdot_ctrl, n * (maxs + 2) * sizeof(double));
-  if (io.yawddot_ctrl) memcpy(io.yawddot_ctrl, H.yawddot_ctrl, n * (maxs + 1) * sizeof(double));
-  for (int b = 0; b < H.n_prob; ++b)
-    if (io.status[b] == -1) {
-      fuelmi_set_error("yaw plan: problem %d needs %d yaw segments, more than max_seg = %d", b, io.seg_num[b],
-                       H.cfg.max_seg);
-      return FUELMI_ELIMIT;
-    }
-  return FUELMI_OK;
+// behind the results in the caller's arrays: FUELMI_ELIMIT when a problem's status is -1
+int yaw_limit(const YawArgs& Y, const YawIO& io) {
+  const int b = first_over_limit(io.status, Y.n_prob);
+  if (b < 0) return FUELMI_OK;
+  fuelmi_set_error("yaw plan: problem %d needs %d yaw segments, more than max_seg = %d", b, io.seg_num[b],
+                   Y.cfg.max_seg);
+  return FUELMI_ELIMIT;
 }
 
 int yaw_launch(hipStream_t st, const YawArgs& Y) {
@@ -508,10 +492,11 @@ extern "C" int fuelmi_map_plan_yaws(fuelmi_map* m, const fuelmi_bspline_cfg* w, 
   const size_t n = (size_t)n_prob, maxc = (size_t)cfg->max_ctrl;
   YawArgs Y;
   yaw_args(w, cfg, n_prob, Y);
-  const size_t b_out = yaw_out_bytes(Y, nullptr, io);
+  ResultBlock R(16);
+  yaw_results(R, Y, io);
+  ARGCHK(!R.overflow);
   int* p_nc;
   double *p_knot, *p_end, *p_pos, *p_start;
-  unsigned char* p_out;
   auto layout = [&](unsigned char* base) {  // the slot's pinned block: the inputs, then the results
     BlockLayout L(base, 16);
     p_nc = L.take<int>(n);
@@ -519,7 +504,7 @@ extern "C" int fuelmi_map_plan_yaws(fuelmi_map* m, const fuelmi_bspline_cfg* w, 
     p_end = L.take<double>(n);
     p_pos = L.take<double>(n * maxc * 3);
     p_start = L.take<double>(n * 3);
-    p_out = L.take<unsigned char>(b_out);
+    R.place(L);
     return L.size();
   };
   QuerySlotGuard q;
@@ -538,13 +523,13 @@ extern "C" int fuelmi_map_plan_yaws(fuelmi_map* m, const fuelmi_bspline_cfg* w, 
   memcpy(p_start, start_yaw, n * 3 * sizeof(double));
   Y.src = {p_nc, 0, p_pos, maxc * 3, p_knot, 1};
   Y.start_yaw = p_start, Y.end_yaw = p_end;
-  yaw_out_bytes(Y, p_out, io);
   {
     const int rc = yaw_launch(q.s->st, Y);
     if (rc) return rc;
   }
   HIPCHK(q.finish());
-  return yaw_copy_out(Y, io);
+  R.scatter(R.base);
+  return yaw_limit(Y, io);
 }
 
 // the batch route: the splines the batch's last solve left on the device; staged in yaw_dev on the map's stream, downloaded
@@ -571,22 +556,22 @@ extern "C" int fuelmi_bspline_dev_plan_yaws(fuelmi_bspline_dev* b, const fuelmi_
   const size_t C = (size_t)A.C;
   YawArgs Y;
   yaw_args(&A.cfg, &yc, A.C, Y);
-  const size_t b_out = yaw_out_bytes(Y, nullptr, io);
+  ResultBlock R(16);
+  yaw_results(R, Y, io);
+  ARGCHK(!R.overflow);
   double *d_start, *d_end;
-  unsigned char* d_out;
   auto layout = [&](unsigned char* base) {
     BlockLayout L(base, 16);
     d_start = L.take<double>(C * 3);
     d_end = L.take<double>(C);
-    d_out = L.take<unsigned char>(b_out);
+    R.place(L);
     return L.size();
   };
   hipStream_t st = m->stream;
   {
-    const int rc = b->yaw_dev.reserve(st, layout(nullptr));
+    const int rc = b->yaw_dev.carve(st, layout);
     if (rc) return rc;
   }
-  layout(b->yaw_dev.base());
   HIPCHK(hipMemcpyAsync(d_start, start_yaw, C * 3 * sizeof(double), hipMemcpyHostToDevice, st));
   if (end_yaw)
     HIPCHK(hipMemcpyAsync(d_end, end_yaw, C * sizeof(double), hipMemcpyHostToDevice, st));
@@ -594,16 +579,14 @@ extern "C" int fuelmi_bspline_dev_plan_yaws(fuelmi_bspline_dev* b, const fuelmi_
     HIPCHK(hipMemsetAsync(d_end, 0, C * sizeof(double), st));
   Y.src = opt_spline_src(b);
   Y.start_yaw = d_start, Y.end_yaw = d_end;
-  yaw_out_bytes(Y, d_out, io);
   {
     StageScope sc(m, FUELMI_K_BSPLINE);
     const int rc = yaw_launch(st, Y);
     if (rc) return rc;
   }
-  std::vector<unsigned char> host(b_out);
-  HIPCHK(hipMemcpyAsync(host.data(), d_out, b_out, hipMemcpyDeviceToHost, st));
-  HIPCHK(stream_wait(st));
-  YawArgs H = Y;
-  yaw_out_bytes(H, host.data(), io);
-  return yaw_copy_out(H, io);
+  {
+    const int rc = result_fetch(R, st);
+    if (rc) return rc;
+  }
+  return yaw_limit(Y, io);
 }

@@ -31,6 +31,11 @@ def test_spline_kernels_host_build(name):
     assert check(name)[-1].endswith("all identical, sanitizers silent")
 
 
+def test_result_block_host_build():
+    """the result-block descriptor of the staged batch calls (csrc/block_layout.h): no kernel text, host memory only"""
+    assert check("result_block")[-1].endswith("all passed, sanitizers silent")
+
+
 def test_map_cloud_host_build():
     import fuel_amd._lib as fl
     if not os.path.exists(fl.LIB_PATH):
