@@ -310,6 +310,8 @@ SYMBOLS = {
     "fuelmi_map_last_esdf_family": (C.c_int, [_P]),
     "fuelmi_map_esdf_plan": (C.c_int, [_ip, _ip, _ip, C.c_int, C.c_int, _ip]),
     "fuelmi_map_last_inflate_kernel": (C.c_int, [_P]),
+    "fuelmi_map_set_inflate_kernel": (C.c_int, [_P, C.c_int]),
+    "fuelmi_map_inflate_plan": (C.c_int, [_ip, C.c_int, _ip, _ip, C.c_int, _ip]),
     "fuelmi_map_reset_buffer_all": (C.c_int, [_P]),
     "fuelmi_map_reset_buffer": (C.c_int, [_P, _dp, _dp]),
     "fuelmi_map_set_occupied": (C.c_int, [_P, _dp, C.c_int, C.c_int]),

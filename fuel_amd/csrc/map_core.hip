@@ -567,6 +567,10 @@ static inline void bound_index(const fuelmi_map* m, int id[3]) {
   const int nv[3] = {m->g.nx, m->g.ny, m->g.nz};
   for (int i = 0; i < 3; ++i) id[i] = std::max(std::min(id[i], nv[i] - 1), 0);
 }
+// ---- the launch ranges of the inflation ------------------------------------------------------------------------------
+// Plain host arithmetic, in one place: fuelmi_map_create sizes the planes' margins with it, fuelmi_map_inflate_local
+// launches what it says, fuelmi_map_inflate_plan reports it, and the host build of the inflation kernels
+// (tests/golden/check_inflate_host_build.py cuts this text out) runs them on planes of exactly this size.
 static inline long adr_of(const Geo& g, const int id[3]) {
   return (long)id[0] * g.nyz + (long)id[1] * g.nz + id[2];
 }
@@ -576,6 +580,65 @@ static inline int blocks_for(long n, int threads, int cap = 1 << 20) {
   if (b > cap) b = cap;
   return (int)b;
 }
+// zero words either side of every bit-plane (plane_alloc): the reach of a stamp's corner, so that the shifted window
+// loads of the inflation kernels need no bounds tests.  Step 0 keeps the margin of step 1.
+static inline int inflate_margin_words(const Geo& g, int inflate_step) {
+  const int step = std::max(inflate_step, 1);
+  return (int)(((long)step * ((long)g.nyz + g.nz + 1) + 64) / 64 + 4);
+}
+struct InflatePlan {
+  int margin_words;
+  long reach;          // of a stamp's corner along the linear address string, in voxels
+  int out_lo, out_hi;  // output words: every word a stamp of a source inside the box can reach
+  int rx, ryz;         // reach in words of the x pass's and the y/z pass's window loads
+  int t_lo, t_hi;      // words of the y/z-dilated plane T the x pass reads: the y/z pass writes them
+  int s_lo, s_hi;      // words of the box-masked source plane S the y/z pass reads: the masking pass writes them
+  bool whole;          // the box is the whole map: the occupancy plane itself is S
+  bool two_pass;       // the box's address range is past what the caches hold
+  int ry;              // y/z reach of an output word of the fused kernel, in words
+  size_t lds_f;        // dynamic LDS of the fused kernel
+  int kernel;          // FUELMI_INFLATE_FUSED or _FACTORED: what runs
+  int grid_fused, grid_box, grid_yz, grid_x;  // workgroups of 256; 0: not launched
+};
+static inline InflatePlan inflate_plan(const Geo& g, int step, const Box3& b, int pin) {
+  InflatePlan P;
+  P.margin_words = inflate_margin_words(g, step);
+  P.reach = (long)step * ((long)g.nyz + g.nz + 1);
+  const long a_lo = adr_of(g, b.lo) - P.reach, a_hi = adr_of(g, b.hi) + P.reach;
+  P.out_lo = (int)std::max(0L, a_lo >> 6), P.out_hi = (int)std::min((long)g.W - 1, a_hi >> 6);
+  // T (y/z-dilated sources) must be valid wherever the x pass reads, S wherever the y/z pass reads
+  P.rx = (int)(((long)step * g.nyz + 127) / 64) + 1;
+  P.ryz = (int)(((long)step * (g.nz + 1) + step + 127) / 64) + 1;
+  P.t_lo = std::max(P.out_lo - P.rx, -P.margin_words), P.t_hi = std::min(P.out_hi + P.rx, g.W - 1 + P.margin_words);
+  P.s_lo = std::max(P.t_lo - P.ryz, -P.margin_words), P.s_hi = std::min(P.t_hi + P.ryz, g.W - 1 + P.margin_words);
+  // sources = occupied voxels inside the box.  A box that is the whole map needs no masking: the occupancy
+  // plane itself (zero margins included) is the source plane
+  P.whole = b.lo[0] == 0 && b.lo[1] == 0 && b.lo[2] == 0 && b.hi[0] == g.nx - 1 && b.hi[1] == g.ny - 1 &&
+            b.hi[2] == g.nz - 1;
+  // The fused kernel re-reads every source word five times: free while the words it touches sit in the caches (400^2 x
+  // 100: 9.8 against 11.8 us and a launch saved; the local box of a streaming frame on any map), not for the full box of
+  // the HBM-resident 800^2 x 200 map (53.6 against 42 us): by the size of the BOX's address range, like every other
+  // kernel choice.
+  P.two_pass = (long)(P.out_hi - P.out_lo + 1) * 64 > (48L << 20);
+  P.ry = (step * (g.nz + 1) + 63) / 64 + 1;
+  P.lds_f = (size_t)(2 * step + 1) * (2 * (size_t)(256 + 2 * P.ry + 2) + 2) * sizeof(u64);
+  // (the LDS term cannot fail on a map fuelmi_map_create accepts: nz <= 255 bounds lds_f of step 2 at 22 320 bytes; it
+  // stays as the guard of the launch below it.)  A pin overrules the size term only: the fused kernel is compiled for
+  // step 2 alone, and fuelmi_map_set_inflate_kernel refuses FUSED on any other map
+  const bool fused_fits = step == 2 && P.lds_f <= 64 * 1024;
+  const bool fused = pin == FUELMI_INFLATE_AUTO ? (fused_fits && !P.two_pass) : (pin == FUELMI_INFLATE_FUSED && fused_fits);
+  P.kernel = fused ? FUELMI_INFLATE_FUSED : FUELMI_INFLATE_FACTORED;
+  P.grid_fused = P.grid_box = P.grid_yz = P.grid_x = 0;
+  if (fused) {
+    P.grid_fused = blocks_for(P.out_hi - P.out_lo + 1, 256);
+  } else {
+    if (!P.whole) P.grid_box = blocks_for(P.s_hi - P.s_lo + 1, 256);
+    P.grid_yz = blocks_for(P.t_hi - P.t_lo + 1, 256);
+    P.grid_x = ((blocks_for(P.out_hi - P.out_lo + 1, 256) + 7) / 8) * 8;  // (k_inflate_x deals eighths of its grid to the XCDs)
+  }
+  return P;
+}
+// ---- end of the launch ranges ----------------------------------------------------------------------------------------
 
 extern "C" int fuelmi_map_create(const fuelmi_map_cfg* c, fuelmi_map** out) {
   ARGCHK(c && out);
@@ -641,8 +704,7 @@ extern "C" int fuelmi_map_create(const fuelmi_map_cfg* c, fuelmi_map** out) {
   for (int i = 0; i < 3; ++i) m->local_bound.lo[i] = m->local_bound.hi[i] = 0;
   for (int i = 0; i < 3; ++i) m->upd_min[i] = m->upd_max[i] = 0.0;
   m->reset_updated_box = true;
-  int step = std::max(I.inflate_step, 1);
-  m->margin_words = (int)(((long)step * ((long)g.nyz + g.nz + 1) + 64) / 64 + 4);
+  m->margin_words = inflate_margin_words(g, I.inflate_step);
 
   int rc = FUELMI_OK;
   auto fail = [&](int code) {
@@ -783,44 +845,24 @@ extern "C" int fuelmi_map_inflate_local(fuelmi_map* m) {
   const Geo& g = m->g;
   const Box3& b = m->local_bound;
   const int step = m->info.inflate_step;
-  long reach = (long)step * ((long)g.nyz + g.nz + 1);
-  long a_lo = adr_of(g, b.lo) - reach, a_hi = adr_of(g, b.hi) + reach;
-  int out_lo = (int)std::max(0L, a_lo >> 6), out_hi = (int)std::min((long)g.W - 1, a_hi >> 6);
-  // T (y/z-dilated sources) must be valid wherever the x pass reads, S wherever the y/z pass reads
-  const int rx = (int)(((long)step * g.nyz + 127) / 64) + 1;
-  const int ryz = (int)(((long)step * (g.nz + 1) + step + 127) / 64) + 1;
-  const int t_lo = std::max(out_lo - rx, -m->margin_words), t_hi = std::min(out_hi + rx, g.W - 1 + m->margin_words);
-  const int s_lo = std::max(t_lo - ryz, -m->margin_words), s_hi = std::min(t_hi + ryz, g.W - 1 + m->margin_words);
+  const InflatePlan P = inflate_plan(g, step, b, m->inflate_kernel_pin);
   {
     StageScope sc(m, FUELMI_K_INFLATE);
-    // sources = occupied voxels inside the box.  A box that is the whole map needs no masking: the occupancy
-    // plane itself (zero margins included) is the source plane
-    const bool whole = b.lo[0] == 0 && b.lo[1] == 0 && b.lo[2] == 0 && b.hi[0] == g.nx - 1 && b.hi[1] == g.ny - 1 &&
-                       b.hi[2] == g.nz - 1;
-    // The fused kernel re-reads every source word five times: free while the words it touches sit in the caches (400^2 x
-    // 100: 9.8 against 11.8 us and a launch saved; the local box of a streaming frame on any map), not for the full box of
-    // the HBM-resident 800^2 x 200 map (53.6 against 42 us): by the size of the BOX's address range, like every other
-    // kernel choice.
-    const bool two_pass = (long)(out_hi - out_lo + 1) * 64 > (48L << 20);
-    const int ry = (step * (g.nz + 1) + 63) / 64 + 1;
-    const size_t lds_f = (size_t)(2 * step + 1) * (2 * (size_t)(256 + 2 * ry + 2) + 2) * sizeof(u64);
-    m->last_inflate_kernel = (step == 2 && !two_pass && lds_f <= 64 * 1024) ? 0 : 1;
-    if (step == 2 && !two_pass && lds_f <= 64 * 1024) {
-      const int nb = blocks_for(out_hi - out_lo + 1, 256);
-      if (whole)
-        k_inflate_fused<2, true><<<nb, 256, lds_f, m->stream>>>(g, b, m->occ_bits.p, m->infl_bits.p, out_lo, out_hi, m->margin_words);
+    m->last_inflate_kernel = P.kernel;
+    if (P.kernel == FUELMI_INFLATE_FUSED) {
+      if (P.whole)
+        k_inflate_fused<2, true><<<P.grid_fused, 256, P.lds_f, m->stream>>>(g, b, m->occ_bits.p, m->infl_bits.p, P.out_lo, P.out_hi, m->margin_words);
       else
-        k_inflate_fused<2, false><<<nb, 256, lds_f, m->stream>>>(g, b, m->occ_bits.p, m->infl_bits.p, out_lo, out_hi, m->margin_words);
+        k_inflate_fused<2, false><<<P.grid_fused, 256, P.lds_f, m->stream>>>(g, b, m->occ_bits.p, m->infl_bits.p, P.out_lo, P.out_hi, m->margin_words);
     } else {
-    const u64* S = whole ? m->occ_bits.p : m->tmp_bits.p;
-    if (!whole)
-      k_box_and<<<blocks_for(s_hi - s_lo + 1, 256), 256, 0, m->stream>>>(g, b, m->occ_bits.p, m->tmp_bits.p, s_lo, s_hi);
-    if (step == 2)
-      k_inflate_yz<2><<<blocks_for(t_hi - t_lo + 1, 256), 256, 0, m->stream>>>(g, step, S, m->tmp2_bits.p, t_lo, t_hi);
-    else
-      k_inflate_yz<0><<<blocks_for(t_hi - t_lo + 1, 256), 256, 0, m->stream>>>(g, step, S, m->tmp2_bits.p, t_lo, t_hi);
-    k_inflate_x<<<((blocks_for(out_hi - out_lo + 1, 256) + 7) / 8) * 8, 256, 0, m->stream>>>(g, b, step, m->tmp2_bits.p,
-                                                                             m->infl_bits.p, out_lo, out_hi);
+      const u64* S = P.whole ? m->occ_bits.p : m->tmp_bits.p;
+      if (!P.whole)
+        k_box_and<<<P.grid_box, 256, 0, m->stream>>>(g, b, m->occ_bits.p, m->tmp_bits.p, P.s_lo, P.s_hi);
+      if (step == 2)
+        k_inflate_yz<2><<<P.grid_yz, 256, 0, m->stream>>>(g, step, S, m->tmp2_bits.p, P.t_lo, P.t_hi);
+      else
+        k_inflate_yz<0><<<P.grid_yz, 256, 0, m->stream>>>(g, step, S, m->tmp2_bits.p, P.t_lo, P.t_hi);
+      k_inflate_x<<<P.grid_x, 256, 0, m->stream>>>(g, b, step, m->tmp2_bits.p, m->infl_bits.p, P.out_lo, P.out_hi);
     }
   }
   if (m->cfg.virtual_ceil_height > -0.5) {
@@ -841,6 +883,44 @@ extern "C" int fuelmi_map_inflate_local(fuelmi_map* m) {
 }
 
 extern "C" int fuelmi_map_last_inflate_kernel(const fuelmi_map* m) { return m ? m->last_inflate_kernel : FUELMI_EINVAL; }
+extern "C" int fuelmi_map_set_inflate_kernel(fuelmi_map* m, int kernel) {
+  ARGCHK(m && kernel >= FUELMI_INFLATE_AUTO && kernel <= FUELMI_INFLATE_FACTORED);
+  if (kernel == FUELMI_INFLATE_FUSED && m->info.inflate_step != 2) {
+    fuelmi_set_error("the fused inflation kernel exists for an inflation step of 2 only: this map's is %d", m->info.inflate_step);
+    return FUELMI_EINVAL;
+  }
+  m->inflate_kernel_pin = kernel;
+  return FUELMI_OK;
+}
+extern "C" int fuelmi_map_inflate_plan(const int dims[3], int step, const int lo[3], const int hi[3], int kernel,
+                                       int out[FUELMI_INFLATE_PLAN_INTS]) {
+  ARGCHK(dims && lo && hi && out && kernel >= FUELMI_INFLATE_AUTO && kernel <= FUELMI_INFLATE_FACTORED);
+  ARGCHK(dims[0] > 0 && dims[1] > 0 && dims[2] > 0);
+  const long N = (long)dims[0] * dims[1] * dims[2];
+  if (N >= (1L << 31) - 64 || dims[2] > 255 || step < 0 || step > 31) {  // (fuelmi_map_create's limits)
+    fuelmi_set_error("a map of %d x %d x %d voxels with an inflation step of %d is refused at creation", dims[0], dims[1],
+                     dims[2], step);
+    return FUELMI_ELIMIT;
+  }
+  Geo g;
+  memset(&g, 0, sizeof(g));
+  g.nx = dims[0], g.ny = dims[1], g.nz = dims[2];
+  g.nyz = dims[1] * dims[2];
+  g.N = (int)N;
+  g.W = (int)((N + 63) / 64);
+  Box3 b;
+  for (int i = 0; i < 3; ++i) {
+    ARGCHK(lo[i] >= 0 && lo[i] <= hi[i] && hi[i] < dims[i]);
+    b.lo[i] = lo[i], b.hi[i] = hi[i];
+  }
+  ARGCHK(kernel != FUELMI_INFLATE_FUSED || step == 2);
+  const InflatePlan P = inflate_plan(g, step, b, kernel);
+  const int v[FUELMI_INFLATE_PLAN_INTS] = {P.kernel, P.margin_words, g.W,       P.out_lo,     P.out_hi,   P.t_lo,
+                                           P.t_hi,   P.s_lo,         P.s_hi,    P.whole,      (int)P.lds_f, P.grid_fused,
+                                           P.grid_box, P.grid_yz,    P.grid_x,  0};
+  memcpy(out, v, sizeof(v));
+  return FUELMI_OK;
+}
 
 extern "C" int fuelmi_map_update_esdf(fuelmi_map* m) {
   ARGCHK(m);

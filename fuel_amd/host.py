@@ -299,6 +299,7 @@ class SDFMap:
     """fast_planner::SDFMap with the grid resident in HBM."""
     UNKNOWN, FREE, OCCUPIED = 0, 1, 2
     ESDF_AUTO, ESDF_PLAIN, ESDF_FAR, ESDF_PLAIN32 = -1, 0, 1, 2
+    INFLATE_AUTO, INFLATE_FUSED, INFLATE_FACTORED = -1, 0, 1
     # family every newly created map is pinned to (None: the library's per-update choice); the parity tests run each
     # ESDF test once per family by setting this
     default_esdf_family = None
@@ -374,6 +375,23 @@ class SDFMap:
     def lastInflateKernel(self):
         """0: the fused inflation kernel ran in the last clearAndInflateLocalMap, 1: the factored pair"""
         return self.L.fuelmi_map_last_inflate_kernel(self.h)
+
+    def setInflateKernel(self, kernel):
+        """pin the inflation kernels (INFLATE_AUTO / _FUSED / _FACTORED); both forms compute the same bits.  FUSED exists
+        for an inflation step of 2 only: FuelmiError (FUELMI_EINVAL) on a map with another step"""
+        check(self.L.fuelmi_map_set_inflate_kernel(self.h, int(kernel)))
+
+    @staticmethod
+    def inflatePlan(dims, step, lo, hi, kernel=-1):
+        """The word ranges and launches clearAndInflateLocalMap uses for the box [lo, hi] of a dims grid whose
+        inflate_step is `step` under the pin `kernel` (fuelmi_map_inflate_plan, host only).  "grids": workgroups of 256
+        of the fused kernel, the masking pass, the y/z pass and the x pass; 0 where a kernel does not run."""
+        out = (C.c_int * 16)()
+        check(lib().fuelmi_map_inflate_plan(_i3(dims), int(step), _i3(lo), _i3(hi), int(kernel), out))
+        v = [int(a) for a in out]
+        return {"kernel": v[0], "margin_words": v[1], "W": v[2], "out": (v[3], v[4]), "t": (v[5], v[6]), "s": (v[7], v[8]),
+                "whole": bool(v[9]), "lds": v[10],
+                "grids": {"fused": v[11], "box_and": v[12], "yz": v[13], "x": v[14]}}
 
     def close(self):
         if getattr(self, "h", None):

@@ -185,6 +185,23 @@ int fuelmi_map_esdf_plan(const int dims[3], const int lo[3], const int hi[3], in
 /* which inflation kernels the last fuelmi_map_inflate_local ran: 0 the fused single launch, 1 the factored y/z + x pair
  * (chosen by the size of the box's address range; -1 before the first call).  For tests that must know which code ran. */
 int fuelmi_map_last_inflate_kernel(const fuelmi_map* m);
+/* Pins that choice (tests, A/B runs; both forms compute the same bits).  AUTO (default): by the step and the size of the
+ * box's address range; FUSED: the single launch, which exists for an inflation step of 2 only -- FUELMI_EINVAL on a map
+ * with another step; FACTORED: the y/z + x pair, any step.  The codes are fuelmi_map_last_inflate_kernel's. */
+enum { FUELMI_INFLATE_AUTO = -1, FUELMI_INFLATE_FUSED = 0, FUELMI_INFLATE_FACTORED = 1 };
+int fuelmi_map_set_inflate_kernel(fuelmi_map* m, int kernel);
+/* The word ranges and launches fuelmi_map_inflate_local uses for a box (host only, no device needed; the plan the call
+ * itself runs).  dims: grid voxels; step: the map's inflate_step (0..31); lo / hi: the inclusive box; kernel: a pin as
+ * above.  out[0] = the kernel that runs (0 fused, 1 factored), out[1] = margin words either side of every bit-plane,
+ * out[2] = W (words that cover the grid), out[3..4] = first / last output word, out[5..6] = first / last word of the
+ * y/z-dilated plane the x pass reads, out[7..8] = first / last word of the box-masked source plane, out[9] = 1 if the
+ * box is the whole map (no masking pass), out[10] = dynamic LDS bytes of the fused kernel, out[11] = its grid,
+ * out[12..14] = grids of the masking pass (0 if none), the y/z pass and the x pass (a multiple of 8), out[15] = 0; grids
+ * of the form that does not run are 0.  FUELMI_EINVAL for a box that leaves the grid or FUSED with a step other than 2,
+ * FUELMI_ELIMIT for a grid or a step a map refuses. */
+enum { FUELMI_INFLATE_PLAN_INTS = 16 };
+int fuelmi_map_inflate_plan(const int dims[3], int step, const int lo[3], const int hi[3], int kernel,
+                            int out[FUELMI_INFLATE_PLAN_INTS]);
 /* SDFMap::resetBuffer() (sdf_map.cpp:95-99) and resetBuffer(min,max) (:101-114) */
 int fuelmi_map_reset_buffer_all(fuelmi_map* m);
 int fuelmi_map_reset_buffer(fuelmi_map* m, const double min_pos[3], const double max_pos[3]);

@@ -43,6 +43,12 @@ def test_map_cloud_host_build():
     assert check("map_cloud")[-1].endswith("all identical, sanitizers silent")
 
 
+def test_inflate_host_build():
+    """the inflation kernels and their launch ranges on planes of exactly the allocated size, every scene of
+    tests/inflate_cases.py through the fused kernel and the factored pair, against the oracle"""
+    assert check("inflate")[-1].endswith("all identical, sanitizers silent")
+
+
 def test_kino_host_build():
     if not glob.glob(os.path.join(ROOT, "build", "kino_golden", "*.in")):
         if not os.path.isdir(REF):

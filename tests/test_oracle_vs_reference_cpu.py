@@ -106,6 +106,37 @@ def test_full_box_and_map_face_wrap(tape):
     tape.equal(om.dist, lambda: rm.dist)
 
 
+def test_inflation_steps_other_than_2_match_reference(tape):
+    """Every other test observes the reference at inflate_step 2 (0.199 m at 0.1 m).  Steps 1, 3 and 31 (the device's
+    limit) on a small map with seeds on its corners and face centres, where the stamps wrap across rows and planes and
+    leave [0, N): the full box, then -- on bits left by it -- a sub-box that holds some of the seeds."""
+    res = 0.125
+
+    def corners(d):
+        return [(x, y, z) for x in (0, d[0] - 1) for y in (0, d[1] - 1) for z in (0, d[2] - 1)]
+
+    small, tall = (9, 6, 20), (3, 2, 150)  # (step 31 fills any map whose z-lines are shorter than its stamp)
+    faces = [(0, 3, 10), (8, 3, 10), (4, 0, 10), (4, 5, 10), (4, 3, 0), (4, 3, 19)]
+    for step, dims, seeds, sub in [(1, small, corners(small) + faces, ((0, 2, 5), (4, 5, 19))),
+                                   (3, small, corners(small) + faces, ((0, 2, 5), (4, 5, 19))),
+                                   (31, tall, [(0, 0, 0), (2, 1, 149), (1, 0, 75)], ((0, 0, 60), (1, 1, 149)))]:
+        size = tuple(d * res for d in dims)
+        om, rm = twin(size, (None, None), resolution=res, obstacles_inflation=(step - 0.5) * res, ground_height=0.0)
+        assert om.nvox == dims and int(np.ceil(om.cfg.obstacles_inflation / om.cfg.resolution)) == step
+        tape.equal(om.nvox, lambda: rm.nvox)
+        for m in maps(om, rm):
+            occ = m.occ.reshape(dims)
+            occ[:] = om.l_min
+            for id3 in seeds:
+                occ[id3] = om.l_max
+        for lo, hi in [helpers.full_box(dims), sub]:
+            for m in maps(om, rm):
+                m.set_local_bound(lo, hi)
+                m.inflate_local()
+            assert 0 < om.infl.sum() < om.N
+            tape.equal(om.infl, lambda: rm.infl)
+
+
 @pytest.mark.parametrize("ceil_h", [1.5, 1.55, 2.95])
 def test_virtual_ceiling_matches_reference(tape, ceil_h):
     """clearAndInflateLocalMap's virtual ceiling (sdf_map.cpp:464-471; enabled at 3.2 m by kino_algorithm.xml:75 /
