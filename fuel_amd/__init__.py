@@ -8,4 +8,4 @@ fuel_amd/libfuelmi.so (built by __graft_entry__.build()) and a gfx950 device.
 from ._lib import FuelmiError, LIB_PATH, lib  # noqa: F401
 from .host import (DepthRenderer, DeviceBuffer, RegisteredHostBuffer, BsplineBatchProblem, BsplineOptimizer, NonUniformBspline, EDTEnvironment, FrontierFinder,  # noqa: F401
                    SDFMap, TourSolver, tour_matrix, DEFAULT_BSPLINE, DEFAULT_MAP, SMOOTHNESS, DISTANCE, FEASIBILITY, START,
-                   END, GUIDE, WAYPOINTS, VIEWCONS, MINTIME, GUIDE_PHASE, NORMAL_PHASE, gain_cfg, yawpath_cfg, yawpath_plan)
+                   END, GUIDE, WAYPOINTS, VIEWCONS, MINTIME, GUIDE_PHASE, NORMAL_PHASE, gain_cfg, quad_plan, yawpath_cfg, yawpath_plan)

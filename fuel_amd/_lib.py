@@ -188,6 +188,17 @@ YAW_OK, YAW_DEGENERATE = 0, 1
 YAW_MAX_SEG, YAW_MAX_CTRL = 256, 1024
 
 
+class QuadCfg(C.Structure):
+    """fuelmi_quad_cfg: the cost mask, the dimension, the strides of the control-point and way-point arrays, the number of
+    end rows and whether optimize()'s bounds are checked."""
+    _fields_ = [("cost_function", C.c_int), ("dim", C.c_int), ("max_ctrl", C.c_int), ("end_n", C.c_int),
+                ("max_waypt", C.c_int), ("bounds", C.c_int)]
+
+
+QUAD_OK, QUAD_BOUNDED, QUAD_DEGENERATE = 0, 1, 2
+QUAD_MAX_CTRL = 1024
+
+
 class TrajChkCfg(C.Structure):
     """fuelmi_trajchk_cfg: checkTrajCollision's two literals, the spline's degree and the stride of the control points."""
     _fields_ = [("degree", C.c_int), ("max_ctrl", C.c_int), ("step", C.c_double), ("max_radius", C.c_double)]
@@ -399,6 +410,10 @@ SYMBOLS = {
     "fuelmi_bspline_dev_plan_yaws": (C.c_int, [_P, C.POINTER(YawCfg), _dp, _dp, _ip, _dp, _ip, _dp, _dp, _ip, _dp, _dp,
                                                _dp, _dp, _dp]),
     "fuelmi_yaw_plan": (C.c_int, [C.POINTER(YawCfg), _ip]),
+    "fuelmi_map_solve_quadratic": (C.c_int, [_P, C.POINTER(BsplineCfg), C.POINTER(QuadCfg), C.c_int, _ip, _dp, _dp, _dp, _dp,
+                                             _dp, _ip, _dp, _ip, _ip, _dp, _dp, _dp]),
+    "fuelmi_bspline_dev_solve_quadratic": (C.c_int, [_P, C.POINTER(QuadCfg), _dp, _ip, _dp, _dp, _dp]),
+    "fuelmi_quad_plan": (C.c_int, [C.POINTER(QuadCfg), _ip]),
     "fuelmi_map_check_trajs": (C.c_int, [_P, C.POINTER(TrajChkCfg), C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _dp, _ip, _ip, _dp,
                                          _dp, _ip, _dp]),
     "fuelmi_bspline_dev_check_trajs": (C.c_int, [_P, C.POINTER(TrajChkCfg), _dp, _ip, _ip, _dp, _ip, _ip, _dp, _dp, _ip, _dp]),

@@ -928,7 +928,7 @@ extern "C" void fuelmi_bspline_dev_destroy(fuelmi_bspline_dev* b) {
       }
   }
   for (void* p : b->allocs) (void)hipFree(p);
-  for (DevScratch* sc : {&b->fit_in, &b->yaw_dev, &b->chk_dev, &b->smp_dev, &b->adj_dev}) sc->release();
+  for (DevScratch* sc : {&b->fit_in, &b->yaw_dev, &b->chk_dev, &b->smp_dev, &b->adj_dev, &b->quad_dev}) sc->release();
   for (int k = 0; k < 2; ++k) {
     if (b->pin_out[k]) (void)hipHostFree(b->pin_out[k]);
     if (b->ev_out[k]) (void)hipEventDestroy(b->ev_out[k]);

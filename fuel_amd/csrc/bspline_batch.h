@@ -49,6 +49,7 @@ struct fuelmi_bspline_dev {
   DevScratch chk_dev;  // fuelmi_bspline_dev_check_trajs: t_now | results
   DevScratch smp_dev;  // fuelmi_bspline_dev_sample_trajs: yaw splines, times | results
   DevScratch adj_dev;  // fuelmi_bspline_dev_adjust_trajs: knots, ratios, groups | results
+  DevScratch quad_dev; // fuelmi_bspline_dev_solve_quadratic: guide points | results
 };
 
 struct FitArgs {

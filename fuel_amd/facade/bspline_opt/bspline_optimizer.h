@@ -188,6 +188,24 @@ public:
   bool reparamLocalTraj(const GlobalTrajState& state, double start_t, double duration, const std::vector<double>& dts,
                         std::vector<LocalSegment>& out);
 
+  // addition: the exact solve of the quadratic phases (fuelmi_map_solve_quadratic, include/fuelmi.h).  With the parameter
+  // optimization/exact_quadratic set (default false: nothing changes), optimize() sends a cost mask without DISTANCE,
+  // FEASIBILITY, VIEWCONS or MINTIME there -- the minimiser the phase is defined to reach instead of the iteration's best
+  // of max_iteration_num evaluations -- and falls back to the iteration when the problem's status is FUELMI_QUAD_BOUNDED
+  // or FUELMI_QUAD_DEGENERATE.  exact_status_ says what the last optimize() did: -1 the iteration alone, otherwise the
+  // exact solve's status.
+  // optimizeGuidePhase is the first phase of optimizeTopoBspline (plan_manage/src/planner_manager.cpp:584-588) for ALL
+  // guide paths in one device call, each with its own number of control points (rows of ctrl_pts[i], knot span dts[i],
+  // start / end states as setBoundaryStates takes them, guide[i] as setGuidePath takes it: rows - 2 bspline_degree
+  // points).  ctrl_pts[i] is replaced where status[i] is FUELMI_QUAD_OK; the others are left for optimize().  Returns
+  // false, and touches no output, when the call fails.
+  bool exact_quadratic_ = false;
+  int exact_status_ = -1;
+  bool optimizeGuidePhase(std::vector<Eigen::MatrixXd>& ctrl_pts, const std::vector<double>& dts,
+                          const std::vector<vector<Eigen::Vector3d>>& start, const std::vector<vector<Eigen::Vector3d>>& end,
+                          const std::vector<vector<Eigen::Vector3d>>& guide, std::vector<int>& status,
+                          std::vector<double>& cost);
+
   Eigen::MatrixXd getControlPoints();
   vector<Eigen::Vector3d> matrixToVectors(const Eigen::MatrixXd& ctrl_pts);
 
@@ -207,6 +225,7 @@ public:
 
 private:
   bool isQuadratic();
+  bool solveExact();  // optimize()'s exact route: true when it took the problem
 
   // environment and parameters
   shared_ptr<EDTEnvironment> edt_environment_;

@@ -969,6 +969,7 @@ void BsplineOptimizer::setParam(ros::NodeHandle& nh) {
   nh.param("optimization/algorithm2", algorithm2_, -1);
   nh.param("manager/bspline_degree", bspline_degree_, 3);
   cfg_.bspline_degree = bspline_degree_;
+  nh.param("optimization/exact_quadratic", exact_quadratic_, false);
   time_lb_ = -1;
   static bool told = false;
   if (!told && (algorithm1_ >= 0 || algorithm2_ >= 0)) {
@@ -1098,6 +1099,8 @@ void BsplineOptimizer::optimize() {
   // evaluation cap and xtol_rel as the reference configures them; box-projected L-BFGS in place of
   // NLopt's LD_LBFGS / LD_TNEWTON).  max_iteration_time_ is the solver's wall-clock cap (set_maxtime, :170-172):
   // the device checks its clock between evaluations and returns the best variables seen when it runs out.
+  exact_status_ = -1;
+  if (exact_quadratic_ && solveExact()) return;
   const int n = variable_num_;
   std::vector<double> q(n);
   for (int i = 0; i < point_num_; ++i)
@@ -1122,6 +1125,98 @@ void BsplineOptimizer::optimize() {
   for (int i = 0; i < point_num_; ++i)
     for (int j = 0; j < dim_; ++j) control_points_(i, j) = best_variable_[dim_ * i + j];
   if (optimize_time_) knot_span_ = best_variable_[n - 1];
+}
+
+// optimization/exact_quadratic: a mask whose every term is quadratic goes to fuelmi_map_solve_quadratic (one problem);
+// anything but FUELMI_QUAD_OK leaves the problem to the iteration
+bool BsplineOptimizer::solveExact() {
+  const int quad = SMOOTHNESS | START | END | GUIDE | WAYPOINTS;
+  if (cost_function_ == 0 || (cost_function_ & ~quad) || (dim_ != 1 && dim_ != 3)) return false;
+  const int N = point_num_, dim = dim_, nw = (int)waypoints_.size();
+  fuelmi_quad_cfg qc = {cost_function_, dim, N, (int)std::max<size_t>(1, std::min<size_t>(3, end_state_.size())), nw, dim == 3};
+  std::vector<double> q((size_t)N * dim), st(3 * dim, 0.0), en(3 * dim, 0.0), guide, wp((size_t)nw * dim), out((size_t)N * dim);
+  for (int i = 0; i < N; ++i)
+    for (int j = 0; j < dim; ++j) q[dim * i + j] = control_points_(i, j);
+  for (size_t i = 0; i < start_state_.size() && i < 3; ++i)
+    for (int k = 0; k < dim; ++k) st[dim * i + k] = start_state_[i](k);
+  for (size_t i = 0; i < end_state_.size() && i < 3; ++i)
+    for (int k = 0; k < dim; ++k) en[dim * i + k] = end_state_[i](k);
+  const int n_guide = std::max(N - 2 * order_, 0);
+  if (cost_function_ & GUIDE) {
+    if ((int)guide_pts_.size() < n_guide) return false;
+    for (int i = 0; i < n_guide; ++i)
+      for (int k = 0; k < dim; ++k) guide.push_back(guide_pts_[i](k));
+  }
+  for (int i = 0; i < nw; ++i)
+    for (int k = 0; k < dim; ++k) wp[dim * i + k] = waypoints_[i](k);
+  if ((cost_function_ & WAYPOINTS) && (int)waypt_idx_.size() < nw) return false;
+  int status = -1;
+  double cost = 0.0, ptd = 0.0;
+  auto t1 = std::chrono::steady_clock::now();
+  const int rc = fuelmi_map_solve_quadratic(edt_environment_->sdf_map_->device(), &cfg_, &qc, 1, &N, q.data(), &knot_span_,
+                                            st.data(), en.data(), guide.empty() ? nullptr : guide.data(), &nw,
+                                            wp.empty() ? nullptr : wp.data(), waypt_idx_.empty() ? nullptr : waypt_idx_.data(),
+                                            &status, out.data(), &cost, &ptd);
+  comb_time += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+  if (rc) return false;  // (an input the exact route refuses is the iteration's to judge)
+  exact_status_ = status;
+  if (status != FUELMI_QUAD_OK) return false;
+  iter_num_ = 0;
+  min_cost_ = cost;
+  best_variable_ = out;
+  for (int i = 0; i < N; ++i)
+    for (int j = 0; j < dim; ++j) control_points_(i, j) = out[dim * i + j];
+  return true;
+}
+
+bool BsplineOptimizer::optimizeGuidePhase(std::vector<Eigen::MatrixXd>& ctrl_pts, const std::vector<double>& dts,
+                                          const std::vector<vector<Eigen::Vector3d>>& start,
+                                          const std::vector<vector<Eigen::Vector3d>>& end,
+                                          const std::vector<vector<Eigen::Vector3d>>& guide, std::vector<int>& status,
+                                          std::vector<double>& cost) {
+  const size_t n = ctrl_pts.size();
+  if (dts.size() != n || start.size() != n || end.size() != n || guide.size() != n) return false;
+  int maxc = 4, end_n = 3;
+  for (size_t b = 0; b < n; ++b) {
+    if (ctrl_pts[b].cols() != 3 || start[b].size() < 3 || end[b].empty()) return false;
+    maxc = std::max(maxc, (int)ctrl_pts[b].rows());
+    end_n = b ? end_n : (int)std::min<size_t>(3, end[b].size());
+    if ((int)std::min<size_t>(3, end[b].size()) != end_n) return false;  // (one call shares the number of end rows)
+    if ((int)guide[b].size() < (int)ctrl_pts[b].rows() - 2 * bspline_degree_) return false;
+  }
+  const size_t maxg = (size_t)std::max(maxc - 2 * bspline_degree_, 0);
+  fuelmi_quad_cfg qc = {GUIDE_PHASE, 3, maxc, end_n, 0, 1};
+  std::vector<int> nc(n), st_out(n);
+  std::vector<double> q(n * maxc * 3, 0.0), st(n * 9, 0.0), en(n * 9, 0.0), g(n * maxg * 3 + 1, 0.0), out(n * maxc * 3), c(n), pd(n);
+  for (size_t b = 0; b < n; ++b) {
+    nc[b] = (int)ctrl_pts[b].rows();
+    for (int i = 0; i < nc[b]; ++i)
+      for (int k = 0; k < 3; ++k) q[(b * maxc + i) * 3 + k] = ctrl_pts[b](i, k);
+    for (int i = 0; i < 3; ++i)
+      for (int k = 0; k < 3; ++k) {
+        st[b * 9 + 3 * i + k] = start[b][i](k);
+        if (i < end_n) en[b * 9 + 3 * i + k] = end[b][i](k);
+      }
+    for (int i = 0; i < nc[b] - 2 * bspline_degree_; ++i)
+      for (int k = 0; k < 3; ++k) g[(b * maxg + i) * 3 + k] = guide[b][i](k);
+  }
+  if (n == 0) {
+    status.clear(), cost.clear();
+    return true;
+  }
+  const int rc = fuelmi_map_solve_quadratic(edt_environment_->sdf_map_->device(), &cfg_, &qc, (int)n, nc.data(), q.data(),
+                                            dts.data(), st.data(), en.data(), g.data(), nullptr, nullptr, nullptr,
+                                            st_out.data(), out.data(), c.data(), pd.data());
+  if (rc) {
+    warn("fuelmi_map_solve_quadratic", rc);
+    return false;
+  }
+  for (size_t b = 0; b < n; ++b)
+    if (st_out[b] == FUELMI_QUAD_OK)
+      for (int i = 0; i < nc[b]; ++i)
+        for (int k = 0; k < 3; ++k) ctrl_pts[b](i, k) = out[(b * maxc + i) * 3 + k];
+  status = st_out, cost = c;
+  return true;
 }
 
 int BsplineOptimizer::planThroughWaypoints(const vector<Eigen::Vector3d>& tour, const Eigen::Vector3d& cur_vel,

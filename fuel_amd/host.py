@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BsplineBatch, BsplineCfg, CloudCfg, ColRangeCfg, FrontierCfg, GainCfg, GoalCfg, KinoCfg, LocalSegCfg, MapCfg, MapInfo, PathCfg, RefineCfg, RenderCfg, TopoCfg, TrajAdjCfg, TrajChkCfg, TrajSmpCfg, TspCfg,
+from ._lib import (BsplineBatch, BsplineCfg, CloudCfg, ColRangeCfg, FrontierCfg, GainCfg, GoalCfg, KinoCfg, LocalSegCfg, MapCfg, MapInfo, PathCfg, QuadCfg, RefineCfg, RenderCfg, TopoCfg, TrajAdjCfg, TrajChkCfg, TrajSmpCfg, TspCfg,
                    WptrajCfg, YawCfg, YawPathCfg, check, lib)
 
 # exploration.launch / algorithm.xml defaults (exploration_manager/launch/algorithm.xml:33-59,170-181)
@@ -62,6 +62,15 @@ def yaw_cfg(mode=0, pos_degree=3, max_ctrl=4, max_seg=None, seg_num=12, lookfwd=
         max_seg = seg_num if mode == _lib.YAW_EXPLORE else _lib.YAW_MAX_SEG
     return YawCfg(int(mode), int(pos_degree), int(max_ctrl), int(max_seg), int(seg_num), 1 if lookfwd else 0,
                   float(relax_time), float(forward_t), float(dt_target), float(end_back))
+
+
+def quad_plan(cost_function=SMOOTHNESS | GUIDE | START | END, dim=3, max_ctrl=4, end_n=3, max_waypt=0, bounds=False):
+    """(lanes per problem, LDS bytes, largest max_ctrl accepted) of the quadratic solve's kernel (fuelmi_quad_plan); host
+    only"""
+    out = (C.c_int * 3)()
+    check(lib().fuelmi_quad_plan(C.byref(QuadCfg(int(cost_function), int(dim), int(max_ctrl), int(end_n), int(max_waypt),
+                                                 1 if bounds else 0)), out))
+    return tuple(out)
 
 
 def kino_cfg(max_tau=0.8, init_max_tau=1.0, max_vel=2.25, max_acc=2.0, w_time=10.0, horizon=5.0, resolution=0.025,
@@ -1044,6 +1053,55 @@ class SDFMap:
         check(lib().fuelmi_yaw_plan(C.byref(cfg), out))
         return tuple(out)
 
+    # --- the exact solve of the optimiser's quadratic phases (include/fuelmi.h fuelmi_map_solve_quadratic) ---
+    QUAD_OK, QUAD_BOUNDED, QUAD_DEGENERATE = _lib.QUAD_OK, _lib.QUAD_BOUNDED, _lib.QUAD_DEGENERATE
+
+    def solve_quadratic(self, ctrl, knot_span, cost_function=GUIDE_PHASE, start_state=None, end_state=None, end_n=3,
+                        guide_pts=None, waypoints=None, waypt_idx=None, weights=None, bounds=False, dim=3, max_ctrl=None,
+                        max_waypt=None):
+        """The minimiser of optimize()'s objective for a mask within SMOOTHNESS | START | END | GUIDE | WAYPOINTS, per
+        problem: ctrl is a list of [n_ctrl, dim] control-point arrays (each its own length), knot_span [n], start_state /
+        end_state [n, 3, dim], guide_pts a list of [n_ctrl - 2 order, dim] arrays, waypoints / waypt_idx lists of [k, dim] /
+        [k] arrays.  weights: a BsplineCfg or a dict of its fields (default: the launch file's).  Returns a dict: status [n],
+        ctrl (a list of [n_ctrl, dim] arrays), ctrl_out [n, max_ctrl, dim], cost [n], pt_dist [n]."""
+        dim = int(dim)
+        cs = [np.ascontiguousarray(c, dtype=np.float64).reshape(-1, dim) for c in ctrl]
+        n = len(cs)
+        maxc = int(max_ctrl) if max_ctrl is not None else max([len(c) for c in cs] + [4])
+        w = weights if isinstance(weights, BsplineCfg) else BsplineCfg(**dict(DEFAULT_BSPLINE, **(weights or {})))
+        order = 3 if dim == 1 else int(w.bspline_degree)
+        maxg = max(maxc - 2 * order, 0)
+
+        def pack(rows, width, dtype=np.float64, cols=dim):
+            """a list of per-problem [k, cols] arrays as ([n, width, cols], the counts)"""
+            shape = (n, max(width, 0), cols) if cols else (n, max(width, 0))
+            arr = np.zeros(shape, dtype=dtype)
+            cnt = np.zeros(n, dtype=np.int32)
+            for b, r in enumerate(rows or []):
+                r = np.ascontiguousarray(r, dtype=dtype).reshape((-1, cols) if cols else (-1,))
+                cnt[b] = len(r)
+                k = min(len(r), arr.shape[1])  # (a problem longer than the stride: the call refuses it by its count)
+                arr[b, :k] = r[:k]
+            return arr, cnt
+        carr, n_ctrl = pack(cs, maxc)
+        knot = np.ascontiguousarray(np.broadcast_to(np.asarray(knot_span, dtype=np.float64), (n,)))
+        st = None if start_state is None else np.ascontiguousarray(start_state, dtype=np.float64).reshape(n, 3, dim)
+        en = None if end_state is None else np.ascontiguousarray(end_state, dtype=np.float64).reshape(n, 3, dim)
+        garr = None if guide_pts is None else pack(guide_pts, maxg)[0]
+        maxw = int(max_waypt) if max_waypt is not None else max([len(np.atleast_1d(i)) for i in (waypt_idx or [])] + [0])
+        warr = n_w = iarr = None
+        if waypoints is not None:
+            warr, n_w = pack(waypoints, maxw)
+            iarr = pack(waypt_idx, maxw, np.int32, 0)[0]
+        c = QuadCfg(int(cost_function), dim, maxc, int(end_n), maxw, 1 if bounds else 0)
+        o = dict(status=np.zeros(n, dtype=np.int32), ctrl_out=np.zeros((n, max(maxc, 0), dim)), cost=np.zeros(n),
+                 pt_dist=np.zeros(n))
+        check(self.L.fuelmi_map_solve_quadratic(self.h, C.byref(w), C.byref(c), n, _ip(n_ctrl), _dp(carr), _dp(knot), _dp(st),
+                                                _dp(en), _dp(garr), _ip(n_w), _dp(warr), _ip(iarr), _ip(o["status"]),
+                                                _dp(o["ctrl_out"]), _dp(o["cost"]), _dp(o["pt_dist"])))
+        o["ctrl"] = [o["ctrl_out"][b, :len(cs[b])] for b in range(n)]
+        return o
+
     # --- the safety check of flown trajectories (include/fuelmi.h fuelmi_map_check_trajs) ---
     def check_trajs(self, pos_ctrl, knot_span, t_now, allow_limit=False, max_ctrl=None, **cfg):
         """checkTrajCollision per problem against the inflated plane on the device: pos_ctrl is a list of [n_ctrl, 3]
@@ -1830,6 +1888,24 @@ class BsplineDeviceProblem:
         if not (allow_limit and rc == -5):
             check(rc)
         o["limit"] = rc == -5
+        return o
+
+    def solve_quadratic(self, cost_function=GUIDE_PHASE, guide_pts=None, bounds=False):
+        """The exact minimiser of a quadratic mask on what the batch holds (fuelmi_bspline_dev_solve_quadratic); the
+        solution of every QUAD_OK candidate becomes the batch's variables, the next optimize() starts from it.  guide_pts
+        [C, point_num - 2 order, 3]: this phase's guide points (None: the batch's own).  Returns a dict: status [C], ctrl_out
+        [C, point_num, dim], cost [C], pt_dist [C]."""
+        c = self.problem.c
+        n = c.n_traj
+        g = None if guide_pts is None else np.ascontiguousarray(guide_pts, dtype=np.float64)
+        order = 3 if c.dim == 1 else self.degree
+        if g is not None and g.size != n * max(c.point_num - 2 * order, 0) * 3:
+            raise ValueError("solve_quadratic: guide_pts [C][point_num - 2 order][3]")
+        qc = QuadCfg(int(cost_function), c.dim, c.point_num, max(c.end_n, 1), c.n_waypt, 1 if bounds else 0)
+        o = dict(status=np.zeros(n, dtype=np.int32), ctrl_out=np.zeros((n, c.point_num, c.dim)), cost=np.zeros(n),
+                 pt_dist=np.zeros(n))
+        check(self.L.fuelmi_bspline_dev_solve_quadratic(self.h, C.byref(qc), _dp(g), _ip(o["status"]), _dp(o["ctrl_out"]),
+                                                        _dp(o["cost"]), _dp(o["pt_dist"])))
         return o
 
     def check_trajs(self, t_now, allow_limit=False, **cfg):

@@ -866,6 +866,88 @@ int fuelmi_bspline_dev_plan_yaws(fuelmi_bspline_dev* b, const fuelmi_yaw_cfg* cf
 int fuelmi_yaw_plan(const fuelmi_yaw_cfg* cfg, int out3[3]);
 
 /* ------------------------------------------------------------------------------------------
+ * Exact solve of the optimiser's quadratic phases: BsplineOptimizer::optimize() (bspline_opt/src/bspline_optimizer.cpp:
+ * 110-253) for a cost mask within SMOOTHNESS | START | END | GUIDE | WAYPOINTS, for n_prob independent problems in one
+ * call, EACH WITH ITS OWN NUMBER OF CONTROL POINTS.  These are the reference's isQuadratic() masks (:738-747: GUIDE_PHASE,
+ * SMOOTHNESS, SMOOTHNESS | WAYPOINTS) and the yaw objective SMOOTHNESS | WAYPOINTS | START | END.
+ * Per problem, with N control points of dimension dim, the knot span dt fixed and everything f64 in this order:
+ *   1. pt_dist = (sum |q[i+1] - q[i]|) / N from the input as given, not clamped (:136-140).
+ *   2. with pt_dist frozen, every term of combineCost (:571-630) is c (a . q - b)^2 over at most four neighbouring
+ *      control points, the same a for every axis:
+ *        jerk rows (-1, 3, -3, 1) / pt_dist, i = 0 .. N-4, weight ld_smooth                               (:263-266)
+ *        start rows: position (1, 4, 1)/6 with the literal weight 10, velocity (-1, 0, 1)/(2 dt), acceleration
+ *        (1, -2, 1)/dt^2, weight ld_start                                                                  (:369-389)
+ *        end rows: the first end_n of the same three on the last three control points, weight ld_end      (:407-430)
+ *        guide rows: a unit row per guide point, i = order .. N-order-1, order = bspline_degree for dim 3 and 3 for
+ *        dim 1 (:124-127), weight ld_guide; none when N <= 2 order                                        (:468-474)
+ *        way-point rows (1, 4, 1)/6 at waypt_idx, weight ld_waypt; a repeated index is legal and adds up  (:442-456)
+ *      ctrl_out = THE MINIMISER: H q = g with H = sum c a a^T symmetric of half-bandwidth 3, shared by the axes,
+ *      factored once by a banded Cholesky, one substitution per axis.  cost = combineCost at ctrl_out, summed in the
+ *      reference's order.
+ *   3. bounds (dim 3 with cfg.bounds != 0): q0 = the input clamped into the map's box shrunk by 0.1 (:174-202), lb / ub =
+ *      q0 -+ 10 cut to that box (:206-214).  The unconstrained minimiser is the reference's constrained one only if
+ *      lb <= q <= ub holds in every coordinate; otherwise the status is FUELMI_QUAD_BOUNDED.  dim 1 has no bounds (:206).
+ * THE REFERENCE'S ITERATE IS NOT REPRODUCED.  The reference runs GUIDE_PHASE with NLopt LD_TNEWTON, max_iteration_num1 = 2
+ * and 0.1 ms (exploration_manager/launch/algorithm.xml:182-189): it keeps the better of two evaluations.  This call
+ * returns the point that phase is defined to reach; its cost is never above the iteration's, except by rounding.
+ * Per-problem status:
+ *   FUELMI_QUAD_OK.
+ *   FUELMI_QUAD_BOUNDED     ctrl_out = q0, cost = the objective at q0: the caller falls back to the iterative route
+ *                           (fuelmi_bspline_optimize).
+ *   FUELMI_QUAD_DEGENERATE  pt_dist is 0 or not finite while SMOOTHNESS is set, or a Cholesky pivot is <= 0 or not finite
+ *                           (SMOOTHNESS alone, whose null space is the quadratics), or the cost is not finite: ctrl_out =
+ *                           the input, cost = 0.  Also (device batches only, the host route refuses them): a knot span
+ *                           that is not finite and > 0 -- then ctrl_out and pt_dist are 0 -- or a way-point index outside
+ *                           [0, N-3].
+ * Entries of ctrl_out past N are written as 0.  pt_dist is reported for every status.
+ * Checked on the host before anything is launched (FUELMI_EINVAL): pointers the mask reads; a mask that is empty or has a
+ * bit outside the five; dim 1 or 3; bspline_degree in 3..5 for dim 3; max(4, order + 1) <= n_ctrl[i] <= max_ctrl; end_n in
+ * 1..3; 0 <= n_waypt[i] <= max_waypt, 0 <= waypt_idx <= N - 3; every input the mask reads finite with |value| < 1e7; knot
+ * spans finite and > 0; the weights the mask reads finite and >= 0.  max_ctrl > FUELMI_QUAD_MAX_CTRL: FUELMI_ELIMIT (one
+ * problem's LDS is 14 max_ctrl + 16 doubles at dim 3; the 160 KiB budget holds 1462 control points, the cap is the power
+ * of two below, as for the yaw entry).  n_prob = 0 is FUELMI_OK.
+ * fuelmi_map_solve_quadratic runs on a query slot of the map like fuelmi_map_plan_yaws: host arrays in and out,
+ * synchronous, re-entrant, no device allocation once warm; a result does not depend on the problem's place in the batch.
+ * ---------------------------------------------------------------------------------------- */
+#define FUELMI_QUAD_OK 0
+#define FUELMI_QUAD_BOUNDED 1
+#define FUELMI_QUAD_DEGENERATE 2
+#define FUELMI_QUAD_MAX_CTRL 1024  /* largest max_ctrl (control points per problem) */
+typedef struct {
+  int cost_function;   /* FUELMI_COST_* within SMOOTHNESS | START | END | GUIDE | WAYPOINTS */
+  int dim;             /* 1 or 3 */
+  int max_ctrl;        /* stride of ctrl / ctrl_out; guide_pts holds max(max_ctrl - 2 order, 0) rows per problem */
+  int end_n;           /* end_state_.size(): 1..3 */
+  int max_waypt;       /* stride of waypoints / waypt_idx */
+  int bounds;          /* dim 3: != 0 checks the minimiser against optimize()'s bounds */
+} fuelmi_quad_cfg;
+/* w: ld_smooth, ld_start, ld_end, ld_guide, ld_waypt and bspline_degree are read.  ctrl [n_prob][max_ctrl][dim],
+ * knot_span [n_prob], start_state / end_state [n_prob][3][dim] (position, velocity, acceleration), guide_pts
+ * [n_prob][max(max_ctrl - 2 order, 0)][dim] (problem i reads its first n_ctrl[i] - 2 order rows), n_waypt [n_prob],
+ * waypoints [n_prob][max_waypt][dim], waypt_idx [n_prob][max_waypt]; an array the mask does not read may be NULL.
+ * Out, per problem: status, ctrl_out [n_prob][max_ctrl][dim], cost, pt_dist. */
+int fuelmi_map_solve_quadratic(fuelmi_map* m, const fuelmi_bspline_cfg* w, const fuelmi_quad_cfg* cfg, int n_prob,
+                               const int* n_ctrl, const double* ctrl, const double* knot_span, const double* start_state,
+                               const double* end_state, const double* guide_pts, const int* n_waypt,
+                               const double* waypoints, const int* waypt_idx, int* status, double* ctrl_out, double* cost,
+                               double* pt_dist);
+/* The same kernel on what a device batch holds (fuelmi_bspline_dev_create): one problem per candidate, its variables,
+ * knot span, states, way-points and weights the batch's; only cfg->cost_function and cfg->bounds are read (dim, the point
+ * count, end_n and the way-point count are the batch's).  guide_pts [C][point_num - 2 order][3]: the guide points of this
+ * phase, or NULL for the batch's own (a NORMAL_PHASE batch holds none).  The batch must not optimise the knot span
+ * (MINTIME): FUELMI_EINVAL.  The solution of every FUELMI_QUAD_OK candidate becomes the candidate's variables and its
+ * pt_dist_ the candidate's, as optimize() sets both up for its next phase (:116, :136-140): the next
+ * fuelmi_bspline_dev_optimize starts from it, and equals fuelmi_bspline_optimize on ctrl_out with that pt_dist_.  A
+ * candidate of another status keeps its state.  The call clears the flag fuelmi_bspline_dev_plan_yaws / _check_trajs
+ * test (the last solve's variables are no longer the batch's).  ctrl_out [C][point_num][dim].  Runs on the map's stream
+ * and waits for it. */
+int fuelmi_bspline_dev_solve_quadratic(fuelmi_bspline_dev* b, const fuelmi_quad_cfg* cfg, const double* guide_pts,
+                                       int* status, double* ctrl_out, double* cost, double* pt_dist);
+/* what the kernel needs for cfg->max_ctrl and cfg->dim (host only, no device needed): out3 = {lanes per problem, dynamic
+ * LDS bytes, largest max_ctrl accepted}.  The mask, dim, end_n, max_waypt and max_ctrl are checked like above. */
+int fuelmi_quad_plan(const fuelmi_quad_cfg* cfg, int out3[3]);
+
+/* ------------------------------------------------------------------------------------------
  * Kinodynamic search for the mid-range goal branch: KinodynamicAstar::search + getSamples
  * (path_searching/src/kinodynamic_astar.cpp:15-263, 543-634) as FastPlannerManager::kinodynamicReplan calls them
  * (plan_manage/src/planner_manager.cpp:124-164) for n_prob independent problems (start position / velocity /
