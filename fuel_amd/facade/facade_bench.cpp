@@ -4,69 +4,18 @@
 // the host mirrors the callers' inline getters read switched on and off, beside the same sequence issued
 // straight at the C-ABI.  Scenario file as facade_demo's: header + point-cloud frames.
 //   facade_bench <scenario.bin> [repeat]
-#include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <string>
-#include <vector>
+#include "facade_driver.h"
 
-#include <plan_env/sdf_map.h>
-#include <plan_env/edt_environment.h>
 #include <active_perception/frontier_finder.h>
-#include <active_perception/graph_node.h>
-#include <active_perception/perception_utils.h>
 #include <bspline_opt/bspline_optimizer.h>
 
-#include <algorithm>
 #include <thread>
 
-namespace fast_planner {
-double ViewNode::computeCost(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, const double& y1, const double& y2,
-                             const Eigen::Vector3d&, const double&, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm() + 0.1 * std::fabs(y2 - y1);
-}
-double ViewNode::searchPath(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm();
-}
-PerceptionUtils::PerceptionUtils(ros::NodeHandle&) {}
-class MapROS {
-public:
-  static void inflate(SDFMap& m) { m.clearAndInflateLocalMap(); }
-};
-}  // namespace fast_planner
-using namespace fast_planner;
-
-struct Frame {
-  pcl::PointCloud<pcl::PointXYZ> cloud;
-  std::vector<float> xyz;
-  double cam[3];
-};
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-template <typename T>
-static void rd(FILE* f, T* p, size_t n) {
-  if (fread(p, sizeof(T), n, f) != n) {
-    std::fprintf(stderr, "short read\n");
-    std::exit(2);
-  }
-}
 
 static void params(ros::NodeHandle& nh, const double* hdr) {
-  auto& P = nh.num;
-  P["sdf_map/resolution"] = 0.1;
-  P["sdf_map/map_size_x"] = hdr[0], P["sdf_map/map_size_y"] = hdr[1], P["sdf_map/map_size_z"] = hdr[2];
-  P["sdf_map/obstacles_inflation"] = 0.199, P["sdf_map/local_bound_inflate"] = 0.5, P["sdf_map/ground_height"] = -1.0;
-  P["sdf_map/default_dist"] = 0.0, P["sdf_map/optimistic"] = 0, P["sdf_map/signed_dist"] = 0;
-  P["sdf_map/p_hit"] = 0.65, P["sdf_map/p_miss"] = 0.35, P["sdf_map/p_min"] = 0.12, P["sdf_map/p_max"] = 0.90;
-  P["sdf_map/p_occ"] = 0.80, P["sdf_map/max_ray_length"] = 4.5, P["sdf_map/virtual_ceil_height"] = -10;
-  const char* ax[3] = {"x", "y", "z"};
-  for (int i = 0; i < 3; ++i) {
-    P[std::string("sdf_map/box_min_") + ax[i]] = hdr[3 + i];
-    P[std::string("sdf_map/box_max_") + ax[i]] = hdr[6 + i];
-  }
-  P["frontier/cluster_min"] = hdr[9];
+  sdf_map_params(nh, hdr, hdr + 3, hdr + 6);
+  nh.num["frontier/cluster_min"] = hdr[9];
 }
 
 // one pass over the frames through the facade; returns seconds per cycle
@@ -75,16 +24,13 @@ static double run_facade(const double* hdr, const std::vector<Frame>& frames, bo
   ros::NodeHandle nh;
   params(nh, hdr);
   if (ref_order >= 0) nh.num["frontier/reference_order"] = ref_order;
-  SDFMap::Ptr map(new SDFMap);
-  map->initMap(nh);
-  map->setHostMirror(mirrors, mirrors, mirrors);
-  EDTEnvironment::Ptr edt(new EDTEnvironment);
-  edt->setMap(map);
-  FrontierFinder ff(edt, nh);
+  const DriverMap dm = make_map(nh, !mirrors);
+  const SDFMap::Ptr& map = dm.map;
+  FrontierFinder ff(dm.edt, nh);
   fuelmi_map_synchronize(map->device());
   const double t0 = now_s();
   for (const Frame& f : frames) {
-    map->inputPointCloud(f.cloud, (int)f.cloud.points.size(), Eigen::Vector3d(f.cam[0], f.cam[1], f.cam[2]));
+    f.fuse(*map);
     MapROS::inflate(*map);
     map->updateESDF3d();
     ff.searchFrontiers();
@@ -141,18 +87,11 @@ static double run_fullbox(const double* hdr, const std::vector<double>& occ, boo
                           size_t* n_cells) {
   ros::NodeHandle nh;
   params(nh, hdr);
-  SDFMap::Ptr map(new SDFMap);
-  map->initMap(nh);
-  map->setHostMirror(mirrors, mirrors, mirrors);
-  EDTEnvironment::Ptr edt(new EDTEnvironment);
-  edt->setMap(map);
-  FrontierFinder ff(edt, nh);
+  const DriverMap dm = make_map(nh, !mirrors);
+  const SDFMap::Ptr& map = dm.map;
+  FrontierFinder ff(dm.edt, nh);
   fuelmi_map* dev = map->device();
-  if (fuelmi_map_upload_occupancy(dev, occ.data()) != FUELMI_OK) return -1.0;
-  fuelmi_map_info inf;
-  fuelmi_map_get_info(dev, &inf);
-  const int lo[3] = {0, 0, 0}, hi[3] = {inf.voxel_num[0] - 1, inf.voxel_num[1] - 1, inf.voxel_num[2] - 1};
-  fuelmi_map_set_local_bound(dev, lo, hi);
+  upload_occupancy(*map, occ, LOAD_BOUND);
   std::vector<std::vector<Eigen::Vector3d>> cl;
   double t0 = 0.0;
   for (int k = -3; k < cycles; ++k) {  // three untimed cycles first
@@ -185,30 +124,16 @@ static double run_fullbox(const double* hdr, const std::vector<double>& occ, boo
 static void run_candidate(const double* hdr, const std::vector<double>& occ, double out[4]) {
   ros::NodeHandle nh;
   params(nh, hdr);
-  auto& P = nh.num;
-  P["optimization/ld_smooth"] = 20.0, P["optimization/ld_dist"] = 10.0, P["optimization/ld_feasi"] = 2.0;
-  P["optimization/ld_start"] = 100.0, P["optimization/ld_end"] = 0.5, P["optimization/ld_guide"] = 1.5;
-  P["optimization/ld_waypt"] = 0.3, P["optimization/ld_view"] = 0.0, P["optimization/ld_time"] = 1.0;
-  P["optimization/dist0"] = 0.7, P["optimization/max_vel"] = 2.0, P["optimization/max_acc"] = 2.0;
-  P["optimization/dlmin"] = 0.0, P["optimization/wnl"] = 1.0;
-  for (int i = 1; i <= 4; ++i) {
-    P["optimization/max_iteration_num" + std::to_string(i)] = 300;   // algorithm.xml:184-191
-    P["optimization/max_iteration_time" + std::to_string(i)] = 0.005;
+  optimization_params(nh);
+  for (int i = 1; i <= 4; ++i) {  // a timed solve keeps the launch file's counts and a wall-clock cap (algorithm.xml:184-191)
+    nh.num["optimization/max_iteration_num" + std::to_string(i)] = 300;
+    nh.num["optimization/max_iteration_time" + std::to_string(i)] = 0.005;
   }
-  P["manager/bspline_degree"] = 3;
-  SDFMap::Ptr map(new SDFMap);
-  map->initMap(nh);
-  EDTEnvironment::Ptr edt(new EDTEnvironment);
-  edt->setMap(map);
-  fuelmi_map* dev = map->device();
-  if (fuelmi_map_upload_occupancy(dev, occ.data()) != FUELMI_OK) return;
-  fuelmi_map_info inf;
-  fuelmi_map_get_info(dev, &inf);
-  const int lo[3] = {0, 0, 0}, hi[3] = {inf.voxel_num[0] - 1, inf.voxel_num[1] - 1, inf.voxel_num[2] - 1};
-  fuelmi_map_set_local_bound(dev, lo, hi);
-  MapROS::inflate(*map);
-  map->updateESDF3d();
-  fuelmi_map_synchronize(dev);
+  const DriverMap dm = make_map(nh, false);
+  const SDFMap::Ptr& map = dm.map;
+  const EDTEnvironment::Ptr& edt = dm.edt;
+  upload_occupancy(*map, occ, LOAD_BOUND | LOAD_INFLATE | LOAD_ESDF);
+  fuelmi_map_synchronize(map->device());
   const int N = 32;
   auto make = [&](int seed, Eigen::MatrixXd& ctrl, std::vector<Eigen::Vector3d>& st) {
     ctrl = Eigen::MatrixXd(N, 3);
@@ -330,16 +255,8 @@ int main(int argc, char** argv) {
   rd(in, hdr, 10);
   int n_frames;
   rd(in, &n_frames, 1);
-  std::vector<Frame> frames(n_frames);
-  for (Frame& f : frames) {
-    int n;
-    rd(in, &n, 1);
-    rd(in, f.cam, 3);
-    f.xyz.resize((size_t)n * 3);
-    rd(in, f.xyz.data(), f.xyz.size());
-    f.cloud.points.resize(n);
-    for (int i = 0; i < n; ++i) f.cloud.points[i] = pcl::PointXYZ(f.xyz[3 * i], f.xyz[3 * i + 1], f.xyz[3 * i + 2]);
-  }
+  std::vector<Frame> frames;
+  for (int k = 0; k < n_frames; ++k) frames.push_back(read_frame(in));
   fclose(in);
   double best[4] = {1e30, 1e30, 1e30, 1e30};
   int ncl[4] = {0, 0, 0, 0};

@@ -8,31 +8,9 @@
 // max_sample_num, max_raw_path, max_raw_path2, reserve_num, seed; ctrl_pt_dist; one occupancy log-odds grid (f64, the
 // map's voxel count); then any number of problems: double degree, n_ctrl, dt, and n_ctrl control points.  Every problem is
 // searched with the engine seeded anew.
-#include <cstdio>
-#include <cstdlib>
-#include <string>
-#include <vector>
+#include "facade_driver.h"
 
-#include <plan_env/sdf_map.h>
-#include <plan_env/edt_environment.h>
-#include <active_perception/graph_node.h>
-#include <active_perception/perception_utils.h>
 #include <path_searching/topo_prm.h>
-
-namespace fast_planner {
-// the facade library's open ends, defined by the packages of a FUEL workspace; unused here
-double ViewNode::computeCost(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, const double&, const double&,
-                             const Eigen::Vector3d&, const double&, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm();
-}
-double ViewNode::searchPath(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm();
-}
-PerceptionUtils::PerceptionUtils(ros::NodeHandle&) {}
-}  // namespace fast_planner
-using namespace fast_planner;
 
 static void put_path(const char* tag, size_t b, const vector<Eigen::Vector3d>& p) {
   std::printf("%s %zu %zu", tag, b, p.size());
@@ -45,43 +23,20 @@ int main(int argc, char** argv) {
   FILE* in = fopen(argv[1], "rb");
   if (!in) return 1;
   double hdr[16];
-  if (fread(hdr, sizeof(double), 16, in) != 16) return 2;
+  rd(in, hdr, 16);
   ros::NodeHandle nh;
   auto& P = nh.num;
-  const double ground = hdr[4];
-  P["sdf_map/resolution"] = hdr[3];
-  P["sdf_map/map_size_x"] = hdr[0], P["sdf_map/map_size_y"] = hdr[1], P["sdf_map/map_size_z"] = hdr[2];
-  P["sdf_map/obstacles_inflation"] = 0.199, P["sdf_map/local_bound_inflate"] = 0.5, P["sdf_map/ground_height"] = ground;
-  P["sdf_map/default_dist"] = 0.0, P["sdf_map/optimistic"] = 0, P["sdf_map/signed_dist"] = 0;
-  P["sdf_map/p_hit"] = 0.65, P["sdf_map/p_miss"] = 0.35, P["sdf_map/p_min"] = 0.12, P["sdf_map/p_max"] = 0.90;
-  P["sdf_map/p_occ"] = 0.80, P["sdf_map/max_ray_length"] = 4.5, P["sdf_map/virtual_ceil_height"] = -10;
-  const char* ax[3] = {"x", "y", "z"};
-  for (int i = 0; i < 3; ++i) {
-    const double lo = i < 2 ? -hdr[i] / 2.0 : ground;
-    P[std::string("sdf_map/box_min_") + ax[i]] = lo;
-    P[std::string("sdf_map/box_max_") + ax[i]] = lo + hdr[i];
-  }
+  double box_lo[3], box_hi[3];
+  whole_map_box(hdr, hdr[4], box_lo, box_hi);
+  sdf_map_params(nh, hdr, box_lo, box_hi, hdr[3], hdr[4]);
   P["topo_prm/sample_inflate_x"] = hdr[5], P["topo_prm/sample_inflate_y"] = hdr[6], P["topo_prm/sample_inflate_z"] = hdr[7];
   P["topo_prm/clearance"] = hdr[8], P["topo_prm/ratio_to_short"] = hdr[9], P["topo_prm/max_sample_num"] = hdr[10];
   P["topo_prm/max_raw_path"] = hdr[11], P["topo_prm/max_raw_path2"] = hdr[12], P["topo_prm/reserve_num"] = hdr[13];
   P["topo_prm/seed"] = hdr[14];
   const double ctrl_pt_dist = hdr[15];
-  SDFMap::Ptr map(new SDFMap);
-  map->initMap(nh);
-  map->setHostMirror(false, false, false);  // nothing below reads or refreshes a mirror
-  EDTEnvironment::Ptr edt(new EDTEnvironment);
-  edt->setMap(map);
-  fuelmi_map* m = map->device();
-  fuelmi_map_info info;
-  fuelmi_map_get_info(m, &info);
-  const int N = info.voxel_num[0] * info.voxel_num[1] * info.voxel_num[2];
-  std::vector<double> occ(N);
-  if (fread(occ.data(), sizeof(double), N, in) != (size_t)N) return 2;
-  const int b0[3] = {0, 0, 0};
-  const int b1[3] = {info.voxel_num[0] - 1, info.voxel_num[1] - 1, info.voxel_num[2] - 1};
-  if (fuelmi_map_upload_occupancy(m, occ.data()) || fuelmi_map_set_local_bound(m, b0, b1)) return 3;
-  if (fuelmi_map_inflate_local(m)) return 3;
-  map->updateESDF3d();
+  const DriverMap dm = make_map(nh, true);  // nothing below reads or refreshes a mirror
+  const EDTEnvironment::Ptr& edt = dm.edt;
+  load_occupancy(*dm.map, in, LOAD_BOUND | LOAD_INFLATE_ABI | LOAD_ESDF);
   double rec[3];
   for (size_t b = 0; fread(rec, sizeof(double), 3, in) == 3; ++b) {
     const int degree = (int)rec[0], n = (int)rec[1];

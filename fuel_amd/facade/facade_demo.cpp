@@ -3,50 +3,11 @@
 // updateESDFCallback -> updateESDF3d; planExploreMotion -> searchFrontiers;
 // planExploreTraj -> BsplineOptimizer::optimize) and dumps results for tests/test_facade_gpu.py.
 //   facade_demo <scenario.bin> <result.bin>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <string>
-#include <vector>
+#include "facade_driver.h"
 
-#include <plan_env/sdf_map.h>
-#include <plan_env/edt_environment.h>
 #include <active_perception/frontier_finder.h>
 #include <bspline_opt/bspline_optimizer.h>
-#include <active_perception/graph_node.h>
-#include <active_perception/perception_utils.h>
 
-namespace fast_planner {
-// ViewNode belongs to the part of active_perception the facade does not replace (graph_node.cpp: A*
-// through the map).  For this demo: straight flight plus a yaw term, the path is its two end points
-// (tests/test_facade_gpu.py rebuilds the expected cost matrix with the same formula).
-double ViewNode::computeCost(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, const double& y1, const double& y2,
-                             const Eigen::Vector3d&, const double&, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm() + 0.1 * std::fabs(y2 - y1);
-}
-PerceptionUtils::PerceptionUtils(ros::NodeHandle&) {}  // (the package's perception_utils.cpp in a FUEL workspace)
-double ViewNode::searchPath(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm();
-}
-// the reference's MapROS is a friend of SDFMap and calls its private clearAndInflateLocalMap
-// (plan_env/src/map_ros.cpp:142,170); this stand-in does the same
-class MapROS {
-public:
-  static void inflate(SDFMap& m) { m.clearAndInflateLocalMap(); }
-};
-}  // namespace fast_planner
-
-using namespace fast_planner;
-
-template <typename T>
-static void rd(FILE* f, T* p, size_t n) {
-  if (fread(p, sizeof(T), n, f) != n) {
-    std::fprintf(stderr, "short read\n");
-    std::exit(2);
-  }
-}
 template <typename T>
 static void wr(FILE* f, const T* p, size_t n) { fwrite(p, sizeof(T), n, f); }
 
@@ -59,18 +20,11 @@ int main(int argc, char** argv) {
   rd(in, hdr, 10);
   ros::NodeHandle nh;
   auto& P = nh.num;
-  P["sdf_map/resolution"] = 0.1;
-  P["sdf_map/map_size_x"] = hdr[0], P["sdf_map/map_size_y"] = hdr[1], P["sdf_map/map_size_z"] = hdr[2];
-  P["sdf_map/obstacles_inflation"] = 0.199, P["sdf_map/local_bound_inflate"] = 0.5, P["sdf_map/ground_height"] = -1.0;
-  P["sdf_map/default_dist"] = 0.0, P["sdf_map/optimistic"] = 0, P["sdf_map/signed_dist"] = 0;
-  P["sdf_map/p_hit"] = 0.65, P["sdf_map/p_miss"] = 0.35, P["sdf_map/p_min"] = 0.12, P["sdf_map/p_max"] = 0.90;
-  P["sdf_map/p_occ"] = 0.80, P["sdf_map/max_ray_length"] = 4.5, P["sdf_map/virtual_ceil_height"] = -10;
-  const char* ax[3] = {"x", "y", "z"};
-  for (int i = 0; i < 3; ++i) {
-    P[std::string("sdf_map/box_min_") + ax[i]] = hdr[3 + i];
-    P[std::string("sdf_map/box_max_") + ax[i]] = hdr[6 + i];
-  }
+  sdf_map_params(nh, hdr, hdr + 3, hdr + 6);
   P["frontier/cluster_min"] = hdr[9];
+  // Not optimization_params(): this driver leaves dlmin, wnl and max_iteration_num1/3/4 to the defaults of
+  // BsplineOptimizer::setParam (-1), which differ from the shared values, and names the NLopt ids the facade reports
+  // as unused.  tests/test_facade_gpu.py compares the cost and gradient this set gives with the oracle's.
   P["optimization/ld_smooth"] = 20.0, P["optimization/ld_dist"] = 10.0, P["optimization/ld_feasi"] = 2.0;
   P["optimization/ld_start"] = 100.0, P["optimization/ld_end"] = 0.5, P["optimization/ld_guide"] = 1.5;
   P["optimization/ld_waypt"] = 0.3, P["optimization/ld_view"] = 0.0, P["optimization/ld_time"] = 1.0;
@@ -78,24 +32,14 @@ int main(int argc, char** argv) {
   P["optimization/max_iteration_num2"] = 300, P["optimization/max_iteration_time2"] = 5.0;
   P["optimization/algorithm1"] = 15, P["optimization/algorithm2"] = 11;
 
-  SDFMap::Ptr map(new SDFMap);
-  map->initMap(nh);
-  EDTEnvironment::Ptr edt(new EDTEnvironment);
-  edt->setMap(map);
+  const DriverMap dm = make_map(nh, false);
+  const SDFMap::Ptr& map = dm.map;
+  const EDTEnvironment::Ptr& edt = dm.edt;
 
   int n_frames;
   rd(in, &n_frames, 1);
   for (int k = 0; k < n_frames; ++k) {
-    int n;
-    double cam[3];
-    rd(in, &n, 1);
-    rd(in, cam, 3);
-    std::vector<float> xyz((size_t)n * 3);
-    rd(in, xyz.data(), xyz.size());
-    pcl::PointCloud<pcl::PointXYZ> cloud;
-    cloud.points.resize(n);
-    for (int i = 0; i < n; ++i) cloud.points[i] = pcl::PointXYZ(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
-    map->inputPointCloud(cloud, n, Eigen::Vector3d(cam[0], cam[1], cam[2]));
+    read_frame(in).fuse(*map);
     MapROS::inflate(*map);
     map->updateESDF3d();
   }
@@ -211,21 +155,7 @@ int main(int argc, char** argv) {
   // computeFrontiersToVisit -> getTopViewpointsInfo, plus the FSM's isFrontierCovered check
   {
     ros::NodeHandle nh2 = nh;
-    auto& Q = nh2.num;
-    Q["frontier/cluster_size_xy"] = 1.0;
-    Q["frontier/down_sample"] = 3;
-    Q["frontier/candidate_rmin"] = 1.5;
-    Q["frontier/candidate_rmax"] = 2.5;
-    Q["frontier/candidate_rnum"] = 3;
-    Q["frontier/candidate_dphi"] = 15 * 3.1415926 / 180.0;
-    Q["frontier/min_candidate_clearance"] = 0.21;
-    Q["frontier/min_visib_num"] = 3;
-    Q["frontier/min_candidate_dist"] = 0.75;
-    Q["frontier/min_view_finish_fraction"] = 0.2;
-    Q["perception_utils/top_angle"] = 0.56125;
-    Q["perception_utils/left_angle"] = 0.69222;
-    Q["perception_utils/right_angle"] = 0.68901;
-    Q["perception_utils/max_dist"] = 4.5;
+    frontier_params(nh2, hdr[9], 1.0, 3);
     double lo[3] = {ub_min(0), ub_min(1), ub_min(2)}, hi[3] = {ub_max(0), ub_max(1), ub_max(2)};
     fuelmi_map_set_updated_box(map->device(), lo, hi);
     FrontierFinder ff2(edt, nh2);
@@ -249,16 +179,7 @@ int main(int argc, char** argv) {
     int n_extra = 0;
     if (fread(&n_extra, sizeof(int), 1, in) != 1) n_extra = 0;
     for (int k = 0; k < n_extra; ++k) {
-      int n;
-      double cam[3];
-      rd(in, &n, 1);
-      rd(in, cam, 3);
-      std::vector<float> xyz((size_t)n * 3);
-      rd(in, xyz.data(), xyz.size());
-      pcl::PointCloud<pcl::PointXYZ> cloud;
-      cloud.points.resize(n);
-      for (int i = 0; i < n; ++i) cloud.points[i] = pcl::PointXYZ(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
-      map->inputPointCloud(cloud, n, Eigen::Vector3d(cam[0], cam[1], cam[2]));
+      read_frame(in).fuse(*map);
       MapROS::inflate(*map);
     }
     ff2.searchFrontiers();

@@ -7,31 +7,9 @@
 // scenario.bin (doubles): map_size[3], box_min[3], box_max[3], half_vert_num, yaw_diff, max_yaw_rate, w, weight_type,
 // lambda1, lambda2, far, n_path, n_pose; one occupancy log-odds grid (the map's voxel count); per trajectory L, dt, n_ctrl,
 // pts[L][3], yaws[L], ctrl[n_ctrl][3]; per pose pt[3], yaw.
-#include <cstdio>
-#include <cstdlib>
-#include <string>
-#include <vector>
+#include "facade_driver.h"
 
-#include <plan_env/sdf_map.h>
-#include <plan_env/edt_environment.h>
-#include <active_perception/graph_node.h>
-#include <active_perception/perception_utils.h>
 #include <active_perception/heading_planner.h>
-
-namespace fast_planner {
-// the facade library's open ends, defined by the packages of a FUEL workspace; unused here
-double ViewNode::computeCost(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, const double&, const double&,
-                             const Eigen::Vector3d&, const double&, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm();
-}
-double ViewNode::searchPath(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm();
-}
-PerceptionUtils::PerceptionUtils(ros::NodeHandle&) {}
-}  // namespace fast_planner
-using namespace fast_planner;
 
 static void put(const char* tag, size_t b, const std::vector<double>& v) {
   std::printf("%s %zu %zu", tag, b, v.size());
@@ -44,36 +22,18 @@ int main(int argc, char** argv) {
   FILE* in = fopen(argv[1], "rb");
   if (!in) return 1;
   double hdr[19];
-  if (fread(hdr, sizeof(double), 19, in) != 19) return 2;
+  rd(in, hdr, 19);
   ros::NodeHandle nh;
   auto& P = nh.num;
-  P["sdf_map/resolution"] = 0.1;
-  P["sdf_map/map_size_x"] = hdr[0], P["sdf_map/map_size_y"] = hdr[1], P["sdf_map/map_size_z"] = hdr[2];
-  P["sdf_map/obstacles_inflation"] = 0.199, P["sdf_map/local_bound_inflate"] = 0.5, P["sdf_map/ground_height"] = -1.0;
-  P["sdf_map/default_dist"] = 0.0, P["sdf_map/optimistic"] = 0, P["sdf_map/signed_dist"] = 0;
-  P["sdf_map/p_hit"] = 0.65, P["sdf_map/p_miss"] = 0.35, P["sdf_map/p_min"] = 0.12, P["sdf_map/p_max"] = 0.90;
-  P["sdf_map/p_occ"] = 0.80, P["sdf_map/max_ray_length"] = 4.5, P["sdf_map/virtual_ceil_height"] = -10;
-  const char* ax[3] = {"x", "y", "z"};
-  for (int i = 0; i < 3; ++i) {
-    P[std::string("sdf_map/box_min_") + ax[i]] = hdr[3 + i];
-    P[std::string("sdf_map/box_max_") + ax[i]] = hdr[6 + i];
-  }
+  sdf_map_params(nh, hdr, hdr + 3, hdr + 6);
   P["heading_planner/half_vert_num"] = hdr[9], P["heading_planner/yaw_diff"] = hdr[10];
   P["heading_planner/max_yaw_rate"] = hdr[11], P["heading_planner/w"] = hdr[12], P["heading_planner/weight_type"] = hdr[13];
   P["heading_planner/lambda1"] = hdr[14], P["heading_planner/lambda2"] = hdr[15];
   const int n_path = (int)hdr[17], n_pose = (int)hdr[18];
-  SDFMap::Ptr map(new SDFMap);
-  map->initMap(nh);
-  map->setHostMirror(false, false, false);  // nothing below reads a mirror
-  fuelmi_map* m = map->device();
-  fuelmi_map_info info;
-  fuelmi_map_get_info(m, &info);
-  const int N = info.voxel_num[0] * info.voxel_num[1] * info.voxel_num[2];
-  std::vector<double> occ(N);
-  if (fread(occ.data(), sizeof(double), N, in) != (size_t)N) return 2;
-  if (fuelmi_map_upload_occupancy(m, occ.data())) return 3;
+  const DriverMap dm = make_map(nh, true);  // nothing below reads a mirror
+  load_occupancy(*dm.map, in, 0);        // the grid alone: the planner reads occupancy, no bound, no inflation
   HeadingPlanner hp(nh);
-  hp.setMap(map);
+  hp.setMap(dm.map);
   hp.far_ = hdr[16];
   vector<vector<Eigen::Vector3d>> pts(n_path);
   vector<vector<double>> yaws(n_path);

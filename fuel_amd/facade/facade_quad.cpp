@@ -11,39 +11,15 @@
 // scenario.bin, all f64: map_size[3], box_min[3], box_max[3]; the number of guide paths; per path N, dt, ctrl[N][3],
 // start[3][3], end[3][3], guide[N-6][3]; then the yaw problem: N, dt, ctrl[N], start[3], end[2], the number of
 // way-points, their indices, their values.
-#include <cstdio>
-#include <cstdlib>
-#include <string>
-#include <vector>
+#include "facade_driver.h"
 
-#include <plan_env/sdf_map.h>
-#include <plan_env/edt_environment.h>
-#include <active_perception/graph_node.h>
-#include <active_perception/perception_utils.h>
 #include <bspline_opt/bspline_optimizer.h>
 
-namespace fast_planner {
-// the package's own ViewNode in a FUEL workspace (graph_node.cpp); the facade library refers to it, nothing here calls it
-double ViewNode::computeCost(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, const double&, const double&,
-                             const Eigen::Vector3d&, const double&, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm();
-}
-double ViewNode::searchPath(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm();
-}
-PerceptionUtils::PerceptionUtils(ros::NodeHandle&) {}
-}  // namespace fast_planner
-using namespace fast_planner;
 typedef std::vector<Eigen::Vector3d> Pts;
 
 static std::vector<double> rd(FILE* in, size_t n) {
   std::vector<double> v(n);
-  if (n && fread(v.data(), sizeof(double), n, in) != n) {
-    std::fprintf(stderr, "short read\n");
-    std::exit(2);
-  }
+  rd(in, v.data(), n);
   return v;
 }
 static Pts pts(const std::vector<double>& v) {
@@ -67,35 +43,14 @@ int main(int argc, char** argv) {
   if (!in) return 1;
   const std::vector<double> hdr = rd(in, 9);
   ros::NodeHandle nh;
-  auto& P = nh.num;
-  P["sdf_map/resolution"] = 0.1;
-  P["sdf_map/map_size_x"] = hdr[0], P["sdf_map/map_size_y"] = hdr[1], P["sdf_map/map_size_z"] = hdr[2];
-  P["sdf_map/obstacles_inflation"] = 0.199, P["sdf_map/local_bound_inflate"] = 0.5, P["sdf_map/ground_height"] = -1.0;
-  P["sdf_map/default_dist"] = 0.0, P["sdf_map/optimistic"] = 0, P["sdf_map/signed_dist"] = 0;
-  P["sdf_map/p_hit"] = 0.65, P["sdf_map/p_miss"] = 0.35, P["sdf_map/p_min"] = 0.12, P["sdf_map/p_max"] = 0.90;
-  P["sdf_map/p_occ"] = 0.80, P["sdf_map/max_ray_length"] = 4.5, P["sdf_map/virtual_ceil_height"] = -10;
-  const char* ax[3] = {"x", "y", "z"};
-  for (int i = 0; i < 3; ++i) {
-    P[std::string("sdf_map/box_min_") + ax[i]] = hdr[3 + i];
-    P[std::string("sdf_map/box_max_") + ax[i]] = hdr[6 + i];
-  }
-  SDFMap::Ptr map(new SDFMap);
-  map->initMap(nh);
-  EDTEnvironment::Ptr edt(new EDTEnvironment);
-  edt->setMap(map);
-  // exploration_manager/launch/algorithm.xml:170-194, without the wall-clock cap (a result must not depend on the clock)
-  P["optimization/ld_smooth"] = 20.0, P["optimization/ld_dist"] = 10.0, P["optimization/ld_feasi"] = 2.0;
-  P["optimization/ld_start"] = 100.0, P["optimization/ld_end"] = 0.5, P["optimization/ld_guide"] = 1.5;
-  P["optimization/ld_waypt"] = 0.3, P["optimization/ld_view"] = 0.0, P["optimization/ld_time"] = 1.0;
-  P["optimization/dist0"] = 0.7, P["optimization/max_vel"] = 2.0, P["optimization/max_acc"] = 2.0;
-  P["optimization/dlmin"] = 0.0, P["optimization/wnl"] = 1.0;
-  P["optimization/max_iteration_num1"] = 2, P["optimization/max_iteration_num2"] = 2000;
-  P["optimization/max_iteration_num3"] = 100, P["optimization/max_iteration_num4"] = 100;
-  P["manager/bspline_degree"] = 3;
+  sdf_map_params(nh, hdr.data(), hdr.data() + 3, hdr.data() + 6);
+  const EDTEnvironment::Ptr edt = make_map(nh, false).edt;
+  optimization_params(nh);
+  nh.num["optimization/max_iteration_num2"] = 2000;  // the iterative yaw solve (max_num_id 1) gets 2000 evaluations
   BsplineOptimizer iter, exact;
   iter.setParam(nh);
   iter.setEnvironment(edt);
-  P["optimization/exact_quadratic"] = 1;
+  nh.num["optimization/exact_quadratic"] = 1;
   exact.setParam(nh);
   exact.setEnvironment(edt);
 

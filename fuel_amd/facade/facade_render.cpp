@@ -5,67 +5,24 @@
 //   map B  fuelmi_map_input_depth on the host copy of the same frame
 // both maps inflated, their occupancy and inflate planes refreshed and compared; for both models of the renderer.  Prints
 // one JSON document with what the two routes fused and whether the maps are byte-equal.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
+#include "facade_driver.h"
+
 #include <cstring>
-#include <string>
-#include <vector>
 
-#include <plan_env/sdf_map.h>
-#include <active_perception/graph_node.h>
-#include <active_perception/perception_utils.h>
-
-namespace fast_planner {
-// the package's own ViewNode in a FUEL workspace (graph_node.cpp); the facade library refers to it, nothing here calls it
-double ViewNode::computeCost(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, const double& y1, const double& y2,
-                             const Eigen::Vector3d&, const double&, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm() + 0.1 * std::fabs(y2 - y1);
+// the whole map's planes, refreshed from the device on request only
+static void planes(SDFMap& m, std::vector<double>& occ, std::vector<char>& infl) {
+  const Eigen::Vector3i lo(0, 0, 0), hi = MapROS::param(m).map_voxel_num_ - Eigen::Vector3i(1, 1, 1);
+  MapROS::refresh(m, lo, hi, true, true, false);
+  occ = MapROS::data(m).occupancy_buffer_;
+  infl = MapROS::data(m).occupancy_buffer_inflate_;
 }
-double ViewNode::searchPath(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm();
-}
-PerceptionUtils::PerceptionUtils(ros::NodeHandle&) {}
-// the reference's MapROS is a friend of SDFMap: it calls clearAndInflateLocalMap and reads md_
-class MapROS {
-public:
-  static void inflate(SDFMap& m) { m.clearAndInflateLocalMap(); }
-  static void mirrors(SDFMap& m, int out[3]) {
-    out[0] = m.ext_->mirror_occ, out[1] = m.ext_->mirror_infl, out[2] = m.ext_->mirror_dist;
-  }
-  // the whole map's planes, refreshed from the device on request only
-  static void planes(SDFMap& m, std::vector<double>& occ, std::vector<char>& infl) {
-    const Eigen::Vector3i lo(0, 0, 0), hi = m.mp_->map_voxel_num_ - Eigen::Vector3i(1, 1, 1);
-    m.syncMirrors(lo, hi, true, true, false);
-    occ = m.md_->occupancy_buffer_;
-    infl = m.md_->occupancy_buffer_inflate_;
-  }
-  static double minOccupancyLog(SDFMap& m) { return m.mp_->min_occupancy_log_; }
-};
-}  // namespace fast_planner
-using namespace fast_planner;
 
 static SDFMap::Ptr make_map(const double size[3]) {
   ros::NodeHandle nh;
-  auto& P = nh.num;
-  P["sdf_map/resolution"] = 0.1;
-  P["sdf_map/map_size_x"] = size[0], P["sdf_map/map_size_y"] = size[1], P["sdf_map/map_size_z"] = size[2];
-  P["sdf_map/obstacles_inflation"] = 0.199, P["sdf_map/local_bound_inflate"] = 0.5, P["sdf_map/ground_height"] = -1.0;
-  P["sdf_map/default_dist"] = 0.0, P["sdf_map/optimistic"] = 0, P["sdf_map/signed_dist"] = 0;
-  P["sdf_map/p_hit"] = 0.65, P["sdf_map/p_miss"] = 0.35, P["sdf_map/p_min"] = 0.12, P["sdf_map/p_max"] = 0.90;
-  P["sdf_map/p_occ"] = 0.80, P["sdf_map/max_ray_length"] = 4.5, P["sdf_map/virtual_ceil_height"] = -10;
-  const char* ax[3] = {"x", "y", "z"};
-  const double org[3] = {-size[0] / 2.0, -size[1] / 2.0, -1.0};
-  for (int i = 0; i < 3; ++i) {
-    P[std::string("sdf_map/box_min_") + ax[i]] = org[i] + 0.3;
-    P[std::string("sdf_map/box_max_") + ax[i]] = org[i] + size[i] - 0.3;
-  }
-  SDFMap::Ptr map(new SDFMap);
-  map->initMap(nh);
-  if (map->device()) map->setHostMirror(false, false, false);  // nothing below refreshes a mirror unless it says so
-  return map;
+  double box_lo[3], box_hi[3];
+  inset_box(size, box_lo, box_hi);
+  sdf_map_params(nh, size, box_lo, box_hi);
+  return make_map(nh, true).map;  // nothing below refreshes a mirror unless it says so
 }
 
 #define CHK(call)                                                             \
@@ -129,7 +86,6 @@ int main() {
   const char* names[2] = {"host_node", "cuda_node"};
   for (int model = 0; model < 2; ++model) {
     SDFMap::Ptr A = make_map(size), B = make_map(size);
-    if (!A->device() || !B->device()) return 3;
     int mir[3];
     MapROS::mirrors(*A, mir);
     if (model == 0) std::printf(", \"mirrors\": [%d, %d, %d]", mir[0], mir[1], mir[2]);
@@ -160,10 +116,10 @@ int main() {
     CHK(fuelmi_render_destroy(ren));
     std::vector<double> oa, ob;
     std::vector<char> ia, ib;
-    MapROS::planes(*A, oa, ia);
-    MapROS::planes(*B, ob, ib);
+    planes(*A, oa, ia);
+    planes(*B, ob, ib);
     long occupied = 0;
-    for (double v : oa) occupied += v > MapROS::minOccupancyLog(*A);
+    for (double v : oa) occupied += v > MapROS::param(*A).min_occupancy_log_;
     const bool occ_eq = oa.size() == ob.size() && !oa.empty() && memcmp(oa.data(), ob.data(), oa.size() * sizeof(double)) == 0;
     const bool inf_eq = ia.size() == ib.size() && !ia.empty() && memcmp(ia.data(), ib.data(), ia.size()) == 0;
     std::printf(",\n\"%s\": {\"pixels_with_return\": %ld, \"fused_device_pointer\": %s], \"fused_host_copy\": %s], "

@@ -8,32 +8,9 @@
 // knots.  A problem with ops == 0 goes through trajectoryMetrics, every other through adjustTime.  The last four
 // problems (uniform, one degree) are ranked by selectBestTraj, and the first of them alone once more.  Every double is
 // printed as a hex float in a string: the test compares bits.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <string>
-#include <vector>
+#include "facade_driver.h"
 
-#include <plan_env/sdf_map.h>
-#include <plan_env/edt_environment.h>
-#include <active_perception/graph_node.h>
-#include <active_perception/perception_utils.h>
 #include <bspline_opt/bspline_optimizer.h>
-
-namespace fast_planner {
-// the package's own ViewNode in a FUEL workspace (graph_node.cpp); the facade library refers to it, nothing here calls it
-double ViewNode::computeCost(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, const double& y1, const double& y2,
-                             const Eigen::Vector3d&, const double&, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm() + 0.1 * std::fabs(y2 - y1);
-}
-double ViewNode::searchPath(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm();
-}
-PerceptionUtils::PerceptionUtils(ros::NodeHandle&) {}
-}  // namespace fast_planner
-using namespace fast_planner;
 
 static void print_hex(const char* name, const double* v, size_t n) {
   std::printf("\"%s\": [", name);
@@ -46,36 +23,14 @@ int main(int argc, char** argv) {
   FILE* in = fopen(argv[1], "rb");
   if (!in) return 1;
   double hdr[12];
-  if (fread(hdr, sizeof(double), 12, in) != 12) return 2;
+  rd(in, hdr, 12);
   ros::NodeHandle nh;
-  auto& P = nh.num;
-  P["sdf_map/resolution"] = hdr[9];
-  P["sdf_map/map_size_x"] = hdr[0], P["sdf_map/map_size_y"] = hdr[1], P["sdf_map/map_size_z"] = hdr[2];
-  P["sdf_map/obstacles_inflation"] = 0.199, P["sdf_map/local_bound_inflate"] = 0.5, P["sdf_map/ground_height"] = hdr[10];
-  P["sdf_map/default_dist"] = 0.0, P["sdf_map/optimistic"] = 0, P["sdf_map/signed_dist"] = 0;
-  P["sdf_map/p_hit"] = 0.65, P["sdf_map/p_miss"] = 0.35, P["sdf_map/p_min"] = 0.12, P["sdf_map/p_max"] = 0.90;
-  P["sdf_map/p_occ"] = 0.80, P["sdf_map/max_ray_length"] = 4.5, P["sdf_map/virtual_ceil_height"] = -10;
-  const char* ax[3] = {"x", "y", "z"};
-  for (int i = 0; i < 3; ++i) {
-    P[std::string("sdf_map/box_min_") + ax[i]] = hdr[3 + i];
-    P[std::string("sdf_map/box_max_") + ax[i]] = hdr[6 + i];
-  }
-  SDFMap::Ptr map(new SDFMap);
-  map->initMap(nh);
-  map->setHostMirror(false, false, false);  // the adjustment reads no plane and no mirror
-  EDTEnvironment::Ptr edt(new EDTEnvironment);
-  edt->setMap(map);
-  P["optimization/ld_smooth"] = 20.0, P["optimization/ld_dist"] = 10.0, P["optimization/ld_feasi"] = 2.0;
-  P["optimization/ld_start"] = 100.0, P["optimization/ld_end"] = 0.5, P["optimization/ld_guide"] = 1.5;
-  P["optimization/ld_waypt"] = 0.3, P["optimization/ld_view"] = 0.0, P["optimization/ld_time"] = 1.0;
-  P["optimization/dist0"] = 0.7, P["optimization/max_vel"] = 2.0, P["optimization/max_acc"] = 2.0;
-  P["optimization/dlmin"] = 0.0, P["optimization/wnl"] = 1.0;
-  P["optimization/max_iteration_num1"] = 2, P["optimization/max_iteration_num2"] = 100;
-  P["optimization/max_iteration_num3"] = 100, P["optimization/max_iteration_num4"] = 100;
-  P["manager/bspline_degree"] = 3;
+  sdf_map_params(nh, hdr, hdr + 3, hdr + 6, hdr[9], hdr[10]);
+  optimization_params(nh);
+  const DriverMap dm = make_map(nh, true);  // the adjustment reads no plane and no mirror
   BsplineOptimizer opt;
   opt.setParam(nh);
-  opt.setEnvironment(edt);
+  opt.setEnvironment(dm.edt);
   const int n_prob = (int)hdr[11];
   if (n_prob < 4 || n_prob > 4096) return 2;
   std::vector<Eigen::MatrixXd> tail;

@@ -7,41 +7,9 @@
 // (f64, the map's voxel count); then any number of problems, double degree, n_ctrl, knot span, t_now and n_ctrl x 3
 // control points.  With reps > 0 every problem is also timed, median of reps calls each: the device call, and the route
 // it replaces (refresh the inflate mirror for the trajectory's box, then the host loop).
-#include <algorithm>
-#include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <string>
-#include <vector>
+#include "facade_driver.h"
 
-#include <plan_env/sdf_map.h>
-#include <plan_env/edt_environment.h>
-#include <active_perception/graph_node.h>
-#include <active_perception/perception_utils.h>
 #include <bspline_opt/bspline_optimizer.h>
-
-namespace fast_planner {
-// the package's own ViewNode in a FUEL workspace (graph_node.cpp); the facade library refers to it, nothing here calls it
-double ViewNode::computeCost(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, const double& y1, const double& y2,
-                             const Eigen::Vector3d&, const double&, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm() + 0.1 * std::fabs(y2 - y1);
-}
-double ViewNode::searchPath(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm();
-}
-PerceptionUtils::PerceptionUtils(ros::NodeHandle&) {}
-class MapROS {
-public:
-  static void inflate(SDFMap& m) { m.clearAndInflateLocalMap(); }
-  static void refresh(SDFMap& m, const Eigen::Vector3i& lo, const Eigen::Vector3i& hi) {
-    m.syncMirrors(lo, hi, false, true, false);
-  }
-};
-}  // namespace fast_planner
-using namespace fast_planner;
 
 // a uniform position spline on the host: setUniformBspline's knots and evaluateDeBoorT
 struct HostSpline {
@@ -86,66 +54,22 @@ static bool host_loop(SDFMap& map, const HostSpline& s, double t_now, double& di
   return true;
 }
 
-template <class F>
-static double median_us(int reps, F f) {
-  std::vector<double> us;
-  for (int r = 0; r < reps; ++r) {
-    const auto a = std::chrono::steady_clock::now();
-    f();
-    us.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - a).count());
-  }
-  std::sort(us.begin(), us.end());
-  return us[us.size() / 2];
-}
-
 int main(int argc, char** argv) {
   if (argc < 2) return 1;
   FILE* in = fopen(argv[1], "rb");
   if (!in) return 1;
   const int reps = argc > 2 ? atoi(argv[2]) : 0;
   double hdr[11];
-  if (fread(hdr, sizeof(double), 11, in) != 11) return 2;
+  rd(in, hdr, 11);
   ros::NodeHandle nh;
-  auto& P = nh.num;
-  P["sdf_map/resolution"] = hdr[9];
-  P["sdf_map/map_size_x"] = hdr[0], P["sdf_map/map_size_y"] = hdr[1], P["sdf_map/map_size_z"] = hdr[2];
-  P["sdf_map/obstacles_inflation"] = 0.199, P["sdf_map/local_bound_inflate"] = 0.5, P["sdf_map/ground_height"] = hdr[10];
-  P["sdf_map/default_dist"] = 0.0, P["sdf_map/optimistic"] = 0, P["sdf_map/signed_dist"] = 0;
-  P["sdf_map/p_hit"] = 0.65, P["sdf_map/p_miss"] = 0.35, P["sdf_map/p_min"] = 0.12, P["sdf_map/p_max"] = 0.90;
-  P["sdf_map/p_occ"] = 0.80, P["sdf_map/max_ray_length"] = 4.5, P["sdf_map/virtual_ceil_height"] = -10;
-  const char* ax[3] = {"x", "y", "z"};
-  for (int i = 0; i < 3; ++i) {
-    P[std::string("sdf_map/box_min_") + ax[i]] = hdr[3 + i];
-    P[std::string("sdf_map/box_max_") + ax[i]] = hdr[6 + i];
-  }
-  SDFMap::Ptr map(new SDFMap);
-  map->initMap(nh);
-  map->setHostMirror(false, false, false);  // nothing below refreshes a mirror unless it says so
-  EDTEnvironment::Ptr edt(new EDTEnvironment);
-  edt->setMap(map);
-  fuelmi_map* m = map->device();
-  fuelmi_map_info info;
-  fuelmi_map_get_info(m, &info);
-  const int N = info.voxel_num[0] * info.voxel_num[1] * info.voxel_num[2];
-  {
-    std::vector<double> occ(N);
-    if (fread(occ.data(), sizeof(double), N, in) != (size_t)N) return 2;
-    const int b0[3] = {0, 0, 0};
-    const int b1[3] = {info.voxel_num[0] - 1, info.voxel_num[1] - 1, info.voxel_num[2] - 1};
-    if (fuelmi_map_upload_occupancy(m, occ.data()) || fuelmi_map_set_local_bound(m, b0, b1)) return 3;
-    MapROS::inflate(*map);
-  }
-  P["optimization/ld_smooth"] = 20.0, P["optimization/ld_dist"] = 10.0, P["optimization/ld_feasi"] = 2.0;
-  P["optimization/ld_start"] = 100.0, P["optimization/ld_end"] = 0.5, P["optimization/ld_guide"] = 1.5;
-  P["optimization/ld_waypt"] = 0.3, P["optimization/ld_view"] = 0.0, P["optimization/ld_time"] = 1.0;
-  P["optimization/dist0"] = 0.7, P["optimization/max_vel"] = 2.0, P["optimization/max_acc"] = 2.0;
-  P["optimization/dlmin"] = 0.0, P["optimization/wnl"] = 1.0;
-  P["optimization/max_iteration_num1"] = 2, P["optimization/max_iteration_num2"] = 100;
-  P["optimization/max_iteration_num3"] = 100, P["optimization/max_iteration_num4"] = 100;
-  P["manager/bspline_degree"] = 3;
+  sdf_map_params(nh, hdr, hdr + 3, hdr + 6, hdr[9], hdr[10]);
+  optimization_params(nh);
+  const DriverMap dm = make_map(nh, true);  // nothing below refreshes a mirror unless it says so
+  const SDFMap::Ptr& map = dm.map;
+  load_occupancy(*map, in, LOAD_BOUND | LOAD_INFLATE);
   BsplineOptimizer opt;
   opt.setParam(nh);
-  opt.setEnvironment(edt);
+  opt.setEnvironment(dm.edt);
   std::printf("{\"problems\": [");
   double head[4];
   for (int b = 0; fread(head, sizeof(double), 4, in) == 4; ++b) {
@@ -179,7 +103,7 @@ int main(int argc, char** argv) {
       bool mirror_safe = true;
       const double us_dev = median_us(reps, [&] { opt.checkTrajCollision(ctrl, degree, dt, t_now, d); });
       const double us_host = median_us(reps, [&] {
-        MapROS::refresh(*map, ilo, ihi);
+        MapROS::refresh(*map, ilo, ihi, false, true, false);
         mirror_safe = host_loop(*map, s, t_now, d);
       });
       std::printf(", \"fresh_mirror_safe\": %d, \"device_us\": %.3f, \"sync_and_host_loop_us\": %.3f, \"box_voxels\": %ld",

@@ -8,34 +8,9 @@
 // n_ctrl x 3 control points, n_yaw yaw control points, n_t times.  COMMAND problems go through evaluateCommand in one
 // call with a flight record from zeros; STATE problems through one replanState per time.  With reps > 0 every problem is
 // also timed, median of reps runs each: the facade's device route and the host loop.
-#include <algorithm>
-#include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <string>
-#include <vector>
+#include "facade_driver.h"
 
-#include <plan_env/sdf_map.h>
-#include <plan_env/edt_environment.h>
-#include <active_perception/graph_node.h>
-#include <active_perception/perception_utils.h>
 #include <bspline_opt/bspline_optimizer.h>
-
-namespace fast_planner {
-// the package's own ViewNode in a FUEL workspace (graph_node.cpp); the facade library refers to it, nothing here calls it
-double ViewNode::computeCost(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, const double& y1, const double& y2,
-                             const Eigen::Vector3d&, const double&, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm() + 0.1 * std::fabs(y2 - y1);
-}
-double ViewNode::searchPath(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm();
-}
-PerceptionUtils::PerceptionUtils(ros::NodeHandle&) {}
-}  // namespace fast_planner
-using namespace fast_planner;
 
 // NonUniformBspline on the host with the members evaluateDeBoor reads: setUniformBspline's knots (:25-31), evaluateDeBoorT
 // (:51-75) and getDerivative (:77-106) as the class has them -- a derivative is a spline of its own
@@ -194,54 +169,20 @@ static void print_result(const char* name, const Result& R, bool command) {
   std::printf("]}");
 }
 
-template <class F>
-static double median_us(int reps, F f) {
-  std::vector<double> us;
-  for (int r = 0; r < reps; ++r) {
-    const auto a = std::chrono::steady_clock::now();
-    f();
-    us.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - a).count());
-  }
-  std::sort(us.begin(), us.end());
-  return us[us.size() / 2];
-}
-
 int main(int argc, char** argv) {
   if (argc < 2) return 1;
   FILE* in = fopen(argv[1], "rb");
   if (!in) return 1;
   const int reps = argc > 2 ? atoi(argv[2]) : 0;
   double hdr[11];
-  if (fread(hdr, sizeof(double), 11, in) != 11) return 2;
+  rd(in, hdr, 11);
   ros::NodeHandle nh;
-  auto& P = nh.num;
-  P["sdf_map/resolution"] = hdr[9];
-  P["sdf_map/map_size_x"] = hdr[0], P["sdf_map/map_size_y"] = hdr[1], P["sdf_map/map_size_z"] = hdr[2];
-  P["sdf_map/obstacles_inflation"] = 0.199, P["sdf_map/local_bound_inflate"] = 0.5, P["sdf_map/ground_height"] = hdr[10];
-  P["sdf_map/default_dist"] = 0.0, P["sdf_map/optimistic"] = 0, P["sdf_map/signed_dist"] = 0;
-  P["sdf_map/p_hit"] = 0.65, P["sdf_map/p_miss"] = 0.35, P["sdf_map/p_min"] = 0.12, P["sdf_map/p_max"] = 0.90;
-  P["sdf_map/p_occ"] = 0.80, P["sdf_map/max_ray_length"] = 4.5, P["sdf_map/virtual_ceil_height"] = -10;
-  const char* ax[3] = {"x", "y", "z"};
-  for (int i = 0; i < 3; ++i) {
-    P[std::string("sdf_map/box_min_") + ax[i]] = hdr[3 + i];
-    P[std::string("sdf_map/box_max_") + ax[i]] = hdr[6 + i];
-  }
-  SDFMap::Ptr map(new SDFMap);
-  map->initMap(nh);
-  map->setHostMirror(false, false, false);  // sampling reads no plane and no mirror
-  EDTEnvironment::Ptr edt(new EDTEnvironment);
-  edt->setMap(map);
-  P["optimization/ld_smooth"] = 20.0, P["optimization/ld_dist"] = 10.0, P["optimization/ld_feasi"] = 2.0;
-  P["optimization/ld_start"] = 100.0, P["optimization/ld_end"] = 0.5, P["optimization/ld_guide"] = 1.5;
-  P["optimization/ld_waypt"] = 0.3, P["optimization/ld_view"] = 0.0, P["optimization/ld_time"] = 1.0;
-  P["optimization/dist0"] = 0.7, P["optimization/max_vel"] = 2.0, P["optimization/max_acc"] = 2.0;
-  P["optimization/dlmin"] = 0.0, P["optimization/wnl"] = 1.0;
-  P["optimization/max_iteration_num1"] = 2, P["optimization/max_iteration_num2"] = 100;
-  P["optimization/max_iteration_num3"] = 100, P["optimization/max_iteration_num4"] = 100;
-  P["manager/bspline_degree"] = 3;
+  sdf_map_params(nh, hdr, hdr + 3, hdr + 6, hdr[9], hdr[10]);
+  optimization_params(nh);
+  const DriverMap dm = make_map(nh, true);  // sampling reads no plane and no mirror
   BsplineOptimizer opt;
   opt.setParam(nh);
-  opt.setEnvironment(edt);
+  opt.setEnvironment(dm.edt);
   std::printf("{\"problems\": [");
   double head[10];
   for (int b = 0; fread(head, sizeof(double), 10, in) == 10; ++b) {

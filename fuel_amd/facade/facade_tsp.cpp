@@ -8,39 +8,13 @@
 //   facade_tsp --malformed <tsp_dir>
 //     a stale single.txt, a problem file with a TSP type, solveTSPLKH: "lkh_rc" and whether a tour file is left.
 // scenario.bin: double map_size[3], box_min[3], box_max[3]; then the occupancy log-odds grid (f64, the map's voxels).
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
+#include "facade_driver.h"
+
 #include <fstream>
 #include <sstream>
-#include <string>
-#include <vector>
 
-#include <plan_env/sdf_map.h>
-#include <plan_env/edt_environment.h>
 #include <active_perception/frontier_finder.h>
-#include <active_perception/graph_node.h>
-#include <active_perception/perception_utils.h>
 #include <lkh_tsp_solver/lkh_interface.h>
-
-namespace fast_planner {
-// the package's own ViewNode is not used with frontier/device_path_cost (the driver's stand-ins are never reached)
-double ViewNode::computeCost(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, const double&, const double&,
-                             const Eigen::Vector3d&, const double&, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm();
-}
-double ViewNode::searchPath(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm();
-}
-PerceptionUtils::PerceptionUtils(ros::NodeHandle&) {}
-class MapROS {
-public:
-  static void inflate(SDFMap& m) { m.clearAndInflateLocalMap(); }
-};
-}  // namespace fast_planner
-using namespace fast_planner;
 
 // the parameter and problem files in the format findGlobalTour writes (:342-376), the tour back as it reads it
 // (:381-410): lines after TOUR_SECTION, node 1 skipped, up to -1, id - 2
@@ -94,56 +68,16 @@ int main(int argc, char** argv) {
   if (!in) return 1;
   const std::string dir = argv[2];
   double hdr[9];
-  if (fread(hdr, sizeof(double), 9, in) != 9) return 2;
+  rd(in, hdr, 9);
   ros::NodeHandle nh;
-  auto& P = nh.num;
-  P["sdf_map/resolution"] = 0.1;
-  P["sdf_map/map_size_x"] = hdr[0], P["sdf_map/map_size_y"] = hdr[1], P["sdf_map/map_size_z"] = hdr[2];
-  P["sdf_map/obstacles_inflation"] = 0.199, P["sdf_map/local_bound_inflate"] = 0.5, P["sdf_map/ground_height"] = -1.0;
-  P["sdf_map/default_dist"] = 0.0, P["sdf_map/optimistic"] = 0, P["sdf_map/signed_dist"] = 0;
-  P["sdf_map/p_hit"] = 0.65, P["sdf_map/p_miss"] = 0.35, P["sdf_map/p_min"] = 0.12, P["sdf_map/p_max"] = 0.90;
-  P["sdf_map/p_occ"] = 0.80, P["sdf_map/max_ray_length"] = 4.5, P["sdf_map/virtual_ceil_height"] = -10;
-  const char* ax[3] = {"x", "y", "z"};
-  for (int i = 0; i < 3; ++i) {
-    P[std::string("sdf_map/box_min_") + ax[i]] = hdr[3 + i];
-    P[std::string("sdf_map/box_max_") + ax[i]] = hdr[6 + i];
-  }
-  P["frontier/cluster_min"] = 100;
-  P["frontier/cluster_size_xy"] = 2.0;
-  P["frontier/down_sample"] = 3;
-  P["frontier/candidate_rmin"] = 1.5;
-  P["frontier/candidate_rmax"] = 2.5;
-  P["frontier/candidate_rnum"] = 3;
-  P["frontier/candidate_dphi"] = 15 * 3.1415926 / 180.0;
-  P["frontier/min_candidate_clearance"] = 0.21;
-  P["frontier/min_visib_num"] = 15;
-  P["frontier/min_candidate_dist"] = 0.75;
-  P["frontier/min_view_finish_fraction"] = 0.2;
-  P["perception_utils/top_angle"] = 0.56125;
-  P["perception_utils/left_angle"] = 0.69222;
-  P["perception_utils/right_angle"] = 0.68901;
-  P["perception_utils/max_dist"] = 4.5;
-  P["frontier/device_path_cost"] = 1;
-  P["exploration/vm"] = 2.0;
-  P["exploration/yd"] = 60 * 3.1415926 / 180.0;
-  P["exploration/w_dir"] = 1.5;
-  SDFMap::Ptr map(new SDFMap);
-  map->initMap(nh);
-  EDTEnvironment::Ptr edt(new EDTEnvironment);
-  edt->setMap(map);
-  fuelmi_map* m = map->device();
-  fuelmi_map_info info;
-  fuelmi_map_get_info(m, &info);
-  const int N = info.voxel_num[0] * info.voxel_num[1] * info.voxel_num[2];
-  std::vector<double> occ(N);
-  if (fread(occ.data(), sizeof(double), N, in) != (size_t)N) return 2;
+  sdf_map_params(nh, hdr, hdr + 3, hdr + 6);
+  frontier_params(nh, 100, 2.0, 15);  // the launch file's own cluster sizes
+  nh.num["frontier/device_path_cost"] = 1;  // (the stand-in ViewNode is never reached)
+  exploration_params(nh);
+  const DriverMap dm = make_map(nh, false);
+  load_occupancy(*dm.map, in, LOAD_BOUND | LOAD_INFLATE, hdr + 3, hdr + 6);
   fclose(in);
-  const int b0[3] = {0, 0, 0};
-  const int b1[3] = {info.voxel_num[0] - 1, info.voxel_num[1] - 1, info.voxel_num[2] - 1};
-  if (fuelmi_map_upload_occupancy(m, occ.data()) || fuelmi_map_set_local_bound(m, b0, b1)) return 3;
-  MapROS::inflate(*map);
-  fuelmi_map_set_updated_box(m, hdr + 3, hdr + 6);
-  FrontierFinder ff(edt, nh);
+  FrontierFinder ff(dm.edt, nh);
   ff.searchFrontiers();
   ff.computeFrontiersToVisit();
   std::vector<std::vector<Eigen::Vector3d>> act;

@@ -5,114 +5,28 @@
 //   facade_yaw <scenario.bin>
 // scenario.bin: double map_size[3], box_min[3], box_max[3]; one occupancy log-odds grid (f64, the map's voxel count);
 // then any number of problems, double start[3], goal[3], velocity[3], acceleration[3], start_yaw[3], end_yaw, relax_time.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <string>
-#include <vector>
+#include "facade_driver.h"
 
-#include <plan_env/sdf_map.h>
-#include <plan_env/edt_environment.h>
 #include <active_perception/frontier_finder.h>
-#include <active_perception/graph_node.h>
-#include <active_perception/perception_utils.h>
 #include <bspline_opt/bspline_optimizer.h>
-
-namespace fast_planner {
-// the package's own ViewNode in a FUEL workspace (graph_node.cpp); here the demo's stand-in: straight flight plus a
-// yaw term, the path is its two end points
-double ViewNode::computeCost(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, const double& y1, const double& y2,
-                             const Eigen::Vector3d&, const double&, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm() + 0.1 * std::fabs(y2 - y1);
-}
-double ViewNode::searchPath(const Eigen::Vector3d& p1, const Eigen::Vector3d& p2, std::vector<Eigen::Vector3d>& path) {
-  path = {p1, p2};
-  return (p2 - p1).norm();
-}
-PerceptionUtils::PerceptionUtils(ros::NodeHandle&) {}
-class MapROS {
-public:
-  static void inflate(SDFMap& m) { m.clearAndInflateLocalMap(); }
-};
-}  // namespace fast_planner
-using namespace fast_planner;
-
-static void load(SDFMap& map, FILE* in, int N, const double lo[3], const double hi[3]) {
-  std::vector<double> occ(N);
-  if (fread(occ.data(), sizeof(double), N, in) != (size_t)N) {
-    std::fprintf(stderr, "short read\n");
-    std::exit(2);
-  }
-  fuelmi_map* m = map.device();
-  fuelmi_map_info info;
-  fuelmi_map_get_info(m, &info);
-  const int b0[3] = {0, 0, 0};
-  const int b1[3] = {info.voxel_num[0] - 1, info.voxel_num[1] - 1, info.voxel_num[2] - 1};
-  if (fuelmi_map_upload_occupancy(m, occ.data()) || fuelmi_map_set_local_bound(m, b0, b1)) std::exit(3);
-  MapROS::inflate(map);
-  map.updateESDF3d();
-  fuelmi_map_set_updated_box(m, lo, hi);
-}
 
 int main(int argc, char** argv) {
   if (argc < 2) return 1;
   FILE* in = fopen(argv[1], "rb");
   if (!in) return 1;
   double hdr[9];
-  if (fread(hdr, sizeof(double), 9, in) != 9) return 2;
+  rd(in, hdr, 9);
   ros::NodeHandle nh;
-  auto& P = nh.num;
-  P["sdf_map/resolution"] = 0.1;
-  P["sdf_map/map_size_x"] = hdr[0], P["sdf_map/map_size_y"] = hdr[1], P["sdf_map/map_size_z"] = hdr[2];
-  P["sdf_map/obstacles_inflation"] = 0.199, P["sdf_map/local_bound_inflate"] = 0.5, P["sdf_map/ground_height"] = -1.0;
-  P["sdf_map/default_dist"] = 0.0, P["sdf_map/optimistic"] = 0, P["sdf_map/signed_dist"] = 0;
-  P["sdf_map/p_hit"] = 0.65, P["sdf_map/p_miss"] = 0.35, P["sdf_map/p_min"] = 0.12, P["sdf_map/p_max"] = 0.90;
-  P["sdf_map/p_occ"] = 0.80, P["sdf_map/max_ray_length"] = 4.5, P["sdf_map/virtual_ceil_height"] = -10;
-  const char* ax[3] = {"x", "y", "z"};
-  for (int i = 0; i < 3; ++i) {
-    P[std::string("sdf_map/box_min_") + ax[i]] = hdr[3 + i];
-    P[std::string("sdf_map/box_max_") + ax[i]] = hdr[6 + i];
-  }
-  P["frontier/cluster_min"] = 10;
-  P["frontier/cluster_size_xy"] = 1.0;
-  P["frontier/down_sample"] = 3;
-  P["frontier/candidate_rmin"] = 1.5;
-  P["frontier/candidate_rmax"] = 2.5;
-  P["frontier/candidate_rnum"] = 3;
-  P["frontier/candidate_dphi"] = 15 * 3.1415926 / 180.0;
-  P["frontier/min_candidate_clearance"] = 0.21;
-  P["frontier/min_visib_num"] = 3;
-  P["frontier/min_candidate_dist"] = 0.75;
-  P["frontier/min_view_finish_fraction"] = 0.2;
-  P["perception_utils/top_angle"] = 0.56125;
-  P["perception_utils/left_angle"] = 0.69222;
-  P["perception_utils/right_angle"] = 0.68901;
-  P["perception_utils/max_dist"] = 4.5;
-  SDFMap::Ptr map(new SDFMap);
-  map->initMap(nh);
-  EDTEnvironment::Ptr edt(new EDTEnvironment);
-  edt->setMap(map);
-  fuelmi_map_info info;
-  fuelmi_map_get_info(map->device(), &info);
-  const int N = info.voxel_num[0] * info.voxel_num[1] * info.voxel_num[2];
-  FrontierFinder ff(edt, nh);
-  load(*map, in, N, hdr + 3, hdr + 6);
-  // exploration_manager/launch/algorithm.xml:170-194, without the wall-clock cap (a result must not depend on the clock)
-  P["optimization/ld_smooth"] = 20.0, P["optimization/ld_dist"] = 10.0, P["optimization/ld_feasi"] = 2.0;
-  P["optimization/ld_start"] = 100.0, P["optimization/ld_end"] = 0.5, P["optimization/ld_guide"] = 1.5;
-  P["optimization/ld_waypt"] = 0.3, P["optimization/ld_view"] = 0.0, P["optimization/ld_time"] = 1.0;
-  P["optimization/dist0"] = 0.7, P["optimization/max_vel"] = 2.0, P["optimization/max_acc"] = 2.0;
-  P["optimization/dlmin"] = 0.0, P["optimization/wnl"] = 1.0;
-  P["optimization/max_iteration_num1"] = 2, P["optimization/max_iteration_num2"] = 100;
-  P["optimization/max_iteration_num3"] = 100, P["optimization/max_iteration_num4"] = 100;
-  P["manager/bspline_degree"] = 3;
+  sdf_map_params(nh, hdr, hdr + 3, hdr + 6);
+  frontier_params(nh, 10, 1.0, 3);
+  optimization_params(nh);
+  const DriverMap dm = make_map(nh, false);
+  FrontierFinder ff(dm.edt, nh);
+  load_occupancy(*dm.map, in, LOAD_BOUND | LOAD_INFLATE | LOAD_ESDF, hdr + 3, hdr + 6);
   BsplineOptimizer opt;
   opt.setParam(nh);
-  opt.setEnvironment(edt);
-  std::vector<double> pr;
-  double rec[17];
-  while (fread(rec, sizeof(double), 17, in) == 17) pr.insert(pr.end(), rec, rec + 17);
+  opt.setEnvironment(dm.edt);
+  const std::vector<double> pr = read_records(in, 17);
   fclose(in);
   std::printf("{\"problems\": [");
   for (size_t b = 0; b < pr.size() / 17; ++b) {
