@@ -232,6 +232,7 @@ class TrajAdjCfg(C.Structure):
 
 TRAJADJ_LENGTHEN, TRAJADJ_REALLOC, TRAJADJ_RESAMPLE, TRAJADJ_SELECT = 1, 2, 4, 8
 TRAJADJ_OK, TRAJADJ_BADSPLINE, TRAJADJ_LONG = range(3)
+KNOTS_UNIFORM, KNOTS_ADJUSTED = 0, 1  # fuelmi_bspline_dev_set_knot_source
 TRAJADJ_MAX_CTRL, TRAJADJ_MAX_SAMPLES, TRAJADJ_MAX_PROB, TRAJADJ_MAX_STEPS = 1024, 4096, 1 << 16, 1 << 16
 TRAJADJ_INFO = ("status", "feasible_in", "iters", "feasible", "feasible_out", "num_vel", "num_acc", "n_samples")
 TRAJADJ_METRICS = ("duration_in", "ratio", "duration_out", "length", "jerk", "mean_vel", "max_vel", "mean_acc", "max_acc",
@@ -407,6 +408,8 @@ SYMBOLS = {
     "fuelmi_yawpath_plan": (C.c_int, [C.POINTER(YawPathCfg), _ip]),
     "fuelmi_map_plan_yaws": (C.c_int, [_P, C.POINTER(BsplineCfg), C.POINTER(YawCfg), C.c_int, _ip, _dp, _dp, _dp, _dp, _ip,
                                        _dp, _ip, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp]),
+    "fuelmi_map_plan_yaws_knots": (C.c_int, [_P, C.POINTER(BsplineCfg), C.POINTER(YawCfg), C.c_int, _ip, _dp, _dp, _dp, _dp,
+                                             _ip, _dp, _ip, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp]),
     "fuelmi_bspline_dev_plan_yaws": (C.c_int, [_P, C.POINTER(YawCfg), _dp, _dp, _ip, _dp, _ip, _dp, _dp, _ip, _dp, _dp,
                                                _dp, _dp, _dp]),
     "fuelmi_yaw_plan": (C.c_int, [C.POINTER(YawCfg), _ip]),
@@ -416,10 +419,14 @@ SYMBOLS = {
     "fuelmi_quad_plan": (C.c_int, [C.POINTER(QuadCfg), _ip]),
     "fuelmi_map_check_trajs": (C.c_int, [_P, C.POINTER(TrajChkCfg), C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _dp, _ip, _ip, _dp,
                                          _dp, _ip, _dp]),
+    "fuelmi_map_check_trajs_knots": (C.c_int, [_P, C.POINTER(TrajChkCfg), C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _dp, _ip, _ip,
+                                               _dp, _dp, _ip, _dp]),
     "fuelmi_bspline_dev_check_trajs": (C.c_int, [_P, C.POINTER(TrajChkCfg), _dp, _ip, _ip, _dp, _ip, _ip, _dp, _dp, _ip, _dp]),
     "fuelmi_traj_check_plan": (C.c_int, [C.POINTER(TrajChkCfg), _ip]),
     "fuelmi_map_sample_trajs": (C.c_int, [_P, C.POINTER(TrajSmpCfg), C.c_int, _ip, _dp, _dp, _ip, _dp, _dp, _dp, _ip, _dp,
                                           _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "fuelmi_map_sample_trajs_knots": (C.c_int, [_P, C.POINTER(TrajSmpCfg), C.c_int, _ip, _dp, _dp, _ip, _dp, _dp, _dp, _ip,
+                                                _dp, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "fuelmi_bspline_dev_sample_trajs": (C.c_int, [_P, C.POINTER(TrajSmpCfg), _ip, _dp, _dp, _dp, _ip, _dp, _ip, _dp, _dp,
                                                   _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "fuelmi_traj_sample_plan": (C.c_int, [C.POINTER(TrajSmpCfg), _ip]),
@@ -427,6 +434,8 @@ SYMBOLS = {
                                           _ip]),
     "fuelmi_bspline_dev_adjust_trajs": (C.c_int, [_P, C.POINTER(TrajAdjCfg), _dp, _dp, _ip, _ip, _dp, _dp, _dp, _ip]),
     "fuelmi_traj_adjust_plan": (C.c_int, [C.POINTER(TrajAdjCfg), _ip]),
+    "fuelmi_bspline_dev_set_knot_source": (C.c_int, [_P, C.c_int]),
+    "fuelmi_bspline_dev_knot_source": (C.c_int, [_P]),
     "fuelmi_map_extract_cloud": (C.c_int, [_P, C.POINTER(CloudCfg), C.c_void_p, C.c_int, _ip]),
     "fuelmi_cloud_plan": (C.c_int, [_ip, _ip, _ip, _ip]),
     "fuelmi_map_cloud_times": (C.c_int, [_P, _dp]),

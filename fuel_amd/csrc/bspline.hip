@@ -1192,7 +1192,7 @@ extern "C" int fuelmi_bspline_dev_optimize_timed(fuelmi_bspline_dev* b, int max_
   HIPCHK(hipMemcpyAsync(ev.data(), b->opt_evals, C * sizeof(int), hipMemcpyDeviceToHost, m->stream));
   HIPCHK(hipStreamSynchronize(m->stream));
   if (evals_out) memcpy(evals_out, ev.data(), C * sizeof(int));
-  b->opt_valid = true;
+  opt_set_valid(b, true);
   return FUELMI_OK;
 }
 
@@ -1435,7 +1435,7 @@ extern "C" int fuelmi_bspline_dev_load_samples(fuelmi_bspline_dev* b, int n_poin
   BsplineArgs& A = b->a;
   const int degree = A.cfg.bspline_degree;
   ARGCHK(A.dim == 3 && degree >= 3 && degree <= 5 && n_points >= 2 && n_points + degree - 1 == A.N);
-  b->opt_valid = false;
+  opt_set_valid(b, false);
   fuelmi_map* m = b->map;
   HIPCHK(hipSetDevice(m->device));
   const size_t C = (size_t)A.C, K = (size_t)n_points;

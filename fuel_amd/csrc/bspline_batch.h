@@ -42,6 +42,11 @@ struct fuelmi_bspline_dev {
   double* pin_out[2] = {nullptr, nullptr};
   hipEvent_t ev_out[2] = {nullptr, nullptr};
   bool opt_valid = false;    // opt_x holds the solve of what the batch holds now (a reload clears it)
+  // the knots fuelmi_bspline_dev_adjust_trajs left for that solve: [C][N + degree + 1], allocated once (in allocs);
+  // knot_source says whether check_trajs / sample_trajs / plan_yaws read them.  Only opt_set_valid changes opt_valid.
+  double* adj_knots = nullptr;
+  bool adj_valid = false;
+  int knot_source = FUELMI_KNOTS_UNIFORM;
   // per-call scratch, reserved on the map's stream (every kernel that reads it runs there); no pointer into it
   // outlives the call that carved it
   DevScratch fit_in;   // fuelmi_bspline_dev_load_*: ts | points | derivs, then the loader's own arrays
@@ -76,6 +81,19 @@ struct FitArgs {
 FitArgs fit_args(const fuelmi_bspline_dev* b, double* ts, double* points, double* derivs, int* skip);
 int fit_launch(fuelmi_map* m, const FitArgs& F, hipStream_t st = nullptr);
 SplineSrc opt_spline_src(const fuelmi_bspline_dev* b);
+// ... with the retained knots while the batch's knot source is FUELMI_KNOTS_ADJUSTED (the three calls that read them)
+inline SplineSrc opt_spline_src_knots(const fuelmi_bspline_dev* b) {
+  SplineSrc s = opt_spline_src(b);
+  if (b->knot_source == FUELMI_KNOTS_ADJUSTED && b->adj_valid && b->adj_knots)
+    s.knots = b->adj_knots, s.knots_stride = (size_t)b->a.N + b->a.cfg.bspline_degree + 1;
+  return s;
+}
+// a reload (false) or a new solve (true): either way the retained knots belong to an earlier solve
+inline void opt_set_valid(fuelmi_bspline_dev* b, bool valid) {
+  b->opt_valid = valid;
+  b->adj_valid = false;
+  b->knot_source = FUELMI_KNOTS_UNIFORM;
+}
 
 // ---- a SplineSrc from the caller's host arrays n_ctrl [n], pos_ctrl [n][max_ctrl][3], knot_span [n] -----------------
 // the arguments: every n_ctrl in degree + 1 .. max_ctrl, every knot span finite and positive (knots_given: the entry
@@ -88,6 +106,20 @@ inline int spline_src_check(int n_prob, int degree, int max_ctrl, const int* n_c
     if (!knots_given) ARGCHK(std::isfinite(knot_span[b]) && knot_span[b] > 0.0);
     const double* P = pos_ctrl + (size_t)b * max_ctrl * 3;
     for (int k = 0; k < 3 * n_ctrl[b]; ++k) ARGCHK(std::fabs(P[k]) < 1e7);
+  }
+  return FUELMI_OK;
+}
+// whole knot vectors knots [n][max_ctrl + degree + 1] given in place of spans (n_ctrl null: every problem has n_all
+// control points): each problem's n_ctrl + degree + 1 knots finite and strictly increasing.  More than the reference
+// asks, which asks nothing and divides by their differences.
+inline int spline_knots_check(int n_prob, int degree, int max_ctrl, const int* n_ctrl, int n_all, const double* knots) {
+  ARGCHK(knots);
+  const size_t ks = (size_t)max_ctrl + degree + 1;
+  for (int b = 0; b < n_prob; ++b) {
+    const double* u = knots + (size_t)b * ks;
+    const int m = (n_ctrl ? n_ctrl[b] : n_all) + degree;
+    ARGCHK(std::isfinite(u[0]));
+    for (int j = 1; j <= m; ++j) ARGCHK(std::isfinite(u[j]) && u[j - 1] < u[j]);
   }
   return FUELMI_OK;
 }

@@ -818,7 +818,7 @@ extern "C" int fuelmi_bspline_dev_load_kino(fuelmi_bspline_dev* b, const fuelmi_
   }
   fuelmi_map* m = b->map;
   ARGCHK(m);
-  b->opt_valid = false;
+  opt_set_valid(b, false);
   HIPCHK(hipSetDevice(m->device));
   const size_t C = (size_t)A.C, K = (size_t)n_points;
   hipStream_t st = m->stream;

@@ -519,7 +519,7 @@ extern "C" int fuelmi_bspline_dev_load_local_segments(
   }
   fuelmi_map* m = b->map;
   ARGCHK(m);
-  b->opt_valid = false;
+  opt_set_valid(b, false);
   HIPCHK(hipSetDevice(m->device));
   hipStream_t st = m->stream;
   const size_t nt = (size_t)n_traj, C = (size_t)Ab.C, K = (size_t)cfg.max_points;

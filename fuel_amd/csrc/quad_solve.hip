@@ -665,7 +665,7 @@ extern "C" int fuelmi_bspline_dev_solve_quadratic(fuelmi_bspline_dev* b, const f
   Q.guide = up_guide ? d_guide : A.guide_pts, Q.guide_stride = ng * 3;
   Q.n_waypt = nullptr, Q.n_waypt_all = A.n_waypt, Q.waypts = A.waypoints, Q.waypt_idx = A.waypt_idx;
   Q.x_next = const_cast<double*>(A.x), Q.x_next_stride = (size_t)A.nvar, Q.pt_dist_next = const_cast<double*>(A.pt_dist);
-  b->opt_valid = false;  // opt_x no longer is the solve of what the batch holds
+  opt_set_valid(b, false);  // opt_x no longer is the solve of what the batch holds
   {
     StageScope sc(m, FUELMI_K_BSPLINE);
     const int rc = quad_launch(st, Q);

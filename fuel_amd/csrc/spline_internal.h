@@ -1,4 +1,4 @@
-// spline_internal.h -- NonUniformBspline's evaluation on the device, shared by the kernels that read a batch of uniform
+// spline_internal.h -- NonUniformBspline's evaluation on the device, shared by the kernels that read a batch of
 // position splines (yaw_plan.hip, traj_check.hip, traj_sample.hip, traj_adjust.hip, collide_range.hip) or one spline a
 // state (local_segment.hip): where a problem's spline lies, its knots, its evaluation, its derivative splines.  f64, the
 // reference's operations in the reference's order.
@@ -15,6 +15,8 @@ struct SplineSrc {
   size_t pos_stride;
   const double* knot;       // problem b: knot[b * knot_stride]
   size_t knot_stride;
+  const double* knots;      // null: uniform knots of the span above.  Else problem b's whole knot vector u[0 .. n + p] at
+  size_t knots_stride;      // knots + b * knots_stride, and the span is not read (k_traj_check, k_traj_sample, k_yaw_plan)
 };
 
 // problem b of a batch: its number of control points, its knot span, its control points [n][3].  Three reads, so that a
@@ -29,6 +31,9 @@ __device__ __forceinline__ bool spline_sane(double dt, int n, int p, int max_ctr
   return dt > 0.0 && isfinite(dt) && n >= p + 1 && n <= max_ctrl;
 }
 
+// the span a kernel tests where whole knot vectors are given and none is read
+__device__ __forceinline__ double spline_dt_or_one(const SplineSrc& s, int b) { return s.knots ? 1.0 : spline_dt(s, b); }
+
 // doubles of one wave's knot block in LDS: n + p + 1 <= max_ctrl + 6 knots, kept a multiple of 16 bytes
 __host__ __device__ inline int spline_knot_stride(int max_ctrl) { return (max_ctrl + 6 + 1) & ~1; }
 
@@ -42,6 +47,29 @@ __device__ __forceinline__ void spline_uniform_knots(double* u, int p, int n, do
     acc = acc + dt;
     u[i] = acc;
   }
+}
+
+// problem b's knots into its wave's block u[0 .. n + p], by the 64 lanes of that wave; sane: spline_sane of the problem
+// (false for a wave without one; the same in every lane).  Returns whether the wave may evaluate on u, the same answer in
+// every lane.  No whole knot vectors: lane 0 accumulates the uniform ones, as above.  Else every lane copies its share
+// and tests it -- finite, and above the knot in front of it (what the host asks of given knots wherever it sees them; a
+// device batch's it does not see) -- and a ballot joins the lanes: one bad knot and the problem is a bad spline.  The
+// caller's barrier stands between these writes and the first read.
+__device__ __forceinline__ bool spline_stage_knots(const SplineSrc& s, int b, double* u, int p, int n, double dt, int lane,
+                                                   bool sane) {
+  if (!s.knots) {
+    if (sane && lane == 0) spline_uniform_knots(u, p, n, dt);
+    return sane;
+  }
+  if (!sane) return false;
+  const double* kin = s.knots + (size_t)b * s.knots_stride;
+  bool bad = false;
+  for (int j = lane; j <= n + p; j += 64) {
+    const double v = kin[j];
+    u[j] = v;
+    if (!isfinite(v) || (j > 0 && !(kin[j - 1] < v))) bad = true;
+  }
+  return __ballot(bad) == 0;
 }
 
 // the clamp and the knot search of evaluateDeBoor (non_uniform_bspline.cpp:52-57) for evaluateDeBoorT(t) of a spline of

@@ -552,13 +552,8 @@ int trajadj_check(const fuelmi_trajadj_cfg* cfg, int n_prob, bool host_spline, i
     if (rc) return rc;
   }
   if (io.knots_in) {
-    const size_t ks = (size_t)cfg->max_ctrl + p + 1;
-    for (int b = 0; b < n_prob; ++b) {
-      const double* u = io.knots_in + (size_t)b * ks;
-      const int m = (host_spline ? io.n_ctrl[b] : n_all) + p;
-      ARGCHK(std::isfinite(u[0]));
-      for (int j = 1; j <= m; ++j) ARGCHK(std::isfinite(u[j]) && u[j - 1] < u[j]);
-    }
+    const int rc = spline_knots_check(n_prob, p, cfg->max_ctrl, host_spline ? io.n_ctrl : nullptr, n_all, io.knots_in);
+    if (rc) return rc;
   }
   for (int b = 0; b < n_prob; ++b) {
     if (io.ratio_in) ARGCHK(std::isfinite(io.ratio_in[b]));
@@ -574,8 +569,9 @@ size_t trajadj_bytes(const fuelmi_trajadj_cfg* cfg, int n_prob, bool host_spline
 }
 
 // uploads, the launches on stream st, the results into the caller's arrays and the wait.  A device batch presets A.src.
+// keep: null, or where a device batch retains the final knots [n_prob][max_ctrl + degree + 1] (copied on the device).
 int trajadj_run(hipStream_t st, const fuelmi_trajadj_cfg* cfg, int n_prob, bool host_spline, const TrajAdjIO& io, TrajAdjArgs& A,
-                unsigned char* scratch) {
+                unsigned char* scratch, double* keep = nullptr) {
   const fuelmi_trajadj_cfg& c = *cfg;
   const size_t n = (size_t)n_prob, ks = (size_t)c.max_ctrl + c.degree + 1;
   A.cfg = c;
@@ -604,6 +600,7 @@ int trajadj_run(hipStream_t st, const fuelmi_trajadj_cfg* cfg, int n_prob, bool 
   HIPCHK(down(io.info, A.info, n * FUELMI_TRAJADJ_NI * sizeof(int)));
   HIPCHK(down(io.metrics, A.metrics, n * FUELMI_TRAJADJ_NM * sizeof(double)));
   HIPCHK(down(io.knots_out, A.knots_out, n * ks * sizeof(double)));
+  if (keep) HIPCHK(hipMemcpyAsync(keep, A.knots_out, n * ks * sizeof(double), hipMemcpyDeviceToDevice, st));
   if (A.samples) HIPCHK(down(io.samples, A.samples, n * c.max_samples * 3 * sizeof(double)));
   if (A.best) HIPCHK(down(io.best, A.best, (size_t)c.n_group * sizeof(int)));
   HIPCHK(stream_wait(st));
@@ -668,8 +665,36 @@ extern "C" int fuelmi_bspline_dev_adjust_trajs(fuelmi_bspline_dev* b, const fuel
     const int rc = b->adj_dev.reserve(m->stream, trajadj_bytes(&sc, A.C, false, io));
     if (rc) return rc;
   }
+  if (!b->adj_knots) {  // the knots this call leaves for check_trajs / sample_trajs / plan_yaws: once, freed with the batch
+    void* d = nullptr;
+    HIPCHK(hipMalloc(&d, (size_t)A.C * ((size_t)A.N + sc.degree + 1) * sizeof(double)));
+    b->allocs.push_back(d);
+    b->adj_knots = (double*)d;
+  }
+  b->adj_valid = false;
   TrajAdjArgs T;
   memset(&T, 0, sizeof(T));
   T.src = opt_spline_src(b);
-  return trajadj_run(m->stream, &sc, A.C, false, io, T, b->adj_dev.base());
+  const int rc = trajadj_run(m->stream, &sc, A.C, false, io, T, b->adj_dev.base(), b->adj_knots);
+  if (rc) {
+    b->knot_source = FUELMI_KNOTS_UNIFORM;
+    return rc;
+  }
+  b->adj_valid = true;
+  return FUELMI_OK;
+}
+
+extern "C" int fuelmi_bspline_dev_set_knot_source(fuelmi_bspline_dev* b, int source) {
+  ARGCHK(b);
+  ARGCHK(source == FUELMI_KNOTS_UNIFORM || source == FUELMI_KNOTS_ADJUSTED);
+  if (source == FUELMI_KNOTS_ADJUSTED && !(b->opt_valid && b->adj_valid && b->adj_knots)) {
+    fuelmi_set_error("knot source: no fuelmi_bspline_dev_adjust_trajs has run since the batch's last solve");
+    return FUELMI_EINVAL;
+  }
+  b->knot_source = source;
+  return FUELMI_OK;
+}
+
+extern "C" int fuelmi_bspline_dev_knot_source(const fuelmi_bspline_dev* b) {
+  return b ? b->knot_source : FUELMI_KNOTS_UNIFORM;
 }

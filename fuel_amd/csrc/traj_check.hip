@@ -11,12 +11,13 @@
 // each lane repeats the window's additions of `step` up to its own sample (lane 63's value plus one addition is the next
 // window's base), evaluates its point by the literal de Boor recursion, reads its bit and takes r_(k-1) from the lane
 // below (lane 0: lane 63 of the previous window).  Three ballots and a count of trailing zeros pick the first event.
-// Knots are staged in LDS by the accumulated additions (one block per wave); control points are read from global memory
+// Knots are staged in LDS (one block per wave), by the accumulated additions or copied and checked as given; control points are read from global memory
 // through L2: a window touches p + 1 neighbouring points per lane, 24 B each, and neighbouring lanes share them, so
 // staging up to 24 KiB per problem would cost more than it saves.  All f64, -ffp-contract=off.  A result does not depend
 // on the problem's place in the batch: the only workgroup-wide step is the barrier behind the knots.
-// Behind the kernel, the two entries that share its checks, layout and trajchk_run: fuelmi_map_check_trajs (splines from
-// the host) and fuelmi_bspline_dev_check_trajs (the splines a device batch's last solve left, bspline_batch.h).
+// Behind the kernel, the entries that share its checks, layout and trajchk_run: fuelmi_map_check_trajs and
+// fuelmi_map_check_trajs_knots (splines from the host, uniform or on given knots) and fuelmi_bspline_dev_check_trajs (the
+// splines a device batch's last solve left, on the knots its adjustment left if the batch says so, bspline_batch.h).
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -90,12 +91,11 @@ __global__ void __launch_bounds__(TC_WIN * TC_WAVES) k_traj_check(Geo g, TrajChk
   double dt = 0.0;
   if (live) {
     n = spline_n(T.src, b);
-    dt = spline_dt(T.src, b);
+    dt = spline_dt_or_one(T.src, b);
   }
-  const bool sane = live && spline_sane(dt, n, p, T.cfg.max_ctrl);
 
   // 1. knots; every wave of the workgroup meets at the barrier, with or without a problem
-  if (sane && lane == 0) spline_uniform_knots(u, p, n, dt);
+  const bool sane = spline_stage_knots(T.src, b, u, p, n, dt, lane, live && spline_sane(dt, n, p, T.cfg.max_ctrl));
   __syncthreads();
   if (!live) return;
   if (!sane) {
@@ -178,6 +178,8 @@ struct TrajChkIO {
   const double *pos_ctrl, *knot_span, *t_now;
   int *status, *safe, *n_samples, *hit_index, *end_reason;
   double *distance, *hit_t, *hit_pos, *duration;
+  const double* knots = nullptr;  // fuelmi_map_check_trajs_knots: [n_prob][max_ctrl + degree + 1] in place of knot_span
+  bool knots_given = false;
 };
 
 int trajchk_check(const fuelmi_trajchk_cfg* cfg, int n_prob, const TrajChkIO& io) {
@@ -190,8 +192,12 @@ int trajchk_check(const fuelmi_trajchk_cfg* cfg, int n_prob, const TrajChkIO& io
   ARGCHK(io.t_now);
   for (int b = 0; b < n_prob; ++b) ARGCHK(std::isfinite(io.t_now[b]));
   if (io.n_ctrl) {  // (a device batch: its variables are checked by the kernel)
-    const int rc = spline_src_check(n_prob, cfg->degree, cfg->max_ctrl, io.n_ctrl, io.pos_ctrl, io.knot_span);
+    const int rc = spline_src_check(n_prob, cfg->degree, cfg->max_ctrl, io.n_ctrl, io.pos_ctrl, io.knot_span, io.knots_given);
     if (rc) return rc;
+    if (io.knots_given) {
+      const int rck = spline_knots_check(n_prob, cfg->degree, cfg->max_ctrl, io.n_ctrl, 0, io.knots);
+      if (rck) return rck;
+    }
   }
   ARGCHK(io.status && io.safe && io.distance && io.n_samples && io.hit_index && io.hit_t && io.hit_pos && io.end_reason &&
          io.duration);
@@ -243,12 +249,10 @@ extern "C" int fuelmi_traj_check_plan(const fuelmi_trajchk_cfg* cfg, int out3[3]
   return FUELMI_OK;
 }
 
-extern "C" int fuelmi_map_check_trajs(fuelmi_map* m, const fuelmi_trajchk_cfg* cfg, int n_prob, const int* n_ctrl,
-                                      const double* pos_ctrl, const double* knot_span, const double* t_now, int* status,
-                                      int* safe, double* distance, int* n_samples, int* hit_index, double* hit_t,
-                                      double* hit_pos, int* end_reason, double* duration) {
-  const TrajChkIO io = {n_ctrl,    pos_ctrl,   knot_span, t_now, status,  safe,    n_samples,
-                        hit_index, end_reason, distance,  hit_t, hit_pos, duration};
+// the host route of both entries: io's splines uploaded, uniform (knot_span) or on given knots
+static int trajchk_host(fuelmi_map* m, const fuelmi_trajchk_cfg* cfg, int n_prob, const TrajChkIO& io) {
+  const int* n_ctrl = io.n_ctrl;
+  const double *pos_ctrl = io.pos_ctrl, *knot_span = io.knot_span, *t_now = io.t_now;
   {  // every argument on the host, before the map is touched
     ARGCHK(n_prob <= 0 || n_ctrl);
     const int rc = trajchk_check(cfg, n_prob, io);
@@ -264,10 +268,12 @@ extern "C" int fuelmi_map_check_trajs(fuelmi_map* m, const fuelmi_trajchk_cfg* c
   ResultBlock R(16);
   trajchk_results(R, T, n_prob, io);
   ARGCHK(!R.overflow);
-  double* d_now;
+  const size_t ks = (size_t)cfg->max_ctrl + cfg->degree + 1;
+  double *d_now, *d_knots = nullptr;
   auto layout = [&](unsigned char* base) {
     BlockLayout L(base, 16);
     spline_src_take(L, n, cfg->max_ctrl, T.src);
+    if (io.knots_given) d_knots = L.take<double>(n * ks);
     d_now = L.take<double>(n);
     R.place(L);
     return L.size();
@@ -280,11 +286,34 @@ extern "C" int fuelmi_map_check_trajs(fuelmi_map* m, const fuelmi_trajchk_cfg* c
     const int rc = spline_src_upload(st, T.src, n, cfg->max_ctrl, n_ctrl, pos_ctrl, knot_span);
     if (rc) return rc;
   }
+  if (io.knots_given) {
+    HIPCHK(hipMemcpyAsync(d_knots, io.knots, n * ks * sizeof(double), hipMemcpyHostToDevice, st));
+    T.src.knots = d_knots, T.src.knots_stride = ks;
+  }
   HIPCHK(hipMemcpyAsync(d_now, t_now, n * sizeof(double), hipMemcpyHostToDevice, st));
   T.cfg = *cfg;
   T.n_prob = n_prob;
   T.t_now = d_now;
   return trajchk_run(m, T, R, io);
+}
+
+extern "C" int fuelmi_map_check_trajs(fuelmi_map* m, const fuelmi_trajchk_cfg* cfg, int n_prob, const int* n_ctrl,
+                                      const double* pos_ctrl, const double* knot_span, const double* t_now, int* status,
+                                      int* safe, double* distance, int* n_samples, int* hit_index, double* hit_t,
+                                      double* hit_pos, int* end_reason, double* duration) {
+  const TrajChkIO io = {n_ctrl,    pos_ctrl,   knot_span, t_now, status,  safe,    n_samples,
+                        hit_index, end_reason, distance,  hit_t, hit_pos, duration};
+  return trajchk_host(m, cfg, n_prob, io);
+}
+
+// ... on whole knot vectors (fuelmi_map_adjust_trajs' knots_out as it stands) in place of the spans
+extern "C" int fuelmi_map_check_trajs_knots(fuelmi_map* m, const fuelmi_trajchk_cfg* cfg, int n_prob, const int* n_ctrl,
+                                            const double* pos_ctrl, const double* knots, const double* t_now, int* status,
+                                            int* safe, double* distance, int* n_samples, int* hit_index, double* hit_t,
+                                            double* hit_pos, int* end_reason, double* duration) {
+  const TrajChkIO io = {n_ctrl,     pos_ctrl, nullptr, t_now,   status,   safe,  n_samples, hit_index,
+                        end_reason, distance, hit_t,   hit_pos, duration, knots, true};
+  return trajchk_host(m, cfg, n_prob, io);
 }
 
 // the safety check of a device batch's optimised position splines, read from the variables the last solve left on the
@@ -328,7 +357,7 @@ extern "C" int fuelmi_bspline_dev_check_trajs(fuelmi_bspline_dev* b, const fuelm
   HIPCHK(hipMemcpyAsync(d_now, t_now, C * sizeof(double), hipMemcpyHostToDevice, st));
   T.cfg = tc;
   T.n_prob = A.C;
-  T.src = opt_spline_src(b);
+  T.src = opt_spline_src_knots(b);
   T.t_now = d_now;
   return trajchk_run(m, T, R, io);
 }

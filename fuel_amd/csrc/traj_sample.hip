@@ -1,5 +1,5 @@
-// traj_sample.hip -- what the reference does with a finished trajectory, for a batch of problems (uniform position
-// spline, optional uniform yaw spline, a tape of sample times):
+// traj_sample.hip -- what the reference does with a finished trajectory, for a batch of problems (position spline,
+// uniform or on given knots, optional uniform yaw spline, a tape of sample times):
 //   FUELMI_TRAJSMP_COMMAND  traj_server's cmdCallback (plan_manage/src/traj_server.cpp:257-343): position, velocity,
 //                           acceleration, jerk, yaw and yaw rate at each tick, and the flight record (:328-339)
 //   FUELMI_TRAJSMP_STATE    the FSM's replan start state (exploration_manager/src/fast_exploration_fsm.cpp:86-95)
@@ -7,15 +7,17 @@
 // of evaluateDeBoor give every derivative the same span (spline_internal.h), and the p + 1 position points of that span
 // give the points each derivative reads there by getDerivativeControlPoints' own operations.
 //
-// One 64-lane wave per problem, TS_WAVES problems per workgroup.  Lane 0 stages the knots of both splines in LDS by the
-// accumulated additions (one block per wave); control points are read from global memory through L2 (traj_check.hip
+// One 64-lane wave per problem, TS_WAVES problems per workgroup.  The knots of both splines are staged in LDS (one block
+// per wave): by lane 0's accumulated additions, or the position spline's copied and checked as given; control points are read from global memory through L2 (traj_check.hip
 // says why).  The lanes take a window of 64 consecutive sample times, one each.  The flight record is a chain through
 // the samples -- each is compared with the last one PUSHED -- so behind every window all lanes walk its 64 samples in
 // order by lane reads, each lane making the same additions, and lane 0 stores the record at the end: the sums are the
 // reference's, term by term.  All f64, -ffp-contract=off.  A result does not depend on the problem's place in the
 // batch: the only workgroup-wide step is the barrier behind the knots.
-// Behind the kernel, the two entries that share its checks, layout and trajsmp_run: fuelmi_map_sample_trajs (splines from
-// the host) and fuelmi_bspline_dev_sample_trajs (the splines a device batch's last solve left, bspline_batch.h).
+// Behind the kernel, the entries that share its checks, layout and trajsmp_run: fuelmi_map_sample_trajs and
+// fuelmi_map_sample_trajs_knots (splines from the host, the position spline uniform or on given knots) and
+// fuelmi_bspline_dev_sample_trajs (the splines a device batch's last solve left, on the knots its adjustment left if the
+// batch says so, bspline_batch.h).
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -61,18 +63,17 @@ __global__ void __launch_bounds__(TS_WIN * TS_WAVES) k_traj_sample(TrajSmpArgs A
   double dt = 0.0, dty = 0.0;
   if (live) {
     n = spline_n(A.src, b);
-    dt = spline_dt(A.src, b);
+    dt = spline_dt_or_one(A.src, b);
     if (A.n_yaw && A.cfg.max_yaw_ctrl > 0) ny = A.n_yaw[b];
     if (ny > 0) dty = A.yaw_dt[b];
   }
-  const bool sane = live && spline_sane(dt, n, p, A.cfg.max_ctrl) &&
-                    (ny <= 0 || (dty > 0.0 && isfinite(dty) && py >= 3 && py <= 5 && ny >= py + 1 && ny <= A.cfg.max_yaw_ctrl));
+  const bool sane_in = live && spline_sane(dt, n, p, A.cfg.max_ctrl) &&
+                       (ny <= 0 || (dty > 0.0 && isfinite(dty) && py >= 3 && py <= 5 && ny >= py + 1 && ny <= A.cfg.max_yaw_ctrl));
 
-  // 1. knots; every wave of the workgroup meets at the barrier, with or without a problem
-  if (sane && lane == 0) {
-    spline_uniform_knots(u, p, n, dt);
-    if (ny > 0) spline_uniform_knots(uy, py, ny, dty);
-  }
+  // 1. knots (the yaw spline's are always uniform); every wave of the workgroup meets at the barrier, with or without
+  // a problem
+  const bool sane = spline_stage_knots(A.src, b, u, p, n, dt, lane, sane_in);
+  if (sane && lane == 0 && ny > 0) spline_uniform_knots(uy, py, ny, dty);
   __syncthreads();
   if (!live) return;
 
@@ -222,6 +223,8 @@ struct TrajSmpIO {
   const double* t;
   int* status;
   double *pos, *vel, *acc, *jerk, *yaw, *yawdot, *yawddot, *duration, *flight;
+  const double* knots = nullptr;  // fuelmi_map_sample_trajs_knots: [n_prob][max_ctrl + degree + 1] in place of knot_span
+  bool knots_given = false;
 };
 
 // the scratch block (a BlockLayout over the map's or the batch's DevScratch): the inputs the host hands over, the
@@ -231,6 +234,7 @@ size_t ts_layout(const fuelmi_trajsmp_cfg& c, int n_prob, bool host_spline, cons
   const size_t n = (size_t)n_prob, s = n * (size_t)c.max_t;
   BlockLayout L(base, 16);
   if (host_spline) spline_src_take(L, n, c.max_ctrl, A.src);
+  if (io.knots_given) A.src.knots_stride = (size_t)c.max_ctrl + c.degree + 1, A.src.knots = L.take<double>(n * A.src.knots_stride);
   const bool yaw = io.n_yaw_ctrl && c.max_yaw_ctrl > 0;
   A.n_yaw = yaw ? L.take<int>(n) : nullptr;
   A.yaw = yaw ? L.take<double>(n * c.max_yaw_ctrl) : nullptr;
@@ -268,8 +272,12 @@ int trajsmp_check(const fuelmi_trajsmp_cfg* cfg, int n_prob, bool host_spline, c
   const int p = cfg->degree, py = cfg->yaw_degree;
   if (cfg->mode == FUELMI_TRAJSMP_STATE) ARGCHK(!io.t_stop && !io.flight);  // cmdCallback's alone
   if (host_spline) {
-    const int rc = spline_src_check(n_prob, p, cfg->max_ctrl, io.n_ctrl, io.pos_ctrl, io.knot_span);
+    const int rc = spline_src_check(n_prob, p, cfg->max_ctrl, io.n_ctrl, io.pos_ctrl, io.knot_span, io.knots_given);
     if (rc) return rc;
+    if (io.knots_given) {
+      const int rck = spline_knots_check(n_prob, p, cfg->max_ctrl, io.n_ctrl, 0, io.knots);
+      if (rck) return rck;
+    }
   }
   if (io.n_yaw_ctrl) {
     ARGCHK(cfg->max_yaw_ctrl > 0 && io.yaw_ctrl && io.yaw_dt);
@@ -319,6 +327,7 @@ int trajsmp_run(hipStream_t st, const fuelmi_trajsmp_cfg* cfg, int n_prob, bool 
     const int rc = spline_src_upload(st, A.src, n, c.max_ctrl, io.n_ctrl, io.pos_ctrl, io.knot_span);
     if (rc) return rc;
   }
+  if (io.knots_given) HIPCHK(up(A.src.knots, io.knots, n * A.src.knots_stride * sizeof(double)));
   if (A.n_yaw) {
     HIPCHK(up(A.n_yaw, io.n_yaw_ctrl, n * sizeof(int)));
     HIPCHK(up(A.yaw, io.yaw_ctrl, n * c.max_yaw_ctrl * sizeof(double)));
@@ -356,14 +365,8 @@ extern "C" int fuelmi_traj_sample_plan(const fuelmi_trajsmp_cfg* cfg, int out3[3
   return FUELMI_OK;
 }
 
-extern "C" int fuelmi_map_sample_trajs(fuelmi_map* m, const fuelmi_trajsmp_cfg* cfg, int n_prob, const int* n_ctrl,
-                                       const double* pos_ctrl, const double* knot_span, const int* n_yaw_ctrl,
-                                       const double* yaw_ctrl, const double* yaw_dt, const double* t_stop,
-                                       const int* n_t, const double* t, int* status, double* pos, double* vel,
-                                       double* acc, double* jerk, double* yaw, double* yawdot, double* yawddot,
-                                       double* duration, double* flight) {
-  const TrajSmpIO io = {n_ctrl, pos_ctrl, knot_span, n_yaw_ctrl, yaw_ctrl, yaw_dt, t_stop, n_t,     t,     status,
-                        pos,    vel,      acc,       jerk,       yaw,      yawdot, yawddot, duration, flight};
+// the host route of both entries: io's splines uploaded, uniform (knot_span) or on given knots
+static int trajsmp_host(fuelmi_map* m, const fuelmi_trajsmp_cfg* cfg, int n_prob, const TrajSmpIO& io) {
   bool nothing = true;
   {  // every argument on the host, before the map is touched
     const int rc = trajsmp_check(cfg, n_prob, true, io, &nothing);
@@ -380,6 +383,30 @@ extern "C" int fuelmi_map_sample_trajs(fuelmi_map* m, const fuelmi_trajsmp_cfg* 
   TrajSmpArgs A;
   memset(&A, 0, sizeof(A));
   return trajsmp_run(st, cfg, n_prob, true, io, A, m->trajsmp_dev.base());
+}
+
+extern "C" int fuelmi_map_sample_trajs(fuelmi_map* m, const fuelmi_trajsmp_cfg* cfg, int n_prob, const int* n_ctrl,
+                                       const double* pos_ctrl, const double* knot_span, const int* n_yaw_ctrl,
+                                       const double* yaw_ctrl, const double* yaw_dt, const double* t_stop,
+                                       const int* n_t, const double* t, int* status, double* pos, double* vel,
+                                       double* acc, double* jerk, double* yaw, double* yawdot, double* yawddot,
+                                       double* duration, double* flight) {
+  const TrajSmpIO io = {n_ctrl, pos_ctrl, knot_span, n_yaw_ctrl, yaw_ctrl, yaw_dt, t_stop, n_t,     t,     status,
+                        pos,    vel,      acc,       jerk,       yaw,      yawdot, yawddot, duration, flight};
+  return trajsmp_host(m, cfg, n_prob, io);
+}
+
+// ... the position splines on whole knot vectors (fuelmi_map_adjust_trajs' knots_out as it stands) in place of the
+// spans; the yaw splines stay uniform (the reference builds every one with setUniformBspline)
+extern "C" int fuelmi_map_sample_trajs_knots(fuelmi_map* m, const fuelmi_trajsmp_cfg* cfg, int n_prob, const int* n_ctrl,
+                                             const double* pos_ctrl, const double* knots, const int* n_yaw_ctrl,
+                                             const double* yaw_ctrl, const double* yaw_dt, const double* t_stop,
+                                             const int* n_t, const double* t, int* status, double* pos, double* vel,
+                                             double* acc, double* jerk, double* yaw, double* yawdot, double* yawddot,
+                                             double* duration, double* flight) {
+  const TrajSmpIO io = {n_ctrl, pos_ctrl, nullptr, n_yaw_ctrl, yaw_ctrl, yaw_dt,  t_stop,   n_t,    t,     status, pos,
+                        vel,    acc,      jerk,    yaw,        yawdot,   yawddot, duration, flight, knots, true};
+  return trajsmp_host(m, cfg, n_prob, io);
 }
 
 // the batch route: a device batch's optimised position splines sampled as commands or replan states, read from
@@ -412,6 +439,6 @@ extern "C" int fuelmi_bspline_dev_sample_trajs(fuelmi_bspline_dev* b, const fuel
   }
   TrajSmpArgs T;
   memset(&T, 0, sizeof(T));
-  T.src = opt_spline_src(b);
+  T.src = opt_spline_src_knots(b);
   return trajsmp_run(m->stream, &sc, A.C, false, io, T, b->smp_dev.base());
 }

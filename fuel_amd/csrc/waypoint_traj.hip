@@ -462,7 +462,7 @@ extern "C" int fuelmi_bspline_dev_load_waypoints(fuelmi_bspline_dev* b, const fu
   }
   fuelmi_map* m = b->map;
   ARGCHK(m);
-  b->opt_valid = false;
+  opt_set_valid(b, false);
   HIPCHK(hipSetDevice(m->device));
   const size_t C = (size_t)A.C, K = (size_t)n_points, maxw = (size_t)wc.max_way_points;
   WpTrajArgs W;

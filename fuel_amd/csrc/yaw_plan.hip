@@ -16,10 +16,13 @@
 // side, lane 0 factors by Cholesky and substitutes: the reference's NLopt run iterates towards this point.
 //
 // One wave of YP_NT lanes per problem, one lane per way-point (looped past YP_NT), all f64, -ffp-contract=off.  The
-// knots are staged in LDS by the accumulated additions; the unwrap chain and the factorisation are serial in lane 0
+// position knots are staged in LDS by the accumulated additions or copied and checked as given, the yaw spline's always by
+// the additions; the unwrap chain and the factorisation are serial in lane 0
 // (N <= 259).  A result does not depend on the problem's place in the batch.
-// Behind the kernel, the two entries that share its checks, argument fill, result layout and copy-out: fuelmi_map_plan_yaws
-// (through a query slot) and fuelmi_bspline_dev_plan_yaws (the splines a device batch's last solve left, bspline_batch.h).
+// Behind the kernel, the entries that share its checks, argument fill, result layout and copy-out: fuelmi_map_plan_yaws
+// and fuelmi_map_plan_yaws_knots (through a query slot, the position spline uniform or on given knots) and
+// fuelmi_bspline_dev_plan_yaws (the splines a device batch's last solve left, on the knots its adjustment left if the
+// batch says so, bspline_batch.h).
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -140,15 +143,14 @@ __global__ void __launch_bounds__(YP_NT) k_yaw_plan(YawArgs Y) {
   const bool follow = Y.cfg.mode == FUELMI_YAW_FOLLOW;
   const int p = Y.cfg.pos_degree;
   const int n = spline_n(Y.src, b);
-  const double dt = spline_dt(Y.src, b);
+  const double dt = spline_dt_or_one(Y.src, b);
   const double* C = spline_ctrl(Y.src, b);
-  if (!spline_sane(dt, n, p, Y.cfg.max_ctrl)) {
+
+  // 1. knots, duration = getTimeSum
+  if (!spline_stage_knots(Y.src, b, u, p, n, dt, tid, spline_sane(dt, n, p, Y.cfg.max_ctrl))) {
     yp_write(Y, b, tid, FUELMI_YAW_DEGENERATE, 0.0, 0, 0.0, 0, nullptr, 0, nullptr, 0.0, 0.0, nullptr, 3);
     return;
   }
-
-  // 1. knots, duration = getTimeSum
-  if (tid == 0) spline_uniform_knots(u, p, n, dt);
   __syncthreads();
   const double duration = u[n] - u[p];
 
@@ -393,6 +395,8 @@ struct YawIO {
   const double *pos_ctrl, *knot_span, *start_yaw, *end_yaw;
   int *status, *seg_num, *n_waypt;
   double *duration, *dt_yaw, *yaw_ctrl, *waypts, *end_yaw_out, *cost, *yawdot_ctrl, *yawddot_ctrl;  // the last two or null
+  const double* knots = nullptr;  // fuelmi_map_plan_yaws_knots: [n_prob][max_ctrl + pos_degree + 1] in place of knot_span
+  bool knots_given = false;
 };
 
 int yaw_check(const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob, const YawIO& io) {
@@ -413,8 +417,12 @@ int yaw_check(const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob
     if (cfg->mode == FUELMI_YAW_EXPLORE) ARGCHK(std::fabs(io.end_yaw[b]) <= 1e3);
   }
   if (io.n_ctrl) {  // (a device batch: its variables are checked by the kernel)
-    const int rc = spline_src_check(n_prob, cfg->pos_degree, cfg->max_ctrl, io.n_ctrl, io.pos_ctrl, io.knot_span);
+    const int rc = spline_src_check(n_prob, cfg->pos_degree, cfg->max_ctrl, io.n_ctrl, io.pos_ctrl, io.knot_span, io.knots_given);
     if (rc) return rc;
+    if (io.knots_given) {
+      const int rck = spline_knots_check(n_prob, cfg->pos_degree, cfg->max_ctrl, io.n_ctrl, 0, io.knots);
+      if (rck) return rck;
+    }
   }
   ARGCHK(io.status && io.duration && io.seg_num && io.dt_yaw && io.yaw_ctrl && io.n_waypt && io.waypts &&
          io.end_yaw_out && io.cost);
@@ -473,14 +481,11 @@ extern "C" int fuelmi_yaw_plan(const fuelmi_yaw_cfg* cfg, int out3[3]) {
   return FUELMI_OK;
 }
 
-// the host route: staged in a query slot's pinned block, launched on the slot's stream, copied out of the pinned block
-extern "C" int fuelmi_map_plan_yaws(fuelmi_map* m, const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob,
-                                    const int* n_ctrl, const double* pos_ctrl, const double* knot_span,
-                                    const double* start_yaw, const double* end_yaw, int* status, double* duration,
-                                    int* seg_num, double* dt_yaw, double* yaw_ctrl, int* n_waypt, double* waypts,
-                                    double* end_yaw_out, double* cost, double* yawdot_ctrl, double* yawddot_ctrl) {
-  const YawIO io = {n_ctrl, pos_ctrl, knot_span, start_yaw, end_yaw,     status, seg_num,     n_waypt,
-                    duration, dt_yaw, yaw_ctrl,  waypts,    end_yaw_out, cost,   yawdot_ctrl, yawddot_ctrl};
+// the host route of both entries: staged in a query slot's pinned block, launched on the slot's stream, copied out of the
+// pinned block; the position splines uniform (knot_span) or on given knots
+static int yaw_host(fuelmi_map* m, const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob, const YawIO& io) {
+  const int* n_ctrl = io.n_ctrl;
+  const double *pos_ctrl = io.pos_ctrl, *knot_span = io.knot_span, *start_yaw = io.start_yaw, *end_yaw = io.end_yaw;
   {  // every argument on the host, before the map is touched
     ARGCHK(n_prob <= 0 || n_ctrl);
     const int rc = yaw_check(w, cfg, n_prob, io);
@@ -495,12 +500,14 @@ extern "C" int fuelmi_map_plan_yaws(fuelmi_map* m, const fuelmi_bspline_cfg* w, 
   ResultBlock R(16);
   yaw_results(R, Y, io);
   ARGCHK(!R.overflow);
+  const size_t ks = maxc + cfg->pos_degree + 1;
   int* p_nc;
-  double *p_knot, *p_end, *p_pos, *p_start;
+  double *p_knot, *p_end, *p_pos, *p_start, *p_knots = nullptr;
   auto layout = [&](unsigned char* base) {  // the slot's pinned block: the inputs, then the results
     BlockLayout L(base, 16);
     p_nc = L.take<int>(n);
     p_knot = L.take<double>(n);
+    if (io.knots_given) p_knots = L.take<double>(n * ks);
     p_end = L.take<double>(n);
     p_pos = L.take<double>(n * maxc * 3);
     p_start = L.take<double>(n * 3);
@@ -514,7 +521,10 @@ extern "C" int fuelmi_map_plan_yaws(fuelmi_map* m, const fuelmi_bspline_cfg* w, 
   }
   layout(q.s->pin);
   memcpy(p_nc, n_ctrl, n * sizeof(int));
-  memcpy(p_knot, knot_span, n * sizeof(double));
+  if (knot_span)
+    memcpy(p_knot, knot_span, n * sizeof(double));
+  else
+    memset(p_knot, 0, n * sizeof(double));
   if (end_yaw)
     memcpy(p_end, end_yaw, n * sizeof(double));
   else
@@ -522,6 +532,10 @@ extern "C" int fuelmi_map_plan_yaws(fuelmi_map* m, const fuelmi_bspline_cfg* w, 
   memcpy(p_pos, pos_ctrl, n * maxc * 3 * sizeof(double));
   memcpy(p_start, start_yaw, n * 3 * sizeof(double));
   Y.src = {p_nc, 0, p_pos, maxc * 3, p_knot, 1};
+  if (io.knots_given) {
+    memcpy(p_knots, io.knots, n * ks * sizeof(double));
+    Y.src.knots = p_knots, Y.src.knots_stride = ks;
+  }
   Y.start_yaw = p_start, Y.end_yaw = p_end;
   {
     const int rc = yaw_launch(q.s->st, Y);
@@ -530,6 +544,28 @@ extern "C" int fuelmi_map_plan_yaws(fuelmi_map* m, const fuelmi_bspline_cfg* w, 
   HIPCHK(q.finish());
   R.scatter(R.base);
   return yaw_limit(Y, io);
+}
+
+extern "C" int fuelmi_map_plan_yaws(fuelmi_map* m, const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob,
+                                    const int* n_ctrl, const double* pos_ctrl, const double* knot_span,
+                                    const double* start_yaw, const double* end_yaw, int* status, double* duration,
+                                    int* seg_num, double* dt_yaw, double* yaw_ctrl, int* n_waypt, double* waypts,
+                                    double* end_yaw_out, double* cost, double* yawdot_ctrl, double* yawddot_ctrl) {
+  const YawIO io = {n_ctrl, pos_ctrl, knot_span, start_yaw, end_yaw,     status, seg_num,     n_waypt,
+                    duration, dt_yaw, yaw_ctrl,  waypts,    end_yaw_out, cost,   yawdot_ctrl, yawddot_ctrl};
+  return yaw_host(m, w, cfg, n_prob, io);
+}
+
+// ... the position splines on whole knot vectors (fuelmi_map_adjust_trajs' knots_out as it stands) in place of the
+// spans; the yaw spline that comes out is uniform, as the reference builds it
+extern "C" int fuelmi_map_plan_yaws_knots(fuelmi_map* m, const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob,
+                                          const int* n_ctrl, const double* pos_ctrl, const double* knots,
+                                          const double* start_yaw, const double* end_yaw, int* status, double* duration,
+                                          int* seg_num, double* dt_yaw, double* yaw_ctrl, int* n_waypt, double* waypts,
+                                          double* end_yaw_out, double* cost, double* yawdot_ctrl, double* yawddot_ctrl) {
+  const YawIO io = {n_ctrl,   pos_ctrl, nullptr,     start_yaw, end_yaw,     status,       seg_num, n_waypt, duration,
+                    dt_yaw,   yaw_ctrl, waypts,      end_yaw_out, cost,      yawdot_ctrl,  yawddot_ctrl, knots, true};
+  return yaw_host(m, w, cfg, n_prob, io);
 }
 
 // the batch route: the splines the batch's last solve left on the device; staged in yaw_dev on the map's stream, downloaded
@@ -577,7 +613,7 @@ extern "C" int fuelmi_bspline_dev_plan_yaws(fuelmi_bspline_dev* b, const fuelmi_
     HIPCHK(hipMemcpyAsync(d_end, end_yaw, C * sizeof(double), hipMemcpyHostToDevice, st));
   else
     HIPCHK(hipMemsetAsync(d_end, 0, C * sizeof(double), st));
-  Y.src = opt_spline_src(b);
+  Y.src = opt_spline_src_knots(b);
   Y.start_yaw = d_start, Y.end_yaw = d_end;
   {
     StageScope sc(m, FUELMI_K_BSPLINE);

@@ -98,6 +98,10 @@ public:
                      double end_yaw, bool lookfwd, double relax_time, Eigen::MatrixXd& yaw_ctrl, double& dt_yaw);
   int planYaw(const Eigen::MatrixXd& pos_ctrl, int pos_degree, double pos_dt, const Eigen::Vector3d& start_yaw,
               Eigen::MatrixXd& yaw_ctrl, double& dt_yaw, std::vector<double>* path_yaw);
+  // ... on a position spline whose knots were moved (setKnot): `knots` holds pos_ctrl.rows() + pos_degree + 1 of them,
+  // what adjustTime returns (fuelmi_map_plan_yaws_knots).  The yaw spline that comes out is uniform, as ever.
+  int planYaw(const Eigen::MatrixXd& pos_ctrl, int pos_degree, const Eigen::VectorXd& knots, const Eigen::Vector3d& start_yaw,
+              Eigen::MatrixXd& yaw_ctrl, double& dt_yaw, std::vector<double>* path_yaw);
 
   // addition: the body of FastPlannerManager::checkTrajCollision (plan_manage/src/planner_manager.cpp:96-118) in one
   // device call (fuelmi_map_check_trajs, include/fuelmi.h) on the uniform position spline (pos_ctrl rows, degree, knot
@@ -106,6 +110,10 @@ public:
   // the reference's value; `distance` is written only when the result is false, as the reference does.  A call that
   // fails, or a point the reference could not index (FUELMI_TRAJCHK_NONFINITE), is reported as a collision at distance 0.
   bool checkTrajCollision(const Eigen::MatrixXd& pos_ctrl, int degree, double dt, double t_now, double& distance);
+  // ... on the knots adjustTime returned (pos_ctrl.rows() + degree + 1 of them; fuelmi_map_check_trajs_knots): what the
+  // safety callback walks once local_data_.position_traj_ has been time-adjusted
+  bool checkTrajCollision(const Eigen::MatrixXd& pos_ctrl, int degree, const Eigen::VectorXd& knots, double t_now,
+                          double& distance);
 
   // addition: the two things the reference does with a finished trajectory, each in one device call
   // (fuelmi_map_sample_trajs, include/fuelmi.h) on the uniform position spline (pos_ctrl rows, degree, knot span dt) and
@@ -122,6 +130,16 @@ public:
                        Eigen::MatrixXd& jerk, Eigen::MatrixXd& yaw, double* flight8);
   bool replanState(const Eigen::MatrixXd& pos_ctrl, int degree, double dt, const Eigen::MatrixXd& yaw_ctrl, int yaw_degree,
                    double yaw_dt, double t_r, Eigen::Vector3d& start_pt, Eigen::Vector3d& start_vel,
+                   Eigen::Vector3d& start_acc, Eigen::Vector3d& start_yaw);
+  // ... with the position spline on the knots adjustTime returned (pos_ctrl.rows() + degree + 1 of them) -- traj_server's
+  // pos_traj.setKnot(knots) (traj_server.cpp:230) before it samples -- through fuelmi_map_sample_trajs_knots; the yaw
+  // spline stays uniform (Bspline.msg carries only yaw_dt)
+  bool evaluateCommand(const Eigen::MatrixXd& pos_ctrl, int degree, const Eigen::VectorXd& knots, const Eigen::MatrixXd& yaw_ctrl,
+                       int yaw_degree, double yaw_dt, const std::vector<double>& t, const double* t_stop,
+                       std::vector<int>& status, Eigen::MatrixXd& pos, Eigen::MatrixXd& vel, Eigen::MatrixXd& acc,
+                       Eigen::MatrixXd& jerk, Eigen::MatrixXd& yaw, double* flight8);
+  bool replanState(const Eigen::MatrixXd& pos_ctrl, int degree, const Eigen::VectorXd& knots, const Eigen::MatrixXd& yaw_ctrl,
+                   int yaw_degree, double yaw_dt, double t_r, Eigen::Vector3d& start_pt, Eigen::Vector3d& start_vel,
                    Eigen::Vector3d& start_acc, Eigen::Vector3d& start_yaw);
 
   // addition: the half of NonUniformBspline that moves knots and measures a spline (bspline/src/non_uniform_bspline.cpp

@@ -1336,11 +1336,22 @@ int BsplineOptimizer::planKinodynamic(const Eigen::Vector3d& start_pt, const Eig
 }
 
 // one fuelmi_map_plan_yaws problem; the outputs are touched only when its status is FUELMI_YAW_OK
+// a problem's whole knot vector for a _knots entry; false: not n_ctrl + degree + 1 of them
+static bool knots_of(const Eigen::VectorXd& knots, int n_ctrl, int degree, std::vector<double>& u) {
+  if ((int)knots.rows() != n_ctrl + degree + 1) return false;
+  u.resize((size_t)knots.rows());
+  for (int i = 0; i < (int)u.size(); ++i) u[i] = knots(i);
+  return true;
+}
+
+// (knots null: the uniform spline of the span pos_dt; else the spline on those knots, pos_dt is not read)
 static int plan_one_yaw(fuelmi_map* m, const fuelmi_bspline_cfg& w, const fuelmi_yaw_cfg& yc, const Eigen::MatrixXd& pos_ctrl,
                         double pos_dt, const Eigen::Vector3d& start_yaw, double end_yaw, Eigen::MatrixXd& yaw_ctrl,
-                        double& dt_yaw, std::vector<double>* path_yaw) {
+                        double& dt_yaw, std::vector<double>* path_yaw, const Eigen::VectorXd* knots = nullptr) {
   const int n_ctrl = (int)pos_ctrl.rows();
   if (n_ctrl < 1 || pos_ctrl.cols() != 3) return FUELMI_EINVAL;
+  std::vector<double> u;
+  if (knots && !knots_of(*knots, n_ctrl, yc.pos_degree, u)) return FUELMI_EINVAL;
   std::vector<double> pos(3 * (size_t)n_ctrl);
   for (int i = 0; i < n_ctrl; ++i)
     for (int k = 0; k < 3; ++k) pos[3 * i + k] = pos_ctrl(i, k);
@@ -1348,10 +1359,13 @@ static int plan_one_yaw(fuelmi_map* m, const fuelmi_bspline_cfg& w, const fuelmi
   int status = 0, seg_num = 0, n_waypt = 0;
   double duration = 0.0, dt = 0.0, e = 0.0, cost = 0.0;
   std::vector<double> q((size_t)yc.max_seg + 3), wp((size_t)yc.max_seg);
-  const int rc = fuelmi_map_plan_yaws(m, &w, &yc, 1, &n_ctrl, pos.data(), &pos_dt, start, &end_yaw, &status, &duration,
-                                      &seg_num, &dt, q.data(), &n_waypt, wp.data(), &e, &cost, nullptr, nullptr);
+  const int rc = knots ? fuelmi_map_plan_yaws_knots(m, &w, &yc, 1, &n_ctrl, pos.data(), u.data(), start, &end_yaw, &status,
+                                                    &duration, &seg_num, &dt, q.data(), &n_waypt, wp.data(), &e, &cost,
+                                                    nullptr, nullptr)
+                       : fuelmi_map_plan_yaws(m, &w, &yc, 1, &n_ctrl, pos.data(), &pos_dt, start, &end_yaw, &status, &duration,
+                                              &seg_num, &dt, q.data(), &n_waypt, wp.data(), &e, &cost, nullptr, nullptr);
   if (rc) {
-    warn("fuelmi_map_plan_yaws", rc);
+    warn(knots ? "fuelmi_map_plan_yaws_knots" : "fuelmi_map_plan_yaws", rc);
     return rc;
   }
   if (status != FUELMI_YAW_OK) return status;
@@ -1378,21 +1392,33 @@ int BsplineOptimizer::planYaw(const Eigen::MatrixXd& pos_ctrl, int pos_degree, d
                       path_yaw);
 }
 
-bool BsplineOptimizer::checkTrajCollision(const Eigen::MatrixXd& pos_ctrl, int degree, double dt, double t_now,
-                                          double& distance) {
+int BsplineOptimizer::planYaw(const Eigen::MatrixXd& pos_ctrl, int pos_degree, const Eigen::VectorXd& knots,
+                              const Eigen::Vector3d& start_yaw, Eigen::MatrixXd& yaw_ctrl, double& dt_yaw,
+                              std::vector<double>* path_yaw) {
+  fuelmi_yaw_cfg yc = {FUELMI_YAW_FOLLOW, pos_degree, (int)pos_ctrl.rows(), FUELMI_YAW_MAX_SEG, 0, 1, 0.0, 2.0, 0.3, 0.1};
+  return plan_one_yaw(edt_environment_->sdf_map_->device(), cfg_, yc, pos_ctrl, 0.0, start_yaw, 0.0, yaw_ctrl, dt_yaw,
+                      path_yaw, &knots);
+}
+
+// both checkTrajCollision (knots null: the uniform spline of the span dt)
+static bool check_one_traj(fuelmi_map* m, const Eigen::MatrixXd& pos_ctrl, int degree, double dt, const Eigen::VectorXd* knots,
+                           double t_now, double& distance) {
   const int n_ctrl = (int)pos_ctrl.rows();
   int rc = FUELMI_EINVAL, status = 0, safe = 0, n_samples = 0, hit_index = 0, end_reason = 0;
   double dist = 0.0, hit_t = 0.0, hit_pos[3], duration = 0.0;
-  if (n_ctrl >= 1 && pos_ctrl.cols() == 3) {
+  std::vector<double> u;
+  if (n_ctrl >= 1 && pos_ctrl.cols() == 3 && (!knots || knots_of(*knots, n_ctrl, degree, u))) {
     std::vector<double> pos(3 * (size_t)n_ctrl);
     for (int i = 0; i < n_ctrl; ++i)
       for (int k = 0; k < 3; ++k) pos[3 * i + k] = pos_ctrl(i, k);
     const fuelmi_trajchk_cfg tc = {degree, n_ctrl, 0.02, 6.0};  // planner_manager.cpp:102, 104
-    rc = fuelmi_map_check_trajs(edt_environment_->sdf_map_->device(), &tc, 1, &n_ctrl, pos.data(), &dt, &t_now, &status,
-                                &safe, &dist, &n_samples, &hit_index, &hit_t, hit_pos, &end_reason, &duration);
+    rc = knots ? fuelmi_map_check_trajs_knots(m, &tc, 1, &n_ctrl, pos.data(), u.data(), &t_now, &status, &safe, &dist,
+                                              &n_samples, &hit_index, &hit_t, hit_pos, &end_reason, &duration)
+               : fuelmi_map_check_trajs(m, &tc, 1, &n_ctrl, pos.data(), &dt, &t_now, &status, &safe, &dist, &n_samples,
+                                        &hit_index, &hit_t, hit_pos, &end_reason, &duration);
   }
   if (rc && rc != FUELMI_ELIMIT) {
-    warn("fuelmi_map_check_trajs", rc);
+    warn(knots ? "fuelmi_map_check_trajs_knots" : "fuelmi_map_check_trajs", rc);
     dist = 0.0, safe = 0;
   }
   if (safe) return true;
@@ -1400,12 +1426,26 @@ bool BsplineOptimizer::checkTrajCollision(const Eigen::MatrixXd& pos_ctrl, int d
   return false;
 }
 
-// one problem through fuelmi_map_sample_trajs; out = status | pos | vel | acc | jerk | yaw | yawdot | yawddot
+bool BsplineOptimizer::checkTrajCollision(const Eigen::MatrixXd& pos_ctrl, int degree, double dt, double t_now,
+                                          double& distance) {
+  return check_one_traj(edt_environment_->sdf_map_->device(), pos_ctrl, degree, dt, nullptr, t_now, distance);
+}
+
+bool BsplineOptimizer::checkTrajCollision(const Eigen::MatrixXd& pos_ctrl, int degree, const Eigen::VectorXd& knots,
+                                          double t_now, double& distance) {
+  return check_one_traj(edt_environment_->sdf_map_->device(), pos_ctrl, degree, 0.0, &knots, t_now, distance);
+}
+
+// one problem through fuelmi_map_sample_trajs (knots null) or fuelmi_map_sample_trajs_knots; out = status | pos | vel |
+// acc | jerk | yaw | yawdot | yawddot
 static int sample_one_traj(fuelmi_map* m, int mode, const Eigen::MatrixXd& pos_ctrl, int degree, double dt,
-                           const Eigen::MatrixXd& yaw_ctrl, int yaw_degree, double yaw_dt, const std::vector<double>& t,
-                           const double* t_stop, std::vector<int>& status, std::vector<double> out[7], double* flight8) {
+                           const Eigen::VectorXd* knots, const Eigen::MatrixXd& yaw_ctrl, int yaw_degree, double yaw_dt,
+                           const std::vector<double>& t, const double* t_stop, std::vector<int>& status,
+                           std::vector<double> out[7], double* flight8) {
   const int n_ctrl = (int)pos_ctrl.rows(), n_yaw = (int)yaw_ctrl.rows(), n_t = (int)t.size();
   if (n_ctrl < 1 || pos_ctrl.cols() != 3 || (n_yaw > 0 && yaw_ctrl.cols() < 1)) return FUELMI_EINVAL;
+  std::vector<double> u;
+  if (knots && !knots_of(*knots, n_ctrl, degree, u)) return FUELMI_EINVAL;
   std::vector<double> pos(3 * (size_t)n_ctrl), yawc((size_t)n_yaw);
   for (int i = 0; i < n_ctrl; ++i)
     for (int k = 0; k < 3; ++k) pos[3 * i + k] = pos_ctrl(i, k);
@@ -1414,21 +1454,27 @@ static int sample_one_traj(fuelmi_map* m, int mode, const Eigen::MatrixXd& pos_c
   status.assign(n_t, 0);
   for (int k = 0; k < 7; ++k) out[k].assign((k < 4 ? 3 : 1) * (size_t)n_t, 0.0);
   double duration = 0.0;
+  if (knots)
+    return fuelmi_map_sample_trajs_knots(m, &sc, 1, &n_ctrl, pos.data(), u.data(), n_yaw > 0 ? &n_yaw : nullptr, yawc.data(),
+                                         &yaw_dt, t_stop, &n_t, t.data(), status.data(), out[0].data(), out[1].data(),
+                                         out[2].data(), out[3].data(), out[4].data(), out[5].data(), out[6].data(), &duration,
+                                         flight8);
   return fuelmi_map_sample_trajs(m, &sc, 1, &n_ctrl, pos.data(), &dt, n_yaw > 0 ? &n_yaw : nullptr, yawc.data(), &yaw_dt,
                                  t_stop, &n_t, t.data(), status.data(), out[0].data(), out[1].data(), out[2].data(),
                                  out[3].data(), out[4].data(), out[5].data(), out[6].data(), &duration, flight8);
 }
 
-bool BsplineOptimizer::evaluateCommand(const Eigen::MatrixXd& pos_ctrl, int degree, double dt, const Eigen::MatrixXd& yaw_ctrl,
-                                       int yaw_degree, double yaw_dt, const std::vector<double>& t, const double* t_stop,
-                                       std::vector<int>& status, Eigen::MatrixXd& pos, Eigen::MatrixXd& vel,
-                                       Eigen::MatrixXd& acc, Eigen::MatrixXd& jerk, Eigen::MatrixXd& yaw, double* flight8) {
+// both evaluateCommand (knots null: the uniform spline of the span dt)
+static bool command_one_traj(fuelmi_map* m, const Eigen::MatrixXd& pos_ctrl, int degree, double dt, const Eigen::VectorXd* knots,
+                             const Eigen::MatrixXd& yaw_ctrl, int yaw_degree, double yaw_dt, const std::vector<double>& t,
+                             const double* t_stop, std::vector<int>& status, Eigen::MatrixXd& pos, Eigen::MatrixXd& vel,
+                             Eigen::MatrixXd& acc, Eigen::MatrixXd& jerk, Eigen::MatrixXd& yaw, double* flight8) {
   std::vector<int> st;
   std::vector<double> out[7];
-  const int rc = sample_one_traj(edt_environment_->sdf_map_->device(), FUELMI_TRAJSMP_COMMAND, pos_ctrl, degree, dt, yaw_ctrl,
-                                 yaw_degree, yaw_dt, t, t_stop, st, out, flight8);
+  const int rc = sample_one_traj(m, FUELMI_TRAJSMP_COMMAND, pos_ctrl, degree, dt, knots, yaw_ctrl, yaw_degree, yaw_dt, t, t_stop,
+                                 st, out, flight8);
   if (rc) {
-    warn("fuelmi_map_sample_trajs", rc);
+    warn(knots ? "fuelmi_map_sample_trajs_knots" : "fuelmi_map_sample_trajs", rc);
     return false;
   }
   const int n_t = (int)t.size();
@@ -1445,19 +1491,52 @@ bool BsplineOptimizer::evaluateCommand(const Eigen::MatrixXd& pos_ctrl, int degr
   return true;
 }
 
-bool BsplineOptimizer::replanState(const Eigen::MatrixXd& pos_ctrl, int degree, double dt, const Eigen::MatrixXd& yaw_ctrl,
-                                   int yaw_degree, double yaw_dt, double t_r, Eigen::Vector3d& start_pt,
-                                   Eigen::Vector3d& start_vel, Eigen::Vector3d& start_acc, Eigen::Vector3d& start_yaw) {
+bool BsplineOptimizer::evaluateCommand(const Eigen::MatrixXd& pos_ctrl, int degree, double dt, const Eigen::MatrixXd& yaw_ctrl,
+                                       int yaw_degree, double yaw_dt, const std::vector<double>& t, const double* t_stop,
+                                       std::vector<int>& status, Eigen::MatrixXd& pos, Eigen::MatrixXd& vel,
+                                       Eigen::MatrixXd& acc, Eigen::MatrixXd& jerk, Eigen::MatrixXd& yaw, double* flight8) {
+  return command_one_traj(edt_environment_->sdf_map_->device(), pos_ctrl, degree, dt, nullptr, yaw_ctrl, yaw_degree, yaw_dt, t,
+                          t_stop, status, pos, vel, acc, jerk, yaw, flight8);
+}
+
+bool BsplineOptimizer::evaluateCommand(const Eigen::MatrixXd& pos_ctrl, int degree, const Eigen::VectorXd& knots,
+                                       const Eigen::MatrixXd& yaw_ctrl, int yaw_degree, double yaw_dt,
+                                       const std::vector<double>& t, const double* t_stop, std::vector<int>& status,
+                                       Eigen::MatrixXd& pos, Eigen::MatrixXd& vel, Eigen::MatrixXd& acc, Eigen::MatrixXd& jerk,
+                                       Eigen::MatrixXd& yaw, double* flight8) {
+  return command_one_traj(edt_environment_->sdf_map_->device(), pos_ctrl, degree, 0.0, &knots, yaw_ctrl, yaw_degree, yaw_dt, t,
+                          t_stop, status, pos, vel, acc, jerk, yaw, flight8);
+}
+
+// both replanState (knots null: the uniform spline of the span dt)
+static bool state_one_traj(fuelmi_map* m, const Eigen::MatrixXd& pos_ctrl, int degree, double dt, const Eigen::VectorXd* knots,
+                           const Eigen::MatrixXd& yaw_ctrl, int yaw_degree, double yaw_dt, double t_r, Eigen::Vector3d& start_pt,
+                           Eigen::Vector3d& start_vel, Eigen::Vector3d& start_acc, Eigen::Vector3d& start_yaw) {
   std::vector<int> st;
   std::vector<double> out[7];
-  const int rc = sample_one_traj(edt_environment_->sdf_map_->device(), FUELMI_TRAJSMP_STATE, pos_ctrl, degree, dt, yaw_ctrl,
-                                 yaw_degree, yaw_dt, std::vector<double>(1, t_r), nullptr, st, out, nullptr);
+  const int rc = sample_one_traj(m, FUELMI_TRAJSMP_STATE, pos_ctrl, degree, dt, knots, yaw_ctrl, yaw_degree, yaw_dt,
+                                 std::vector<double>(1, t_r), nullptr, st, out, nullptr);
   if (rc) {
-    warn("fuelmi_map_sample_trajs", rc);
+    warn(knots ? "fuelmi_map_sample_trajs_knots" : "fuelmi_map_sample_trajs", rc);
     return false;
   }
   for (int k = 0; k < 3; ++k) start_pt(k) = out[0][k], start_vel(k) = out[1][k], start_acc(k) = out[2][k], start_yaw(k) = out[4 + k][0];
   return true;
+}
+
+bool BsplineOptimizer::replanState(const Eigen::MatrixXd& pos_ctrl, int degree, double dt, const Eigen::MatrixXd& yaw_ctrl,
+                                   int yaw_degree, double yaw_dt, double t_r, Eigen::Vector3d& start_pt,
+                                   Eigen::Vector3d& start_vel, Eigen::Vector3d& start_acc, Eigen::Vector3d& start_yaw) {
+  return state_one_traj(edt_environment_->sdf_map_->device(), pos_ctrl, degree, dt, nullptr, yaw_ctrl, yaw_degree, yaw_dt, t_r,
+                        start_pt, start_vel, start_acc, start_yaw);
+}
+
+bool BsplineOptimizer::replanState(const Eigen::MatrixXd& pos_ctrl, int degree, const Eigen::VectorXd& knots,
+                                   const Eigen::MatrixXd& yaw_ctrl, int yaw_degree, double yaw_dt, double t_r,
+                                   Eigen::Vector3d& start_pt, Eigen::Vector3d& start_vel, Eigen::Vector3d& start_acc,
+                                   Eigen::Vector3d& start_yaw) {
+  return state_one_traj(edt_environment_->sdf_map_->device(), pos_ctrl, degree, 0.0, &knots, yaw_ctrl, yaw_degree, yaw_dt, t_r,
+                        start_pt, start_vel, start_acc, start_yaw);
 }
 
 static fuelmi_trajadj_cfg trajadj_cfg(const BsplineOptimizer::TrajAdjust& c, int ops, int degree, int max_ctrl, int n_group) {

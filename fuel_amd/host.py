@@ -226,6 +226,24 @@ def traj_adjust_cfg(ops=0, degree=3, max_ctrl=4, max_samples=0, realloc_iters=3,
                       float(stat_step))
 
 
+def _knots_or_span(n, ks, knot_span, knots):
+    """What the calls that take a position spline's knot span or its whole knot vectors share: (span [n] or None, knots
+    [n, ks] or None).  knots is one 1-D array per problem, as adjust_trajs takes knots_in and returns knots_out; exactly
+    one of the two is given."""
+    if (knots is None) == (knot_span is None):
+        raise ValueError("give either knot_span or knots")
+    if knots is None:
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(knot_span, dtype=np.float64), (n,))), None
+    if len(knots) != n:
+        raise ValueError("knots: one array per problem")
+    kin = np.zeros((n, ks))
+    for b, v in enumerate(knots):
+        v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+        k = min(len(v), ks)
+        kin[b, :k] = v[:k]
+    return None, kin
+
+
 def _trajadj_io(n, n_ctrl, degree, maxc, knots_in, ratio_in, group, ops, max_samples, n_group):
     """The host arrays both adjustment calls share: (arguments from knots_in on, the result dict, max_samples, n_group,
     the arrays behind the pointers).  knots_in is one 1-D array per problem."""
@@ -1019,12 +1037,14 @@ class SDFMap:
     YAW_EXPLORE, YAW_FOLLOW, YAW_OK, YAW_DEGENERATE = _lib.YAW_EXPLORE, _lib.YAW_FOLLOW, _lib.YAW_OK, _lib.YAW_DEGENERATE
 
     def plan_yaws(self, pos_ctrl, knot_span, start_yaw, end_yaw=None, weights=None, derivs=True, allow_limit=False,
-                  max_ctrl=None, **cfg):
+                  max_ctrl=None, knots=None, **cfg):
         """planYawExplore (mode 0) / planYaw (mode 1) per problem: pos_ctrl is a list of [n_ctrl, 3] control-point arrays
         of uniform position splines, knot_span [n], start_yaw [n, 3] (yaw, rate, acceleration), end_yaw [n] (EXPLORE).
         weights: a BsplineCfg or a dict of ld_* (default: the launch file's); cfg: the fields of yaw_cfg().  Returns a
         dict of arrays: status, duration, seg_num, dt_yaw, yaw_ctrl [n, max_seg+3], n_waypt, waypts [n, max_seg],
-        end_yaw, cost, yawdot_ctrl, yawddot_ctrl (with derivs), limit.  FUELMI_ELIMIT raises unless allow_limit."""
+        end_yaw, cost, yawdot_ctrl, yawddot_ctrl (with derivs), limit.  FUELMI_ELIMIT raises unless allow_limit.
+        knots (with knot_span None): a list of 1-D arrays of n_ctrl + pos_degree + 1 knots, e.g. the rows of adjust_trajs'
+        knots_out (fuelmi_map_plan_yaws_knots)."""
         pos = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in pos_ctrl]
         n = len(pos)
         maxc = int(max_ctrl) if max_ctrl is not None else max([len(p) for p in pos] + [4])
@@ -1034,13 +1054,17 @@ class SDFMap:
         for b, p in enumerate(pos):
             k = min(len(p), arr.shape[1])
             arr[b, :k] = p[:k]
-        knot = np.ascontiguousarray(np.broadcast_to(np.asarray(knot_span, dtype=np.float64), (n,)))
+        knot, kin = _knots_or_span(n, max(maxc, 0) + c.pos_degree + 1, knot_span, knots)
         sy = np.ascontiguousarray(start_yaw, dtype=np.float64).reshape(n, 3)
         ey = None if end_yaw is None else np.ascontiguousarray(np.broadcast_to(np.asarray(end_yaw, dtype=np.float64), (n,)))
         w = weights if isinstance(weights, BsplineCfg) else BsplineCfg(**dict(DEFAULT_BSPLINE, **(weights or {})))
         o, args = _yaw_outputs(n, c.max_seg, derivs)
-        rc = self.L.fuelmi_map_plan_yaws(self.h, C.byref(w), C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(knot), _dp(sy),
-                                         _dp(ey), *args)
+        if kin is None:
+            rc = self.L.fuelmi_map_plan_yaws(self.h, C.byref(w), C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(knot), _dp(sy),
+                                             _dp(ey), *args)
+        else:
+            rc = self.L.fuelmi_map_plan_yaws_knots(self.h, C.byref(w), C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(kin),
+                                                   _dp(sy), _dp(ey), *args)
         if not (allow_limit and rc == -5):
             check(rc)
         o["limit"] = rc == -5
@@ -1103,11 +1127,13 @@ class SDFMap:
         return o
 
     # --- the safety check of flown trajectories (include/fuelmi.h fuelmi_map_check_trajs) ---
-    def check_trajs(self, pos_ctrl, knot_span, t_now, allow_limit=False, max_ctrl=None, **cfg):
+    def check_trajs(self, pos_ctrl, knot_span, t_now, allow_limit=False, max_ctrl=None, knots=None, **cfg):
         """checkTrajCollision per problem against the inflated plane on the device: pos_ctrl is a list of [n_ctrl, 3]
         control-point arrays of uniform position splines, knot_span [n], t_now [n]; cfg: the fields of traj_check_cfg().
         Returns a dict of arrays: status, safe, distance (-1 when safe), n_samples, hit_index, hit_t, hit_pos [n, 3],
-        end_reason, duration, limit.  FUELMI_ELIMIT raises unless allow_limit."""
+        end_reason, duration, limit.  FUELMI_ELIMIT raises unless allow_limit.
+        knots (with knot_span None): a list of 1-D arrays of n_ctrl + degree + 1 knots, e.g. the rows of adjust_trajs'
+        knots_out (fuelmi_map_check_trajs_knots)."""
         pos = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in pos_ctrl]
         n = len(pos)
         maxc = int(max_ctrl) if max_ctrl is not None else max([len(p) for p in pos] + [4])
@@ -1117,10 +1143,13 @@ class SDFMap:
         for b, p in enumerate(pos):
             k = min(len(p), arr.shape[1])
             arr[b, :k] = p[:k]
-        knot = np.ascontiguousarray(np.broadcast_to(np.asarray(knot_span, dtype=np.float64), (n,)))
+        knot, kin = _knots_or_span(n, max(maxc, 0) + c.degree + 1, knot_span, knots)
         now = np.ascontiguousarray(np.broadcast_to(np.asarray(t_now, dtype=np.float64), (n,)))
         o, args = _trajchk_outputs(n)
-        rc = self.L.fuelmi_map_check_trajs(self.h, C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(knot), _dp(now), *args)
+        if kin is None:
+            rc = self.L.fuelmi_map_check_trajs(self.h, C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(knot), _dp(now), *args)
+        else:
+            rc = self.L.fuelmi_map_check_trajs_knots(self.h, C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(kin), _dp(now), *args)
         if not (allow_limit and rc == -5):
             check(rc)
         o["limit"] = rc == -5
@@ -1136,13 +1165,15 @@ class SDFMap:
 
     # --- sampling of flown trajectories (include/fuelmi.h fuelmi_map_sample_trajs) ---
     def sampleTrajs(self, pos_ctrl, knot_span, t, yaw_ctrl=None, yaw_dt=None, t_stop=None, flight=None, max_ctrl=None,
-                    max_yaw_ctrl=None, max_t=None, **cfg):
+                    max_yaw_ctrl=None, max_t=None, knots=None, **cfg):
         """cmdCallback (mode TRAJSMP_COMMAND, the default) or the FSM's replan state (TRAJSMP_STATE) per problem on the
         device: pos_ctrl is a list of [n_ctrl, 3] control-point arrays of uniform position splines, knot_span [n], t a list
         of 1-D arrays of sample times; yaw_ctrl a list of 1-D control-point arrays (None: no yaw spline) with yaw_dt [n];
         t_stop [n] or None; flight [n, 8] or None (a copy is updated and returned); cfg: mode, degree, yaw_degree.
         Returns a dict of arrays: status [n, max_t], pos / vel / acc / jerk [n, max_t, 3], yaw / yawdot / yawddot
-        [n, max_t], duration [n], flight, n_t."""
+        [n, max_t], duration [n], flight, n_t.
+        knots (with knot_span None): a list of 1-D arrays of n_ctrl + degree + 1 position knots, e.g. the rows of
+        adjust_trajs' knots_out (fuelmi_map_sample_trajs_knots); the yaw splines stay uniform."""
         pos = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in pos_ctrl]
         n = len(pos)
         maxc = int(max_ctrl) if max_ctrl is not None else max([len(p) for p in pos] + [4])
@@ -1153,9 +1184,14 @@ class SDFMap:
         for b, p in enumerate(pos):
             k = min(len(p), arr.shape[1])
             arr[b, :k] = p[:k]
-        knot = np.ascontiguousarray(np.broadcast_to(np.asarray(knot_span, dtype=np.float64), (n,)))
-        check(self.L.fuelmi_map_sample_trajs(self.h, C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(knot), *args))
+        knot, kin = _knots_or_span(n, max(maxc, 0) + c.degree + 1, knot_span, knots)
+        if kin is None:
+            check(self.L.fuelmi_map_sample_trajs(self.h, C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(knot), *args))
+        else:
+            check(self.L.fuelmi_map_sample_trajs_knots(self.h, C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(kin), *args))
         return o
+
+    sample_trajs = sampleTrajs
 
     @staticmethod
     def traj_sample_plan(cfg):
@@ -1948,6 +1984,19 @@ class BsplineDeviceProblem:
         ac = traj_adjust_cfg(ops=ops, max_ctrl=c.point_num, max_samples=maxs, n_group=ng, **cfg)
         check(self.L.fuelmi_bspline_dev_adjust_trajs(self.h, C.byref(ac), *args))
         return _trajadj_named(o)
+
+    KNOTS_UNIFORM, KNOTS_ADJUSTED = _lib.KNOTS_UNIFORM, _lib.KNOTS_ADJUSTED
+
+    def set_knot_source(self, source):
+        """Which knots check_trajs / sample_trajs / plan_yaws put under the candidates' position splines: KNOTS_UNIFORM
+        (the default) or KNOTS_ADJUSTED, the knots the last adjust_trajs() left on the device
+        (fuelmi_bspline_dev_set_knot_source).  KNOTS_ADJUSTED raises unless adjust_trajs() has run since the last
+        optimize(); a reload or another optimize() puts the source back to KNOTS_UNIFORM."""
+        check(self.L.fuelmi_bspline_dev_set_knot_source(self.h, int(source)))
+
+    @property
+    def knot_source(self):
+        return int(self.L.fuelmi_bspline_dev_knot_source(self.h))
 
     def close(self):
         if getattr(self, "h", None):

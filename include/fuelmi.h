@@ -778,8 +778,10 @@ int fuelmi_wptraj_plan(const fuelmi_wptraj_cfg* cfg, int out3[3]);
  * Yaw trajectory of a position spline: FastPlannerManager::planYawExplore (plan_manage/src/planner_manager.cpp:774-865,
  * mode FUELMI_YAW_EXPLORE) and ::planYaw (:695-772, FUELMI_YAW_FOLLOW) for n_prob independent problems in one call.
  * The position spline is UNIFORM (control points + one knot span, setUniformBspline): the exploration path sets no
- * other.  Moving knots (lengthenTime, reallocateTime) is fuelmi_map_adjust_trajs, below; feeding the moved knots into
- * this call is out of scope.
+ * other.  Moving knots (lengthenTime, reallocateTime) is fuelmi_map_adjust_trajs, below; the moved knots go into
+ * fuelmi_map_plan_yaws_knots (and, for a device batch, FUELMI_KNOTS_ADJUSTED; both below).  The yaw spline that comes
+ * out is uniform either way: the reference builds every yaw spline with setUniformBspline, and given knots for yaw
+ * splines are out of scope.
  * Per problem, EXPLORE, everything f64 in this order:
  *   1. knots as setUniformBspline builds them (non_uniform_bspline.cpp:25-31): u[i] = double(i - p) * dt for i <= p,
  *      then ACCUMULATED u[i] = u[i-1] + dt; duration = u[n_ctrl] - u[p] (a result of the additions, not a product).
@@ -850,13 +852,30 @@ int fuelmi_map_plan_yaws(fuelmi_map* m, const fuelmi_bspline_cfg* w, const fuelm
                          const double* end_yaw, int* status, double* duration, int* seg_num, double* dt_yaw,
                          double* yaw_ctrl, int* n_waypt, double* waypts, double* end_yaw_out, double* cost,
                          double* yawdot_ctrl, double* yawddot_ctrl);
+/* The same on whole knot vectors (setKnot) in place of the spans: knots [n_prob][max_ctrl + pos_degree + 1], the layout
+ * of fuelmi_map_adjust_trajs' knots_out, so that call's output is this call's input as it stands.  Step 1 then takes
+ * problem i's n_ctrl[i] + pos_degree + 1 knots as given; duration stays u[n_ctrl] - u[p], every evaluation stays
+ * evaluateDeBoorT (t + u[p] and the clamp), FOLLOW's derivative points are divided by the given knots' differences.
+ * Checked on the host before anything is launched (FUELMI_EINVAL), beside everything above but the spans: knots not
+ * NULL, every knot finite, every knot above the one in front of it.  Strict increase is more than the reference asks
+ * for: it asks for nothing and divides by knot differences. */
+int fuelmi_map_plan_yaws_knots(fuelmi_map* m, const fuelmi_bspline_cfg* w, const fuelmi_yaw_cfg* cfg, int n_prob,
+                               const int* n_ctrl, const double* pos_ctrl, const double* knots, const double* start_yaw,
+                               const double* end_yaw, int* status, double* duration, int* seg_num, double* dt_yaw,
+                               double* yaw_ctrl, int* n_waypt, double* waypts, double* end_yaw_out, double* cost,
+                               double* yawdot_ctrl, double* yawddot_ctrl);
 /* The device chain optimised batch -> yaw trajectories: one problem per candidate of `b` (dim 3), read from the
  * variables the batch's last fuelmi_bspline_dev_optimize[_timed] left in device memory: the control points are those
  * variables, the knot span is x[nvar-1] under MINTIME and the batch's knot span otherwise; the weights are the batch's;
  * cfg->pos_degree must be the batch's bspline_degree and cfg->max_ctrl is ignored (it is point_num).  Only the yaw
  * results are copied back; they equal, bit for bit, fuelmi_map_plan_yaws on the x_out that solve returned.
  * FUELMI_EINVAL when the batch is not dim 3 or has not been optimised since it was created or last (re)loaded by
- * fuelmi_bspline_dev_load_samples / _load_waypoints.  Runs on the map's stream and waits for it. */
+ * fuelmi_bspline_dev_load_samples / _load_waypoints.  Runs on the map's stream and waits for it.
+ * While the batch's knot source is FUELMI_KNOTS_ADJUSTED (fuelmi_bspline_dev_set_knot_source, below) the position
+ * splines stand on the knots the batch's last fuelmi_bspline_dev_adjust_trajs left on the device, and the results equal,
+ * bit for bit, fuelmi_map_plan_yaws_knots on that solve's x_out and that adjustment's knots_out.  The host never sees
+ * those knots, so the kernel checks them (finite, strictly increasing): a candidate that fails -- one the adjustment
+ * marked FUELMI_TRAJADJ_BADSPLINE, whose knots are 0 -- is FUELMI_YAW_DEGENERATE with every output 0. */
 int fuelmi_bspline_dev_plan_yaws(fuelmi_bspline_dev* b, const fuelmi_yaw_cfg* cfg, const double* start_yaw,
                                  const double* end_yaw, int* status, double* duration, int* seg_num, double* dt_yaw,
                                  double* yaw_ctrl, int* n_waypt, double* waypts, double* end_yaw_out, double* cost,
@@ -1449,7 +1468,8 @@ int fuelmi_yawpath_plan(const fuelmi_yawpath_cfg* cfg, int out10[10]);
  * (plan_manage/src/planner_manager.cpp:96-118), which the exploration FSM's safetyCallback runs every 50 ms while a
  * trajectory is flown (exploration_manager/src/fast_exploration_fsm.cpp:335-345), for n_prob independent problems in
  * one call.  The position spline is UNIFORM (control points + one knot span, setUniformBspline); a time
- * reallocation is fuelmi_map_adjust_trajs, below, and feeding the knots it moved into this call is out of scope.  Per problem, everything f64 in this order:
+ * reallocation is fuelmi_map_adjust_trajs, below, and the knots it moved go into fuelmi_map_check_trajs_knots (and,
+ * for a device batch, FUELMI_KNOTS_ADJUSTED; both below).  Per problem, everything f64 in this order:
  *   1. knots as setUniformBspline builds them (non_uniform_bspline.cpp:25-31): u[i] = double(i - p) * dt for i <= p,
  *      then ACCUMULATED u[i] = u[i-1] + dt; duration = u[n_ctrl] - u[p].
  *   2. cur = evaluateDeBoorT(t_now) (the literal clamp, knot search and alpha recursion of :51-75).
@@ -1509,13 +1529,30 @@ int fuelmi_map_check_trajs(fuelmi_map* m, const fuelmi_trajchk_cfg* cfg, int n_p
                            const double* pos_ctrl, const double* knot_span, const double* t_now, int* status, int* safe,
                            double* distance, int* n_samples, int* hit_index, double* hit_t, double* hit_pos,
                            int* end_reason, double* duration);
+/* The same on whole knot vectors (setKnot, as local_data_.position_traj_ carries them behind a time adjustment) in place
+ * of the spans: knots [n_prob][max_ctrl + degree + 1], the layout of fuelmi_map_adjust_trajs' knots_out, so that call's
+ * output is this call's input as it stands.  Step 1 then takes problem i's n_ctrl[i] + degree + 1 knots as given;
+ * duration stays u[n_ctrl] - u[p] and every evaluation stays evaluateDeBoorT (t + u[p] and the clamp).  Checked on the
+ * host before anything is launched (FUELMI_EINVAL), beside everything above but the spans: knots not NULL, every knot
+ * finite, every knot above the one in front of it.  Strict increase is more than the reference asks for: it asks for
+ * nothing and divides by knot differences. */
+int fuelmi_map_check_trajs_knots(fuelmi_map* m, const fuelmi_trajchk_cfg* cfg, int n_prob, const int* n_ctrl,
+                                 const double* pos_ctrl, const double* knots, const double* t_now, int* status, int* safe,
+                                 double* distance, int* n_samples, int* hit_index, double* hit_t, double* hit_pos,
+                                 int* end_reason, double* duration);
 /* The device chain optimised batch -> safety check: one problem per candidate of `b` (dim 3), read from the variables
  * the batch's last fuelmi_bspline_dev_optimize[_timed] left in device memory (control points = those variables, knot
  * span = x[nvar-1] under MINTIME and the batch's knot span otherwise) against the batch's map.  cfg->degree must be the
  * batch's bspline_degree and cfg->max_ctrl is ignored (it is point_num).  t_now [n_traj].  Only the results are copied
  * back; they equal, bit for bit, fuelmi_map_check_trajs on the x_out that solve returned.  FUELMI_EINVAL when the batch
  * is not dim 3 or has not been optimised since it was created or last (re)loaded (the flag fuelmi_bspline_dev_plan_yaws
- * uses).  Runs on the map's stream and waits for it. */
+ * uses).  Runs on the map's stream and waits for it.
+ * While the batch's knot source is FUELMI_KNOTS_ADJUSTED (fuelmi_bspline_dev_set_knot_source, below) the splines stand on
+ * the knots the batch's last fuelmi_bspline_dev_adjust_trajs left on the device, and the results equal, bit for bit,
+ * fuelmi_map_check_trajs_knots on that solve's x_out and that adjustment's knots_out.  The host never sees those knots,
+ * so the kernel checks them (finite, strictly increasing): a candidate that fails -- one the adjustment marked
+ * FUELMI_TRAJADJ_BADSPLINE, whose knots are 0 -- is FUELMI_TRAJCHK_NONFINITE / _END_NONFINITE with duration and
+ * n_samples 0, like a bad knot span. */
 int fuelmi_bspline_dev_check_trajs(fuelmi_bspline_dev* b, const fuelmi_trajchk_cfg* cfg, const double* t_now, int* status,
                                    int* safe, double* distance, int* n_samples, int* hit_index, double* hit_t,
                                    double* hit_pos, int* end_reason, double* duration);
@@ -1562,8 +1599,9 @@ int fuelmi_traj_check_plan(const fuelmi_trajchk_cfg* cfg, int out3[3]);
  *            The spline is never indexed: every sample of the problem has this status, every output is 0, duration 0,
  *            the record untouched.
  *   Entries from n_t[b] to max_t are written as 0 (status too).
- * Out of scope: loop correction (:292-300), the FOV markers and all publishing, and sampling on knots moved by a time
- * reallocation (moving and measuring them is fuelmi_map_adjust_trajs, below; this call takes uniform splines).
+ * Out of scope: loop correction (:292-300), the FOV markers and all publishing, and given knots for yaw splines
+ * (Bspline.msg carries only yaw_dt).  Sampling a position spline on knots moved by a time reallocation (moving and
+ * measuring them is fuelmi_map_adjust_trajs, below) is fuelmi_map_sample_trajs_knots, below.
  * Checked on the host before anything is launched (FUELMI_EINVAL): pointers; mode; degree in 3..5 and, with max_yaw_ctrl
  * > 0, yaw_degree in 3..5; degree + 1 <= n_ctrl[b] <= max_ctrl; n_yaw_ctrl[b] == 0 or yaw_degree + 1 <= n_yaw_ctrl[b] <=
  * max_yaw_ctrl; spans finite and > 0; control points finite with |value| < 1e7; 0 <= n_t[b] <= max_t; every t, t_stop and
@@ -1603,6 +1641,20 @@ int fuelmi_map_sample_trajs(fuelmi_map* m, const fuelmi_trajsmp_cfg* cfg, int n_
                             const double* yaw_ctrl, const double* yaw_dt, const double* t_stop, const int* n_t,
                             const double* t, int* status, double* pos, double* vel, double* acc, double* jerk,
                             double* yaw, double* yawdot, double* yawddot, double* duration, double* flight);
+/* The same with the position splines on whole knot vectors in place of the spans -- what traj_server does with the knots
+ * of Bspline.msg, pos_traj.setKnot(knots) (plan_manage/src/traj_server.cpp:230), before it samples commands: knots
+ * [n_prob][max_ctrl + degree + 1], the layout of fuelmi_map_adjust_trajs' knots_out, so that call's output is this
+ * call's input as it stands.  Step 1 then takes problem b's n_ctrl[b] + degree + 1 position knots as given; D stays
+ * u[n_ctrl] - u[p], the derivative points of step 2 are divided by the given knots' differences, step 3 is unchanged (t +
+ * u[p], the clamp, the strict < of the search).  The yaw splines stay uniform.  Checked on the host before anything is
+ * launched (FUELMI_EINVAL), beside everything above but the position spans: knots not NULL, every knot finite, every
+ * knot above the one in front of it.  Strict increase is more than the reference asks for: it asks for nothing and
+ * divides by knot differences. */
+int fuelmi_map_sample_trajs_knots(fuelmi_map* m, const fuelmi_trajsmp_cfg* cfg, int n_prob, const int* n_ctrl,
+                                  const double* pos_ctrl, const double* knots, const int* n_yaw_ctrl,
+                                  const double* yaw_ctrl, const double* yaw_dt, const double* t_stop, const int* n_t,
+                                  const double* t, int* status, double* pos, double* vel, double* acc, double* jerk,
+                                  double* yaw, double* yawdot, double* yawddot, double* duration, double* flight);
 /* The device chain optimised batch -> commands / next start states: one problem per candidate of `b` (dim 3), the
  * position spline read from the variables the batch's last fuelmi_bspline_dev_optimize[_timed] left in device memory
  * (control points = those variables, knot span = x[nvar-1] under MINTIME and the batch's knot span otherwise).
@@ -1610,7 +1662,12 @@ int fuelmi_map_sample_trajs(fuelmi_map* m, const fuelmi_trajsmp_cfg* cfg, int n_
  * the times come from the host; only the results are copied back.  They equal, bit for bit, fuelmi_map_sample_trajs on
  * the x_out that solve returned.  FUELMI_EINVAL when the batch is not dim 3 or has not been optimised since it was
  * created or last (re)loaded (the preconditions of fuelmi_bspline_dev_check_trajs).  Runs on the map's stream and waits
- * for it. */
+ * for it.
+ * While the batch's knot source is FUELMI_KNOTS_ADJUSTED (fuelmi_bspline_dev_set_knot_source, below) the position
+ * splines stand on the knots the batch's last fuelmi_bspline_dev_adjust_trajs left on the device, and the results equal,
+ * bit for bit, fuelmi_map_sample_trajs_knots on that solve's x_out and that adjustment's knots_out.  The host never sees
+ * those knots, so the kernel checks them (finite, strictly increasing): a candidate that fails -- one the adjustment
+ * marked FUELMI_TRAJADJ_BADSPLINE, whose knots are 0 -- is FUELMI_TRAJSMP_BADSPLINE on every sample. */
 int fuelmi_bspline_dev_sample_trajs(fuelmi_bspline_dev* b, const fuelmi_trajsmp_cfg* cfg, const int* n_yaw_ctrl,
                                     const double* yaw_ctrl, const double* yaw_dt, const double* t_stop, const int* n_t,
                                     const double* t, int* status, double* pos, double* vel, double* acc, double* jerk,
@@ -1667,8 +1724,10 @@ int fuelmi_traj_sample_plan(const fuelmi_trajsmp_cfg* cfg, int out3[3]);
  * group and best given and every group[b] in 0..n_group-1; with RESAMPLE samples given and max_samples >=
  * max_ctrl - degree + 2.  FUELMI_ELIMIT: max_ctrl > FUELMI_TRAJADJ_MAX_CTRL, max_samples > FUELMI_TRAJADJ_MAX_SAMPLES,
  * n_prob or n_group > FUELMI_TRAJADJ_MAX_PROB.  n_prob == 0 is FUELMI_OK: nothing is launched, nothing is written.
- * Out of scope: feeding moved knots into fuelmi_map_sample_trajs, _check_trajs, _plan_yaws or the kinodynamic loader
- * (those take uniform splines); a device-to-device hand-over of the resampled points to load_samples; yaw (1-D)
+ * The moved knots go on: knots_out is, as it stands, the `knots` of fuelmi_map_check_trajs_knots, _sample_trajs_knots
+ * and _plan_yaws_knots (above), and a device batch keeps them for its own three calls (FUELMI_KNOTS_ADJUSTED, below).
+ * Out of scope: given knots into fuelmi_map_collision_ranges, fuelmi_map_local_segments and the kinodynamic loader
+ * (those take uniform splines), and given knots for yaw splines; a device-to-device hand-over of the resampled points to load_samples; yaw (1-D)
  * splines; the reference's ROS_INFO output; the commented-out VIEWCONS path of refineTraj.
  * fuelmi_map_adjust_trajs takes host arrays in and out, is synchronous, runs on the map's stream, one thread at a time
  * per map; its scratch is one grow-only allocation on the map.  It reads no plane and no mirror.  One 64-lane wave per
@@ -1735,10 +1794,25 @@ int fuelmi_map_adjust_trajs(fuelmi_map* m, const fuelmi_trajadj_cfg* cfg, int n_
  * the span).  cfg->degree must be the batch's bspline_degree and cfg->max_ctrl is ignored (it is point_num).  Only the
  * results are copied back; they equal, bit for bit, fuelmi_map_adjust_trajs on the x_out that solve returned.
  * FUELMI_EINVAL when the batch is not dim 3 or has not been optimised since it was created or last (re)loaded (the
- * preconditions of fuelmi_bspline_dev_check_trajs).  Runs on the map's stream and waits for it. */
+ * preconditions of fuelmi_bspline_dev_check_trajs).  Runs on the map's stream and waits for it.
+ * The call also keeps every candidate's final knots [n_traj][point_num + degree + 1] in a buffer the batch owns
+ * (allocated by the first call, freed with the batch): what FUELMI_KNOTS_ADJUSTED reads. */
 int fuelmi_bspline_dev_adjust_trajs(fuelmi_bspline_dev* b, const fuelmi_trajadj_cfg* cfg, const double* knots_in,
                                     const double* ratio_in, const int* group, int* info, double* metrics,
                                     double* knots_out, double* samples, int* best);
+/* Which knots fuelmi_bspline_dev_check_trajs, _sample_trajs and _plan_yaws put under the batch's position splines:
+ *   FUELMI_KNOTS_UNIFORM   (the default) setUniformBspline's, from the knot span
+ *   FUELMI_KNOTS_ADJUSTED  the knots the last fuelmi_bspline_dev_adjust_trajs kept: the device chain solve -> adjustment
+ *                          -> safety check / commands / yaw, the knots never leaving the device
+ * FUELMI_KNOTS_ADJUSTED is FUELMI_EINVAL unless an adjustment has run since the batch's last solve.  Whatever ends that
+ * solve -- a reload (fuelmi_bspline_dev_load_*), fuelmi_bspline_dev_solve_quadratic's hand-over, the next
+ * fuelmi_bspline_dev_optimize[_timed] -- drops the kept knots and puts the source back to FUELMI_KNOTS_UNIFORM.  No
+ * other call reads the source (fuelmi_bspline_dev_adjust_trajs itself starts from the span or its knots_in).  Host only:
+ * nothing is launched.  _knot_source of NULL is FUELMI_KNOTS_UNIFORM. */
+#define FUELMI_KNOTS_UNIFORM 0
+#define FUELMI_KNOTS_ADJUSTED 1
+int fuelmi_bspline_dev_set_knot_source(fuelmi_bspline_dev* b, int source);
+int fuelmi_bspline_dev_knot_source(const fuelmi_bspline_dev* b);
 /* what the kernel needs for cfg (host only, no device needed): out3 = {lanes per problem, dynamic LDS bytes of a
  * workgroup, largest max_ctrl accepted}.  cfg is checked like above. */
 int fuelmi_traj_adjust_plan(const fuelmi_trajadj_cfg* cfg, int out3[3]);
