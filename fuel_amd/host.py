@@ -13,8 +13,11 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BsplineBatch, BsplineCfg, CloudCfg, ColRangeCfg, FrontierCfg, GainCfg, GoalCfg, KinoCfg, LocalSegCfg, MapCfg, MapInfo, PathCfg, QuadCfg, RefineCfg, RenderCfg, TopoCfg, TrajAdjCfg, TrajChkCfg, TrajSmpCfg, TspCfg,
+from ._lib import (BsplineBatch, BsplineCfg, CloudCfg, ColRangeCfg, FrontierCfg, GainCfg, GoalCfg, KinoCfg, LocalSegCfg, MapCfg, MapInfo, PathCfg, QuadCfg, RefineCfg, RenderCfg, TopoCfg, TrajAdjCfg, TrajChkCfg, TrajSmpCfg, TspCfg,  # noqa: F401
                    WptrajCfg, YawCfg, YawPathCfg, check, lib)
+# (_dp and _ip are also what the per-stage timing scripts build their argument lists with)
+from ._pack import dp as _dp, ip as _ip, limited as _limited, outputs as _outputs, pack as _pack, per_problem as _per_problem
+from ._pack import plan_query as _plan_query, ptr as _ptr, weights as _weights
 
 # exploration.launch / algorithm.xml defaults (exploration_manager/launch/algorithm.xml:33-59,170-181)
 DEFAULT_MAP = dict(resolution=0.1, ground_height=-1.0, obstacles_inflation=0.199,
@@ -29,28 +32,14 @@ SMOOTHNESS, DISTANCE, FEASIBILITY, START, END, GUIDE, WAYPOINTS, VIEWCONS, MINTI
     (1 << k for k in range(9))
 GUIDE_PHASE = SMOOTHNESS | GUIDE | START | END
 NORMAL_PHASE = SMOOTHNESS | DISTANCE | FEASIBILITY | START | END
-
-
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-def _ip(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
+_I, _D = np.int32, np.float64
 
 
 def _pack_waypoints(ways, vels, accs, max_vel, ctrl_pt_dist, min_seg, seg_num, max_way_points, max_samples):
     """lists of [k, 3] way-point arrays -> (n_way [n], way [n, max_way_points, 3], vel [n, 3], acc [n, 3], WptrajCfg)"""
-    ways = [np.ascontiguousarray(w, dtype=np.float64).reshape(-1, 3) for w in ways]
-    n = len(ways)
-    vel = np.ascontiguousarray(vels, dtype=np.float64).reshape(n, 3)
-    acc = np.ascontiguousarray(accs, dtype=np.float64).reshape(n, 3)
-    n_way = np.array([len(w) for w in ways], dtype=np.int32)
-    maxw = int(max_way_points) if max_way_points is not None else max([len(w) for w in ways] + [3])
-    way = np.zeros((n, max(maxw, 0), 3))
-    for b, w in enumerate(ways):
-        k = min(len(w), way.shape[1])  # (a problem longer than max_way_points: the call refuses it by n_way)
-        way[b, :k] = w[:k]
+    n_way, way, maxw = _pack(ways, max_way_points, 3, floor=3)
+    vel = np.ascontiguousarray(vels, dtype=np.float64).reshape(len(n_way), 3)
+    acc = np.ascontiguousarray(accs, dtype=np.float64).reshape(len(n_way), 3)
     c = WptrajCfg(float(max_vel), float(ctrl_pt_dist), int(min_seg), int(seg_num), maxw, int(max_samples))
     return n_way, way, vel, acc, c
 
@@ -67,10 +56,8 @@ def yaw_cfg(mode=0, pos_degree=3, max_ctrl=4, max_seg=None, seg_num=12, lookfwd=
 def quad_plan(cost_function=SMOOTHNESS | GUIDE | START | END, dim=3, max_ctrl=4, end_n=3, max_waypt=0, bounds=False):
     """(lanes per problem, LDS bytes, largest max_ctrl accepted) of the quadratic solve's kernel (fuelmi_quad_plan); host
     only"""
-    out = (C.c_int * 3)()
-    check(lib().fuelmi_quad_plan(C.byref(QuadCfg(int(cost_function), int(dim), int(max_ctrl), int(end_n), int(max_waypt),
-                                                 1 if bounds else 0)), out))
-    return tuple(out)
+    return _plan_query(lib().fuelmi_quad_plan, 3, QuadCfg(int(cost_function), int(dim), int(max_ctrl), int(end_n),
+                                                          int(max_waypt), 1 if bounds else 0))
 
 
 def kino_cfg(max_tau=0.8, init_max_tau=1.0, max_vel=2.25, max_acc=2.0, w_time=10.0, horizon=5.0, resolution=0.025,
@@ -114,21 +101,15 @@ def yawpath_cfg(half_vert_num=3, max_layer=7, yaw_diff=5 * 3.1415926 / 180.0, ma
 
 def yawpath_plan(cfg=None):
     """host only: the shape of the gain and search kernels for a YawPathCfg (fuelmi_yawpath_plan)"""
-    out = (C.c_int * 10)()
-    check(lib().fuelmi_yawpath_plan(C.byref(cfg if cfg is not None else yawpath_cfg()), out))
-    return dict(zip(("lanes", "lds_bytes", "groups_per_workgroup", "max_cells", "max_yaw", "max_ctrl", "search_lanes",
-                     "search_lds_bytes", "search_problems_per_workgroup", "max_layer"), [int(v) for v in out]))
+    return _plan_query(lib().fuelmi_yawpath_plan, 10, cfg if cfg is not None else yawpath_cfg(),
+                       names=("lanes", "lds_bytes", "groups_per_workgroup", "max_cells", "max_yaw", "max_ctrl", "search_lanes",
+                              "search_lds_bytes", "search_problems_per_workgroup", "max_layer"))
 
 
-def _pack_ctrl(ctrl, max_ctrl):
-    """a list of [n, 3] control-point arrays as (n_ctrl [k], ctrl [k, max_ctrl, 3], max_ctrl)"""
-    cs = [np.ascontiguousarray(c, dtype=np.float64).reshape(-1, 3) for c in ctrl]
-    mc = int(max_ctrl) if max_ctrl is not None else max([len(c) for c in cs] + [1])
-    arr = np.zeros((len(cs), max(mc, 0), 3))
-    for i, c in enumerate(cs):
-        k = min(len(c), arr.shape[1])
-        arr[i, :k] = c[:k]
-    return np.array([len(c) for c in cs], dtype=np.int32), arr, mc
+def _spline(ctrl, max_ctrl, floor=4, cols=3):
+    """a list of [n_ctrl, cols] control-point arrays as (n, n_ctrl [n], ctrl [n, max_ctrl, cols], max_ctrl)"""
+    n_ctrl, arr, maxc = _pack(ctrl, max_ctrl, cols, floor=floor)
+    return len(n_ctrl), n_ctrl, arr, maxc
 
 
 def _pack_localseg(states, problems, degree, max_seg, max_ctrl):
@@ -136,25 +117,11 @@ def _pack_localseg(states, problems, degree, max_seg, max_ctrl):
     the state arrays, n_prob, the problem arrays).  A state is a dict: seg_times [S], coef [S, 3, 6], global_duration,
     and -- all optional, as setGlobalTraj leaves them -- local_ctrl [n, 3] with local_knot_span, local_ts (-1),
     local_te (-1), time_change (0), last_time_inc (0).  A problem is (state index, mode, start_t, arg0, arg1)."""
-    nt, n = len(states), len(problems)
-    T = [np.ascontiguousarray(st["seg_times"], dtype=np.float64).reshape(-1) for st in states]
-    cf = [np.ascontiguousarray(st["coef"], dtype=np.float64).reshape(-1, 3, 6) for st in states]
-    lc = [np.zeros((0, 3)) if st.get("local_ctrl") is None else
-          np.ascontiguousarray(st["local_ctrl"], dtype=np.float64).reshape(-1, 3) for st in states]
-    ms = int(max_seg) if max_seg is not None else max([len(v) for v in T] + [1])
-    mc = int(max_ctrl) if max_ctrl is not None else max([len(v) for v in lc] + [int(degree) + 1])
-    c = LocalSegCfg(int(degree), ms, mc, 0)
-    n_seg = np.array([len(v) for v in T], dtype=np.int32)
-    n_loc = np.array([len(v) for v in lc], dtype=np.int32)
-    a_T, a_cf, a_lc = np.zeros((nt, max(ms, 0))), np.zeros((nt, max(ms, 0), 3, 6)), np.zeros((nt, max(mc, 0), 3))
-    for i in range(nt):
-        if len(cf[i]) != len(T[i]):
-            raise ValueError("local segments: state %d has %d segment times and %d coefficient blocks" %
-                             (i, len(T[i]), len(cf[i])))
-        k = min(len(T[i]), a_T.shape[1])
-        a_T[i, :k], a_cf[i, :k] = T[i][:k], cf[i][:k]
-        k = min(len(lc[i]), a_lc.shape[1])
-        a_lc[i, :k] = lc[i][:k]
+    n_seg, a_T, ms = _pack([st["seg_times"] for st in states], max_seg, 0, floor=1)
+    n_cf, a_cf, _ = _pack([st["coef"] for st in states], ms, (3, 6))
+    for i in np.flatnonzero(n_cf != n_seg):
+        raise ValueError("local segments: state %d has %d segment times and %d coefficient blocks" % (i, n_seg[i], n_cf[i]))
+    n_loc, a_lc, mc = _pack([st.get("local_ctrl") for st in states], max_ctrl, 3, floor=int(degree) + 1)
 
     def col(key, default):
         return np.array([float(st.get(key, default)) for st in states], dtype=np.float64)
@@ -163,11 +130,7 @@ def _pack_localseg(states, problems, degree, max_seg, max_ctrl):
     pr = [tuple(q) for q in problems]
     pr_arr = [np.array([int(q[0]) for q in pr], dtype=np.int32), np.array([int(q[1]) for q in pr], dtype=np.int32)] + \
         [np.array([float(q[k]) for q in pr], dtype=np.float64) for k in (2, 3, 4)]
-    return c, nt, st_arr, n, pr_arr
-
-
-def _ptr(a):
-    return _ip(a) if a.dtype == np.int32 else _dp(a)
+    return LocalSegCfg(int(degree), ms, mc, 0), len(states), st_arr, len(pr), pr_arr
 
 
 def traj_check_cfg(degree=3, max_ctrl=4, step=0.02, max_radius=6.0):
@@ -184,37 +147,21 @@ def traj_sample_cfg(mode=_lib.TRAJSMP_COMMAND, degree=3, yaw_degree=3, max_ctrl=
 def _trajsmp_io(n, t, yaw_ctrl, yaw_dt, t_stop, flight, max_yaw_ctrl, max_t):
     """The host arrays both sampling calls share: (arguments from n_yaw_ctrl on, the result dict, the two strides).  t
     and yaw_ctrl are one 1-D array per problem (yaw_ctrl None, or None for a problem: no yaw spline)."""
-    ts = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in t]
-    assert len(ts) == n
-    maxt = int(max_t) if max_t is not None else max([len(v) for v in ts] + [0])
-    n_t = np.array([len(v) for v in ts], dtype=np.int32)
-    tt = np.zeros((n, max(maxt, 0)))
-    for b, v in enumerate(ts):
-        k = min(len(v), tt.shape[1])
-        tt[b, :k] = v[:k]
+    n_t, tt, maxt = _pack(t, max_t, 0)
+    assert len(n_t) == n
     n_yaw = yaw = ydt = None
     maxy = int(max_yaw_ctrl) if max_yaw_ctrl is not None else 0
     if yaw_ctrl is not None:
-        ys = [np.zeros(0) if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in yaw_ctrl]
-        assert len(ys) == n
-        if max_yaw_ctrl is None:
-            maxy = max([len(v) for v in ys] + [0])
-        n_yaw = np.array([len(v) for v in ys], dtype=np.int32)
-        yaw = np.zeros((n, max(maxy, 0)))
-        for b, v in enumerate(ys):
-            k = min(len(v), yaw.shape[1])
-            yaw[b, :k] = v[:k]
-        ydt = np.ascontiguousarray(np.broadcast_to(np.asarray(yaw_dt, dtype=np.float64), (n,)))
-    stop = None if t_stop is None else np.ascontiguousarray(np.broadcast_to(np.asarray(t_stop, dtype=np.float64), (n,)))
+        n_yaw, yaw, maxy = _pack(yaw_ctrl, max_yaw_ctrl, 0)
+        assert len(n_yaw) == n
+        ydt = _per_problem(yaw_dt, n)
+    stop = _per_problem(t_stop, n, optional=True)
     fl = None if flight is None else np.array(flight, dtype=np.float64).reshape(n, 8)
-    s = (n, max(maxt, 0))
-    o = {"status": np.zeros(s, dtype=np.int32), "pos": np.zeros(s + (3,)), "vel": np.zeros(s + (3,)),
-         "acc": np.zeros(s + (3,)), "jerk": np.zeros(s + (3,)), "yaw": np.zeros(s), "yawdot": np.zeros(s),
-         "yawddot": np.zeros(s), "duration": np.zeros(n), "flight": fl, "n_t": n_t}
-    args = (_ip(n_yaw), _dp(yaw), _dp(ydt), _dp(stop), _ip(n_t), _dp(tt), _ip(o["status"]), _dp(o["pos"]), _dp(o["vel"]),
-            _dp(o["acc"]), _dp(o["jerk"]), _dp(o["yaw"]), _dp(o["yawdot"]), _dp(o["yawddot"]), _dp(o["duration"]), _dp(fl))
-    keep = (n_yaw, yaw, ydt, stop, tt)  # (the arrays behind the pointers live as long as the tuple)
-    return args, o, maxy, maxt, keep
+    mt = max(maxt, 0)
+    o, out = _outputs(n, [("status", _I, (mt,)), ("pos vel acc jerk", _D, (mt, 3)), ("yaw yawdot yawddot", _D, (mt,)),
+                          ("duration", _D, ())])
+    o.update(flight=fl, n_t=n_t)
+    return (_ip(n_yaw), _dp(yaw), _dp(ydt), _dp(stop), _ip(n_t), _dp(tt), *out, _dp(fl)), o, maxy, maxt
 
 
 def traj_adjust_cfg(ops=0, degree=3, max_ctrl=4, max_samples=0, realloc_iters=3, n_group=0, limit_vel=2.0, limit_acc=2.0,
@@ -226,52 +173,37 @@ def traj_adjust_cfg(ops=0, degree=3, max_ctrl=4, max_samples=0, realloc_iters=3,
                       float(stat_step))
 
 
-def _knots_or_span(n, ks, knot_span, knots):
-    """What the calls that take a position spline's knot span or its whole knot vectors share: (span [n] or None, knots
-    [n, ks] or None).  knots is one 1-D array per problem, as adjust_trajs takes knots_in and returns knots_out; exactly
-    one of the two is given."""
+def _knot_source(n, ks, knot_span, knots):
+    """What the calls that take a position spline's knot span or its whole knot vectors share: (span [n], "") or (knots
+    [n, ks], "_knots"), the array and the suffix of the entry that takes it.  knots is one 1-D array per problem, as
+    adjust_trajs takes knots_in and returns knots_out; exactly one of the two is given."""
     if (knots is None) == (knot_span is None):
         raise ValueError("give either knot_span or knots")
     if knots is None:
-        return np.ascontiguousarray(np.broadcast_to(np.asarray(knot_span, dtype=np.float64), (n,))), None
+        return _per_problem(knot_span, n), ""
     if len(knots) != n:
         raise ValueError("knots: one array per problem")
-    kin = np.zeros((n, ks))
-    for b, v in enumerate(knots):
-        v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
-        k = min(len(v), ks)
-        kin[b, :k] = v[:k]
-    return None, kin
+    return _pack(knots, ks, 0)[1], "_knots"
 
 
 def _trajadj_io(n, n_ctrl, degree, maxc, knots_in, ratio_in, group, ops, max_samples, n_group):
-    """The host arrays both adjustment calls share: (arguments from knots_in on, the result dict, max_samples, n_group,
-    the arrays behind the pointers).  knots_in is one 1-D array per problem."""
+    """The host arrays both adjustment calls share: (arguments from knots_in on, the result dict, max_samples, n_group).
+    knots_in is one 1-D array per problem."""
     ks = maxc + degree + 1
-    kin = None
-    if knots_in is not None:
-        kin = np.zeros((n, ks))
-        for b, v in enumerate(knots_in):
-            v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
-            k = min(len(v), ks)
-            kin[b, :k] = v[:k]
-    rin = None if ratio_in is None else np.ascontiguousarray(np.broadcast_to(np.asarray(ratio_in, dtype=np.float64), (n,)))
-    grp = best = smp = None
+    kin = None if knots_in is None else _pack(knots_in, ks, 0, n=n)[1]
+    rin = _per_problem(ratio_in, n, optional=True)
+    grp = best = None
     if ops & _lib.TRAJADJ_SELECT:
-        grp = np.ascontiguousarray(np.broadcast_to(np.asarray(0 if group is None else group, dtype=np.int32), (n,)))
+        grp = _per_problem(0 if group is None else group, n, np.int32)
         if n_group is None:
             n_group = int(grp.max()) + 1 if n else 1
         best = np.full(max(int(n_group), 0), -1, dtype=np.int32)
-    if ops & _lib.TRAJADJ_RESAMPLE:
-        if max_samples is None:
-            max_samples = maxc - degree + 2
-        smp = np.zeros((n, max(int(max_samples), 0), 3))
-    info = np.zeros((n, _lib.TRAJADJ_NI), dtype=np.int32)
-    met = np.zeros((n, _lib.TRAJADJ_NM))
-    kout = np.zeros((n, ks))
-    o = {"info": info, "metrics": met, "knots_out": kout, "samples": smp, "best": best, "n_ctrl": n_ctrl}
-    args = (_dp(kin), _dp(rin), _ip(grp), _ip(info), _dp(met), _dp(kout), _dp(smp), _ip(best))
-    return args, o, int(max_samples or 0), int(n_group or 0), (kin, rin, grp)
+    if ops & _lib.TRAJADJ_RESAMPLE and max_samples is None:
+        max_samples = maxc - degree + 2
+    o, out = _outputs(n, [("info", _I, (_lib.TRAJADJ_NI,)), ("metrics", _D, (_lib.TRAJADJ_NM,)), ("knots_out", _D, (ks,)),
+                          ("samples", _D, (max(int(max_samples or 0), 0), 3), ops & _lib.TRAJADJ_RESAMPLE)])
+    o.update(best=best, n_ctrl=n_ctrl)
+    return (_dp(kin), _dp(rin), _ip(grp), *out, _ip(best)), o, int(max_samples or 0), int(n_group or 0)
 
 
 def _trajadj_named(o):
@@ -286,32 +218,50 @@ def _trajadj_named(o):
 def cloud_plan(dims, lo, hi):
     """The geometry fuelmi_map_extract_cloud's kernels use for the inclusive box lo..hi of a dims grid
     (fuelmi_cloud_plan, host only).  Raises FuelmiError for a box that leaves the map."""
-    out = (C.c_int * 8)()
-    check(lib().fuelmi_cloud_plan(_i3(dims), _i3(lo), _i3(hi), out))
-    keys = ("items_per_line", "lines", "items_per_workgroup", "workgroups", "scan_width", "scan_rounds", "scratch_bytes",
-            "voxels")
-    return dict(zip(keys, [int(v) for v in out]))
+    return _plan_query(lib().fuelmi_cloud_plan, 8, _i3(dims), _i3(lo), _i3(hi),
+                       names=("items_per_line", "lines", "items_per_workgroup", "workgroups", "scan_width", "scan_rounds",
+                              "scratch_bytes", "voxels"))
 
 
-def _trajchk_outputs(n):
-    o = {"status": np.zeros(n, dtype=np.int32), "safe": np.zeros(n, dtype=np.int32), "distance": np.zeros(n),
-         "n_samples": np.zeros(n, dtype=np.int32), "hit_index": np.zeros(n, dtype=np.int32), "hit_t": np.zeros(n),
-         "hit_pos": np.zeros((n, 3)), "end_reason": np.zeros(n, dtype=np.int32), "duration": np.zeros(n)}
-    args = (_ip(o["status"]), _ip(o["safe"]), _dp(o["distance"]), _ip(o["n_samples"]), _ip(o["hit_index"]),
-            _dp(o["hit_t"]), _dp(o["hit_pos"]), _ip(o["end_reason"]), _dp(o["duration"]))
-    return o, args
+# --- the stages an SDFMap runs on splines from the host and a BsplineDeviceProblem on its own: each body builds the inputs
+# and results both share; `call` is the C entry with the spline source in front, taking the rest of the arguments ---
+def _check_trajs(n, t_now, allow_limit, call):
+    now = _per_problem(t_now, n)
+    o, out = _outputs(n, [("status safe", _I, ()), ("distance", _D, ()), ("n_samples hit_index", _I, ()), ("hit_t", _D, ()),
+                          ("hit_pos", _D, (3,)), ("end_reason", _I, ()), ("duration", _D, ())])
+    o["limit"] = _limited(call(_dp(now), *out), allow_limit)
+    return o
 
 
-def _yaw_outputs(n, max_seg, derivs):
-    ms = max(int(max_seg), 0)
-    o = {"status": np.zeros(n, dtype=np.int32), "duration": np.zeros(n), "seg_num": np.zeros(n, dtype=np.int32),
-         "dt_yaw": np.zeros(n), "yaw_ctrl": np.zeros((n, ms + 3)), "n_waypt": np.zeros(n, dtype=np.int32),
-         "waypts": np.zeros((n, ms)), "end_yaw": np.zeros(n), "cost": np.zeros(n),
-         "yawdot_ctrl": np.zeros((n, ms + 2)) if derivs else None, "yawddot_ctrl": np.zeros((n, ms + 1)) if derivs else None}
-    args = (_ip(o["status"]), _dp(o["duration"]), _ip(o["seg_num"]), _dp(o["dt_yaw"]), _dp(o["yaw_ctrl"]),
-            _ip(o["n_waypt"]), _dp(o["waypts"]), _dp(o["end_yaw"]), _dp(o["cost"]), _dp(o["yawdot_ctrl"]),
-            _dp(o["yawddot_ctrl"]))
-    return o, args
+def _plan_yaws(n, yc, start_yaw, end_yaw, derivs, allow_limit, call):
+    sy = np.ascontiguousarray(start_yaw, dtype=np.float64).reshape(n, 3)
+    ey = _per_problem(end_yaw, n, optional=True)
+    ms = max(int(yc.max_seg), 0)
+    o, out = _outputs(n, [("status", _I, ()), ("duration", _D, ()), ("seg_num", _I, ()), ("dt_yaw", _D, ()),
+                          ("yaw_ctrl", _D, (ms + 3,)), ("n_waypt", _I, ()), ("waypts", _D, (ms,)), ("end_yaw cost", _D, ()),
+                          ("yawdot_ctrl", _D, (ms + 2,), derivs), ("yawddot_ctrl", _D, (ms + 1,), derivs)])
+    o["limit"] = _limited(call(C.byref(yc), _dp(sy), _dp(ey), *out), allow_limit)
+    return o
+
+
+def _solve_quadratic(n, qc, call):
+    o, out = _outputs(n, [("status", _I, ()), ("ctrl_out", _D, (max(qc.max_ctrl, 0), qc.dim)), ("cost pt_dist", _D, ())])
+    check(call(C.byref(qc), *out))
+    return o
+
+
+def _kino(points, cfg, n, table, allow_limit, call):
+    """start, velocity, acceleration, goal, goal velocity [n, 3] each (n None: as many as there are starts) and the fields
+    of kino_cfg() -> (the KinoCfg, the results of table(cfg), the limit flag); call(cfg, n, the five arrays, the results)"""
+    kc = kino_cfg(**cfg)
+    arr = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3) for a in points]
+    if n is None:
+        n = len(arr[0])
+        assert all(len(a) == n for a in arr)
+    elif any(len(a) != n for a in arr):
+        raise ValueError("load_kino: one problem per candidate")
+    o, out = _outputs(n, table(kc))
+    return kc, o, _limited(call(C.byref(kc), n, *[_dp(a) for a in arr], *out), allow_limit)
 
 
 def _d3(v):
@@ -378,10 +328,8 @@ class SDFMap:
         _PLAIN32; fuelmi_map_esdf_plan, host only): {"family": what lastEsdfFamily() then reports, "launches": [{"kernel",
         "grid", "block", "lds", "ZC", "nzc", "z0a"}, ...] in order z/y+, x+ (, z/y-, x- for signed maps)}.  Raises
         FuelmiError for a box the update refuses."""
-        out = (C.c_int * 42)()
-        ints = lambda v: (C.c_int * 3)(*[int(a) for a in v])
         flags = (1 if optimistic else 0) | (2 if signed_dist else 0)
-        check(lib().fuelmi_map_esdf_plan(ints(dims), ints(lo), ints(hi), int(family), flags, out))
+        out = _plan_query(lib().fuelmi_map_esdf_plan, 42, _i3(dims), _i3(lo), _i3(hi), int(family), flags)
         launches = []
         for i in range(out[0]):
             k, a0, a1, a2, grid, block, lds, zc, nzc, z0a = out[2 + 10 * i:12 + 10 * i]
@@ -395,8 +343,7 @@ class SDFMap:
     def insertPlan():
         """The geometry the fusion kernels are compiled with (fuelmi_map_insert_plan, host only): lanes that share a ray
         walk, point slots per ray-walk and per classify workgroup, voxel extents of a ray workgroup's LDS miss cube."""
-        out = (C.c_int * 8)()
-        check(lib().fuelmi_map_insert_plan(out))
+        out = _plan_query(lib().fuelmi_map_insert_plan, 8)
         return {"lanes_per_ray": out[0], "ray_slots": out[1], "classify_slots": out[2], "cube": (out[3], out[4], out[5])}
 
     def lastInflateKernel(self):
@@ -413,9 +360,7 @@ class SDFMap:
         """The word ranges and launches clearAndInflateLocalMap uses for the box [lo, hi] of a dims grid whose
         inflate_step is `step` under the pin `kernel` (fuelmi_map_inflate_plan, host only).  "grids": workgroups of 256
         of the fused kernel, the masking pass, the y/z pass and the x pass; 0 where a kernel does not run."""
-        out = (C.c_int * 16)()
-        check(lib().fuelmi_map_inflate_plan(_i3(dims), int(step), _i3(lo), _i3(hi), int(kernel), out))
-        v = [int(a) for a in out]
+        v = _plan_query(lib().fuelmi_map_inflate_plan, 16, _i3(dims), int(step), _i3(lo), _i3(hi), int(kernel))
         return {"kernel": v[0], "margin_words": v[1], "W": v[2], "out": (v[3], v[4]), "t": (v[5], v[6]), "s": (v[7], v[8]),
                 "whole": bool(v[9]), "lds": v[10],
                 "grids": {"fused": v[11], "box_and": v[12], "yz": v[13], "x": v[14]}}
@@ -588,8 +533,7 @@ class SDFMap:
         cap = int(cap)
         out = np.empty((max(cap, 0), 3), dtype=np.float32)
         rc = self.L.fuelmi_map_extract_cloud(self.h, C.byref(cfg), out.ctypes.data if cap > 0 else None, cap, C.byref(n))
-        if rc != _lib.ELIMIT:
-            check(rc)
+        _limited(rc, True)
         return out[:min(n.value, cap)].copy(), n.value
 
     def cloud_times(self):
@@ -672,22 +616,15 @@ class SDFMap:
         n = len(p1)
         c = GoalCfg(PathCfg(float(res), float(edge_step), 0.0, int(max_path_points)), float(shorten_dist),
                     float(end_eps), float(radius_close), float(radius_far), int(max_way_points))
-        status = np.zeros(n, dtype=np.int32)
-        length = np.zeros(n)
-        n_way = np.zeros(n, dtype=np.int32)
-        way = np.zeros((n, max(int(max_way_points), 0), 3))
-        nxt = np.zeros((n, 3))
-        rlen = np.zeros(n, dtype=np.int32) if raw else None
-        rxyz = np.zeros((n, max(int(max_path_points), 0), 3)) if raw else None
-        rc = self.L.fuelmi_map_goal_paths(self.h, C.byref(c), n, _dp(p1), _dp(p2), _ip(status), _dp(length), _ip(n_way),
-                                          _dp(way), _dp(nxt), _ip(rlen), _dp(rxyz))
-        if not (allow_limit and rc == -5):
-            check(rc)
-        out = {"status": status, "length": length, "n_way": n_way, "next_goal": nxt, "limit": rc == -5,
-               "way": [way[b, :min(n_way[b], way.shape[1])].copy() for b in range(n)]}
+        mw, mp = max(int(max_way_points), 0), max(int(max_path_points), 0)
+        out, res = _outputs(n, [("status", _I, ()), ("length", _D, ()), ("n_way", _I, ()), ("way", _D, (mw, 3)),
+                                ("next_goal", _D, (3,)), ("raw_len", _I, (), raw), ("raw", _D, (mp, 3), raw)])
+        out["limit"] = _limited(self.L.fuelmi_map_goal_paths(self.h, C.byref(c), n, _dp(p1), _dp(p2), *res), allow_limit)
+        way, rlen, rxyz = out["way"], out.pop("raw_len"), out.pop("raw")
+        out["way"] = [way[b, :min(out["n_way"][b], mw)].copy() for b in range(n)]
         if raw:
             out["raw_len"] = rlen
-            out["raw"] = [rxyz[b, :rlen[b] if rlen[b] <= rxyz.shape[1] else 0].copy() for b in range(n)]
+            out["raw"] = [rxyz[b, :rlen[b] if rlen[b] <= mp else 0].copy() for b in range(n)]
         return out
 
     def goal_path_times(self):
@@ -708,24 +645,16 @@ class SDFMap:
         [S, 3, 6]); limit (a sample count exceeded max_samples).  FUELMI_ELIMIT raises FuelmiError unless allow_limit."""
         n_way, way, vel, acc, c = _pack_waypoints(ways, vels, accs, max_vel, ctrl_pt_dist, min_seg, seg_num,
                                                   max_way_points, max_samples)
-        n, maxw, maxs = len(n_way), c.max_way_points, max(c.max_samples, 0)
-        status = np.zeros(n, dtype=np.int32)
-        segs = np.zeros(n, dtype=np.int32)
-        ns = np.zeros(n, dtype=np.int32)
-        duration, length, dt = np.zeros(n), np.zeros(n), np.zeros(n)
-        samples = np.zeros((n, maxs, 3))
-        derivs = np.zeros((n, 4, 3))
-        tim = np.zeros((n, max(maxw - 1, 0))) if coef else None
-        cf = np.zeros((n, max(maxw - 1, 0), 3, 6)) if coef else None
-        rc = self.L.fuelmi_map_waypoint_trajs(self.h, C.byref(c), n, _ip(n_way), _dp(way), _dp(vel), _dp(acc), _ip(status),
-                                              _dp(duration), _dp(length), _ip(segs), _dp(dt), _ip(ns), _dp(samples),
-                                              _dp(derivs), _dp(tim), _dp(cf))
-        if not (allow_limit and rc == -5):
-            check(rc)
-        out = {"status": status, "duration": duration, "length": length, "seg_num": segs, "dt": dt, "n_samples": ns,
-               "derivs": derivs, "limit": rc == -5, "samples": [samples[b, :min(ns[b], maxs)].copy() for b in range(n)]}
+        n, maxs, segs = len(n_way), max(c.max_samples, 0), max(c.max_way_points - 1, 0)
+        out, res = _outputs(n, [("status", _I, ()), ("duration length", _D, ()), ("seg_num", _I, ()), ("dt", _D, ()),
+                                ("n_samples", _I, ()), ("samples", _D, (maxs, 3)), ("derivs", _D, (4, 3)),
+                                ("seg_times", _D, (segs,), coef), ("coef", _D, (segs, 3, 6), coef)])
+        out["limit"] = _limited(self.L.fuelmi_map_waypoint_trajs(self.h, C.byref(c), n, _ip(n_way), _dp(way), _dp(vel),
+                                                                 _dp(acc), *res), allow_limit)
+        samples, tim, cf = out["samples"], out.pop("seg_times"), out.pop("coef")
+        out["samples"] = [samples[b, :min(out["n_samples"][b], maxs)].copy() for b in range(n)]
         if coef:
-            live = [max(int(n_way[b]) - 1, 0) if status[b] in (0, -1) else 0 for b in range(n)]
+            live = [max(int(n_way[b]) - 1, 0) if out["status"][b] in (0, -1) else 0 for b in range(n)]
             out["seg_times"] = [tim[b, :live[b]].copy() for b in range(n)]
             out["coef"] = [cf[b, :live[b]].copy() for b in range(n)]
         return out
@@ -733,9 +662,7 @@ class SDFMap:
     @staticmethod
     def waypoint_traj_plan(max_way_points):
         """(lanes per problem, LDS bytes, largest max_way_points accepted) of the way-point kernel; host only"""
-        out = (C.c_int * 3)()
-        check(lib().fuelmi_wptraj_plan(C.byref(WptrajCfg(2.0, 0.45, 8, 0, int(max_way_points), 1)), out))
-        return tuple(out)
+        return _plan_query(lib().fuelmi_wptraj_plan, 3, WptrajCfg(2.0, 0.45, 8, 0, int(max_way_points), 1))
 
     # --- the kinodynamic search of the mid-range branch (include/fuelmi.h fuelmi_map_kino_paths) ---
     KINO_REACH_HORIZON, KINO_REACH_END, KINO_NO_PATH, KINO_NEAR_END, KINO_CLOSE_GOAL = (
@@ -747,43 +674,27 @@ class SDFMap:
         shot, t_shot, coef [n, 3, 4], T_sum, ts, seg_num, n_samples [n], samples (list of [k, 3]), derivs [n, 4, 3], and
         with nodes: node_state (list of [k, 6]), node_input (list of [k, 3]), node_duration (list of [k]); limit.
         FUELMI_ELIMIT raises FuelmiError unless allow_limit."""
-        c = kino_cfg(**cfg)
-        arr = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3) for a in (starts, vels, accs, goals, goal_vels)]
-        n = len(arr[0])
-        assert all(len(a) == n for a in arr)
-        maxn, maxs = max(c.max_path_nodes, 0), max(c.max_samples, 0)
-        iv = {k: np.zeros(n, dtype=np.int32) for k in ("status", "which", "iter_num", "use_node_num", "n_nodes", "shot",
-                                                       "seg_num", "n_samples")}
-        dv = {k: np.zeros(n) for k in ("t_shot", "T_sum", "ts")}
-        coef, derivs, samples = np.zeros((n, 3, 4)), np.zeros((n, 4, 3)), np.zeros((n, maxs, 3))
-        ns = np.zeros((n, maxn, 6)) if nodes else None
-        ni = np.zeros((n, maxn, 3)) if nodes else None
-        nd = np.zeros((n, maxn)) if nodes else None
-        rc = self.L.fuelmi_map_kino_paths(self.h, C.byref(c), n, *[_dp(a) for a in arr], _ip(iv["status"]),
-                                          _ip(iv["which"]), _ip(iv["iter_num"]), _ip(iv["use_node_num"]),
-                                          _ip(iv["n_nodes"]), _dp(ns), _dp(ni), _dp(nd), _ip(iv["shot"]), _dp(dv["t_shot"]),
-                                          _dp(coef), _dp(dv["T_sum"]), _dp(dv["ts"]), _ip(iv["seg_num"]),
-                                          _ip(iv["n_samples"]), _dp(samples), _dp(derivs))
-        if not (allow_limit and rc == -5):
-            check(rc)
-        out = dict(iv)
-        out.update(dv)
-        out.update(coef=coef, derivs=derivs, limit=rc == -5,
-                   samples=[samples[b, :min(iv["n_samples"][b], maxs)].copy() for b in range(n)])
-        if nodes:
-            live = [min(int(iv["n_nodes"][b]), maxn) for b in range(n)]
-            out["node_state"] = [ns[b, :live[b]].copy() for b in range(n)]
-            out["node_input"] = [ni[b, :live[b]].copy() for b in range(n)]
-            out["node_duration"] = [nd[b, :live[b]].copy() for b in range(n)]
+        def table(c):
+            maxn, maxs = max(c.max_path_nodes, 0), max(c.max_samples, 0)
+            return [("status which iter_num use_node_num n_nodes", _I, ()), ("node_state", _D, (maxn, 6), nodes),
+                    ("node_input", _D, (maxn, 3), nodes), ("node_duration", _D, (maxn,), nodes), ("shot", _I, ()),
+                    ("t_shot", _D, ()), ("coef", _D, (3, 4)), ("T_sum ts", _D, ()), ("seg_num n_samples", _I, ()),
+                    ("samples", _D, (maxs, 3)), ("derivs", _D, (4, 3))]
+        c, out, out["limit"] = _kino((starts, vels, accs, goals, goal_vels), cfg, None, table, allow_limit,
+                                     lambda *a: self.L.fuelmi_map_kino_paths(self.h, *a))
+        for key, count in (("samples", "n_samples"), ("node_state", "n_nodes"), ("node_input", "n_nodes"),
+                           ("node_duration", "n_nodes")):
+            arr = out.pop(key)
+            if arr is not None:
+                out[key] = [arr[b, :min(int(k), arr.shape[1])].copy() for b, k in enumerate(out[count])]
         return out
 
     @staticmethod
     def kino_plan(**cfg):
         """host only: dict(lanes, lds_bytes, workspace_bytes, n_init, n_regular, max_prims, max_alloc, hash_slots)"""
-        out = (C.c_longlong * 8)()
-        check(lib().fuelmi_kino_plan(C.byref(kino_cfg(**cfg)), out))
-        return dict(zip(("lanes", "lds_bytes", "workspace_bytes", "n_init", "n_regular", "max_prims", "max_alloc",
-                         "hash_slots"), [int(v) for v in out]))
+        return _plan_query(lib().fuelmi_kino_plan, 8, kino_cfg(**cfg), ctype=C.c_longlong,
+                           names=("lanes", "lds_bytes", "workspace_bytes", "n_init", "n_regular", "max_prims", "max_alloc",
+                                  "hash_slots"))
 
     # --- the topological path search of guided replanning (include/fuelmi.h fuelmi_map_topo_paths) ---
     TOPO_OK, TOPO_NO_PATH, TOPO_UNDEFINED = _lib.TOPO_OK, _lib.TOPO_NO_PATH, _lib.TOPO_UNDEFINED
@@ -802,36 +713,21 @@ class SDFMap:
         smp = np.ascontiguousarray(samples, dtype=np.float64).reshape(n, -1, 3) if n else np.zeros((0, 0, 3))
         c = topo_cfg(**dict(cfg, max_sample_num=smp.shape[1]))
 
-        def pack(lists):
-            lists = [np.zeros((0, 3)) if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3)
-                     for a in (lists if lists is not None else [None] * n)]
-            cap = max([len(a) for a in lists] + [0])
-            cnt = np.array([len(a) for a in lists], dtype=np.int32)
-            arr = np.zeros((n, cap, 3))
-            for b, a in enumerate(lists):
-                arr[b, :len(a)] = a
-            return cap, cnt, arr
-        ms, nsp, sp = pack(start_pts)
-        me, nep, ep = pack(end_pts)
+        nsp, sp, ms = _pack(start_pts, None, 3, n=n)
+        nep, ep, me = _pack(end_pts, None, 3, n=n)
         maxn, mpp, r2, rs = max(c.max_nodes, 0), max(c.max_path_points, 0), max(c.max_raw_path2, 0), max(c.reserve_num, 0)
-        iv = dict(status=np.zeros(n, dtype=np.int32), counts=np.zeros((n, 4), dtype=np.int32),
-                  events=np.zeros((n, 6), dtype=np.int32), n_nodes=np.zeros(n, dtype=np.int32))
-        nid, nty = np.zeros((n, maxn), dtype=np.int32), np.zeros((n, maxn), dtype=np.int32)
-        nxyz, off, ids = np.zeros((n, maxn, 3)), np.zeros((n, maxn + 1), dtype=np.int32), np.zeros((n, 4 * maxn), dtype=np.int32)
-        raw, filt, sel = np.zeros((n, r2, mpp, 3)), np.zeros((n, r2, mpp, 3)), np.zeros((n, rs, mpp, 3))
-        rl, fl, sl = np.zeros((n, r2), dtype=np.int32), np.zeros((n, r2), dtype=np.int32), np.zeros((n, rs), dtype=np.int32)
-        slen = np.zeros((n, rs))
-        rc = self.L.fuelmi_map_topo_paths(self.h, C.byref(c), n, _dp(st), _dp(en), ms, _ip(nsp), _dp(sp), me, _ip(nep),
-                                          _dp(ep), _dp(smp), _ip(iv["status"]), _ip(iv["counts"]), _ip(iv["events"]),
-                                          _ip(iv["n_nodes"]), _ip(nid), _ip(nty), _dp(nxyz), _ip(off), _ip(ids), _dp(raw),
-                                          _ip(rl), _dp(filt), _ip(fl), _dp(sel), _ip(sl), _dp(slen))
-        if not (allow_limit and rc == -5):
-            check(rc)
-        out = dict(iv)
-        out.update(limit=rc == -5, raw_len=rl, filt_len=fl, sel_len=sl, sel_length=slen)
+        out, res = _outputs(n, [("status", _I, ()), ("counts", _I, (4,)), ("events", _I, (6,)), ("n_nodes", _I, ()),
+                                ("nid nty", _I, (maxn,)), ("nxyz", _D, (maxn, 3)), ("off", _I, (maxn + 1,)),
+                                ("ids", _I, (4 * maxn,)), ("raw", _D, (r2, mpp, 3)), ("raw_len", _I, (r2,)),
+                                ("filt", _D, (r2, mpp, 3)), ("filt_len", _I, (r2,)), ("sel", _D, (rs, mpp, 3)),
+                                ("sel_len", _I, (rs,)), ("sel_length", _D, (rs,))])
+        out["limit"] = _limited(self.L.fuelmi_map_topo_paths(self.h, C.byref(c), n, _dp(st), _dp(en), ms, _ip(nsp), _dp(sp),
+                                                             me, _ip(nep), _dp(ep), _dp(smp), *res), allow_limit)
+        nid, nty, nxyz, off, ids = (out.pop(k) for k in ("nid", "nty", "nxyz", "off", "ids"))
         out["nodes"] = [[(int(nid[b, i]), int(nty[b, i]), nxyz[b, i].copy(), ids[b, off[b, i]:off[b, i + 1]].copy())
-                         for i in range(min(int(iv["n_nodes"][b]), maxn))] for b in range(n)]
-        for key, arr, ln in (("raw", raw, rl), ("filt", filt, fl), ("sel", sel, sl)):
+                         for i in range(min(int(out["n_nodes"][b]), maxn))] for b in range(n)]
+        for key in ("raw", "filt", "sel"):
+            arr, ln = out[key], out[key + "_len"]
             out[key] = [[arr[b, r, :min(int(ln[b, r]), mpp)].copy() for r in range(ln.shape[1]) if ln[b, r] > 0]
                         for b in range(n)]
         return out
@@ -840,11 +736,10 @@ class SDFMap:
     def topo_plan(**cfg):
         """host only: dict(lanes, lds_bytes, workspace_bytes, guard_chunk, max_samples, max_raw, max_path_points,
         max_dis_points, max_neighbors, undefined_raw_nodes, max_points_in, max_workspace)"""
-        out = (C.c_longlong * 12)()
-        check(lib().fuelmi_topo_plan(C.byref(topo_cfg(**cfg)), out))
-        return dict(zip(("lanes", "lds_bytes", "workspace_bytes", "guard_chunk", "max_samples", "max_raw", "max_path_points",
-                         "max_dis_points", "max_neighbors", "undefined_raw_nodes", "max_points_in", "max_workspace"),
-                        [int(v) for v in out]))
+        return _plan_query(lib().fuelmi_topo_plan, 12, topo_cfg(**cfg), ctype=C.c_longlong,
+                           names=("lanes", "lds_bytes", "workspace_bytes", "guard_chunk", "max_samples", "max_raw",
+                                  "max_path_points", "max_dis_points", "max_neighbors", "undefined_raw_nodes", "max_points_in",
+                                  "max_workspace"))
 
     def topo_pool_bytes(self):
         """bytes of the map's grow-only workspace of topo_paths"""
@@ -861,39 +756,23 @@ class SDFMap:
         n_end_events, t_s, t_e, colli_start / colli_end [n, max_events, 3], n_start_pts / n_end_pts, start_pts / end_pts
         [n, max_pts, 3] (the layout topo_paths' C entry takes), first_start / last_end [n, 3]; limit.  FUELMI_ELIMIT
         raises FuelmiError unless allow_limit."""
-        pos = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in pos_ctrl]
-        n = len(pos)
-        maxc = int(max_ctrl) if max_ctrl is not None else max([len(p) for p in pos] + [4])
+        n, n_ctrl, arr, maxc = _spline(pos_ctrl, max_ctrl)
         c = colrange_cfg(max_ctrl=maxc, **cfg)
-        n_ctrl = np.array([len(p) for p in pos], dtype=np.int32)
-        arr = np.zeros((n, max(maxc, 0), 3))
-        for b, p in enumerate(pos):
-            k = min(len(p), arr.shape[1])
-            arr[b, :k] = p[:k]
-        knot = np.ascontiguousarray(np.broadcast_to(np.asarray(knot_span, dtype=np.float64), (n,)))
+        knot = _per_problem(knot_span, n)
         ev, mp = max(c.max_events, 0), max(c.max_pts, 0)
-        o = {k: np.zeros(n, dtype=np.int32) for k in ("status", "n_ticks", "n_start_events", "n_end_events", "n_start_pts",
-                                                      "n_end_pts")}
-        o.update(t_s=np.zeros(n), t_e=np.zeros(n), colli_start=np.zeros((n, ev, 3)), colli_end=np.zeros((n, ev, 3)),
-                 start_pts=np.zeros((n, mp, 3)), end_pts=np.zeros((n, mp, 3)), first_start=np.zeros((n, 3)),
-                 last_end=np.zeros((n, 3)))
-        rc = self.L.fuelmi_map_collision_ranges(
-            self.h, C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(knot), _ip(o["status"]), _ip(o["n_ticks"]),
-            _ip(o["n_start_events"]), _ip(o["n_end_events"]), _dp(o["t_s"]), _dp(o["t_e"]), _dp(o["colli_start"]),
-            _dp(o["colli_end"]), _ip(o["n_start_pts"]), _dp(o["start_pts"]), _ip(o["n_end_pts"]), _dp(o["end_pts"]),
-            _dp(o["first_start"]), _dp(o["last_end"]))
-        if not (allow_limit and rc == -5):
-            check(rc)
-        o["limit"] = rc == -5
+        o, out = _outputs(n, [("status n_ticks n_start_events n_end_events", _I, ()), ("t_s t_e", _D, ()),
+                              ("colli_start colli_end", _D, (ev, 3)), ("n_start_pts", _I, ()), ("start_pts", _D, (mp, 3)),
+                              ("n_end_pts", _I, ()), ("end_pts", _D, (mp, 3)), ("first_start last_end", _D, (3,))])
+        o["limit"] = _limited(self.L.fuelmi_map_collision_ranges(self.h, C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(knot), *out),
+                              allow_limit)
         return o
 
     @staticmethod
     def colrange_plan(cfg):
         """host only: dict(lanes, lds_bytes, waves, max_ticks, max_ctrl, max_pts) of the collision-range kernel for a
         ColRangeCfg"""
-        out = (C.c_int * 6)()
-        check(lib().fuelmi_colrange_plan(C.byref(cfg), out))
-        return dict(zip(("lanes", "lds_bytes", "waves", "max_ticks", "max_ctrl", "max_pts"), [int(v) for v in out]))
+        return _plan_query(lib().fuelmi_colrange_plan, 6, cfg,
+                           names=("lanes", "lds_bytes", "waves", "max_ticks", "max_ctrl", "max_pts"))
 
     def guide_points(self, paths, duration, ctrl_pt_dist=0.5, degree=3, max_guide=64, max_path_points=None,
                      allow_limit=False):
@@ -901,24 +780,13 @@ class SDFMap:
         duration [n] the local segment's duration.  Returns a dict of arrays: status (TOPO_OK, TOPO_UNDEFINED; -1: over
         max_guide or the point cap), seg_num, dt, n_pts, n_ctrl, n_guide, guide_pts [n, max_guide, 3] (rows as
         BsplineBatchProblem's guide_pts takes them for degrees 3 and 4); limit."""
-        ps = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in paths]
-        n = len(ps)
-        mpp = int(max_path_points) if max_path_points is not None else max([len(p) for p in ps] + [1])
-        arr = np.zeros((n, max(mpp, 0), 3))
-        for b, p in enumerate(ps):
-            k = min(len(p), arr.shape[1])
-            arr[b, :k] = p[:k]
-        plen = np.array([len(p) for p in ps], dtype=np.int32)
-        dur = np.ascontiguousarray(np.broadcast_to(np.asarray(duration, dtype=np.float64), (n,)))
-        mg = max(int(max_guide), 0)
-        o = {k: np.zeros(n, dtype=np.int32) for k in ("status", "seg_num", "n_pts", "n_ctrl", "n_guide")}
-        o.update(dt=np.zeros(n), guide_pts=np.zeros((n, mg, 3)))
-        rc = self.L.fuelmi_map_guide_points(self.h, n, mpp, _dp(arr), _ip(plen), _dp(dur), float(ctrl_pt_dist), int(degree),
-                                            int(max_guide), _ip(o["status"]), _ip(o["seg_num"]), _dp(o["dt"]),
-                                            _ip(o["n_pts"]), _ip(o["n_ctrl"]), _ip(o["n_guide"]), _dp(o["guide_pts"]))
-        if not (allow_limit and rc == -5):
-            check(rc)
-        o["limit"] = rc == -5
+        plen, arr, mpp = _pack(paths, max_path_points, 3, floor=1)
+        n = len(plen)
+        dur = _per_problem(duration, n)
+        o, out = _outputs(n, [("status seg_num", _I, ()), ("dt", _D, ()), ("n_pts n_ctrl n_guide", _I, ()),
+                              ("guide_pts", _D, (max(int(max_guide), 0), 3))])
+        o["limit"] = _limited(self.L.fuelmi_map_guide_points(self.h, n, mpp, _dp(arr), _ip(plen), _dp(dur), float(ctrl_pt_dist),
+                                                             int(degree), int(max_guide), *out), allow_limit)
         return o
 
     # --- local segments of the global trajectory (include/fuelmi.h fuelmi_map_local_segments) ---
@@ -937,26 +805,20 @@ class SDFMap:
         c, nt, st_arr, n, pr_arr = _pack_localseg(states, problems, degree, max_seg, max_ctrl)
         c.max_points = int(max_points)
         mp = max(c.max_points, 0)
-        o = {k: np.zeros(n, dtype=np.int32) for k in ("status", "n_steps", "seg_num", "n_points", "n_ctrl")}
-        o.update(segment_len=np.zeros(n), duration=np.zeros(n), dt=np.zeros(n), points=np.zeros((n, mp, 3)),
-                 derivs=np.zeros((n, 4, 3)), ctrl=np.zeros((n, mp + max(c.degree, 1) - 1, 3)))
-        rc = self.L.fuelmi_map_local_segments(
-            self.h, C.byref(c), nt, *[_ptr(a) for a in st_arr], n, *[_ptr(a) for a in pr_arr], _ip(o["status"]),
-            _ip(o["n_steps"]), _dp(o["segment_len"]), _ip(o["seg_num"]), _dp(o["duration"]), _dp(o["dt"]),
-            _ip(o["n_points"]), _dp(o["points"]), _dp(o["derivs"]), _ip(o["n_ctrl"]), _dp(o["ctrl"]))
-        if not (allow_limit and rc == -5):
-            check(rc)
-        o["limit"] = rc == -5
+        o, out = _outputs(n, [("status n_steps", _I, ()), ("segment_len", _D, ()), ("seg_num", _I, ()), ("duration dt", _D, ()),
+                              ("n_points", _I, ()), ("points", _D, (mp, 3)), ("derivs", _D, (4, 3)), ("n_ctrl", _I, ()),
+                              ("ctrl", _D, (mp + max(c.degree, 1) - 1, 3))])
+        o["limit"] = _limited(self.L.fuelmi_map_local_segments(self.h, C.byref(c), nt, *[_ptr(a) for a in st_arr], n,
+                                                               *[_ptr(a) for a in pr_arr], *out), allow_limit)
         return o
 
     @staticmethod
     def localseg_plan(degree=3, max_seg=1, max_ctrl=4, max_points=64):
         """host only: dict(lanes, lds_bytes, waves, max_seg, max_ctrl, max_points, count_cap, fit_lds_bytes) of the
         local-segment kernel"""
-        out = (C.c_int * 8)()
-        check(lib().fuelmi_localseg_plan(C.byref(LocalSegCfg(int(degree), int(max_seg), int(max_ctrl), int(max_points))), out))
-        return dict(zip(("lanes", "lds_bytes", "waves", "max_seg", "max_ctrl", "max_points", "count_cap", "fit_lds_bytes"),
-                        [int(v) for v in out]))
+        return _plan_query(lib().fuelmi_localseg_plan, 8, LocalSegCfg(int(degree), int(max_seg), int(max_ctrl), int(max_points)),
+                           names=("lanes", "lds_bytes", "waves", "max_seg", "max_ctrl", "max_points", "count_cap",
+                                  "fit_lds_bytes"))
 
     # --- information gain and yaw search of HeadingPlanner (include/fuelmi.h fuelmi_map_info_gains) ---
     GAIN_NON_UNIFORM, GAIN_UNIFORM = _lib.GAIN_NON_UNIFORM, _lib.GAIN_UNIFORM
@@ -968,29 +830,17 @@ class SDFMap:
         (-1: over the cell cap), gain / n_cand / n_visible [n, max_yaw], n_rays [n]; limit."""
         pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
         n = len(pos)
-        ys = [np.atleast_1d(np.asarray(y, dtype=np.float64)) for y in yaws]
-        assert len(ys) == n
-        my = int(max_yaw) if max_yaw is not None else max([len(y) for y in ys] + [1])
+        n_yaw, ya, my = _pack(yaws, max_yaw, 0, floor=1)
+        assert len(n_yaw) == n
         c = gain_cfg(**dict(cfg, max_yaw=my))
-        n_yaw = np.array([len(y) for y in ys], dtype=np.int32)
-        ya = np.zeros((n, max(my, 0)))
-        for b, y in enumerate(ys):
-            k = min(len(y), ya.shape[1])
-            ya[b, :k] = y[:k]
         n_ctrl = carr = pof = None
         n_path = 0
         if ctrl is not None:
-            n_ctrl, carr, c.max_ctrl = _pack_ctrl(ctrl, max_ctrl)
-            n_path = len(n_ctrl)
-            pof = np.ascontiguousarray(np.broadcast_to(np.asarray(0 if path_of is None else path_of, dtype=np.int32), (n,)))
-        o = dict(status=np.zeros(n, dtype=np.int32), gain=np.zeros((n, my)), n_cand=np.zeros((n, my), dtype=np.int32),
-                 n_visible=np.zeros((n, my), dtype=np.int32), n_rays=np.zeros(n, dtype=np.int32))
-        rc = self.L.fuelmi_map_info_gains(self.h, C.byref(c), n, _dp(pos), _ip(n_yaw), _dp(ya), n_path, _ip(n_ctrl),
-                                          _dp(carr), _ip(pof), _ip(o["status"]), _dp(o["gain"]), _ip(o["n_cand"]),
-                                          _ip(o["n_visible"]), _ip(o["n_rays"]))
-        if not (allow_limit and rc == -5):
-            check(rc)
-        o["limit"] = rc == -5
+            n_path, n_ctrl, carr, c.max_ctrl = _spline(ctrl, max_ctrl, floor=1)
+            pof = _per_problem(0 if path_of is None else path_of, n, np.int32)
+        o, out = _outputs(n, [("status", _I, ()), ("gain", _D, (my,)), ("n_cand n_visible", _I, (my,)), ("n_rays", _I, ())])
+        o["limit"] = _limited(self.L.fuelmi_map_info_gains(self.h, C.byref(c), n, _dp(pos), _ip(n_yaw), _dp(ya), n_path,
+                                                           _ip(n_ctrl), _dp(carr), _ip(pof), *out), allow_limit)
         return o
 
     def yaw_paths(self, pts, yaws, dt, ctrl=None, gains_in=None, allow_limit=False, max_layer=None, max_ctrl=None, **cfg):
@@ -999,38 +849,24 @@ class SDFMap:
         runs on those gains and no ray is walked.  cfg: the fields of yawpath_cfg().  Returns a dict of arrays: status
         (-1: a layer over the cell cap), n_layer, path / path_vertex [n, max_layer], gains / g_value
         [n, max_layer, 2h + 1], n_rays [n, max_layer]; limit."""
-        ps = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in pts]
-        ys = [np.atleast_1d(np.asarray(y, dtype=np.float64)) for y in yaws]
-        n = len(ps)
-        assert len(ys) == n and all(len(p) == len(y) for p, y in zip(ps, ys))
-        ml = int(max_layer) if max_layer is not None else max([len(y) for y in ys] + [1])
+        n_layer, ya, ml = _pack(yaws, max_layer, 0, floor=1)
+        n_pts, pa, _ = _pack(pts, ml, 3)
+        n = len(n_pts)
+        assert len(n_layer) == n and (n_pts == n_layer).all()
         c = yawpath_cfg(**dict(cfg, max_layer=ml))
         nv = 2 * c.half_vert_num + 1
-        n_layer = np.array([len(y) for y in ys], dtype=np.int32)
-        pa, ya = np.zeros((n, max(ml, 0), 3)), np.zeros((n, max(ml, 0)))
-        for b in range(n):
-            k = min(len(ys[b]), ya.shape[1])
-            pa[b, :k], ya[b, :k] = ps[b][:k], ys[b][:k]
-        dta = np.ascontiguousarray(np.broadcast_to(np.asarray(dt, dtype=np.float64), (n,)))
+        dta = _per_problem(dt, n)
         n_ctrl = carr = gin = None
         if ctrl is not None:
-            n_ctrl, carr, c.gain.max_ctrl = _pack_ctrl(ctrl, max_ctrl)
-            assert len(n_ctrl) == n
+            n_path, n_ctrl, carr, c.gain.max_ctrl = _spline(ctrl, max_ctrl, floor=1)
+            assert n_path == n
         if gains_in is not None:
-            gin = np.zeros((n, max(ml, 0), max(nv, 0)))
-            for b, gi in enumerate(gains_in):
-                gi = np.asarray(gi, dtype=np.float64).reshape(-1, nv)
-                k = min(len(gi), gin.shape[1])
-                gin[b, :k] = gi[:k]
-        o = dict(status=np.zeros(n, dtype=np.int32), n_layer=n_layer, path=np.zeros((n, ml)),
-                 path_vertex=np.zeros((n, ml), dtype=np.int32), gains=np.zeros((n, ml, max(nv, 0))),
-                 g_value=np.zeros((n, ml, max(nv, 0))), n_rays=np.zeros((n, ml), dtype=np.int32))
-        rc = self.L.fuelmi_map_yaw_paths(self.h, C.byref(c), n, _ip(n_layer), _dp(pa), _dp(ya), _dp(dta), _ip(n_ctrl),
-                                         _dp(carr), _dp(gin), _ip(o["status"]), _dp(o["path"]), _ip(o["path_vertex"]),
-                                         _dp(o["gains"]), _dp(o["g_value"]), _ip(o["n_rays"]))
-        if not (allow_limit and rc == -5):
-            check(rc)
-        o["limit"] = rc == -5
+            gin = _pack(gains_in, ml, nv, n=n)[1]
+        o, out = _outputs(n, [("status", _I, ()), ("path", _D, (ml,)), ("path_vertex", _I, (ml,)),
+                              ("gains g_value", _D, (ml, max(nv, 0))), ("n_rays", _I, (ml,))])
+        o["n_layer"] = n_layer
+        o["limit"] = _limited(self.L.fuelmi_map_yaw_paths(self.h, C.byref(c), n, _ip(n_layer), _dp(pa), _dp(ya), _dp(dta),
+                                                          _ip(n_ctrl), _dp(carr), _dp(gin), *out), allow_limit)
         return o
 
     # --- the yaw trajectory of a position spline (include/fuelmi.h fuelmi_map_plan_yaws) ---
@@ -1045,37 +881,18 @@ class SDFMap:
         end_yaw, cost, yawdot_ctrl, yawddot_ctrl (with derivs), limit.  FUELMI_ELIMIT raises unless allow_limit.
         knots (with knot_span None): a list of 1-D arrays of n_ctrl + pos_degree + 1 knots, e.g. the rows of adjust_trajs'
         knots_out (fuelmi_map_plan_yaws_knots)."""
-        pos = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in pos_ctrl]
-        n = len(pos)
-        maxc = int(max_ctrl) if max_ctrl is not None else max([len(p) for p in pos] + [4])
+        n, n_ctrl, arr, maxc = _spline(pos_ctrl, max_ctrl)
         c = yaw_cfg(max_ctrl=maxc, **cfg)
-        n_ctrl = np.array([len(p) for p in pos], dtype=np.int32)
-        arr = np.zeros((n, max(maxc, 0), 3))
-        for b, p in enumerate(pos):
-            k = min(len(p), arr.shape[1])
-            arr[b, :k] = p[:k]
-        knot, kin = _knots_or_span(n, max(maxc, 0) + c.pos_degree + 1, knot_span, knots)
-        sy = np.ascontiguousarray(start_yaw, dtype=np.float64).reshape(n, 3)
-        ey = None if end_yaw is None else np.ascontiguousarray(np.broadcast_to(np.asarray(end_yaw, dtype=np.float64), (n,)))
-        w = weights if isinstance(weights, BsplineCfg) else BsplineCfg(**dict(DEFAULT_BSPLINE, **(weights or {})))
-        o, args = _yaw_outputs(n, c.max_seg, derivs)
-        if kin is None:
-            rc = self.L.fuelmi_map_plan_yaws(self.h, C.byref(w), C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(knot), _dp(sy),
-                                             _dp(ey), *args)
-        else:
-            rc = self.L.fuelmi_map_plan_yaws_knots(self.h, C.byref(w), C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(kin),
-                                                   _dp(sy), _dp(ey), *args)
-        if not (allow_limit and rc == -5):
-            check(rc)
-        o["limit"] = rc == -5
-        return o
+        knot, suffix = _knot_source(n, max(maxc, 0) + c.pos_degree + 1, knot_span, knots)
+        w = _weights(weights, DEFAULT_BSPLINE)
+        fn = getattr(self.L, "fuelmi_map_plan_yaws" + suffix)
+        return _plan_yaws(n, c, start_yaw, end_yaw, derivs, allow_limit,
+                          lambda yc, *a: fn(self.h, C.byref(w), yc, n, _ip(n_ctrl), _dp(arr), _dp(knot), *a))
 
     @staticmethod
     def yaw_plan(cfg):
         """(lanes per problem, LDS bytes, largest max_ctrl accepted) of the yaw kernel for a YawCfg; host only"""
-        out = (C.c_int * 3)()
-        check(lib().fuelmi_yaw_plan(C.byref(cfg), out))
-        return tuple(out)
+        return _plan_query(lib().fuelmi_yaw_plan, 3, cfg)
 
     # --- the exact solve of the optimiser's quadratic phases (include/fuelmi.h fuelmi_map_solve_quadratic) ---
     QUAD_OK, QUAD_BOUNDED, QUAD_DEGENERATE = _lib.QUAD_OK, _lib.QUAD_BOUNDED, _lib.QUAD_DEGENERATE
@@ -1089,41 +906,23 @@ class SDFMap:
         [k] arrays.  weights: a BsplineCfg or a dict of its fields (default: the launch file's).  Returns a dict: status [n],
         ctrl (a list of [n_ctrl, dim] arrays), ctrl_out [n, max_ctrl, dim], cost [n], pt_dist [n]."""
         dim = int(dim)
-        cs = [np.ascontiguousarray(c, dtype=np.float64).reshape(-1, dim) for c in ctrl]
-        n = len(cs)
-        maxc = int(max_ctrl) if max_ctrl is not None else max([len(c) for c in cs] + [4])
-        w = weights if isinstance(weights, BsplineCfg) else BsplineCfg(**dict(DEFAULT_BSPLINE, **(weights or {})))
+        n, n_ctrl, carr, maxc = _spline(ctrl, max_ctrl, cols=dim)
+        w = _weights(weights, DEFAULT_BSPLINE)
         order = 3 if dim == 1 else int(w.bspline_degree)
-        maxg = max(maxc - 2 * order, 0)
-
-        def pack(rows, width, dtype=np.float64, cols=dim):
-            """a list of per-problem [k, cols] arrays as ([n, width, cols], the counts)"""
-            shape = (n, max(width, 0), cols) if cols else (n, max(width, 0))
-            arr = np.zeros(shape, dtype=dtype)
-            cnt = np.zeros(n, dtype=np.int32)
-            for b, r in enumerate(rows or []):
-                r = np.ascontiguousarray(r, dtype=dtype).reshape((-1, cols) if cols else (-1,))
-                cnt[b] = len(r)
-                k = min(len(r), arr.shape[1])  # (a problem longer than the stride: the call refuses it by its count)
-                arr[b, :k] = r[:k]
-            return arr, cnt
-        carr, n_ctrl = pack(cs, maxc)
-        knot = np.ascontiguousarray(np.broadcast_to(np.asarray(knot_span, dtype=np.float64), (n,)))
+        knot = _per_problem(knot_span, n)
         st = None if start_state is None else np.ascontiguousarray(start_state, dtype=np.float64).reshape(n, 3, dim)
         en = None if end_state is None else np.ascontiguousarray(end_state, dtype=np.float64).reshape(n, 3, dim)
-        garr = None if guide_pts is None else pack(guide_pts, maxg)[0]
+        garr = None if guide_pts is None else _pack(guide_pts, max(maxc - 2 * order, 0), dim, n=n)[1]
         maxw = int(max_waypt) if max_waypt is not None else max([len(np.atleast_1d(i)) for i in (waypt_idx or [])] + [0])
         warr = n_w = iarr = None
         if waypoints is not None:
-            warr, n_w = pack(waypoints, maxw)
-            iarr = pack(waypt_idx, maxw, np.int32, 0)[0]
+            n_w, warr, _ = _pack(waypoints, maxw, dim, n=n)
+            iarr = _pack(waypt_idx, maxw, 0, np.int32, n=n)[1]
         c = QuadCfg(int(cost_function), dim, maxc, int(end_n), maxw, 1 if bounds else 0)
-        o = dict(status=np.zeros(n, dtype=np.int32), ctrl_out=np.zeros((n, max(maxc, 0), dim)), cost=np.zeros(n),
-                 pt_dist=np.zeros(n))
-        check(self.L.fuelmi_map_solve_quadratic(self.h, C.byref(w), C.byref(c), n, _ip(n_ctrl), _dp(carr), _dp(knot), _dp(st),
-                                                _dp(en), _dp(garr), _ip(n_w), _dp(warr), _ip(iarr), _ip(o["status"]),
-                                                _dp(o["ctrl_out"]), _dp(o["cost"]), _dp(o["pt_dist"])))
-        o["ctrl"] = [o["ctrl_out"][b, :len(cs[b])] for b in range(n)]
+        o = _solve_quadratic(n, c, lambda qc, *out: self.L.fuelmi_map_solve_quadratic(
+            self.h, C.byref(w), qc, n, _ip(n_ctrl), _dp(carr), _dp(knot), _dp(st), _dp(en), _dp(garr), _ip(n_w), _dp(warr),
+            _ip(iarr), *out))
+        o["ctrl"] = [o["ctrl_out"][b, :n_ctrl[b]] for b in range(n)]
         return o
 
     # --- the safety check of flown trajectories (include/fuelmi.h fuelmi_map_check_trajs) ---
@@ -1134,34 +933,18 @@ class SDFMap:
         end_reason, duration, limit.  FUELMI_ELIMIT raises unless allow_limit.
         knots (with knot_span None): a list of 1-D arrays of n_ctrl + degree + 1 knots, e.g. the rows of adjust_trajs'
         knots_out (fuelmi_map_check_trajs_knots)."""
-        pos = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in pos_ctrl]
-        n = len(pos)
-        maxc = int(max_ctrl) if max_ctrl is not None else max([len(p) for p in pos] + [4])
+        n, n_ctrl, arr, maxc = _spline(pos_ctrl, max_ctrl)
         c = traj_check_cfg(max_ctrl=maxc, **cfg)
-        n_ctrl = np.array([len(p) for p in pos], dtype=np.int32)
-        arr = np.zeros((n, max(maxc, 0), 3))
-        for b, p in enumerate(pos):
-            k = min(len(p), arr.shape[1])
-            arr[b, :k] = p[:k]
-        knot, kin = _knots_or_span(n, max(maxc, 0) + c.degree + 1, knot_span, knots)
-        now = np.ascontiguousarray(np.broadcast_to(np.asarray(t_now, dtype=np.float64), (n,)))
-        o, args = _trajchk_outputs(n)
-        if kin is None:
-            rc = self.L.fuelmi_map_check_trajs(self.h, C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(knot), _dp(now), *args)
-        else:
-            rc = self.L.fuelmi_map_check_trajs_knots(self.h, C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(kin), _dp(now), *args)
-        if not (allow_limit and rc == -5):
-            check(rc)
-        o["limit"] = rc == -5
-        return o
+        knot, suffix = _knot_source(n, max(maxc, 0) + c.degree + 1, knot_span, knots)
+        fn = getattr(self.L, "fuelmi_map_check_trajs" + suffix)
+        return _check_trajs(n, t_now, allow_limit,
+                            lambda *a: fn(self.h, C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(knot), *a))
 
     @staticmethod
     def traj_check_plan(cfg):
         """(lanes per problem, LDS bytes of a workgroup, largest max_ctrl accepted) of the check kernel for a TrajChkCfg;
         host only"""
-        out = (C.c_int * 3)()
-        check(lib().fuelmi_traj_check_plan(C.byref(cfg), out))
-        return tuple(out)
+        return _plan_query(lib().fuelmi_traj_check_plan, 3, cfg)
 
     # --- sampling of flown trajectories (include/fuelmi.h fuelmi_map_sample_trajs) ---
     def sampleTrajs(self, pos_ctrl, knot_span, t, yaw_ctrl=None, yaw_dt=None, t_stop=None, flight=None, max_ctrl=None,
@@ -1174,21 +957,12 @@ class SDFMap:
         [n, max_t], duration [n], flight, n_t.
         knots (with knot_span None): a list of 1-D arrays of n_ctrl + degree + 1 position knots, e.g. the rows of
         adjust_trajs' knots_out (fuelmi_map_sample_trajs_knots); the yaw splines stay uniform."""
-        pos = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in pos_ctrl]
-        n = len(pos)
-        maxc = int(max_ctrl) if max_ctrl is not None else max([len(p) for p in pos] + [4])
-        args, o, maxy, maxt, keep = _trajsmp_io(n, t, yaw_ctrl, yaw_dt, t_stop, flight, max_yaw_ctrl, max_t)
+        n, n_ctrl, arr, maxc = _spline(pos_ctrl, max_ctrl)
+        args, o, maxy, maxt = _trajsmp_io(n, t, yaw_ctrl, yaw_dt, t_stop, flight, max_yaw_ctrl, max_t)
         c = traj_sample_cfg(max_ctrl=maxc, max_yaw_ctrl=maxy, max_t=maxt, **cfg)
-        n_ctrl = np.array([len(p) for p in pos], dtype=np.int32)
-        arr = np.zeros((n, max(maxc, 0), 3))
-        for b, p in enumerate(pos):
-            k = min(len(p), arr.shape[1])
-            arr[b, :k] = p[:k]
-        knot, kin = _knots_or_span(n, max(maxc, 0) + c.degree + 1, knot_span, knots)
-        if kin is None:
-            check(self.L.fuelmi_map_sample_trajs(self.h, C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(knot), *args))
-        else:
-            check(self.L.fuelmi_map_sample_trajs_knots(self.h, C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(kin), *args))
+        knot, suffix = _knot_source(n, max(maxc, 0) + c.degree + 1, knot_span, knots)
+        check(getattr(self.L, "fuelmi_map_sample_trajs" + suffix)(self.h, C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(knot),
+                                                                  *args))
         return o
 
     sample_trajs = sampleTrajs
@@ -1197,9 +971,7 @@ class SDFMap:
     def traj_sample_plan(cfg):
         """(lanes per problem, LDS bytes of a workgroup, largest max_ctrl accepted) of the sampling kernel for a
         TrajSmpCfg; host only"""
-        out = (C.c_int * 3)()
-        check(lib().fuelmi_traj_sample_plan(C.byref(cfg), out))
-        return tuple(out)
+        return _plan_query(lib().fuelmi_traj_sample_plan, 3, cfg)
 
     # --- time adjustment and metrics of trajectories (include/fuelmi.h fuelmi_map_adjust_trajs) ---
     def adjust_trajs(self, pos_ctrl, knot_span=None, knots_in=None, ratio_in=None, group=None, ops=0, max_ctrl=None,
@@ -1211,18 +983,11 @@ class SDFMap:
         other fields of traj_adjust_cfg.  Returns a dict of arrays: info [n, 8] and metrics [n, 12] and each of their
         columns under its name (status, iters, jerk, ...), knots_out [n, max_ctrl + degree + 1], samples
         [n, max_samples, 3] or None, best [n_group] or None, n_ctrl."""
-        pos = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in pos_ctrl]
-        n = len(pos)
         degree = int(cfg.get("degree", 3))
-        maxc = int(max_ctrl) if max_ctrl is not None else max([len(p) for p in pos] + [degree + 1])
-        n_ctrl = np.array([len(p) for p in pos], dtype=np.int32)
-        args, o, maxs, ng, keep = _trajadj_io(n, n_ctrl, degree, maxc, knots_in, ratio_in, group, int(ops), max_samples, n_group)
+        n, n_ctrl, arr, maxc = _spline(pos_ctrl, max_ctrl, floor=degree + 1)
+        args, o, maxs, ng = _trajadj_io(n, n_ctrl, degree, maxc, knots_in, ratio_in, group, int(ops), max_samples, n_group)
         c = traj_adjust_cfg(ops=ops, max_ctrl=maxc, max_samples=maxs, n_group=ng, **cfg)
-        arr = np.zeros((n, max(maxc, 0), 3))
-        for b, p in enumerate(pos):
-            k = min(len(p), arr.shape[1])
-            arr[b, :k] = p[:k]
-        knot = None if knot_span is None else np.ascontiguousarray(np.broadcast_to(np.asarray(knot_span, dtype=np.float64), (n,)))
+        knot = _per_problem(knot_span, n, optional=True)
         check(self.L.fuelmi_map_adjust_trajs(self.h, C.byref(c), n, _ip(n_ctrl), _dp(arr), _dp(knot), *args))
         return _trajadj_named(o)
 
@@ -1230,9 +995,7 @@ class SDFMap:
     def traj_adjust_plan(cfg):
         """(lanes per problem, LDS bytes of a workgroup, largest max_ctrl accepted) of the adjustment kernel for a
         TrajAdjCfg; host only"""
-        out = (C.c_int * 3)()
-        check(lib().fuelmi_traj_adjust_plan(C.byref(cfg), out))
-        return tuple(out)
+        return _plan_query(lib().fuelmi_traj_adjust_plan, 3, cfg)
 
     # --- measurement ---
     def timerBegin(self):
@@ -1537,9 +1300,7 @@ class FrontierFinder:
 
     def stats(self):
         """(searches on the fast chain, on the legacy chain, fast-chain searches that fell back)"""
-        o = (C.c_int * 3)()
-        check(self.L.fuelmi_frontier_stats(self.h, o))
-        return tuple(o)
+        return _plan_query(self.L.fuelmi_frontier_stats, 3, self.h)
 
     def resolvedInLaunch(self):
         """fast-chain searches resolved by the last workgroup of k_tile_cross itself (the others: by k_resolve)"""
@@ -1548,25 +1309,20 @@ class FrontierFinder:
     def pathStats(self):
         """(fast-chain searches that outgrew the in-launch resolve with no k_resolve queued behind it -- the late
         resolve --, fast-chain searches run again on a smaller tile)"""
-        o = (C.c_int * 2)()
-        check(self.L.fuelmi_frontier_path_stats(self.h, o))
-        return tuple(o)
+        return _plan_query(self.L.fuelmi_frontier_path_stats, 2, self.h)
 
     def changedStats(self):
         """the changed-cluster test in front of the searches: {"paths": launches of (one workgroup, in-kernel barrier,
         two passes on an LDS table, two passes on a device table), "nc", "total", "mark": candidates, pooled cells and
         mark of the last test (mark 0 on the one-workgroup path), "rebuilds": device pool rebuilds so far, "pool_cap":
         the pool's capacity in cells}"""
-        o = (C.c_int * 9)()
-        check(self.L.fuelmi_frontier_changed_stats(self.h, o))
+        o = _plan_query(self.L.fuelmi_frontier_changed_stats, 9, self.h)
         return {"paths": tuple(o[:4]), "nc": o[4], "total": o[5], "mark": o[6], "rebuilds": o[7], "pool_cap": o[8]}
 
     def orderStats(self):
         """(order of the last search: 0 address / 1 reference BFS, searches in the reference's order, mode-2 searches
         that fell back to the address order, cells of the cluster that forced the last fallback)"""
-        o = (C.c_int * 4)()
-        check(self.L.fuelmi_frontier_order_stats(self.h, o))
-        return tuple(o)
+        return _plan_query(self.L.fuelmi_frontier_order_stats, 4, self.h)
 
     def clusters(self, which=0):
         out = []
@@ -1697,9 +1453,9 @@ class BsplineBatchProblem:
         self.x = f64(x)
         self.C = self.x.shape[0]
         self.nvar = self.x.shape[1]
-        self.pt_dist = f64(np.broadcast_to(pt_dist, (self.C,)))
-        self.knot_span = f64(np.broadcast_to(knot_span if knot_span is not None else 0.0, (self.C,)))
-        self.time_lb = None if time_lb is None else f64(np.broadcast_to(time_lb, (self.C,)))
+        self.pt_dist = _per_problem(pt_dist, self.C)
+        self.knot_span = _per_problem(knot_span if knot_span is not None else 0.0, self.C)
+        self.time_lb = _per_problem(time_lb, self.C, optional=True)
         self.start_state = f64(start_state)
         self.end_state = f64(end_state)
         self.guide_pts = f64(guide_pts)
@@ -1734,9 +1490,7 @@ class BsplineOptimizer:
     """Cost/gradient side of fast_planner::BsplineOptimizer, batched over candidates."""
 
     def __init__(self, **params):
-        p = dict(DEFAULT_BSPLINE)
-        p.update(params)
-        self.cfg = BsplineCfg(**p)
+        self.cfg = _weights(params, DEFAULT_BSPLINE)
         self.L = lib()
         self.env = None
 
@@ -1772,9 +1526,7 @@ class BsplineOptimizer:
         """Which solve kernel optimize() and deviceProblem().optimize() run for `problem` (fuelmi_bspline_opt_plan, host
         only): (npl, waves per candidate, dynamic LDS bytes); npl 0 is the LDS-state kernel.  Raises FuelmiError for a
         batch neither call would take."""
-        out = (C.c_int * 3)()
-        check(lib().fuelmi_bspline_opt_plan(C.byref(problem.c), out))
-        return tuple(out)
+        return _plan_query(lib().fuelmi_bspline_opt_plan, 3, problem.c)
 
 
 class NonUniformBspline:
@@ -1871,13 +1623,10 @@ class BsplineDeviceProblem:
         if len(ways) != c.n_traj:
             raise ValueError("load_waypoints: one list of way-points per candidate")
         n_way, way, vel, acc, wc = _pack_waypoints(ways, vels, accs, max_vel, ctrl_pt_dist, min_seg, 0, max_way_points, 1)
-        status = np.zeros(c.n_traj, dtype=np.int32)
-        duration = np.zeros(c.n_traj)
-        rc = self.L.fuelmi_bspline_dev_load_waypoints(self.h, C.byref(wc), _ip(n_way), _dp(way), _dp(vel), _dp(acc),
-                                                      _ip(status), _dp(duration))
-        if not (allow_limit and rc == -5):
-            check(rc)
-        return status, duration
+        o, out = _outputs(c.n_traj, [("status", _I, ()), ("duration", _D, ())])
+        _limited(self.L.fuelmi_bspline_dev_load_waypoints(self.h, C.byref(wc), _ip(n_way), _dp(way), _dp(vel), _dp(acc), *out),
+                 allow_limit)
+        return o["status"], o["duration"]
 
     def load_local_segments(self, states, problems, max_seg=None, max_ctrl=None):
         """the global trajectory's local segment -> loadSamples' fit, without leaving the device
@@ -1888,43 +1637,27 @@ class BsplineDeviceProblem:
         if len(problems) != c.n_traj:
             raise ValueError("load_local_segments: one problem per candidate")
         lc, nt, st_arr, n, pr_arr = _pack_localseg(states, problems, self.degree, max_seg, max_ctrl)
-        status = np.zeros(c.n_traj, dtype=np.int32)
-        duration = np.zeros(c.n_traj)
+        o, out = _outputs(c.n_traj, [("status", _I, ()), ("duration", _D, ())])
         check(self.L.fuelmi_bspline_dev_load_local_segments(self.h, lc.max_seg, lc.max_ctrl, nt, *[_ptr(a) for a in st_arr],
-                                                            *[_ptr(a) for a in pr_arr], _ip(status), _dp(duration)))
-        return status, duration
+                                                            *[_ptr(a) for a in pr_arr], *out))
+        return o["status"], o["duration"]
 
     def load_kino(self, starts, vels, accs, goals, goal_vels, allow_limit=False, **cfg):
         """start / goal -> kinodynamic search -> getSamples -> loadSamples' fit, without leaving the device
         (fuelmi_bspline_dev_load_kino): one problem per candidate, seg_num forced to point_num - bspline_degree.  Returns
         (status [C], T_sum [C]); a candidate without a path keeps its state."""
-        c = self.problem.c
-        arr = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3) for a in (starts, vels, accs, goals, goal_vels)]
-        if any(len(a) != c.n_traj for a in arr):
-            raise ValueError("load_kino: one problem per candidate")
-        kc = kino_cfg(**cfg)
-        status = np.zeros(c.n_traj, dtype=np.int32)
-        t_sum = np.zeros(c.n_traj)
-        rc = self.L.fuelmi_bspline_dev_load_kino(self.h, C.byref(kc), *[_dp(a) for a in arr], _ip(status), _dp(t_sum))
-        if not (allow_limit and rc == -5):
-            check(rc)
-        return status, t_sum
+        _, o, _ = _kino((starts, vels, accs, goals, goal_vels), cfg, self.problem.c.n_traj,
+                        lambda kc: [("status", _I, ()), ("T_sum", _D, ())], allow_limit,
+                        lambda kc, n, *a: self.L.fuelmi_bspline_dev_load_kino(self.h, kc, *a))
+        return o["status"], o["T_sum"]
 
     def plan_yaws(self, start_yaw, end_yaw=None, derivs=True, allow_limit=False, **cfg):
         """The yaw trajectories of the candidates' optimised position splines, read from what the last optimize() left
         on the device (fuelmi_bspline_dev_plan_yaws); the batch's own weights.  Same result dict as SDFMap.plan_yaws."""
         c = self.problem.c
-        n = c.n_traj
         cfg.setdefault("pos_degree", 3)
-        yc = yaw_cfg(max_ctrl=c.point_num, **cfg)
-        sy = np.ascontiguousarray(start_yaw, dtype=np.float64).reshape(n, 3)
-        ey = None if end_yaw is None else np.ascontiguousarray(np.broadcast_to(np.asarray(end_yaw, dtype=np.float64), (n,)))
-        o, args = _yaw_outputs(n, yc.max_seg, derivs)
-        rc = self.L.fuelmi_bspline_dev_plan_yaws(self.h, C.byref(yc), _dp(sy), _dp(ey), *args)
-        if not (allow_limit and rc == -5):
-            check(rc)
-        o["limit"] = rc == -5
-        return o
+        return _plan_yaws(c.n_traj, yaw_cfg(max_ctrl=c.point_num, **cfg), start_yaw, end_yaw, derivs, allow_limit,
+                          lambda *a: self.L.fuelmi_bspline_dev_plan_yaws(self.h, *a))
 
     def solve_quadratic(self, cost_function=GUIDE_PHASE, guide_pts=None, bounds=False):
         """The exact minimiser of a quadratic mask on what the batch holds (fuelmi_bspline_dev_solve_quadratic); the
@@ -1938,26 +1671,16 @@ class BsplineDeviceProblem:
         if g is not None and g.size != n * max(c.point_num - 2 * order, 0) * 3:
             raise ValueError("solve_quadratic: guide_pts [C][point_num - 2 order][3]")
         qc = QuadCfg(int(cost_function), c.dim, c.point_num, max(c.end_n, 1), c.n_waypt, 1 if bounds else 0)
-        o = dict(status=np.zeros(n, dtype=np.int32), ctrl_out=np.zeros((n, c.point_num, c.dim)), cost=np.zeros(n),
-                 pt_dist=np.zeros(n))
-        check(self.L.fuelmi_bspline_dev_solve_quadratic(self.h, C.byref(qc), _dp(g), _ip(o["status"]), _dp(o["ctrl_out"]),
-                                                        _dp(o["cost"]), _dp(o["pt_dist"])))
-        return o
+        return _solve_quadratic(n, qc, lambda q, *out: self.L.fuelmi_bspline_dev_solve_quadratic(self.h, q, _dp(g), *out))
 
     def check_trajs(self, t_now, allow_limit=False, **cfg):
         """The safety check of the candidates' optimised position splines against the batch's map, read from what the last
         optimize() left on the device (fuelmi_bspline_dev_check_trajs).  Same result dict as SDFMap.check_trajs."""
         c = self.problem.c
-        n = c.n_traj
         cfg.setdefault("degree", 3)
         tc = traj_check_cfg(max_ctrl=c.point_num, **cfg)
-        now = np.ascontiguousarray(np.broadcast_to(np.asarray(t_now, dtype=np.float64), (n,)))
-        o, args = _trajchk_outputs(n)
-        rc = self.L.fuelmi_bspline_dev_check_trajs(self.h, C.byref(tc), _dp(now), *args)
-        if not (allow_limit and rc == -5):
-            check(rc)
-        o["limit"] = rc == -5
-        return o
+        return _check_trajs(c.n_traj, t_now, allow_limit,
+                            lambda *a: self.L.fuelmi_bspline_dev_check_trajs(self.h, C.byref(tc), *a))
 
     def sample_trajs(self, t, yaw_ctrl=None, yaw_dt=None, t_stop=None, flight=None, max_yaw_ctrl=None, max_t=None, **cfg):
         """The candidates' optimised position splines sampled as commands or replan states, read from what the last
@@ -1966,7 +1689,7 @@ class BsplineDeviceProblem:
         c = self.problem.c
         n = c.n_traj
         cfg.setdefault("degree", 3)
-        args, o, maxy, maxt, keep = _trajsmp_io(n, t, yaw_ctrl, yaw_dt, t_stop, flight, max_yaw_ctrl, max_t)
+        args, o, maxy, maxt = _trajsmp_io(n, t, yaw_ctrl, yaw_dt, t_stop, flight, max_yaw_ctrl, max_t)
         sc = traj_sample_cfg(max_ctrl=c.point_num, max_yaw_ctrl=maxy, max_t=maxt, **cfg)
         check(self.L.fuelmi_bspline_dev_sample_trajs(self.h, C.byref(sc), *args))
         return o
@@ -1979,8 +1702,8 @@ class BsplineDeviceProblem:
         n = c.n_traj
         degree = int(cfg.setdefault("degree", 3))
         n_ctrl = np.full(n, c.point_num, dtype=np.int32)
-        args, o, maxs, ng, keep = _trajadj_io(n, n_ctrl, degree, c.point_num, knots_in, ratio_in, group, int(ops), max_samples,
-                                              n_group)
+        args, o, maxs, ng = _trajadj_io(n, n_ctrl, degree, c.point_num, knots_in, ratio_in, group, int(ops), max_samples,
+                                        n_group)
         ac = traj_adjust_cfg(ops=ops, max_ctrl=c.point_num, max_samples=maxs, n_group=ng, **cfg)
         check(self.L.fuelmi_bspline_dev_adjust_trajs(self.h, C.byref(ac), *args))
         return _trajadj_named(o)

@@ -43,20 +43,135 @@ def test_python_binding_covers_header(built):
     assert L.fuelmi_version().startswith(b"fuelmi")
 
 
+# every ctypes.Structure of fuel_amd._lib and the typedef of include/fuelmi.h it mirrors
+STRUCTS = {
+    "MapCfg": "fuelmi_map_cfg", "DepthCfg": "fuelmi_depth_cfg", "MapInfo": "fuelmi_map_info",
+    "FrontierCfg": "fuelmi_frontier_cfg", "ViewpointCfg": "fuelmi_viewpoint_cfg", "PathCfg": "fuelmi_path_cfg",
+    "RefineCfg": "fuelmi_refine_cfg", "GoalCfg": "fuelmi_goal_cfg", "WptrajCfg": "fuelmi_wptraj_cfg",
+    "KinoCfg": "fuelmi_kino_cfg", "TopoCfg": "fuelmi_topo_cfg", "ColRangeCfg": "fuelmi_colrange_cfg",
+    "GainCfg": "fuelmi_gain_cfg", "YawPathCfg": "fuelmi_yawpath_cfg", "LocalSegCfg": "fuelmi_localseg_cfg",
+    "YawCfg": "fuelmi_yaw_cfg", "QuadCfg": "fuelmi_quad_cfg", "TrajChkCfg": "fuelmi_trajchk_cfg",
+    "TrajSmpCfg": "fuelmi_trajsmp_cfg", "TrajAdjCfg": "fuelmi_trajadj_cfg", "CloudCfg": "fuelmi_cloud_cfg",
+    "TspCfg": "fuelmi_tsp_cfg", "RenderCfg": "fuelmi_render_cfg", "BsplineCfg": "fuelmi_bspline_cfg",
+    "BsplineBatch": "fuelmi_bspline_batch",
+}
+
+
 def test_ctypes_struct_layouts_match_c(built, tmp_path):
+    """sizeof and the offsetof of every field, for every Structure of _lib, against a gcc-compiled probe of the header"""
     from fuel_amd import _lib
+    classes = {n: c for n, c in vars(_lib).items() if isinstance(c, type) and issubclass(c, C.Structure) and c is not C.Structure}
+    assert sorted(classes) == sorted(STRUCTS) and len(classes) == 25
+    want, lines = [], []
+    for py, ctype in sorted(STRUCTS.items()):
+        want.append(("sizeof", ctype, "", C.sizeof(classes[py])))
+        lines.append('printf("%%zu\\n", sizeof(%s));' % ctype)
+        for field, _ in classes[py]._fields_:
+            want.append(("offsetof", ctype, field, getattr(classes[py], field).offset))
+            lines.append('printf("%%zu\\n", offsetof(%s, %s));' % (ctype, field))
+    assert len(want) > 225
     prog = tmp_path / "sz.c"
-    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "fuelmi.h"\n'
-                    'int main(){printf("%zu %zu %zu %zu %zu %zu %zu\\n", sizeof(fuelmi_map_cfg), '
-                    'sizeof(fuelmi_map_info), sizeof(fuelmi_frontier_cfg), sizeof(fuelmi_bspline_cfg), '
-                    'sizeof(fuelmi_bspline_batch), offsetof(fuelmi_map_cfg, device), '
-                    'offsetof(fuelmi_bspline_batch, view_idx));return 0;}\n')
+    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "fuelmi.h"\nint main(){\n%s\nreturn 0;}\n' % "\n".join(lines))
     exe = tmp_path / "sz"
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
     got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    want = [C.sizeof(_lib.MapCfg), C.sizeof(_lib.MapInfo), C.sizeof(_lib.FrontierCfg), C.sizeof(_lib.BsplineCfg),
-            C.sizeof(_lib.BsplineBatch), _lib.MapCfg.device.offset, _lib.BsplineBatch.view_idx.offset]
-    assert got == want
+    assert len(got) == len(want)
+    wrong = [(w[:3], w[3], g) for w, g in zip(want, got) if w[3] != g]
+    assert not wrong, "(what, C type, field), ctypes, C: %s" % wrong
+
+
+HANDLES = ("fuelmi_map", "fuelmi_frontier", "fuelmi_tsp", "fuelmi_render", "fuelmi_bspline_dev")
+C_SCALARS = {"int": "int", "unsigned": "int", "double": "double", "size_t": "size"}
+C_POINTEES = {"int": "int", "int32_t": "int", "double": "double", "int64_t": "int64", "long long": "int64"}
+
+
+def c_kind(decl, is_return=False):
+    """a parameter (or return type) of a prototype as a kind: int / double / size scalars, int* / double* / int64* by
+    pointer depth, `struct <typedef>*`, and void* for handles and every other pointer"""
+    d = re.sub(r"\bconst\b", " ", decl)
+    depth = d.count("*") + d.count("[")
+    d = re.sub(r"\[[^\]]*\]", " ", d).replace("*", " ")
+    words = d.split()
+    if not is_return and len(words) > 1 and not (len(words) == 2 and words == ["long", "long"]):
+        words = words[:-1]                       # the parameter's name
+    base = " ".join(words)
+    if depth == 0:
+        return C_SCALARS.get(base, base)
+    if base in STRUCTS.values() and depth == 1:
+        return "struct %s*" % base
+    if base in C_POINTEES:
+        return C_POINTEES[base] + "*" * depth
+    return "void" + "*" * depth                  # handles, images, clouds, flags, strings
+
+
+def py_kind(t):
+    from fuel_amd import _lib
+    if t is None:
+        return "void"
+    if t in (C.c_int, C.c_uint):
+        return "int"
+    if t is C.c_double:
+        return "double"
+    if t is C.c_size_t:
+        return "size"
+    if t is C.c_longlong:
+        return "long long"
+    if t in (C.c_void_p, C.c_char_p):
+        return "void*"
+    if hasattr(t, "_type_") and not isinstance(t._type_, str):
+        inner = t._type_
+        if issubclass(inner, C.Structure):
+            return "struct %s*" % STRUCTS[inner.__name__]
+        if inner is C.c_void_p:
+            return "void**"
+        if inner is C.c_float:
+            return "void*"
+        if inner in (C.c_int, C.c_int32):
+            return "int*"
+        if inner is C.c_double:
+            return "double*"
+        if inner in (C.c_int64, C.c_longlong):
+            return "int64*"
+    raise AssertionError("no kind for %r" % (t,))
+
+
+def prototypes():
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    src = re.sub(r"//[^\n]*|^\s*#[^\n]*", "", src, flags=re.M)
+    out = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(fuelmi_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        args = [a for a in (" ".join(a.split()) for a in args.split(",")) if a and a != "void"]
+        out[name] = (c_kind(ret, True), [c_kind(a) for a in args])
+    return out
+
+
+def test_binding_signatures_match_the_header():
+    """each SYMBOLS[name] against the prototype of `name`: the argument count and the kind of every argument and of the
+    result -- a ctypes argtypes list that drifts from the header passes garbage without any error"""
+    from fuel_amd import _lib
+    protos = prototypes()
+    assert sorted(protos) == declared_functions() == sorted(_lib.SYMBOLS)
+    wrong = []
+    for name, (res, argtypes) in _lib.SYMBOLS.items():
+        cret, cargs = protos[name]
+        if len(cargs) != len(argtypes):
+            wrong.append((name, "arguments", len(argtypes), len(cargs)))
+            continue
+        if py_kind(res) != cret:
+            wrong.append((name, "result", py_kind(res), cret))
+        wrong += [(name, k, py_kind(t), c) for k, (t, c) in enumerate(zip(argtypes, cargs)) if py_kind(t) != c]
+    assert not wrong, "(symbol, argument, ctypes, header): %s" % wrong
+    assert len(protos) >= 153
+
+
+def test_signature_kinds():
+    assert [c_kind(d) for d in ("int n", "const double* pos", "const int lo[3]", "fuelmi_map* m", "fuelmi_map** out",
+                                "const fuelmi_quad_cfg* cfg", "const void* const* frames", "size_t bytes", "float* ms",
+                                "long long out[12]", "const int32_t* costs", "unsigned mask", "double scaling")] == \
+        ["int", "double*", "int*", "void*", "void**", "struct fuelmi_quad_cfg*", "void**", "size", "void*", "int64*", "int*",
+         "int", "double"]
+    assert py_kind(C.POINTER(C.c_int)) == "int*" and py_kind(C.POINTER(C.c_double)) == "double*"
+    assert py_kind(C.c_void_p) == "void*" and py_kind(C.POINTER(C.c_void_p)) == "void**"
 
 
 def test_header_is_plain_c(tmp_path):
